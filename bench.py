@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: caption-tokens/sec, training (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense|attention]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense|attention] [--dump-outputs DIR]
 
 One "step" = one full train_step (forward + backward + clip + Adam) of the hot path on one
 synthetic batch already resident in HBM.  Workload at N=1 is BASELINE config 2
@@ -312,9 +312,9 @@ SETTLE_STEPS = 30      # untimed steps in front of the W warm-up steps: the firs
                        # raise the clocks; with W = 5 alone the K timed steps measured 0.513 ms/step, with these 0.493 (W = 50: 0.493)
 
 
-def timed_steps(model, batch, steps, warmup, world=1, dist=None, device=None):
+def timed_steps(model, batch, steps, warmup, world=1, dist=None, device=None, last=None):
     """SETTLE_STEPS untimed set-up steps, W warm-up steps, then exactly K steps between barrier + synchronize on both sides;
-    max over ranks."""
+    max over ranks.  ``last``: a list that receives the Metrics the last timed step returned."""
     import torch
     for _ in range(max(0, SETTLE_STEPS - warmup)):
         model.train_step(batch)
@@ -339,7 +339,7 @@ def timed_steps(model, batch, steps, warmup, world=1, dist=None, device=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        model.train_step(batch)
+        metrics = model.train_step(batch)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -349,7 +349,37 @@ def timed_steps(model, batch, steps, warmup, world=1, dist=None, device=None):
         t = torch.tensor([el], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if last is not None:
+        last.append(metrics)
     return el, note
+
+
+DUMP_MAX_ELEMS = 1 << 20        # --dump-outputs: a larger weight is written as a fixed seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model, metrics, prefix=""):
+    """What a caller of the timed path holds after its last step: the Metrics train_step returned (float64 scalars) and the
+    weights the step left (float32, keras layouts, named as in save_weights' .npz).  Read after the timed region."""
+    import numpy as np
+    out = {prefix + k: np.float64(v) for k, v in metrics.as_floats().items()}
+    for name in model.keras_shapes:
+        w = np.ascontiguousarray(model.get_weight(name), dtype=np.float32)
+        if w.size > DUMP_MAX_ELEMS:
+            w = w.reshape(-1)[np.sort(np.random.default_rng(0).choice(w.size, DUMP_MAX_ELEMS, replace=False))]
+        out[prefix + name.replace("/", "__")] = w
+    return out
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy for every array; refuses to write more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dp_world1_rehearsal(args, device):
@@ -401,7 +431,11 @@ def main():
     ap.add_argument("--host-inputs", action="store_true", help="feed numpy batches (PCIe-inclusive rate; never the headline value)")
     ap.add_argument("--force-dp", action="store_true", help="run the data-parallel schedule even at world size 1 (rehearsal)")
     ap.add_argument("--no-dp-world1", action="store_true", help="skip the world-size-1 rehearsal of the data-parallel schedule")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (metrics and weights of each "
+                    "timed workload) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
@@ -441,7 +475,9 @@ def main():
         x, cap, z, tgt = host_batch
         batch = ((x, cap, z, z), tgt)
 
-    el, seq_note = timed_steps(model, batch, args.steps, args.warmup, world, dist, device)
+    last_timed = []
+    el, seq_note = timed_steps(model, batch, args.steps, args.warmup, world, dist, device, last_timed)
+    dump = step_outputs(model, last_timed[0]) if args.dump_outputs and rank == 0 else None
     pct = step_percentiles(model, batch, min(args.steps, 200)) if args.steps >= 10 else None
     last = model.train_step(batch).as_floats()
     model.check_device_errors()          # a guard trip of the persistent LSTM kernel would void the run
@@ -477,7 +513,10 @@ def main():
             torch.cuda.empty_cache()
             m3 = make_model("attention", device, None)
             k3 = min(args.steps, 200)
-            el3, _ = timed_steps(m3, batch, k3, min(args.warmup, 20), 1, None, device)
+            last_timed3 = []
+            el3, _ = timed_steps(m3, batch, k3, min(args.warmup, 20), 1, None, device, last_timed3)
+            if dump is not None:
+                dump.update(step_outputs(m3, last_timed3[0], "config3__"))
             ms3 = el3 / k3 * 1e3
             dom3, others3, total3 = kernel_breakdown(m3, batch, "attention")
             m3.check_device_errors()
@@ -489,6 +528,8 @@ def main():
             out["dp_world1"] = dp_world1_rehearsal(args, device)
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload, host_batch)
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         print(json.dumps(out), flush=True)
     if use_dp:
         dist.barrier()

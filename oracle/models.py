@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY -- see oracle/__init__.py.  PARITY UNPINNED.
 
-Two model forms, both restated from the reference (paths relative to /root/reference):
+Two model forms, both restated from the reference (paths relative to the reference repository):
   * ``NICDense``  -- AttemptFour/Model/NIC.py:22-299   (BASELINE config 2: dense voxel encoder
                      + BatchNorm, feature as LSTM step 0, masked text LSTM, softmax head)
   * ``LcNIC``     -- AttemptFour/Model/lc_NIC.py:42-638 + layers.py + attention.py

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY -- see oracle/__init__.py.  PARITY UNPINNED.
 
-Restates (paths relative to /root/reference/ThinkAndTell):
+Restates (paths relative to ThinkAndTell/ of the reference repository):
   * ``Encoder``  att_model.py:31-52   Dense(E, relu, L2 on the kernel), Dropout only when training
   * ``Decoder``  att_model.py:61-129  Embedding (no mask, L2 on the table) -> the feature prepended as token 0 ->
                  GRU over T+1 steps from zero state (keras GRU v2: reset_after=True, bias (2, 3U), L2 on kernel

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY -- see oracle/__init__.py.  PARITY UNPINNED.
 
-Restates (paths relative to /root/reference/AttemptFour/Model):
+Restates (paths relative to AttemptFour/Model/ of the reference repository):
   * ``lc_NIC.call_fc``            lc_NIC.py:298-323
   * ``FullyConnected.call``       fullyConnected.py:20-27  (Dense -> BatchNorm -> Dropout; the
                                   construction the reference keeps commented at lc_NIC.py:60-67)

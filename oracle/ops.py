@@ -4,7 +4,7 @@ TEST INFRASTRUCTURE ONLY -- see oracle/__init__.py.  PARITY UNPINNED.
 
 Each function restates one reference op with Keras/TF semantics (SURVEY.md
 section 9); the reference line each one follows is cited in its docstring
-(paths relative to /root/reference).  Forward functions return what the
+(paths relative to the reference repository).  Forward functions return what the
 backward needs; backward functions are explicit formulas (verified against
 finite differences and torch autograd in tests/).
 """

@@ -155,12 +155,12 @@ def D_tok():
     return tok
 
 
-REF_CAPS = "/root/reference/soloist/Modified-Show-And-Tell-Keras/target_caps.txt"
+# data fixture held by the reference: soloist/Modified-Show-And-Tell-Keras/target_caps.txt (all 4 000 lines)
+REF_CAPS = os.path.join(HERE, "golden", "target_caps.txt")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CAPS), reason="reference corpus not present (GPU box): read in place, never copied")
 def test_tokenizer_pipeline_over_the_reference_corpus():
-    """The only caption corpus the reference holds (4 000 lines, read IN PLACE) through the whole text side of the input
+    """The only caption corpus the reference holds (4 000 lines, stored as a fixture) through the whole text side of the input
     contract: build_tokenizer (load_avg_betas.py:184-188: fit, then '<pad>' -> 0), create_pairs' '<start> ... <end>'
     wrapping (:259-265), texts_to_sequences / pad_sequences / shifted target / to_categorical
     (data_generator_guse.py:156-163).  Asserted: the invariants those call sites rely on, and the vocabulary against an
