@@ -580,6 +580,23 @@ int32_t tnt_beam_topk_f32(const float* probs, const float* score_in, const int32
                           int32_t* parent, int32_t* token, int32_t* fin_out, void* stream);
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,
                             void* stream);
+/* Greedy feedback step of the free-running decoder (lc_NIC.call_naive_attention, lc_NIC.py:175-221), one launch per
+ * step with no host round trip.  logits [B][ld] (V valid columns, ld >= V) are step i's output rows; table [V][E] the
+ * Embedding; w [E][ldw] (N columns) the text rows of the LSTM input kernel (gate-interleaved layout).
+ *   fed[b*T + col] = id_b = argmax over the row's V logits: ties go to the lowest index, NaN never wins, and the id is
+ *                    always in [0, V) (a row without a winner, e.g. all NaN, gives 0);
+ *   text[b][0..E)  = table[id_b] * keep / (1 - rate): the LSTM layer's per-call input mask of step col, i.e. the decision
+ *                    tnt_dropout_f32(rows_per_site = B) makes for row b, columns lcol0 .. lcol0 + E of the logical
+ *                    (B, lwidth) input, stream (seed, site, step + *step_dev); rate 0: no mask;
+ *   xz[b][0..N)    = text[b] . w  (no bias).
+ * The argmax is over the logits, not the probabilities the reference takes it over: the two differ only where two
+ * distinct logits round to the same float32 probability.  E % 4 == 0, E <= 1016, ldt % 4 == 0, table / text 16-byte
+ * aligned; rate > 0 needs lwidth, lcol0 % 4 == 0. */
+int32_t tnt_greedy_feedback_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
+                                const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T, int32_t col,
+                                float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B, float rate,
+                                uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev,
+                                int32_t lwidth, int32_t lcol0, void* stream);
 /* out[0] = scale * sum_i x[i]  (fixed-order, one workgroup). */
 /* Categorical sampling per row (tf.random.categorical(logits / temperature, 1): ThinkAndTell/evaluate.py:223,278;
  * lc_NIC.sample_choice lc_NIC.py:571-575 samples from log(probs)).  x: logits (from_logits=1) or probabilities.

@@ -420,6 +420,11 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     shard_encoder=True (dense-encoder NIC; default: TNT_DP_SHARD_ENC): the encoder kernel's update is row-sharded over the
     ranks (PipelinedDenseSync.step).  Every rank keeps the complete, identical kernel; only the optimizer moments of a shard
     live on its owner alone."""
+    if not getattr(model, "teacher_forcing", True):
+        # the free-running training step (lc_nic.NIC(teacher_forcing=False)) has no data-parallel schedule: refuse instead
+        # of running the teacher-forced one
+        raise NotImplementedError("data parallel training of the free-running decoder (teacher_forcing=False) is not "
+                                  "supported: train it on one device")
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.__dict__.get("agc") and world > 1:

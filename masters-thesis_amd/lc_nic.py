@@ -28,6 +28,7 @@ from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gate
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
 S_DEEP = 6            # + i: feature dropout behind deep stage i of the depth-n encoder (deep_layers.py:58)
+S_NOUT = 144          # + i: output Dropout of step i of the free-running decoder, on the U-wide LSTM output (lc_NIC.py:207)
 from .ops import ACT_LEAKY
 
 
@@ -72,8 +73,12 @@ class NIC(ModelBase):
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
-                 attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False, **kw):
+                 attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
+                 teacher_forcing=True, **kw):
         super().__init__(**kw)
+        # teacher_forcing=False: __call__ / train_step / test_step / fit run lc_NIC.call_naive_attention (lc_NIC.py:175-221),
+        # the decoder fed its own greedy predictions (call_naive_attention's docstring)
+        self.teacher_forcing = bool(teacher_forcing)
         # use_layer_norm: the decoder cell is tensorflow_addons' LayerNormLSTMCell (lc_NIC.py:115,126-136; hard-wired off in
         # the reference): LayerNorm on x W, on h U and on the new cell state, no dropout inside the cell
         self.use_layer_norm = bool(use_layer_norm)
@@ -217,6 +222,8 @@ class NIC(ModelBase):
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
+        if not self.teacher_forcing:
+            self._naive_check()
 
     # ------------------------------------------------------------------ weights
     def _init_weights(self, rng):
@@ -335,7 +342,8 @@ class NIC(ModelBase):
         self.gates = f(T, B, U, 4)
         self.qpre, self.alpha = f(T, B, A), f(T, B, R)
         self.ctx, self.ctx_d = f(T, B, D), f(T, B, D)
-        self.Hd = f(n, U) if self.r_lstm > 0 else None
+        self.Hd = f(n, U) if (self.r_lstm > 0 or self.r_out > 0) else None
+        self.last_ids = torch.zeros(B, dtype=torch.int32, device=self.device)     # free-running decode: step T-1's argmax
         if self.use_layer_norm:       # LayerNormLSTMCell: normalised projections, LayerNorm caches, per-step gradients
             self.ZK, self.ZR, self.ZRn = f(n, U, 4), f(n, U, 4), f(n, U, 4)
             self.xh_k, self.xh_r = f(n, 4 * U), f(n, 4 * U)
@@ -403,8 +411,9 @@ class NIC(ModelBase):
         return B, T
 
     # ------------------------------------------------------------------ forward
-    def _encode(self, B, training):
-        """dropout_input -> layers.LocallyDense.call (lc_NIC.py:227-230; layers.py:43-53)."""
+    def _encode(self, B, training, feat2=False):
+        """dropout_input -> layers.LocallyDense.call (lc_NIC.py:227-230; layers.py:43-53).  feat2: the feature Dropout
+        once more behind the encoder (call_naive_attention, lc_NIC.py:183-184)."""
         be, a = self.be, self.arena
         R, D, S = self.R, self.D, self.S
         sd, ds = self.seed, self.drop_step
@@ -455,6 +464,8 @@ class NIC(ModelBase):
                                  self.deep_istd[i], B * R, D, D, BN_EPS)
             if training and self.r_feat > 0 and not dropped:
                 be.dropout(out, out, B * R, D, D, 0, D, 0, self.r_feat, sd, S_DEEP + i, 0, ds)
+        if feat2 and training and self.r_feat > 0:
+            be.dropout(self.F, self.F, B * R, D, D, 0, D, 0, self.r_feat, sd, S_FEAT2, 0, ds)
         self.gemm_sk(self.F, a.p("attention/W1/kernel"), self.P, B * R, self.A, D, D, self.A, self.A,
                 bias=a.p("attention/W1/bias"), pre=self.Ppre, act=ACT_LEAKY, slope=0.2)      # attention.py:32 (hoisted)
 
@@ -570,6 +581,67 @@ class NIC(ModelBase):
         self.gemm_sk(inter, a.p("time_distributed_softmax/kernel"), self.logits, n, V, H, H, ldV, ldV,
                 bias=a.p("time_distributed_softmax/bias"))                                     # :261
 
+    def _naive_check(self):
+        """the combinations the free-running decoder is built for; anything else refuses instead of running another mode"""
+        if self.S != 1:
+            raise NotImplementedError("the free-running decoder (call_naive_attention) is a single-subject mode: n_subjects > 1 "
+                                      "is not supported")
+        if self.use_layer_norm:
+            raise NotImplementedError("the free-running decoder (call_naive_attention) is not built for the LayerNormLSTMCell "
+                                      "(use_layer_norm=True)")
+        if self.Et % 4:
+            raise NotImplementedError("the free-running decoder needs embedding_text % 4 == 0 (tnt_greedy_feedback_f32)")
+
+    def _forward_naive(self, B, T, training):
+        """lc_NIC.call_naive_attention (lc_NIC.py:175-221): the decoder fed its own greedy predictions.  Per step: attention
+        -> LSTM step (per-step kernels: the head sits inside the recurrence, so the persistent chain cannot run) -> the
+        LSTM-output and output Dropouts on the U-wide state in one pass -> dense_inter -> dense_out -> the feedback launch
+        (tnt_greedy_feedback_f32: argmax -> fed id, its Embedding row through the next step's LSTM input mask, the text half
+        of the next step's input projection).  The fed ids go to column i + 1 of ``self.cap`` in place: column 0 keeps
+        the staged start token, and the backward pass scatters the Embedding gradient to exactly these ids."""
+        be, a = self.be, self.arena
+        D, U, Et, V, H, ldV = self.D, self.U, self.Et, self.V, self.H, self.ldV
+        sd, ds = self.seed, self.drop_step
+        self._encode(B, training, feat2=True)                                               # :180-184
+        emb, Wl = a.p("emb_text/embeddings"), a.p("lstm/kernel")
+        lstm_in = training and self.r_lstm > 0
+        # step 0's input: the start token through the Embedding, the text Dropout (:187-189) and step 0's LSTM input mask,
+        # as the teacher-forced step forms it (one launch over all T caption columns; rows 1.. are replaced by the fed ones)
+        if training and self.r_text > 0:
+            be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
+                                  mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if lstm_in else None)
+        else:
+            be.embedding_fwd(emb, self.cap, self.text, B, T, Et, Et, V)
+            if lstm_in:
+                be.dropout(self.text, self.text, B, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds)
+        self.gemm_sk(self.text[:B], Wl[D:], self.XZ[:B], B, 4 * U, Et, Et, 4 * U, 4 * U)
+        if training and self._keep_stored and not self.__dict__.get("_masks_staged"):
+            be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
+        r_lo, r_o = (self.r_lstm, self.r_out) if training else (0.0, 0.0)
+        for i in range(T):                                                                  # :191-219
+            rows = slice(i * B, (i + 1) * B)
+            self._decode_step(i, B, training, xz_bias=a.p("lstm/bias"))
+            h = self.Hs[i + 1]
+            if r_lo > 0 and r_o > 0:        # seq = dropout_lstm(a); output = dropout_output(seq)  (:205-207)
+                be.dropout2(h, self.Hd[rows], B, U, U, (0, U, 0, 0, r_lo, S_LSTM_OUT + i), (0, U, 0, 0, r_o, S_NOUT + i), sd, 0, ds)
+            elif r_lo > 0 or r_o > 0:
+                be.dropout(h, self.Hd[rows], B, U, U, 0, U, 0, max(r_lo, r_o), sd, S_LSTM_OUT + i if r_lo > 0 else S_NOUT + i, 0, ds)
+            if r_lo > 0 or r_o > 0:
+                h = self.Hd[rows]
+            self.gemm_sk(h, a.p("time_distributed_nonlinear/kernel"), self.inter[rows], B, H, U, U, H, H,
+                         bias=a.p("time_distributed_nonlinear/bias"), pre=self.ipre[rows], act=ACT_LEAKY, slope=0.2)   # :209
+            self.gemm_sk(self.inter[rows], a.p("time_distributed_softmax/kernel"), self.logits[rows], B, V, H, H, ldV, ldV,
+                         bias=a.p("time_distributed_softmax/bias"))                                                 # :211
+            if i + 1 < T:                                                                   # :215-217
+                nxt = slice((i + 1) * B, (i + 2) * B)
+                be.greedy_feedback(self.logits[rows], ldV, V, emb, Et, Wl[D:], 4 * U, 4 * U, self.cap, T, i + 1, self.text[nxt],
+                                   Et, self.XZ[nxt], 4 * U, B, self.r_lstm if lstm_in else 0.0, sd, S_LSTM_IN + i + 1, 0, ds,
+                                   lwidth=D + Et, lcol0=D)
+        self._hs_used = self.Hd if (r_lo > 0 or r_o > 0) else self.Hs[1:].view(T * B, U)
+        self._inter_used = self.inter
+        self._out_dropped = False
+        self._metric_parts_ready = False
+
     def _loss_metrics(self, B, T, want_grad):
         be = self.be
         n = T * B
@@ -604,12 +676,13 @@ class NIC(ModelBase):
     def _backward(self, B, T):
         """tape.gradient (lc_NIC.py:386-387) as four launch groups, in the order the gradients become final -- the
         data-parallel schedule (dp.PipelinedAttentionSync) issues one all-reduce bucket after each."""
-        self._bwd_head(B, T)
+        naive = not self.teacher_forcing       # the free-running step: its own head and text branch, the same chain
+        (self._bwd_head_naive if naive else self._bwd_head)(B, T)
         self._bwd_chain(B, T)
         # the text branch (input Dropout', sparse Embedding scatter) and the front branch (attention parameters, BatchNorm,
         # region-wise encoder) only share the chain's outputs: with `branch_streams` they are two parallel branches of the step
         with self.side(0 if getattr(self, "branch_streams", False) else -1):
-            self._bwd_emb(B, T)
+            (self._bwd_emb_naive if naive else self._bwd_emb)(B, T)
         self._bwd_front(B, T)
         self.join()
 
@@ -806,6 +879,62 @@ class NIC(ModelBase):
         self._emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
         self._embedding_bwd(self.dtext, self.cap, "emb_text/embeddings", B, T, Et, Et, V)
 
+    def _bwd_head_naive(self, B, T):
+        """vocabulary head of the free-running step: no Dropout between dense_inter and dense_out; the LSTM-output and the
+        output Dropout' both act on dHs (lc_NIC.py:205-211)."""
+        be, a = self.be, self.arena
+        U, V, H, ldV = self.U, self.V, self.H, self.ldV
+        n = T * B
+        sd, ds = self.seed, self.drop_step
+        dlog, inter, hs = self.logits, self.inter, self._hs_used
+        if not (getattr(self, "g3_riders", True) and self.gemm3_pair(
+                dict(A=inter, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=H, N=V, K=n, lda=H, ldb=ldV, ldc=ldV, transA=True),
+                dict(A=dlog, B=a.p("time_distributed_softmax/kernel"), C=self.dinter, M=n, N=H, K=V, lda=ldV, ldb=ldV, ldc=H,
+                     transB=True))):
+            self.gemm_sk(inter, dlog, a.g("time_distributed_softmax/kernel"), H, V, n, H, ldV, ldV, transA=True)
+            self.gemm_sk(dlog, a.p("time_distributed_softmax/kernel"), self.dinter, n, H, V, ldV, ldV, H, transB=True)
+        dhs_done = False
+        if hasattr(be, "bias_act_drop_bwd") and n <= 2048 and H % 4 == 0:
+            # LeakyReLU' + both bias gradients in one launch (rate 0: no Dropout on this side)
+            be.bias_act_drop_bwd(self.dinter, self.ipre, self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H,
+                                 ACT_LEAKY, 0.2, 0, H, 0, 0.0, sd, S_OUT, ds,
+                                 extra=(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV))
+            dhs_done = bool(getattr(self, "g3_riders", True) and self.gemm3_pair(
+                dict(A=hs, B=self.dinter, C=a.g("time_distributed_nonlinear/kernel"), M=U, N=H, K=n, lda=U, ldb=H, ldc=H,
+                     transA=True, small=True),
+                dict(A=self.dinter, B=a.p("time_distributed_nonlinear/kernel"), C=self.dHs, M=n, N=U, K=H, lda=H, ldb=H, ldc=U,
+                     transB=True, small=True)))
+        else:
+            be.colsum(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV, self.work)
+            be.act_bwd(self.ipre, self.dinter, self.dinter, n * H, ACT_LEAKY, 0.2)
+            be.colsum(self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H, self.work)
+        if not dhs_done:
+            self.gemm_sk(hs, self.dinter, a.g("time_distributed_nonlinear/kernel"), U, H, n, U, H, H, transA=True)
+            self.gemm_sk(self.dinter, a.p("time_distributed_nonlinear/kernel"), self.dHs, n, U, H, H, H, U, transB=True)
+        self._dout_masked = True            # both masks are applied here, none rides in the backward chain
+        r_lo, r_o = self.r_lstm, self.r_out
+        if r_lo > 0 and r_o > 0:
+            be.dropout2(self.dHs, self.dHs, n, U, U, (0, U, 0, B, r_lo, S_LSTM_OUT), (0, U, 0, B, r_o, S_NOUT), sd, 0, ds)
+        elif r_lo > 0 or r_o > 0:
+            be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, max(r_lo, r_o), sd, S_LSTM_OUT if r_lo > 0 else S_NOUT, 0, ds,
+                       rows_per_site=B)
+
+    def _bwd_emb_naive(self, B, T):
+        """text branch of the free-running step: the LSTM input mask' on every step's text rows, the text Dropout' on step
+        0's only (the fed tokens have none, lc_NIC.py:217), the Embedding scatter to the fed ids."""
+        be, a = self.be, self.arena
+        D, U, Et, V = self.D, self.U, self.Et, self.V
+        n = T * B
+        sd, ds = self.seed, self.drop_step
+        if not self.__dict__.pop("_dtext_done", False):
+            self.gemm_sk(self.dZ, a.p("lstm/kernel")[D:], self.dtext, n, Et, 4 * U, 4 * U, 4 * U, Et, transB=True)
+        if self.r_lstm > 0:
+            be.dropout(self.dtext, self.dtext, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds, rows_per_site=B)
+        if self.r_text > 0:          # step 0's rows of the logical (B, T, Et) mask the forward's Embedding launch applied
+            be.dropout(self.dtext[:B], self.dtext[:B], B, Et, Et, 0, T * Et, 0, self.r_text, sd, S_TEXT, 0, ds)
+        self._emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
+        self._embedding_bwd(self.dtext, self.cap, "emb_text/embeddings", B, T, Et, Et, V)
+
     def _bwd_front(self, B, T):
         """attention parameters, then BatchNorm / region-wise encoder backward."""
         be, a = self.be, self.arena
@@ -842,6 +971,8 @@ class NIC(ModelBase):
             self.gemm_sk(self.F, self.dP, a.g("attention/W1/kernel"), D, A, B * R, D, A, A, transA=True)
             be.colsum(self.dP, a.g("attention/W1/bias"), B * R, A, A, self.work)
             self.gemm_sk(self.dP, a.p("attention/W1/kernel"), self.dF, B * R, D, A, A, A, D, transB=True, accumulate=True)
+        if not self.teacher_forcing and self.r_feat > 0:     # the second feature Dropout of call_naive_attention (:184)
+            be.dropout(self.dF, self.dF, B * R, D, D, 0, D, 0, self.r_feat, sd, S_FEAT2, 0, ds)
         # encoder
         S = self.S
         Bs = B // S
@@ -893,7 +1024,7 @@ class NIC(ModelBase):
 
     # ------------------------------------------------------------------ steps
     def _train_graph(self, B, T):
-        self._forward(B, T, True)
+        (self._forward if self.teacher_forcing else self._forward_naive)(B, T, True)
         self._loss_metrics(B, T, True)
         self._backward(B, T)
 
@@ -939,6 +1070,8 @@ class NIC(ModelBase):
         """lc_NIC.train_step (lc_NIC.py:328-408): returns {loss, L2, accuracy, attention, lr}."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
+        if not self.teacher_forcing and self.grad_sync is not None:
+            raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
@@ -974,6 +1107,9 @@ class NIC(ModelBase):
         same dropout masks.  One captured launch sequence: two forward / backward passes and the update."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step_sam")
+        if not self.teacher_forcing:
+            raise NotImplementedError("train_step_sam is a teacher-forced step (lc_NIC.py:713-838): not built for "
+                                      "teacher_forcing=False")
         if self.S != 1:
             raise NotImplementedError("train_step_sam is a single-subject step (lc_NIC.py)")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
@@ -1017,7 +1153,7 @@ class NIC(ModelBase):
         train_flag = self.S > 1
 
         def run():
-            self._forward(B, T, train_flag)
+            (self._forward if self.teacher_forcing else self._forward_naive)(B, T, train_flag)
             self._loss_metrics(B, T, False)
             self._norms_and_l2(self.met[2:3])
             if train_flag:
@@ -1026,8 +1162,16 @@ class NIC(ModelBase):
         return self._metrics(False)
 
     def __call__(self, data, training=False):
-        """lc_NIC.call -> call_attention (lc_NIC.py:163-164,223-263):
+        """lc_NIC.call -> call_attention (lc_NIC.py:163-164,223-263), or call_naive_attention with teacher_forcing=False:
         returns (probabilities (B,T,V), attention scores (T,B,R,1))."""
+        if not self.teacher_forcing:
+            return self.call_naive_attention(data, training)
+        return self.call_attention(data, training)
+
+    call = __call__
+
+    def call_attention(self, data, training=False):
+        """lc_NIC.call_attention (lc_NIC.py:223-263): returns (probabilities (B,T,V), attention scores (T,B,R,1))."""
         B, T = self._stage_inputs(data)
         self._masks_staged = False
 
@@ -1038,7 +1182,29 @@ class NIC(ModelBase):
             return probs, self.alpha.clone().unsqueeze(-1)
         return self._guarded(run)
 
-    call = call_attention = __call__
+    def call_naive_attention(self, data, training=False, return_ids=False):
+        """lc_NIC.call_naive_attention (lc_NIC.py:175-221): only the caption's start token (column 0) is read; every
+        later step is fed the argmax of the step before.  Returns (probabilities (B,T,V), attention scores (T,B,R,1)),
+        plus the predicted ids (B,T) int32 (the argmax of every step's output) with return_ids=True.  The argmax is taken
+        over the logits (include/tnt_hip.h: tnt_greedy_feedback_f32)."""
+        self._naive_check()
+        B, T = self._stage_inputs(data)
+        self._masks_staged = False
+
+        def run():
+            self._forward_naive(B, T, training)
+            self.be.argmax_rows(self.logits[(T - 1) * B:], self.last_ids, B, self.V, self.ldV)
+            self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
+            probs = self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
+            out = (probs, self.alpha.clone().unsqueeze(-1))
+            if return_ids:
+                out += (torch.cat([self.cap[:, 1:], self.last_ids.view(B, 1)], dim=1),)
+            return out
+        return self._guarded(run)
+
+    def fed_ids(self):
+        """(B, T) int32 numpy: the tokens the last free-running pass fed its decoder steps (column 0: the start token)"""
+        return self.cap.cpu().numpy().copy()
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
                        sample_step=0):

@@ -305,6 +305,14 @@ class HipBackend:
     def argmax_rows(self, x, out, rows, V, ld):
         self._call(self.lib.tnt_argmax_rows_f32, "tnt_argmax_rows_f32", _p(x), _p(out), rows, V, ld, self._s())
 
+    def greedy_feedback(self, logits, ld, V, table, E, w, ldw, N, fed, T, col, text, ldt, xz, ldz, B, rate, seed, site, step,
+                        step_dev=None, lwidth=0, lcol0=0):
+        """one free-running decoder step's feedback (tnt_greedy_feedback_f32): fed[b*T + col] = argmax of logits row b,
+        text[b] = table[id] through the LSTM input mask (seed, site, lwidth, lcol0), xz[b] = text[b] . w"""
+        self._call(self.lib.tnt_greedy_feedback_f32, "tnt_greedy_feedback_f32", _p(logits), ld, V, _p(table), E, _p(w), ldw, N,
+                   _p(fed), T, col, _p(text), ldt, _p(xz), ldz, B, float(rate), int(seed), int(site), int(step), _p(step_dev),
+                   int(lwidth), int(lcol0), self._s())
+
     def enc_tail_fwd(self, y, gamma, beta, mov_mean, mov_var, out, xhat, inv_std, rows, C, ldo, training, eps, momentum,
                      r_feat, r_lstm, seed, site_feat, site_lstm, step_dev=None):
         self._call(self.lib.tnt_enc_tail_fwd_f32, "tnt_enc_tail_fwd_f32", _p(y), _p(gamma), _p(beta), _p(mov_mean), _p(mov_var), _p(out), _p(xhat),
