@@ -605,6 +605,29 @@ int32_t tnt_greedy_feedback_f32(const float* logits, int32_t ld, int32_t V, cons
 int32_t tnt_sample_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,
                             float temperature, int32_t from_logits, uint64_t seed, uint32_t site,
                             uint32_t step, const uint32_t* step_dev, void* stream);
+/* Top-k / nucleus (top-p) categorical sampling per row (lc_NIC.select_nucleus2 lc_NIC.py:694-710, img_NIC
+ * select_topk / select_nucleus img_NIC.py:510-539, defined in rank order; restated in float64 by
+ * tests/topkp_oracle.py).  Definition, per row:
+ *  - l_j = x_j (from_logits) or log(x_j) (probabilities; log 0 = -inf).  Let m = max_j l_j and
+ *    w_j = exp((l_j - m) / temperature).  These are the weights of tnt_sample_rows_f32.
+ *  - Rank order: w descending, ties broken by the lower index.
+ *  - Top-k: with K = min(top_k, V) when top_k >= 1, else K = V, the candidates are the first K tokens in rank
+ *    order.  S_K is their total weight.
+ *  - Nucleus: when top_p < 1, a candidate of rank r is kept iff the weight of the candidates ranked before it is
+ *    < top_p * S_K.  This keeps the shortest rank prefix whose mass reaches top_p * S_K, and rank 0 is always kept.
+ *    top_p >= 1 switches the filter off; no comparison is made.
+ *  - Draw: u is the Philox uniform of element `row` in stream (seed, site, step + *step_dev), exactly as in
+ *    tnt_sample_rows_f32.  out[row] is the first index j, in ascending index order, at which the running sum of kept
+ *    weights exceeds u * sum(kept).
+ *  - The written id is always in [0, V), whatever the input, NaN rows included.
+ * Implementation notes: a NaN weight counts as 0; the nucleus masses are summed in 2^-38 fixed point (deterministic;
+ * off by < V * 2^-39 <= 3e-8 of S_K); the draw keeps tnt_sample_rows_f32's 256 contiguous chunks and serial prefix
+ * over the chunk sums, so top_k = 0, top_p = 1 returns that kernel's ids; if rounding leaves no index past the target,
+ * the id is the last kept index of positive weight (0 if there is none).  One workgroup per row, the row's weights
+ * in LDS: V <= 16384.  TNT_BADARG for rows <= 0 or V <= 0, temperature <= 0, top_p <= 0, V > 16384. */
+int32_t tnt_sample_topkp_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,
+                             float temperature, int32_t top_k, float top_p, int32_t from_logits,
+                             uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev, void* stream);
 /* out[0] = mean_i (c - x[i])^2 (MeanSquaredError against a constant target, lc_NIC.py:813-814) */
 int32_t tnt_sqdiff_mean_f32(const float* x, float* out, int64_t n, float c, void* stream);
 int32_t tnt_sum_f32(const float* x, float* out, int32_t n, float scale, void* stream);

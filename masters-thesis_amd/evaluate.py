@@ -79,19 +79,26 @@ def ids_to_captions(ids, tokenizer, end_token="<end>", drop=("<start>", "<pad>")
     return caps
 
 
-def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>"):
+def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>", top_k=0,
+                top_p=1.0):
     """ThinkAndTell/evaluate.py:261-284 (`simple_eval`): one teacher-forced forward of the caption generator, then one
     categorical draw per position from the logits (tf.random.categorical(logits, 1)); the caption is cut at the first
     <end>.  The draw runs on the device (tnt_sample_rows_f32, Philox stream (seed, S_SAMPLE, sample_step)).
+    ``top_k`` / ``top_p`` filter the draw (tnt_sample_topkp_f32 on the same stream; the defaults 0 / 1 are off).
     Returns (ids (B, T+1) int64, captions or None)."""
     import torch
     from . import ops
-    from .model_base import S_SAMPLE
+    from .model_base import S_SAMPLE, check_sampling
+    top_k, top_p, _ = check_sampling(top_k, top_p, temperature)
     logits = model((betas, None, target), training=False)                 # (B, T+1, V), device tensor
     Bn, Tn, V = logits.shape
     flat = logits.reshape(Bn * Tn, V).contiguous()
     ids = torch.zeros(Bn * Tn, dtype=torch.int32, device=flat.device)
-    ops.backend().sample_rows(flat, ids, Bn * Tn, V, V, temperature, True, model.seed, S_SAMPLE, sample_step)
+    if top_k == 0 and top_p == 1.0:
+        ops.backend().sample_rows(flat, ids, Bn * Tn, V, V, temperature, True, model.seed, S_SAMPLE, sample_step)
+    else:
+        ops.backend().sample_topkp(flat, ids, Bn * Tn, V, V, temperature, top_k, top_p, True, model.seed, S_SAMPLE,
+                                   sample_step)
     ids = ids.view(Bn, Tn).cpu().numpy().astype(np.int64)
     caps = None
     if tokenizer is not None:

@@ -23,7 +23,7 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
-                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, BN_EPS, BN_MOMENTUM)
+                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, BN_EPS, BN_MOMENTUM, check_sampling)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -1207,16 +1207,26 @@ class NIC(ModelBase):
         return self.cap.cpu().numpy().copy()
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       sample_step=0):
+                       sample_step=0, top_k=0, top_p=1.0, return_s=True):
         """greedy_predict_attention with the argmax replaced by lc_NIC.sample_choice (lc_NIC.py:571-575:
         tf.random.categorical(log(probs), 1)); ``temperature`` as in ThinkAndTell/evaluate.py:223.  TF's
         sampler cannot be reproduced; the draw is the Philox stream (seed, S_SAMPLE + position, sample_step),
-        restated by oracle.ops.sample_rows.  Same return tuple as greedy_predict."""
+        restated by oracle.ops.sample_rows.  Same return tuple as greedy_predict.
+
+        ``top_k`` (>= 1: only the k most likely tokens) and ``top_p`` (< 1: only the shortest most-likely prefix whose
+        mass reaches top_p) filter each draw (tnt_sample_topkp_f32, definition in include/tnt_hip.h; lc_NIC
+        select_nucleus2, lc_NIC.py:694-710).  With both at their defaults the draw is the unfiltered one above.  A
+        filtered decode is captured and replayed like greedy_predict; sample_step reaches the replay through a device
+        word, so every call draws its own stream without a re-capture."""
+        top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
+        if top_k == 0 and top_p == 1.0:
+            return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
+                                       _sample=(temperature, int(sample_step)), return_s=return_s)
         return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
-                                   _sample=(float(temperature), int(sample_step)))
+                                   _filter=(temperature, top_k, top_p, int(sample_step)), return_s=return_s)
 
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, training=False,
-                       _sample=None, return_s=True):
+                       _sample=None, return_s=True, _filter=None):
         """lc_NIC.greedy_predict -> greedy_predict_attention (lc_NIC.py:507-508,577-638).
         Returns (words (B,max_len,1) int64, probs (B,max_len,V), alpha (max_len,B,R,1), s (max_len,B,R,A))
         as numpy arrays; the whole decode runs on the device with no per-step host sync."""
@@ -1238,6 +1248,8 @@ class NIC(ModelBase):
                          torch.zeros(max_len, B, dtype=torch.int32, device=self.device))
         start_buf, probs, s_all, ids = bufs[key]
         start_buf.copy_(start.view(B, 1))
+        if _filter is not None:
+            step_buf = self._sample_step_word(_filter[3])
 
         def run():
             self._encode(B, False)
@@ -1253,12 +1265,17 @@ class NIC(ModelBase):
                 self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), probs[i], B, V, H, H, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))                                # :623
                 be.softmax_cce(probs[i], None, probs[i], None, None, None, B, V, ldV, 0.0)
-                if _sample is None:
+                if _filter is not None:
+                    be.sample_topkp(probs[i], ids[i], B, V, ldV, _filter[0], _filter[1], _filter[2], False, self.seed,
+                                    S_SAMPLE + i, 0, step_buf)
+                elif _sample is None:
                     be.argmax_rows(probs[i], ids[i], B, V, ldV)                                    # :627
                 else:
                     be.sample_rows(probs[i], ids[i], B, V, ldV, _sample[0], False, self.seed, S_SAMPLE + i, _sample[1])
                 words = ids[i].view(B, 1)
-        if _sample is None:
+        if _filter is not None:     # the stream step is read from step_buf on the device: captured like the greedy loop
+            self._run_captured(("sample",) + key + tuple(_filter[:3]), run)
+        elif _sample is None:
             self._run_captured(("greedy",) + key, run)
         else:                      # the sampling stream step is a launch argument: not captured
             run()

@@ -24,6 +24,22 @@ S_SAMPLE = 112          # + decode position: categorical-sampling stream of samp
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
+def check_sampling(top_k, top_p, temperature):
+    """host validation of the sampling filters (tnt_sample_topkp_f32): top_k an int >= 0 (0 = off), 0 < top_p <= 1
+    (1 = off), temperature > 0.  Returns (int top_k, float top_p, float temperature); ValueError otherwise."""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
+        raise ValueError(f"top_k must be an int >= 0 (0: no top-k filter), got {top_k!r}")
+    try:
+        p, t = float(top_p), float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"top_p and temperature must be numbers, got {top_p!r}, {temperature!r}") from None
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1] (1: no nucleus filter), got {top_p!r}")
+    if not t > 0.0:
+        raise ValueError(f"temperature must be > 0, got {temperature!r}")
+    return int(top_k), p, t
+
+
 def interleave_gates(w, U):
     """keras [.., 4U] (i,f,c~,o blocks) -> kernel layout [.., U, 4]."""
     w = np.asarray(w)
@@ -843,6 +859,15 @@ class ModelBase:
         self._graphs = {}
 
     # ------------------------------------------------------------------ graph capture
+    def _sample_step_word(self, step):
+        """the static device word a captured sampled decode reads its Philox stream step from (step_dev), set to
+        ``step`` (mod 2^32) on the stream before the launch or replay"""
+        w = self.__dict__.get("_step_word")
+        if w is None:
+            w = self._step_word = torch.zeros(1, dtype=torch.int32, device=self.device)
+        w.fill_(int(np.uint32(int(step) & 0xFFFFFFFF).view(np.int32)))
+        return w
+
     def _run_captured(self, key, fn):
         """Run ``fn`` (a fixed launch sequence over static buffers) through a hipGraph:
         first call eager (warm-up), second call captures, later calls replay."""

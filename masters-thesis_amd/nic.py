@@ -19,7 +19,7 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM)
+                         BN_MOMENTUM, S_SAMPLE, check_sampling)
 from .ops import ACT_LEAKY
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -639,6 +639,27 @@ class NIC(ModelBase):
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None):
         """NIC.greedy_predict (NIC.py:148-195), inference mode; returns np.ndarray (max_len, B, 1, V).
         A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does."""
+        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None)
+        return probs_all[:, :, :self.V].cpu().numpy()[:, :, None, :]
+
+    def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
+                       top_k=0, top_p=1.0, sample_step=0):
+        """greedy_predict with the argmax replaced by a categorical draw from each step's probabilities, filtered by
+        ``top_k`` (>= 1: only the k most likely tokens; 0: off) and ``top_p`` (< 1: only the shortest most-likely prefix
+        whose mass reaches top_p; 1: off) at ``temperature`` (tnt_sample_topkp_f32, definition in include/tnt_hip.h).
+        The draw is the Philox stream (seed, S_SAMPLE + position, sample_step), as in lc_nic.NIC.sample_predict.  A
+        sampled id 0 masks the following LSTM step exactly as a greedy 0 does.  The decode is captured and replayed like
+        greedy_predict; sample_step reaches the replay through a device word.
+        Returns (ids (B, max_len, 1) int64, probs (max_len, B, 1, V))."""
+        top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
+        probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)))
+        V = self.V
+        return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
+                probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
+
+    def _decode(self, img_input, a0, c0, start_seq, max_len, filt):
+        """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
+        sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None)"""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         B = start.shape[0]
@@ -654,6 +675,13 @@ class NIC(ModelBase):
                          torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device))
         start_buf, words, probs_all = bufs[key]
         start_buf.copy_(start.view(B, 1))
+        ids = None
+        if filt is not None:
+            sbufs = self.__dict__.setdefault("_sample_ids", {})
+            if key not in sbufs:
+                sbufs[key] = torch.zeros(max_len, B, dtype=torch.int32, device=self.device)
+            ids = sbufs[key]
+            step_buf = self._sample_step_word(filt[3])
 
         def run():
             self.gemm_sk(self.x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
@@ -672,16 +700,25 @@ class NIC(ModelBase):
             be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, None, 0, 0, None, h[1], c[1], None, self.gates[0], B, U)
             cur = 1
             out = self.Out[0]
+            prev = words
             for i in range(max_len):
-                tok = start_buf if i == 0 else words
+                tok = start_buf if i == 0 else prev
                 be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, B, 1, E, E, V)
                 self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-                be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, words if i > 0 else None, 1, 0, None,
+                be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, prev if i > 0 else None, 1, 0, None,
                                  h[1 - cur], c[1 - cur], out, self.gates[0], B, U)
                 cur = 1 - cur
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs_all[i], B, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
                 be.softmax_cce(probs_all[i], None, probs_all[i], None, None, None, B, V, ldV, 0.0)
-                be.argmax_rows(probs_all[i], words, B, V, ldV)
-        self._run_captured(("greedy",) + key, run)
-        return probs_all[:, :, :V].cpu().numpy()[:, :, None, :]
+                if filt is None:
+                    be.argmax_rows(probs_all[i], words, B, V, ldV)
+                else:
+                    be.sample_topkp(probs_all[i], ids[i], B, V, ldV, filt[0], filt[1], filt[2], False, self.seed,
+                                    S_SAMPLE + i, 0, step_buf)
+                    prev = ids[i].view(B, 1)
+        if filt is None:
+            self._run_captured(("greedy",) + key, run)
+        else:
+            self._run_captured(("sample",) + key + tuple(filt[:3]), run)
+        return probs_all, ids

@@ -488,6 +488,11 @@ class HipBackend:
         self._call(self.lib.tnt_sample_rows_f32, "tnt_sample_rows_f32", _p(x), _p(out), rows, V, ld, float(temperature), int(from_logits),
                                                 int(seed), int(site), int(step), _p(step_dev), self._s())
 
+    def sample_topkp(self, x, out, rows, V, ld, temperature, top_k, top_p, from_logits, seed, site, step, step_dev=None):
+        """top-k / nucleus filtered sample_rows (tnt_sample_topkp_f32; definition in include/tnt_hip.h)"""
+        self._call(self.lib.tnt_sample_topkp_f32, "tnt_sample_topkp_f32", _p(x), _p(out), rows, V, ld, float(temperature),
+                   int(top_k), float(top_p), int(from_logits), int(seed), int(site), int(step), _p(step_dev), self._s())
+
     def sum(self, x, out, n, scale):
         self._call(self.lib.tnt_sum_f32, "tnt_sum_f32", _p(x), _p(out), n, scale, self._s())
 
