@@ -578,6 +578,23 @@ int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t 
 int32_t tnt_beam_topk_f32(const float* probs, const float* score_in, const int32_t* fin_in, int32_t B,
                           int32_t V, int32_t ld, int32_t k, int32_t end_id, float* score_out,
                           int32_t* parent, int32_t* token, int32_t* fin_out, void* stream);
+/* One beam-search step: the expansion of tnt_beam_topk_f32 and the reorder of the LSTM state by parent, in one launch
+ * (restated by tests/dense_beam_oracle.py).  Definition:
+ *  - Expansion: score_out, parent, token, fin_out [B*k] are exactly those of tnt_beam_topk_f32 for the same
+ *    (probs, score_in, fin_in, B, V, ld, k, end_id), bit for bit for every finite score_in: candidate (beam j, token v)
+ *    is the float32 value score_in[j] + logf(fmaxf(p, 1e-30f)); a finished beam (fin_in != 0) has one candidate, token
+ *    0 at its own score; ties go to the lower flat index j*V + v; output in rank order, best first.
+ *  - Reorder: h_out[r][0..U) = h_in[parent[r]][0..U) for every r < B*k, likewise c; plain bit copies, row stride ldh.
+ *    U == 0 skips the reorder (the state pointers are then not read).  h_out / c_out must not overlap h_in / c_in:
+ *    callers ping-pong the buffers.
+ *  - k <= 16, any V.  One workgroup of 16 waves per sample, 16 / k waves per beam row; each workgroup touches only its
+ *    own sample's rows.  Deterministic, no scratch memory, no host sync.
+ * TNT_BADARG for B <= 0, V <= 0, k < 1, k > 16, ld < V, U < 0, ldh < U, score_out == score_in, fin_out == fin_in, and
+ * (U > 0) a null state pointer or an output state buffer that overlaps an input one. */
+int32_t tnt_beam_step_f32(const float* probs, int32_t ld, const float* score_in, const int32_t* fin_in, int32_t B,
+                          int32_t V, int32_t k, int32_t end_id, float* score_out, int32_t* parent, int32_t* token,
+                          int32_t* fin_out, const float* h_in, const float* c_in, int32_t ldh, int32_t U,
+                          float* h_out, float* c_out, void* stream);
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,
                             void* stream);
 /* Greedy feedback step of the free-running decoder (lc_NIC.call_naive_attention, lc_NIC.py:175-221), one launch per

@@ -4,6 +4,8 @@
   ``model.greedy_predict`` and write ``output_captions_<epoch>.npy``, ``output_captions_raw_<epoch>.npy``,
   ``attention_scores_<epoch>.npy`` and ``tokenizer.json`` with the reference's array layouts, so the
   thesis' analysis scripts keep working.
+* ``beam_captions``                   -- the best beam-search caption of either model (``beam_search``), from the
+  tokenizer's <start> / <end> indices.
 * ``ids_to_captions``                 -- tokenizer.sequences_to_texts with the <start>/<end>/<pad> handling of
   ThinkAndTell/evaluate.py:178-201.
 * ``sentence_bleu`` / ``bleu_scores`` -- ThinkAndTell/img_evaluate.py:212-250 calls
@@ -77,6 +79,18 @@ def ids_to_captions(ids, tokenizer, end_token="<end>", drop=("<start>", "<pad>")
             words.append(w)
         caps.append(words)
     return caps
+
+
+def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, length_penalty=0.0, end_token="<end>"):
+    """Beam-search captions of either model (nic.NIC or lc_nic.NIC ``beam_search``): every caption starts at the
+    tokenizer's "<start>" index and a beam ends at ``end_token``'s index.  Returns (ids (B, max_len) int64 of each
+    sample's best beam, captions: token lists cut at ``end_token`` as ids_to_captions cuts)."""
+    end_id = int(tokenizer.word_index[end_token])
+    start = np.full(int(features.shape[0]), int(tokenizer.word_index["<start>"]), np.int64)
+    seqs, _ = model.beam_search(features, a0, c0, start, max_len, beam_width=beam_width, end_id=end_id,
+                                length_penalty=length_penalty)
+    ids = np.ascontiguousarray(seqs[:, 0, :]).astype(np.int64)
+    return ids, ids_to_captions(ids, tokenizer, end_token=end_token)
 
 
 def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>", top_k=0,

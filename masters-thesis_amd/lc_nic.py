@@ -23,7 +23,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
-                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, BN_EPS, BN_MOMENTUM, check_sampling)
+                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, BN_EPS, BN_MOMENTUM, check_sampling, check_length_penalty,
+                         length_normalise)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -1287,15 +1288,19 @@ class NIC(ModelBase):
 
     greedy_predict_attention = greedy_predict
 
-    def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None):
+    def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
+                    length_penalty=0.0):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,
         lc_NIC.py:640-692, recurse without returning; ThinkAndTell/evaluate.py:203-228 stops after one expansion), so
         the definition is this library's: standard log-probability beam search of width ``beam_width`` with the greedy
-        decoder's step (lc_NIC.py:596-632), no length normalisation; a beam that emits ``end_id`` (the tokenizer's
+        decoder's step (lc_NIC.py:596-632), no length normalisation by default; a beam that emits ``end_id`` (the tokenizer's
         '<end>' index; -1 = never) is finished and pads with 0.  Returns (sequences (B, k, max_len) int64, best first;
         scores (B, k) float32 = sum of log-probabilities).  The whole search runs on the device: per token one
         expansion launch (tnt_beam_topk_f32) and row gathers of the LSTM state by parent beam; the paths are
-        back-tracked on the host at the end.  Restated by oracle.models.LcNIC.beam_search."""
+        back-tracked on the host at the end.  Restated by oracle.models.LcNIC.beam_search.
+        ``length_penalty`` > 0 reorders the k results by score / ((5 + L) / 6) ** length_penalty and returns that key as
+        the scores (model_base.length_normalise); the search itself is unchanged."""
+        length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
         start = np.asarray(start_seq).reshape(-1)
@@ -1345,4 +1350,6 @@ class NIC(ModelBase):
                 for i in range(max_len - 1, -1, -1):
                     seqs[b, r, i] = tok[i, row]
                     row = par[i, row]
+        if length_penalty > 0:
+            return length_normalise(seqs, final, end_id, length_penalty)
         return seqs, final

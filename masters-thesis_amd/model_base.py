@@ -40,6 +40,47 @@ def check_sampling(top_k, top_p, temperature):
     return int(top_k), p, t
 
 
+def check_length_penalty(length_penalty):
+    """host validation of beam search's length_penalty: a finite number >= 0.  Returns it as a float; ValueError
+    otherwise."""
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float, np.integer, np.floating)):
+        raise ValueError(f"length_penalty must be a finite number >= 0, got {length_penalty!r}")
+    lp = float(length_penalty)
+    if not (np.isfinite(lp) and lp >= 0.0):
+        raise ValueError(f"length_penalty must be a finite number >= 0, got {length_penalty!r}")
+    return lp
+
+
+def check_beam(beam_width, max_len, end_id, length_penalty, V):
+    """host validation of beam search's arguments: beam_width an int in [1, 16] (tnt_beam_step_f32's limit), max_len an
+    int >= 1, end_id an int in [-1, V) (-1: never ends), length_penalty as check_length_penalty.  Returns
+    (beam_width, max_len, end_id, length_penalty); ValueError otherwise."""
+    def is_int(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+    if not is_int(beam_width) or not 1 <= beam_width <= 16:
+        raise ValueError(f"beam_width must be an int in [1, 16], got {beam_width!r}")
+    if not is_int(max_len) or max_len < 1:
+        raise ValueError(f"max_len must be an int >= 1, got {max_len!r}")
+    if not is_int(end_id) or not -1 <= end_id < V:
+        raise ValueError(f"end_id must be an int in [-1, {V}) (-1: no end token), got {end_id!r}")
+    return int(beam_width), int(max_len), int(end_id), check_length_penalty(length_penalty)
+
+
+def length_normalise(seqs, scores, end_id, length_penalty):
+    """Length normalisation of beam search's k finished results per sample (seqs (B, k, max_len), scores (B, k), best
+    first): the results are reordered by the key  score / ((5 + L) / 6) ** length_penalty, computed in float64, where L
+    is the number of tokens up to and including the first end_id (max_len if there is none).  Ties keep the search's
+    rank order.  Returns (seqs, key as float32).  length_penalty = 0: the key is the raw sum, the order unchanged."""
+    seqs = np.asarray(seqs)
+    B, k, T = seqs.shape
+    hit = seqs == end_id
+    L = np.where(hit.any(axis=2), hit.argmax(axis=2) + 1, T)
+    key = np.asarray(scores, np.float32).astype(np.float64) / ((5.0 + L) / 6.0) ** float(length_penalty)
+    order = np.argsort(-key, axis=1, kind="stable")
+    return (np.take_along_axis(seqs, order[:, :, None], axis=1),
+            np.take_along_axis(key, order, axis=1).astype(np.float32))
+
+
 def interleave_gates(w, U):
     """keras [.., 4U] (i,f,c~,o blocks) -> kernel layout [.., U, 4]."""
     w = np.asarray(w)

@@ -19,7 +19,7 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM, S_SAMPLE, check_sampling)
+                         BN_MOMENTUM, S_SAMPLE, check_sampling, check_beam, length_normalise)
 from .ops import ACT_LEAKY
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -657,6 +657,24 @@ class NIC(ModelBase):
         return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
                 probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
 
+    def _decode_encode(self, B):
+        """the inference encoder (dense_img, BatchNorm / LayerNorm) and the feature LSTM step of a decode over the staged
+        B rows: the state after the feature step is Hs[1], Cs[1]"""
+        be, a = self.be, self.arena
+        N, U, E = self.N, self.U, self.E
+        self.gemm_sk(self.x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
+                     pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
+        if self.norm == "batch":
+            be.batchnorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.mov_mean, self.mov_var,
+                             self.Xin, self.xhat, self.inv_std, B, E, E, False, BN_EPS, BN_MOMENTUM, self.work)
+        else:
+            be.layernorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.Xin, self.xhat,
+                             self.inv_std, B, E, E, BN_EPS)
+        xz = self.XZ[:B]
+        self.gemm_sk(self.Xin, a.p("lstm/kernel"), xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
+        be.lstm_step_fwd(xz, self.Hs[0], self.Cs[0], a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None,
+                         self.Hs[1], self.Cs[1], None, self.gates[0], B, U)
+
     def _decode(self, img_input, a0, c0, start_seq, max_len, filt):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
         sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None)"""
@@ -684,20 +702,11 @@ class NIC(ModelBase):
             step_buf = self._sample_step_word(filt[3])
 
         def run():
-            self.gemm_sk(self.x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
-                         pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
-            if self.norm == "batch":
-                be.batchnorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.mov_mean, self.mov_var,
-                                 self.Xin, self.xhat, self.inv_std, B, E, E, False, BN_EPS, BN_MOMENTUM, self.work)
-            else:
-                be.layernorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.Xin, self.xhat,
-                                 self.inv_std, B, E, E, BN_EPS)
+            self._decode_encode(B)
             Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
             xz, emb = self.XZ[:B], self.Xin[B:2 * B]
             h = [self.Hs[0], self.Hs[1]]
             c = [self.Cs[0], self.Cs[1]]
-            self.gemm_sk(self.Xin, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-            be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, None, 0, 0, None, h[1], c[1], None, self.gates[0], B, U)
             cur = 1
             out = self.Out[0]
             prev = words
@@ -722,3 +731,77 @@ class NIC(ModelBase):
         else:
             self._run_captured(("sample",) + key + tuple(filt[:3]), run)
         return probs_all, ids
+
+    def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
+                    units=None, tokenizer=None):
+        """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches
+        it): log-probability beam search of width ``beam_width`` with greedy_predict's step, whose Keras mask rule it
+        keeps (a 0 fed back masks the next LSTM step); at step 0 the k beams of a sample are copies and only beam 0
+        counts; a beam that emits ``end_id`` (-1: never) is finished and pads with 0.  ``length_penalty`` > 0 reorders
+        the k results by score / ((5 + L) / 6) ** length_penalty (model_base.length_normalise).
+        The encoder and the feature step run once on the B rows; their state is gathered to the B*k beam rows.  Then
+        per token: Embedding gather, input projection, LSTM step, head GEMM, softmax, and one tnt_beam_step_f32 launch
+        (expansion + reorder of the state by parent into the other state buffer).  The loop is captured and replayed
+        like greedy_predict, over static buffers of its own per (B, k, max_len, end_id); the paths are back-tracked on
+        the host from one copy of the parents / tokens.
+        Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
+        length-normalised key)."""
+        k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
+        be, a = self.be, self.arena
+        start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
+        B = start.shape[0]
+        cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
+        self._stage_inputs((img_input, cap, a0, c0))
+        U, E, V, ldV = self.U, self.E, self.V, self.ldV
+        Bk = B * k
+        key = (B, k, max_len, end_id)
+        bufs = self.__dict__.setdefault("_beam_bufs", {})
+        if key not in bufs:
+            dev, i32, f = self.device, torch.int32, self._f
+            init = f(B, k)
+            init[:, 1:] = -1e30                    # step 0: the k beams of a sample are copies, only beam 0 counts
+            bufs[key] = dict(
+                rep=torch.arange(B, dtype=i32, device=dev).repeat_interleave(k).view(Bk, 1),
+                start=torch.zeros(Bk, 1, dtype=i32, device=dev), init=init.view(Bk),
+                score=f(2, Bk), fin=f(2, Bk, dtype=i32), pt=f(2, max_len, Bk, dtype=i32),
+                h=f(2, Bk, U), c=f(2, Bk, U), emb=f(Bk, E), xz=f(Bk, U, 4), out=f(Bk, U), gates=f(Bk, U, 4),
+                probs=f(Bk, ldV))
+        bb = bufs[key]
+        bb["start"].copy_(start.repeat_interleave(k).view(Bk, 1))
+        bb["score"][0].copy_(bb["init"])
+        bb["fin"][0].zero_()
+        score, fin, parents, tokens = bb["score"], bb["fin"], bb["pt"][0], bb["pt"][1]
+        h, c, emb, xz, out, probs = bb["h"], bb["c"], bb["emb"], bb["xz"], bb["out"], bb["probs"]
+
+        def run():
+            self._decode_encode(B)
+            Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
+            # the B rows' state after the feature step -> the B*k beam rows (row gather b*k + j <- b)
+            be.embedding_fwd(self.Hs[1], bb["rep"], h[0], Bk, 1, U, U, B)
+            be.embedding_fwd(self.Cs[1], bb["rep"], c[0], Bk, 1, U, U, B)
+            for i in range(max_len):
+                tok = bb["start"] if i == 0 else tokens[i - 1].view(Bk, 1)
+                be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, Bk, 1, E, E, V)
+                self.gemm_sk(emb, Wl, xz, Bk, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
+                be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, tok if i > 0 else None, 1, 0, None,
+                                 h[1], c[1], out, bb["gates"], Bk, U)
+                self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, Bk, V, U, U, ldV, ldV,
+                             bias=a.p("time_distributed_softmax/bias"))
+                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
+                cur, nxt = i & 1, (i & 1) ^ 1
+                # expansion, and the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]
+                be.beam_step(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
+                             fin[nxt], h[1], c[1], U, U, h[0], c[0])
+        self._run_captured(("beam",) + key, run)
+        pt = bb["pt"].cpu().numpy()
+        final = score[max_len & 1].cpu().numpy().reshape(B, k)
+        par, tok = pt[0], pt[1]
+        seqs = np.zeros((max_len, Bk), np.int64)
+        row = np.arange(Bk)
+        for i in range(max_len - 1, -1, -1):           # back-track every beam at once
+            seqs[i] = tok[i, row]
+            row = par[i, row]
+        seqs = seqs.T.reshape(B, k, max_len)
+        if length_penalty > 0:
+            return length_normalise(seqs, final, end_id, length_penalty)
+        return seqs, final

@@ -596,6 +596,14 @@ class HipBackend:
         self._call(self.lib.tnt_beam_topk_f32, "tnt_beam_topk_f32", _p(probs), _p(score_in), _p(fin_in), B, V, ld, k, end_id,
                    _p(score_out), _p(parent), _p(token), _p(fin_out), self._s())
 
+    def beam_step(self, probs, ld, score_in, fin_in, B, V, k, end_id, score_out, parent, token, fin_out, h_in, c_in, ldh,
+                  U, h_out, c_out):
+        """beam_topk plus the reorder of the LSTM state by parent in one launch (tnt_beam_step_f32; definition in
+        include/tnt_hip.h); U = 0 skips the reorder"""
+        self._call(self.lib.tnt_beam_step_f32, "tnt_beam_step_f32", _p(probs), ld, _p(score_in), _p(fin_in), B, V, k, end_id,
+                   _p(score_out), _p(parent), _p(token), _p(fin_out), _p(h_in), _p(c_in), ldh, U, _p(h_out), _p(c_out),
+                   self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
