@@ -614,6 +614,36 @@ int32_t tnt_greedy_feedback_f32(const float* logits, int32_t ld, int32_t V, cons
                                 float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B, float rate,
                                 uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev,
                                 int32_t lwidth, int32_t lcol0, void* stream);
+/* Scheduled sampling (Bengio et al. 2015) for the dense caption model's training step (nic.NIC(scheduled_sampling=...)),
+ * one launch per LSTM step, no host sync; restated by tests/ss_oracle.py.  This library's definition:
+ *  - Schedule.  i = *counter (int64: the updates applied so far, the model's adam_t) and sched[0..3) (float64) are
+ *    read on the device when the launch runs, so a recorded plan or a hipGraph replays with the live values.  kind 0,
+ *    linear(p0 = sched[0], slope = sched[1], p_max = sched[2]): p = clip(p0 + slope * i, 0, p_max); kind 1,
+ *    inverse_sigmoid(k = sched[0], p_max = sched[2]): p = p_max * (1 - k / (k + exp(i / k))).  p is computed in float64
+ *    and rounded once to float32.  The parameters are the caller's to validate (finite, p0 and p_max in [0, 1], k >= 1:
+ *    model_base.ScheduledSampling).
+ *  - Step.  LSTM step t = j + 1 consumes token position j and its logits row predicts position j + 1; this launch is the
+ *    one for col = j + 1 (1 <= col < T), logits [B][ld] (V valid columns) being step t's rows.
+ *  - Coin.  Row b feeds the model's token iff element b of the Philox stream (seed, coin_site, step + *step_dev) is
+ *    dropped at rate p by tnt_keep's rule: (w >> 8) < ceil(p * 2^24).  p = 0 never feeds the model's token, p = 1 always.
+ *  - Model token.  mode 0 (greedy): the argmax of the logits row, ties to the lowest index, NaN never wins (the rule of
+ *    tnt_greedy_feedback_f32).  mode 1 (sample): the draw of tnt_sample_rows_f32 on the logits at temperature 1, with the
+ *    uniform of element b of the stream (seed, draw_site, step + *step_dev); the same id as that kernel.  The id is always
+ *    in [0, V) (a row without a winner gives 0).
+ *  - Write-back.  A model row writes its id to fed[b*T + col]; a ground-truth row leaves fed as it is and uses fed[b*T + col]
+ *    (clamped to [0, V)).  text[b] = table[id] through the LSTM input mask of tnt_greedy_feedback_f32 (site, lwidth, lcol0,
+ *    rate; the teacher-forced mask of (b, col) is lwidth = T*E, lcol0 = col*E), xz[b][0..N) = text[b] . w (no bias), for
+ *    every row; the projection is the same code, and the same bits, as tnt_greedy_feedback_f32's.
+ *  - Rows whose coin picks the ground truth do not read their logits.  Workgroups of 16 rows x 128 columns; deterministic,
+ *    no scratch memory.
+ * TNT_BADARG for the conditions of tnt_greedy_feedback_f32, col < 1, null pointers, an unknown kind or mode. */
+int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
+                                   const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T, int32_t col,
+                                   float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B, float rate,
+                                   uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev,
+                                   int32_t lwidth, int32_t lcol0, int32_t kind, int32_t mode, const double* sched,
+                                   const int64_t* counter, uint32_t coin_site, uint32_t draw_site,
+                                   void* stream);
 /* out[0] = scale * sum_i x[i]  (fixed-order, one workgroup). */
 /* Categorical sampling per row (tf.random.categorical(logits / temperature, 1): ThinkAndTell/evaluate.py:223,278;
  * lc_NIC.sample_choice lc_NIC.py:571-575 samples from log(probs)).  x: logits (from_logits=1) or probabilities.

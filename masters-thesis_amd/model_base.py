@@ -21,7 +21,78 @@ from .optimizers import Adam
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
 S_ATTN, S_LSTM_IN, S_LSTM_OUT = 16, 48, 80
 S_SAMPLE = 112          # + decode position: categorical-sampling stream of sample_predict
+# + token position j (< 32): scheduled sampling's coin and draw streams (nic.NIC(scheduled_sampling=...)); after
+# lc_nic.S_NOUT = 144 + step
+S_SS_COIN, S_SS_DRAW = 176, 208
+SS_MAX_POSITIONS = 32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
+
+
+class ScheduledSampling:
+    """Scheduled sampling (Bengio et al. 2015) for nic.NIC's train_step; the definition is tnt_scheduled_feedback_f32's
+    (include/tnt_hip.h).  At each step, each caption row is fed the model's own token with probability p, the ground
+    truth otherwise; p grows with i, the updates applied so far (the model's device counter adam_t):
+      ScheduledSampling.linear(p0, slope, p_max=1.0):  p = clip(p0 + slope * i, 0, p_max)   (constant p: slope = 0)
+      ScheduledSampling.inverse_sigmoid(k, p_max=1.0): p = p_max * (1 - k / (k + exp(i / k))), k >= 1
+    mode "greedy" feeds the argmax of the step's logits, "sample" a categorical draw from them (temperature 1).
+    p is computed in float64 and rounded to float32, on the device by the kernel and on the host by ``p(i)``.
+    Bad parameters raise ValueError here, before any launch."""
+
+    KINDS = ("linear", "inverse_sigmoid")
+    MODES = ("greedy", "sample")
+
+    def __init__(self, kind, mode="greedy", p0=0.0, slope=0.0, p_max=1.0, k=1.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"scheduled sampling kind must be one of {self.KINDS}, got {kind!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"scheduled sampling mode must be one of {self.MODES}, got {mode!r}")
+
+        def num(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                raise ValueError(f"scheduled sampling {name} must be a finite number, got {v!r}")
+            return float(v)
+        p0, slope, p_max, k = num("p0", p0), num("slope", slope), num("p_max", p_max), num("k", k)
+        if not 0.0 <= p_max <= 1.0:
+            raise ValueError(f"scheduled sampling p_max must be in [0, 1], got {p_max!r}")
+        if kind == "linear" and not 0.0 <= p0 <= 1.0:
+            raise ValueError(f"scheduled sampling p0 must be in [0, 1], got {p0!r}")
+        if kind == "inverse_sigmoid" and not k >= 1.0:
+            raise ValueError(f"scheduled sampling k must be >= 1, got {k!r}")
+        self.kind, self.mode, self.p0, self.slope, self.p_max, self.k = kind, mode, p0, slope, p_max, k
+
+    @classmethod
+    def linear(cls, p0, slope, p_max=1.0, mode="greedy"):
+        return cls("linear", mode, p0=p0, slope=slope, p_max=p_max)
+
+    @classmethod
+    def inverse_sigmoid(cls, k, p_max=1.0, mode="greedy"):
+        return cls("inverse_sigmoid", mode, k=k, p_max=p_max)
+
+    @property
+    def kind_id(self):
+        return self.KINDS.index(self.kind)
+
+    @property
+    def mode_id(self):
+        return self.MODES.index(self.mode)
+
+    def params(self):
+        """the kernel's float64 parameter triple"""
+        return (self.p0, self.slope, self.p_max) if self.kind == "linear" else (self.k, 0.0, self.p_max)
+
+    def p(self, i):
+        """p after i updates, as the kernel computes it: float64, rounded to float32"""
+        i = float(int(i))
+        if self.kind == "linear":
+            return np.float32(min(max(self.p0 + self.slope * i, 0.0), self.p_max))
+        with np.errstate(over="ignore"):
+            e = float(np.exp(np.float64(i / self.k)))
+        return np.float32(self.p_max * (1.0 - self.k / (self.k + e)))
+
+    def __repr__(self):
+        if self.kind == "linear":
+            return f"ScheduledSampling.linear(p0={self.p0}, slope={self.slope}, p_max={self.p_max}, mode={self.mode!r})"
+        return f"ScheduledSampling.inverse_sigmoid(k={self.k}, p_max={self.p_max}, mode={self.mode!r})"
 
 
 def check_sampling(top_k, top_p, temperature):

@@ -19,7 +19,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM, S_SAMPLE, check_sampling, check_beam, length_normalise)
+                         BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, ScheduledSampling, check_sampling,
+                         check_beam, length_normalise)
 from .ops import ACT_LEAKY
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -31,7 +32,7 @@ def _r4(n):
 
 class NIC(ModelBase):
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
-                 dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", **kw):
+                 dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, **kw):
         super().__init__(**kw)
         self.N, self.U, self.E, self.V, self.max_length = int(input_size), int(units), int(embedding_dim), int(vocab_size), int(max_length)
         self.r_in, self.r_feat, self.r_lstm = float(dropout_input), float(dropout), float(dropout_lstm)
@@ -42,6 +43,16 @@ class NIC(ModelBase):
         if self.U % 16:
             raise ValueError("units must be a multiple of 16 (LSTM step kernel tile)")
         N, U, E, V = self.N, self.U, self.E, self.V
+        # scheduled_sampling (model_base.ScheduledSampling): train_step feeds each caption row the model's own token with
+        # the schedule's probability (tnt_scheduled_feedback_f32); None keeps the teacher-forced step
+        if scheduled_sampling is not None:
+            if not isinstance(scheduled_sampling, ScheduledSampling):
+                raise ValueError("scheduled_sampling must be None or a model_base.ScheduledSampling, got "
+                                 f"{scheduled_sampling!r}")
+            if E % 4 or E > 1016:
+                raise ValueError(f"scheduled sampling needs embedding_dim % 4 == 0 and <= 1016 "
+                                 f"(tnt_scheduled_feedback_f32), got {E}")
+        self.scheduled_sampling = scheduled_sampling
         self.ldx, self.ldV = _r4(N), _r4(V)
         self.layers_spec = OrderedDict([
             ("dense_img", ["kernel", "bias"]),
@@ -70,6 +81,8 @@ class NIC(ModelBase):
         a.finalize()
         self.mov_mean, self.mov_var = self._f(E), torch.ones(E, dtype=torch.float32, device=self.device)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if scheduled_sampling is not None:      # the schedule's parameters, read by the kernel (float64, device)
+            self.ss_sched = torch.tensor(scheduled_sampling.params(), dtype=torch.float64, device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
 
@@ -223,7 +236,8 @@ class NIC(ModelBase):
                 and not self._sync_bn_on())        # synchronised BatchNorm: the statistics leave the kernel for a collective
 
     # ------------------------------------------------------------------ forward
-    def _forward(self, B, T, training):
+    def _forward(self, B, T, training, ss=False):
+        """``ss``: the scheduled-sampling training forward (_forward_ss) behind the Embedding gather"""
         be, a = self.be, self.arena
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
         R1 = (T + 1) * B
@@ -295,6 +309,9 @@ class NIC(ModelBase):
             if drop_l:       # LSTM(dropout=...) masks the layer input, one mask per call
                 be.dropout(self.Xin[B:], self.Xin_d[B:], T * B, E, E, B, E, 0, self.r_lstm, sd, S_LSTM_IN + 1, 0, ds)
         self._xin_used = xin
+        if ss:
+            self._forward_ss(B, T, xin, drop_l)
+            return
         # input projection of all T+1 steps as ONE epilogue-free GEMM; the LSTM bias is added inside the step kernel
         if getattr(self, "fused_xproj", False) and hasattr(be, "gemm_fused") and be.gemm_fused_cfg(R1, 4 * U, E) > 0:
             be.gemm_fused(xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U)
@@ -317,6 +334,33 @@ class NIC(ModelBase):
                                  self.Out[t - 1], self.gates[t], B, U, xz_bias=bl)
         self.gemm_sk(self.Out, a.p("time_distributed_softmax/kernel"), self.logits, T * B, V, U, U, ldV, ldV,
                 bias=a.p("time_distributed_softmax/bias"))                         # NIC.py:143
+
+    def _forward_ss(self, B, T, xin, drop_l):
+        """The scheduled-sampling forward behind the teacher-forced Embedding gather: XZ of the feature and start-token
+        rows, then per LSTM step t the per-step LSTM kernel (gates, Hs, Cs, Out as the per-step fallback writes them), the
+        B-row head GEMM into the step's logits rows, and (t <= T-1) tnt_scheduled_feedback_f32, which decides token
+        position t of every row, writes a fed token into cap, its masked Embedding row into xin and its projection into
+        XZ for step t+1.  The loss, its targets (tgt) and the whole backward are the teacher-forced ones, over the fed ids."""
+        be, a, ss = self.be, self.arena, self.scheduled_sampling
+        U, E, V, ldV = self.U, self.E, self.V, self.ldV
+        Wl, Ur, bl = a.p("lstm/kernel"), a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
+        Wo, bo = a.p("time_distributed_softmax/kernel"), a.p("time_distributed_softmax/bias")
+        table = a.p("emb_text/embeddings")
+        self.gemm_sk(xin, Wl, self.XZ, 2 * B, 4 * U, E, E, 4 * U, 4 * U)
+        be.lstm_step_fwd(self.XZ[:B], self.Hs[0], self.Cs[0], Ur, None, None, 0, None, 0, 0, None, self.Hs[1],
+                         self.Cs[1], None, self.gates[0], B, U, xz_bias=bl)
+        rate = self.r_lstm if drop_l else 0.0
+        for t in range(1, T + 1):
+            be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, self.cap, T,
+                             t - 1, self.Out[t - 2] if t > 1 else None, self.Hs[t + 1], self.Cs[t + 1],
+                             self.Out[t - 1], self.gates[t], B, U, xz_bias=bl)
+            logits = self.logits[(t - 1) * B:t * B]
+            self.gemm_sk(self.Out[t - 1], Wo, logits, B, V, U, U, ldV, ldV, bias=bo)
+            if t < T:
+                be.scheduled_feedback(logits, ldV, V, table, E, Wl, 4 * U, 4 * U, self.cap, T, t, xin[(t + 1) * B:], E,
+                                      self.XZ[(t + 1) * B:], 4 * U, B, rate, self.seed, S_LSTM_IN + 1, 0, self.drop_step,
+                                      T * E, t * E, ss.kind_id, ss.mode_id, self.ss_sched, self.adam_t,
+                                      S_SS_COIN + t - 1, S_SS_DRAW + t - 1)
 
     def _loss_metrics(self, B, T, want_grad):
         """softmax + per-timestep mean CE / accuracy summed over T and divided by T
@@ -560,7 +604,7 @@ class NIC(ModelBase):
 
     # ------------------------------------------------------------------ steps
     def _train_graph(self, B, T):
-        self._forward(B, T, True)
+        self._forward(B, T, True, ss=self.scheduled_sampling is not None)
         self._loss_metrics(B, T, True)
         self._backward(B, T)
 
@@ -586,7 +630,12 @@ class NIC(ModelBase):
         """NIC.train_step (NIC.py:198-252): data = ((betas, cap, a0, c0), target)."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
+        if self.scheduled_sampling is not None and self.grad_sync is not None:
+            raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
         B, T = self._stage_batch(data[0], data[1], self.N)
+        if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
+            raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
+                             f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
         self._sync_lr()
         self._enc_grad_stale = None
         ring = False

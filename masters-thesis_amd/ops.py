@@ -313,6 +313,16 @@ class HipBackend:
                    _p(fed), T, col, _p(text), ldt, _p(xz), ldz, B, float(rate), int(seed), int(site), int(step), _p(step_dev),
                    int(lwidth), int(lcol0), self._s())
 
+    def scheduled_feedback(self, logits, ld, V, table, E, w, ldw, N, fed, T, col, text, ldt, xz, ldz, B, rate, seed, site,
+                           step, step_dev, lwidth, lcol0, kind, mode, sched, counter, coin_site, draw_site):
+        """one scheduled-sampling step (tnt_scheduled_feedback_f32; definition in include/tnt_hip.h): per row a coin at the
+        schedule's p (parameters ``sched`` float64[3] and ``counter`` read on the device) between fed[b*T + col] and the model's token (argmax or draw),
+        written back to fed, text[b] = its Embedding row through the LSTM input mask, xz[b] = text[b] . w"""
+        self._call(self.lib.tnt_scheduled_feedback_f32, "tnt_scheduled_feedback_f32", _p(logits), ld, V, _p(table), E, _p(w),
+                   ldw, N, _p(fed), T, col, _p(text), ldt, _p(xz), ldz, B, float(rate), int(seed), int(site), int(step),
+                   _p(step_dev), int(lwidth), int(lcol0), int(kind), int(mode), _p(sched), _p(counter),
+                   int(coin_site), int(draw_site), self._s())
+
     def enc_tail_fwd(self, y, gamma, beta, mov_mean, mov_var, out, xhat, inv_std, rows, C, ldo, training, eps, momentum,
                      r_feat, r_lstm, seed, site_feat, site_lstm, step_dev=None):
         self._call(self.lib.tnt_enc_tail_fwd_f32, "tnt_enc_tail_fwd_f32", _p(y), _p(gamma), _p(beta), _p(mov_mean), _p(mov_var), _p(out), _p(xhat),
