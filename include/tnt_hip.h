@@ -644,6 +644,36 @@ int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, int32_t V, c
                                    int32_t lwidth, int32_t lcol0, int32_t kind, int32_t mode, const double* sched,
                                    const int64_t* counter, uint32_t coin_site, uint32_t draw_site,
                                    void* stream);
+/* Scheduled sampling for the attention caption model's training step (lc_nic.NIC(scheduled_sampling=...)); restated by
+ * tests/ss_att_oracle.py.  tnt_scheduled_feedback_f32 with one more mask: the gathered row table[id] is multiplied first by
+ * the keep / scale of element b*lwidth_t + lcol0_t + e of the stream (seed, site_t, step + *step_dev) at rate_t, then by
+ * the LSTM input mask of tnt_scheduled_feedback_f32 (rate, site, lwidth, lcol0).  Both are tnt_keep's rule, each a
+ * multiplication by 1 / (1 - rate) where kept and 0 where dropped, in this order: the order and the arithmetic of
+ * tnt_embedding_fwd_drop2_f32, so a row gets the same bits as that kernel's row (b, col) when
+ *   rate_t = the text Dropout's rate, site_t = its site, lwidth_t = T*E, lcol0_t = col*E  (element (b*T + col)*E + e of the
+ *     logical (B, T, E) caption tensor), and
+ *   rate = the LSTM's input rate, site = site2 + col, lwidth = lwidth2, lcol0 = lcol0_2  (the per-call mask of step col).
+ * The model's definition, for LSTM step t (token position t; its logits row predicts position t + 1) and col = 1 .. T-1:
+ *  - p from the live counter (float64, rounded once to float32); row b's coin is element b of (seed, S_SS_COIN + col - 1,
+ *    step + drop_step) and it feeds the model's token iff (w >> 8) < ceil(p * 2^24);
+ *  - the model's token is the argmax of step col-1's logits (ties to the lowest index, NaN never wins), or in sample mode
+ *    tnt_sample_rows_f32's draw at temperature 1 on (seed, S_SS_DRAW + col - 1, step + drop_step);
+ *  - otherwise the row keeps cap[b, col] (clamped to [0, V)), not written back, its logits not read;
+ *  - text = table[id] x the text Dropout (S_TEXT, lwidth_t = T*E, lcol0_t = col*E) x the LSTM input mask (S_LSTM_IN + col,
+ *    lwidth = D + E, lcol0 = D); xz = text . W_lstm[D:] (no bias), the projection code of tnt_scheduled_feedback_f32.
+ * Everything else in the step is the teacher-forced step applied to the fed ids (attention, LSTM-output and output Dropouts,
+ * metric, loss, backward, the Embedding gradient scattered to the fed ids).  At p = 0 it is the teacher-forced step (to
+ * float32 rounding: the forward runs per step); at p = 1 it is not call_naive_attention, whose Dropouts differ.
+ * rate_t = 0 gives the bits of tnt_scheduled_feedback_f32.  No scratch memory.
+ * TNT_BADARG for the conditions of tnt_scheduled_feedback_f32, rate_t outside [0, 1), and (rate_t > 0) lwidth_t or
+ * lcol0_t not a multiple of 4, lcol0_t < 0 or lcol0_t + E > lwidth_t. */
+int32_t tnt_scheduled_feedback2_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
+                                    const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T, int32_t col,
+                                    float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B, float rate,
+                                    uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev,
+                                    int32_t lwidth, int32_t lcol0, int32_t kind, int32_t mode, const double* sched,
+                                    const int64_t* counter, uint32_t coin_site, uint32_t draw_site, float rate_t,
+                                    uint32_t site_t, int32_t lwidth_t, int32_t lcol0_t, void* stream);
 /* out[0] = scale * sum_i x[i]  (fixed-order, one workgroup). */
 /* Categorical sampling per row (tf.random.categorical(logits / temperature, 1): ThinkAndTell/evaluate.py:223,278;
  * lc_NIC.sample_choice lc_NIC.py:571-575 samples from log(probs)).  x: logits (from_logits=1) or probabilities.

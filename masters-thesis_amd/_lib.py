@@ -76,6 +76,8 @@ SIGNATURES = {
                                 I32, I32, P],
     "tnt_scheduled_feedback_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
                                    I32, I32, I32, I32, P, P, U32, U32, P],
+    "tnt_scheduled_feedback2_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
+                                    I32, I32, I32, I32, P, P, U32, U32, F32, U32, I32, I32, P],
     "tnt_enc_tail_fwd_f32": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, F32, F32, F32, F32, U64, U32, U32, P, P],
     "tnt_enc_tail_bwd_f32": [P, P, P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, U64, U32, U32, P, P],
     "tnt_enc_tail_bwd_drop_f32": [P, P, P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, U64, U32, U32, P, P, I32, I32, I32, I32,

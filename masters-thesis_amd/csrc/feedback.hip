@@ -42,11 +42,19 @@ __device__ __forceinline__ void gf_take(float v, int j, float& best, int& bi) {
   if (v > best || (v == best && j < bi)) { best = v; bi = j; }
 }
 
-// 2. the 16 rows' Embedding rows (id s_id[rr]) through the LSTM input mask of step col (rows_per_site = B: local row b,
-// element b lwidth + lcol0 + j) -> LDS image s_text [16][E + 4]; the lead workgroup of a row tile also stores them to text.
-// nthr threads, this one tid.  Elementwise: the values do not depend on nthr.
-__device__ __forceinline__ void gf_gather(const GfArgs& a, const int* s_id, float* s_text, int row0, bool lead, int tid,
-                                          int nthr) {
+// The mask in front of the LSTM input mask (tnt_scheduled_feedback2_f32: the Embedding Dropout): row b, element
+// b lwidth + lcol0 + j of the stream (seed, site, step + *step_dev); rate 0: none.
+struct GfMask {
+  float rate, scale; uint32_t site; int lwidth, lcol0;
+};
+
+// 2. the 16 rows' Embedding rows (id s_id[rr]) through [kText: the mask tm, then] the LSTM input mask of step col
+// (rows_per_site = B: local row b, element b lwidth + lcol0 + j) -> LDS image s_text [16][E + 4]; the lead workgroup of a
+// row tile also stores them to text.  nthr threads, this one tid.  Elementwise: the values do not depend on nthr.  The
+// two masks are applied in the order and with the arithmetic of tnt_embedding_fwd_drop2_f32 (emb_fwd_drop_kernel).
+template <bool kText>
+__device__ __forceinline__ void gf_gather(const GfArgs& a, const GfMask& tm, const int* s_id, float* s_text, int row0,
+                                          bool lead, int tid, int nthr) {
   const uint32_t step = a.step + (a.step_dev ? a.step_dev[0] : 0u);
   const int e4 = a.E >> 2, lds = a.E + 4;
   for (int c = tid; c < GF_ROWS * e4; c += nthr) {
@@ -54,6 +62,12 @@ __device__ __forceinline__ void gf_gather(const GfArgs& a, const int* s_id, floa
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < a.B) {
       v = *reinterpret_cast<const float4*>(a.table + (long)s_id[rr] * a.E + j);
+      if (kText && tm.rate > 0.f) {
+        bool k[4];
+        tnt_keep4((uint64_t)r * (uint64_t)tm.lwidth + (uint64_t)(tm.lcol0 + j), tm.rate, a.seed, tm.site, step, k);
+        v = make_float4(k[0] ? v.x * tm.scale : 0.f, k[1] ? v.y * tm.scale : 0.f, k[2] ? v.z * tm.scale : 0.f,
+                        k[3] ? v.w * tm.scale : 0.f);
+      }
       if (a.rate > 0.f) {
         bool k[4];
         tnt_keep4((uint64_t)r * (uint64_t)a.lwidth + (uint64_t)(a.lcol0 + j), a.rate, a.seed, a.site, step, k);
@@ -179,7 +193,7 @@ __global__ __launch_bounds__(256) void greedy_feedback_kernel(GfArgs a) {
     a.fed[(long)(row0 + threadIdx.x) * a.T + a.col] = s_id[threadIdx.x];
 
   // ---- 2. gather + the LSTM input mask; 3. text . w
-  gf_gather(a, s_id, s_text, row0, blockIdx.y == 0, threadIdx.x, 256);
+  gf_gather<false>(a, GfMask{}, s_id, s_text, row0, blockIdx.y == 0, threadIdx.x, 256);
   __syncthreads();
   gf_project(a, s_text, row0, blockIdx.y * GF_COLS + wave * 16 + (lane & 15), lane);
 }
@@ -195,6 +209,8 @@ __global__ __launch_bounds__(256) void greedy_feedback_kernel(GfArgs a) {
 //      tnt_sample_rows_f32 at temperature 1 (sample): its 256 contiguous chunks, 4 per lane, the chunk sums in the same
 //      serial order, the serial prefix over them, the same target search -- the same id as that kernel;
 //   2., 3. gf_gather, gf_project.
+// tnt_scheduled_feedback2_f32 is the same kernel with the Embedding Dropout in front of the LSTM input mask (kText: the
+// attention model, whose teacher-forced text rows carry both masks); with its rate 0 it computes the bits of the first.
 constexpr int SF_WAVES = 8;
 constexpr int SF_COLS = SF_WAVES * 16;
 
@@ -204,6 +220,7 @@ struct SfArgs {
   const double* sched;               // device [3]: linear p0, slope, p_max; inverse sigmoid k, -, p_max
   const int64_t* counter;            // updates applied so far (the model's adam_t)
   uint32_t coin_site, draw_site;
+  GfMask text;                       // kText only: the mask in front of the LSTM input mask
 };
 
 // p of the schedule at the live counter: float64, rounded once to float32 (model_base.scheduled_p restates it)
@@ -309,6 +326,7 @@ __device__ __forceinline__ int sf_sample_row(const float* x, int V, float u, flo
   return (pick >= 0 && pick < V) ? pick : 0;
 }
 
+template <bool kText>
 __global__ __launch_bounds__(SF_WAVES * 64) void scheduled_feedback_kernel(SfArgs sa) {
   const GfArgs& a = sa.g;
   extern __shared__ float4 gf_lds4[];
@@ -349,7 +367,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void scheduled_feedback_kernel(SfArg
   __syncthreads();
 
   // ---- 2. gather + the LSTM input mask; 3. text . w
-  gf_gather(a, s_id, s_text, row0, lead, threadIdx.x, SF_WAVES * 64);
+  gf_gather<kText>(a, sa.text, s_id, s_text, row0, lead, threadIdx.x, SF_WAVES * 64);
   __syncthreads();
   gf_project(a, s_text, row0, blockIdx.y * SF_COLS + wave * 16 + (lane & 15), lane);
 }
@@ -383,13 +401,14 @@ extern "C" int32_t tnt_greedy_feedback_f32(const float* logits, int32_t ld, int3
   return 0;
 }
 
-extern "C" int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
-                                              const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T,
-                                              int32_t col, float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B,
-                                              float rate, uint64_t seed, uint32_t site, uint32_t step,
-                                              const uint32_t* step_dev, int32_t lwidth, int32_t lcol0, int32_t kind,
-                                              int32_t mode, const double* sched, const int64_t* counter,
-                                              uint32_t coin_site, uint32_t draw_site, void* stream) {
+namespace {
+
+// argument checks and launch of both scheduled-sampling entry points (text_mask == nullptr: tnt_scheduled_feedback_f32)
+int32_t sf_launch(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E, const float* w, int32_t ldw,
+                  int32_t N, int32_t* fed, int32_t T, int32_t col, float* text, int32_t ldt, float* xz, int32_t ldz,
+                  int32_t B, float rate, uint64_t seed, uint32_t site, uint32_t step, const uint32_t* step_dev,
+                  int32_t lwidth, int32_t lcol0, int32_t kind, int32_t mode, const double* sched, const int64_t* counter,
+                  uint32_t coin_site, uint32_t draw_site, const GfMask* text_mask, void* stream) {
   if (B <= 0) return 0;
   if (V <= 0 || ld < V || !logits) return TNT_BADARG(2);
   if (E <= 0 || (E & 3) || E > GF_MAX_E || !tnt_aligned16(table)) return TNT_BADARG(5);
@@ -404,6 +423,11 @@ extern "C" int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, i
   if (mode != 0 && mode != 1) return TNT_BADARG(25);
   if (!sched) return TNT_BADARG(26);
   if (!counter) return TNT_BADARG(27);
+  if (text_mask) {
+    const GfMask& m = *text_mask;
+    if (!(m.rate >= 0.f && m.rate < 1.f)) return TNT_BADARG(30);
+    if (m.rate > 0.f && ((m.lwidth & 3) || (m.lcol0 & 3) || m.lcol0 < 0 || m.lcol0 + E > m.lwidth)) return TNT_BADARG(32);
+  }
   SfArgs sa;
   GfArgs& a = sa.g;
   a.logits = logits; a.ld = ld; a.V = V; a.table = table; a.E = E; a.w = w; a.ldw = ldw; a.N = N;
@@ -413,9 +437,39 @@ extern "C" int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, i
   a.vec = ((ld & 3) == 0 && tnt_aligned16(logits)) ? 1 : 0;
   sa.kind = kind; sa.mode = mode; sa.sched = sched; sa.counter = counter;
   sa.coin_site = coin_site; sa.draw_site = draw_site;
+  sa.text = text_mask ? *text_mask : GfMask{0.f, 1.f, 0u, 0, 0};
   const dim3 grid((B + GF_ROWS - 1) / GF_ROWS, (N + SF_COLS - 1) / SF_COLS);
   const size_t lds_bytes = (size_t)GF_ROWS * (E + 4) * sizeof(float);
-  hipLaunchKernelGGL(scheduled_feedback_kernel, grid, dim3(SF_WAVES * 64), lds_bytes, tnt_stream(stream), sa);
+  if (text_mask)
+    hipLaunchKernelGGL(scheduled_feedback_kernel<true>, grid, dim3(SF_WAVES * 64), lds_bytes, tnt_stream(stream), sa);
+  else
+    hipLaunchKernelGGL(scheduled_feedback_kernel<false>, grid, dim3(SF_WAVES * 64), lds_bytes, tnt_stream(stream), sa);
   TNT_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int32_t tnt_scheduled_feedback_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
+                                              const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T,
+                                              int32_t col, float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B,
+                                              float rate, uint64_t seed, uint32_t site, uint32_t step,
+                                              const uint32_t* step_dev, int32_t lwidth, int32_t lcol0, int32_t kind,
+                                              int32_t mode, const double* sched, const int64_t* counter,
+                                              uint32_t coin_site, uint32_t draw_site, void* stream) {
+  return sf_launch(logits, ld, V, table, E, w, ldw, N, fed, T, col, text, ldt, xz, ldz, B, rate, seed, site, step, step_dev,
+                   lwidth, lcol0, kind, mode, sched, counter, coin_site, draw_site, nullptr, stream);
+}
+
+extern "C" int32_t tnt_scheduled_feedback2_f32(const float* logits, int32_t ld, int32_t V, const float* table, int32_t E,
+                                               const float* w, int32_t ldw, int32_t N, int32_t* fed, int32_t T,
+                                               int32_t col, float* text, int32_t ldt, float* xz, int32_t ldz, int32_t B,
+                                               float rate, uint64_t seed, uint32_t site, uint32_t step,
+                                               const uint32_t* step_dev, int32_t lwidth, int32_t lcol0, int32_t kind,
+                                               int32_t mode, const double* sched, const int64_t* counter,
+                                               uint32_t coin_site, uint32_t draw_site, float rate_t, uint32_t site_t,
+                                               int32_t lwidth_t, int32_t lcol0_t, void* stream) {
+  const GfMask tm{rate_t, 1.0f / (1.0f - rate_t), site_t, lwidth_t, lcol0_t};
+  return sf_launch(logits, ld, V, table, E, w, ldw, N, fed, T, col, text, ldt, xz, ldz, B, rate, seed, site, step, step_dev,
+                   lwidth, lcol0, kind, mode, sched, counter, coin_site, draw_site, &tm, stream);
 }

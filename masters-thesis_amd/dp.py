@@ -426,7 +426,7 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
         raise NotImplementedError("data parallel training of the free-running decoder (teacher_forcing=False) is not "
                                   "supported: train it on one device")
     if getattr(model, "scheduled_sampling", None) is not None:
-        # nic.NIC(scheduled_sampling=...) has no data-parallel schedule either
+        # nic.NIC / lc_nic.NIC(scheduled_sampling=...) have no data-parallel schedule either
         raise NotImplementedError("data parallel training with scheduled sampling is not supported: train it on one device")
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank

@@ -23,8 +23,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
-                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, BN_EPS, BN_MOMENTUM, check_sampling, check_length_penalty,
-                         length_normalise)
+                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, BN_EPS, BN_MOMENTUM,
+                         ScheduledSampling, check_sampling, check_length_penalty, length_normalise)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -75,7 +75,7 @@ class NIC(ModelBase):
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
-                 teacher_forcing=True, **kw):
+                 teacher_forcing=True, scheduled_sampling=None, **kw):
         super().__init__(**kw)
         # teacher_forcing=False: __call__ / train_step / test_step / fit run lc_NIC.call_naive_attention (lc_NIC.py:175-221),
         # the decoder fed its own greedy predictions (call_naive_attention's docstring)
@@ -221,6 +221,12 @@ class NIC(ModelBase):
         self.mov_mean = [self._f(D) for _ in range(self.S + self.depth)]
         self.mov_var = [torch.ones(D, dtype=torch.float32, device=self.device) for _ in range(self.S + self.depth)]
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # scheduled_sampling (model_base.ScheduledSampling): train_step feeds each caption row the model's own token with the
+        # schedule's probability (tnt_scheduled_feedback2_f32, _forward_ss); None keeps the teacher-forced step
+        self.scheduled_sampling = scheduled_sampling
+        if scheduled_sampling is not None:
+            self._ss_check()
+            self.ss_sched = torch.tensor(scheduled_sampling.params(), dtype=torch.float64, device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
         if not self.teacher_forcing:
@@ -592,6 +598,75 @@ class NIC(ModelBase):
                                       "(use_layer_norm=True)")
         if self.Et % 4:
             raise NotImplementedError("the free-running decoder needs embedding_text % 4 == 0 (tnt_greedy_feedback_f32)")
+
+    def _ss_check(self):
+        """the combinations scheduled sampling is built for; anything else refuses instead of training another mode"""
+        ss = self.scheduled_sampling
+        if not isinstance(ss, ScheduledSampling):
+            raise ValueError(f"scheduled_sampling must be None or a model_base.ScheduledSampling, got {ss!r}")
+        if not self.teacher_forcing:
+            raise ValueError("scheduled_sampling is a teacher-forced curriculum: it cannot be combined with "
+                             "teacher_forcing=False (the free-running decoder)")
+        if self.S != 1:
+            raise NotImplementedError("scheduled sampling is a single-subject mode: n_subjects > 1 is not supported")
+        if self.use_layer_norm:
+            raise NotImplementedError("scheduled sampling is not built for the LayerNormLSTMCell (use_layer_norm=True)")
+        if self.Et % 4 or self.Et > 1016:
+            raise ValueError(f"scheduled sampling needs embedding_text % 4 == 0 and <= 1016 (tnt_scheduled_feedback2_f32), "
+                             f"got {self.Et}")
+
+    def _forward_ss(self, B, T):
+        """The scheduled-sampling training forward (definition: include/tnt_hip.h, tnt_scheduled_feedback2_f32).  The
+        teacher-forced front -- encoder, the Embedding of all T caption columns through the text Dropout and the LSTM
+        input mask, XZ of step 0's rows -- then per step t the attention -> LSTM step, the teacher-forced LSTM-output
+        Dropout on the step's rows, dense_inter, the output Dropout (logical (B, T, H): lwidth T*H, lcol0 t*H), dense_out
+        into the step's logits rows and, for t + 1 < T, the feedback launch: it decides token position t + 1 of every row,
+        writes a fed token into ``cap``, its doubly masked Embedding row into ``text`` and its projection into ``XZ``.
+        The loss, its targets and the whole backward are the teacher-forced ones, over the fed ids.  At p = 1 this is not
+        call_naive_attention: that mode's Dropouts differ (text Dropout on step 0 only, the output Dropout on the U-wide
+        LSTM output, a second feature Dropout)."""
+        be, a, ss = self.be, self.arena, self.scheduled_sampling
+        D, U, Et, V, H, ldV = self.D, self.U, self.Et, self.V, self.H, self.ldV
+        sd, ds = self.seed, self.drop_step
+        self._encode(B, True)
+        emb, Wl = a.p("emb_text/embeddings"), a.p("lstm/kernel")
+        lstm_in = self.r_lstm > 0
+        if self.r_text > 0:            # (D % 16 == 0: the LSTM input mask always rides in the Embedding launch)
+            be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
+                                  mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if lstm_in else None)
+        else:
+            be.embedding_fwd(emb, self.cap, self.text, B, T, Et, Et, V)
+            if lstm_in:
+                be.dropout(self.text, self.text, T * B, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds,
+                           rows_per_site=B)
+        self.gemm_sk(self.text[:B], Wl[D:], self.XZ[:B], B, 4 * U, Et, Et, 4 * U, 4 * U)
+        if self._keep_stored and not self.__dict__.get("_masks_staged"):
+            be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
+        Wi, bi = a.p("time_distributed_nonlinear/kernel"), a.p("time_distributed_nonlinear/bias")
+        Wo, bo = a.p("time_distributed_softmax/kernel"), a.p("time_distributed_softmax/bias")
+        for t in range(T):
+            rows = slice(t * B, (t + 1) * B)
+            self._decode_step(t, B, True, xz_bias=a.p("lstm/bias"))
+            h = self.Hs[t + 1]
+            if self.r_lstm > 0:                                     # :256, site S_LSTM_OUT + t on the step's B rows
+                be.dropout(h, self.Hd[rows], B, U, U, 0, U, 0, self.r_lstm, sd, S_LSTM_OUT + t, 0, ds)
+                h = self.Hd[rows]
+            self.gemm_sk(h, Wi, self.inter[rows], B, H, U, U, H, H, bias=bi, pre=self.ipre[rows], act=ACT_LEAKY, slope=0.2)
+            inter = self.inter[rows]
+            if self.r_out > 0:                                      # element (b*T + t)*H + j of the logical (B, T, H)
+                be.dropout(inter, self.inter_d[rows], B, H, H, 0, T * H, t * H, self.r_out, sd, S_OUT, 0, ds)
+                inter = self.inter_d[rows]
+            self.gemm_sk(inter, Wo, self.logits[rows], B, V, H, H, ldV, ldV, bias=bo)
+            if t + 1 < T:
+                col, nxt = t + 1, slice((t + 1) * B, (t + 2) * B)
+                be.scheduled_feedback2(self.logits[rows], ldV, V, emb, Et, Wl[D:], 4 * U, 4 * U, self.cap, T, col,
+                                       self.text[nxt], Et, self.XZ[nxt], 4 * U, B, self.r_lstm, sd, S_LSTM_IN + col, 0, ds,
+                                       D + Et, D, ss.kind_id, ss.mode_id, self.ss_sched, self.adam_t, S_SS_COIN + t,
+                                       S_SS_DRAW + t, self.r_text, S_TEXT, T * Et, col * Et)
+        self._hs_used = self.Hd if self.r_lstm > 0 else self.Hs[1:].view(T * B, U)
+        self._inter_used = self.inter_d if self.r_out > 0 else self.inter
+        self._out_dropped = False
+        self._metric_parts_ready = False           # the attention metric: _loss_metrics, behind the loop
 
     def _forward_naive(self, B, T, training):
         """lc_NIC.call_naive_attention (lc_NIC.py:175-221): the decoder fed its own greedy predictions.  Per step: attention
@@ -1025,7 +1100,10 @@ class NIC(ModelBase):
 
     # ------------------------------------------------------------------ steps
     def _train_graph(self, B, T):
-        (self._forward if self.teacher_forcing else self._forward_naive)(B, T, True)
+        if self.scheduled_sampling is not None:
+            self._forward_ss(B, T)
+        else:
+            (self._forward if self.teacher_forcing else self._forward_naive)(B, T, True)
         self._loss_metrics(B, T, True)
         self._backward(B, T)
 
@@ -1073,7 +1151,12 @@ class NIC(ModelBase):
             raise RuntimeError("compile() the model before train_step")
         if not self.teacher_forcing and self.grad_sync is not None:
             raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
+        if self.scheduled_sampling is not None and self.grad_sync is not None:
+            raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
+        if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
+            raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
+                             f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
         ring = False
@@ -1113,6 +1196,8 @@ class NIC(ModelBase):
                                       "teacher_forcing=False")
         if self.S != 1:
             raise NotImplementedError("train_step_sam is a single-subject step (lc_NIC.py)")
+        if self.scheduled_sampling is not None:
+            raise NotImplementedError("train_step_sam is a teacher-forced step: not built for scheduled_sampling")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()

@@ -21,17 +21,18 @@ from .optimizers import Adam
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
 S_ATTN, S_LSTM_IN, S_LSTM_OUT = 16, 48, 80
 S_SAMPLE = 112          # + decode position: categorical-sampling stream of sample_predict
-# + token position j (< 32): scheduled sampling's coin and draw streams (nic.NIC(scheduled_sampling=...)); after
-# lc_nic.S_NOUT = 144 + step
+# + token position j (< 32): scheduled sampling's coin and draw streams (nic.NIC and lc_nic.NIC(scheduled_sampling=...));
+# after lc_nic.S_NOUT = 144 + step
 S_SS_COIN, S_SS_DRAW = 176, 208
 SS_MAX_POSITIONS = 32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
 class ScheduledSampling:
-    """Scheduled sampling (Bengio et al. 2015) for nic.NIC's train_step; the definition is tnt_scheduled_feedback_f32's
-    (include/tnt_hip.h).  At each step, each caption row is fed the model's own token with probability p, the ground
-    truth otherwise; p grows with i, the updates applied so far (the model's device counter adam_t):
+    """Scheduled sampling (Bengio et al. 2015) for the train_step of nic.NIC and lc_nic.NIC; the definitions are
+    tnt_scheduled_feedback_f32's and tnt_scheduled_feedback2_f32's (include/tnt_hip.h).  At each step, each caption row is
+    fed the model's own token with probability p, the ground truth otherwise; p grows with i, the updates applied so far
+    (the model's device counter adam_t):
       ScheduledSampling.linear(p0, slope, p_max=1.0):  p = clip(p0 + slope * i, 0, p_max)   (constant p: slope = 0)
       ScheduledSampling.inverse_sigmoid(k, p_max=1.0): p = p_max * (1 - k / (k + exp(i / k))), k >= 1
     mode "greedy" feeds the argmax of the step's logits, "sample" a categorical draw from them (temperature 1).

@@ -323,6 +323,16 @@ class HipBackend:
                    _p(step_dev), int(lwidth), int(lcol0), int(kind), int(mode), _p(sched), _p(counter),
                    int(coin_site), int(draw_site), self._s())
 
+    def scheduled_feedback2(self, logits, ld, V, table, E, w, ldw, N, fed, T, col, text, ldt, xz, ldz, B, rate, seed, site,
+                            step, step_dev, lwidth, lcol0, kind, mode, sched, counter, coin_site, draw_site, rate_t, site_t,
+                            lwidth_t, lcol0_t):
+        """scheduled_feedback with the Embedding Dropout (rate_t, site_t, lwidth_t, lcol0_t) in front of the LSTM input
+        mask (tnt_scheduled_feedback2_f32; definition in include/tnt_hip.h): the attention model's text rows"""
+        self._call(self.lib.tnt_scheduled_feedback2_f32, "tnt_scheduled_feedback2_f32", _p(logits), ld, V, _p(table), E,
+                   _p(w), ldw, N, _p(fed), T, col, _p(text), ldt, _p(xz), ldz, B, float(rate), int(seed), int(site),
+                   int(step), _p(step_dev), int(lwidth), int(lcol0), int(kind), int(mode), _p(sched), _p(counter),
+                   int(coin_site), int(draw_site), float(rate_t), int(site_t), int(lwidth_t), int(lcol0_t), self._s())
+
     def enc_tail_fwd(self, y, gamma, beta, mov_mean, mov_var, out, xhat, inv_std, rows, C, ldo, training, eps, momentum,
                      r_feat, r_lstm, seed, site_feat, site_lstm, step_dev=None):
         self._call(self.lib.tnt_enc_tail_fwd_f32, "tnt_enc_tail_fwd_f32", _p(y), _p(gamma), _p(beta), _p(mov_mean), _p(mov_var), _p(out), _p(xhat),

@@ -1,8 +1,8 @@
-"""ms/step of the config-2 training step, teacher-forced (bench.py's make_model("dense")) and with scheduled sampling at
-p = 0.25 in greedy and in sample mode (the same model with scheduled_sampling=ScheduledSampling.linear(0.25, 0)), in one
-process with alternating timed windows:
+"""ms/step of the config-2 (--workload dense, the default) or config-3 (--workload attention) training step, teacher-forced
+(bench.py's make_model) and with scheduled sampling at p = 0.25 in greedy and in sample mode (the same model with
+scheduled_sampling=ScheduledSampling.linear(0.25, 0)), in one process with alternating timed windows:
 
-    python tools/ss_step_bench.py [--windows 5] [--steps 100] [--warmup 30]
+    python tools/ss_step_bench.py [--workload dense|attention] [--windows 5] [--steps 100] [--warmup 30]
 
 Prints one line per mode: the best and the median window."""
 import argparse
@@ -16,26 +16,35 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 
-def make_ss(device, mode):
+def make_ss(workload, device, mode):
     from masters_thesis_amd.model_base import ScheduledSampling
-    from masters_thesis_amd.nic import NIC
     from masters_thesis_amd.optimizers import Adam
-    # the shapes and rates of bench.make_model("dense")
-    model = NIC(bench.N_VOX, bench.U, bench.E, bench.V, bench.T, 0.0, 0.2, 0.2, 0.01, 0.00003, 0.00001, device=device,
-                seed=42, scheduled_sampling=ScheduledSampling.linear(0.25, 0.0, mode=mode))
+    ss = ScheduledSampling.linear(0.25, 0.0, mode=mode)
+    # the shapes and rates of bench.make_model(workload)
+    if workload == "dense":
+        from masters_thesis_amd.nic import NIC
+        model = NIC(bench.N_VOX, bench.U, bench.E, bench.V, bench.T, 0.0, 0.2, 0.2, 0.01, 0.00003, 0.00001, device=device,
+                    seed=42, scheduled_sampling=ss)
+    else:
+        from masters_thesis_amd.lc_nic import NIC as LcNIC, synthetic_groups
+        groups = synthetic_groups(bench.N_VOX, 360, 32, seed=42)
+        model = LcNIC(groups, bench.U, 512, bench.E, 32, bench.V, bench.T, 0.0, 0.2, 0.2, 0.2, 0.2, 0.2, 0.01, 0.001,
+                      0.00003, 0.00001, device=device, seed=42, scheduled_sampling=ss)
     model.compile(Adam(learning_rate=0.0001, beta_1=0.9, beta_2=0.98, epsilon=1e-8, clipnorm=0.1))
     return model
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=("dense", "attention"), default="dense")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    models = {"teacher-forced": bench.make_model("dense", dev), "ss greedy p=0.25": make_ss(dev, "greedy"),
-              "ss sample p=0.25": make_ss(dev, "sample")}
+    w = args.workload
+    models = {"teacher-forced": bench.make_model(w, dev), "ss greedy p=0.25": make_ss(w, dev, "greedy"),
+              "ss sample p=0.25": make_ss(w, dev, "sample")}
     batch, _ = bench.synth(0, dev)
     for m in models.values():
         for _ in range(args.warmup):
