@@ -674,6 +674,24 @@ int32_t tnt_scheduled_feedback2_f32(const float* logits, int32_t ld, int32_t V, 
                                     int32_t lwidth, int32_t lcol0, int32_t kind, int32_t mode, const double* sched,
                                     const int64_t* counter, uint32_t coin_site, uint32_t draw_site, float rate_t,
                                     uint32_t site_t, int32_t lwidth_t, int32_t lcol0_t, void* stream);
+/* Self-critical sequence training loss (Rennie et al. 2017) of the dense caption model's SCST step
+ * (nic.NIC(self_critical=...)); restated by tests/scst_oracle.py.  R sampled captions of T tokens; logits [T*R][ld], V valid
+ * columns, row (t-1)*R + r holding LSTM step t's logits of caption r (t = 1..T).  For that row:
+ *  - sampled token: w = fed[r*T + t] for t < T, last[r] for t = T;
+ *  - mask: m = 1 iff no terminator (end_id or 0) occurs among fed[r*T + 1 .. r*T + t-1]: the tokens up to and including
+ *    the first terminator count (end_id < 0: only 0 terminates);
+ *  - lp = x_w - logsumexp(x) (no clip); loss_row[row] = -adv[r] * m * lp, lp_row[row] = m * lp (both nullable; a row
+ *    with m = 0 or adv[r] = 0 has loss_row 0);
+ *  - dlogits[row][j] = gscale * adv[r] * m * (softmax(x)_j - [j == w]) for j < V (dlogits may alias logits); a row with
+ *    m = 0 or adv[r] = 0 is written as zeros, and a row with m = 0 does not read its logits.  Columns [V, ld) are not
+ *    written.
+ * The step's loss is gscale * sum of loss_row with gscale = 1/R.  The ids are device data: a counted row (m = 1) whose w is
+ * outside [0, V) writes NaN to loss_row and lp_row and a zero gradient row.  One 256-thread workgroup per row, float32,
+ * deterministic, no scratch memory.
+ * TNT_BADARG for null logits / fed / last / adv / dlogits, V < 1, ld < V, T < 1, R < 1, end_id >= V. */
+int32_t tnt_scst_cce_f32(const float* logits, int32_t ld, int32_t V, const int32_t* fed, int32_t T, const int32_t* last,
+                         const float* adv, int32_t end_id, float* loss_row, float* lp_row, float* dlogits, int32_t R,
+                         float gscale, void* stream);
 /* out[0] = scale * sum_i x[i]  (fixed-order, one workgroup). */
 /* Categorical sampling per row (tf.random.categorical(logits / temperature, 1): ThinkAndTell/evaluate.py:223,278;
  * lc_NIC.sample_choice lc_NIC.py:571-575 samples from log(probs)).  x: logits (from_logits=1) or probabilities.

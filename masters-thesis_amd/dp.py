@@ -428,6 +428,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if getattr(model, "scheduled_sampling", None) is not None:
         # nic.NIC / lc_nic.NIC(scheduled_sampling=...) have no data-parallel schedule either
         raise NotImplementedError("data parallel training with scheduled sampling is not supported: train it on one device")
+    if getattr(model, "self_critical", None) is not None:
+        # nic.NIC(self_critical=...): the step's host round trip has no data-parallel schedule
+        raise NotImplementedError("data parallel self-critical training is not supported: train it on one device")
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.__dict__.get("agc") and world > 1:

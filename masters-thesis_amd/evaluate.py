@@ -167,3 +167,93 @@ def bleu_scores(references, candidate):
     """The four scores of ThinkAndTell/img_evaluate.py:245-248 (BLEU-1..4, cumulative weights, method 1)."""
     ws = [(1, 0, 0, 0), (0.5, 0.5, 0, 0), (0.33, 0.33, 0.33, 0), (0.25, 0.25, 0.25, 0.25)]
     return tuple(sentence_bleu(references, candidate, weights=w) for w in ws)
+
+
+class CiderD:
+    """CIDEr-D (Vedantam et al. 2015) of tokenised captions, restated from the published definition with the choices of
+    coco-caption's CiderD scorer: n-grams of n = 1..4, each with its own tf-idf vector (tf = the raw n-gram count,
+    idf = log(number of documents) - log(max(1, df)), df = the number of documents whose references contain the n-gram;
+    a document is one scan's set of references); the numerator is clipped, each n-gram of the candidate contributing
+    min(candidate, reference) x reference tf-idf, over the product of the two vector norms; a Gaussian length penalty
+    exp(-(l_c - l_r)^2 / (2 sigma^2)), sigma = 6; the scores are averaged over n and over the references and multiplied by 10.
+    ``corpus`` (a list of documents, each a list of tokenised references): the document frequencies, fixed for this
+    scorer, and each reference's vectors are cached across calls.  ``corpus=None``: the frequencies come from the
+    documents of each ``batch_scores`` call, coco-caption's behaviour (with one document every idf is 0 and so is every
+    score).  PARITY UNPINNED against pycocoevalcap itself, which is not available here; pinned by hand-computed cases
+    (tests/test_host_scst.py).  Host-side Python."""
+
+    def __init__(self, corpus=None, n=4, sigma=6.0):
+        self.n, self.sigma = int(n), float(sigma)
+        self._cache = {}
+        self._df = self._log_docs = None
+        if corpus is not None:
+            self._df, self._log_docs = self._doc_freq(corpus)
+
+    def _counts(self, seq):
+        seq = tuple(int(w) if isinstance(w, (int, np.integer)) else w for w in seq)
+        return [_ngrams(seq, k) for k in range(1, self.n + 1)], len(seq)
+
+    def _doc_freq(self, docs):
+        df = Counter()
+        ndoc = 0
+        for refs in docs:
+            ndoc += 1
+            seen = set()
+            for ref in refs:
+                for c in self._counts(ref)[0]:
+                    seen.update(c)
+            df.update(seen)
+        return df, math.log(float(max(ndoc, 1)))
+
+    def _vec(self, seq, df, log_docs):
+        """(per-n tf-idf dicts, per-n squared norms, length)"""
+        counts, length = self._counts(seq)
+        vecs, sq = [], []
+        for c in counts:
+            v = {g: float(tf) * (log_docs - math.log(max(1.0, float(df.get(g, 0))))) for g, tf in c.items()}
+            vecs.append(v)
+            sq.append(sum(x * x for x in v.values()))
+        return vecs, sq, length
+
+    def _sim(self, hyp, ref):
+        (vh, sh, lh), (vr, sr, lr) = hyp, ref
+        pen = math.exp(-((lh - lr) ** 2) / (2.0 * self.sigma ** 2))
+        total = 0.0
+        for k in range(self.n):
+            num = sum(min(x, vr[k].get(g, 0.0)) * vr[k].get(g, 0.0) for g, x in vh[k].items())
+            den = sh[k] * sr[k]
+            total += (num / math.sqrt(den) if den != 0.0 else 0.0) * pen
+        return total / self.n
+
+    def _score(self, hyp, refs):
+        if not refs:
+            return 0.0
+        return 10.0 * sum(self._sim(hyp, r) for r in refs) / len(refs)
+
+    def batch_scores(self, candidates, references):
+        """candidates: one list of candidate token sequences per document; references: one list of reference token
+        sequences per document.  Returns one float64 array of scores per document."""
+        if len(candidates) != len(references):
+            raise ValueError(f"{len(candidates)} candidate lists for {len(references)} documents")
+        if self._df is None:
+            df, log_docs = self._doc_freq(references)
+            ref_vec = lambda r: self._vec(r, df, log_docs)
+        else:
+            df, log_docs = self._df, self._log_docs
+
+            def ref_vec(r):
+                key = tuple(r)
+                v = self._cache.get(key)
+                if v is None:
+                    v = self._cache[key] = self._vec(r, df, log_docs)
+                return v
+        out = []
+        for cands, refs in zip(candidates, references):
+            rv = [ref_vec(r) for r in refs]
+            out.append(np.array([self._score(self._vec(c, df, log_docs), rv) for c in cands], np.float64))
+        return out
+
+    def __call__(self, candidate, references):
+        """the score of one candidate against its references (one document: the scorer's corpus frequencies, or,
+        without a corpus, these references alone)"""
+        return float(self.batch_scores([[candidate]], [references])[0][0])

@@ -25,6 +25,7 @@ S_SAMPLE = 112          # + decode position: categorical-sampling stream of samp
 # after lc_nic.S_NOUT = 144 + step
 S_SS_COIN, S_SS_DRAW = 176, 208
 SS_MAX_POSITIONS = 32
+S_SCST_LAST = 240       # self-critical rollouts: the draw of the last token position (nic.NIC(self_critical=...))
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
@@ -94,6 +95,107 @@ class ScheduledSampling:
         if self.kind == "linear":
             return f"ScheduledSampling.linear(p0={self.p0}, slope={self.slope}, p_max={self.p_max}, mode={self.mode!r})"
         return f"ScheduledSampling.inverse_sigmoid(k={self.k}, p_max={self.p_max}, mode={self.mode!r})"
+
+
+class SelfCritical:
+    """Self-critical sequence training (Rennie et al. 2017) for nic.NIC's train_step (nic.NIC.train_step_scst): per scan
+    K = ``n_samples`` captions are sampled from the model (temperature 1), each scored by ``reward`` against the scan's
+    references, and the loss (1/R) sum_r -(reward_r - baseline_r) sum_t m_rt log p(w_rt) (R = B*K, m: the tokens up to and
+    including the first terminator) is minimised; its definition on the device is tnt_scst_cce_f32's (include/tnt_hip.h).
+      end_id     the tokenizer's <end> index; a caption ends at its first end_id or 0
+      n_samples  K sampled captions per scan, 1..16
+      baseline   "greedy": the reward of the model's inference-mode greedy caption of the scan; "mean": the mean reward of
+                 the scan's other K-1 samples (K >= 2, no decode)
+      reward     "cider-d" (evaluate.CiderD), "bleu4" (evaluate.sentence_bleu, weights (0.25,)*4, method 1) or a callable
+                 (candidate_ids, reference_id_lists) -> float
+      corpus     tokenised reference captions, one list of references per scan: CIDEr-D's document frequencies; None takes
+                 them from each batch's references
+    Bad arguments raise ValueError here, before any launch."""
+
+    BASELINES = ("greedy", "mean")
+    REWARDS = ("cider-d", "bleu4")
+
+    def __init__(self, end_id, n_samples=1, baseline="greedy", reward="cider-d", corpus=None):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not is_int(end_id) or end_id < 1:
+            raise ValueError(f"self-critical end_id must be an int >= 1 (the <end> index), got {end_id!r}")
+        if not is_int(n_samples) or not 1 <= n_samples <= 16:
+            raise ValueError(f"self-critical n_samples must be an int in [1, 16], got {n_samples!r}")
+        if baseline not in self.BASELINES:
+            raise ValueError(f"self-critical baseline must be one of {self.BASELINES}, got {baseline!r}")
+        if baseline == "mean" and n_samples < 2:
+            raise ValueError("self-critical baseline 'mean' needs n_samples >= 2 (the other samples of the scan)")
+        if not (callable(reward) or (isinstance(reward, str) and reward in self.REWARDS)):
+            raise ValueError(f"self-critical reward must be one of {self.REWARDS} or a callable, got {reward!r}")
+        if corpus is not None:
+            try:
+                corpus = [[list(r) for r in doc] for doc in corpus]
+            except TypeError:
+                raise ValueError("self-critical corpus must be None or a list of documents, each a list of tokenised "
+                                 "references") from None
+        self.end_id, self.n_samples, self.baseline, self.reward, self.corpus = int(end_id), int(n_samples), baseline, reward, corpus
+        self._cider = None
+        if reward == "cider-d":
+            from .evaluate import CiderD
+            self._cider = CiderD(corpus)
+
+    def truncate(self, ids):
+        """the tokens of a caption before its first terminator (end_id or 0)"""
+        out = []
+        for w in ids:
+            w = int(w)
+            if w == 0 or w == self.end_id:
+                break
+            out.append(w)
+        return out
+
+    def counted(self, ids):
+        """the number of token positions the loss counts: up to and including the first terminator"""
+        for i, w in enumerate(ids):
+            if int(w) == 0 or int(w) == self.end_id:
+                return i + 1
+        return len(ids)
+
+    def scores(self, candidates, references):
+        """candidates: one list of token-id sequences per scan, references: one list of references per scan ->
+        one float64 array of rewards per scan"""
+        if self._cider is not None:
+            return self._cider.batch_scores(candidates, references)
+        if self.reward == "bleu4":
+            from .evaluate import sentence_bleu
+            fn = lambda c, refs: sentence_bleu(refs, c, weights=(0.25,) * 4) if refs else 0.0
+        else:
+            fn = self.reward
+        return [np.array([float(fn(c, refs)) for c in cands], np.float64) for cands, refs in zip(candidates, references)]
+
+    def advantages(self, samples, references, greedy=None):
+        """samples: (B*K, T) sampled ids w_1..w_T (row b*K + k: sample k of scan b); references: B lists of references;
+        greedy: (B, T) greedy ids (baseline "greedy").  Returns float64 arrays (adv, reward, baseline, counted), each (B*K,)."""
+        samples = np.asarray(samples)
+        K = self.n_samples
+        B = samples.shape[0] // K
+        if samples.shape[0] != B * K or len(references) != B:
+            raise ValueError(f"{samples.shape[0]} samples and {len(references)} reference lists for n_samples = {K}")
+        refs = [[list(r) for r in doc] for doc in references]
+        cands = [[self.truncate(samples[b * K + k]) for k in range(K)] for b in range(B)]
+        if self.baseline == "greedy":
+            if greedy is None:
+                raise ValueError("baseline 'greedy' needs the greedy captions")
+            g = np.asarray(greedy)
+            cands = [c + [self.truncate(g[b])] for b, c in enumerate(cands)]
+        sc = self.scores(cands, refs)
+        reward = np.concatenate([s[:K] for s in sc])
+        if self.baseline == "greedy":
+            base = np.repeat(np.array([s[K] for s in sc]), K)
+        else:
+            r = reward.reshape(B, K)
+            base = ((r.sum(1, keepdims=True) - r) / (K - 1)).reshape(-1)
+        counted = np.array([self.counted(row) for row in samples], np.float64)
+        return reward - base, reward, base, counted
+
+    def __repr__(self):
+        return (f"SelfCritical(end_id={self.end_id}, n_samples={self.n_samples}, baseline={self.baseline!r}, "
+                f"reward={self.reward!r}, corpus={'None' if self.corpus is None else f'<{len(self.corpus)} documents>'})")
 
 
 def check_sampling(top_k, top_p, temperature):

@@ -19,8 +19,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, ScheduledSampling, check_sampling,
-                         check_beam, length_normalise)
+                         BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
+                         SelfCritical, check_sampling, check_beam, length_normalise)
 from .ops import ACT_LEAKY
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -32,7 +32,8 @@ def _r4(n):
 
 class NIC(ModelBase):
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
-                 dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, **kw):
+                 dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
+                 **kw):
         super().__init__(**kw)
         self.N, self.U, self.E, self.V, self.max_length = int(input_size), int(units), int(embedding_dim), int(vocab_size), int(max_length)
         self.r_in, self.r_feat, self.r_lstm = float(dropout_input), float(dropout), float(dropout_lstm)
@@ -53,6 +54,20 @@ class NIC(ModelBase):
                 raise ValueError(f"scheduled sampling needs embedding_dim % 4 == 0 and <= 1016 "
                                  f"(tnt_scheduled_feedback_f32), got {E}")
         self.scheduled_sampling = scheduled_sampling
+        # self_critical (model_base.SelfCritical): train_step runs the self-critical step (train_step_scst); its rollout is
+        # the scheduled-sampling forward at a constant p = 1 in sample mode
+        if self_critical is not None:
+            if not isinstance(self_critical, SelfCritical):
+                raise ValueError(f"self_critical must be None or a model_base.SelfCritical, got {self_critical!r}")
+            if scheduled_sampling is not None:
+                raise ValueError("a model takes scheduled_sampling or self_critical, not both")
+            if E % 4 or E > 1016:
+                raise ValueError(f"self-critical training needs embedding_dim % 4 == 0 and <= 1016 "
+                                 f"(tnt_scheduled_feedback_f32), got {E}")
+            if self_critical.end_id >= V:
+                raise ValueError(f"self-critical end_id {self_critical.end_id} is not below vocab_size {V}")
+        self.self_critical = self_critical
+        self._rollout_ss = ScheduledSampling.linear(1.0, 0.0, 1.0, mode="sample") if self_critical is not None else None
         self.ldx, self.ldV = _r4(N), _r4(V)
         self.layers_spec = OrderedDict([
             ("dense_img", ["kernel", "bias"]),
@@ -81,8 +96,9 @@ class NIC(ModelBase):
         a.finalize()
         self.mov_mean, self.mov_var = self._f(E), torch.ones(E, dtype=torch.float32, device=self.device)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if scheduled_sampling is not None:      # the schedule's parameters, read by the kernel (float64, device)
-            self.ss_sched = torch.tensor(scheduled_sampling.params(), dtype=torch.float64, device=self.device)
+        if scheduled_sampling is not None or self_critical is not None:     # the schedule's parameters, read by the kernel
+            self.ss_sched = torch.tensor((scheduled_sampling or self._rollout_ss).params(), dtype=torch.float64,
+                                         device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
 
@@ -341,7 +357,8 @@ class NIC(ModelBase):
         B-row head GEMM into the step's logits rows, and (t <= T-1) tnt_scheduled_feedback_f32, which decides token
         position t of every row, writes a fed token into cap, its masked Embedding row into xin and its projection into
         XZ for step t+1.  The loss, its targets (tgt) and the whole backward are the teacher-forced ones, over the fed ids."""
-        be, a, ss = self.be, self.arena, self.scheduled_sampling
+        be, a = self.be, self.arena
+        ss = self.scheduled_sampling if self.scheduled_sampling is not None else self._rollout_ss
         U, E, V, ldV = self.U, self.E, self.V, self.ldV
         Wl, Ur, bl = a.p("lstm/kernel"), a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
         Wo, bo = a.p("time_distributed_softmax/kernel"), a.p("time_distributed_softmax/bias")
@@ -626,12 +643,21 @@ class NIC(ModelBase):
             self._defer_sum2 = False
         self._update_fused(self.met[2:3])
 
+    def _step_runner(self):
+        """_run_planned where the training step is backend launches only (see train_step), else _run_captured"""
+        plan = (getattr(self, "plan_step", True) and self.E % 4 == 0 and getattr(self, "sparse_emb_bwd", True)
+                and hasattr(self.be, "embedding_bwd_sparse"))
+        return self._run_planned if plan else self._run_captured
+
     def train_step(self, data):
-        """NIC.train_step (NIC.py:198-252): data = ((betas, cap, a0, c0), target)."""
+        """NIC.train_step (NIC.py:198-252): data = ((betas, cap, a0, c0), target).  With ``self_critical`` set, the
+        self-critical step (train_step_scst) instead."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
         if self.scheduled_sampling is not None and self.grad_sync is not None:
             raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
+        if self.self_critical is not None:
+            return self.train_step_scst(data)
         B, T = self._stage_batch(data[0], data[1], self.N)
         if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
             raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
@@ -646,10 +672,7 @@ class NIC(ModelBase):
             # models, repeated, spread 0.0005).  ``plan_step = False`` restores the graph.  A plan re-issues backend launches
             # only, so it is used where the step is nothing else: the sparse Embedding backward (the dense form hands its ids on
             # with a tensor copy, which a graph captures and a plan would drop).
-            plan = (getattr(self, "plan_step", True) and self.E % 4 == 0 and getattr(self, "sparse_emb_bwd", True)
-                    and hasattr(self.be, "embedding_bwd_sparse"))
-            run = self._run_planned if plan else self._run_captured
-            ring = self._run_step(run, ("train", B, T), lambda: self._train_and_update_graph(B, T))
+            ring = self._run_step(self._step_runner(), ("train", B, T), lambda: self._train_and_update_graph(B, T))
             self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
@@ -660,6 +683,148 @@ class NIC(ModelBase):
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         return self._metrics_from(m, loss=0, L2=2, accuracy=1)
+
+    # ------------------------------------------------------------------ self-critical sequence training
+    def _scst_bufs(self, B, T):
+        """per (B, T): the B staged rows (betas, state, caption, start token), the greedy ids (T, B), the last sampled
+        token and the advantage (R), and the host side of the step's one round trip"""
+        R = B * self.self_critical.n_samples
+        st = self.__dict__.get("_scst")
+        if st is not None and st["key"] == (B, T):
+            return st
+        f, dev, i32 = self._f, self.device, torch.int32
+        pin = self.device.type == "cuda"
+        h = lambda *shape, dtype=i32: torch.zeros(*shape, dtype=dtype, pin_memory=pin)
+        st = self._scst = dict(key=(B, T), x=f(B, self.ldx), h0=f(B, self.U), c0=f(B, self.U),
+                               cap=torch.zeros(B, T, dtype=i32, device=dev), start=torch.zeros(B, 1, dtype=i32, device=dev),
+                               greedy=torch.zeros(T, B, dtype=i32, device=dev), last=torch.zeros(R, dtype=i32, device=dev),
+                               adv=f(R), h_cap=h(R, T), h_last=h(R), h_greedy=h(T, B), h_ref=h(B, T),
+                               h_adv=h(R, dtype=torch.float32))
+        return st
+
+    def _stage_scst(self, inputs):
+        """Stages the B rows of a self-critical step, and their K copies as the R = B*K rows of the step's buffers (row
+        b*K + k: copy k of scan b), on the device (a torch copy, at staging: a recorded launch plan re-issues backend
+        launches only).  Over K identical copies BatchNorm's batch statistics are those of the B rows; every copy draws its
+        own Dropout masks (so with input Dropout the copies, and the statistics, differ)."""
+        x, cap, a0, c0 = inputs[:4]
+        cap_t = self._to_dev(cap, torch.int32)
+        B, T = cap_t.shape
+        if T - 1 > SS_MAX_POSITIONS:
+            raise ValueError(f"self-critical rollouts sample at most {SS_MAX_POSITIONS} token positions per caption through "
+                             f"the scheduled-sampling sites (S_SS_DRAW + j): caption length {T} is too long")
+        K = self.self_critical.n_samples
+        self._build(B * K, T)
+        st = self._scst_bufs(B, T)
+        xs = self._to_dev(x, torch.float32)
+        assert xs.shape == (B, self.N), f"betas shape {tuple(xs.shape)} != {(B, self.N)}"
+        st["x"][:, :self.N].copy_(xs)
+        st["h0"].copy_(self._to_dev(a0, torch.float32))
+        st["c0"].copy_(self._to_dev(c0, torch.float32))
+        st["cap"].copy_(cap_t)
+        st["start"].copy_(cap_t[:, :1])
+        self.x.view(B, K, self.ldx).copy_(st["x"][:, None, :].expand(B, K, self.ldx))
+        self.Hs[0].view(B, K, self.U).copy_(st["h0"][:, None, :].expand(B, K, self.U))
+        self.Cs[0].view(B, K, self.U).copy_(st["c0"][:, None, :].expand(B, K, self.U))
+        self.cap.view(B, K, T).copy_(cap_t[:, None, :].expand(B, K, T))
+        return B, T
+
+    def _scst_greedy(self, B, T):
+        """the baseline: greedy_predict's inference-mode decode of the B staged rows for T positions, the argmax ids of
+        position i into greedy[i], on slices of the step's buffers (rows [0, B) of enc_y, Xin, XZ, Hs[1..2], Cs[1..2],
+        gates[0], Out[0], logits) before the rollout overwrites them"""
+        be, a, st = self.be, self.arena, self._scst
+        U, E, V, ldV = self.U, self.E, self.V, self.ldV
+        h, c = [self.Hs[1][:B], self.Hs[2][:B]], [self.Cs[1][:B], self.Cs[2][:B]]
+        self._decode_encode(B, (st["x"], st["h0"], st["c0"], h[0], c[0]))
+        Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
+        xz, emb, out, probs, ids = self.XZ[:B], self.Xin[B:2 * B], self.Out[0][:B], self.logits[:B], st["greedy"]
+        for i in range(T):
+            tok = st["start"] if i == 0 else ids[i - 1].view(B, 1)
+            be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, B, 1, E, E, V)
+            self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
+            be.lstm_step_fwd(xz, h[i & 1], c[i & 1], Ur, None, None, 0, tok if i > 0 else None, 1, 0, None,
+                             h[(i & 1) ^ 1], c[(i & 1) ^ 1], out, self.gates[0][:B], B, U)
+            self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, B, V, U, U, ldV, ldV,
+                         bias=a.p("time_distributed_softmax/bias"))
+            be.softmax_cce(probs, None, probs, None, None, None, B, V, ldV, 0.0)
+            be.argmax_rows(probs, ids[i], B, V, ldV)
+
+    def _scst_rollout(self, R, T):
+        """the training forward over the R rows with every token position sampled (_forward_ss at p = 1, sample mode:
+        w_1..w_{T-1} into cap[:, 1:]), and the draw of w_T from step T's logits (Philox site S_SCST_LAST)"""
+        self._forward(R, T, True, ss=True)
+        self.be.sample_rows(self.logits[(T - 1) * R:], self._scst["last"], R, self.V, self.ldV, 1.0, True, self.seed,
+                            S_SCST_LAST, 0, self.drop_step)
+
+    def _scst_update(self, R, T):
+        """tnt_scst_cce_f32 (loss rows, dlogits in place of the logits), the teacher-forced backward over the sampled ids,
+        and the fused update: the L2 terms, the clip and Adam of train_step"""
+        st = self._scst
+        self._defer_sum2 = True
+        try:
+            self.be.scst_cce(self.logits, self.ldV, self.V, self.cap, T, st["last"], st["adv"], self.self_critical.end_id,
+                             self.loss_row, None, self.logits, R, 1.0 / R)
+            self._sum2(self.loss_row, self.met[0:1], self.loss_row, self.met[1:2], T * R, 1.0 / R)
+            self._backward(R, T)
+        finally:
+            self._defer_sum2 = False
+        self._update_fused(self.met[2:3])
+
+    def _scst_round_trip(self, B, T):
+        """the step's one synchronisation: sampled (R, T), greedy (T, B) and staged caption (B, T) ids to the host"""
+        st = self._scst
+        pairs = [(st["h_cap"], self.cap), (st["h_last"], st["last"]), (st["h_ref"], st["cap"])]
+        if self.self_critical.baseline == "greedy":
+            pairs.append((st["h_greedy"], st["greedy"]))
+        for hst, dv in pairs:
+            hst.copy_(dv, non_blocking=True)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream().synchronize()
+        samples = np.concatenate([st["h_cap"].numpy()[:, 1:], st["h_last"].numpy()[:, None]], 1)
+        return samples, st["h_greedy"].numpy().T, st["h_ref"].numpy()
+
+    def train_step_scst(self, data, references=None):
+        """Self-critical sequence training (Rennie et al. 2017), one step; model_base.SelfCritical holds the definition.
+        data = ((betas, cap, a0, c0)[, target]); the target is not used.  ``references``: B lists of tokenised reference
+        captions (several per scan); None takes each row's own caption, cap[b, 1:] cut at its first end_id or 0.
+        With R = B*K: the B rows are staged and expanded to R on the device (_stage_scst); [greedy baseline: an inference
+        decode of the B rows, ids kept on the device]; the rollout: the training forward over the R rows with every token
+        sampled (Philox sites S_SS_DRAW + j and S_SCST_LAST, stream step drop_step); one device-to-host copy of the ids,
+        the rewards and advantages on the host, the advantages back to the device; then tnt_scst_cce_f32, the backward
+        and the update as one recorded segment.  Each device segment is replayed as a launch plan or a hipGraph like
+        train_step.  Metrics: loss (the policy-gradient loss), L2, reward (mean sampled reward), baseline (mean baseline
+        reward), sample_len (mean number of tokens the loss counts)."""
+        sc = self.self_critical
+        if sc is None:
+            raise ValueError("train_step_scst needs a model built with self_critical=model_base.SelfCritical(...)")
+        if self.optimizer is None:
+            raise RuntimeError("compile() the model before train_step")
+        if self.grad_sync is not None:
+            raise NotImplementedError("self-critical training has no data-parallel schedule: train it on one device")
+        B, T = self._stage_scst(data[0])
+        if references is not None and len(references) != B:
+            raise ValueError(f"references: {len(references)} reference lists for a batch of {B}")
+        R = B * sc.n_samples
+        self._sync_lr()
+        self._enc_grad_stale = None
+        run = self._step_runner()
+        if sc.baseline == "greedy":
+            run(("scst_greedy", B, T), lambda: self._scst_greedy(B, T))
+        run(("scst_rollout", R, T), lambda: self._scst_rollout(R, T))
+        samples, greedy, cap0 = self._scst_round_trip(B, T)
+        if references is None:
+            references = [[sc.truncate(row[1:])] for row in cap0]
+        adv, reward, base, counted = sc.advantages(samples, references, greedy if sc.baseline == "greedy" else None)
+        st = self._scst
+        st["h_adv"].copy_(torch.from_numpy(adv.astype(np.float32)))
+        st["adv"].copy_(st["h_adv"], non_blocking=True)
+        ring = self._run_step(run, ("scst_update", R, T), lambda: self._scst_update(R, T))
+        self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
+        self.optimizer.iterations += 1
+        m = self._met_snapshot(ring)
+        return self._metrics_from(m, loss=0, L2=2, reward=float(reward.mean()), baseline=float(base.mean()),
+                                  sample_len=float(counted.mean()))
 
     def test_step(self, data):
         """NIC.test_step (NIC.py:254-299)."""
@@ -706,12 +871,14 @@ class NIC(ModelBase):
         return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
                 probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
 
-    def _decode_encode(self, B):
+    def _decode_encode(self, B, src=None):
         """the inference encoder (dense_img, BatchNorm / LayerNorm) and the feature LSTM step of a decode over the staged
-        B rows: the state after the feature step is Hs[1], Cs[1]"""
+        B rows: the state after the feature step is Hs[1], Cs[1].  ``src`` = (x, h0, c0, h1, c1): other input rows and
+        initial state, and where the state after the feature step goes"""
         be, a = self.be, self.arena
         N, U, E = self.N, self.U, self.E
-        self.gemm_sk(self.x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
+        x, h0, c0, h1, c1 = src if src is not None else (self.x, self.Hs[0], self.Cs[0], self.Hs[1], self.Cs[1])
+        self.gemm_sk(x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
                      pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
         if self.norm == "batch":
             be.batchnorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.mov_mean, self.mov_var,
@@ -721,8 +888,8 @@ class NIC(ModelBase):
                              self.inv_std, B, E, E, BN_EPS)
         xz = self.XZ[:B]
         self.gemm_sk(self.Xin, a.p("lstm/kernel"), xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
-        be.lstm_step_fwd(xz, self.Hs[0], self.Cs[0], a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None,
-                         self.Hs[1], self.Cs[1], None, self.gates[0], B, U)
+        be.lstm_step_fwd(xz, h0, c0, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h1, c1, None,
+                         self.gates[0], B, U)
 
     def _decode(self, img_input, a0, c0, start_seq, max_len, filt):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,

@@ -504,6 +504,12 @@ class HipBackend:
         self._call(fn, name, _p(x), _p(x_dst), _p(cap), _p(cap_dst), _p(tgt), _p(tgt_tmajor), _p(a0),
                                                 _p(h0), _p(c0), _p(c0_dst), B, T, N, ldx, U, _p(xT_dst), ldt, self._s())
 
+    def scst_cce(self, logits, ld, V, fed, T, last, adv, end_id, loss_row, lp_row, dlogits, R, gscale):
+        """the SCST policy-gradient loss of R sampled captions and its logits gradient (tnt_scst_cce_f32; definition in
+        include/tnt_hip.h): row (t-1)*R + r, token fed[r*T + t] (t < T) or last[r], masked after the first terminator"""
+        self._call(self.lib.tnt_scst_cce_f32, "tnt_scst_cce_f32", _p(logits), ld, V, _p(fed), T, _p(last), _p(adv), int(end_id),
+                   _p(loss_row), _p(lp_row), _p(dlogits), R, float(gscale), self._s())
+
     def sample_rows(self, x, out, rows, V, ld, temperature, from_logits, seed, site, step, step_dev=None):
         self._call(self.lib.tnt_sample_rows_f32, "tnt_sample_rows_f32", _p(x), _p(out), rows, V, ld, float(temperature), int(from_logits),
                                                 int(seed), int(site), int(step), _p(step_dev), self._s())

@@ -1,0 +1,188 @@
+"""Self-critical sequence training on the GPU: tnt_scst_cce_f32 against the float64 restatement over a grid of
+vocabularies, leading dimensions, rows, advantages and terminator positions; nic.NIC's SCST step against the float64
+step of tests/scst_oracle.py at a small shape; config 2 with K = 4 "mean" and K = 1 "greedy"; launch-plan replay against
+hipGraph replay; and a small synthetic task on which the sampled reward rises."""
+import numpy as np
+import pytest
+import torch
+
+from helpers import synth_batch
+from scst_oracle import SCSTNICDense, expand, greedy, policy_grads, rollout, scst_cce
+
+pytestmark = pytest.mark.gpu
+
+END = 2
+LAM = {"dense_img/kernel": 0.01, "lstm/kernel": 3e-5, "time_distributed_softmax/kernel": 3e-5}
+
+
+@pytest.fixture
+def be():
+    import masters_thesis_amd.ops as ops
+    return ops.backend()
+
+
+def _ids(R, T, V, rng):
+    """fed (R, T) and last (R,) with terminators at t = 1, mid-caption, never, and an id 0, by row"""
+    fed = rng.integers(3, V, (R, T)).astype(np.int32) if V > 3 else rng.integers(1, V, (R, T)).astype(np.int32)
+    fed[:, 0] = 1
+    last = rng.integers(0, V, R).astype(np.int32)
+    for r in range(R):
+        kind = r % 4
+        if kind == 0:
+            fed[r, 1] = END                                   # ends at t = 1: only w_1 counts
+        elif kind == 1:
+            fed[r, T // 2] = END                              # mid-caption
+        elif kind == 2:
+            fed[r, 2] = 0                                     # an id 0 terminates too
+        # kind 3: never ends
+    return fed, last
+
+
+@pytest.mark.parametrize("V,ld", [(13, 16), (13, 16 + 3), (5001, 5004), (5001, 5001 + 7), (5001, 5012)])
+@pytest.mark.parametrize("R", [6, 64, 320])
+def test_kernel_matches_float64(be, V, ld, R):
+    rng = np.random.default_rng(V + R + ld)
+    T = 5
+    fed, last = _ids(R, T, V, rng)
+    adv = rng.standard_normal(R).astype(np.float32)
+    adv[rng.integers(0, R, max(1, R // 5))] = 0.0                            # zero advantages
+    adv[0], adv[min(3, R - 1)] = 1.5, -2.0
+    x = (rng.standard_normal((T * R, ld)) * 3).astype(np.float32)
+    x[:, V:] = 123.0                                                          # pad columns: never read, never written
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    want_loss, want_lp, want_d, m = scst_cce(x[:, :V].astype(np.float64), fed, last, adv, END, 1.0 / R)
+    for lp_on in (True, False):
+        for alias in (True, False):
+            logits = dev(x)
+            out = logits if alias else torch.full_like(logits, -5.0)
+            loss_row = torch.full((T * R,), -9.0, device="cuda")
+            lp_row = torch.full((T * R,), -9.0, device="cuda") if lp_on else None
+            be.scst_cce(logits, ld, V, dev(fed), T, dev(last), dev(adv), END, loss_row, lp_row, out, R, 1.0 / R)
+            torch.cuda.synchronize()
+            d = out.cpu().numpy()
+            tol = 2e-5 * np.abs(want_d).max() + 1e-7
+            assert np.abs(d[:, :V] - want_d).max() <= tol, (lp_on, alias)
+            assert np.all(d[:, V:] == (123.0 if alias else -5.0))
+            zero = (m.T.reshape(-1) == 0) | (np.repeat(adv[None, :], T, 0).reshape(-1) == 0)
+            assert not d[zero, :V].any()
+            assert np.allclose(loss_row.cpu().numpy(), want_loss, rtol=1e-5, atol=1e-5)
+            if lp_on:
+                assert np.allclose(lp_row.cpu().numpy(), want_lp, rtol=1e-5, atol=1e-5)
+    assert m.sum() < m.size and m.sum() > R            # the grid holds both counted and masked rows
+
+
+def test_kernel_bad_arguments(be):
+    from masters_thesis_amd._lib import KernelLibraryError
+    t = torch.zeros(8, 16, device="cuda")
+    i = torch.zeros(8, dtype=torch.int32, device="cuda")
+    f = torch.zeros(8, device="cuda")
+    for args in ((t, 12, 13, i, 1, i, f, END), (t, 16, 13, i, 1, i, f, 13), (t, 16, 0, i, 1, i, f, END)):
+        with pytest.raises(KernelLibraryError):
+            be.scst_cce(*args, None, None, t, 8, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------- the model
+def _case(shape, sc, rates=(0.0, 0.2, 0.2), seed=42, plan=True):
+    from masters_thesis_amd.nic import NIC
+    from masters_thesis_amd.optimizers import Adam
+    if shape == "small":
+        B, N, T, V, U, E = 8, 23, 6, 13, 16, 12
+    else:
+        B, N, T, V, U, E = 64, 20000, 15, 5001, 512, 512
+    model = NIC(N, U, E, V, T, *rates, 0.01, 3e-5, 1e-5, seed=seed, self_critical=sc)
+    model.plan_step = plan
+    model.compile(Adam(1e-3, clipnorm=None))
+    orc = SCSTNICDense(N, U, E, V, T, *rates, 0.01, 3e-5, 1e-5)
+    orc.p = {k: v.astype(np.float64) for k, v in model.get_weights_dict().items()}
+    data, tgt = synth_batch(B, N, T, V, U, np.random.default_rng(17))
+    return model, orc, data, tgt
+
+
+@pytest.mark.parametrize("K,baseline", [(1, "greedy"), (3, "mean")])
+def test_model_matches_float64(K, baseline):
+    from masters_thesis_amd.model_base import SelfCritical
+    from oracle import models as M
+    sc = SelfCritical(END, n_samples=K, baseline=baseline, reward=lambda c, refs: len(c) + 0.5 * len(set(c) & set(refs[0])))
+    model, orc, data, tgt = _case("small", sc)
+    drop = M.DropCtx(seed=42, step=0, training=True)
+    data_r = expand(data, K)
+    fed, last, margin = rollout(orc, data_r, drop)
+    got = model.train_step((data, tgt)).as_floats()
+    dfed, dlast = model.cap.cpu().numpy(), model._scst["last"].cpu().numpy()
+    ok = margin > 1e-4
+    print(f"K={K} {baseline}: {int((~ok).sum())} of {len(ok)} rows hold a draw inside the margin")
+    assert np.array_equal(dfed[ok], fed[ok]) and np.array_equal(dlast[ok], last[ok])
+    refs = [[sc.truncate(row[1:])] for row in data[1]]
+    g = None
+    if baseline == "greedy":
+        g = model._scst["greedy"].cpu().numpy().T
+        assert np.array_equal(g, greedy(orc, data, data[1].shape[1]))
+    samples = np.concatenate([dfed[:, 1:], dlast[:, None]], 1)
+    adv, reward, base, counted = sc.advantages(samples, refs, g)
+    assert abs(got["reward"] - reward.mean()) < 1e-9 and abs(got["baseline"] - base.mean()) < 1e-9
+    assert got["sample_len"] == counted.mean() and np.any(adv != 0)
+    loss, grads = policy_grads(orc, data_r, dfed.astype(np.int64), dlast, adv, END, drop)
+    assert abs(got["loss"] - loss) < 1e-4 * max(1, abs(loss))
+    for k in M.NICDense.TRAINABLE:
+        gk = model.get_gradient(k) + 2 * LAM.get(k, 0.0) * orc.p[k]
+        assert np.abs(gk - grads[k]).max() <= 1e-4 * np.abs(grads[k]).max() + 1e-9, k
+
+
+@pytest.mark.parametrize("K,baseline", [(4, "mean"), (1, "greedy")])
+def test_config2_step_is_finite(K, baseline):
+    from masters_thesis_amd.model_base import SelfCritical
+    sc = SelfCritical(END, n_samples=K, baseline=baseline)
+    model, _, data, tgt = _case("config2", sc)
+    w0 = model.get_weight("lstm/kernel")
+    for _ in range(3):
+        got = model.train_step((data, tgt)).as_floats()          # raises DeviceGuardError if the guard tripped
+        assert all(np.isfinite(v) for v in got.values()), got
+        assert 1 <= got["sample_len"] <= 15 and got["reward"] >= 0
+    model.check_device_errors()
+    assert np.isfinite(model.get_weight("lstm/kernel")).all() and not np.array_equal(model.get_weight("lstm/kernel"), w0)
+    assert model.cap.shape == (64 * K, 15)
+
+
+@pytest.mark.parametrize("K,baseline", [(2, "greedy"), (2, "mean")])
+def test_launch_plan_replay_equals_graph_replay(K, baseline):
+    """Four SCST steps (eager, record / capture, two replays) as launch plans and as hipGraphs: bit-identical metrics,
+    sampled ids and weights"""
+    from masters_thesis_amd.model_base import SelfCritical
+    sc = SelfCritical(END, n_samples=K, baseline=baseline, reward="bleu4")
+    models = [_case("small", sc, rates=(0.1, 0.2, 0.2), seed=5, plan=p) for p in (True, False)]
+    mets, feds = [[], []], [[], []]
+    for _ in range(4):
+        for i, (m, _, data, tgt) in enumerate(models):
+            mets[i].append(m.train_step((data, tgt)).as_floats())
+            feds[i].append(m.cap.cpu().numpy().copy())
+    assert mets[0] == mets[1]
+    for a, b in zip(*feds):
+        assert np.array_equal(a, b)
+    assert not np.array_equal(feds[0][3], feds[0][2])           # a new stream step, new draws
+    a, b = models[0][0], models[1][0]
+    assert isinstance(a._graphs[("scst_update", 8 * K, 6)], tuple)                  # a recorded plan
+    assert isinstance(b._graphs[("scst_update", 8 * K, 6)], torch.cuda.CUDAGraph)
+    for k in a.trainable_names():
+        assert np.array_equal(a.get_weight(k), b.get_weight(k)), k
+
+
+def test_sampled_reward_rises_on_a_synthetic_task():
+    """every scan's reference is <start> 5 6 7 8 <end>: 200 SCST steps (K = 4, "mean", BLEU-4) raise the mean sampled
+    reward of the last 20 steps above that of the first 20"""
+    from masters_thesis_amd.model_base import SelfCritical
+    from masters_thesis_amd.nic import NIC
+    from masters_thesis_amd.optimizers import Adam
+    B, N, T, V, U, E = 16, 32, 7, 16, 32, 16
+    sc = SelfCritical(END, n_samples=4, baseline="mean", reward="bleu4")
+    m = NIC(N, U, E, V, T, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, seed=3, self_critical=sc)
+    m.compile(Adam(1e-2, clipnorm=None))
+    rng = np.random.default_rng(0)
+    x = rng.standard_normal((B, N)).astype(np.float32)
+    cap = np.zeros((B, T), np.int32)
+    cap[:, 0] = 1
+    cap[:, 1:6] = [5, 6, 7, 8, END]
+    z = np.zeros((B, U), np.float32)
+    rewards = [m.train_step(((x, cap, z, z), cap)).as_floats()["reward"] for _ in range(200)]
+    first, last = float(np.mean(rewards[:20])), float(np.mean(rewards[-20:]))
+    print(f"mean sampled reward: first 20 steps {first:.4f}, last 20 {last:.4f}")
+    assert last > first
