@@ -333,7 +333,12 @@ __global__ __launch_bounds__(256) void sam_kernel(float* theta, float* grad_rw, 
     const float w = theta[off + i];
     const float e = (grad_rw[off + i] + lam2 * w) * scale;
     ew[off + i] = e;
-    theta[off + i] = w + e;
+    {
+      // theta + e_w is the float32 add of the STORED e_w (param.assign_add(e_w)); contracted into fma(g, scale, w) the
+      // weights moved by the unrounded product and mode 1's theta - e_w was not the inverse of this step
+#pragma clang fp contract(off)
+      theta[off + i] = w + e;
+    }
   }
 }
 

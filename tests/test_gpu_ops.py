@@ -1999,3 +1999,153 @@ def test_dropout_metric_rider(be, T, B, R):
     be.dropout_metric(x, y1, T * B, H, H, B, H, 0, 0.4, 99, 7, 0, step_dev, alpha, p1, T, B, R)
     torch.cuda.synchronize()
     assert torch.equal(y0, y1) and torch.equal(p0, p1)
+
+
+# -------------------------------------------------- fused encoder-tail paths of the dense model, small row ops
+@pytest.mark.parametrize("rows,C,T,V,training,rates,emb_rate", [
+    (64, 512, 15, 5001, True, (0.2, 0.2), 0.2), (64, 512, 15, 5001, False, (0.0, 0.0), 0.0),
+    (5, 36, 7, 31, True, (0.1, 0.0), 0.0), (33, 96, 4, 50, True, (0.0, 0.3), 0.3)])
+def test_enc_tail_fwd_sk_emb_equals_composition(be, rows, C, T, V, training, rates, emb_rate):
+    """tnt_enc_tail_fwd_sk_emb_f32 (the encoder tail + the Embedding gather and its input dropout of the rows behind the
+    features, nic.py's emb ride) bit-identical to tnt_enc_tail_fwd_sk_f32 followed by embedding_fwd(_drop)"""
+    rng = np.random.default_rng(rows + C + T)
+    ns = 3
+    part = dev(rng.standard_normal((ns, rows, C)) * 0.5)
+    bias, gamma, beta = dev(0.1 * rng.standard_normal(C)), dev(1 + 0.1 * rng.standard_normal(C)), dev(0.1 * rng.standard_normal(C))
+    mm0, mv0 = 0.1 * rng.standard_normal(C), 1 + 0.1 * rng.random(C)
+    table, ids = dev(rng.standard_normal((V, C))), dev(rng.integers(0, V, (rows, T)), torch.int32)
+    step_dev = torch.tensor([6], dtype=torch.int32, device="cuda")
+    seed, sf, sl, se = 77, 2, 48, 49
+    r_feat, r_lstm = rates if training else (0.0, 0.0)
+    res = []
+    for fused in (False, True):
+        f = lambda *s: torch.full(s, 7.0, dtype=torch.float32, device="cuda")
+        pre, out, xhat, inv, mm, mv = f(rows, C), f(rows + T * rows, C), f(rows, C), f(max(rows, C)), dev(mm0), dev(mv0)
+        targs = (part, ns, bias, pre, 0.2, gamma, beta, mm, mv, out, xhat, inv, rows, C, C, training, 1e-3, 0.99, r_feat, r_lstm,
+                 seed, sf, sl, step_dev)
+        if fused:
+            be.enc_tail_fwd_sk_emb(*targs, table, ids, out[rows:], rows, T, V, emb_rate, se)
+        else:
+            be.enc_tail_fwd_sk(*targs)
+            if emb_rate > 0:
+                be.embedding_fwd_drop(table, ids, f(T * rows, C), out[rows:], rows, T, C, C, V, emb_rate, seed, se, 0, step_dev)
+            else:
+                be.embedding_fwd(table, ids, out[rows:], rows, T, C, C, V)
+        res.append((pre, out, xhat, inv, mm, mv))
+    torch.cuda.synchronize()
+    for k, (a_, b_) in enumerate(zip(*res)):
+        assert torch.equal(a_, b_), k
+    emb = res[1][1][rows:].view(T, rows, C).permute(1, 0, 2).cpu().numpy()
+    want = O.embedding_fwd(table.cpu().numpy(), ids.cpu().numpy())
+    if emb_rate > 0:
+        want = np.where(keep_mask((rows, T, C), emb_rate, seed, se, 6), want / np.float32(1 - emb_rate), 0.0)
+    close(emb, want, rtol=1e-6)
+
+
+@pytest.mark.parametrize("rows,C,T,rates,drop_rate,tmajor", [
+    (64, 512, 15, (0.2, 0.2), 0.2, True), (64, 512, 15, (0.2, 0.2), 0.2, False), (5, 36, 7, (0.1, 0.0), 0.3, True),
+    (33, 96, 4, (0.0, 0.0), 0.0, True), (33, 96, 4, (0.0, 0.3), 0.5, False)])
+def test_enc_tail_bwd_drop_equals_composition(be, rows, C, T, rates, drop_rate, tmajor):
+    """tnt_enc_tail_bwd_drop_f32 (the encoder tail backward + the text rows' LSTM-input dropout' in one launch) bit-identical
+    to tnt_enc_tail_bwd_f32 + an in-place dropout of drop_x: the two branches nic.py takes with the ride on / off"""
+    rng = np.random.default_rng(rows + C + T + 1)
+    r_feat, r_lstm = rates
+    dX0 = rng.standard_normal((rows + T * rows, C))
+    xhat, gamma, inv = dev(rng.standard_normal((rows, C))), dev(1 + 0.1 * rng.standard_normal(C)), dev(1 + rng.random(max(rows, C)))
+    pre = dev(rng.standard_normal((rows, C)))
+    step_dev = torch.tensor([3], dtype=torch.int32, device="cuda")
+    seed, sf, sl, sd = 77, 2, 48, 49
+    tB = rows if tmajor else 0
+    res = []
+    for fused in (False, True):
+        dX = dev(dX0)
+        f = lambda *s: torch.full(s, 7.0, dtype=torch.float32, device="cuda")
+        dpre, dg, db, dbias = f(rows, C), f(C), f(C), f(C)
+        targs = (dX, xhat, gamma, inv, pre, dpre, dg, db, dbias, rows, C, C, r_feat, r_lstm, 0.2, seed, sf, sl, step_dev)
+        if fused:
+            be.enc_tail_bwd_drop(*targs, dX[rows:], T * rows, C, C, tB, C, 0, drop_rate, sd)
+        else:
+            be.enc_tail_bwd(*targs)
+            if drop_rate > 0:
+                be.dropout(dX[rows:], dX[rows:], T * rows, C, C, tB, C, 0, drop_rate, seed, sd, 0, step_dev)
+        res.append((dX, dpre, dg, db, dbias))
+    torch.cuda.synchronize()
+    for k, (a_, b_) in enumerate(zip(*res)):
+        assert torch.equal(a_, b_), k
+    if drop_rate > 0:                                          # the text rows: dropout' of the logical (B, T, C) layout
+        got = res[1][0][rows:].cpu().numpy()
+        shape = (rows, T, C) if tmajor else (T * rows, 1, C)
+        k = keep_mask(shape, drop_rate, seed, sd, 3)
+        k = k.transpose(1, 0, 2).reshape(T * rows, C) if tmajor else k.reshape(T * rows, C)
+        close(got, np.where(k, dX0[rows:].astype(np.float32) / np.float32(1 - drop_rate), 0.0), rtol=1e-6)
+
+
+def test_enc_tail_bwd_drop_refuses_bad_arguments(be):
+    """C % 4 != 0, drop_rate >= 1 and drop_rows % drop_tmajor_B != 0 are refused with an error code; nothing is written"""
+    from masters_thesis_amd._lib import KernelLibraryError
+    rows, C, T = 8, 36, 3
+    rng = np.random.default_rng(5)
+    dX = dev(rng.standard_normal((rows + T * rows, C)))
+    xhat, gamma, inv, pre = dev(rng.standard_normal((rows, C))), dev(np.ones(C)), dev(np.ones(C)), dev(rng.standard_normal((rows, C)))
+    outs = [torch.full(s, 7.0, device="cuda") for s in ((rows, C), (C,), (C,), (C,))]
+    dX0 = dX.clone()
+    step_dev = torch.tensor([3], dtype=torch.int32, device="cuda")
+    for Ck, rate, drows in ((34, 0.2, T * rows), (C, 1.0, T * rows), (C, 0.2, T * rows - 2)):
+        with pytest.raises(KernelLibraryError):
+            be.enc_tail_bwd_drop(dX, xhat, gamma, inv, pre, *outs, rows, Ck, C, 0.1, 0.2, 0.2, 77, 2, 48, step_dev,
+                                 dX[rows:], drows, C, C, rows, C, 0, rate, 49)
+    torch.cuda.synchronize()
+    assert torch.equal(dX, dX0) and all(float(o.min()) == 7.0 == float(o.max()) for o in outs)
+
+
+@pytest.mark.parametrize("j0,j1", [((2048, 512, 512), (64, 2048, 2052)), ((2048, 37, 40), (1, 5, 5)),
+                                   ((960, 2048, 2048), (15, 999, 1001)), ((7, 4, 4), (2047, 3, 8))])
+def test_colsum2(be, j0, j1):
+    """two column-sum jobs of different rows / C / ld in one launch (up to T * B = 2048 rows, C % 4 != 0)"""
+    rng = np.random.default_rng(sum(j0) + sum(j1))
+    xs, outs = [], []
+    for rows, C, ld in (j0, j1):
+        xs.append(rng.standard_normal((rows, ld)) + 0.5)
+        outs.append(torch.full((C + 4,), 7.0, device="cuda"))
+    be.colsum2(dev(xs[0]), outs[0], *j0, dev(xs[1]), outs[1], *j1)
+    torch.cuda.synchronize()
+    for x, out, (rows, C, ld) in zip(xs, outs, (j0, j1)):
+        close(out[:C], x[:, :C].sum(0))
+        assert float(out[C:].min()) == 7.0 == float(out[C:].max())
+
+
+@pytest.mark.parametrize("B,R,Din,Dout", [(5, 3, 1, 17), (7, 4, 17, 1), (6, 3, 64, 64), (5, 2, 17, 64), (3, 2, 64, 17),
+                                          (64, 36, 32, 32), (1, 1, 1, 1)])
+def test_block_dense_dx(be, B, R, Din, Dout):
+    """input gradient of the per-region Dense stack: dx[b, r] = W[r] @ dpre[b, r] against float64"""
+    rng = np.random.default_rng(B * R + Din + Dout)
+    W, dpre = rng.standard_normal((R, Din, Dout)), rng.standard_normal((B, R, Dout))
+    dx = torch.full((B * R * Din + 4,), 7.0, device="cuda")
+    be.block_dense_dx(dev(dpre), dev(W), dx, B, R, Din, Dout)
+    torch.cuda.synchronize()
+    close(dx[:B * R * Din].view(B, R, Din), np.einsum("rkn,brn->brk", W, dpre))
+    assert float(dx[B * R * Din:].min()) == 7.0 == float(dx[B * R * Din:].max())
+
+
+def test_block_dense_dx_refuses_wide_layers(be):
+    from masters_thesis_amd._lib import KernelLibraryError
+    W, dpre, dx = torch.zeros(2 * 65 * 65, device="cuda"), torch.zeros(3 * 2 * 65, device="cuda"), torch.full((3 * 2 * 65,), 7.0, device="cuda")
+    for Din, Dout in ((65, 16), (16, 65)):
+        with pytest.raises(KernelLibraryError):
+            be.block_dense_dx(dpre, W, dx, 3, 2, Din, Dout)
+    torch.cuda.synchronize()
+    assert float(dx.min()) == 7.0 == float(dx.max())
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1025, 15 * 64 * 360])
+@pytest.mark.parametrize("c", [0.0, 1 / 360])
+def test_sqdiff_mean(be, n, c):
+    """mean((c - x)^2) of the attention metric (c = 1 / R) against float64"""
+    rng = np.random.default_rng(n)
+    x = rng.random(n) * 2 / 360
+    out = torch.full((2,), 7.0, device="cuda")
+    be.sqdiff_mean(dev(x), out, n, c)
+    torch.cuda.synchronize()
+    xf = x.astype(np.float32).astype(np.float64)
+    close(out[:1], [((np.float32(c) - xf) ** 2).mean()])
+    assert float(out[1]) == 7.0
