@@ -1,18 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark: caption-tokens/sec, training (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense|attention] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense|attention] [--dump-outputs DIR] [--full]
 
 One "step" = one full train_step (forward + backward + clip + Adam) of the hot path on one
 synthetic batch already resident in HBM.  Workload at N=1 is BASELINE config 2
-(20k-voxel dense encoder + 512-unit LSTM, B=64, T=15, V=5001); config 3 (region-wise encoder +
-attention) is timed in the same run and reported as the ``config3`` sub-object (``--workload
-attention`` makes it the headline instead).  N>1: one process per GPU, weak scaling (B=64 per
-GPU), gradient exchange over RCCL; when WORLD_SIZE is not set the script starts the N ranks itself
-(``python -m torch.distributed.run``, before anything touches the GPU) and relays rank 0's line.
-Rank 0 prints ONE JSON line.
+(20k-voxel dense encoder + 512-unit LSTM, B=64, T=15, V=5001); ``--workload attention`` makes
+config 3 (region-wise encoder + attention) the headline instead.  N>1: one process per GPU, weak
+scaling (B=64 per GPU), gradient exchange over RCCL; when WORLD_SIZE is not set the script starts
+the N ranks itself (``python -m torch.distributed.run``, before anything touches the GPU) and relays
+rank 0's line.  Rank 0 prints ONE JSON line.
 
-``roofline`` describes the C-ABI call group that takes the most device time per step, found live:
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, the
+outputs of --dump-outputs, the result line.  ``--full`` adds what takes runs of its own: the
+per-step percentiles, the live roofline and per-kernel table below, config 3 timed in the same
+run (the ``config3`` sub-object), the world-size-1 rehearsal of the data-parallel schedule
+(``dp_world1``) and the numpy CPU baseline (``cpu_baseline``).
+
+``roofline`` (--full) describes the C-ABI call group that takes the most device time per step, found live:
 one eager step is recorded (every launch goes through HipBackend._call), each distinct call is then
 timed back to back with HIP events on the launch stream, and its algorithmic work (SURVEY 8d
 formulas at the run's dims) is priced against the gfx950 peak that bounds it.  ``kernels`` lists the
@@ -390,7 +395,7 @@ def dp_world1_rehearsal(args, device):
     for name, wl, extra in (("dense", "dense", {}), ("attention", "attention", {}),
                             ("dense_row_sharded_encoder", "dense", {"TNT_DP_SHARD_ENC": "1"})):      # opt-in form (dp.py)
         cmd = [sys.executable, os.path.abspath(__file__), "--force-dp", "--workload", wl, "--steps", str(min(args.steps, 200)),
-               "--warmup", str(min(args.warmup, 20)), "--no-cpu-baseline", "--no-config3", "--no-dp-world1"]
+               "--warmup", str(min(args.warmup, 20))]        # a plain run: ms_per_step is all that is read
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         env["MASTER_PORT"] = str(29600 + os.getpid() % 300)
@@ -426,11 +431,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="dense", choices=["dense", "attention"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config3", action="store_true", help="skip the config-3 sub-measurement of the default run")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: step percentiles, "
+                    "roofline and per-kernel table, config 3, the data-parallel rehearsal and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--no-config3", action="store_true", help="skip config 3 (its measurement under --full, its outputs under "
+                    "--dump-outputs)")
     ap.add_argument("--host-inputs", action="store_true", help="feed numpy batches (PCIe-inclusive rate; never the headline value)")
     ap.add_argument("--force-dp", action="store_true", help="run the data-parallel schedule even at world size 1 (rehearsal)")
-    ap.add_argument("--no-dp-world1", action="store_true", help="skip the world-size-1 rehearsal of the data-parallel schedule")
+    ap.add_argument("--no-dp-world1", action="store_true", help="skip the world-size-1 rehearsal of the data-parallel schedule "
+                    "(--full)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (metrics and weights of each "
                     "timed workload) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -478,8 +487,9 @@ def main():
     last_timed = []
     el, seq_note = timed_steps(model, batch, args.steps, args.warmup, world, dist, device, last_timed)
     dump = step_outputs(model, last_timed[0]) if args.dump_outputs and rank == 0 else None
-    pct = step_percentiles(model, batch, min(args.steps, 200)) if args.steps >= 10 else None
-    last = model.train_step(batch).as_floats()
+    last = last_timed[0].as_floats()     # final_loss: the loss of the last timed step, in either kind of run
+    if args.full:
+        pct = step_percentiles(model, batch, min(args.steps, 200)) if args.steps >= 10 else None
     model.check_device_errors()          # a guard trip of the persistent LSTM kernel would void the run
 
     if rank == 0:
@@ -492,15 +502,17 @@ def main():
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic" + (" (host numpy batches, PCIe-inclusive)" if args.host_inputs else ""),
             "config": {"workload": WORKLOAD_NAME[args.workload], "global_batch": B * world, "seq_len": T,
-                       "parallelism": f"dp{world}", "final_loss": round(last["loss"], 4), "step_ms_p10_p50_p90": pct},
+                       "parallelism": f"dp{world}", "final_loss": round(last["loss"], 4)},
         }
+        if args.full:
+            out["config"]["step_ms_p10_p50_p90"] = pct
         # how the step's launches are re-issued: recorded launch plans (ModelBase._run_planned) or a hipGraph
         plans = [k for k, v in model._graphs.items() if isinstance(v, tuple)]
         out["config"]["replay"] = ("launch plan" if plans and len(plans) == len(model._graphs) else
                                    "launch plans + hipGraph segments" if plans else "hipGraph")
         if seq_note:
             out["config"]["note"] = seq_note
-        if not use_dp:
+        if args.full and not use_dp:
             dom, others, total = kernel_breakdown(model, batch, args.workload)
             out["roofline"] = dom
             out["kernels"] = others
@@ -508,7 +520,9 @@ def main():
         gf = STEP_GFLOP[args.workload]
         out["step_frac"] = {"gflop_per_step": gf, "achieved_tflops": round(gf / ms, 2), "peak": MFMA_F32_PEAK_TF,
                             "frac": round(gf / ms / MFMA_F32_PEAK_TF, 4)}
-        if world == 1 and not use_dp and args.workload == "dense" and not args.no_config3:
+        # config 3 runs under --full, and under --dump-outputs alone for its outputs (its timing is then not reported)
+        if (world == 1 and not use_dp and args.workload == "dense" and not args.no_config3
+                and (args.full or dump is not None)):
             del model
             torch.cuda.empty_cache()
             m3 = make_model("attention", device, None)
@@ -517,16 +531,17 @@ def main():
             el3, _ = timed_steps(m3, batch, k3, min(args.warmup, 20), 1, None, device, last_timed3)
             if dump is not None:
                 dump.update(step_outputs(m3, last_timed3[0], "config3__"))
-            ms3 = el3 / k3 * 1e3
-            dom3, others3, total3 = kernel_breakdown(m3, batch, "attention")
+            if args.full:
+                ms3 = el3 / k3 * 1e3
+                dom3, others3, total3 = kernel_breakdown(m3, batch, "attention")
+                out["config3"] = {"workload": WORKLOAD_NAME["attention"], "steps": k3, "ms_per_step": round(ms3, 4),
+                                  "value": round(B * T * k3 / el3, 1), "unit": "caption-tokens/s", "roofline": dom3,
+                                  "kernels": others3[:6], "kernel_us_per_step": total3,
+                                  "step_frac": round(STEP_GFLOP["attention"] / ms3 / MFMA_F32_PEAK_TF, 4)}
             m3.check_device_errors()
-            out["config3"] = {"workload": WORKLOAD_NAME["attention"], "steps": k3, "ms_per_step": round(ms3, 4),
-                              "value": round(B * T * k3 / el3, 1), "unit": "caption-tokens/s", "roofline": dom3,
-                              "kernels": others3[:6], "kernel_us_per_step": total3,
-                              "step_frac": round(STEP_GFLOP["attention"] / ms3 / MFMA_F32_PEAK_TF, 4)}
-        if world == 1 and not use_dp and not args.no_dp_world1:
+        if args.full and world == 1 and not use_dp and not args.no_dp_world1:
             out["dp_world1"] = dp_world1_rehearsal(args, device)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload, host_batch)
         if dump is not None:
             write_outputs(args.dump_outputs, dump)
