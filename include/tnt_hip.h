@@ -561,15 +561,18 @@ int32_t tnt_gru_step_bwd_f32(const float* drec_next, const float* Uk, const floa
  * alias logits): (p - onehot)*gscale, zero rows where the clip is active.
  * from_logits=1: tf SparseCategoricalCrossentropy(from_logits=True) (ThinkAndTell/train.py:262-263):
  * loss = logsumexp - x_y, no clipping.  mask_zero=1: rows whose target id is 0 give zero loss
- * and zero gradient (CaptionGenerator.loss_function, ThinkAndTell/model.py:319-334). */
+ * and zero gradient (CaptionGenerator.loss_function, ThinkAndTell/model.py:319-334).
+ * Pad columns [V, ld) of logits are ignored; those of an output are either left as they were or written
+ * as zero (seqops.hip: softmax_cce_reg_kernel).  rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0,
+ * ld < V, null logits. */
 int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* target, float* probs,
                             float* loss_row, float* correct_row, float* dlogits,
                             int32_t rows, int32_t V, int32_t ld, float gscale,
                             int32_t from_logits, int32_t mask_zero, void* stream);
-/* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v. */
+/* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v (first max wins).
+ * B == 0 or T == 0 is a no-op; TNT_BADARG for B < 0, T < 0, V <= 0, null pointers. */
 int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T,
                               int32_t V, void* stream);
-/* row argmax (first max wins), out int32[rows]. */
 /* Beam-search expansion (beam search is only sketched in the reference: lc_NIC.py:640-692,
  * ThinkAndTell/evaluate.py:203-228).  Rows b*k .. b*k+k-1 of probs [B*k][ld] are the k beams of sample b; candidate
  * (beam j, token v) scores score_in[j] + log(max(p, 1e-30)); a finished beam (fin_in != 0: it has emitted end_id)
@@ -595,6 +598,8 @@ int32_t tnt_beam_step_f32(const float* probs, int32_t ld, const float* score_in,
                           int32_t V, int32_t k, int32_t end_id, float* score_out, int32_t* parent, int32_t* token,
                           int32_t* fin_out, const float* h_in, const float* c_in, int32_t ldh, int32_t U,
                           float* h_out, float* c_out, void* stream);
+/* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
+ * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,
                             void* stream);
 /* Greedy feedback step of the free-running decoder (lc_NIC.call_naive_attention, lc_NIC.py:175-221), one launch per

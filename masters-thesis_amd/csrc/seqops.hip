@@ -402,7 +402,10 @@ __global__ __launch_bounds__(256) void softmax_cce_kernel(const float* logits, c
 // instruction-bound at V = 5001 (1750 instructions per wave: index-tracking argmax, two expf per element,
 // per-element target select); here the inner work per element is mask, max, expf, add, mul -- the argmax
 // index is recovered from an equality pass and the target element is patched by its owner afterwards.
-// Pad columns [V, ld) are read (they are zero by the layout contract) and rewritten as zero.
+// Pad columns [V, ld) take no part in any result: they are masked to -inf as they are read, whatever they hold.
+// The kernel touches only its window [0, 1024*NV4) of each row: a pad column inside the window is written as zero
+// in every output (probs, dlogits) the call writes, and one at or beyond it (ld > 1024*NV4, e.g. V = 1024 with
+// ld = 1028) is neither read nor written.  The generic kernel above neither reads nor writes any pad column.
 template <int NV4>
 __global__ __launch_bounds__(256) void softmax_cce_reg_kernel(const float* logits, const int* target, float* probs,
                                                               float* loss_row, float* correct_row, float* dlogits,
@@ -697,7 +700,11 @@ extern "C" int32_t tnt_embedding_bwd_f32(const float* drows, const int32_t* ids,
 extern "C" int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* target, float* probs, float* loss_row,
                                        float* correct_row, float* dlogits, int32_t rows, int32_t V, int32_t ld,
                                        float gscale, int32_t from_logits, int32_t mask_zero, void* stream) {
-  if (rows <= 0) return 0;
+  if (rows == 0) return 0;               // an empty batch tail: callers rely on a no-op here
+  if (rows < 0) return TNT_BADARG(6);
+  if (V <= 0) return TNT_BADARG(7);
+  if (ld < V) return TNT_BADARG(8);
+  if (!logits) return TNT_BADARG(0);
   hipStream_t s = tnt_stream(stream);
   const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
                   (!dlogits || tnt_aligned16(dlogits));
@@ -720,12 +727,21 @@ extern "C" int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* targe
 
 extern "C" int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T, int32_t V,
                                          void* stream) {
+  if (B < 0 || T < 0) return TNT_BADARG(2);
+  if (V <= 0) return TNT_BADARG(4);
+  if (!onehot || !ids_tmajor) return TNT_BADARG(0);
+  if (B == 0 || T == 0) return 0;
   hipLaunchKernelGGL(onehot_argmax_kernel, dim3(B * T), dim3(256), 0, tnt_stream(stream), onehot, ids_tmajor, B, T, V);
   TNT_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld, void* stream) {
+  if (rows < 0) return TNT_BADARG(2);
+  if (V <= 0) return TNT_BADARG(3);
+  if (ld < V) return TNT_BADARG(4);
+  if (!x || !out) return TNT_BADARG(0);
+  if (rows == 0) return 0;
   hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(256), 0, tnt_stream(stream), x, out, rows, V, ld);
   TNT_LAUNCH_CHECK();
   return 0;
