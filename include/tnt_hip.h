@@ -697,6 +697,25 @@ int32_t tnt_scheduled_feedback2_f32(const float* logits, int32_t ld, int32_t V, 
 int32_t tnt_scst_cce_f32(const float* logits, int32_t ld, int32_t V, const int32_t* fed, int32_t T, const int32_t* last,
                          const float* adv, int32_t end_id, float* loss_row, float* lp_row, float* dlogits, int32_t R,
                          float gscale, void* stream);
+/* Caption log-likelihood scoring (nic.NIC.score_captions, lc_nic.NIC.score_captions; library-defined, restated by
+ * tests/score_oracle.py): log p(caption | scan) of R captions from the logits of the teacher-forced inference forward,
+ * read-only.  cap [R][T] holds a caption's ids w_0 .. w_{T-1} (w_0 the start token); logits [steps*R][ld], V valid columns,
+ * row (j-1)*R + r = the logits x_j that the step fed with w_{j-1} yields for position j of caption r, j = 1 .. steps
+ * (steps in 1 .. T-1).
+ *  - lp_j = x_j[w_j] - logsumexp(x_j): no clip at 1e-7, no renormalisation (a log-likelihood, not Keras'
+ *    CategoricalCrossentropy);
+ *  - position j is counted iff none of w_1 .. w_{j-1} is end_id or 0, and w_j != 0: the terminator itself counts, padding
+ *    never does; end_id = -1: up to the first 0;
+ *  - tok_lp[(j-1)*R + r] (nullable) = lp_j at counted positions, 0 elsewhere; cap_len[r] (nullable) = the number of
+ *    counted positions; cap_lp[r] = the sum of lp_j over the counted positions, added in ascending j in float32 (0 for a
+ *    caption without counted positions).
+ * The ids are device data: a counted id outside [0, V) gives NaN for that position and that caption, and no read.  The
+ * logits of a row that is not counted, and the pad columns [V, ld), are never read; nothing is written to the logits.
+ * With tok_lp: one 256-thread workgroup per logits row, then one thread per caption adds that caption's tok_lp entries;
+ * without: one workgroup per caption walks its rows.  Same bits either way and run to run (no atomics), no scratch memory.
+ * TNT_BADARG for null logits / cap / cap_lp, V < 1, ld < V, T < 2, R < 1, end_id >= V, steps outside 1 .. T-1. */
+int32_t tnt_caption_score_f32(const float* logits, int32_t ld, int32_t V, const int32_t* cap, int32_t T, int32_t steps,
+                              int32_t R, int32_t end_id, float* tok_lp, float* cap_lp, int32_t* cap_len, void* stream);
 /* out[0] = scale * sum_i x[i]  (fixed-order, one workgroup). */
 /* Categorical sampling per row (tf.random.categorical(logits / temperature, 1): ThinkAndTell/evaluate.py:223,278;
  * lc_NIC.sample_choice lc_NIC.py:571-575 samples from log(probs)).  x: logits (from_logits=1) or probabilities.

@@ -257,3 +257,42 @@ class CiderD:
         """the score of one candidate against its references (one document: the scorer's corpus frequencies, or,
         without a corpus, these references alone)"""
         return float(self.batch_scores([[candidate]], [references])[0][0])
+
+
+# ---------------------------------------------------------------------------------------------------- likelihood metrics
+def caption_perplexity(model, betas, a0, c0, captions, end_id):
+    """Per-token perplexity of the batch's own captions under ``model`` (score_captions): exp(-sum logprob / sum length)
+    over the batch; padding is not counted and probabilities are not clipped (unlike the Keras loss test_step reports).
+    Returns (perplexity, logprob (B,), length (B,))."""
+    lp, length = model.score_captions(betas, a0, c0, captions, end_id=end_id)
+    total = int(length.sum())
+    ppl = float(np.exp(-float(lp.astype(np.float64).sum()) / total)) if total > 0 else float("nan")
+    return ppl, lp, length
+
+
+def identification(model, betas, a0, c0, captions, end_id, normalise=None, max_rows=None):
+    """n-way identification: every scan of the batch scored against all B captions of the batch (the candidate path of
+    score_captions with C = B, chunked by ``max_rows``).  Candidate rows with the same ids count as one candidate.
+    Returns a dict: scores (B, B) (scores[b, c] = log p(caption c | scan b), length-normalised with normalise="mean"),
+    rank (B,) = the number of distinct candidates scoring strictly higher than scan b's own caption, top1 (fraction of
+    rank 0) and mrr (mean of 1 / (rank + 1))."""
+    caps = np.asarray(captions.detach().cpu().numpy() if hasattr(captions, "detach") else captions)
+    if caps.ndim != 2:
+        raise ValueError(f"identification takes the batch's captions (B, T), got {caps.shape}")
+    B = caps.shape[0]
+    cand = np.ascontiguousarray(np.broadcast_to(caps[None], (B,) + caps.shape))
+    scores, _ = model.score_captions(betas, a0, c0, cand, end_id=end_id, normalise=normalise, max_rows=max_rows)
+    rank = identification_ranks(scores, caps)
+    return dict(scores=scores, rank=rank, top1=float((rank == 0).mean()), mrr=float((1.0 / (rank + 1.0)).mean()))
+
+
+def identification_ranks(scores, captions):
+    """rank of candidate b for scan b in a (B, B) score matrix: the number of distinct candidates (rows of ``captions``
+    with other ids) scoring strictly higher"""
+    caps = np.asarray(captions)
+    _, first = np.unique(caps, axis=0, return_index=True)
+    keep = np.zeros(len(caps), bool)
+    keep[first] = True                                   # one representative per distinct caption
+    scores = np.asarray(scores)
+    own = scores[np.arange(len(caps)), np.arange(len(caps))]
+    return ((scores > own[:, None]) & keep[None, :]).sum(1).astype(np.int64)

@@ -1373,6 +1373,85 @@ class NIC(ModelBase):
 
     greedy_predict_attention = greedy_predict
 
+    # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
+    def _score_refuse(self):
+        if self.S > 1:
+            raise NotImplementedError("score_captions is built for one subject: n_subjects > 1 is not supported")
+        if self.use_layer_norm:
+            raise NotImplementedError("score_captions is not built for the LayerNorm LSTM cell (use_layer_norm=True)")
+        if self.grad_sync is not None:
+            raise NotImplementedError("score_captions has no data-parallel schedule: score on one device")
+
+    def _score_chain(self, R):
+        """the persistent attention -> LSTM chain applies to a scoring pass of R rows"""
+        return bool(self._lc_seq_ok() and R <= 128 and self.be.lstm_seq_supported(R, self.U))
+
+    def _score_bufs(self, Rmax, T):
+        """decoder buffers of one scoring pass of up to Rmax rows: the gathered region features F and their loop-invariant
+        projection P, T-1 attention -> LSTM steps, the head, the kernel's outputs"""
+        f, Rg, D, A, U, Et, H, steps = self._f, self.R, self.D, self.A, self.U, self.Et, self.H, T - 1
+        # the persistent chain (passes of <= 128 rows) keeps every step's attention and gates, the per-step kernels one slab
+        seq_rows = min(Rmax, 128) if self._lc_seq_ok() else 0
+        slab = max(Rmax, steps * seq_rows)
+        work = f(self.be.lc_seq_fwd_work_floats(seq_rows)) if seq_rows else None
+        return dict(cap=torch.zeros(Rmax * T, dtype=torch.int32, device=self.device), F=f(Rmax * Rg * D), P=f(Rmax * Rg * A),
+                    text=f(T * Rmax * Et), xz=f(steps * Rmax * 4 * U), hs=f((steps + 1) * Rmax * U),
+                    cs=f((steps + 1) * Rmax * U), gates=f(slab * 4 * U), qpre=f(slab * A), alpha=f(slab * Rg), ctx=f(slab * D),
+                    ctx_d=f(slab * D), ipre=f(steps * Rmax * H), inter=f(steps * Rmax * H),
+                    logits=f(steps * Rmax * self.ldV), tok_lp=f(steps * Rmax), cap_lp=f(Rmax),
+                    cap_len=torch.zeros(Rmax, dtype=torch.int32, device=self.device), work=work)
+
+    def _score_shape(self, st, R, T):
+        Rg, D, A, U, Et, H, steps = self.R, self.D, self.A, self.U, self.Et, self.H, T - 1
+        pre = lambda k, *shape: st[k][:int(np.prod(shape))].view(*shape)
+        seq = st["work"] is not None and self._score_chain(R)
+        lead = (steps, R) if seq else (R,)
+        return dict(cap=pre("cap", R, T), F=pre("F", R, Rg, D), P=pre("P", R * Rg, A), text=pre("text", T * R, Et),
+                    xz=pre("xz", steps * R, U, 4), hs=pre("hs", steps + 1, R, U), cs=pre("cs", steps + 1, R, U),
+                    gates=pre("gates", *lead, U, 4), qpre=pre("qpre", *lead, A), alpha=pre("alpha", *lead, Rg),
+                    ctx=pre("ctx", *lead, D), ctx_d=pre("ctx_d", *lead, D), ipre=pre("ipre", steps * R, H),
+                    inter=pre("inter", steps * R, H), logits=pre("logits", steps * R, self.ldV),
+                    tok_lp=pre("tok_lp", steps * R), cap_lp=pre("cap_lp", R), cap_len=pre("cap_len", R), seq=seq,
+                    work=st["work"])
+
+    def _score_pass(self, B, Cr, T, end_id, v, first):
+        """one scoring pass over R = B*Cr decoder rows.  ``first``: the inference encoder of the B staged scans (_encode:
+        the normalised region features F and P = LeakyReLU(W1 F + b1)) runs in front.  Then: F, P and the initial state
+        gathered to the R rows (the voxel-wide input is never repeated); the Embedding gather and the text half of the
+        input projection of the T-1 steps; the attention -> LSTM steps as the persistent chain or per step, in inference
+        mode; the two head GEMMs; and tnt_caption_score_f32 on the logits (no softmax launch)."""
+        be, a = self.be, self.arena
+        Rg, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
+        R, steps = B * Cr, T - 1
+        n = steps * R
+        if first:
+            self._encode(B, False)
+        F, P, hs, cs, xz, cap, rep = v["F"], v["P"], v["hs"], v["cs"], v["xz"], v["cap"], v["rep"]
+        be.embedding_fwd(self.F, rep, F, R, 1, Rg * D, Rg * D, B)
+        be.embedding_fwd(self.P, rep, P, R, 1, Rg * A, Rg * A, B)
+        be.embedding_fwd(self.Hs[0], rep, hs[0], R, 1, U, U, B)
+        be.embedding_fwd(self.Cs[0], rep, cs[0], R, 1, U, U, B)
+        be.embedding_fwd(a.p("emb_text/embeddings"), cap, v["text"], R, T, Et, Et, V)   # t-major; rows [0, n) are used
+        Wl, Ur, bl = a.p("lstm/kernel"), a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
+        self.gemm_sk(v["text"], Wl[D:], xz, n, 4 * U, Et, Et, 4 * U, 4 * U)
+        att = (a.p("attention/W2/kernel"), a.p("attention/W2/bias"), a.p("attention/V/kernel"), a.p("attention/V/bias"))
+        if v["seq"]:
+            be.lc_seq_fwd(F, P, *att, v["qpre"], v["alpha"], v["ctx"], v["ctx_d"], None, 0, xz, Wl[:D], Ur, bl, hs, cs,
+                          v["gates"], steps, R, Rg, D, A, U, 0.2, 0.0, 0.0, D + Et, self.seed, S_ATTN, S_LSTM_IN,
+                          self.drop_step, v["work"], self.seq_sync, self._guard_out(), out_drop=None)
+        else:
+            for i in range(steps):
+                be.attention_step_fwd(hs[i], F, P, *att, v["qpre"], v["alpha"], v["ctx"], v["ctx_d"], None, R, Rg, D, A, U,
+                                      0.2, 0.0, 0.0, D + Et, self.seed, S_ATTN + i, S_LSTM_IN + i, 0, self.drop_step,
+                                      keep4=None)
+                be.lstm_step_fwd(xz[i * R:(i + 1) * R], hs[i], cs[i], Ur, v["ctx_d"], Wl[:D], D, None, 0, 0, None,
+                                 hs[i + 1], cs[i + 1], None, v["gates"], R, U, xz_bias=bl)
+        self.gemm_sk(hs[1:].view(n, U), a.p("time_distributed_nonlinear/kernel"), v["inter"], n, H, U, U, H, H,
+                     bias=a.p("time_distributed_nonlinear/bias"), pre=v["ipre"], act=ACT_LEAKY, slope=0.2)
+        self.gemm_sk(v["inter"], a.p("time_distributed_softmax/kernel"), v["logits"], n, V, H, H, ldV, ldV,
+                     bias=a.p("time_distributed_softmax/bias"))
+        be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
+
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
                     length_penalty=0.0):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,

@@ -29,6 +29,9 @@ S_SCST_LAST = 240       # self-critical rollouts: the draw of the last token pos
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
+SCORE_LOGITS_BYTES = 256 << 20      # score_captions: default bound on the logits of one decoder pass (sets max_rows)
+
+
 class ScheduledSampling:
     """Scheduled sampling (Bengio et al. 2015) for the train_step of nic.NIC and lc_nic.NIC; the definitions are
     tnt_scheduled_feedback_f32's and tnt_scheduled_feedback2_f32's (include/tnt_hip.h).  At each step, each caption row is
@@ -1130,6 +1133,110 @@ class ModelBase:
         for f, name, args in st[1]:
             if f(*args) != 0:
                 raise RuntimeError(f"{name} failed while replaying launch plan {key}")
+
+    # ------------------------------------------------------------------ caption scoring
+    def score_captions(self, img_input, a0, c0, captions, end_id=-1, normalise=None, return_tokens=False, max_rows=None):
+        """log p(caption | scan) under the teacher-forced inference forward (definition: tnt_caption_score_f32 in
+        include/tnt_hip.h).  captions: int (B, T), row b the caption of scan b exactly as train_step takes it (column 0 the
+        start token) -> (logprob (B,) float32, length (B,) int32); or int (B, C, T), C candidate captions per scan ->
+        (logprob (B, C), length (B, C)).  A position counts up to and including the first ``end_id`` (-1: none) and never
+        at or behind a 0; length is the number of counted positions.  ``normalise``: None = the sum, "mean" = the sum
+        / max(length, 1).  ``return_tokens``: also tok_lp (B, [C,] T-1), 0 at positions that do not count.
+
+        The encoder runs on the B scans once per call; its result is gathered to the B*C decoder rows on the device (row
+        b*C + c).  ``max_rows`` bounds the decoder rows of one pass: the candidates are processed in chunks of
+        max_rows // B whole candidates over buffers sized for one chunk.  Default: as many whole candidates as keep one
+        pass's logits ((T-1) * ld(V) * 4 bytes per decoder row) within SCORE_LOGITS_BYTES = 256 MiB, at least one.  Each
+        pass is one recorded sequence per (B, chunk, T, end_id), replayed like greedy_predict; the captions reach it
+        through a device buffer, and the results (with the persistent chain's guard word) come back in one copy.
+        The model's weights, optimizer state and Philox counters are not touched."""
+        if normalise not in (None, "mean"):
+            raise ValueError(f"normalise must be None or 'mean', got {normalise!r}")
+        caps = captions.detach().cpu().numpy() if isinstance(captions, torch.Tensor) else np.asarray(captions)
+        if caps.ndim not in (2, 3) or not np.issubdtype(caps.dtype, np.integer):
+            raise ValueError(f"captions must be an integer array (B, T) or (B, C, T), got {caps.dtype} {caps.shape}")
+        flat = caps.ndim == 2
+        caps = np.ascontiguousarray(caps[:, None, :] if flat else caps, dtype=np.int32)
+        B, C, T = caps.shape
+        if B < 1 or C < 1 or T < 2:
+            raise ValueError(f"captions {caps.shape}: need at least one scan, one candidate and two positions")
+        end_id = int(end_id)
+        if end_id >= self.V or end_id < -1 or end_id == 0:
+            raise ValueError(f"end_id must be -1 (none) or a token id in [1, {self.V}), got {end_id}")
+        self._score_refuse()
+        steps = T - 1
+        if max_rows is None:
+            max_rows = max(1, SCORE_LOGITS_BYTES // (steps * self.ldV * 4) // B) * B
+        max_rows = int(max_rows)
+        if max_rows < B:
+            raise ValueError(f"max_rows = {max_rows} is below the batch of {B} scans: one pass holds at least one candidate "
+                             "per scan")
+        Cc = min(C, max_rows // B)
+        self._stage_inputs((img_input, caps[:, 0, :], a0, c0))          # the B scans, their state; builds the (B, T) buffers
+        n = B * C
+
+        def run():
+            st = self._score_state(B, Cc, C, T)
+            st["caps"].copy_(torch.from_numpy(caps), non_blocking=True)
+            res = st["res"]
+            lp_all, len_all = res[:n].view(B, C), res[n:2 * n].view(torch.int32).view(B, C)
+            tok_all = res[2 * n + 1:].view(B, C, steps)
+            for c_lo in range(0, C, Cc):
+                Cr = min(Cc, C - c_lo)
+                v = self._score_views(st, B, Cr, T)
+                v["cap"].view(B, Cr, T).copy_(st["caps"][:, c_lo:c_lo + Cr])
+                first = c_lo == 0
+                self._run_captured(("score", B, Cr, T, end_id, first), lambda: self._score_pass(B, Cr, T, end_id, v, first))
+                lp_all[:, c_lo:c_lo + Cr].copy_(v["cap_lp"].view(B, Cr))
+                len_all[:, c_lo:c_lo + Cr].copy_(v["cap_len"].view(B, Cr))
+                if return_tokens:
+                    tok_all[:, c_lo:c_lo + Cr].copy_(v["tok_lp"].view(steps, B, Cr).permute(1, 2, 0))
+            guard = self._guard_word() is not None
+            if guard:
+                res[2 * n:2 * n + 1].copy_(self.met[self.GUARD:self.GUARD + 1])
+            host = (res if return_tokens else res[:2 * n + 1]).cpu().numpy()         # the call's one device-to-host copy
+            return host, guard and host[2 * n] != 0.0
+        host, tripped = run()
+        if tripped:                  # as _guarded: fall back to the per-step kernels and run once more
+            self.disable_seq_lstm()
+            host, _ = run()
+        lp = host[:n].reshape(B, C).copy()
+        length = host[n:2 * n].view(np.int32).reshape(B, C).copy()
+        if normalise == "mean":
+            lp = lp / np.maximum(length, 1).astype(np.float32)
+        out = (lp[:, 0], length[:, 0]) if flat else (lp, length)
+        if return_tokens:
+            tok = host[2 * n + 1:].reshape(B, C, steps).copy()
+            out += (tok[:, 0] if flat else tok,)
+        return out
+
+    def _score_refuse(self):
+        raise NotImplementedError(f"{type(self).__name__} has no caption scoring")
+
+    def _score_state(self, B, Cc, C, T):
+        """per (B, chunk, C, T): the captions (B, C, T) on the device, the packed results [logprob B*C | length B*C (int32
+        bits) | guard word | tok_lp B*C*(T-1)], and the model's decoder buffers for one chunk of B*Cc rows (_score_bufs),
+        allocated once and viewed per pass (_score_views)"""
+        st = self.__dict__.get("_score")
+        key = (B, Cc, C, T, bool(self.__dict__.get("_seq_lstm")))
+        if st is None or st["key"] != key:
+            n = B * C
+            st = self._score = dict(key=key, caps=torch.zeros(B, C, T, dtype=torch.int32, device=self.device),
+                                    res=self._f(2 * n + 1 + n * (T - 1)), views={})
+            st.update(self._score_bufs(B * Cc, T))
+            for k in [k for k in self._graphs if isinstance(k, tuple) and k and k[0] == "score"]:
+                del self._graphs[k]             # recorded over the buffers just replaced
+        return st
+
+    def _score_views(self, st, B, Cr, T):
+        """the chunk buffers viewed for a pass of R = B*Cr rows (the prefix of each allocation: same addresses every call),
+        and the gather index of the pass (decoder row b*Cr + c <- scan b)"""
+        v = st["views"].get(Cr)
+        if v is None:
+            R = B * Cr
+            v = st["views"][Cr] = self._score_shape(st, R, T)
+            v["rep"] = torch.arange(B, dtype=torch.int32, device=self.device).repeat_interleave(Cr).view(R, 1)
+        return v
 
     def _dp_mean_logs(self, logs):
         """epoch logs averaged over the data-parallel ranks (same keys on every rank, sorted)"""

@@ -948,6 +948,59 @@ class NIC(ModelBase):
             self._run_captured(("sample",) + key + tuple(filt[:3]), run)
         return probs_all, ids
 
+    # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
+    def _score_refuse(self):
+        if self.grad_sync is not None:
+            raise NotImplementedError("score_captions has no data-parallel schedule: score on one device")
+
+    def _score_bufs(self, Rmax, T):
+        """decoder buffers of one scoring pass of up to Rmax rows: T-1 LSTM steps, their logits, the kernel's outputs"""
+        f, U, E, steps = self._f, self.U, self.E, T - 1
+        # the persistent chain (passes of <= 128 rows) keeps the gates of every step, the per-step kernels reuse one slab
+        seq_rows = min(Rmax, 128) if self.__dict__.get("_seq_lstm") else 0
+        return dict(cap=torch.zeros(Rmax * T, dtype=torch.int32, device=self.device), xin=f(T * Rmax * E),
+                    xz=f(steps * Rmax * 4 * U), hs=f((steps + 1) * Rmax * U), cs=f((steps + 1) * Rmax * U),
+                    out=f(steps * Rmax * U), gates=f(max(Rmax, steps * seq_rows) * 4 * U), logits=f(steps * Rmax * self.ldV),
+                    tok_lp=f(steps * Rmax), cap_lp=f(Rmax), cap_len=torch.zeros(Rmax, dtype=torch.int32, device=self.device))
+
+    def _score_shape(self, st, R, T):
+        U, E, steps = self.U, self.E, T - 1
+        pre = lambda k, *shape: st[k][:int(np.prod(shape))].view(*shape)
+        seq = bool(self.__dict__.get("_seq_lstm")) and R <= 128 and self.be.lstm_seq_supported(R, U)
+        return dict(cap=pre("cap", R, T), xin=pre("xin", T * R, E), xz=pre("xz", steps * R, U, 4),
+                    hs=pre("hs", steps + 1, R, U), cs=pre("cs", steps + 1, R, U), out=pre("out", steps, R, U),
+                    gates=pre("gates", steps, R, U, 4) if seq else pre("gates", R, U, 4),
+                    logits=pre("logits", steps * R, self.ldV), tok_lp=pre("tok_lp", steps * R), cap_lp=pre("cap_lp", R),
+                    cap_len=pre("cap_len", R), seq=seq)
+
+    def _score_pass(self, B, Cr, T, end_id, v, first):
+        """one scoring pass over R = B*Cr decoder rows.  ``first``: the inference encoder and the feature LSTM step of the
+        B staged scans (_decode_encode: state in Hs[1], Cs[1]) run in front.  Then: that state gathered to the R rows; the
+        Embedding gather and the input projection of the T-1 text steps; the masked LSTM steps (NIC.py:140's Embedding
+        mask: a fed 0 carries state and output) as the persistent chain or per step; the head GEMM; and
+        tnt_caption_score_f32 on the logits (no softmax launch)."""
+        be, a = self.be, self.arena
+        U, E, V, ldV = self.U, self.E, self.V, self.ldV
+        R, steps = B * Cr, T - 1
+        n = steps * R
+        if first:
+            self._decode_encode(B)
+        hs, cs, out, xz, cap = v["hs"], v["cs"], v["out"], v["xz"], v["cap"]
+        be.embedding_fwd(self.Hs[1], v["rep"], hs[0], R, 1, U, U, B)
+        be.embedding_fwd(self.Cs[1], v["rep"], cs[0], R, 1, U, U, B)
+        be.embedding_fwd(a.p("emb_text/embeddings"), cap, v["xin"], R, T, E, E, V)      # t-major; rows [0, n) are used
+        self.gemm_sk(v["xin"], a.p("lstm/kernel"), xz, n, 4 * U, E, E, 4 * U, 4 * U)
+        Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
+        if v["seq"]:
+            be.lstm_seq_fwd(xz, hs, cs, Ur, bl, cap, T, 0, out, v["gates"], steps, R, U, self.seq_sync, self._guard_out())
+        else:
+            for t in range(steps):
+                be.lstm_step_fwd(xz[t * R:(t + 1) * R], hs[t], cs[t], Ur, None, None, 0, cap, T, t,
+                                 out[t - 1] if t > 0 else None, hs[t + 1], cs[t + 1], out[t], v["gates"], R, U, xz_bias=bl)
+        self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), v["logits"], n, V, U, U, ldV, ldV,
+                     bias=a.p("time_distributed_softmax/bias"))
+        be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
+
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
                     units=None, tokenizer=None):
         """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches

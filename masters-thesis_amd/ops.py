@@ -510,6 +510,12 @@ class HipBackend:
         self._call(self.lib.tnt_scst_cce_f32, "tnt_scst_cce_f32", _p(logits), ld, V, _p(fed), T, _p(last), _p(adv), int(end_id),
                    _p(loss_row), _p(lp_row), _p(dlogits), R, float(gscale), self._s())
 
+    def caption_score(self, logits, ld, V, cap, T, steps, R, end_id, tok_lp, cap_lp, cap_len=None):
+        """log p(caption) of R captions from their teacher-forced logits, read-only (tnt_caption_score_f32; definition in
+        include/tnt_hip.h): row (j-1)*R + r scores token cap[r*T + j], j = 1..steps; tok_lp / cap_len optional"""
+        self._call(self.lib.tnt_caption_score_f32, "tnt_caption_score_f32", _p(logits), ld, V, _p(cap), T, steps, R, int(end_id),
+                   _p(tok_lp), _p(cap_lp), _p(cap_len), self._s())
+
     def sample_rows(self, x, out, rows, V, ld, temperature, from_logits, seed, site, step, step_dev=None):
         self._call(self.lib.tnt_sample_rows_f32, "tnt_sample_rows_f32", _p(x), _p(out), rows, V, ld, float(temperature), int(from_logits),
                                                 int(seed), int(site), int(step), _p(step_dev), self._s())
