@@ -598,6 +598,42 @@ int32_t tnt_beam_step_f32(const float* probs, int32_t ld, const float* score_in,
                           int32_t V, int32_t k, int32_t end_id, float* score_out, int32_t* parent, int32_t* token,
                           int32_t* fin_out, const float* h_in, const float* c_in, int32_t ldh, int32_t U,
                           float* h_out, float* c_out, void* stream);
+/* Constrained decoding: the repetition penalty and the bans of one decode step, applied to the step's logits in place,
+ * in front of the softmax launch (restated by tests/constrain_oracle.py).  Library-defined:
+ *  - Step and history.  logits [rows][ld], V valid columns, are the logits of step i (0-based: the step chooses the token
+ *    at position i).  The history h_0 .. h_{i-1} of row r is the tokens chosen so far on the row's path, the start token
+ *    not among them.  The caller owns two [rows][ldh] int32 buffers used in ping-pong: this launch forms
+ *      hist_out[r][0..i) = hist_in[parent[r]][0..i-1) ++ last_token[r]
+ *    (last_token[r]: the token chosen at step i-1; parent[r]: the global row that r continues, as tnt_beam_step_f32 /
+ *    tnt_beam_topk_f32 write it; parent == NULL: r itself; a parent outside [0, rows) counts as r) and applies the rules
+ *    from it.  Two dependent loads per row; the beam reorder of the history happens in this launch.  hist_out is written
+ *    for every row, finished ones included.  i == 0: no history, hist_in / last_token are not read.  The two buffers
+ *    must not overlap anywhere in their [rows][ldh] extents: one row's wave reads hist_in[parent[r]] while another's
+ *    writes its hist_out row.
+ *  - Rules, in this order, on each logit x_v as a float32:
+ *    1. repetition penalty theta >= 1 (1 = off): for every DISTINCT v in the history, x_v <- x_v / theta if x_v > 0,
+ *       else x_v * theta: once per distinct token, one correctly rounded float32 operation (NaN stays NaN);
+ *    2. bans, x_v <- -inf, overriding 1:
+ *       - every v of bad_ids [n_bad], at every step;
+ *       - v == end_id while i < m (the minimum length);
+ *       - no-repeat n-gram, n >= 1 (0 = off): for every s with s + n - 1 <= i - 1 whose h_s .. h_{s+n-2} equal the last
+ *         n - 1 tokens h_{i-n+1} .. h_{i-1}, the token h_{s+n-1}.  n == 1 bans every history token; i < n bans nothing.
+ *         The ids are compared as stored.
+ *    The ban value is -inf: tnt_softmax_cce_f32 turns it into probability exactly 0.0f (checked by
+ *    tests/test_gpu_constrain.py).
+ *  - A row with fin[r] != 0 (fin nullable: beam search's finished flags) keeps its logits.  Columns [V, ld) are never
+ *    written; no other logit changes.  An id outside [0, V), in the history, in bad_ids or as end_id, is ignored: nothing
+ *    is read or written for it (in the history it still takes part in the n-gram comparison).
+ *  - One wave per row, lane j holding h_j: i <= 64, n_bad <= 64.  First occurrences by wave shuffles; every address is
+ *    stored by a lane that has decided its final value and every store to one address carries the same value, so no
+ *    order between lanes is relied on.  No atomics, no LDS, no scratch memory; deterministic.
+ * TNT_BADARG for rows <= 0, V <= 0, ld < V, ldh < max(i, 1), i < 0, i > 64, theta < 1 or not finite, n < 0, m < 0, m > 0
+ * with end_id < 0, n_bad outside [0, 64], null logits, null hist_in or last_token with i > 0, null hist_out, null bad_ids
+ * with n_bad > 0, hist_in == hist_out or any overlap of their [rows][ldh] extents; nothing is launched then. */
+int32_t tnt_decode_constrain_f32(float* logits, int32_t ld, int32_t V, int32_t rows, int32_t i, const int32_t* hist_in,
+                                 int32_t* hist_out, int32_t ldh, const int32_t* last_token, const int32_t* parent,
+                                 const int32_t* fin, float theta, int32_t n, int32_t m, int32_t end_id,
+                                 const int32_t* bad_ids, int32_t n_bad, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

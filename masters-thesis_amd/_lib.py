@@ -71,6 +71,7 @@ SIGNATURES = {
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],
+    "tnt_decode_constrain_f32": [P, I32, I32, I32, I32, P, P, I32, P, P, P, F32, I32, I32, I32, P, I32, P],
     "tnt_argmax_rows_f32": [P, P, I32, I32, I32, P],
     "tnt_greedy_feedback_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
                                 I32, I32, P],

@@ -22,16 +22,24 @@ from collections import Counter
 import numpy as np
 
 
-def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_name=""):
+def _con_kw(constraints):
+    """the ``constraints=`` keyword of a decode call, passed only when set: a model without constrained decoding then
+    refuses the call instead of ignoring the constraints"""
+    return {} if constraints is None else {"constraints": constraints}
+
+
+def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_name="", constraints=None):
     """eval.py:148-194.  greedy_predict returns (words (B,T,1), probs (B,T,V), alpha (T,B,R,1), s); the files hold
-    outputs (n,T,1), outputs_raw (n,T,V) and attention_scores (n,T,R,1) (eval.py:172-174)."""
+    outputs (n,T,1), outputs_raw (n,T,V) and attention_scores (n,T,R,1) (eval.py:172-174).  ``constraints``
+    (model_base.DecodeConstraints) goes to greedy_predict: outputs_raw then holds the constrained distributions."""
     outs, raws, attns = [], [], []
     for i in range(len(data_generator)):
         sample = data_generator[i]
         features, _, a0, c0 = sample[0][:4]
         start_seq = np.repeat([tokenizer.word_index["<start>"]], features.shape[0])
         words, probs, alpha, _ = model.greedy_predict(features, a0, c0, start_seq, config["max_length"], config["units"],
-                                                      tokenizer, return_s=False)     # eval.py never reads `s`
+                                                      tokenizer, return_s=False,     # eval.py never reads `s`
+                                                      **_con_kw(constraints))
         outs.append(words); raws.append(probs); attns.append(alpha)
     outputs = np.concatenate(outs, axis=0)
     outputs_raw = np.concatenate(raws, axis=0)
@@ -45,14 +53,16 @@ def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_na
     return outputs, attention_scores
 
 
-def eval_fc_model(model, data_generator, tokenizer, config, out_path, epoch, add_name=""):
-    """eval.py:196-216: greedy_predict_fc returns ids (T,B,1); the file holds (n,T,1)."""
+def eval_fc_model(model, data_generator, tokenizer, config, out_path, epoch, add_name="", constraints=None):
+    """eval.py:196-216: greedy_predict_fc returns ids (T,B,1); the file holds (n,T,1).  ``constraints`` goes to the
+    model's greedy_predict (a model whose decode has no constraints refuses it)."""
     outs = []
     for i in range(len(data_generator)):
         sample = data_generator[i]
         features, _, a0, c0 = sample[0][:4]
         start_seq = np.repeat([tokenizer.word_index["<start>"]], features.shape[0])
-        outs.append(model.greedy_predict(features, a0, c0, start_seq, config["max_length"], config["units"], tokenizer))
+        outs.append(model.greedy_predict(features, a0, c0, start_seq, config["max_length"], config["units"], tokenizer,
+                                         **_con_kw(constraints)))
     all_outputs = np.swapaxes(np.concatenate(outs, axis=1), 0, 1)
     os.makedirs(out_path, exist_ok=True)
     np.save(os.path.join(out_path, f"output_captions_{epoch}{add_name}.npy"), all_outputs)
@@ -81,34 +91,54 @@ def ids_to_captions(ids, tokenizer, end_token="<end>", drop=("<start>", "<pad>")
     return caps
 
 
-def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, length_penalty=0.0, end_token="<end>"):
+def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, length_penalty=0.0, end_token="<end>",
+                  constraints=None):
     """Beam-search captions of either model (nic.NIC or lc_nic.NIC ``beam_search``): every caption starts at the
     tokenizer's "<start>" index and a beam ends at ``end_token``'s index.  Returns (ids (B, max_len) int64 of each
-    sample's best beam, captions: token lists cut at ``end_token`` as ids_to_captions cuts)."""
+    sample's best beam, captions: token lists cut at ``end_token`` as ids_to_captions cuts).  ``constraints``
+    (model_base.DecodeConstraints) goes to beam_search; its min_length counts against ``end_token``'s index."""
     end_id = int(tokenizer.word_index[end_token])
     start = np.full(int(features.shape[0]), int(tokenizer.word_index["<start>"]), np.int64)
     seqs, _ = model.beam_search(features, a0, c0, start, max_len, beam_width=beam_width, end_id=end_id,
-                                length_penalty=length_penalty)
+                                length_penalty=length_penalty, **_con_kw(constraints))
     ids = np.ascontiguousarray(seqs[:, 0, :]).astype(np.int64)
     return ids, ids_to_captions(ids, tokenizer, end_token=end_token)
 
 
 def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>", top_k=0,
-                top_p=1.0):
+                top_p=1.0, constraints=None):
     """ThinkAndTell/evaluate.py:261-284 (`simple_eval`): one teacher-forced forward of the caption generator, then one
     categorical draw per position from the logits (tf.random.categorical(logits, 1)); the caption is cut at the first
     <end>.  The draw runs on the device (tnt_sample_rows_f32, Philox stream (seed, S_SAMPLE, sample_step)).
     ``top_k`` / ``top_p`` filter the draw (tnt_sample_topkp_f32 on the same stream; the defaults 0 / 1 are off).
+    ``constraints`` (model_base.DecodeConstraints; None or neutral: the draw above): the positions are drawn one after the
+    other instead, position t from its teacher-forced logits constrained by the tokens drawn at positions 0 .. t-1
+    (tnt_decode_constrain_f32 in front of each draw; the history is the draws, not the target), on the stream
+    (seed, S_SAMPLE + t, sample_step), element b; more than 32 positions are refused (ValueError), the streams behind
+    S_SAMPLE + 31 belong to other sites.  ``end_token``'s index serves min_length when the object names none.
     Returns (ids (B, T+1) int64, captions or None)."""
     import torch
     from . import ops
-    from .model_base import S_SAMPLE, check_sampling
+    from .model_base import S_SAMPLE, SS_MAX_POSITIONS, check_sampling
     top_k, top_p, _ = check_sampling(top_k, top_p, temperature)
     logits = model((betas, None, target), training=False)                 # (B, T+1, V), device tensor
     Bn, Tn, V = logits.shape
+    end_id = int(tokenizer.word_index.get(end_token, -1)) if tokenizer is not None else -1
+    con = model._constrain(constraints, Bn, Tn, 1, end_id) if constraints is not None else None
+    if con is not None and Tn > SS_MAX_POSITIONS:
+        raise ValueError(f"simple_eval with constraints draws at most {SS_MAX_POSITIONS} positions (one Philox site each), "
+                         f"got {Tn}")
     flat = logits.reshape(Bn * Tn, V).contiguous()
     ids = torch.zeros(Bn * Tn, dtype=torch.int32, device=flat.device)
-    if top_k == 0 and top_p == 1.0:
+    if con is not None:
+        rows = logits.permute(1, 0, 2).contiguous()                      # (T+1, B, V): one position's rows side by side
+        ids = ids.view(Tn, Bn)
+        for t in range(Tn):
+            con.step(t, rows[t], V, ids[t - 1] if t > 0 else None)
+            ops.backend().sample_topkp(rows[t], ids[t], Bn, V, V, temperature, top_k, top_p, True, model.seed, S_SAMPLE + t,
+                                       sample_step)
+        ids = ids.t().contiguous().view(-1)
+    elif top_k == 0 and top_p == 1.0:
         ops.backend().sample_rows(flat, ids, Bn * Tn, V, V, temperature, True, model.seed, S_SAMPLE, sample_step)
     else:
         ops.backend().sample_topkp(flat, ids, Bn * Tn, V, V, temperature, top_k, top_p, True, model.seed, S_SAMPLE,

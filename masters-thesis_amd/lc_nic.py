@@ -1293,7 +1293,7 @@ class NIC(ModelBase):
         return self.cap.cpu().numpy().copy()
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       sample_step=0, top_k=0, top_p=1.0, return_s=True):
+                       sample_step=0, top_k=0, top_p=1.0, return_s=True, constraints=None):
         """greedy_predict_attention with the argmax replaced by lc_NIC.sample_choice (lc_NIC.py:571-575:
         tf.random.categorical(log(probs), 1)); ``temperature`` as in ThinkAndTell/evaluate.py:223.  TF's
         sampler cannot be reproduced; the draw is the Philox stream (seed, S_SAMPLE + position, sample_step),
@@ -1303,23 +1303,31 @@ class NIC(ModelBase):
         mass reaches top_p) filter each draw (tnt_sample_topkp_f32, definition in include/tnt_hip.h; lc_NIC
         select_nucleus2, lc_NIC.py:694-710).  With both at their defaults the draw is the unfiltered one above.  A
         filtered decode is captured and replayed like greedy_predict; sample_step reaches the replay through a device
-        word, so every call draws its own stream without a re-capture."""
+        word, so every call draws its own stream without a re-capture.
+        ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what the
+        returned probabilities hold then."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         if top_k == 0 and top_p == 1.0:
             return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
-                                       _sample=(temperature, int(sample_step)), return_s=return_s)
+                                       _sample=(temperature, int(sample_step)), return_s=return_s, constraints=constraints)
         return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
-                                   _filter=(temperature, top_k, top_p, int(sample_step)), return_s=return_s)
+                                   _filter=(temperature, top_k, top_p, int(sample_step)), return_s=return_s,
+                                   constraints=constraints)
 
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, training=False,
-                       _sample=None, return_s=True, _filter=None):
+                       _sample=None, return_s=True, _filter=None, constraints=None):
         """lc_NIC.greedy_predict -> greedy_predict_attention (lc_NIC.py:507-508,577-638).
         Returns (words (B,max_len,1) int64, probs (B,max_len,V), alpha (max_len,B,R,1), s (max_len,B,R,A))
-        as numpy arrays; the whole decode runs on the device with no per-step host sync."""
+        as numpy arrays; the whole decode runs on the device with no per-step host sync.
+        ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
+        applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
+        softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
+        a neutral object: the decode as it is without the keyword."""
         assert training is False, "training is set to True"                                  # lc_NIC.py:591
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         B = start.shape[0]
+        con = self._constrain(constraints, B, max_len)
         self._stage_inputs((img_input, torch.zeros(B, max_len, dtype=torch.int32), a0, c0))
         R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
         Wl = a.p("lstm/kernel")
@@ -1350,6 +1358,8 @@ class NIC(ModelBase):
                              bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)     # :621
                 self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), probs[i], B, V, H, H, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))                                # :623
+                if con is not None:
+                    con.step(i, probs[i], ldV, words if i > 0 else None)
                 be.softmax_cce(probs[i], None, probs[i], None, None, None, B, V, ldV, 0.0)
                 if _filter is not None:
                     be.sample_topkp(probs[i], ids[i], B, V, ldV, _filter[0], _filter[1], _filter[2], False, self.seed,
@@ -1359,10 +1369,11 @@ class NIC(ModelBase):
                 else:
                     be.sample_rows(probs[i], ids[i], B, V, ldV, _sample[0], False, self.seed, S_SAMPLE + i, _sample[1])
                 words = ids[i].view(B, 1)
+        ckey = con.key if con is not None else ()
         if _filter is not None:     # the stream step is read from step_buf on the device: captured like the greedy loop
-            self._run_captured(("sample",) + key + tuple(_filter[:3]), run)
+            self._run_captured(("sample",) + key + tuple(_filter[:3]) + ckey, run)
         elif _sample is None:
-            self._run_captured(("greedy",) + key, run)
+            self._run_captured(("greedy",) + key + ckey, run)
         else:                      # the sampling stream step is a launch argument: not captured
             run()
         out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
@@ -1453,7 +1464,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
-                    length_penalty=0.0):
+                    length_penalty=0.0, constraints=None):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,
         lc_NIC.py:640-692, recurse without returning; ThinkAndTell/evaluate.py:203-228 stops after one expansion), so
         the definition is this library's: standard log-probability beam search of width ``beam_width`` with the greedy
@@ -1463,13 +1474,18 @@ class NIC(ModelBase):
         expansion launch (tnt_beam_topk_f32) and row gathers of the LSTM state by parent beam; the paths are
         back-tracked on the host at the end.  Restated by oracle.models.LcNIC.beam_search.
         ``length_penalty`` > 0 reorders the k results by score / ((5 + L) / 6) ** length_penalty and returns that key as
-        the scores (model_base.length_normalise); the search itself is unchanged."""
+        the scores (model_base.length_normalise); the search itself is unchanged.
+        ``constraints`` (model_base.DecodeConstraints): each live beam row's logits are constrained from the row's own path
+        (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
+        beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
+        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword."""
         length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
         start = np.asarray(start_seq).reshape(-1)
         B = start.shape[0]
         Bk = B * k
+        con = self._constrain(constraints, Bk, max_len, k, int(end_id))
         rep = lambda t: np.repeat(np.asarray(t), k, axis=0)
         x = img_input.cpu().numpy() if isinstance(img_input, torch.Tensor) else np.asarray(img_input)
         self._stage_inputs((rep(x), torch.zeros(Bk, max_len, dtype=torch.int32), rep(np.asarray(a0)), rep(np.asarray(c0))))
@@ -1496,8 +1512,10 @@ class NIC(ModelBase):
                          bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)
             self.gemm_sk(self.inter[:Bk], a.p("time_distributed_softmax/kernel"), probs, Bk, V, H, H, ldV, ldV,
                          bias=a.p("time_distributed_softmax/bias"))
-            be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
             cur, nxt = i & 1, (i & 1) ^ 1
+            if con is not None:
+                con.step(i, probs, ldV, tokens[i - 1] if i > 0 else None, parents[i - 1] if i > 0 else None, fin[cur])
+            be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
             be.beam_topk(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
             # the surviving beams continue from their parents' LSTM state (row gather by parent)
             be.embedding_fwd(self.Hs[i + 1], parents[i].view(Bk, 1), hg, Bk, 1, U, U, Bk)

@@ -201,6 +201,87 @@ class SelfCritical:
                 f"reward={self.reward!r}, corpus={'None' if self.corpus is None else f'<{len(self.corpus)} documents>'})")
 
 
+class DecodeConstraints:
+    """Constraints on caption decoding, for the ``constraints=`` keyword of greedy_predict, sample_predict and beam_search
+    of nic.NIC and lc_nic.NIC; applied to each step's logits on the device, in front of the softmax, from the tokens the
+    row's path has chosen so far (the start token is not among them).  The definition is tnt_decode_constrain_f32's
+    (include/tnt_hip.h):
+      repetition_penalty    theta >= 1 (1: off): the logit of every token of the history is divided by theta if positive,
+                            multiplied by it otherwise, once per distinct token
+      no_repeat_ngram_size  n >= 0 (0: off): a token that would complete an n-gram the history already holds is banned
+      min_length            m >= 0: ``end_id`` is banned at positions 0 .. m-1
+      bad_ids               up to 64 token ids banned at every step (<unk>, <pad>, <start>, ...)
+      end_id                the tokenizer's <end> index for min_length; -1: beam_search's own end_id
+    A banned token has probability exactly 0.  Bad values raise ValueError here, before any launch; what depends on the
+    model or the call (vocabulary size, max_len, beam width) is checked by the decode."""
+
+    MAX_LEN = 64        # the kernel holds one history token per lane
+    MAX_BAD = 64
+
+    def __init__(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, bad_ids=(), end_id=-1):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        th = repetition_penalty
+        if isinstance(th, bool) or not isinstance(th, (int, float, np.integer, np.floating)) or not np.isfinite(th) or th < 1:
+            raise ValueError(f"repetition_penalty must be a finite number >= 1 (1: off), got {th!r}")
+        if float(th) > float(np.finfo(np.float32).max):
+            raise ValueError(f"repetition_penalty must be finite in float32, got {th!r}")
+        if not is_int(no_repeat_ngram_size) or no_repeat_ngram_size < 0:
+            raise ValueError(f"no_repeat_ngram_size must be an int >= 0 (0: off), got {no_repeat_ngram_size!r}")
+        if not is_int(min_length) or min_length < 0:
+            raise ValueError(f"min_length must be an int >= 0, got {min_length!r}")
+        if not is_int(end_id) or end_id < -1:
+            raise ValueError(f"end_id must be an int >= -1 (-1: beam_search's end_id), got {end_id!r}")
+        try:
+            bad = tuple(bad_ids)
+        except TypeError:
+            raise ValueError(f"bad_ids must be a sequence of token ids, got {bad_ids!r}") from None
+        if not all(is_int(v) and v >= 0 for v in bad):
+            raise ValueError(f"bad_ids must be ints >= 0, got {bad_ids!r}")
+        if len(bad) > self.MAX_BAD:
+            raise ValueError(f"at most {self.MAX_BAD} bad_ids, got {len(bad)}")
+        self.repetition_penalty, self.no_repeat_ngram_size, self.min_length = float(th), int(no_repeat_ngram_size), int(min_length)
+        self.bad_ids, self.end_id = tuple(int(v) for v in bad), int(end_id)
+
+    @property
+    def neutral(self):
+        """every rule is off: the decode runs as without constraints"""
+        return (np.float32(self.repetition_penalty) == 1 and self.no_repeat_ngram_size == 0 and self.min_length == 0
+                and not self.bad_ids)
+
+    def __repr__(self):
+        return (f"DecodeConstraints(repetition_penalty={self.repetition_penalty}, no_repeat_ngram_size="
+                f"{self.no_repeat_ngram_size}, min_length={self.min_length}, bad_ids={self.bad_ids}, end_id={self.end_id})")
+
+
+class _ConstrainedDecode:
+    """The host part of a constrained decode over ``rows`` rows (ModelBase._constrain): the ping-pong history buffers and
+    the bad_ids buffer on the device, the per-step launch, and the suffix of the capture key."""
+
+    def __init__(self, model, c, rows, max_len, end_id):
+        bufs = model.__dict__.setdefault("_con_bufs", {})
+        if (rows, max_len) not in bufs:
+            bufs[rows, max_len] = torch.zeros(2, rows, max_len, dtype=torch.int32, device=model.device)
+        if "bad" not in bufs:
+            bufs["bad"] = torch.zeros(DecodeConstraints.MAX_BAD, dtype=torch.int32, device=model.device)
+        self.be, self.V, self.rows, self.ldh = model.be, model.V, rows, max_len
+        self.hist, self.bad = bufs[rows, max_len], bufs["bad"]
+        # the list reaches a replay through the buffer: only its length is in the capture key.  One buffer per model, written
+        # here alone and in stream order; an unchanged list is not copied again (the copy is a synchronous one from pageable memory)
+        if c.bad_ids and bufs.get("bad_ids") != c.bad_ids:
+            self.bad[:len(c.bad_ids)].copy_(torch.tensor(c.bad_ids, dtype=torch.int32))
+            bufs["bad_ids"] = c.bad_ids
+        self.theta, self.n, self.m, self.end_id, self.n_bad = c.repetition_penalty, c.no_repeat_ngram_size, c.min_length, end_id, len(c.bad_ids)
+        self.key = ("constrain", self.theta, self.n, self.m, self.end_id, self.n_bad)
+
+    def step(self, i, logits, ld, last_token, parent=None, fin=None):
+        """decode step i: logits [rows][ld] in place; last_token / parent: what step i-1 chose (None at i = 0; parent None:
+        every row continues itself); fin: the finished flags the step's expansion reads.  hist[i & 1] then holds the rows'
+        histories h_0 .. h_{i-1}."""
+        self.be.decode_constrain(logits, ld, self.V, self.rows, i, self.hist[(i & 1) ^ 1], self.hist[i & 1], self.ldh,
+                                 last_token, parent, fin, self.theta, self.n, self.m, self.end_id,
+                                 self.bad if self.n_bad else None, self.n_bad)
+
+
 def check_sampling(top_k, top_p, temperature):
     """host validation of the sampling filters (tnt_sample_topkp_f32): top_k an int >= 0 (0 = off), 0 < top_p <= 1
     (1 = off), temperature > 0.  Returns (int top_k, float top_p, float temperature); ValueError otherwise."""
@@ -1085,6 +1166,36 @@ class ModelBase:
             w = self._step_word = torch.zeros(1, dtype=torch.int32, device=self.device)
         w.fill_(int(np.uint32(int(step) & 0xFFFFFFFF).view(np.int32)))
         return w
+
+    def _constrain(self, constraints, rows, max_len, beam_width=1, end_id=-1):
+        """The constrained-decode helper of a decode over ``rows`` rows (``end_id``: beam search's), or None when
+        ``constraints`` is None or neutral: then the decode issues no new launch and keeps its capture key and buffers.
+        Refusals (ValueError, before any launch): max_len > 64; a bad id outside [0, V); min_length without an end_id >= 1
+        or above max_len; two different end ids; and len(bad_ids) + max_len + 1 + beam_width > V, so that every live row
+        keeps at least beam_width tokens un-banned at every step."""
+        c = constraints
+        if c is None:
+            return None
+        if not isinstance(c, DecodeConstraints):
+            raise ValueError(f"constraints must be a DecodeConstraints or None, got {c!r}")
+        if c.neutral:
+            return None
+        V = self.V
+        if max_len > c.MAX_LEN:
+            raise ValueError(f"constrained decoding holds at most {c.MAX_LEN} tokens per caption, got max_len = {max_len}")
+        if any(v >= V for v in c.bad_ids):
+            raise ValueError(f"bad_ids must be token ids in [0, {V}), got {c.bad_ids}")
+        if c.end_id >= 0 and end_id >= 0 and c.end_id != end_id:
+            raise ValueError(f"constraints.end_id = {c.end_id} differs from the decode's end_id = {end_id}")
+        eid = c.end_id if c.end_id >= 0 else int(end_id)
+        if c.min_length > 0 and not 1 <= eid < V:
+            raise ValueError(f"min_length = {c.min_length} needs an end_id in [1, {V}), got {eid}")
+        if c.min_length > max_len:
+            raise ValueError(f"min_length = {c.min_length} exceeds max_len = {max_len}")
+        if len(c.bad_ids) + max_len + 1 + beam_width > V:
+            raise ValueError(f"{len(c.bad_ids)} bad ids + max_len {max_len} + 1 + beam width {beam_width} exceed the "
+                             f"vocabulary of {V}: a step could be left without a token to choose")
+        return _ConstrainedDecode(self, c, rows, max_len, eid if c.min_length > 0 else -1)
 
     def _run_captured(self, key, fn):
         """Run ``fn`` (a fixed launch sequence over static buffers) through a hipGraph:

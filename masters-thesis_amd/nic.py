@@ -850,23 +850,30 @@ class NIC(ModelBase):
 
     call = __call__
 
-    def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None):
+    def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, constraints=None):
         """NIC.greedy_predict (NIC.py:148-195), inference mode; returns np.ndarray (max_len, B, 1, V).
-        A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does."""
-        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None)
+        A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does.
+        ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
+        applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
+        softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
+        a neutral object: the decode as it is without the keyword."""
+        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints)
         return probs_all[:, :, :self.V].cpu().numpy()[:, :, None, :]
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       top_k=0, top_p=1.0, sample_step=0):
+                       top_k=0, top_p=1.0, sample_step=0, constraints=None):
         """greedy_predict with the argmax replaced by a categorical draw from each step's probabilities, filtered by
         ``top_k`` (>= 1: only the k most likely tokens; 0: off) and ``top_p`` (< 1: only the shortest most-likely prefix
         whose mass reaches top_p; 1: off) at ``temperature`` (tnt_sample_topkp_f32, definition in include/tnt_hip.h).
         The draw is the Philox stream (seed, S_SAMPLE + position, sample_step), as in lc_nic.NIC.sample_predict.  A
         sampled id 0 masks the following LSTM step exactly as a greedy 0 does.  The decode is captured and replayed like
         greedy_predict; sample_step reaches the replay through a device word.
+        ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what ``probs``
+        holds then.
         Returns (ids (B, max_len, 1) int64, probs (max_len, B, 1, V))."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
-        probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)))
+        probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)),
+                                      constraints)
         V = self.V
         return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
                 probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
@@ -891,12 +898,14 @@ class NIC(ModelBase):
         be.lstm_step_fwd(xz, h0, c0, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h1, c1, None,
                          self.gates[0], B, U)
 
-    def _decode(self, img_input, a0, c0, start_seq, max_len, filt):
+    def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
-        sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None)"""
+        sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None).  With
+        constraints on (ModelBase._constrain) the greedy loop keeps its ids per step too: the history is built from them."""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         B = start.shape[0]
+        con = self._constrain(constraints, B, max_len)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
@@ -910,11 +919,12 @@ class NIC(ModelBase):
         start_buf, words, probs_all = bufs[key]
         start_buf.copy_(start.view(B, 1))
         ids = None
-        if filt is not None:
+        if filt is not None or con is not None:
             sbufs = self.__dict__.setdefault("_sample_ids", {})
             if key not in sbufs:
                 sbufs[key] = torch.zeros(max_len, B, dtype=torch.int32, device=self.device)
             ids = sbufs[key]
+        if filt is not None:
             step_buf = self._sample_step_word(filt[3])
 
         def run():
@@ -935,17 +945,23 @@ class NIC(ModelBase):
                 cur = 1 - cur
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs_all[i], B, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
+                if con is not None:
+                    con.step(i, probs_all[i], ldV, prev if i > 0 else None)
                 be.softmax_cce(probs_all[i], None, probs_all[i], None, None, None, B, V, ldV, 0.0)
-                if filt is None:
+                if filt is None and con is None:
                     be.argmax_rows(probs_all[i], words, B, V, ldV)
+                elif filt is None:
+                    be.argmax_rows(probs_all[i], ids[i], B, V, ldV)
+                    prev = ids[i].view(B, 1)
                 else:
                     be.sample_topkp(probs_all[i], ids[i], B, V, ldV, filt[0], filt[1], filt[2], False, self.seed,
                                     S_SAMPLE + i, 0, step_buf)
                     prev = ids[i].view(B, 1)
+        ckey = con.key if con is not None else ()
         if filt is None:
-            self._run_captured(("greedy",) + key, run)
+            self._run_captured(("greedy",) + key + ckey, run)
         else:
-            self._run_captured(("sample",) + key + tuple(filt[:3]), run)
+            self._run_captured(("sample",) + key + tuple(filt[:3]) + ckey, run)
         return probs_all, ids
 
     # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
@@ -1002,7 +1018,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
-                    units=None, tokenizer=None):
+                    units=None, tokenizer=None, constraints=None):
         """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches
         it): log-probability beam search of width ``beam_width`` with greedy_predict's step, whose Keras mask rule it
         keeps (a 0 fed back masks the next LSTM step); at step 0 the k beams of a sample are copies and only beam 0
@@ -1013,12 +1029,17 @@ class NIC(ModelBase):
         (expansion + reorder of the state by parent into the other state buffer).  The loop is captured and replayed
         like greedy_predict, over static buffers of its own per (B, k, max_len, end_id); the paths are back-tracked on
         the host from one copy of the parents / tokens.
+        ``constraints`` (model_base.DecodeConstraints): each live beam row's logits are constrained from the row's own path
+        (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
+        beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
+        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword.
         Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
         length-normalised key)."""
         k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         B = start.shape[0]
+        con = self._constrain(constraints, B * k, max_len, k, end_id)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
         U, E, V, ldV = self.U, self.E, self.V, self.ldV
@@ -1056,12 +1077,14 @@ class NIC(ModelBase):
                                  h[1], c[1], out, bb["gates"], Bk, U)
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, Bk, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
-                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
                 cur, nxt = i & 1, (i & 1) ^ 1
+                if con is not None:
+                    con.step(i, probs, ldV, tokens[i - 1] if i > 0 else None, parents[i - 1] if i > 0 else None, fin[cur])
+                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
                 # expansion, and the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]
                 be.beam_step(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
                              fin[nxt], h[1], c[1], U, U, h[0], c[0])
-        self._run_captured(("beam",) + key, run)
+        self._run_captured(("beam",) + key + (con.key if con is not None else ()), run)
         pt = bb["pt"].cpu().numpy()
         final = score[max_len & 1].cpu().numpy().reshape(B, k)
         par, tok = pt[0], pt[1]

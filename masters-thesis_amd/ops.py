@@ -636,6 +636,15 @@ class HipBackend:
                    _p(score_out), _p(parent), _p(token), _p(fin_out), _p(h_in), _p(c_in), ldh, U, _p(h_out), _p(c_out),
                    self._s())
 
+    def decode_constrain(self, logits, ld, V, rows, i, hist_in, hist_out, ldh, last_token, parent, fin, theta, n, m, end_id,
+                         bad_ids, n_bad):
+        """repetition penalty and bans (bad ids, minimum length, no-repeat n-gram) of decode step i on its logits, in place,
+        from the device-side token history (tnt_decode_constrain_f32; definition in include/tnt_hip.h); last_token, parent,
+        fin and bad_ids are nullable"""
+        self._call(self.lib.tnt_decode_constrain_f32, "tnt_decode_constrain_f32", _p(logits), ld, V, rows, int(i), _p(hist_in),
+                   _p(hist_out), ldh, _p(last_token), _p(parent), _p(fin), float(theta), int(n), int(m), int(end_id), _p(bad_ids),
+                   int(n_bad), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
