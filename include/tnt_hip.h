@@ -569,6 +569,23 @@ int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* target, float* p
                             float* loss_row, float* correct_row, float* dlogits,
                             int32_t rows, int32_t V, int32_t ld, float gscale,
                             int32_t from_logits, int32_t mask_zero, void* stream);
+/* ---- the same head with label smoothing: tf.keras.losses.CategoricalCrossentropy(from_logits=False,
+ * label_smoothing=eps), one launch (smooth.hip).  With V classes, p = softmax(x) and target id y:
+ *   ys_v      = (1 - eps) [v == y] + eps / V
+ *   loss      = -sum_v ys_v log(clip(p_v, 1e-7, 1 - 1e-7))
+ *   m_v       = 1 where the clip is inactive for class v (1e-7 <= p_v <= 1 - 1e-7), else 0;  c = sum_v m_v ys_v
+ *   dlogits_v = gscale (c p_v - m_v ys_v)            (the gradient through keras's element-wise clip)
+ * A target id outside [0, V) matches no class (ys_v = eps / V).  correct_row = (argmax == y), first maximum wins.
+ * label_smoothing = 0 is tnt_softmax_cce_f32(from_logits=0, mask_zero=0) up to rounding.  No from_logits / mask_zero form.
+ * Shared with tnt_softmax_cce_f32: every output is nullable (target null: probs only, loss_row / correct_row are not
+ * written and dlogits, if given, is zero); probs or dlogits may alias logits; pad columns [V, ld) of logits are ignored
+ * and those of an output are left as they were or written as zero (inside the register kernel's window); rows == 0 is
+ * a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null logits -- and for label_smoothing outside [0, 1) or not
+ * finite. */
+int32_t tnt_softmax_cce_smooth_f32(const float* logits, const int32_t* target, float* probs,
+                                   float* loss_row, float* correct_row, float* dlogits,
+                                   int32_t rows, int32_t V, int32_t ld, float gscale,
+                                   float label_smoothing, void* stream);
 /* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v (first max wins).
  * B == 0 or T == 0 is a no-op; TNT_BADARG for B < 0, T < 0, V <= 0, null pointers. */
 int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T,

@@ -40,5 +40,7 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
                     config["output_reg"], seed=config.get("seed", 42), **kw)
     else:
         raise ValueError(f"unknown mode {mode!r}")
-    model.compile(build_optimizer(config), CategoricalCrossentropy(from_logits=False, reduction="none"), run_eagerly=True)
+    # label_smoothing: an optional key of this library's (the reference's config has none), default 0
+    loss = CategoricalCrossentropy(from_logits=False, reduction="none", label_smoothing=config.get("label_smoothing", 0.0))
+    model.compile(build_optimizer(config), loss, run_eagerly=True)
     return model

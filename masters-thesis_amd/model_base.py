@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .optimizers import Adam
+from .optimizers import Adam, loss_label_smoothing
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -398,6 +398,7 @@ class Metrics(dict):
 class ModelBase:
     GUARD = 7       # slot of ``met`` that carries the device guard word of the step (see Metrics)
     METRIC_RING = 1024      # rows of the metrics ring: a step's Metrics stay readable for this many further training steps
+    SUPPORTS_LABEL_SMOOTHING = True     # False where the step does not go through the compile loss (ThinkAndTell generators)
     # subclasses fill: self.layers_spec = OrderedDict(layer -> [weight names]),
     # self.keras_shapes = {full name: keras shape}
     def __init__(self, device=None, seed=42, use_graph=True, grad_sync=None):
@@ -409,6 +410,7 @@ class ModelBase:
         self.dp_world = int(getattr(grad_sync, "world", 1)) if grad_sync is not None else 1
         self.optimizer = None
         self.loss = None
+        self.label_smoothing = 0.0          # of the compile loss (CategoricalCrossentropy(label_smoothing=...))
         self.built = False
         self.stop_training = False
         self._graphs = {}
@@ -417,8 +419,19 @@ class ModelBase:
     # ------------------------------------------------------------------ keras surface
     def compile(self, optimizer=None, loss=None, *metrics, run_eagerly=True, **kw):
         """model.compile(optimizer, loss_object, run_eagerly=True) -- main.py:134."""
+        eps = loss_label_smoothing(loss)
+        if eps > 0 and not self.SUPPORTS_LABEL_SMOOTHING:
+            raise NotImplementedError(f"{type(self).__name__} computes its own masked sparse loss and does not read the "
+                                      "compile loss: label_smoothing > 0 is not implemented for it")
+        if eps > 0 and getattr(self, "self_critical", None) is not None:
+            raise ValueError("label_smoothing > 0 does not apply to a self_critical model: its loss is the "
+                             "advantage-weighted tnt_scst_cce_f32, not the compile loss")
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
+        # fixed here, not read per step: the head launch sits inside captured graphs
+        if eps != self.label_smoothing:
+            self._graphs = {}
+        self.label_smoothing = eps
         if self.built:
             self._init_optimizer_state()
 

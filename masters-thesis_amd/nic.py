@@ -384,7 +384,12 @@ class NIC(ModelBase):
         (NIC.py:233-240) == sum over all (b,t) / (B*T)."""
         be = self.be
         n = T * B
-        if want_grad:
+        eps = self.label_smoothing
+        if eps > 0:         # keras smooths the evaluation loss too
+            be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
+                                  self.logits if want_grad else None, n, self.V, self.ldV,
+                                  1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
+        elif want_grad:
             be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
                            self.ldV, 1.0 / (n * self.dp_world))
         else:

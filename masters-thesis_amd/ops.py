@@ -299,6 +299,12 @@ class HipBackend:
                                                 _p(dlogits), rows, V, ld, gscale, int(from_logits), int(mask_zero),
                                                 self._s())
 
+    def softmax_cce_smooth(self, logits, target, probs, loss_row, correct_row, dlogits, rows, V, ld, gscale, label_smoothing):
+        """the head with keras label smoothing in the same single launch (tnt_softmax_cce_smooth_f32; definition in
+        include/tnt_hip.h)"""
+        self._call(self.lib.tnt_softmax_cce_smooth_f32, "tnt_softmax_cce_smooth_f32", _p(logits), _p(target), _p(probs), _p(loss_row),
+                   _p(correct_row), _p(dlogits), rows, V, ld, gscale, float(label_smoothing), self._s())
+
     def onehot_argmax(self, onehot, ids_tmajor, B, T, V):
         self._call(self.lib.tnt_onehot_argmax_f32, "tnt_onehot_argmax_f32", _p(onehot), _p(ids_tmajor), B, T, V, self._s())
 

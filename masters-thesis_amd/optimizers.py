@@ -51,9 +51,28 @@ class SGD:
 
 class CategoricalCrossentropy:
     """tf.keras.losses.CategoricalCrossentropy(from_logits=False, reduction='none') -- main.py:107-110.
-    Only this configuration is implemented by the fused softmax+CE kernel."""
+    Only this configuration is implemented by the fused softmax+CE kernel.  ``label_smoothing`` (keras: the target
+    becomes (1 - eps) * onehot + eps / V) is read by ``ModelBase.compile``; with eps > 0 the training and the
+    evaluation step launch tnt_softmax_cce_smooth_f32 instead of tnt_softmax_cce_f32."""
 
-    def __init__(self, from_logits=False, reduction="none"):
+    def __init__(self, from_logits=False, reduction="none", label_smoothing=0.0):
         if from_logits:
             raise NotImplementedError("the reference path uses from_logits=False")
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         self.from_logits, self.reduction = from_logits, reduction
+
+
+def check_label_smoothing(eps):
+    """the value as a float; ValueError unless 0 <= eps < 1 (NaN included)"""
+    try:
+        v = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {eps!r}") from None
+    if not 0.0 <= v < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {eps!r}")
+    return v
+
+
+def loss_label_smoothing(loss):
+    """label_smoothing of a compile() loss argument: None, or an object without the attribute, means 0"""
+    return check_label_smoothing(getattr(loss, "label_smoothing", 0.0) if loss is not None else 0.0)

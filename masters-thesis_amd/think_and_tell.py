@@ -46,6 +46,8 @@ class Decoder:
 
 
 class CaptionGenerator(ModelBase):
+    SUPPORTS_LABEL_SMOOTHING = False    # loss_function is the masked sparse from-logits form, not the compile loss
+
     def __init__(self, encoder, decoder, tokenizer=None, max_length=15, **kw):
         super().__init__(**kw)
         self.encoder, self.decoder, self.tokenizer, self.max_length = encoder, decoder, tokenizer, int(max_length)
