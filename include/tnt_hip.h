@@ -651,6 +651,33 @@ int32_t tnt_decode_constrain_f32(float* logits, int32_t ld, int32_t V, int32_t r
                                  int32_t* hist_out, int32_t ldh, const int32_t* last_token, const int32_t* parent,
                                  const int32_t* fin, float theta, int32_t n, int32_t m, int32_t end_id,
                                  const int32_t* bad_ids, int32_t n_bad, void* stream);
+/* Consensus decoding: the next-word distributions of the G member rows of one mixed row -- several scans of the same
+ * image, or the subjects of the multi-subject model -- combined into one, where softmax + argmax sit in a plain decode
+ * (restated by tests/consensus_oracle.py).  Library-defined:
+ *  - Layout.  Member-major: logits [G*Rm][ld], V valid columns, are the step's logits (behind tnt_decode_constrain_f32,
+ *    if any); member g of mixed row r is row g*Rm + r.  mix [Rm][ldm] receives the mixture; columns [V, ldm) are never
+ *    written.  w [G] are the member weights, positive and summing to 1 (the caller's duty); NULL: 1/G each.
+ *  - Per member row, in float32: m_g = max_v x_gv, s_g = sum_v exp(x_gv - m_g).  A member row with nothing above -inf
+ *    counts as m_g = 0, s_g = 1: each of its columns is then -inf like any banned one.
+ *  - mode 0 (mean of softmaxes):  p_v = sum_g w_g * exp(x_gv - m_g) / s_g, accumulated in ascending g.
+ *    mode 1 (logmean, the renormalised geometric mean):  l_v = sum_g w_g * ((x_gv - m_g) - log s_g) in ascending g,
+ *    p_v = exp(l_v - L) / sum_v exp(l_v - L), L = max_v l_v.
+ *    A -inf logit gives probability exactly 0.0f: in mean only when every member bans the column, in logmean when any
+ *    does.  A logmean row whose every l_v is -inf gets p = 0 everywhere and token 0.
+ *  - token (nullable) [G*Rm]: the argmax of p_r under the rules of tnt_argmax_rows_f32 (first max wins, NaN entries are
+ *    ignored, nothing above -inf gives 0), written to all G member rows g*Rm + r: the word fed back to every member.
+ *  - One workgroup per mixed row, 1 <= G <= 16; fixed summation orders, no atomics, no scratch memory: deterministic.
+ * TNT_BADARG for Rm <= 0, V <= 0, ld < V, ldm < V, G outside [1, 16], mode other than 0 or 1, null logits or mix, mix
+ * overlapping logits anywhere in their extents; nothing is launched then. */
+int32_t tnt_consensus_mix_f32(const float* logits, int32_t ld, int32_t V, int32_t Rm, int32_t G, const float* w,
+                              int32_t mode, float* mix, int32_t ldm, int32_t* token, void* stream);
+/* What a step chose on the Rm mixed rows (tnt_sample_topkp_f32 / tnt_sample_rows_f32 / tnt_beam_topk_f32 /
+ * tnt_beam_step_f32) carried to the G*Rm member rows: token_out[g*Rm + r] = token[r] (the fed-back word),
+ * parent_out[g*Rm + r] = parent[r] + g*Rm (the member's row of the parent beam: the state gather and the history gather
+ * of tnt_decode_constrain_f32), fin_out[g*Rm + r] = fin[r].  Each of token / parent / fin is nullable and skipped then
+ * (all three null: no launch).  TNT_BADARG for Rm <= 0, G outside [1, 16], an input without its output. */
+int32_t tnt_consensus_spread_i32(const int32_t* token, const int32_t* parent, const int32_t* fin, int32_t Rm, int32_t G,
+                                 int32_t* token_out, int32_t* parent_out, int32_t* fin_out, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

@@ -73,6 +73,8 @@ SIGNATURES = {
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],
     "tnt_decode_constrain_f32": [P, I32, I32, I32, I32, P, P, I32, P, P, P, F32, I32, I32, I32, P, I32, P],
+    "tnt_consensus_mix_f32": [P, I32, I32, I32, I32, P, I32, P, I32, P, P],
+    "tnt_consensus_spread_i32": [P, P, P, I32, I32, P, P, P, P],
     "tnt_argmax_rows_f32": [P, P, I32, I32, I32, P],
     "tnt_greedy_feedback_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
                                 I32, I32, P],

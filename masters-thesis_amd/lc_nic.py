@@ -1298,7 +1298,7 @@ class NIC(ModelBase):
         return self.cap.cpu().numpy().copy()
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       sample_step=0, top_k=0, top_p=1.0, return_s=True, constraints=None):
+                       sample_step=0, top_k=0, top_p=1.0, return_s=True, constraints=None, consensus=None):
         """greedy_predict_attention with the argmax replaced by lc_NIC.sample_choice (lc_NIC.py:571-575:
         tf.random.categorical(log(probs), 1)); ``temperature`` as in ThinkAndTell/evaluate.py:223.  TF's
         sampler cannot be reproduced; the draw is the Philox stream (seed, S_SAMPLE + position, sample_step),
@@ -1310,27 +1310,39 @@ class NIC(ModelBase):
         filtered decode is captured and replayed like greedy_predict; sample_step reaches the replay through a device
         word, so every call draws its own stream without a re-capture.
         ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what the
-        returned probabilities hold then."""
+        returned probabilities hold then.
+        ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
+        of a plain decode of M scans uses) and is fed to all of them."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         if top_k == 0 and top_p == 1.0:
             return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
-                                       _sample=(temperature, int(sample_step)), return_s=return_s, constraints=constraints)
+                                       _sample=(temperature, int(sample_step)), return_s=return_s, constraints=constraints,
+                                       consensus=consensus)
         return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
                                    _filter=(temperature, top_k, top_p, int(sample_step)), return_s=return_s,
-                                   constraints=constraints)
+                                   constraints=constraints, consensus=consensus)
 
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, training=False,
-                       _sample=None, return_s=True, _filter=None, constraints=None):
+                       _sample=None, return_s=True, _filter=None, constraints=None, consensus=None):
         """lc_NIC.greedy_predict -> greedy_predict_attention (lc_NIC.py:507-508,577-638).
         Returns (words (B,max_len,1) int64, probs (B,max_len,V), alpha (max_len,B,R,1), s (max_len,B,R,A))
         as numpy arrays; the whole decode runs on the device with no per-step host sync.
         ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
         applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
         softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
-        a neutral object: the decode as it is without the keyword."""
-        assert training is False, "training is set to True"                                  # lc_NIC.py:591
+        a neutral object: the decode as it is without the keyword.
+        ``consensus`` (model_base.Consensus(members=G, ...)): one caption per image from G scans of it.  img_input, a0, c0
+        hold G * M rows, member-major (rows [g*M, (g+1)*M): member g; with n_subjects = S the members are the S subject
+        slices and G must be S), start_seq M entries; per token one tnt_consensus_mix_f32 launch takes the place of softmax
+        + argmax and the mixture's first maximum is fed to all members.  words (M, max_len, 1) and probs (M, max_len, V),
+        the mixtures, are per image; alpha and s stay per member row, (max_len, G*M, R, ...).  None: the decode as it is
+        without the keyword."""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
+        cons = self._consensus(consensus, img_input, start.shape[0], training=training)
+        assert training is False, "training is set to True"                                  # lc_NIC.py:591
+        if cons is not None:
+            start = start.repeat(cons.G)
         B = start.shape[0]
         con = self._constrain(constraints, B, max_len)
         self._stage_inputs((img_input, torch.zeros(B, max_len, dtype=torch.int32), a0, c0))
@@ -1340,6 +1352,11 @@ class NIC(ModelBase):
         # (encoder + max_len x {embed, project, attention, LSTM step, head, softmax, argmax}: ~8 launches per token)
         key = (B, max_len, bool(return_s))
         bufs = self.__dict__.setdefault("_dec_bufs", {})
+        if cons is not None:                           # the mixtures are M rows per step: probs and ids are the helper's
+            cb = cons.bufs(max_len, max_len)
+            bufs, key = self.__dict__.setdefault("_cons_dec_bufs", {}), key + (cons.G,)
+            if key not in bufs:
+                bufs[key] = (cb["start"], cb["mix"], self._f(max_len, B, R, A) if return_s else None, cb["ids"])
         if key not in bufs:
             bufs[key] = (torch.zeros(B, 1, dtype=torch.int32, device=self.device),
                          torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device),
@@ -1361,10 +1378,22 @@ class NIC(ModelBase):
                 self._decode_step(i, B, False, s_all[i] if return_s else None)
                 self.gemm_sk(self.Hs[i + 1], a.p("time_distributed_nonlinear/kernel"), self.inter[:B], B, H, U, U, H, H,
                              bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)     # :621
-                self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), probs[i], B, V, H, H, ldV, ldV,
+                logits = probs[i] if cons is None else cb["logits"]
+                self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), logits, B, V, H, H, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))                                # :623
                 if con is not None:
-                    con.step(i, probs[i], ldV, words if i > 0 else None)
+                    con.step(i, logits, ldV, words if i > 0 else None)
+                if cons is not None:                   # mix (+ argmax, or draw + spread) in the place of softmax + argmax
+                    draw = None
+                    if _filter is not None:
+                        draw = lambda p, out, rows, i=i: be.sample_topkp(p, out, rows, V, ldV, _filter[0], _filter[1], _filter[2],
+                                                                         False, self.seed, S_SAMPLE + i, 0, step_buf)
+                    elif _sample is not None:
+                        draw = lambda p, out, rows, i=i: be.sample_rows(p, out, rows, V, ldV, _sample[0], False, self.seed,
+                                                                        S_SAMPLE + i, _sample[1])
+                    cons.choose(logits, probs[i], cb["pick"][i], ids[i], draw)
+                    words = ids[i].view(B, 1)
+                    continue
                 be.softmax_cce(probs[i], None, probs[i], None, None, None, B, V, ldV, 0.0)
                 if _filter is not None:
                     be.sample_topkp(probs[i], ids[i], B, V, ldV, _filter[0], _filter[1], _filter[2], False, self.seed,
@@ -1374,13 +1403,15 @@ class NIC(ModelBase):
                 else:
                     be.sample_rows(probs[i], ids[i], B, V, ldV, _sample[0], False, self.seed, S_SAMPLE + i, _sample[1])
                 words = ids[i].view(B, 1)
-        ckey = con.key if con is not None else ()
+        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
         if _filter is not None:     # the stream step is read from step_buf on the device: captured like the greedy loop
             self._run_captured(("sample",) + key + tuple(_filter[:3]) + ckey, run)
         elif _sample is None:
             self._run_captured(("greedy",) + key + ckey, run)
         else:                      # the sampling stream step is a launch argument: not captured
             run()
+        if cons is not None:
+            ids = ids[:, :cons.M]                      # member 0's rows: every member holds the common word
         out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
         out_probs = probs[:, :, :V].permute(1, 0, 2).contiguous().cpu().numpy()
         # s (the dropout-free tanh activations, 44 MB at the BASELINE shape) is part of the reference's return tuple but
@@ -1469,7 +1500,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
-                    length_penalty=0.0, constraints=None):
+                    length_penalty=0.0, constraints=None, consensus=None):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,
         lc_NIC.py:640-692, recurse without returning; ThinkAndTell/evaluate.py:203-228 stops after one expansion), so
         the definition is this library's: standard log-probability beam search of width ``beam_width`` with the greedy
@@ -1483,13 +1514,22 @@ class NIC(ModelBase):
         ``constraints`` (model_base.DecodeConstraints): each live beam row's logits are constrained from the row's own path
         (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
         beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
-        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword."""
+        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword.
+        ``consensus`` (model_base.Consensus(members=G, ...)): the beams of image m are scored by the mixture of its G scans
+        (with n_subjects = S: of its S subject slices).  The inputs hold G * M rows, member-major, start_seq M entries; the
+        decoder rows are [G][M][k].  Per token one tnt_consensus_mix_f32 launch takes the softmax's place, the expansion
+        runs on the M * k mixed rows, one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the
+        member rows, and the state is gathered by the spread parents.  Sequences and scores are per image."""
         length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
         start = np.asarray(start_seq).reshape(-1)
-        B = start.shape[0]
-        Bk = B * k
+        cons = self._consensus(consensus, img_input, start.shape[0], k)
+        M = start.shape[0]                            # captions: the expansion runs on M * k rows
+        if cons is not None:
+            start = np.tile(start, cons.G)
+        B = start.shape[0]                            # staged scans: the decoder runs B * k rows, with consensus [G][M][k]
+        Bk, Mk = B * k, M * k
         con = self._constrain(constraints, Bk, max_len, k, int(end_id))
         rep = lambda t: np.repeat(np.asarray(t), k, axis=0)
         x = img_input.cpu().numpy() if isinstance(img_input, torch.Tensor) else np.asarray(img_input)
@@ -1498,12 +1538,18 @@ class NIC(ModelBase):
         Wl = a.p("lstm/kernel")
         dev, i32 = self.device, torch.int32
         words0 = torch.as_tensor(rep(start).astype(np.int32)).to(dev).view(Bk, 1)
-        score = [torch.zeros(Bk, device=dev), torch.zeros(Bk, device=dev)]
-        score[0].view(B, k)[:, 1:] = -1e30            # step 0: the k beams of a sample are copies, only beam 0 counts
-        fin = [torch.zeros(Bk, dtype=i32, device=dev), torch.zeros(Bk, dtype=i32, device=dev)]
-        parents = torch.zeros(max_len, Bk, dtype=i32, device=dev)
-        tokens = torch.zeros(max_len, Bk, dtype=i32, device=dev)
+        score = [torch.zeros(Mk, device=dev), torch.zeros(Mk, device=dev)]
+        score[0].view(M, k)[:, 1:] = -1e30            # step 0: the k beams of a sample are copies, only beam 0 counts
+        fin = [torch.zeros(Mk, dtype=i32, device=dev), torch.zeros(Mk, dtype=i32, device=dev)]
+        parents = torch.zeros(max_len, Mk, dtype=i32, device=dev)
+        tokens = torch.zeros(max_len, Mk, dtype=i32, device=dev)
         probs = self.logits[:Bk]
+        # what the decoder rows read back: the expansion's own outputs or, with consensus, their spread to the member rows
+        tok_d, par_d, fin_d = tokens, parents, fin
+        if cons is not None:
+            cb = cons.bufs(max_len, 1)
+            mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
+            cb["fin"].zero_()
         hg, cg = self._f(Bk, U), self._f(Bk, U)
         self._encode(Bk, False)
         words = words0
@@ -1519,19 +1565,24 @@ class NIC(ModelBase):
                          bias=a.p("time_distributed_softmax/bias"))
             cur, nxt = i & 1, (i & 1) ^ 1
             if con is not None:
-                con.step(i, probs, ldV, tokens[i - 1] if i > 0 else None, parents[i - 1] if i > 0 else None, fin[cur])
-            be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
-            be.beam_topk(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
+                con.step(i, probs, ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
+            if cons is None:
+                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
+                be.beam_topk(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
+            else:   # the mixture in the softmax's place, the expansion on the M*k mixed rows, its choice spread to the members
+                cons.mix(probs, mix)
+                be.beam_topk(mix, score[cur], fin[cur], M, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
+                cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
             # the surviving beams continue from their parents' LSTM state (row gather by parent)
-            be.embedding_fwd(self.Hs[i + 1], parents[i].view(Bk, 1), hg, Bk, 1, U, U, Bk)
-            be.embedding_fwd(self.Cs[i + 1], parents[i].view(Bk, 1), cg, Bk, 1, U, U, Bk)
+            be.embedding_fwd(self.Hs[i + 1], par_d[i].view(Bk, 1), hg, Bk, 1, U, U, Bk)
+            be.embedding_fwd(self.Cs[i + 1], par_d[i].view(Bk, 1), cg, Bk, 1, U, U, Bk)
             self.Hs[i + 1].copy_(hg)
             self.Cs[i + 1].copy_(cg)
-            words = tokens[i].view(Bk, 1)
-        final = score[max_len & 1].cpu().numpy().reshape(B, k)
+            words = tok_d[i].view(Bk, 1)
+        final = score[max_len & 1].cpu().numpy().reshape(M, k)
         par, tok = parents.cpu().numpy(), tokens.cpu().numpy()
-        seqs = np.zeros((B, k, max_len), np.int64)
-        for b in range(B):
+        seqs = np.zeros((M, k, max_len), np.int64)
+        for b in range(M):
             for r in range(k):
                 row = b * k + r
                 for i in range(max_len - 1, -1, -1):

@@ -282,6 +282,96 @@ class _ConstrainedDecode:
                                  self.bad if self.n_bad else None, self.n_bad)
 
 
+class Consensus:
+    """Consensus decoding, for the ``consensus=`` keyword of greedy_predict, sample_predict and beam_search of nic.NIC and
+    lc_nic.NIC: one caption from ``members`` = G scans of the same image (repeated trials, or the subjects of
+    lc_nic.NIC(n_subjects=G)).  At every token the members' next-word distributions are combined on the device
+    (tnt_consensus_mix_f32, include/tnt_hip.h) and the common word is fed back to all of them.
+      members  G, 1 .. 16.  The decode inputs hold G * M rows, member-major: rows [g*M, (g+1)*M) are member g's scans of the
+               M images (np.concatenate([trial1, trial2, ...])); start_seq has M entries
+      mode     "mean": the weighted mean of the members' softmaxes (the standard captioning ensemble);
+               "logmean": the renormalised weighted geometric mean
+      weights  G finite numbers > 0, normalised here to sum 1; None: 1/G each
+    Bad values raise ValueError here, before any launch; what depends on the model or the call is checked by the decode.
+    One model object decodes all members: mixing several models is out of scope (the row layout leaves room for it), and
+    so are NICfc, the ThinkAndTell / ShowAndTell generators and score_captions."""
+
+    MAX_MEMBERS = 16
+    MODES = ("mean", "logmean")
+
+    def __init__(self, members, mode="mean", weights=None):
+        if isinstance(members, bool) or not isinstance(members, (int, np.integer)) or not 1 <= members <= self.MAX_MEMBERS:
+            raise ValueError(f"members must be an int in [1, {self.MAX_MEMBERS}], got {members!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {self.MODES}, got {mode!r}")
+        if weights is not None:
+            try:
+                w = np.asarray(list(weights), dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError(f"weights must be {int(members)} numbers > 0 or None, got {weights!r}") from None
+            if w.shape[0] != members or not np.all(np.isfinite(w)) or not np.all(w > 0):
+                raise ValueError(f"weights must be {int(members)} finite numbers > 0 or None, got {weights!r}")
+            w = (w / w.sum()).astype(np.float32)
+            if not np.all(w > 0):
+                raise ValueError(f"weights must stay > 0 in float32 once normalised, got {weights!r}")
+            weights = tuple(float(v) for v in w)
+        self.members, self.mode, self.weights = int(members), mode, weights
+
+    def __repr__(self):
+        return f"Consensus(members={self.members}, mode={self.mode!r}, weights={self.weights})"
+
+
+class _ConsensusDecode:
+    """The host part of a consensus decode (ModelBase._consensus) of ``M`` samples x ``k`` beams from G members: the
+    decoder runs G*M*k rows (member-major, each member slab laid out [M][k]), the mixture lives on Rm = M*k rows.  Owns
+    the device buffers, the per-step launches and the suffix of the capture key."""
+
+    def __init__(self, model, c, M, k=1):
+        self.be, self.V, self.ldV, self.G, self.M, self.k = model.be, model.V, model.ldV, c.members, M, k
+        self.Rm, self.rows, self.mode = M * k, c.members * M * k, Consensus.MODES.index(c.mode)
+        self._bufs = model.__dict__.setdefault("_cons_bufs", {})
+        self._model = model
+        self.w = None
+        if c.weights is not None:       # one small buffer per distinct weight vector: the vector is part of the capture key
+            if ("w", c.weights) not in self._bufs:
+                self._bufs["w", c.weights] = torch.tensor(c.weights, dtype=torch.float32).to(model.device)
+            self.w = self._bufs["w", c.weights]
+        self.key = ("consensus", self.G, c.mode, c.weights)
+
+    def bufs(self, max_len, steps):
+        """static buffers per (G, M, k, max_len): start (rows, 1) int32, the start token of every member row; logits
+        (rows, ldV), one step's member logits; mix (steps, Rm, ldV), the
+        mixtures (steps = max_len keeps every step's for the return, 1 reuses one slab); pick (max_len, Rm) int32, what the
+        sampler chose on the mixed rows; ids / par (max_len, rows) and fin (rows) int32, the choice on the member rows"""
+        key = (self.G, self.M, self.k, max_len, steps)
+        if key not in self._bufs:
+            f, i32 = self._model._f, torch.int32
+            self._bufs[key] = dict(start=f(self.rows, 1, dtype=i32), logits=f(self.rows, self.ldV), mix=f(steps, self.Rm, self.ldV),
+                                   pick=f(max_len, self.Rm, dtype=i32), ids=f(max_len, self.rows, dtype=i32),
+                                   par=f(max_len, self.rows, dtype=i32), fin=f(self.rows, dtype=i32))
+        return self._bufs[key]
+
+    def mix(self, logits, mix, token=None):
+        """one step: the member rows' logits [rows][ldV] -> the mixture [Rm][ldV]; token (rows,) int32: its argmax, on
+        every member row"""
+        self.be.consensus_mix(logits, self.ldV, self.V, self.Rm, self.G, self.w, self.mode, mix, self.ldV, token)
+
+    def spread(self, token, parent, fin, token_out, parent_out, fin_out):
+        """what the step chose on the mixed rows, carried to the member rows"""
+        self.be.consensus_spread(token, parent, fin, self.Rm, self.G, token_out, parent_out, fin_out)
+
+    def choose(self, logits, mix, pick, ids, sampler=None):
+        """one token of a greedy (sampler None) or sampled decode: mix, then the argmax inside the mix launch, or
+        ``sampler(mix, pick, Rm)`` on the mixed rows (row r draws from the stream row r of a plain decode draws from) and
+        one spread launch.  ids (rows,) then holds the common word of every member row."""
+        if sampler is None:
+            self.mix(logits, mix, ids)
+        else:
+            self.mix(logits, mix)
+            sampler(mix, pick, self.Rm)
+            self.spread(pick, None, None, ids, None, None)
+
+
 def check_sampling(top_k, top_p, temperature):
     """host validation of the sampling filters (tnt_sample_topkp_f32): top_k an int >= 0 (0 = off), 0 < top_p <= 1
     (1 = off), temperature > 0.  Returns (int top_k, float top_p, float temperature); ValueError otherwise."""
@@ -1209,6 +1299,32 @@ class ModelBase:
             raise ValueError(f"{len(c.bad_ids)} bad ids + max_len {max_len} + 1 + beam width {beam_width} exceed the "
                              f"vocabulary of {V}: a step could be left without a token to choose")
         return _ConstrainedDecode(self, c, rows, max_len, eid if c.min_length > 0 else -1)
+
+    def _consensus(self, consensus, img_input, n_start, beam_width=1, training=False):
+        """The consensus-decode helper (``img_input``: the scans to stage, ``n_start`` entries of start_seq), or None when
+        ``consensus`` is None: then the decode issues the launches it issues without the keyword, under the same capture
+        key.  Refusals (before any launch): not a Consensus; training=True; a data-parallel model; n_rows not G * n_start;
+        for a multi-subject model, members other than n_subjects (the subject slices are the members)."""
+        c = consensus
+        if c is None:
+            return None
+        if not isinstance(c, Consensus):
+            raise ValueError(f"consensus must be a Consensus or None, got {c!r}")
+        if training:
+            raise ValueError("consensus decoding is an inference mode: training=True is refused")
+        if self.grad_sync is not None:
+            raise NotImplementedError("consensus decoding has no data-parallel schedule: decode on one device")
+        G, S = c.members, int(getattr(self, "S", 1))
+        n_rows = int(img_input.shape[0]) if hasattr(img_input, "shape") else len(img_input)
+        if S > 1 and G != S:
+            raise ValueError(f"a model of n_subjects = {S} decodes the consensus of its subject slices: members must be {S}, "
+                             f"got {G}")
+        if n_rows % G:
+            raise ValueError(f"consensus of {G} members needs G * M input rows (member-major), got {n_rows}")
+        if n_rows != G * n_start:
+            raise ValueError(f"consensus of {G} members over {n_rows} input rows decodes {n_rows // G} captions: start_seq "
+                             f"must have {n_rows // G} entries, got {n_start}")
+        return _ConsensusDecode(self, c, n_start, int(beam_width))
 
     def _run_captured(self, key, fn):
         """Run ``fn`` (a fixed launch sequence over static buffers) through a hipGraph:

@@ -855,18 +855,24 @@ class NIC(ModelBase):
 
     call = __call__
 
-    def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, constraints=None):
+    def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, constraints=None,
+                       consensus=None):
         """NIC.greedy_predict (NIC.py:148-195), inference mode; returns np.ndarray (max_len, B, 1, V).
         A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does.
         ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
         applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
         softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
-        a neutral object: the decode as it is without the keyword."""
-        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints)
+        a neutral object: the decode as it is without the keyword.
+        ``consensus`` (model_base.Consensus(members=G, ...)): one caption per image from G scans of it.  img_input, a0, c0
+        hold G * M rows, member-major (rows [g*M, (g+1)*M): member g), start_seq M entries; per token one
+        tnt_consensus_mix_f32 launch takes the place of softmax + argmax, the mixture's first maximum is fed to all members,
+        and a fed 0 masks the next LSTM step on every member.  Returns the mixtures, (max_len, M, 1, V).  None: the decode
+        as it is without the keyword."""
+        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints, consensus)
         return probs_all[:, :, :self.V].cpu().numpy()[:, :, None, :]
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       top_k=0, top_p=1.0, sample_step=0, constraints=None):
+                       top_k=0, top_p=1.0, sample_step=0, constraints=None, consensus=None):
         """greedy_predict with the argmax replaced by a categorical draw from each step's probabilities, filtered by
         ``top_k`` (>= 1: only the k most likely tokens; 0: off) and ``top_p`` (< 1: only the shortest most-likely prefix
         whose mass reaches top_p; 1: off) at ``temperature`` (tnt_sample_topkp_f32, definition in include/tnt_hip.h).
@@ -875,11 +881,14 @@ class NIC(ModelBase):
         greedy_predict; sample_step reaches the replay through a device word.
         ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what ``probs``
         holds then.
+        ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
+        of a plain decode of M scans uses) and is fed to all of them; ids and probs are per image (M rows).
         Returns (ids (B, max_len, 1) int64, probs (max_len, B, 1, V))."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)),
-                                      constraints)
+                                      constraints, consensus)
         V = self.V
+        ids = ids[:, :probs_all.shape[1]]              # consensus: member 0's rows (every member holds the common word)
         return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
                 probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
 
@@ -903,12 +912,17 @@ class NIC(ModelBase):
         be.lstm_step_fwd(xz, h0, c0, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h1, c1, None,
                          self.gates[0], B, U)
 
-    def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None):
+    def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
         sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None).  With
-        constraints on (ModelBase._constrain) the greedy loop keeps its ids per step too: the history is built from them."""
+        constraints on (ModelBase._constrain) the greedy loop keeps its ids per step too: the history is built from them.
+        With consensus on (ModelBase._consensus) the decoder runs the G * M member rows, probs holds the M mixtures per
+        step and ids the common word on every member row."""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
+        cons = self._consensus(consensus, img_input, start.shape[0])
+        if cons is not None:
+            start = start.repeat(cons.G)
         B = start.shape[0]
         con = self._constrain(constraints, B, max_len)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
@@ -917,14 +931,20 @@ class NIC(ModelBase):
         # static decode buffers per (B, max_len): the whole loop is one captured hipGraph
         key = (B, max_len)
         bufs = self.__dict__.setdefault("_dec_bufs", {})
-        if key not in bufs:
-            bufs[key] = (torch.zeros(B, 1, dtype=torch.int32, device=self.device),
-                         torch.zeros(B, 1, dtype=torch.int32, device=self.device),
-                         torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device))
-        start_buf, words, probs_all = bufs[key]
+        if cons is not None:                           # the helper's own buffers: the mixtures are M rows per step, not B
+            cb = cons.bufs(max_len, max_len)
+            start_buf, words, probs_all = cb["start"], None, cb["mix"]
+        else:
+            if key not in bufs:
+                bufs[key] = (torch.zeros(B, 1, dtype=torch.int32, device=self.device),
+                             torch.zeros(B, 1, dtype=torch.int32, device=self.device),
+                             torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device))
+            start_buf, words, probs_all = bufs[key]
         start_buf.copy_(start.view(B, 1))
         ids = None
-        if filt is not None or con is not None:
+        if cons is not None:
+            ids = cb["ids"]
+        elif filt is not None or con is not None:
             sbufs = self.__dict__.setdefault("_sample_ids", {})
             if key not in sbufs:
                 sbufs[key] = torch.zeros(max_len, B, dtype=torch.int32, device=self.device)
@@ -948,10 +968,17 @@ class NIC(ModelBase):
                 be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, prev if i > 0 else None, 1, 0, None,
                                  h[1 - cur], c[1 - cur], out, self.gates[0], B, U)
                 cur = 1 - cur
-                self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs_all[i], B, V, U, U, ldV, ldV,
+                logits = probs_all[i] if cons is None else cb["logits"]
+                self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), logits, B, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
                 if con is not None:
-                    con.step(i, probs_all[i], ldV, prev if i > 0 else None)
+                    con.step(i, logits, ldV, prev if i > 0 else None)
+                if cons is not None:                   # mix (+ argmax, or draw + spread) in the place of softmax + argmax
+                    cons.choose(logits, probs_all[i], cb["pick"][i], ids[i], None if filt is None else (
+                        lambda p, out, rows, i=i: be.sample_topkp(p, out, rows, V, ldV, filt[0], filt[1], filt[2], False,
+                                                                  self.seed, S_SAMPLE + i, 0, step_buf)))
+                    prev = ids[i].view(B, 1)
+                    continue
                 be.softmax_cce(probs_all[i], None, probs_all[i], None, None, None, B, V, ldV, 0.0)
                 if filt is None and con is None:
                     be.argmax_rows(probs_all[i], words, B, V, ldV)
@@ -962,7 +989,7 @@ class NIC(ModelBase):
                     be.sample_topkp(probs_all[i], ids[i], B, V, ldV, filt[0], filt[1], filt[2], False, self.seed,
                                     S_SAMPLE + i, 0, step_buf)
                     prev = ids[i].view(B, 1)
-        ckey = con.key if con is not None else ()
+        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
         if filt is None:
             self._run_captured(("greedy",) + key + ckey, run)
         else:
@@ -1023,7 +1050,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
-                    units=None, tokenizer=None, constraints=None):
+                    units=None, tokenizer=None, constraints=None, consensus=None):
         """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches
         it): log-probability beam search of width ``beam_width`` with greedy_predict's step, whose Keras mask rule it
         keeps (a 0 fed back masks the next LSTM step); at step 0 the k beams of a sample are copies and only beam 0
@@ -1038,35 +1065,49 @@ class NIC(ModelBase):
         (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
         beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
         object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword.
+        ``consensus`` (model_base.Consensus(members=G, ...)): the beams of image m are scored by the mixture of its G scans.
+        The inputs hold G * M rows, member-major, start_seq M entries; the decoder rows are [G][M][k].  Per token one
+        tnt_consensus_mix_f32 launch takes the softmax's place, tnt_beam_step_f32 expands the M * k mixed rows (U = 0: no
+        fused reorder), one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the member rows,
+        and the state is gathered by the spread parents.  Sequences and scores are per image: (M, k, max_len), (M, k).
         Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
         length-normalised key)."""
         k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        B = start.shape[0]
+        cons = self._consensus(consensus, img_input, start.shape[0], k)
+        G = cons.G if cons is not None else 1
+        M = start.shape[0]                             # captions: the expansion runs on M * k rows
+        B = G * M                                      # staged scans: the decoder runs B * k rows, with consensus [G][M][k]
         con = self._constrain(constraints, B * k, max_len, k, end_id)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
         U, E, V, ldV = self.U, self.E, self.V, self.ldV
-        Bk = B * k
-        key = (B, k, max_len, end_id)
+        Bk, Mk = B * k, M * k
+        key = (B, k, max_len, end_id) if cons is None else (B, k, max_len, end_id, G)
         bufs = self.__dict__.setdefault("_beam_bufs", {})
         if key not in bufs:
             dev, i32, f = self.device, torch.int32, self._f
-            init = f(B, k)
+            init = f(M, k)
             init[:, 1:] = -1e30                    # step 0: the k beams of a sample are copies, only beam 0 counts
             bufs[key] = dict(
                 rep=torch.arange(B, dtype=i32, device=dev).repeat_interleave(k).view(Bk, 1),
-                start=torch.zeros(Bk, 1, dtype=i32, device=dev), init=init.view(Bk),
-                score=f(2, Bk), fin=f(2, Bk, dtype=i32), pt=f(2, max_len, Bk, dtype=i32),
+                start=torch.zeros(Bk, 1, dtype=i32, device=dev), init=init.view(Mk),
+                score=f(2, Mk), fin=f(2, Mk, dtype=i32), pt=f(2, max_len, Mk, dtype=i32),
                 h=f(2, Bk, U), c=f(2, Bk, U), emb=f(Bk, E), xz=f(Bk, U, 4), out=f(Bk, U), gates=f(Bk, U, 4),
                 probs=f(Bk, ldV))
         bb = bufs[key]
-        bb["start"].copy_(start.repeat_interleave(k).view(Bk, 1))
+        bb["start"].copy_((start if cons is None else start.repeat(G)).repeat_interleave(k).view(Bk, 1))
         bb["score"][0].copy_(bb["init"])
         bb["fin"][0].zero_()
         score, fin, parents, tokens = bb["score"], bb["fin"], bb["pt"][0], bb["pt"][1]
         h, c, emb, xz, out, probs = bb["h"], bb["c"], bb["emb"], bb["xz"], bb["out"], bb["probs"]
+        # what the decoder rows read back: the expansion's own outputs or, with consensus, their spread to the member rows
+        tok_d, par_d, fin_d = tokens, parents, fin
+        if cons is not None:
+            cb = cons.bufs(max_len, 1)
+            mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
+            cb["fin"].zero_()
 
         def run():
             self._decode_encode(B)
@@ -1075,7 +1116,7 @@ class NIC(ModelBase):
             be.embedding_fwd(self.Hs[1], bb["rep"], h[0], Bk, 1, U, U, B)
             be.embedding_fwd(self.Cs[1], bb["rep"], c[0], Bk, 1, U, U, B)
             for i in range(max_len):
-                tok = bb["start"] if i == 0 else tokens[i - 1].view(Bk, 1)
+                tok = bb["start"] if i == 0 else tok_d[i - 1].view(Bk, 1)
                 be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, Bk, 1, E, E, V)
                 self.gemm_sk(emb, Wl, xz, Bk, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
                 be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, tok if i > 0 else None, 1, 0, None,
@@ -1084,21 +1125,32 @@ class NIC(ModelBase):
                              bias=a.p("time_distributed_softmax/bias"))
                 cur, nxt = i & 1, (i & 1) ^ 1
                 if con is not None:
-                    con.step(i, probs, ldV, tokens[i - 1] if i > 0 else None, parents[i - 1] if i > 0 else None, fin[cur])
+                    con.step(i, probs, ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
+                if cons is not None:
+                    # the mixture in the softmax's place; the expansion on the M*k mixed rows without its fused reorder; its
+                    # choice spread to the member rows; every member's state (h[1], c[1]) gathered by its own parent rows
+                    cons.mix(probs, mix)
+                    be.beam_step(mix, ldV, score[cur], fin[cur], M, V, k, end_id, score[nxt], parents[i], tokens[i],
+                                 fin[nxt], None, None, 0, 0, None, None)
+                    cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
+                    be.embedding_fwd(h[1], par_d[i].view(Bk, 1), h[0], Bk, 1, U, U, Bk)
+                    be.embedding_fwd(c[1], par_d[i].view(Bk, 1), c[0], Bk, 1, U, U, Bk)
+                    continue
                 be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
                 # expansion, and the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]
                 be.beam_step(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
                              fin[nxt], h[1], c[1], U, U, h[0], c[0])
-        self._run_captured(("beam",) + key + (con.key if con is not None else ()), run)
+        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
+        self._run_captured(("beam",) + key + ckey, run)
         pt = bb["pt"].cpu().numpy()
-        final = score[max_len & 1].cpu().numpy().reshape(B, k)
+        final = score[max_len & 1].cpu().numpy().reshape(M, k)
         par, tok = pt[0], pt[1]
-        seqs = np.zeros((max_len, Bk), np.int64)
-        row = np.arange(Bk)
+        seqs = np.zeros((max_len, Mk), np.int64)
+        row = np.arange(Mk)
         for i in range(max_len - 1, -1, -1):           # back-track every beam at once
             seqs[i] = tok[i, row]
             row = par[i, row]
-        seqs = seqs.T.reshape(B, k, max_len)
+        seqs = seqs.T.reshape(M, k, max_len)
         if length_penalty > 0:
             return length_normalise(seqs, final, end_id, length_penalty)
         return seqs, final

@@ -651,6 +651,18 @@ class HipBackend:
                    _p(hist_out), ldh, _p(last_token), _p(parent), _p(fin), float(theta), int(n), int(m), int(end_id), _p(bad_ids),
                    int(n_bad), self._s())
 
+    def consensus_mix(self, logits, ld, V, Rm, G, w, mode, mix, ldm, token):
+        """the G member rows' next-word distributions mixed into one per mixed row, plus its argmax on every member row
+        (tnt_consensus_mix_f32; definition in include/tnt_hip.h); mode 0 mean, 1 logmean; w and token are nullable"""
+        self._call(self.lib.tnt_consensus_mix_f32, "tnt_consensus_mix_f32", _p(logits), ld, V, Rm, G, _p(w), int(mode), _p(mix),
+                   ldm, _p(token), self._s())
+
+    def consensus_spread(self, token, parent, fin, Rm, G, token_out, parent_out, fin_out):
+        """a step's choice on the Rm mixed rows carried to the G*Rm member rows (tnt_consensus_spread_i32); each of token /
+        parent / fin is nullable"""
+        self._call(self.lib.tnt_consensus_spread_i32, "tnt_consensus_spread_i32", _p(token), _p(parent), _p(fin), Rm, G,
+                   _p(token_out), _p(parent_out), _p(fin_out), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
