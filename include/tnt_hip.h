@@ -93,7 +93,8 @@ int32_t tnt_gemm_fused_cfg(int32_t M, int32_t N, int32_t K, int32_t transA, int3
  * csrc/gemm3.hip; tools/gemm3_scan.py). */
 int32_t tnt_gemm3_f32(const float* A, const float* B, float* C, const float* bias, float* colsum, const float* A2,
                       float* C2, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t transA,
-                      int32_t transB, int32_t tile, int32_t splitk, float* work, uint32_t* sync, void* stream);
+                      int32_t transB, int32_t tile, int32_t splitk, float* work, uint32_t* sync, const int32_t* live,
+                      int32_t live_mode, void* stream);
 /* Riders (all nullable): bias [N] added to every row; colsum [N] = sum_k B[k][n] (transA = 1, transB = 0, splitk = 1 only:
  * B = dY, so this is the bias gradient of the layer whose kernel gradient the product is); A2 / C2 (both or neither): a
  * second product C2 = op(A2) op(B) with the same dims and strides in the same launch (the LSTM's kernel and
@@ -104,7 +105,16 @@ int32_t tnt_gemm3_f32(const float* A, const float* B, float* C, const float* bia
  * one after the other; `sync`: tnt_gemm3_sync_words(...) uint32 words (one: an error flag, zero before the first use;
  * nonzero afterwards means a workgroup gave up waiting for a peer -- the launch did not fit the device in one round -- and
  * C is invalid).
- * batch = 2 with A2 / C2, else 1. */
+ * batch = 2 with A2 / C2, else 1.
+ * live (nullable; null: the launch is bit-identical to one without it): ONE int32 word in device memory, read by every
+ * workgroup when the launch runs -- an extent only the device knows (the number of distinct rows of tnt_stage_batch_map_f32),
+ * so that a recorded launch replays with whatever the word holds then.  The value is clamped to [0, extent].
+ *   live_mode = 1 (transA = 0): only rows [0, *live) of A and C exist.  The grid is that of M; a workgroup whose tile starts
+ *     at or past *live returns at once, rows of A past it read as zero, rows of C at or past it are NOT written.
+ *   live_mode = 2 (transA = 1, transB = 0, splitk = 1): only rows [0, *live) of the contraction (of A and B as stored) exist:
+ *     C = sum over k < *live, colsum likewise; *live = 0 gives C = bias or 0 and colsum = 0.
+ *   Any other combination: TNT_BADARG.  To get a tile that suits the live extent, ask tnt_gemm3_plan for the shape with the
+ *   EXPECTED extent in place of M (the result stays correct for any value of the word: the grid always covers M). */
 /* The (tile, splitk) the library's cost model picks for a shape (batch = 2 for a dual launch; allow_split = 0 restricts
  * the choice to splitk = 1, which the colsum rider needs). */
 int32_t tnt_gemm3_plan(int32_t M, int32_t N, int32_t K, int32_t transA, int32_t transB, int32_t batch,
@@ -123,6 +133,7 @@ typedef struct tnt_gemm3_desc {
   const float* A; const float* B; float* C; const float* bias; float* colsum; const float* A2; float* C2;
   int32_t M, N, K, lda, ldb, ldc, transA, transB, tile, splitk;
   float* work; uint32_t* sync;
+  const int32_t* live; int32_t live_mode;      /* as tnt_gemm3_f32; several products may share one word */
 } tnt_gemm3_desc;
 int32_t tnt_gemm3_pair_supported(int32_t tile1, int32_t transA1, int32_t transB1, int32_t tile2, int32_t transA2,
                                  int32_t transB2);
@@ -502,11 +513,15 @@ int32_t tnt_ln_lstm_cell_bwd_f32(const float* dh_a, const float* dh_b, const flo
  * model state untouched when it is set.  S <= 64.  Same arithmetic as S calls of tnt_lstm_step_fwd_f32.  A step pays one XCD-local barrier instead of a
  * dependent kernel launch and the recurrent weights stay in VGPRs; needs U == 512, B <= 128 and a 256-CU device on
  * which a 256-workgroup launch places 32 workgroups on each of the 8 XCDs: tnt_lstm_seq_supported() tests exactly that
- * (one synchronising probe launch per process, so call it outside any graph capture) and returns 1 or 0. */
+ * (one synchronising probe launch per process, so call it outside any graph capture) and returns 1 or 0.
+ * out_pos (nullable; null: bit-identical to the call without it): the row map of tnt_stage_batch_map_f32, [S - mask_s0][B]
+ * int32.  Sequence position (t, b) then writes its output to row out_pos[t*B + b] of `out` instead of row t*B + b, and
+ * writes nothing where that is negative. */
 int32_t tnt_lstm_seq_supported(int32_t B, int32_t U);
 int32_t tnt_lstm_seq_fwd_f32(const float* xz, float* hs, float* cs, const float* Ur, const float* xz_bias,
                              const int32_t* mask_ids, int32_t mask_T, int32_t mask_s0, float* out,
-                             float* gates, int32_t S, int32_t B, int32_t U, uint32_t* sync, float* guard_out, void* stream);
+                             float* gates, int32_t S, int32_t B, int32_t U, uint32_t* sync, float* guard_out,
+                             const int32_t* out_pos, void* stream);
 /* Persistent form of the BPTT chain of the same sequence (the S calls of tnt_lstm_step_bwd_f32 that nic.NIC makes, in
  * ONE launch): step s = S-1 .. 0 reads gates[s], cs[s+1], cs[s] and writes dz[s] ([S][B][U][4]); steps s >= mask_s0
  * add dout_seq[s - mask_s0] (gradient of the sequence output, nullable) and are masked by column s - mask_s0 of
@@ -514,12 +529,15 @@ int32_t tnt_lstm_seq_fwd_f32(const float* xz, float* hs, float* cs, const float*
  * the carried output gradient is dropped below mask_s0 (NIC.py:138: the feature step's output is not part of the
  * sequence).  Weights stay in registers, the recurrent product is "pushed" as partial tiles through `work`
  * (tnt_lstm_seq_bwd_work_floats(B, U) floats, 16-byte aligned) inside one XCD per 16-row block; sync / guard_out and the
- * device requirements as tnt_lstm_seq_fwd_f32 (same sync buffer, launches on one stream).  Deterministic. */
+ * device requirements as tnt_lstm_seq_fwd_f32 (same sync buffer, launches on one stream).  Deterministic.
+ * dout_pos (nullable; null: bit-identical to the call without it): the same row map; position (t, b) reads its output
+ * gradient from row dout_pos[t*B + b] of dout_seq and takes zero where that is negative (the row it was merged into carries
+ * its share: the chain hands a masked step's output gradient on to the last live step anyway). */
 int32_t tnt_lstm_seq_bwd_work_floats(int32_t B, int32_t U);
 int32_t tnt_lstm_seq_bwd_f32(const float* Ur, const float* dout_seq, const int32_t* mask_ids, int32_t mask_T,
                              int32_t mask_s0, const float* gates, const float* cs, float* dz, float* work,
                              int64_t work_floats, int32_t S, int32_t B, int32_t U, uint32_t* sync,
-                             float* guard_out, void* stream);
+                             float* guard_out, const int32_t* dout_pos, void* stream);
 /* bwd of one step, fused with the recurrent matmul of the step after it:
  *   da = da_pass_in + dh_ext + (dz_next ? dz_next[B][U][4] @ Ur^T : 0)
  *   dout = dout_in + dout_t ; masked rows pass (da, dc, dout) through, dz = 0
@@ -569,6 +587,14 @@ int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* target, float* p
                             float* loss_row, float* correct_row, float* dlogits,
                             int32_t rows, int32_t V, int32_t ld, float gscale,
                             int32_t from_logits, int32_t mask_zero, void* stream);
+/* tnt_softmax_cce_f32(from_logits = 0, mask_zero = 0) over the distinct rows of a row map (tnt_stage_batch_map_f32): rows at
+ * or past live[0] (one int32 in device memory, read when the launch runs) are neither read nor written; row r stands for
+ * row_weight[r] identical positions, so loss_row[r], correct_row[r] and dlogits[r] are the plain values times row_weight[r].
+ * `rows` is the size of the grid and must cover the largest value live[0] can take.  live and row_weight must be given. */
+int32_t tnt_softmax_cce_live_f32(const float* logits, const int32_t* target, float* probs,
+                                 float* loss_row, float* correct_row, float* dlogits,
+                                 int32_t rows, int32_t V, int32_t ld, float gscale,
+                                 const int32_t* live, const float* row_weight, void* stream);
 /* ---- the same head with label smoothing: tf.keras.losses.CategoricalCrossentropy(from_logits=False,
  * label_smoothing=eps), one launch (smooth.hip).  With V classes, p = softmax(x) and target id y:
  *   ys_v      = (1 - eps) [v == y] + eps / V
@@ -841,6 +867,19 @@ int32_t tnt_stage_batch_f32(const float* x, float* x_dst, const int32_t* cap, in
                             const int32_t* tgt, int32_t* tgt_tmajor, const float* a0, float* h0,
                             const float* c0, float* c0_dst, int32_t B, int32_t T, int32_t N, int32_t ldx,
                             int32_t U, float* xT_dst, int32_t ldt, void* stream);
+/* tnt_stage_batch_f32 with the row map of the vocabulary head riding in the same launch (one extra workgroup).  The text LSTM
+ * carries its output through a step that is fed id 0 (mask_zero), so position (t, b), t >= 1, with cap[b][t] == 0 holds
+ * the output row of the nearest earlier position of caption b that has a row; where its target equals that row's target
+ * as well, its logits, loss and dlogits are repeats.  Such a position is MERGED: pos[t*B + b] = -1.  Every other position
+ * gets a row of its own, pos[t*B + b] = 0 .. live-1 in time-major order.  row_weight[r] = 1 + the number of positions merged
+ * into row r (float, exact), tgt_compact[r] = the row's target, live[0] = the number of rows.  row_weight, tgt_compact and
+ * (nullable) loss_row, corr_row are zeroed in [live, B*T).  tgt is required.  Padded captions (<start>, L words, <end>,
+ * 0 ...; tgt[t] = cap[t+1]) have L + 2 rows each. */
+int32_t tnt_stage_batch_map_f32(const float* x, float* x_dst, const int32_t* cap, int32_t* cap_dst,
+                                const int32_t* tgt, int32_t* tgt_tmajor, const float* a0, float* h0,
+                                const float* c0, float* c0_dst, int32_t B, int32_t T, int32_t N, int32_t ldx,
+                                int32_t U, float* xT_dst, int32_t ldt, int32_t* pos, float* row_weight,
+                                int32_t* tgt_compact, int32_t* live, float* loss_row, float* corr_row, void* stream);
 /* tnt_stage_batch_f32 with tnt_dropout_mask4_u8's job riding in the same launch: keep_out [keep_sites][keep_n / 4] bytes, the
  * keep masks of sites keep_site0 .. of stream (keep_seed, *keep_step_dev) -- the attention-dropout masks of the training
  * step this batch feeds (attention.py:36).  The Philox-bound mask blocks and the memory-bound copies share the chip; the

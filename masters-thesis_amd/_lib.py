@@ -23,7 +23,7 @@ SIGNATURES = {
     "tnt_gemm_f32": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, P],
     "tnt_gemm_fused_f32": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
     "tnt_gemm_fused_cfg": [I32, I32, I32, I32, I32, I32],
-    "tnt_gemm3_f32": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P],
+    "tnt_gemm3_f32": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P, I32, P],
     "tnt_gemm3_plan": [I32, I32, I32, I32, I32, I32, I32, P, P],
     "tnt_gemm3_work_floats": [I32, I32, I32, I32, I32],
     "tnt_gemm3_sync_words": [I32, I32, I32, I32],
@@ -60,14 +60,15 @@ SIGNATURES = {
     "tnt_embedding_bwd_sparse_f32": [P, P, P, P, P, I32, I32, I32, I32, I32, F32, U64, U32, P, I32, P],
     "tnt_embedding_bwd_f32": [P, P, P, P, P, I32, I32, I32, I32, I32, P],
     "tnt_lstm_seq_supported": [I32, I32],
-    "tnt_lstm_seq_fwd_f32": [P, P, P, P, P, P, I32, I32, P, P, I32, I32, I32, P, P, P],
+    "tnt_lstm_seq_fwd_f32": [P, P, P, P, P, P, I32, I32, P, P, I32, I32, I32, P, P, P, P],
     "tnt_lstm_seq_bwd_work_floats": [I32, I32],
-    "tnt_lstm_seq_bwd_f32": [P, P, P, I32, I32, P, P, P, P, I64, I32, I32, I32, P, P, P],
+    "tnt_lstm_seq_bwd_f32": [P, P, P, I32, I32, P, P, P, P, I64, I32, I32, I32, P, P, P, P],
     "tnt_lstm_step_fwd_f32": [P, P, P, P, P, P, I32, P, I32, I32, P, P, P, P, P, I32, I32, P, P],
     "tnt_ln_lstm_cell_fwd_f32": [P, P, P, P, P, P, P, P, P, P, P, I32, I32, F32, P],
     "tnt_ln_lstm_cell_bwd_f32": [P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, P],
     "tnt_lstm_step_bwd_f32": [P, P, P, P, P, P, P, P, I32, I32, P, P, P, P, P, P, P, I32, I32, P, I32, P, P],
     "tnt_softmax_cce_f32": [P, P, P, P, P, P, I32, I32, I32, F32, I32, I32, P],
+    "tnt_softmax_cce_live_f32": [P, P, P, P, P, P, I32, I32, I32, F32, P, P, P],
     "tnt_softmax_cce_smooth_f32": [P, P, P, P, P, P, I32, I32, I32, F32, F32, P],
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
@@ -119,6 +120,7 @@ SIGNATURES = {
     "tnt_locally_dense_bwd_split_f32": [P, I32, P, P, P, P, I32, P, P, P, I32, I32, I32, I32, P],
     "tnt_sum2_f32": [P, P, P, P, I32, F32, P],
     "tnt_stage_batch_f32": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P],
+    "tnt_stage_batch_map_f32": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P, P, P, P, P, P, P],
     "tnt_stage_batch_h16": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P],
     "tnt_stage_batch_masks_f32": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P, I64, I32, F32, U64, U32, P, P],
     "tnt_scst_cce_f32": [P, I32, I32, P, I32, P, P, I32, P, P, P, I32, F32, P],

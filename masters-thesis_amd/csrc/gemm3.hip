@@ -46,6 +46,12 @@ struct G3Args {
   int splitk, nst_split;      // workgroups per output tile, stages per workgroup
   int err_word;               // index of the error word in sync
   int nx;                     // workgroups per product (tiles x splitk)
+  // optional device-side live extent (one int32 word, read by every workgroup; clamped to [0, extent]):
+  //   live_mode 1: only rows [0, *live) of A / C exist (A K-contiguous) -- the tile map stays that of M, a workgroup whose
+  //                tile starts at or past *live leaves at once, rows past it read as zero and are not stored;
+  //   live_mode 2: only rows [0, *live) of the contraction exist (TN, no split) -- K, the stage count and the column sums
+  //                follow *live; 0 gives the empty sum.
+  const int* live; int live_mode;
 };
 
 // One LDS-DMA piece: 64 lanes x 16 bytes from the buffer `rsrc` + voff (per lane; out-of-range lanes deliver zeros) to
@@ -122,10 +128,13 @@ struct G3Cfg {
   static constexpr int SHMEM = NS * (BM_ + BN_) * BK * 4 + 1024;
   static constexpr bool TA = !A_KC, TB = B_KC;
   static_assert(SHMEM <= 160 * 1024, "LDS ring does not fit");
-  static __device__ __forceinline__ void body(const G3Args& g, int bx, int by);
+  // LIVE: the launch carries a device-side extent (G3Args::live).  A compile-time switch: the launches without one run the
+  // very code they ran before the extent existed (on the 10-20 us products of a step its few extra scalar instructions showed).
+  template <bool LIVE> static __device__ __forceinline__ void body(const G3Args& g, int bx, int by);
 };
 
 template <bool A_KC, bool B_KC, int TM, int TN, int WGM, int WGN, int BK, int NS>
+template <bool LIVE>
 __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::body(const G3Args& g, const int bx, const int by) {
   constexpr int NW = WGM * WGN;
   constexpr int WM = 16 * TM, WN = 16 * TN, BM = WM * WGM, BN = WN * WGN;
@@ -146,20 +155,28 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
   const int r = lane & 15, q = lane >> 4;
   const int MT = (g.M + BM - 1) / BM, NTl = (g.N + BN - 1) / BN;
   const int S = g.splitk;
+  int Mv = g.M, Kv = g.K, nst = g.nst;                         // the extents this launch really has (G3Args::live)
+  if (LIVE && g.live != nullptr) {
+    const int lv = max(*g.live, 0);
+    if (g.live_mode == 1) Mv = min(lv, g.M);
+    else { Kv = min(lv, g.K); nst = (Kv + BK - 1) / BK; }
+  }
   const int nwg = MT * NTl * S, bid = bx;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;       // XCD-contiguous unit order (bijective for any nwg)
   const int u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int t = u / S, z = u - t * S;                          // output tile, K split
   const int m0 = (t % MT) * BM, n0 = (t / MT) * BN;
+  if (LIVE && m0 >= Mv) return;   // a tile of rows that do not exist: every K split of it takes this exit (same word), before
+                               // the first barrier, LDS-DMA piece or exchange access
   const bool second = by != 0;                                 // the second product of a dual launch
   const float* Ag = second ? g.A2 : g.A;
   float* Cg = second ? g.C2 : g.C;
   const int s_begin = z * g.nst_split;
-  const int s_end = min(g.nst, s_begin + g.nst_split);        // this workgroup's stages [s_begin, s_end)
+  const int s_end = min(nst, s_begin + g.nst_split);           // this workgroup's stages [s_begin, s_end)
   const int nloc = max(s_end - s_begin, 0);
 
   // ---- LDS-DMA sources (the extern array is the kernel's only LDS object: byte offsets inside it are LDS addresses)
-  const int rowsA = A_KC ? g.M : g.K, rowsB = B_KC ? g.N : g.K;
+  const int rowsA = A_KC ? Mv : Kv, rowsB = B_KC ? g.N : Kv;
   const g3_v4i rsA = g3_rsrc(Ag, (unsigned)(rowsA * g.lda * 4));
   const g3_v4i rsB = g3_rsrc(g.B, (unsigned)(rowsB * g.ldb * 4));
   int offA[OA::NIW], offB[OB::NIW], kcA[KMASK ? OA::NIW : 1];
@@ -181,7 +198,7 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
       if (OB::NI % NW != 0 && j >= OB::NI) offB[i] = 0x7fffffff;
     }
   }
-  const int k_end = min(((g.K + 3) & ~3), s_end * BK);       // first k this workgroup must not multiply (NT mask)
+  const int k_end = min(((Kv + 3) & ~3), s_end * BK);       // first k this workgroup must not multiply (NT mask)
   const int stepA = A_KC ? BK * 4 : BK * g.lda * 4, stepB = B_KC ? BK * 4 : BK * g.ldb * 4;
   // Piece p (0 .. NPW-1) of this wave for the NEXT stage not yet issued -> the LDS buffer at byte offset boff; the
   // per-lane offsets then advance by one stage.  Stages past the workgroup's last one are issued too (every stage has the
@@ -486,7 +503,7 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const int row = row_of(tm, 4 * q + reg);
-      if (row >= g.M) continue;
+      if (row >= Mv) continue;
       float* crow = Cg + (long)row * g.ldc;
       if constexpr (B_KC) {
 #pragma unroll
@@ -518,19 +535,19 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
   }
 }
 
-template <class Cfg>
-__global__ __launch_bounds__(Cfg::NTHREADS) void gemm3_kernel(G3Args g) { Cfg::body(g, blockIdx.x, blockIdx.y); }
+template <class Cfg, bool LIVE>
+__global__ __launch_bounds__(Cfg::NTHREADS) void gemm3_kernel(G3Args g) { Cfg::template body<LIVE>(g, blockIdx.x, blockIdx.y); }
 
 // Two independent products in ONE launch: workgroups [0, n1) run problem 1, the rest problem 2.  A launch boundary costs a
 // GEMM its ramp-up and its drain (~4-6 us of a 25-50 us kernel); back to back in one grid the second problem's workgroups
 // start on the CUs the first one's tail leaves idle.  (Workgroup programs of both configurations in one code object: the
 // register and LDS footprint is the larger of the two.)
-template <class C1, class C2>
+template <class C1, class C2, bool LIVE>
 __global__ __launch_bounds__(256) void gemm3_pair_kernel(G3Args g1, G3Args g2, int n1) {
   static_assert(C1::NTHREADS == 256 && C2::NTHREADS == 256, "pair launches use 4-wave configurations");
   const int b = blockIdx.x;
-  if (b < n1) C1::body(g1, b % g1.nx, b / g1.nx);
-  else C2::body(g2, (b - n1) % g2.nx, (b - n1) / g2.nx);
+  if (b < n1) C1::template body<LIVE>(g1, b % g1.nx, b / g1.nx);
+  else C2::template body<LIVE>(g2, (b - n1) % g2.nx, (b - n1) / g2.nx);
 }
 
 // derived launch parameters + argument checks of one problem for configuration Cfg; 0 or an error code
@@ -554,11 +571,9 @@ int32_t g3_prepare(G3Args& g) {
   return 0;
 }
 
-template <class Cfg>
-int32_t g3_launch_cfg(const G3Args& g0, hipStream_t s) {
-  G3Args g = g0;
-  if (int32_t rc = g3_prepare<Cfg>(g)) return rc;
-  auto kern = gemm3_kernel<Cfg>;
+template <class Cfg, bool LIVE>
+int32_t g3_launch_kern(const G3Args& g, hipStream_t s) {
+  auto kern = gemm3_kernel<Cfg, LIVE>;
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SHMEM) != hipSuccess)
@@ -569,16 +584,17 @@ int32_t g3_launch_cfg(const G3Args& g0, hipStream_t s) {
   TNT_LAUNCH_CHECK();
   return 0;
 }
+template <class Cfg>
+int32_t g3_launch_cfg(const G3Args& g0, hipStream_t s) {
+  G3Args g = g0;
+  if (int32_t rc = g3_prepare<Cfg>(g)) return rc;
+  return g.live != nullptr ? g3_launch_kern<Cfg, true>(g, s) : g3_launch_kern<Cfg, false>(g, s);
+}
 
-template <class C1, class C2>
-int32_t g3_launch_pair(const G3Args& a0, const G3Args& b0, hipStream_t s) {
-  G3Args a = a0, b = b0;
-  if (int32_t rc = g3_prepare<C1>(a)) return rc;
-  if (int32_t rc = g3_prepare<C2>(b)) return rc;
-  const int n1 = a.nx * (a.A2 ? 2 : 1), n2 = b.nx * (b.A2 ? 2 : 1);
-  if ((a.splitk > 1 || b.splitk > 1) && n1 + n2 > 1024) return TNT_BADARG(16);
+template <class C1, class C2, bool LIVE>
+int32_t g3_launch_pair_kern(const G3Args& a, const G3Args& b, int n1, int n2, hipStream_t s) {
   constexpr int shmem = C1::SHMEM > C2::SHMEM ? C1::SHMEM : C2::SHMEM;
-  auto kern = gemm3_pair_kernel<C1, C2>;
+  auto kern = gemm3_pair_kernel<C1, C2, LIVE>;
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, shmem) != hipSuccess)
@@ -588,6 +604,16 @@ int32_t g3_launch_pair(const G3Args& a0, const G3Args& b0, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3(n1 + n2), dim3(256), shmem, s, a, b, n1);
   TNT_LAUNCH_CHECK();
   return 0;
+}
+template <class C1, class C2>
+int32_t g3_launch_pair(const G3Args& a0, const G3Args& b0, hipStream_t s) {
+  G3Args a = a0, b = b0;
+  if (int32_t rc = g3_prepare<C1>(a)) return rc;
+  if (int32_t rc = g3_prepare<C2>(b)) return rc;
+  const int n1 = a.nx * (a.A2 ? 2 : 1), n2 = b.nx * (b.A2 ? 2 : 1);
+  if ((a.splitk > 1 || b.splitk > 1) && n1 + n2 > 1024) return TNT_BADARG(16);
+  if (a.live != nullptr || b.live != nullptr) return g3_launch_pair_kern<C1, C2, true>(a, b, n1, n2, s);
+  return g3_launch_pair_kern<C1, C2, false>(a, b, n1, n2, s);
 }
 
 template <int TM, int TN, int WGM, int WGN, int BK, int NS>
@@ -698,8 +724,13 @@ extern "C" int32_t tnt_gemm3_plan(int32_t M, int32_t N, int32_t K, int32_t trans
 namespace {
 int32_t g3_fill(G3Args& g, const float* A, const float* B, float* C, const float* bias, float* colsum, const float* A2, float* C2,
                 int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t transA, int32_t transB,
-                int32_t splitk, float* work, uint32_t* sync) {
+                int32_t splitk, float* work, uint32_t* sync, const int32_t* live, int32_t live_mode) {
   if (M <= 0 || N <= 0 || K <= 0) return TNT_BADARG(8);
+  if (live != nullptr) {
+    if (live_mode == 1) { if (transA) return TNT_BADARG(21); }                      // rows of a K-contiguous A
+    else if (live_mode == 2) { if (!transA || transB || splitk > 1) return TNT_BADARG(21); }   // TN, whole K per workgroup
+    else return TNT_BADARG(21);
+  }
   if (transA && transB) return TNT_BADARG(15);
   if (!tnt_aligned16(A) || !tnt_aligned16(B) || !tnt_aligned16(C) || lda % 4 || ldb % 4 || ldc % 4) return TNT_BADARG(1);
   if ((A2 == nullptr) != (C2 == nullptr)) return TNT_BADARG(6);
@@ -711,6 +742,7 @@ int32_t g3_fill(G3Args& g, const float* A, const float* B, float* C, const float
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.work = work; g.sync = sync;
   g.A2 = A2; g.C2 = C2; g.colsum = colsum;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.nst = 0; g.splitk = splitk;
+  g.live = live; g.live_mode = live ? live_mode : 0;
   return 0;
 }
 }  // namespace
@@ -718,9 +750,10 @@ int32_t g3_fill(G3Args& g, const float* A, const float* B, float* C, const float
 extern "C" int32_t tnt_gemm3_f32(const float* A, const float* B, float* C, const float* bias, float* colsum,
                                  const float* A2, float* C2, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                                  int32_t ldc, int32_t transA, int32_t transB, int32_t tile, int32_t splitk, float* work,
-                                 uint32_t* sync, void* stream) {
+                                 uint32_t* sync, const int32_t* live, int32_t live_mode, void* stream) {
   G3Args g;
-  if (int32_t rc = g3_fill(g, A, B, C, bias, colsum, A2, C2, M, N, K, lda, ldb, ldc, transA, transB, splitk, work, sync)) return rc;
+  if (int32_t rc = g3_fill(g, A, B, C, bias, colsum, A2, C2, M, N, K, lda, ldb, ldc, transA, transB, splitk, work, sync, live,
+                           live_mode)) return rc;
   hipStream_t s = tnt_stream(stream);
   const bool tA = transA != 0, tB = transB != 0;
   switch (tile) {
@@ -756,9 +789,9 @@ extern "C" int32_t tnt_gemm3_pair_f32(const tnt_gemm3_desc* p, const tnt_gemm3_d
   if (!tnt_gemm3_pair_supported(p->tile, p->transA, p->transB, q->tile, q->transA, q->transB)) return TNT_BADARG(13);
   G3Args a, b;
   if (int32_t rc = g3_fill(a, p->A, p->B, p->C, p->bias, p->colsum, p->A2, p->C2, p->M, p->N, p->K, p->lda, p->ldb, p->ldc, p->transA,
-                           p->transB, p->splitk, p->work, p->sync)) return rc;
+                           p->transB, p->splitk, p->work, p->sync, p->live, p->live_mode)) return rc;
   if (int32_t rc = g3_fill(b, q->A, q->B, q->C, q->bias, q->colsum, q->A2, q->C2, q->M, q->N, q->K, q->lda, q->ldb, q->ldc, q->transA,
-                           q->transB, q->splitk, q->work, q->sync)) return rc;
+                           q->transB, q->splitk, q->work, q->sync, q->live, q->live_mode)) return rc;
   if (a.splitk > 1 && b.splitk > 1 && a.work == b.work) return TNT_BADARG(2);       // concurrent exchanges need their own space
   hipStream_t s = tnt_stream(stream);
   using TN4 = G3Cfg<false, false, 2, 5, 4, 1, 32, 3>;

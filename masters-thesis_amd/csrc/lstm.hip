@@ -420,6 +420,8 @@ struct LstmSeqArgs {
   int S, B, U, mask_T, mask_s0;
   unsigned* sync;        // TNT_SEQ_SYNC_WORDS words, layout and protocol in tnt_seq_sync.h
   float* guard_out;      // nullable: set to the error code when the error word is seen set
+  const int* pos;        // nullable row map of `out` (tnt_stage_batch_map_f32): sequence position (t, b) writes row pos[t*B + b],
+                         // or nothing where that is negative (its output is a carried copy that has no row of its own)
 };
 
 // POLL: the hand-off of h between the steps needs no flag round at all.  hs[st+1] is written exactly once per launch, so
@@ -537,12 +539,16 @@ __global__ __launch_bounds__(1024) void lstm_seq_fwd_kernel(LstmSeqArgs a) {
   const int ebs = eok ? eb : 0;
   const bool have_ids = a.mask_ids != nullptr;
   if (have_ids && a.mask_s0 <= 0) mid = a.mask_ids[ebs * a.mask_T - a.mask_s0];
+  const bool have_pos = a.pos != nullptr && a.out != nullptr;      // the row of `out` travels with the mask id
+  int prw = -1;
+  if (have_pos && a.mask_s0 <= 0) prw = a.pos[-a.mask_s0 * B + ebs];
   for (int st = 0; st < a.S; ++st) {
     if (POLL && eok && st + 2 <= a.S) a.hs[(long)(st + 2) * BU + ee] = sentinel;       // published by step st + 1
     LST(0);
     float4 x4n = make_float4(0.f, 0.f, 0.f, 0.f);
-    int midn = 1;
+    int midn = 1, prn = -1;
     const bool pf_x = st + 1 < a.S, pf_m = have_ids && st + 1 < a.S && st + 1 >= a.mask_s0;      // uniform
+    const bool pf_p = have_pos && st + 1 < a.S && st + 1 >= a.mask_s0;
     if (RB == 8) {
       // ---- this lane's float4 of h[st]: row rg*4 + j of the block, k = 32 w + 4 cg .. + 3 (sc1 loads, polled)
       const int xrow = rb * RB + x_rg * 4 + x_j;
@@ -566,6 +572,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_fwd_kernel(LstmSeqArgs a) {
       LST(1);
       if (pf_x) x4n = *reinterpret_cast<const float4*>(a.xz + ((long)(st + 1) * BU + ees) * 4);
       if (pf_m) midn = a.mask_ids[ebs * a.mask_T + (st + 1 - a.mask_s0)];
+      if (pf_p) prn = a.pos[(st + 1 - a.mask_s0) * B + ebs];
       floatx4 xa[2];
       xa[0] = (floatx4){0.f, 0.f, 0.f, 0.f}; xa[1] = xa[0];
 #define TNT_X4(q)                                                                                              \
@@ -612,6 +619,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_fwd_kernel(LstmSeqArgs a) {
       }
       if (pf_x) x4n = *reinterpret_cast<const float4*>(a.xz + ((long)(st + 1) * BU + ees) * 4);
       if (pf_m) midn = a.mask_ids[ebs * a.mask_T + (st + 1 - a.mask_s0)];
+      if (pf_p) prn = a.pos[(st + 1 - a.mask_s0) * B + ebs];
       floatx4 acc[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc[g] = (floatx4){0.f, 0.f, 0.f, 0.f};
@@ -633,8 +641,8 @@ __global__ __launch_bounds__(1024) void lstm_seq_fwd_kernel(LstmSeqArgs a) {
     // (the prefetched operands change hands HERE, in front of the step's stores: the copy waits for the prefetch -- issued
     // an MFMA phase ago -- and behind the stores it would also wait for their acknowledgements)
     const float4 xc = x4;
-    const int midc = mid;
-    x4 = x4n; mid = midn;
+    const int midc = mid, prc = prw;
+    x4 = x4n; mid = midn; prw = prn;
     if (eok) {
       float z[4] = {xc.x + zb.x, xc.y + zb.y, xc.z + zb.z, xc.w + zb.w};
       if (RB == 8) {
@@ -665,7 +673,11 @@ __global__ __launch_bounds__(1024) void lstm_seq_fwd_kernel(LstmSeqArgs a) {
       if (POLL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this thread's reset of hs[st+2] is in L2 first
       a.hs[(long)(st + 1) * BU + ee] = hn;
       a.cs[(long)(st + 1) * BU + ee] = cn;
-      if (a.out && seq) { op = m ? h2 : op; a.out[(long)(st - a.mask_s0) * BU + ee] = op; }
+      if (a.out && seq) {
+        op = m ? h2 : op;
+        if (!have_pos) a.out[(long)(st - a.mask_s0) * BU + ee] = op;
+        else if (prc >= 0) a.out[(long)prc * U + eu] = op;
+      }
       *reinterpret_cast<float4*>(a.gates + ((long)st * BU + ee) * 4) = make_float4(gi, gf, gg, go);
       hp = hn; cp = cn;
     }
@@ -700,6 +712,7 @@ struct LstmSeqBwdArgs {
   const float* Ur; const float* dout_seq; const int* mask_ids; const float* gates; const float* cs;
   float* dz; float* xch; unsigned* sync; float* guard_out;
   int S, B, U, mask_T, mask_s0;
+  const int* pos;        // nullable row map of dout_seq (as LstmSeqArgs::pos): a position without a row contributes zero
 };
 
 constexpr int SB_DZLD = 68;                                   // row stride of the dz tile in LDS (16-byte rows, 68 % 64 == 4)
@@ -798,6 +811,11 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_kernel(LstmSeqBwdArgs a) {
   const long BU = (long)B * U;
   const int ridx = ((erow >> 2) * 16 + ecol) * 4 + (erow & 3);           // where the MFMA C layout keeps (erow, ecol)
   float da_c = 0.f, dc_c = 0.f, dout_c = 0.f;
+  // row of dout_seq of the step about to run: fetched one step ahead with the step's other epilogue operands, so that the
+  // load of the gradient row never waits for the load of its index
+  const bool have_pos = a.pos != nullptr && a.dout_seq != nullptr;
+  int pos_c = -1;
+  if (have_pos && S - 1 >= a.mask_s0) pos_c = a.pos[(S - 1 - a.mask_s0) * B + (eok ? eb : 0)];
   const float sentinel = __uint_as_float(TNT_SEQ_SENTINEL);
   const float4 sent4 = make_float4(sentinel, sentinel, sentinel, sentinel);
   // this lane's chunk of the tile for workgroup `dest` in ring buffer `buf`: slot [dest][src = ub], lane-major 1 KB tiles
@@ -829,11 +847,15 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_kernel(LstmSeqBwdArgs a) {
     const long ees = eok ? ee : 0;
     float4 g4;
     float cval, cprev, dout_t = 0.f;
-    int mid = 1;
+    int mid = 1, pos_n = -1;
     auto epi_loads = [&]() {
       g4 = *reinterpret_cast<const float4*>(a.gates + ((long)s * BU + ees) * 4);
       cval = a.cs[(long)(s + 1) * BU + ees]; cprev = a.cs[(long)s * BU + ees];
-      if (seq && a.dout_seq) dout_t = a.dout_seq[(long)(s - a.mask_s0) * BU + ees];
+      if (seq && a.dout_seq) {
+        if (!have_pos) dout_t = a.dout_seq[(long)(s - a.mask_s0) * BU + ees];
+        else if (pos_c >= 0) dout_t = a.dout_seq[(long)pos_c * U + (eok ? eu : 0)];
+      }
+      if (have_pos && s - 1 >= a.mask_s0) pos_n = a.pos[(s - 1 - a.mask_s0) * B + (eok ? eb : 0)];
       if (seq && a.mask_ids) mid = a.mask_ids[(eok ? eb : 0) * a.mask_T + (s - a.mask_s0)];
     };
     if (s == S - 1) epi_loads();                             // the first step of the chain has no push
@@ -920,7 +942,9 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_kernel(LstmSeqBwdArgs a) {
       }
     }
     // ---- cell backward (same arithmetic as bwd_epilogue of the per-step kernel)
-    asm volatile("" : "+v"(g4.x), "+v"(g4.y), "+v"(g4.z), "+v"(g4.w), "+v"(cval), "+v"(cprev), "+v"(dout_t), "+v"(mid));
+    asm volatile("" : "+v"(g4.x), "+v"(g4.y), "+v"(g4.z), "+v"(g4.w), "+v"(cval), "+v"(cprev), "+v"(dout_t), "+v"(mid),
+                 "+v"(pos_n));
+    pos_c = pos_n;
     if (eok) {
       const bool m = mid != 0;
       const float dout = (seq ? dout_c : 0.f) + dout_t;
@@ -1163,7 +1187,7 @@ extern "C" int32_t tnt_lstm_seq_supported(int32_t B, int32_t U) {
 extern "C" int32_t tnt_lstm_seq_fwd_f32(const float* xz, float* hs, float* cs, const float* Ur, const float* xz_bias,
                                         const int32_t* mask_ids, int32_t mask_T, int32_t mask_s0, float* out,
                                         float* gates, int32_t S, int32_t B, int32_t U, uint32_t* sync, float* guard_out,
-                                        void* stream) {
+                                        const int32_t* out_pos, void* stream) {
   if (S <= 0 || S - 1 > TNT_SEQ_MAX_BARRIERS || sync == nullptr) return TNT_BADARG(11);
   if (!tnt_lstm_seq_supported(B, U)) return TNT_BADARG(13);
   if ((long)(S + 1) * B * U * 4 >= (1L << 32)) return TNT_BADARG(2);
@@ -1172,6 +1196,7 @@ extern "C" int32_t tnt_lstm_seq_fwd_f32(const float* xz, float* hs, float* cs, c
   LstmSeqArgs a;
   a.xz = xz; a.hs = hs; a.cs = cs; a.Ur = Ur; a.zbias = xz_bias; a.mask_ids = mask_ids; a.out = out; a.gates = gates;
   a.S = S; a.B = B; a.U = U; a.mask_T = mask_T; a.mask_s0 = mask_s0; a.sync = sync; a.guard_out = guard_out;
+  a.pos = out_pos;
   static const bool flags_only = getenv("TNT_SEQ_FLAGS") && atoi(getenv("TNT_SEQ_FLAGS")) != 0;       // A/B switch
   static const bool rb8 = !(getenv("TNT_SEQ_RB16") && atoi(getenv("TNT_SEQ_RB16")) != 0);             // A/B switch: 16-row blocks
   if (flags_only) hipLaunchKernelGGL((lstm_seq_fwd_kernel<false, 16>), dim3(256), dim3(1024), SEQ_LDS_BYTES, s, a);
@@ -1184,7 +1209,7 @@ extern "C" int32_t tnt_lstm_seq_fwd_f32(const float* xz, float* hs, float* cs, c
 extern "C" int32_t tnt_lstm_seq_bwd_f32(const float* Ur, const float* dout_seq, const int32_t* mask_ids, int32_t mask_T,
                                         int32_t mask_s0, const float* gates, const float* cs, float* dz, float* work,
                                         int64_t work_floats, int32_t S, int32_t B, int32_t U, uint32_t* sync,
-                                        float* guard_out, void* stream) {
+                                        float* guard_out, const int32_t* dout_pos, void* stream) {
   if (S <= 0 || S - 1 > TNT_SEQ_MAX_BARRIERS || sync == nullptr || work == nullptr) return TNT_BADARG(11);
   if (!tnt_lstm_seq_supported(B, U)) return TNT_BADARG(13);
   if (mask_s0 < 0 || mask_s0 > S || (mask_ids != nullptr && S - mask_s0 > mask_T)) return TNT_BADARG(5);
@@ -1201,6 +1226,7 @@ extern "C" int32_t tnt_lstm_seq_bwd_f32(const float* Ur, const float* dout_seq, 
   LstmSeqBwdArgs a;
   a.Ur = Ur; a.dout_seq = dout_seq; a.mask_ids = mask_ids; a.gates = gates; a.cs = cs; a.dz = dz; a.xch = work;
   a.sync = sync; a.guard_out = guard_out; a.S = S; a.B = B; a.U = U; a.mask_T = mask_T; a.mask_s0 = mask_s0;
+  a.pos = dout_pos;
   static const bool flags_only = getenv("TNT_SEQ_FLAGS") && atoi(getenv("TNT_SEQ_FLAGS")) != 0;       // A/B switch
   static const bool rb8 = !(getenv("TNT_SEQ_RB16") && atoi(getenv("TNT_SEQ_RB16")) != 0);             // A/B switch: 16-row blocks
   if (flags_only) hipLaunchKernelGGL((lstm_seq_bwd_kernel<false, 16>), dim3(256), dim3(1024), SB_LDS_BYTES, tnt_stream(stream), a);

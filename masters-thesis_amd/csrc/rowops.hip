@@ -404,7 +404,121 @@ struct StageArgs {
   // optional riding job (blocks >= nstage): the keep masks of tnt_dropout_mask4_u8 for the step that this batch feeds
   uint8_t* mk_out; long mk_n4, mk_total; float mk_rate; uint64_t mk_seed; uint32_t mk_site0; const uint32_t* mk_step_dev;
   int nstage;
+  // optional riding job (the LAST block): the row map of the vocabulary head (tnt_stage_batch_map_f32)
+  int* map_pos; float* map_w; int* map_tgt; int* map_live; float* map_loss; float* map_corr;
 };
+// Row map of the vocabulary head, one workgroup.  The text LSTM carries its output through a step that is fed id 0, so position
+// (t, b) with cap[b][t] == 0, t >= 1, holds the SAME output row as the nearest earlier position of caption b that has a row;
+// where its target is the same too, logits, loss and dlogits repeat and the position is merged into that row (pos = -1, the
+// row's multiplicity + 1).  Every other position gets a row of its own, numbered in time-major order (stable: deterministic).
+// A fed 0 whose target differs keeps its own row (the chain writes the carried output there): correct for any input.
+constexpr int STAGE_MAP_LDS = 1024;      // positions the map holds in LDS (3 arrays + the scan counts inside the 64 x 65 tile)
+// ... with caption ids, targets and the map itself in LDS: every global access is one coalesced pass (B * T <= STAGE_MAP_LDS)
+template <typename SA>
+__device__ __forceinline__ void stage_rowmap_lds(const SA& a, int* lds) {
+  int* s_cap = lds; int* s_tgt = lds + STAGE_MAP_LDS; int* s_pos = lds + 2 * STAGE_MAP_LDS; int* s_cnt = lds + 3 * STAGE_MAP_LDS;
+  const int B = a.B, T = a.T, n = B * T, tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) { s_cap[i] = a.cap[i]; s_tgt[i] = a.tgt[i]; }
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {
+    int rep_y = 0;
+    for (int t = 0; t < T; ++t) {
+      const int id = s_cap[b * T + t], y = s_tgt[b * T + t];
+      const bool merged = t > 0 && id == 0 && y == rep_y;
+      s_pos[t * B + b] = merged ? -1 : 1;
+      if (!merged) rep_y = y;
+    }
+  }
+  __syncthreads();
+  const int per = (n + 255) / 256, lo = min(tid * per, n), hi = min(lo + per, n);
+  int c = 0;
+  for (int i = lo; i < hi; ++i) c += s_pos[i] > 0 ? 1 : 0;
+  s_cnt[tid] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int k = 0; k < 256; ++k) { const int v = s_cnt[k]; s_cnt[k] = run; run += v; }
+    s_cnt[256] = run;
+    a.map_live[0] = run;
+  }
+  __syncthreads();
+  int idx = s_cnt[tid];
+  const int live = s_cnt[256];
+  for (int i = lo; i < hi; ++i)
+    if (s_pos[i] > 0) s_pos[i] = idx++;
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {
+    int rep = -1, cnt = 0;
+    for (int t = 0; t < T; ++t) {
+      const int p = s_pos[t * B + b];
+      if (p >= 0) {
+        if (rep >= 0) a.map_w[rep] = (float)cnt;
+        rep = p; cnt = 1;
+        a.map_tgt[p] = s_tgt[b * T + t];
+      } else {
+        ++cnt;
+      }
+    }
+    if (rep >= 0) a.map_w[rep] = (float)cnt;
+  }
+  for (int i = tid; i < n; i += 256) a.map_pos[i] = s_pos[i];
+  for (int i = live + tid; i < n; i += 256) {
+    a.map_w[i] = 0.f; a.map_tgt[i] = 0;
+    if (a.map_loss) a.map_loss[i] = 0.f;
+    if (a.map_corr) a.map_corr[i] = 0.f;
+  }
+}
+// ... any size: the map is worked on in place in global memory (a workgroup barrier orders the passes)
+template <typename SA>
+__device__ __forceinline__ void stage_rowmap(const SA& a, int* s_cnt) {
+  const int B = a.B, T = a.T, n = B * T, tid = threadIdx.x;
+  for (int b = tid; b < B; b += 256) {                    // 1: which positions have a row (1) or are merged (-1)
+    int rep_y = 0;
+    for (int t = 0; t < T; ++t) {
+      const int id = a.cap[b * T + t], y = a.tgt[b * T + t];
+      const bool merged = t > 0 && id == 0 && y == rep_y;
+      a.map_pos[t * B + b] = merged ? -1 : 1;
+      if (!merged) rep_y = y;
+    }
+  }
+  __syncthreads();
+  const int per = (n + 255) / 256, lo = min(tid * per, n), hi = min(lo + per, n);
+  int c = 0;                                             // 2: number the rows, time-major
+  for (int i = lo; i < hi; ++i) c += a.map_pos[i] > 0 ? 1 : 0;
+  s_cnt[tid] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int k = 0; k < 256; ++k) { const int v = s_cnt[k]; s_cnt[k] = run; run += v; }
+    s_cnt[256] = run;
+    a.map_live[0] = run;
+  }
+  __syncthreads();
+  int idx = s_cnt[tid];
+  const int live = s_cnt[256];
+  for (int i = lo; i < hi; ++i)
+    if (a.map_pos[i] > 0) a.map_pos[i] = idx++;
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {                    // 3: multiplicities and targets of the rows
+    int rep = -1, cnt = 0;
+    for (int t = 0; t < T; ++t) {
+      const int p = a.map_pos[t * B + b];
+      if (p >= 0) {
+        if (rep >= 0) a.map_w[rep] = (float)cnt;
+        rep = p; cnt = 1;
+        a.map_tgt[p] = a.tgt[b * T + t];
+      } else {
+        ++cnt;
+      }
+    }
+    if (rep >= 0) a.map_w[rep] = (float)cnt;
+  }
+  for (int i = live + tid; i < n; i += 256) {             // rows past the live extent: nothing, and they sum to nothing
+    a.map_w[i] = 0.f; a.map_tgt[i] = 0;
+    if (a.map_loss) a.map_loss[i] = 0.f;
+    if (a.map_corr) a.map_corr[i] = 0.f;
+  }
+}
 __device__ __forceinline__ float stage_ld(const float* p) { return *p; }
 __device__ __forceinline__ float stage_ld(const __half* p) { return __half2float(*p); }
 __device__ __forceinline__ float4 stage_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -414,11 +528,20 @@ __device__ __forceinline__ float4 stage_ld4(const __half* p) {          // 8-byt
   const float2 a = __half22float2(lo), b = __half22float2(hi);
   return make_float4(a.x, a.y, b.x, b.y);
 }
-template <typename XT>
+// MAP: the launch carries the row-map block (a compile-time switch: the launches without it run the code they always ran)
+template <typename XT, bool MAP>
 __global__ __launch_bounds__(256) void stage_batch_kernel(StageArgs<XT> a) {
+  __shared__ float tile[64][65];              // the transposing blocks' tile; the row-map block's work space
+  static_assert(sizeof(tile) >= (3 * STAGE_MAP_LDS + 257) * sizeof(int), "the row map's LDS arrays live in the tile");
+  if (MAP && blockIdx.x == gridDim.x - 1) {
+    int* lds = reinterpret_cast<int*>(&tile[0][0]);
+    if (a.B * a.T <= STAGE_MAP_LDS) stage_rowmap_lds(a, lds);
+    else stage_rowmap(a, lds);
+    return;
+  }
   if ((int)blockIdx.x >= a.nstage) {          // Philox-bound, the copies around it memory-bound: they share the chip
     const uint32_t st = a.mk_step_dev ? a.mk_step_dev[0] : 0u;
-    const long nb = gridDim.x - a.nstage;
+    const long nb = gridDim.x - a.nstage - (MAP ? 1 : 0);
     for (long g = (long)(blockIdx.x - a.nstage) * 256 + threadIdx.x; g < a.mk_total; g += nb * 256) {
       const long k = g / a.mk_n4, gi = g - k * a.mk_n4;
       bool kp[4];
@@ -429,7 +552,6 @@ __global__ __launch_bounds__(256) void stage_batch_kernel(StageArgs<XT> a) {
   }
   if ((int)blockIdx.x >= a.ncopy) {
     // voxel-major copy for the region-wise encoder's gather: tile = 64 voxels x 64 batch rows through LDS
-    __shared__ float tile[64][65];
     const int ntc = (a.N + 63) / 64, ntr = (a.B + 63) / 64;
     for (int t = blockIdx.x - a.ncopy; t < ntc * ntr; t += a.nstage - a.ncopy) {
       const int c0 = (t % ntc) * 64, r0 = (t / ntc) * 64;
@@ -1332,8 +1454,11 @@ int32_t stage_batch_launch(const XT* x, float* x_dst, const int32_t* cap, int32_
                            int32_t* tgt_tmajor, const float* a0, float* h0, const float* c0, float* c0_dst, int32_t B,
                            int32_t T, int32_t N, int32_t ldx, int32_t U, float* xT_dst, int32_t ldt, void* stream,
                            uint8_t* keep_out = nullptr, int64_t keep_n = 0, int32_t keep_sites = 0, float keep_rate = 0.f,
-                           uint64_t keep_seed = 0, uint32_t keep_site0 = 0, const uint32_t* keep_step_dev = nullptr) {
+                           uint64_t keep_seed = 0, uint32_t keep_site0 = 0, const uint32_t* keep_step_dev = nullptr,
+                           int32_t* map_pos = nullptr, float* map_w = nullptr, int32_t* map_tgt = nullptr,
+                           int32_t* map_live = nullptr, float* map_loss = nullptr, float* map_corr = nullptr) {
   if (B <= 0 || T <= 0 || N <= 0 || ldx < N || U <= 0) return TNT_BADARG(11);
+  if (map_pos != nullptr && (map_w == nullptr || map_tgt == nullptr || map_live == nullptr || tgt == nullptr)) return TNT_BADARG(19);
   if (keep_out != nullptr && (keep_n <= 0 || keep_n % 4 != 0 || keep_sites <= 0)) return TNT_BADARG(19);
   if (xT_dst && ldt < B) return TNT_BADARG(16);
   const bool vec = (N % 4 == 0) && (ldx % 4 == 0);
@@ -1353,7 +1478,11 @@ int32_t stage_batch_launch(const XT* x, float* x_dst, const int32_t* cap, int32_
     nmask = (a.mk_total + 255) / 256;
     if (nmask > 8192) nmask = 8192;
   }
-  hipLaunchKernelGGL(stage_batch_kernel<XT>, dim3(a.nstage + (int)nmask), dim3(256), 0, tnt_stream(stream), a);
+  a.map_pos = map_pos; a.map_w = map_w; a.map_tgt = map_tgt; a.map_live = map_live; a.map_loss = map_loss; a.map_corr = map_corr;
+  if (map_pos != nullptr)
+    hipLaunchKernelGGL((stage_batch_kernel<XT, true>), dim3(a.nstage + (int)nmask + 1), dim3(256), 0, tnt_stream(stream), a);
+  else
+    hipLaunchKernelGGL((stage_batch_kernel<XT, false>), dim3(a.nstage + (int)nmask), dim3(256), 0, tnt_stream(stream), a);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -1365,6 +1494,19 @@ extern "C" int32_t tnt_stage_batch_f32(const float* x, float* x_dst, const int32
                                        int32_t U, float* xT_dst, int32_t ldt, void* stream) {
   return stage_batch_launch<float>(x, x_dst, cap, cap_dst, tgt, tgt_tmajor, a0, h0, c0, c0_dst, B, T, N, ldx, U, xT_dst,
                                    ldt, stream);
+}
+
+/* see include/tnt_hip.h */
+extern "C" int32_t tnt_stage_batch_map_f32(const float* x, float* x_dst, const int32_t* cap, int32_t* cap_dst,
+                                           const int32_t* tgt, int32_t* tgt_tmajor, const float* a0, float* h0,
+                                           const float* c0, float* c0_dst, int32_t B, int32_t T, int32_t N, int32_t ldx,
+                                           int32_t U, float* xT_dst, int32_t ldt, int32_t* pos, float* row_weight,
+                                           int32_t* tgt_compact, int32_t* live, float* loss_row, float* corr_row,
+                                           void* stream) {
+  if (pos == nullptr) return TNT_BADARG(17);
+  return stage_batch_launch<float>(x, x_dst, cap, cap_dst, tgt, tgt_tmajor, a0, h0, c0, c0_dst, B, T, N, ldx, U, xT_dst,
+                                   ldt, stream, nullptr, 0, 0, 0.f, 0, 0, nullptr, pos, row_weight, tgt_compact, live,
+                                   loss_row, corr_row);
 }
 
 extern "C" int32_t tnt_stage_batch_masks_f32(const float* x, float* x_dst, const int32_t* cap, int32_t* cap_dst,
@@ -1385,4 +1527,4 @@ extern "C" int32_t tnt_stage_batch_h16(const uint16_t* x_half, float* x_dst, con
                                     h0, c0, c0_dst, B, T, N, ldx, U, xT_dst, ldt, stream);
 }
 
-extern "C" int32_t tnt_version(void) { return 114; }
+extern "C" int32_t tnt_version(void) { return 115; }

@@ -357,10 +357,13 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 // one 256-thread workgroup per row
 __global__ __launch_bounds__(256) void softmax_cce_kernel(const float* logits, const int* target, float* probs,
                                                           float* loss_row, float* correct_row, float* dlogits, int rows,
-                                                          int V, int ld, float gscale, int from_logits, int mask_zero) {
+                                                          int V, int ld, float gscale, int from_logits, int mask_zero,
+                                                          const int* live, const float* wrow) {
   __shared__ ArgMax sha[4];
   __shared__ float shf[4];
   const int row = blockIdx.x;
+  if (live != nullptr && row >= live[0]) return;        // rows past the live extent do nothing (tnt_softmax_cce_live_f32)
+  const float wr = wrow != nullptr ? wrow[row] : 1.f;   // the row's multiplicity scales its loss, accuracy and gradient
   const float* x = logits + (long)row * ld;
   ArgMax am; am.v = -INFINITY; am.i = 0x7fffffff;
   for (int j = threadIdx.x; j < V; j += 256) {
@@ -380,19 +383,20 @@ __global__ __launch_bounds__(256) void softmax_cce_kernel(const float* logits, c
   // keras from_logits=False: clip(p, 1e-7, 1-1e-7), zero gradient where the clip is active.
   // from_logits=True (SparseCategoricalCrossentropy, ThinkAndTell/train.py:262-263): lse - x_y, no clip.
   // mask_zero: rows whose target id is 0 contribute neither loss nor gradient (model.py:319-334).
-  const bool live = !(mask_zero && y == 0);
-  const bool active = live && (from_logits || ((py >= 1e-7f) && (py <= 1.f - 1e-7f)));
+  const bool unmasked = !(mask_zero && y == 0);
+  const bool active = unmasked && (from_logits || ((py >= 1e-7f) && (py <= 1.f - 1e-7f)));
   if (threadIdx.x == 0 && target) {
     float l;
     if (from_logits) l = logf(Z) + m - xy;
     else l = -logf(fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f));
-    if (loss_row) loss_row[row] = live ? l : 0.f;
-    if (correct_row) correct_row[row] = (am.i == y) ? 1.f : 0.f;
+    if (loss_row) loss_row[row] = unmasked ? l * wr : 0.f;
+    if (correct_row) correct_row[row] = (am.i == y) ? wr : 0.f;
   }
+  const float gsw = gscale * wr;
   // logits may alias probs/dlogits: every thread reads its own elements before overwriting them
   for (int j = threadIdx.x; j < V; j += 256) {
     const float p = expf(x[j] - m) * invZ;
-    if (dlogits) dlogits[(long)row * ld + j] = active ? (p - (j == y ? 1.f : 0.f)) * gscale : 0.f;
+    if (dlogits) dlogits[(long)row * ld + j] = active ? (p - (j == y ? 1.f : 0.f)) * gsw : 0.f;
     if (probs && probs != dlogits) probs[(long)row * ld + j] = p;
   }
 }
@@ -406,14 +410,18 @@ __global__ __launch_bounds__(256) void softmax_cce_kernel(const float* logits, c
 // The kernel touches only its window [0, 1024*NV4) of each row: a pad column inside the window is written as zero
 // in every output (probs, dlogits) the call writes, and one at or beyond it (ld > 1024*NV4, e.g. V = 1024 with
 // ld = 1028) is neither read nor written.  The generic kernel above neither reads nor writes any pad column.
-template <int NV4>
+// LIVE (tnt_softmax_cce_live_f32): rows at or past live[0] do nothing, row r is weighted by wrow[r]; a compile-time switch, so
+// the plain head runs the code it always ran.
+template <int NV4, bool LIVE = false>
 __global__ __launch_bounds__(256) void softmax_cce_reg_kernel(const float* logits, const int* target, float* probs,
                                                               float* loss_row, float* correct_row, float* dlogits,
                                                               int rows, int V, int ld, float gscale, int from_logits,
-                                                              int mask_zero) {
+                                                              int mask_zero, const int* live, const float* wrow) {
   __shared__ float shf[4];
   __shared__ int shi[4];
   const int row = blockIdx.x, tid = threadIdx.x;
+  if (LIVE && row >= live[0]) return;
+  const float wr = LIVE ? wrow[row] : 1.f;
   const float* x = logits + (long)row * ld;
   float4 v[NV4];
   float m = -INFINITY;
@@ -463,16 +471,16 @@ __global__ __launch_bounds__(256) void softmax_cce_reg_kernel(const float* logit
   am = min(min(shi[0], shi[1]), min(shi[2], shi[3]));
   const float invZ = 1.f / Z;
   const float py = (y >= 0 && y < V) ? expf(xy - m) * invZ : 0.f;
-  const bool live = !(mask_zero && y == 0);
-  const bool active = live && (from_logits || ((py >= 1e-7f) && (py <= 1.f - 1e-7f)));
+  const bool unmasked = !(mask_zero && y == 0);
+  const bool active = unmasked && (from_logits || ((py >= 1e-7f) && (py <= 1.f - 1e-7f)));
   if (tid == 0 && target) {
     float l;
     if (from_logits) l = logf(Z) + m - xy;
     else l = -logf(fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f));
-    if (loss_row) loss_row[row] = live ? l : 0.f;
-    if (correct_row) correct_row[row] = (am == y) ? 1.f : 0.f;
+    if (loss_row) loss_row[row] = unmasked ? l * wr : 0.f;
+    if (correct_row) correct_row[row] = (am == y) ? wr : 0.f;
   }
-  const float gs = active ? gscale : 0.f;
+  const float gs = active ? gscale * wr : 0.f;
   float* drow = dlogits ? dlogits + (long)row * ld : nullptr;
   float* prow = (probs && probs != dlogits) ? probs + (long)row * ld : nullptr;
 #pragma unroll
@@ -709,9 +717,11 @@ extern "C" int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* targe
   const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
                   (!dlogits || tnt_aligned16(dlogits));
   const int nv4 = (V + 1023) / 1024;
+  const int* live = nullptr;             // the plain head: every row, unit weights
+  const float* wrow = nullptr;
 #define TNT_SMX(N)                                                                                              \
   hipLaunchKernelGGL((softmax_cce_reg_kernel<N>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, \
-                     correct_row, dlogits, rows, V, ld, gscale, from_logits, mask_zero)
+                     correct_row, dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow)
   if (al && nv4 == 1) TNT_SMX(1);
   else if (al && nv4 == 2) TNT_SMX(2);
   else if (al && nv4 <= 4) TNT_SMX(4);
@@ -719,8 +729,38 @@ extern "C" int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* targe
   else if (al && nv4 <= 8) TNT_SMX(8);
   else
     hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
-                       dlogits, rows, V, ld, gscale, from_logits, mask_zero);
+                       dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow);
 #undef TNT_SMX
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+/* see include/tnt_hip.h; the kernel ladder of tnt_softmax_cce_f32 with the live word and the row weights passed on */
+extern "C" int32_t tnt_softmax_cce_live_f32(const float* logits, const int32_t* target, float* probs, float* loss_row,
+                                            float* correct_row, float* dlogits, int32_t rows, int32_t V, int32_t ld,
+                                            float gscale, const int32_t* live, const float* row_weight, void* stream) {
+  if (live == nullptr || row_weight == nullptr) return TNT_BADARG(10);
+  if (rows == 0) return 0;
+  if (rows < 0) return TNT_BADARG(6);
+  if (V <= 0) return TNT_BADARG(7);
+  if (ld < V) return TNT_BADARG(8);
+  if (!logits) return TNT_BADARG(0);
+  hipStream_t s = tnt_stream(stream);
+  const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
+                  (!dlogits || tnt_aligned16(dlogits));
+  const int nv4 = (V + 1023) / 1024;
+#define TNT_SMXL(N)                                                                                             \
+  hipLaunchKernelGGL((softmax_cce_reg_kernel<N, true>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, \
+                     correct_row, dlogits, rows, V, ld, gscale, 0, 0, live, row_weight)
+  if (al && nv4 == 1) TNT_SMXL(1);
+  else if (al && nv4 == 2) TNT_SMXL(2);
+  else if (al && nv4 <= 4) TNT_SMXL(4);
+  else if (al && nv4 <= 5) TNT_SMXL(5);
+  else if (al && nv4 <= 8) TNT_SMXL(8);
+  else
+    hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
+                       dlogits, rows, V, ld, gscale, 0, 0, live, row_weight);
+#undef TNT_SMXL
   TNT_LAUNCH_CHECK();
   return 0;
 }

@@ -829,19 +829,27 @@ class ModelBase:
             plans[key] = force or self.be.gemm3_plan(M, N, K, transA, transB, batch, allow_split=not colsum)
         return plans[key]
 
-    def gemm3(self, A, B, C, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=None, colsum=None, A2=None, C2=None):
+    def gemm3(self, A, B, C, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=None, colsum=None, A2=None, C2=None,
+              live=None, live_mode=0, plan_M=None):
         """One product (or two sharing B) on the hand-written FP32-MFMA family of csrc/gemm3.hip, tile and K split from the
-        library's cost model (tnt_gemm3_plan; cached per shape).  True = call issued."""
+        library's cost model (tnt_gemm3_plan; cached per shape).  True = call issued.
+        ``live`` / ``live_mode`` (ops.LIVE_ROWS_M / LIVE_ROWS_K): a device word that bounds the rows (tnt_gemm3_f32);
+        ``plan_M``: the extent to EXPECT in that word -- the tile is planned for it (unsplit: the grid still covers M, and
+        the splits of a tile would have to be resident together), the result never depends on it."""
         be = self.be
         if not getattr(self, "use_gemm3", True) or not hasattr(be, "gemm3") or (transA and transB):
             return False
         if lda % 4 or ldb % 4 or ldc % 4:
             return False
         batch = 2 if A2 is not None else 1
-        tile, sk = self._g3_plan(M, N, K, transA, transB, batch, colsum is not None)
+        if plan_M is not None and live is not None and plan_M < M:
+            tile, sk = self._g3_plan(plan_M, N, K, transA, transB, batch, True)
+        else:
+            tile, sk = self._g3_plan(M, N, K, transA, transB, batch, colsum is not None)
         work, sync = self._g3_space(be.gemm3_work_floats(M, N, tile, sk, batch)) if sk > 1 else (None, None)
+        kw = dict(live=live, live_mode=live_mode) if live is not None else {}
         be.gemm3(A, B, C, M, N, K, lda, ldb, ldc, transA=transA, transB=transB, bias=bias, colsum=colsum, A2=A2, C2=C2,
-                 tile=tile, splitk=sk, work=work, sync=sync)
+                 tile=tile, splitk=sk, work=work, sync=sync, **kw)
         return True
 
     def gemm3_pair(self, p, q):
@@ -877,10 +885,11 @@ class ModelBase:
             return True
         out = []
         for d, tile, sk, off, wf in descs:
+            lv = dict(live=d["live"], live_mode=d["live_mode"]) if d.get("live") is not None else {}
             out.append(be.gemm3_desc(d["A"], d["B"], d["C"], d["M"], d["N"], d["K"], d["lda"], d["ldb"], d["ldc"],
                                      transA=d.get("transA", False), transB=d.get("transB", False), bias=d.get("bias"),
                                      colsum=d.get("colsum"), A2=d.get("A2"), C2=d.get("C2"), tile=tile, splitk=sk,
-                                     work=work[off:off + wf] if wf else None, sync=sync if wf else None))
+                                     work=work[off:off + wf] if wf else None, sync=sync if wf else None, **lv))
         keep[ck] = (out[0], out[1])
         be.gemm3_pair(out[0], out[1])
         return True
@@ -1098,7 +1107,12 @@ class ModelBase:
         batch staging (attention model: the stored attention-dropout masks of all T steps), or None"""
         return None
 
-    def _stage_batch(self, inputs, target, n_cols, masks=False):
+    def _head_map_bufs(self, B, T):
+        """(pos, row_weight, tgt_compact, live, loss_row, corr_row) when this model wants the vocabulary head's row map built
+        with the staging of a training batch (nic.NIC: compact_head), else None"""
+        return None
+
+    def _stage_batch(self, inputs, target, n_cols, masks=False, head_map=False):
         """(inputs, target) -> static buffers.  A batch that already sits on the model's device in the staged
         dtypes (float32 -- or float16 "on-wire" -- betas, float32 states, int32 ids, contiguous) goes through ONE launch
         (tnt_stage_batch_f32 / _h16);
@@ -1112,6 +1126,7 @@ class ModelBase:
         ok = ok and cap.dtype == torch.int32
         ok = ok and x.dim() == 2 and cap.dim() == 2 and x.shape == (cap.shape[0], n_cols)
         ok = ok and (target is None or (target.dtype == torch.int32 and target.shape == cap.shape))
+        self._head_map_fresh = False
         if not ok:
             B, T = self._stage_inputs(inputs)
             if target is not None:
@@ -1128,7 +1143,15 @@ class ModelBase:
         mk = self._stage_mask_job() if masks else None
         if mk is not None:                   # the step's dropout masks ride in the staging launch
             kw["masks"] = mk
-        if xT is not None:
+        hm = self._head_map_bufs(B, T) if (head_map and target is not None and mk is None and xT is None
+                                           and x.dtype == torch.float32) else None
+        if hm is not None:
+            # the head's row map (which caption positions repeat an earlier row) rides in the staging launch: the step that
+            # follows runs its vocabulary head over the distinct rows only
+            self.be.stage_batch_map(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,
+                                    self.ldx, self.U, *hm)
+            self._head_map_fresh = True
+        elif xT is not None:
             self.be.stage_batch(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,
                                 self.ldx, self.U, xT, xT.shape[1], **kw)
         else:

@@ -21,7 +21,7 @@ from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
                          BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
                          SelfCritical, check_sampling, check_beam, length_normalise)
-from .ops import ACT_LEAKY
+from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
 
@@ -214,6 +214,13 @@ class NIC(ModelBase):
         self._init_seq_lstm(B, U)        # persistent sequence kernel: opt-in per shape and per device
         self.logits = f(T * B, ldV)
         self.loss_row, self.corr_row = f(T * B), f(T * B)
+        # row map of the vocabulary head (compact_head; tnt_stage_batch_map_f32): compacted row of every (t, b) or -1, the
+        # rows' multiplicities and targets, and the number of rows
+        self.head_pos = torch.full((T * B,), -1, dtype=torch.int32, device=self.device)
+        self.head_w = f(T * B)
+        self.head_tgt = torch.zeros(T * B, dtype=torch.int32, device=self.device)
+        self.head_live = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._head_live_est = None
         self.met = f(8)
         self.dOut = f(T * B, U)
         self.dZ = f(R1, U, 4)
@@ -245,6 +252,25 @@ class NIC(ModelBase):
         self.Hs[0].copy_(self._to_dev(a0, torch.float32))
         self.Cs[0].copy_(self._to_dev(c0, torch.float32))
         return B, T
+
+    def _head_map_bufs(self, B, T):
+        """The vocabulary head over the DISTINCT rows only (``compact_head``, default on).  The text LSTM carries its output
+        through the padded tail of a caption (fed id 0) and the targets there are all 0, so those positions repeat one row
+        of Out, logits, loss and dlogits; the loss is not masked, so they count -- once, weighted by their multiplicity.
+        Taken by train_step where the step is the persistent chains + the gemm3 products of one process and nothing else
+        writes or reads the head's buffers by position: no scheduled sampling, self-critical step, AGC, label smoothing,
+        data parallel.  Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the
+        position-ordered buffers."""
+        be = self.be
+        ok = (getattr(self, "compact_head", True) and self.__dict__.get("_seq_lstm") and self.__dict__.get("seq_xch") is not None
+              and hasattr(be, "stage_batch_map") and hasattr(be, "softmax_cce_live") and hasattr(be, "gemm3")
+              and getattr(self, "use_gemm3", True) and getattr(self, "g3_riders", True)
+              and self.grad_sync is None and int(self.__dict__.get("dp_world", 1) or 1) == 1
+              and self.scheduled_sampling is None and self.self_critical is None and not self.__dict__.get("agc")
+              and not self.label_smoothing and self.U % 4 == 0)
+        if not ok:
+            return None
+        return (self.head_pos, self.head_w, self.head_tgt, self.head_live, self.loss_row, self.corr_row)
 
     def _fused_tail(self, B):
         """one-launch encoder tail (tnt_enc_tail_*): BatchNorm encoder, batch <= 256 rows, E % 4 == 0"""
@@ -334,11 +360,12 @@ class NIC(ModelBase):
         else:
             self.gemm_sk(xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U)
         Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
+        compact = bool(training and self.__dict__.get("_compact"))       # _head_map_bufs: Out and logits hold the distinct rows
         if self._seq_lstm:
             # both LSTM calls (NIC.py:138,140) as ONE persistent launch: the T+1 dependent steps pay an XCD-local barrier
             # each instead of a kernel launch, the recurrent weights stay in VGPRs (tnt_lstm_seq_fwd_f32)
             be.lstm_seq_fwd(self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 1, self.Out, self.gates, T + 1, B, U,
-                            self.seq_sync, self._guard_out())
+                            self.seq_sync, self._guard_out(), **(dict(out_pos=self.head_pos) if compact else {}))
         else:
             # lstm call 1: the feature, one unmasked step (NIC.py:138)
             be.lstm_step_fwd(self.XZ[:B], self.Hs[0], self.Cs[0], Ur, None, None, 0, None, 0, 0, None, self.Hs[1],
@@ -348,8 +375,22 @@ class NIC(ModelBase):
                 be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, self.cap, T,
                                  t - 1, self.Out[t - 2] if t > 1 else None, self.Hs[t + 1], self.Cs[t + 1],
                                  self.Out[t - 1], self.gates[t], B, U, xz_bias=bl)
+        if compact:
+            # rows [0, live) only; the tile is planned for the live count seen at the warm-up step (any count is correct)
+            self.gemm3(self.Out, a.p("time_distributed_softmax/kernel"), self.logits, T * B, V, U, U, ldV, ldV,
+                       bias=a.p("time_distributed_softmax/bias"), live=self.head_live, live_mode=LIVE_ROWS_M,
+                       plan_M=self._head_plan_rows(T * B))
+            return
         self.gemm_sk(self.Out, a.p("time_distributed_softmax/kernel"), self.logits, T * B, V, U, U, ldV, ldV,
                 bias=a.p("time_distributed_softmax/bias"))                         # NIC.py:143
+
+    def _head_plan_rows(self, n):
+        """the row count the head forward's tile is planned for: the live count of the warm-up batch plus 3 % (batches of the
+        same data differ a little), or n when none was read"""
+        est = self._head_live_est
+        if not getattr(self, "compact_head_replan", True) or est is None or est <= 0:
+            return n
+        return min(n, est + max(est // 32, 1))
 
     def _forward_ss(self, B, T, xin, drop_l):
         """The scheduled-sampling forward behind the teacher-forced Embedding gather: XZ of the feature and start-token
@@ -385,7 +426,11 @@ class NIC(ModelBase):
         be = self.be
         n = T * B
         eps = self.label_smoothing
-        if eps > 0:         # keras smooths the evaluation loss too
+        if want_grad and self.__dict__.get("_compact"):
+            # the distinct rows, each weighted by its multiplicity; rows past the live count hold zeros (staging launch)
+            be.softmax_cce_live(self.logits, self.head_tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
+                                self.ldV, 1.0 / (n * self.dp_world), self.head_live, self.head_w)
+        elif eps > 0:         # keras smooths the evaluation loss too
             be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
                                   self.logits if want_grad else None, n, self.V, self.ldV,
                                   1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
@@ -413,6 +458,19 @@ class NIC(ModelBase):
         dw = dict(A=self.Out, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=U, N=V, K=T * B, lda=U, ldb=ldV, ldc=ldV,
                   transA=True, colsum=a.g("time_distributed_softmax/bias"))
         dx = dict(A=dlog, B=Wo, C=self.dOut, M=T * B, N=U, K=V, lda=ldV, ldb=ldV, ldc=U, transB=True)
+        if self.__dict__.get("_compact"):
+            # dlogits and Out hold `live` rows: dW and db sum over those (each already carries its multiplicity), dOut is
+            # formed for those; one device word bounds both products
+            dw.update(live=self.head_live, live_mode=LIVE_ROWS_K)
+            dx.update(live=self.head_live, live_mode=LIVE_ROWS_M)
+            if not self.gemm3_pair(dw, dx):
+                self.gemm3(dw["A"], dw["B"], dw["C"], U, V, T * B, U, ldV, ldV, transA=True, colsum=dw["colsum"],
+                           live=self.head_live, live_mode=LIVE_ROWS_K)
+                self.gemm3(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True, live=self.head_live,
+                           live_mode=LIVE_ROWS_M)
+            if join:
+                self.join()
+            return
         if getattr(self, "g3_riders", True) and self.gemm3_pair(dw, dx):
             # kernel gradient (with the bias gradient as a rider on the dlogits tiles it streams anyway) and input gradient,
             # the two independent readers of dlogits, in ONE launch
@@ -459,7 +517,7 @@ class NIC(ModelBase):
             # the T+1 dependent backward steps as ONE persistent launch (tnt_lstm_seq_bwd_f32): weights stationary, the
             # recurrent product pushed as partial tiles through the XCD's L2
             be.lstm_seq_bwd(Ur, dOut, self.cap, T, 1, self.gates, self.Cs, self.dZ, self.seq_xch, T + 1, B, U, self.seq_sync,
-                            self._guard_out())
+                            self._guard_out(), **(dict(dout_pos=self.head_pos) if self.__dict__.get("_compact") else {}))
         else:
             for t in range(T, 0, -1):
                 first = t == T
@@ -663,7 +721,7 @@ class NIC(ModelBase):
             raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
         if self.self_critical is not None:
             return self.train_step_scst(data)
-        B, T = self._stage_batch(data[0], data[1], self.N)
+        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None)
         if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
             raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
                              f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
@@ -677,7 +735,16 @@ class NIC(ModelBase):
             # models, repeated, spread 0.0005).  ``plan_step = False`` restores the graph.  A plan re-issues backend launches
             # only, so it is used where the step is nothing else: the sparse Embedding backward (the dense form hands its ids on
             # with a tensor copy, which a graph captures and a plan would drop).
-            ring = self._run_step(self._step_runner(), ("train", B, T), lambda: self._train_and_update_graph(B, T))
+            compact = bool(self.__dict__.get("_head_map_fresh"))      # the staging launch built the head's row map
+            key = ("train", B, T, "compact") if compact else ("train", B, T)
+            if compact and self._head_live_est is None and self._graphs.get(key) is None:
+                # the eager warm-up step synchronises anyway: read the live count once, for the head forward's tile only
+                self._head_live_est = int(self.head_live.item())
+            self._compact = compact
+            try:
+                ring = self._run_step(self._step_runner(), key, lambda: self._train_and_update_graph(B, T))
+            finally:
+                self._compact = False
             self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)

@@ -26,7 +26,7 @@ import ctypes as _ct
 class _G3Desc(_ct.Structure):
     _fields_ = ([(n, _ct.c_void_p) for n in ("A", "B", "C", "bias", "colsum", "A2", "C2")]
                 + [(n, _ct.c_int32) for n in ("M", "N", "K", "lda", "ldb", "ldc", "transA", "transB", "tile", "splitk")]
-                + [(n, _ct.c_void_p) for n in ("work", "sync")])
+                + [(n, _ct.c_void_p) for n in ("work", "sync", "live")] + [("live_mode", _ct.c_int32)])
 
 
 class _FinDesc(_ct.Structure):
@@ -40,6 +40,9 @@ class _FinDesc(_ct.Structure):
                 ("x2", _ct.c_void_p), ("out2", _ct.c_void_p), ("n2", _ct.c_int32), ("scale2", _ct.c_float),
                 ("adam_t", _ct.c_void_p), ("drop_step", _ct.c_void_p), ("lr", _ct.c_void_p), ("lr_t", _ct.c_void_p),
                 ("beta1", _ct.c_float), ("beta2", _ct.c_float), ("guard", _ct.c_void_p), ("arrive", _ct.c_void_p)]
+
+
+LIVE_ROWS_M, LIVE_ROWS_K = 1, 2      # live_mode of gemm3 / gemm3_desc: the device word bounds the rows of A and C / of the contraction
 
 
 class HipBackend:
@@ -88,12 +91,13 @@ class HipBackend:
                    M, N, K, lda, ldb, ldc, int(transA), int(transB), cfg, self._s())
 
     def gemm3(self, A, B, C, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=None, colsum=None, A2=None, C2=None,
-              tile=1, splitk=1, work=None, sync=None):
+              tile=1, splitk=1, work=None, sync=None, live=None, live_mode=0):
         """the round-3 FP32-MFMA family (LDS-DMA staged, b128 fragments): C = op(A) op(B) (+ bias); riders: column sums of B,
         a second product sharing B; splitk > 1 reduces the K splits inside the launch (work / sync: gemm3_work_floats /
-        gemm3_sync_words)"""
+        gemm3_sync_words); live / live_mode: a device-side extent (LIVE_ROWS_M / LIVE_ROWS_K, include/tnt_hip.h)"""
         self._call(self.lib.tnt_gemm3_f32, "tnt_gemm3_f32", _p(A), _p(B), _p(C), _p(bias), _p(colsum), _p(A2), _p(C2),
-                   M, N, K, lda, ldb, ldc, int(transA), int(transB), tile, splitk, _p(work), _p(sync), self._s())
+                   M, N, K, lda, ldb, ldc, int(transA), int(transB), tile, splitk, _p(work), _p(sync), _p(live), int(live_mode),
+                   self._s())
 
     def gemm3_plan(self, M, N, K, transA=False, transB=False, batch=1, allow_split=True):
         """(tile, splitk) of the library's cost model for this shape"""
@@ -120,11 +124,11 @@ class HipBackend:
 
     @staticmethod
     def gemm3_desc(A, B, C, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=None, colsum=None, A2=None, C2=None, tile=1,
-                   splitk=1, work=None, sync=None):
+                   splitk=1, work=None, sync=None, live=None, live_mode=0):
         """tnt_gemm3_desc (include/tnt_hip.h); the returned object keeps the tensors alive"""
         d = _G3Desc(_p(A), _p(B), _p(C), _p(bias), _p(colsum), _p(A2), _p(C2), M, N, K, lda, ldb, ldc, int(transA), int(transB),
-                    tile, splitk, _p(work), _p(sync))
-        d._keep = (A, B, C, bias, colsum, A2, C2, work, sync)
+                    tile, splitk, _p(work), _p(sync), _p(live), int(live_mode))
+        d._keep = (A, B, C, bias, colsum, A2, C2, work, sync, live)
         return d
 
     def gemm3_work_arm(self, work):
@@ -259,9 +263,11 @@ class HipBackend:
         """1 when the persistent sequence kernel can run here (U == 512, 256 CUs, 32 workgroups per XCD); probes once."""
         return bool(self.lib.tnt_lstm_seq_supported(int(B), int(U)))
 
-    def lstm_seq_fwd(self, xz, hs, cs, Ur, xz_bias, mask_ids, mask_T, mask_s0, out, gates, S, B, U, sync, guard_out=None):
+    def lstm_seq_fwd(self, xz, hs, cs, Ur, xz_bias, mask_ids, mask_T, mask_s0, out, gates, S, B, U, sync, guard_out=None,
+                     out_pos=None):
+        """out_pos: the row map of stage_batch_map -- `out` is then written by compacted row"""
         self._call(self.lib.tnt_lstm_seq_fwd_f32, "tnt_lstm_seq_fwd_f32", _p(xz), _p(hs), _p(cs), _p(Ur), _p(xz_bias),
-                   _p(mask_ids), mask_T, mask_s0, _p(out), _p(gates), S, B, U, _p(sync), _p(guard_out), self._s())
+                   _p(mask_ids), mask_T, mask_s0, _p(out), _p(gates), S, B, U, _p(sync), _p(guard_out), _p(out_pos), self._s())
 
     def ln_lstm_cell_fwd(self, zk, zr, bias, c_prev, gamma_s, beta_s, gates, chat, istd, c, h, B, U, eps):
         self._call(self.lib.tnt_ln_lstm_cell_fwd_f32, "tnt_ln_lstm_cell_fwd_f32", _p(zk), _p(zr), _p(bias), _p(c_prev), _p(gamma_s),
@@ -274,10 +280,12 @@ class HipBackend:
     def lstm_seq_bwd_work_floats(self, B, U):
         return int(self.lib.tnt_lstm_seq_bwd_work_floats(int(B), int(U)))
 
-    def lstm_seq_bwd(self, Ur, dout_seq, mask_ids, mask_T, mask_s0, gates, cs, dz, work, S, B, U, sync, guard_out=None):
-        """BPTT over the S steps of one sequence in ONE persistent launch (tnt_lstm_seq_bwd_f32)."""
+    def lstm_seq_bwd(self, Ur, dout_seq, mask_ids, mask_T, mask_s0, gates, cs, dz, work, S, B, U, sync, guard_out=None,
+                     dout_pos=None):
+        """BPTT over the S steps of one sequence in ONE persistent launch (tnt_lstm_seq_bwd_f32); dout_pos: the row map of
+        stage_batch_map -- dout_seq is then read by compacted row."""
         self._call(self.lib.tnt_lstm_seq_bwd_f32, "tnt_lstm_seq_bwd_f32", _p(Ur), _p(dout_seq), _p(mask_ids), mask_T, mask_s0,
-                   _p(gates), _p(cs), _p(dz), _p(work), work.numel(), S, B, U, _p(sync), _p(guard_out), self._s())
+                   _p(gates), _p(cs), _p(dz), _p(work), work.numel(), S, B, U, _p(sync), _p(guard_out), _p(dout_pos), self._s())
 
     def lstm_step_bwd(self, dz_next, Ur, da_pass_in, dh_ext, dc_in, dout_in, dout_t, mask_ids, mask_T, mask_t,
                       gates, c, c_prev, dz, da_pass_out, dc_out, dout_out, B, U, Wc=None, D=0, dctx_part=None):
@@ -298,6 +306,12 @@ class HipBackend:
         self._call(self.lib.tnt_softmax_cce_f32, "tnt_softmax_cce_f32", _p(logits), _p(target), _p(probs), _p(loss_row), _p(correct_row),
                                                 _p(dlogits), rows, V, ld, gscale, int(from_logits), int(mask_zero),
                                                 self._s())
+
+    def softmax_cce_live(self, logits, target, probs, loss_row, correct_row, dlogits, rows, V, ld, gscale, live, row_weight):
+        """softmax_cce over the distinct rows of a row map (stage_batch_map): rows >= live[0] untouched, row r weighted by
+        row_weight[r] (tnt_softmax_cce_live_f32)"""
+        self._call(self.lib.tnt_softmax_cce_live_f32, "tnt_softmax_cce_live_f32", _p(logits), _p(target), _p(probs), _p(loss_row),
+                   _p(correct_row), _p(dlogits), rows, V, ld, gscale, _p(live), _p(row_weight), self._s())
 
     def softmax_cce_smooth(self, logits, target, probs, loss_row, correct_row, dlogits, rows, V, ld, gscale, label_smoothing):
         """the head with keras label smoothing in the same single launch (tnt_softmax_cce_smooth_f32; definition in
@@ -509,6 +523,14 @@ class HipBackend:
                    (self.lib.tnt_stage_batch_f32, "tnt_stage_batch_f32")
         self._call(fn, name, _p(x), _p(x_dst), _p(cap), _p(cap_dst), _p(tgt), _p(tgt_tmajor), _p(a0),
                                                 _p(h0), _p(c0), _p(c0_dst), B, T, N, ldx, U, _p(xT_dst), ldt, self._s())
+
+    def stage_batch_map(self, x, x_dst, cap, cap_dst, tgt, tgt_tmajor, a0, h0, c0, c0_dst, B, T, N, ldx, U, pos, row_weight,
+                        tgt_compact, live, loss_row=None, corr_row=None, xT_dst=None, ldt=0):
+        """stage_batch (float32 betas) with the vocabulary head's row map built in the same launch (tnt_stage_batch_map_f32;
+        definition in include/tnt_hip.h)"""
+        self._call(self.lib.tnt_stage_batch_map_f32, "tnt_stage_batch_map_f32", _p(x), _p(x_dst), _p(cap), _p(cap_dst), _p(tgt),
+                   _p(tgt_tmajor), _p(a0), _p(h0), _p(c0), _p(c0_dst), B, T, N, ldx, U, _p(xT_dst), ldt, _p(pos), _p(row_weight),
+                   _p(tgt_compact), _p(live), _p(loss_row), _p(corr_row), self._s())
 
     def scst_cce(self, logits, ld, V, fed, T, last, adv, end_id, loss_row, lp_row, dlogits, R, gscale):
         """the SCST policy-gradient loss of R sampled captions and its logits gradient (tnt_scst_cce_f32; definition in
