@@ -641,6 +641,32 @@ int32_t tnt_beam_step_f32(const float* probs, int32_t ld, const float* score_in,
                           int32_t V, int32_t k, int32_t end_id, float* score_out, int32_t* parent, int32_t* token,
                           int32_t* fin_out, const float* h_in, const float* c_in, int32_t ldh, int32_t U,
                           float* h_out, float* c_out, void* stream);
+/* One step of diverse (group) beam search with Hamming diversity (Vijayakumar et al. 2016/2018; num_beam_groups /
+ * diversity_penalty in the common toolkits), in one launch (restated by tests/diverse_beam_oracle.py).  Library-defined:
+ *  - Layout.  The k beams of a sample are `groups` = Gd groups of k' = k / Gd: group g of sample b owns rows
+ *    b*k + g*k' + j, j < k', of every [B*k] buffer.
+ *  - Order.  Within the step the groups of a sample choose in ascending g.
+ *  - Candidates of group g: (beam j of the group, token v).  Its score is the float32 s = score_in[j] +
+ *    logf(fmaxf(p, 1e-30f)), exactly as in tnt_beam_step_f32; its selection key is the float32 s - lambda * (float)n_v
+ *    (a rounded product, then a rounded difference), where n_v counts the new beams already chosen at this step by the
+ *    groups < g of the same sample whose token is v and whose parent was live (fin_in == 0).
+ *  - A finished beam (fin_in != 0) has one candidate, token 0 at its own score, key = score; it adds to no n_v.
+ *  - Selection.  The k' best keys of the group become its new beams, best first, at the group's rows; ties go to the
+ *    lower j*V + v.
+ *  - Outputs.  score_out is the unpenalised s: carried scores stay sums of log-probabilities and the penalty steers the
+ *    selection only.  parent is the global row of the extended beam; token and fin_out as in tnt_beam_step_f32.
+ *  - Reorder: h_out[r][0..U) = h_in[parent[r]][0..U), likewise c; U == 0 skips it; aliasing rules of tnt_beam_step_f32.
+ * Consequences: with lambda == 0 the launch is tnt_beam_step_f32(B*Gd, k') on the same buffers, bit for bit (the row
+ * layouts coincide); with Gd == 1 it is tnt_beam_step_f32(B, k), bit for bit, for any lambda; for any lambda group 0 is
+ * a plain beam search of width k'.
+ * k <= 16, any V.  One workgroup of 16 waves per sample: every row's (g+1)*k' best values are prepared once for all groups
+ * (the penalty only lowers keys, so a group's k' best keys are among them), then the groups rank their prepared
+ * candidates in LDS in turn.  Deterministic, no scratch memory, no host sync.
+ * TNT_BADARG for everything tnt_beam_step_f32 refuses, groups < 1, k % groups != 0, lambda < 0 or not finite. */
+int32_t tnt_beam_step_diverse_f32(const float* probs, int32_t ld, const float* score_in, const int32_t* fin_in,
+                                  int32_t B, int32_t V, int32_t k, int32_t end_id, float* score_out, int32_t* parent,
+                                  int32_t* token, int32_t* fin_out, const float* h_in, const float* c_in, int32_t ldh,
+                                  int32_t U, float* h_out, float* c_out, int32_t groups, float lambda, void* stream);
 /* Constrained decoding: the repetition penalty and the bans of one decode step, applied to the step's logits in place,
  * in front of the softmax launch (restated by tests/constrain_oracle.py).  Library-defined:
  *  - Step and history.  logits [rows][ld], V valid columns, are the logits of step i (0-based: the step chooses the token

@@ -73,6 +73,7 @@ SIGNATURES = {
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],
+    "tnt_beam_step_diverse_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, I32, F32, P],
     "tnt_decode_constrain_f32": [P, I32, I32, I32, I32, P, P, I32, P, P, P, F32, I32, I32, I32, P, I32, P],
     "tnt_consensus_mix_f32": [P, I32, I32, I32, I32, P, I32, P, I32, P, P],
     "tnt_consensus_spread_i32": [P, P, P, I32, I32, P, P, P, P],

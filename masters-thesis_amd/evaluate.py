@@ -6,6 +6,8 @@
   thesis' analysis scripts keep working.
 * ``beam_captions``                   -- the best beam-search caption of either model (``beam_search``), from the
   tokenizer's <start> / <end> indices.
+* ``distinct_n``                      -- distinct n-grams / n-grams over a list of captions: the variety of an n-best list
+  (diverse beam search, ``beam_search(diversity=model_base.BeamDiversity(...))``).
 * ``ids_to_captions``                 -- tokenizer.sequences_to_texts with the <start>/<end>/<pad> handling of
   ThinkAndTell/evaluate.py:178-201.
 * ``sentence_bleu`` / ``bleu_scores`` -- ThinkAndTell/img_evaluate.py:212-250 calls
@@ -105,19 +107,31 @@ def ids_to_captions(ids, tokenizer, end_token="<end>", drop=("<start>", "<pad>")
 
 
 def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, length_penalty=0.0, end_token="<end>",
-                  constraints=None, consensus=None):
+                  constraints=None, consensus=None, diversity=None):
     """Beam-search captions of either model (nic.NIC or lc_nic.NIC ``beam_search``): every caption starts at the
     tokenizer's "<start>" index and a beam ends at ``end_token``'s index.  Returns (ids (B, max_len) int64 of each
     sample's best beam, captions: token lists cut at ``end_token`` as ids_to_captions cuts).  ``constraints``
     (model_base.DecodeConstraints) goes to beam_search; its min_length counts against ``end_token``'s index.
     ``consensus`` (model_base.Consensus) goes to beam_search too: ``features`` then holds members * M scans, member-major,
-    and one caption per image comes back."""
+    and one caption per image comes back.  ``diversity`` (model_base.BeamDiversity) goes to beam_search as well; the
+    caption returned is group 0's best, the plain search of width beam_width / groups (call beam_search for all of them)."""
     end_id = int(tokenizer.word_index[end_token])
     start = np.full(_n_start(features, consensus), int(tokenizer.word_index["<start>"]), np.int64)
     seqs, _ = model.beam_search(features, a0, c0, start, max_len, beam_width=beam_width, end_id=end_id,
-                                length_penalty=length_penalty, **_con_kw(constraints, consensus))
+                                length_penalty=length_penalty, **_con_kw(constraints, consensus),
+                                **({} if diversity is None else {"diversity": diversity}))
     ids = np.ascontiguousarray(seqs[:, 0, :]).astype(np.int64)
     return ids, ids_to_captions(ids, tokenizer, end_token=end_token)
+
+
+def distinct_n(captions, n):
+    """distinct-n (Li et al. 2016) of a list of token sequences (lists of words or ids): the number of distinct n-grams
+    over all the sequences divided by the total number of n-grams; 0.0 when no sequence holds an n-gram.  1.0: no n-gram
+    occurs twice; near 1 / len(captions): the sequences are copies of each other."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be an int >= 1, got {n!r}")
+    grams = [tuple(cap[i:i + n]) for cap in (list(c) for c in captions) for i in range(len(cap) - n + 1)]
+    return len(set(grams)) / len(grams) if grams else 0.0
 
 
 def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>", top_k=0,

@@ -1500,7 +1500,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
-                    length_penalty=0.0, constraints=None, consensus=None):
+                    length_penalty=0.0, constraints=None, consensus=None, diversity=None):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,
         lc_NIC.py:640-692, recurse without returning; ThinkAndTell/evaluate.py:203-228 stops after one expansion), so
         the definition is this library's: standard log-probability beam search of width ``beam_width`` with the greedy
@@ -1519,10 +1519,18 @@ class NIC(ModelBase):
         (with n_subjects = S: of its S subject slices).  The inputs hold G * M rows, member-major, start_seq M entries; the
         decoder rows are [G][M][k].  Per token one tnt_consensus_mix_f32 launch takes the softmax's place, the expansion
         runs on the M * k mixed rows, one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the
-        member rows, and the state is gathered by the spread parents.  Sequences and scores are per image."""
+        member rows, and the state is gathered by the spread parents.  Sequences and scores are per image.
+        ``diversity`` (model_base.BeamDiversity(groups=Gd, penalty=lambda)): diverse beam search.  The k beams of a sample
+        search as Gd groups of k' = k / Gd; one tnt_beam_step_diverse_f32 launch (U = 0: the state gathers stay) takes
+        the expansion's place, with consensus too, and every group starts from its own copy of the start state.  The
+        results are group-major: group g's k' results sit best first at slots g*k' .. g*k' + k' - 1 (the group index of
+        the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
+        reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
+        None or groups = 1: the search as it is without the keyword."""
         length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
+        div = self._diversity(diversity, k)
         start = np.asarray(start_seq).reshape(-1)
         cons = self._consensus(consensus, img_input, start.shape[0], k)
         M = start.shape[0]                            # captions: the expansion runs on M * k rows
@@ -1539,7 +1547,10 @@ class NIC(ModelBase):
         dev, i32 = self.device, torch.int32
         words0 = torch.as_tensor(rep(start).astype(np.int32)).to(dev).view(Bk, 1)
         score = [torch.zeros(Mk, device=dev), torch.zeros(Mk, device=dev)]
-        score[0].view(M, k)[:, 1:] = -1e30            # step 0: the k beams of a sample are copies, only beam 0 counts
+        if div is None:
+            score[0].view(M, k)[:, 1:] = -1e30        # step 0: the k beams of a sample are copies, only beam 0 counts
+        else:                                         # ... of every group: only its first beam counts
+            score[0].view(M, div[0], k // div[0])[:, :, 1:] = -1e30
         fin = [torch.zeros(Mk, dtype=i32, device=dev), torch.zeros(Mk, dtype=i32, device=dev)]
         parents = torch.zeros(max_len, Mk, dtype=i32, device=dev)
         tokens = torch.zeros(max_len, Mk, dtype=i32, device=dev)
@@ -1551,6 +1562,12 @@ class NIC(ModelBase):
             mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
             cb["fin"].zero_()
         hg, cg = self._f(Bk, U), self._f(Bk, U)
+        # the expansion launch: tnt_beam_topk_f32, or with diversity tnt_beam_step_diverse_f32 without its reorder (U = 0)
+        if div is None:
+            expand = be.beam_topk
+        else:
+            expand = lambda p, s_in, f_in, n, V_, ld, k_, eid, s_out, par, tok, f_out: be.beam_step_diverse(
+                p, ld, s_in, f_in, n, V_, k_, eid, s_out, par, tok, f_out, None, None, 0, 0, None, None, *div)
         self._encode(Bk, False)
         words = words0
         for i in range(max_len):
@@ -1568,10 +1585,10 @@ class NIC(ModelBase):
                 con.step(i, probs, ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
             if cons is None:
                 be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
-                be.beam_topk(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
+                expand(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
             else:   # the mixture in the softmax's place, the expansion on the M*k mixed rows, its choice spread to the members
                 cons.mix(probs, mix)
-                be.beam_topk(mix, score[cur], fin[cur], M, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
+                expand(mix, score[cur], fin[cur], M, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
                 cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
             # the surviving beams continue from their parents' LSTM state (row gather by parent)
             be.embedding_fwd(self.Hs[i + 1], par_d[i].view(Bk, 1), hg, Bk, 1, U, U, Bk)
@@ -1589,5 +1606,5 @@ class NIC(ModelBase):
                     seqs[b, r, i] = tok[i, row]
                     row = par[i, row]
         if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty)
+            return length_normalise(seqs, final, end_id, length_penalty, div[0] if div is not None else 1)
         return seqs, final

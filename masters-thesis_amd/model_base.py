@@ -414,13 +414,55 @@ def check_beam(beam_width, max_len, end_id, length_penalty, V):
     return int(beam_width), int(max_len), int(end_id), check_length_penalty(length_penalty)
 
 
-def length_normalise(seqs, scores, end_id, length_penalty):
+class BeamDiversity:
+    """Diverse (group) beam search with Hamming diversity (Vijayakumar et al. 2016/2018), for the ``diversity=`` keyword
+    of beam_search of nic.NIC and lc_nic.NIC.  The definition is tnt_beam_step_diverse_f32's (include/tnt_hip.h):
+      groups   Gd >= 1; it must divide beam_width.  The k beams of a sample search as Gd groups of k' = k / Gd beams; at
+               every token the groups choose one after the other
+      penalty  lambda, finite and >= 0: a candidate's selection key is its score minus lambda times the number of beams the
+               earlier groups of the sample chose at this token with the same word.  The carried scores stay sums of
+               log-probabilities: the penalty steers the selection only
+    groups = 1 is plain beam search, whatever the penalty; penalty = 0 gives Gd equal groups.  Bad values raise ValueError
+    here, before any launch; that groups divides the beam width is checked by the search."""
+
+    def __init__(self, groups, penalty=0.5):
+        if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or groups < 1:
+            raise ValueError(f"groups must be an int >= 1, got {groups!r}")
+        lam = penalty
+        if (isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not np.isfinite(lam)
+                or lam < 0 or float(lam) > float(np.finfo(np.float32).max)):
+            raise ValueError(f"penalty must be a finite number >= 0, got {lam!r}")
+        self.groups, self.penalty = int(groups), float(np.float32(lam))
+
+    def __repr__(self):
+        return f"BeamDiversity(groups={self.groups}, penalty={self.penalty})"
+
+
+def check_diversity(diversity, beam_width):
+    """host validation of beam search's ``diversity=``: None or a BeamDiversity whose groups divide beam_width.  Returns
+    (groups, penalty), or None for plain beam search (None, or one group); ValueError otherwise."""
+    if diversity is None:
+        return None
+    if not isinstance(diversity, BeamDiversity):
+        raise ValueError(f"diversity must be a model_base.BeamDiversity or None, got {diversity!r}")
+    if beam_width % diversity.groups != 0:
+        raise ValueError(f"beam_width {beam_width} is not a multiple of the {diversity.groups} groups of {diversity!r}")
+    return (diversity.groups, diversity.penalty) if diversity.groups > 1 else None
+
+
+def length_normalise(seqs, scores, end_id, length_penalty, groups=1):
     """Length normalisation of beam search's k finished results per sample (seqs (B, k, max_len), scores (B, k), best
     first): the results are reordered by the key  score / ((5 + L) / 6) ** length_penalty, computed in float64, where L
     is the number of tokens up to and including the first end_id (max_len if there is none).  Ties keep the search's
-    rank order.  Returns (seqs, key as float32).  length_penalty = 0: the key is the raw sum, the order unchanged."""
+    rank order.  Returns (seqs, key as float32).  length_penalty = 0: the key is the raw sum, the order unchanged.
+    ``groups`` > 1 (diverse beam search's group-major results): every group of k / groups results is reordered on its
+    own and stays at its slots."""
     seqs = np.asarray(seqs)
     B, k, T = seqs.shape
+    if groups > 1:
+        s, key = length_normalise(seqs.reshape(B * groups, k // groups, T), np.asarray(scores).reshape(B * groups, -1),
+                                  end_id, length_penalty)
+        return s.reshape(B, k, T), key.reshape(B, k)
     hit = seqs == end_id
     L = np.where(hit.any(axis=2), hit.argmax(axis=2) + 1, T)
     key = np.asarray(scores, np.float32).astype(np.float64) / ((5.0 + L) / 6.0) ** float(length_penalty)
@@ -1348,6 +1390,15 @@ class ModelBase:
             raise ValueError(f"consensus of {G} members over {n_rows} input rows decodes {n_rows // G} captions: start_seq "
                              f"must have {n_rows // G} entries, got {n_start}")
         return _ConsensusDecode(self, c, n_start, int(beam_width))
+
+    def _diversity(self, diversity, beam_width):
+        """(groups, penalty) of a diverse beam search (check_diversity), or None when ``diversity`` is None or has one
+        group: then the search issues the launches it issues without the keyword, under the same capture key.  Refusals
+        (before any launch): not a BeamDiversity; groups that do not divide beam_width; a data-parallel model."""
+        div = check_diversity(diversity, int(beam_width))
+        if div is not None and self.grad_sync is not None:
+            raise NotImplementedError("diverse beam search has no data-parallel schedule: decode on one device")
+        return div
 
     def _run_captured(self, key, fn):
         """Run ``fn`` (a fixed launch sequence over static buffers) through a hipGraph:

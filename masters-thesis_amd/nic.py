@@ -1117,7 +1117,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
-                    units=None, tokenizer=None, constraints=None, consensus=None):
+                    units=None, tokenizer=None, constraints=None, consensus=None, diversity=None):
         """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches
         it): log-probability beam search of width ``beam_width`` with greedy_predict's step, whose Keras mask rule it
         keeps (a 0 fed back masks the next LSTM step); at step 0 the k beams of a sample are copies and only beam 0
@@ -1137,11 +1137,19 @@ class NIC(ModelBase):
         tnt_consensus_mix_f32 launch takes the softmax's place, tnt_beam_step_f32 expands the M * k mixed rows (U = 0: no
         fused reorder), one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the member rows,
         and the state is gathered by the spread parents.  Sequences and scores are per image: (M, k, max_len), (M, k).
+        ``diversity`` (model_base.BeamDiversity(groups=Gd, penalty=lambda)): diverse beam search.  The k beams of a sample
+        search as Gd groups of k' = k / Gd; one tnt_beam_step_diverse_f32 launch takes tnt_beam_step_f32's place (with
+        consensus too, on the M * k mixed rows), and every group starts from its own copy of the start state.  The
+        results are group-major: group g's k' results sit best first at slots g*k' .. g*k' + k' - 1 (the group index of
+        the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
+        reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
+        None or groups = 1: the search as it is without the keyword.
         Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
         length-normalised key)."""
         k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
+        div = self._diversity(diversity, k)
         cons = self._consensus(consensus, img_input, start.shape[0], k)
         G = cons.G if cons is not None else 1
         M = start.shape[0]                             # captions: the expansion runs on M * k rows
@@ -1164,8 +1172,15 @@ class NIC(ModelBase):
                 h=f(2, Bk, U), c=f(2, Bk, U), emb=f(Bk, E), xz=f(Bk, U, 4), out=f(Bk, U), gates=f(Bk, U, 4),
                 probs=f(Bk, ldV))
         bb = bufs[key]
+        init = "init"
+        if div is not None:                        # step 0 of every group: its k' beams are copies, only its first counts
+            init = ("init", div[0])
+            if init not in bb:
+                bb[init] = self._f(M, div[0], k // div[0])
+                bb[init][:, :, 1:] = -1e30
+                bb[init] = bb[init].view(Mk)
         bb["start"].copy_((start if cons is None else start.repeat(G)).repeat_interleave(k).view(Bk, 1))
-        bb["score"][0].copy_(bb["init"])
+        bb["score"][0].copy_(bb[init])
         bb["fin"][0].zero_()
         score, fin, parents, tokens = bb["score"], bb["fin"], bb["pt"][0], bb["pt"][1]
         h, c, emb, xz, out, probs = bb["h"], bb["c"], bb["emb"], bb["xz"], bb["out"], bb["probs"]
@@ -1175,6 +1190,8 @@ class NIC(ModelBase):
             cb = cons.bufs(max_len, 1)
             mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
             cb["fin"].zero_()
+        # the expansion launch: tnt_beam_step_f32, or with diversity tnt_beam_step_diverse_f32 on the same arguments
+        expand = be.beam_step if div is None else (lambda *args: be.beam_step_diverse(*args, *div))
 
         def run():
             self._decode_encode(B)
@@ -1197,17 +1214,18 @@ class NIC(ModelBase):
                     # the mixture in the softmax's place; the expansion on the M*k mixed rows without its fused reorder; its
                     # choice spread to the member rows; every member's state (h[1], c[1]) gathered by its own parent rows
                     cons.mix(probs, mix)
-                    be.beam_step(mix, ldV, score[cur], fin[cur], M, V, k, end_id, score[nxt], parents[i], tokens[i],
-                                 fin[nxt], None, None, 0, 0, None, None)
+                    expand(mix, ldV, score[cur], fin[cur], M, V, k, end_id, score[nxt], parents[i], tokens[i],
+                           fin[nxt], None, None, 0, 0, None, None)
                     cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
                     be.embedding_fwd(h[1], par_d[i].view(Bk, 1), h[0], Bk, 1, U, U, Bk)
                     be.embedding_fwd(c[1], par_d[i].view(Bk, 1), c[0], Bk, 1, U, U, Bk)
                     continue
                 be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
                 # expansion, and the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]
-                be.beam_step(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
-                             fin[nxt], h[1], c[1], U, U, h[0], c[0])
-        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
+                expand(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
+                       fin[nxt], h[1], c[1], U, U, h[0], c[0])
+        ckey = ((con.key if con is not None else ()) + (cons.key if cons is not None else ())
+                + (("diverse",) + div if div is not None else ()))
         self._run_captured(("beam",) + key + ckey, run)
         pt = bb["pt"].cpu().numpy()
         final = score[max_len & 1].cpu().numpy().reshape(M, k)
@@ -1219,5 +1237,5 @@ class NIC(ModelBase):
             row = par[i, row]
         seqs = seqs.T.reshape(M, k, max_len)
         if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty)
+            return length_normalise(seqs, final, end_id, length_penalty, div[0] if div is not None else 1)
         return seqs, final

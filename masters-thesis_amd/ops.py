@@ -664,6 +664,15 @@ class HipBackend:
                    _p(score_out), _p(parent), _p(token), _p(fin_out), _p(h_in), _p(c_in), ldh, U, _p(h_out), _p(c_out),
                    self._s())
 
+    def beam_step_diverse(self, probs, ld, score_in, fin_in, B, V, k, end_id, score_out, parent, token, fin_out, h_in, c_in,
+                          ldh, U, h_out, c_out, groups, lam):
+        """beam_step for diverse (group) beam search: the k beams of a sample choose in ``groups`` groups of k / groups, a
+        later group's keys lowered by ``lam`` per earlier choice of the same token at this step
+        (tnt_beam_step_diverse_f32; definition in include/tnt_hip.h); U = 0 skips the reorder"""
+        self._call(self.lib.tnt_beam_step_diverse_f32, "tnt_beam_step_diverse_f32", _p(probs), ld, _p(score_in), _p(fin_in),
+                   B, V, k, end_id, _p(score_out), _p(parent), _p(token), _p(fin_out), _p(h_in), _p(c_in), ldh, U, _p(h_out),
+                   _p(c_out), int(groups), float(lam), self._s())
+
     def decode_constrain(self, logits, ld, V, rows, i, hist_in, hist_out, ldh, last_token, parent, fin, theta, n, m, end_id,
                          bad_ids, n_bad):
         """repetition penalty and bans (bad ids, minimum length, no-repeat n-gram) of decode step i on its logits, in place,
