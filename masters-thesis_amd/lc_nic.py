@@ -24,7 +24,8 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
                          S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, BN_EPS, BN_MOMENTUM,
-                         ScheduledSampling, check_sampling, check_length_penalty, length_normalise)
+                         ScheduledSampling, check_sampling, check_length_penalty, length_normalise, beam_init_scores,
+                         beam_backtrack)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -1546,11 +1547,9 @@ class NIC(ModelBase):
         Wl = a.p("lstm/kernel")
         dev, i32 = self.device, torch.int32
         words0 = torch.as_tensor(rep(start).astype(np.int32)).to(dev).view(Bk, 1)
-        score = [torch.zeros(Mk, device=dev), torch.zeros(Mk, device=dev)]
-        if div is None:
-            score[0].view(M, k)[:, 1:] = -1e30        # step 0: the k beams of a sample are copies, only beam 0 counts
-        else:                                         # ... of every group: only its first beam counts
-            score[0].view(M, div[0], k // div[0])[:, :, 1:] = -1e30
+        Gd = div[0] if div is not None else 1
+        # step 0: only the first beam of the sample, or of every group, counts
+        score = [torch.from_numpy(beam_init_scores(M, k, Gd)).to(dev), torch.zeros(Mk, device=dev)]
         fin = [torch.zeros(Mk, dtype=i32, device=dev), torch.zeros(Mk, dtype=i32, device=dev)]
         parents = torch.zeros(max_len, Mk, dtype=i32, device=dev)
         tokens = torch.zeros(max_len, Mk, dtype=i32, device=dev)
@@ -1597,14 +1596,7 @@ class NIC(ModelBase):
             self.Cs[i + 1].copy_(cg)
             words = tok_d[i].view(Bk, 1)
         final = score[max_len & 1].cpu().numpy().reshape(M, k)
-        par, tok = parents.cpu().numpy(), tokens.cpu().numpy()
-        seqs = np.zeros((M, k, max_len), np.int64)
-        for b in range(M):
-            for r in range(k):
-                row = b * k + r
-                for i in range(max_len - 1, -1, -1):
-                    seqs[b, r, i] = tok[i, row]
-                    row = par[i, row]
+        seqs = beam_backtrack(parents.cpu().numpy(), tokens.cpu().numpy(), M, k)
         if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty, div[0] if div is not None else 1)
+            return length_normalise(seqs, final, end_id, length_penalty, Gd)
         return seqs, final

@@ -450,6 +450,27 @@ def check_diversity(diversity, beam_width):
     return (diversity.groups, diversity.penalty) if diversity.groups > 1 else None
 
 
+def beam_init_scores(M, k, groups=1):
+    """beam search's scores in front of step 0, float32 (M * k,): the k' = k / groups beams of every group of a sample are
+    copies of the start state, so only the group's first counts (0) and the others cannot win (-1e30).  groups = 1 is the
+    plain search's rule: only beam 0 of the sample counts."""
+    init = np.full((M, groups, k // groups), -1e30, np.float32)
+    init[:, :, 0] = 0.0
+    return init.reshape(M * k)
+
+
+def beam_backtrack(parents, tokens, M, k):
+    """the paths of beam search's M * k final beams from the (max_len, M * k) parent rows and tokens of every step (host
+    arrays): walks the parent links of every beam at once, last step first.  Returns (M, k, max_len) int64."""
+    max_len = len(tokens)
+    seqs = np.zeros((max_len, M * k), np.int64)
+    row = np.arange(M * k)
+    for i in range(max_len - 1, -1, -1):
+        seqs[i] = tokens[i, row]
+        row = parents[i, row]
+    return seqs.T.reshape(M, k, max_len)
+
+
 def length_normalise(seqs, scores, end_id, length_penalty, groups=1):
     """Length normalisation of beam search's k finished results per sample (seqs (B, k, max_len), scores (B, k), best
     first): the results are reordered by the key  score / ((5 + L) / 6) ** length_penalty, computed in float64, where L

@@ -20,7 +20,8 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
                          BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
-                         SelfCritical, check_sampling, check_beam, length_normalise)
+                         SelfCritical, check_sampling, check_beam, length_normalise, beam_init_scores,
+                         beam_backtrack)
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -1163,22 +1164,17 @@ class NIC(ModelBase):
         bufs = self.__dict__.setdefault("_beam_bufs", {})
         if key not in bufs:
             dev, i32, f = self.device, torch.int32, self._f
-            init = f(M, k)
-            init[:, 1:] = -1e30                    # step 0: the k beams of a sample are copies, only beam 0 counts
             bufs[key] = dict(
                 rep=torch.arange(B, dtype=i32, device=dev).repeat_interleave(k).view(Bk, 1),
-                start=torch.zeros(Bk, 1, dtype=i32, device=dev), init=init.view(Mk),
+                start=torch.zeros(Bk, 1, dtype=i32, device=dev),
                 score=f(2, Mk), fin=f(2, Mk, dtype=i32), pt=f(2, max_len, Mk, dtype=i32),
                 h=f(2, Bk, U), c=f(2, Bk, U), emb=f(Bk, E), xz=f(Bk, U, 4), out=f(Bk, U), gates=f(Bk, U, 4),
                 probs=f(Bk, ldV))
         bb = bufs[key]
-        init = "init"
-        if div is not None:                        # step 0 of every group: its k' beams are copies, only its first counts
-            init = ("init", div[0])
-            if init not in bb:
-                bb[init] = self._f(M, div[0], k // div[0])
-                bb[init][:, :, 1:] = -1e30
-                bb[init] = bb[init].view(Mk)
+        Gd = div[0] if div is not None else 1
+        init = "init" if div is None else ("init", Gd)
+        if init not in bb:                         # step 0: only the first beam of the sample, or of every group, counts
+            bb[init] = torch.from_numpy(beam_init_scores(M, k, Gd)).to(self.device)
         bb["start"].copy_((start if cons is None else start.repeat(G)).repeat_interleave(k).view(Bk, 1))
         bb["score"][0].copy_(bb[init])
         bb["fin"][0].zero_()
@@ -1229,13 +1225,7 @@ class NIC(ModelBase):
         self._run_captured(("beam",) + key + ckey, run)
         pt = bb["pt"].cpu().numpy()
         final = score[max_len & 1].cpu().numpy().reshape(M, k)
-        par, tok = pt[0], pt[1]
-        seqs = np.zeros((max_len, Mk), np.int64)
-        row = np.arange(Mk)
-        for i in range(max_len - 1, -1, -1):           # back-track every beam at once
-            seqs[i] = tok[i, row]
-            row = par[i, row]
-        seqs = seqs.T.reshape(M, k, max_len)
+        seqs = beam_backtrack(pt[0], pt[1], M, k)
         if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty, div[0] if div is not None else 1)
+            return length_normalise(seqs, final, end_id, length_penalty, Gd)
         return seqs, final

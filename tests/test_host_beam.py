@@ -8,7 +8,7 @@ import pytest
 
 import masters_thesis_amd.ops as ops
 from masters_thesis_amd.lc_nic import NIC as LcNIC
-from masters_thesis_amd.model_base import length_normalise
+from masters_thesis_amd.model_base import beam_backtrack, beam_init_scores, length_normalise
 from masters_thesis_amd.nic import NIC as DenseNIC
 from oracle import models as M
 from helpers import synth_batch, tiny_groups
@@ -202,6 +202,45 @@ def test_dense_length_penalty_matches_restatement(lp):
     assert ok.sum() >= 3
     assert np.array_equal(got[ok], want[ok])
     assert np.allclose(gkey[ok], wkey[ok], rtol=1e-4, atol=1e-4)
+
+
+# ---------------------------------------------------------------------------------------------------- the host helpers
+@pytest.mark.parametrize("max_len", [1, 4])
+@pytest.mark.parametrize("k", [1, 5])
+def test_beam_backtrack_is_the_walk_of_every_beam(k, max_len):
+    """against the beam-by-beam walk of the parent links, on parents drawn within the row's own sample"""
+    import torch
+    M = 3
+    rng = np.random.default_rng(90 + 10 * k + max_len)
+    parents = (np.arange(M * k) // k * k + rng.integers(0, k, (max_len, M * k))).astype(np.int32)
+    tokens = rng.integers(0, 50, (max_len, M * k)).astype(np.int32)
+    want = np.zeros((M, k, max_len), np.int64)
+    for b in range(M):
+        for r in range(k):
+            row = b * k + r
+            for i in range(max_len - 1, -1, -1):
+                want[b, r, i] = tokens[i, row]
+                row = parents[i, row]
+    got = beam_backtrack(parents, tokens, M, k)
+    assert got.dtype == np.int64 and got.shape == (M, k, max_len) and np.array_equal(got, want)
+    # the models pass what .cpu().numpy() gives them (rows of one buffer, or two buffers)
+    pt = torch.tensor(np.stack([parents, tokens])).numpy()
+    assert np.array_equal(beam_backtrack(pt[0], pt[1], M, k), want)
+
+
+@pytest.mark.parametrize("M,k,groups", [(2, 1, 1), (2, 6, 1), (2, 6, 3), (1, 16, 4)])
+def test_beam_init_scores_are_the_models_expressions(M, k, groups):
+    import torch
+    plain = torch.zeros(M, k)
+    plain[:, 1:] = -1e30                      # only beam 0 of the sample counts
+    grouped = torch.zeros(M, groups, k // groups)
+    grouped[:, :, 1:] = -1e30                 # only the first beam of every group counts
+    got = beam_init_scores(M, k, groups)
+    assert isinstance(got, np.ndarray) and got.dtype == np.float32 and got.shape == (M * k,)
+    assert np.array_equal(got, grouped.view(M * k).numpy())
+    if groups == 1:
+        assert np.array_equal(got, plain.view(M * k).numpy())
+        assert np.array_equal(beam_init_scores(M, k), got)
 
 
 ARGS = dict(B=4, N=41, R=5, D=16, A=6, U=16, Et=12, V=13, T=5)
