@@ -1761,7 +1761,7 @@ constexpr int LB_RED_FLOATS = 16 * 4 * 16 * 17;                  // gather sums 
 constexpr int LB_LDS_FLOATS = 2 * 16 * LB_DZLD + LB_RED_FLOATS;  // LSTM role: dz tiles, reduction buffer
 constexpr int LB_W2LD = 68;                                      // row stride of the LSTM role's W2 slice [32][64] (16-byte rows, conflict-free b128 reads)
 constexpr int LB_LSTM_FLOATS = LB_LDS_FLOATS + 32 * LB_W2LD + 16 * 64 + 16 * 2 * 4 * 64;   // + W2 slice + the 16 samples' dq + Wc operands
-constexpr int LB_PF_FLOATS = 35 * 1024;                          // attention role: P, F rows and the dF accumulator of the sample, R (A + 2 D) <= this
+constexpr int LB_PF_FLOATS = 35 * 1024;                          // floor of the dynamic LDS block: the RB == 8 LSTM role parks its [512][65] Ur slab here before the loop (the attention role holds P, F, dP and dF in registers and uses none of it)
 constexpr int LB_LDS_BYTES = (LB_LSTM_FLOATS > LB_PF_FLOATS ? LB_LSTM_FLOATS : LB_PF_FLOATS) * 4 + 16;
 
 template <int G4, int NP, int RB>
