@@ -730,6 +730,30 @@ int32_t tnt_consensus_mix_f32(const float* logits, int32_t ld, int32_t V, int32_
  * (all three null: no launch).  TNT_BADARG for Rm <= 0, G outside [1, 16], an input without its output. */
 int32_t tnt_consensus_spread_i32(const int32_t* token, const int32_t* parent, const int32_t* fin, int32_t Rm, int32_t G,
                                  int32_t* token_out, int32_t* parent_out, int32_t* fin_out, void* stream);
+/* Classifier-free guidance (context-aware / contrastive decoding) for caption decoding: the next-word distribution
+ * given the scan contrasted with the one the same model gives for a null scan, where softmax + argmax sit in a plain
+ * decode (restated by tests/guidance_oracle.py).  Library-defined:
+ *  - Layout.  The consensus layout with G = 2, member-major: logits [2*Rm][ld], V valid columns, are the step's logits
+ *    (behind tnt_decode_constrain_f32, if any); row r is the conditional row (the scan), row Rm + r its null row.  mix
+ *    [Rm][ldm] receives the guided distribution; columns [V, ldm) are never written and logits is read only.
+ *  - Per row, in float32: m = max_v x_v, s = sum_v exp(x_v - m), l_v = (x_v - m) - log s; lc the conditional row's
+ *    values, ln the null row's.  A row with nothing above -inf counts as m = 0, s = 1: each of its l_v is then -inf.
+ *  - Guided logit: g_v = lc_v + scale * (lc_v - ln_v) where both are finite, as one fused multiply-add
+ *    fma(scale, lc_v - ln_v, lc_v).  lc_v = -inf gives g_v = -inf (a ban stays a ban; inf - inf is never formed);
+ *    ln_v = -inf with lc_v finite gives g_v = lc_v (the contrast term is dropped).
+ *  - Plausibility mask (Li et al. 2022): with plaus > 0 every v with lc_v < log(plaus) + max_v lc_v gets g_v = -inf;
+ *    max_v lc_v is the conditional maximum's own value 0 - log s, so the conditional row's first maximum is always
+ *    kept.  plaus == 0: no mask.
+ *  - p_v = exp(g_v - Gm) / sum_v exp(g_v - Gm), Gm = max_v g_v.  A -inf guided logit gives exactly 0.0f; a row whose
+ *    every g_v is -inf gets p = 0 everywhere and token 0.
+ *  - token (nullable) [2*Rm]: the argmax of p_r under the rules of tnt_argmax_rows_f32 (first max wins, nothing above
+ *    -inf gives 0), written to both r and Rm + r: the word fed back to the scan's row and to the null row.
+ *  - One workgroup per mixed row, both member rows read once; fixed summation orders, no atomics, no scratch memory:
+ *    deterministic.
+ * TNT_BADARG for Rm <= 0, V <= 0, ld < V, ldm < V, scale not finite or < 0, plaus not finite or outside [0, 1), null
+ * logits or mix, mix overlapping logits anywhere in their extents; nothing is launched then. */
+int32_t tnt_guidance_mix_f32(const float* logits, int32_t ld, int32_t V, int32_t Rm, float scale, float plaus,
+                             float* mix, int32_t ldm, int32_t* token, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

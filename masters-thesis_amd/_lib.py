@@ -77,6 +77,7 @@ SIGNATURES = {
     "tnt_decode_constrain_f32": [P, I32, I32, I32, I32, P, P, I32, P, P, P, F32, I32, I32, I32, P, I32, P],
     "tnt_consensus_mix_f32": [P, I32, I32, I32, I32, P, I32, P, I32, P, P],
     "tnt_consensus_spread_i32": [P, P, P, I32, I32, P, P, P, P],
+    "tnt_guidance_mix_f32": [P, I32, I32, I32, F32, F32, P, I32, P, P],
     "tnt_argmax_rows_f32": [P, P, I32, I32, I32, P],
     "tnt_greedy_feedback_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
                                 I32, I32, P],

@@ -24,12 +24,14 @@ from collections import Counter
 import numpy as np
 
 
-def _con_kw(constraints, consensus=None):
-    """the ``constraints=`` / ``consensus=`` keywords of a decode call, each passed only when set: a model without
-    constrained or consensus decoding then refuses the call instead of ignoring the keyword"""
+def _con_kw(constraints, consensus=None, guidance=None):
+    """the ``constraints=`` / ``consensus=`` / ``guidance=`` keywords of a decode call, each passed only when set: a model
+    without constrained, consensus or guided decoding then refuses the call instead of ignoring the keyword"""
     kw = {} if constraints is None else {"constraints": constraints}
     if consensus is not None:
         kw["consensus"] = consensus
+    if guidance is not None:
+        kw["guidance"] = guidance
     return kw
 
 
@@ -40,12 +42,15 @@ def _n_start(features, consensus):
     return n if consensus is None else max(n // int(consensus.members), 1)
 
 
-def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_name="", constraints=None, consensus=None):
+def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_name="", constraints=None, consensus=None,
+               guidance=None):
     """eval.py:148-194.  greedy_predict returns (words (B,T,1), probs (B,T,V), alpha (T,B,R,1), s); the files hold
     outputs (n,T,1), outputs_raw (n,T,V) and attention_scores (n,T,R,1) (eval.py:172-174).  ``constraints``
     (model_base.DecodeConstraints) goes to greedy_predict: outputs_raw then holds the constrained distributions.
     ``consensus`` (model_base.Consensus) goes to greedy_predict too: every batch then holds members * M scans, member-major,
-    outputs and outputs_raw are per image (the mixtures) and attention_scores stay per member row."""
+    outputs and outputs_raw are per image (the mixtures) and attention_scores stay per member row.
+    ``guidance`` (model_base.Guidance) goes to greedy_predict as well: outputs_raw then holds the guided distributions, and
+    attention_scores keep the scans' rows (the null scans' rows behind them are dropped)."""
     outs, raws, attns = [], [], []
     for i in range(len(data_generator)):
         sample = data_generator[i]
@@ -53,7 +58,9 @@ def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_na
         start_seq = np.repeat([tokenizer.word_index["<start>"]], _n_start(features, consensus))
         words, probs, alpha, _ = model.greedy_predict(features, a0, c0, start_seq, config["max_length"], config["units"],
                                                       tokenizer, return_s=False,     # eval.py never reads `s`
-                                                      **_con_kw(constraints, consensus))
+                                                      **_con_kw(constraints, consensus, guidance))
+        if guidance is not None:
+            alpha = alpha[:, :words.shape[0]]
         outs.append(words); raws.append(probs); attns.append(alpha)
     outputs = np.concatenate(outs, axis=0)
     outputs_raw = np.concatenate(raws, axis=0)
@@ -68,16 +75,16 @@ def eval_model(model, data_generator, tokenizer, config, out_path, epoch, add_na
 
 
 def eval_fc_model(model, data_generator, tokenizer, config, out_path, epoch, add_name="", constraints=None,
-                  consensus=None):
-    """eval.py:196-216: greedy_predict_fc returns ids (T,B,1); the file holds (n,T,1).  ``constraints`` and ``consensus``
-    go to the model's greedy_predict (a model whose decode has no such keyword, NICfc among them, refuses the call)."""
+                  consensus=None, guidance=None):
+    """eval.py:196-216: greedy_predict_fc returns ids (T,B,1); the file holds (n,T,1).  ``constraints``, ``consensus`` and
+    ``guidance`` go to the model's greedy_predict (a model whose decode has no such keyword, NICfc among them, refuses the call)."""
     outs = []
     for i in range(len(data_generator)):
         sample = data_generator[i]
         features, _, a0, c0 = sample[0][:4]
         start_seq = np.repeat([tokenizer.word_index["<start>"]], _n_start(features, consensus))
         outs.append(model.greedy_predict(features, a0, c0, start_seq, config["max_length"], config["units"], tokenizer,
-                                         **_con_kw(constraints, consensus)))
+                                         **_con_kw(constraints, consensus, guidance)))
     all_outputs = np.swapaxes(np.concatenate(outs, axis=1), 0, 1)
     os.makedirs(out_path, exist_ok=True)
     np.save(os.path.join(out_path, f"output_captions_{epoch}{add_name}.npy"), all_outputs)
@@ -107,18 +114,19 @@ def ids_to_captions(ids, tokenizer, end_token="<end>", drop=("<start>", "<pad>")
 
 
 def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, length_penalty=0.0, end_token="<end>",
-                  constraints=None, consensus=None, diversity=None):
+                  constraints=None, consensus=None, diversity=None, guidance=None):
     """Beam-search captions of either model (nic.NIC or lc_nic.NIC ``beam_search``): every caption starts at the
     tokenizer's "<start>" index and a beam ends at ``end_token``'s index.  Returns (ids (B, max_len) int64 of each
     sample's best beam, captions: token lists cut at ``end_token`` as ids_to_captions cuts).  ``constraints``
     (model_base.DecodeConstraints) goes to beam_search; its min_length counts against ``end_token``'s index.
     ``consensus`` (model_base.Consensus) goes to beam_search too: ``features`` then holds members * M scans, member-major,
     and one caption per image comes back.  ``diversity`` (model_base.BeamDiversity) goes to beam_search as well; the
-    caption returned is group 0's best, the plain search of width beam_width / groups (call beam_search for all of them)."""
+    caption returned is group 0's best, the plain search of width beam_width / groups (call beam_search for all of them).
+    ``guidance`` (model_base.Guidance) goes to beam_search too: the beams are scored by the guided distributions."""
     end_id = int(tokenizer.word_index[end_token])
     start = np.full(_n_start(features, consensus), int(tokenizer.word_index["<start>"]), np.int64)
     seqs, _ = model.beam_search(features, a0, c0, start, max_len, beam_width=beam_width, end_id=end_id,
-                                length_penalty=length_penalty, **_con_kw(constraints, consensus),
+                                length_penalty=length_penalty, **_con_kw(constraints, consensus, guidance),
                                 **({} if diversity is None else {"diversity": diversity}))
     ids = np.ascontiguousarray(seqs[:, 0, :]).astype(np.int64)
     return ids, ids_to_captions(ids, tokenizer, end_token=end_token)

@@ -1299,7 +1299,7 @@ class NIC(ModelBase):
         return self.cap.cpu().numpy().copy()
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       sample_step=0, top_k=0, top_p=1.0, return_s=True, constraints=None, consensus=None):
+                       sample_step=0, top_k=0, top_p=1.0, return_s=True, constraints=None, consensus=None, guidance=None):
         """greedy_predict_attention with the argmax replaced by lc_NIC.sample_choice (lc_NIC.py:571-575:
         tf.random.categorical(log(probs), 1)); ``temperature`` as in ThinkAndTell/evaluate.py:223.  TF's
         sampler cannot be reproduced; the draw is the Philox stream (seed, S_SAMPLE + position, sample_step),
@@ -1313,18 +1313,20 @@ class NIC(ModelBase):
         ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what the
         returned probabilities hold then.
         ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
-        of a plain decode of M scans uses) and is fed to all of them."""
+        of a plain decode of M scans uses) and is fed to all of them.
+        ``guidance`` as in greedy_predict: the draw is from the guided distribution (row b on the Philox stream row b of a
+        plain decode uses) and is fed to the scan's row and its null row."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         if top_k == 0 and top_p == 1.0:
             return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
                                        _sample=(temperature, int(sample_step)), return_s=return_s, constraints=constraints,
-                                       consensus=consensus)
+                                       consensus=consensus, guidance=guidance)
         return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
                                    _filter=(temperature, top_k, top_p, int(sample_step)), return_s=return_s,
-                                   constraints=constraints, consensus=consensus)
+                                   constraints=constraints, consensus=consensus, guidance=guidance)
 
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, training=False,
-                       _sample=None, return_s=True, _filter=None, constraints=None, consensus=None):
+                       _sample=None, return_s=True, _filter=None, constraints=None, consensus=None, guidance=None):
         """lc_NIC.greedy_predict -> greedy_predict_attention (lc_NIC.py:507-508,577-638).
         Returns (words (B,max_len,1) int64, probs (B,max_len,V), alpha (max_len,B,R,1), s (max_len,B,R,A))
         as numpy arrays; the whole decode runs on the device with no per-step host sync.
@@ -1337,10 +1339,20 @@ class NIC(ModelBase):
         slices and G must be S), start_seq M entries; per token one tnt_consensus_mix_f32 launch takes the place of softmax
         + argmax and the mixture's first maximum is fed to all members.  words (M, max_len, 1) and probs (M, max_len, V),
         the mixtures, are per image; alpha and s stay per member row, (max_len, G*M, R, ...).  None: the decode as it is
-        without the keyword."""
+        without the keyword.
+        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder runs 2 * B rows,
+        the B scans and behind them their null scans (a0, c0 repeated); per token one tnt_guidance_mix_f32 launch takes
+        the place of softmax + argmax, and the guided distribution's first maximum is fed to both rows.  words and probs,
+        the guided distributions, are per scan; alpha and s stay per member row, (max_len, 2*B, R, ...): the scans' rows
+        first.  ``constraints`` composes (the bans of both rows coincide); consensus and n_subjects > 1 do not.  None or a
+        neutral object: the decode as it is without the keyword."""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        cons = self._consensus(consensus, img_input, start.shape[0], training=training)
+        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], consensus=consensus, training=training)
+        if guide is not None:
+            cons, img_input, a0, c0 = guide
+        else:
+            cons = self._consensus(consensus, img_input, start.shape[0], training=training)
         assert training is False, "training is set to True"                                  # lc_NIC.py:591
         if cons is not None:
             start = start.repeat(cons.G)
@@ -1501,7 +1513,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
-                    length_penalty=0.0, constraints=None, consensus=None, diversity=None):
+                    length_penalty=0.0, constraints=None, consensus=None, diversity=None, guidance=None):
         """Beam search over the attention decoder.  The reference only sketches it (lc_NIC.beam_search / _beam_search,
         lc_NIC.py:640-692, recurse without returning; ThinkAndTell/evaluate.py:203-228 stops after one expansion), so
         the definition is this library's: standard log-probability beam search of width ``beam_width`` with the greedy
@@ -1527,13 +1539,22 @@ class NIC(ModelBase):
         results are group-major: group g's k' results sit best first at slots g*k' .. g*k' + k' - 1 (the group index of
         the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
         reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
-        None or groups = 1: the search as it is without the keyword."""
+        None or groups = 1: the search as it is without the keyword.
+        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder rows are
+        [2][B][k], the scans' beams and behind them the null scans'; per token one tnt_guidance_mix_f32 launch takes the
+        softmax's place and the search runs on the B * k guided rows exactly as a consensus of two members does, so the
+        scores are sums of guided log-probabilities.  ``constraints`` composes; consensus, diverse beams and
+        n_subjects > 1 do not.  None or a neutral object: the search as it is without the keyword."""
         length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
         div = self._diversity(diversity, k)
         start = np.asarray(start_seq).reshape(-1)
-        cons = self._consensus(consensus, img_input, start.shape[0], k)
+        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], k, consensus, div)
+        if guide is not None:
+            cons, img_input, a0, c0 = guide
+        else:
+            cons = self._consensus(consensus, img_input, start.shape[0], k)
         M = start.shape[0]                            # captions: the expansion runs on M * k rows
         if cons is not None:
             start = np.tile(start, cons.G)

@@ -327,16 +327,20 @@ class _ConsensusDecode:
     the device buffers, the per-step launches and the suffix of the capture key."""
 
     def __init__(self, model, c, M, k=1):
-        self.be, self.V, self.ldV, self.G, self.M, self.k = model.be, model.V, model.ldV, c.members, M, k
-        self.Rm, self.rows, self.mode = M * k, c.members * M * k, Consensus.MODES.index(c.mode)
-        self._bufs = model.__dict__.setdefault("_cons_bufs", {})
-        self._model = model
+        self._setup(model, c.members, M, k)
+        self.mode = Consensus.MODES.index(c.mode)
         self.w = None
         if c.weights is not None:       # one small buffer per distinct weight vector: the vector is part of the capture key
             if ("w", c.weights) not in self._bufs:
                 self._bufs["w", c.weights] = torch.tensor(c.weights, dtype=torch.float32).to(model.device)
             self.w = self._bufs["w", c.weights]
         self.key = ("consensus", self.G, c.mode, c.weights)
+
+    def _setup(self, model, G, M, k):
+        self.be, self.V, self.ldV, self.G, self.M, self.k = model.be, model.V, model.ldV, G, M, k
+        self.Rm, self.rows = M * k, G * M * k
+        self._bufs = model.__dict__.setdefault("_cons_bufs", {})
+        self._model = model
 
     def bufs(self, max_len, steps):
         """static buffers per (G, M, k, max_len): start (rows, 1) int32, the start token of every member row; logits
@@ -370,6 +374,65 @@ class _ConsensusDecode:
             self.mix(logits, mix)
             sampler(mix, pick, self.Rm)
             self.spread(pick, None, None, ids, None, None)
+
+
+class Guidance:
+    """Classifier-free guidance (context-aware / contrastive decoding), for the ``guidance=`` keyword of greedy_predict,
+    sample_predict and beam_search of nic.NIC and lc_nic.NIC: at every token the next-word distribution given the scan is
+    contrasted on the device with the one the same model gives for a null scan (tnt_guidance_mix_f32, include/tnt_hip.h),
+    log p = lc + scale * (lc - ln) renormalised, so that words the scan makes more likely than the language prior does
+    are promoted; the common word is fed back to the scan's row and to the null row.
+      scale         finite, >= 0; 0 leaves the conditional distribution
+      null          the null scan: None, the all-zero scan (the mean of z-scored betas); an array (N,), one null scan
+                    shared by every image; an array (M, N), one per image of the decoded batch
+      plausibility  in [0, 1) (0: off): tokens whose conditional probability is below plausibility times the conditional
+                    maximum are banned (Li et al. 2022), which keeps a large scale from promoting implausible words
+    Bad values raise ValueError here, before any launch; what depends on the model or the call (the shape of ``null``
+    against the batch) is checked by the decode.  The decode runs 2 * M decoder rows.  Out of scope: a separately
+    trained unconditional model as the null member, guidance with consensus or diverse beams, NICfc, the ThinkAndTell /
+    ShowAndTell generators and score_captions."""
+
+    def __init__(self, scale, null=None, plausibility=0.0):
+        is_num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+        f32max = float(np.finfo(np.float32).max)
+        if not is_num(scale) or not np.isfinite(scale) or scale < 0 or float(scale) > f32max:
+            raise ValueError(f"scale must be a finite number >= 0 (0: off), got {scale!r}")
+        if not is_num(plausibility) or not np.isfinite(plausibility) or not 0 <= plausibility < 1 or not np.float32(plausibility) < 1:
+            raise ValueError(f"plausibility must be a number in [0, 1) (0: off), got {plausibility!r}")
+        if null is not None:
+            try:
+                v = null.detach().cpu().numpy() if isinstance(null, torch.Tensor) else np.asarray(null)
+                v = np.array(v, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"null must be None or an array (N,) or (M, N) of numbers, got {null!r}") from None
+            if v.ndim not in (1, 2) or v.size == 0 or not np.all(np.isfinite(v)):
+                raise ValueError(f"null must be None or a finite, non-empty array (N,) or (M, N), got shape {v.shape}")
+            null = v
+        self.scale, self.null, self.plausibility = float(scale), null, float(plausibility)
+
+    @property
+    def neutral(self):
+        """scale and plausibility are both off (in float32): the decode runs as without guidance"""
+        return np.float32(self.scale) == 0 and np.float32(self.plausibility) == 0
+
+    def __repr__(self):
+        null = "None" if self.null is None else f"<array {self.null.shape}>"
+        return f"Guidance(scale={self.scale}, null={null}, plausibility={self.plausibility})"
+
+
+class _GuidanceDecode(_ConsensusDecode):
+    """The host part of a guided decode (ModelBase._guidance) of ``M`` samples x ``k`` beams: the consensus helper with the
+    two members (scan, null scan) and tnt_guidance_mix_f32 as the mix launch; buffers, spread and choose are inherited."""
+
+    def __init__(self, model, g, M, k=1):
+        self._setup(model, 2, M, k)
+        self.scale, self.plaus = float(np.float32(g.scale)), float(np.float32(g.plausibility))
+        self.key = ("guidance", self.scale, self.plaus)
+
+    def mix(self, logits, mix, token=None):
+        """one step: the 2 * Rm member rows' logits [rows][ldV] -> the guided distribution [Rm][ldV]; token (rows,) int32:
+        its argmax, on both member rows"""
+        self.be.guidance_mix(logits, self.ldV, self.V, self.Rm, self.scale, self.plaus, mix, self.ldV, token)
 
 
 def check_sampling(top_k, top_p, temperature):
@@ -1411,6 +1474,49 @@ class ModelBase:
             raise ValueError(f"consensus of {G} members over {n_rows} input rows decodes {n_rows // G} captions: start_seq "
                              f"must have {n_rows // G} entries, got {n_start}")
         return _ConsensusDecode(self, c, n_start, int(beam_width))
+
+    def _guidance(self, guidance, img_input, a0, c0, n_start, beam_width=1, consensus=None, diversity=None, training=False):
+        """The guided-decode helper and the inputs it decodes, ``(helper, img_input, a0, c0)`` with the 2 * M rows
+        member-major (the scans, then their null scans; a0 / c0 repeated), or None when ``guidance`` is None or neutral:
+        then the decode issues the launches it issues without the keyword, under the same capture key.  Refusals (before
+        any launch): not a Guidance; together with consensus or diverse beams; training=True; a data-parallel model;
+        n_subjects > 1; img_input rows other than n_start; a null scan whose shape does not fit the batch."""
+        g = guidance
+        if g is None:
+            return None
+        if not isinstance(g, Guidance):
+            raise ValueError(f"guidance must be a Guidance or None, got {g!r}")
+        if g.neutral:
+            return None
+        if consensus is not None:
+            raise ValueError("guidance together with consensus is not supported: pass one of the two")
+        if diversity is not None:
+            raise ValueError("guidance together with diversity (diverse beam search) is not supported: pass one of the two")
+        if training:
+            raise ValueError("guided decoding is an inference mode: training=True is refused")
+        if self.grad_sync is not None:
+            raise NotImplementedError("guided decoding has no data-parallel schedule: decode on one device")
+        S = int(getattr(self, "S", 1))
+        if S > 1:
+            raise ValueError(f"guided decoding is built for one subject: n_subjects = {S} is not supported")
+        if not hasattr(img_input, "shape"):
+            img_input = np.asarray(img_input)
+        shape = tuple(int(v) for v in img_input.shape)
+        if len(shape) != 2 or shape[0] != n_start:
+            raise ValueError(f"guided decoding takes one scan per caption: img_input must be ({n_start}, N) for the "
+                             f"{n_start} entries of start_seq, got {shape}")
+        null = np.zeros(shape[1], np.float32) if g.null is None else g.null
+        if null.shape != shape[1:] and null.shape != shape:
+            raise ValueError(f"the null scan must have shape {shape[1:]} or {shape} for this batch, got {null.shape}")
+        null = np.ascontiguousarray(np.broadcast_to(null, shape))
+
+        def twice(t, second=None):
+            if isinstance(t, torch.Tensor):
+                u = t if second is None else torch.as_tensor(second).to(device=t.device, dtype=t.dtype)
+                return torch.cat([t, u], dim=0)
+            t = np.asarray(t)
+            return np.concatenate([t, t if second is None else second.astype(t.dtype)], axis=0)
+        return _GuidanceDecode(self, g, n_start, int(beam_width)), twice(img_input, null), twice(a0), twice(c0)
 
     def _diversity(self, diversity, beam_width):
         """(groups, penalty) of a diverse beam search (check_diversity), or None when ``diversity`` is None or has one

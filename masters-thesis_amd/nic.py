@@ -924,7 +924,7 @@ class NIC(ModelBase):
     call = __call__
 
     def greedy_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, constraints=None,
-                       consensus=None):
+                       consensus=None, guidance=None):
         """NIC.greedy_predict (NIC.py:148-195), inference mode; returns np.ndarray (max_len, B, 1, V).
         A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does.
         ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
@@ -935,12 +935,17 @@ class NIC(ModelBase):
         hold G * M rows, member-major (rows [g*M, (g+1)*M): member g), start_seq M entries; per token one
         tnt_consensus_mix_f32 launch takes the place of softmax + argmax, the mixture's first maximum is fed to all members,
         and a fed 0 masks the next LSTM step on every member.  Returns the mixtures, (max_len, M, 1, V).  None: the decode
-        as it is without the keyword."""
-        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints, consensus)
+        as it is without the keyword.
+        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder runs 2 * B rows,
+        the B scans and behind them their null scans (a0, c0 repeated); per token one tnt_guidance_mix_f32 launch takes
+        the place of softmax + argmax, and the guided distribution's first maximum is fed to both rows.  Returns the
+        guided distributions, (max_len, B, 1, V).  ``constraints`` composes (the bans of both rows coincide); consensus
+        does not.  None or a neutral object: the decode as it is without the keyword."""
+        probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints, consensus, guidance)
         return probs_all[:, :, :self.V].cpu().numpy()[:, :, None, :]
 
     def sample_predict(self, img_input, a0, c0, start_seq, max_len, units=None, tokenizer=None, temperature=1.0,
-                       top_k=0, top_p=1.0, sample_step=0, constraints=None, consensus=None):
+                       top_k=0, top_p=1.0, sample_step=0, constraints=None, consensus=None, guidance=None):
         """greedy_predict with the argmax replaced by a categorical draw from each step's probabilities, filtered by
         ``top_k`` (>= 1: only the k most likely tokens; 0: off) and ``top_p`` (< 1: only the shortest most-likely prefix
         whose mass reaches top_p; 1: off) at ``temperature`` (tnt_sample_topkp_f32, definition in include/tnt_hip.h).
@@ -951,12 +956,14 @@ class NIC(ModelBase):
         holds then.
         ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
         of a plain decode of M scans uses) and is fed to all of them; ids and probs are per image (M rows).
+        ``guidance`` as in greedy_predict: the draw is from the guided distribution (row b on the Philox stream row b of a
+        plain decode uses) and is fed to the scan's row and its null row; ``probs`` holds the guided distributions.
         Returns (ids (B, max_len, 1) int64, probs (max_len, B, 1, V))."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)),
-                                      constraints, consensus)
+                                      constraints, consensus, guidance)
         V = self.V
-        ids = ids[:, :probs_all.shape[1]]              # consensus: member 0's rows (every member holds the common word)
+        ids = ids[:, :probs_all.shape[1]]              # consensus / guidance: member 0's rows (every member holds the common word)
         return (ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None],
                 probs_all[:, :, :V].cpu().numpy()[:, :, None, :])
 
@@ -980,15 +987,20 @@ class NIC(ModelBase):
         be.lstm_step_fwd(xz, h0, c0, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h1, c1, None,
                          self.gates[0], B, U)
 
-    def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None):
+    def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
         sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None).  With
         constraints on (ModelBase._constrain) the greedy loop keeps its ids per step too: the history is built from them.
         With consensus on (ModelBase._consensus) the decoder runs the G * M member rows, probs holds the M mixtures per
-        step and ids the common word on every member row."""
+        step and ids the common word on every member row.  With guidance on (ModelBase._guidance) the same helper runs
+        the two members (scans, null scans) with tnt_guidance_mix_f32 as its mix launch."""
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        cons = self._consensus(consensus, img_input, start.shape[0])
+        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], consensus=consensus)
+        if guide is not None:
+            cons, img_input, a0, c0 = guide
+        else:
+            cons = self._consensus(consensus, img_input, start.shape[0])
         if cons is not None:
             start = start.repeat(cons.G)
         B = start.shape[0]
@@ -1118,7 +1130,7 @@ class NIC(ModelBase):
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, length_penalty=0.0,
-                    units=None, tokenizer=None, constraints=None, consensus=None, diversity=None):
+                    units=None, tokenizer=None, constraints=None, consensus=None, diversity=None, guidance=None):
         """Beam search over the dense decoder, the definition of lc_nic.NIC.beam_search (the reference only sketches
         it): log-probability beam search of width ``beam_width`` with greedy_predict's step, whose Keras mask rule it
         keeps (a 0 fed back masks the next LSTM step); at step 0 the k beams of a sample are copies and only beam 0
@@ -1145,13 +1157,22 @@ class NIC(ModelBase):
         the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
         reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
         None or groups = 1: the search as it is without the keyword.
+        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder rows are
+        [2][B][k], the scans' beams and behind them the null scans'; per token one tnt_guidance_mix_f32 launch takes the
+        softmax's place and the search runs on the B * k guided rows exactly as a consensus of two members does (spread,
+        state gather by the spread parents), so the scores are sums of guided log-probabilities.  ``constraints``
+        composes; consensus and diverse beams do not.  None or a neutral object: the search as it is without the keyword.
         Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
         length-normalised key)."""
         k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
         be, a = self.be, self.arena
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         div = self._diversity(diversity, k)
-        cons = self._consensus(consensus, img_input, start.shape[0], k)
+        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], k, consensus, div)
+        if guide is not None:
+            cons, img_input, a0, c0 = guide
+        else:
+            cons = self._consensus(consensus, img_input, start.shape[0], k)
         G = cons.G if cons is not None else 1
         M = start.shape[0]                             # captions: the expansion runs on M * k rows
         B = G * M                                      # staged scans: the decoder runs B * k rows, with consensus [G][M][k]

@@ -694,6 +694,13 @@ class HipBackend:
         self._call(self.lib.tnt_consensus_spread_i32, "tnt_consensus_spread_i32", _p(token), _p(parent), _p(fin), Rm, G,
                    _p(token_out), _p(parent_out), _p(fin_out), self._s())
 
+    def guidance_mix(self, logits, ld, V, Rm, scale, plaus, mix, ldm, token):
+        """classifier-free guidance: the Rm conditional rows' next-word distributions contrasted with their null rows'
+        (row Rm + r) at ``scale``, masked at ``plaus`` times the conditional maximum, plus the argmax on both member rows
+        (tnt_guidance_mix_f32; definition in include/tnt_hip.h); token is nullable"""
+        self._call(self.lib.tnt_guidance_mix_f32, "tnt_guidance_mix_f32", _p(logits), ld, V, Rm, float(scale), float(plaus),
+                   _p(mix), ldm, _p(token), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
