@@ -23,9 +23,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
-                         S_LSTM_IN, S_LSTM_OUT, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, BN_EPS, BN_MOMENTUM,
-                         ScheduledSampling, check_sampling, check_length_penalty, length_normalise, beam_init_scores,
-                         beam_backtrack)
+                         S_LSTM_IN, S_LSTM_OUT, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, BN_EPS, BN_MOMENTUM,
+                         ScheduledSampling, check_sampling, check_length_penalty, _TokenChoice, _BeamDecode)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -1310,12 +1309,8 @@ class NIC(ModelBase):
         select_nucleus2, lc_NIC.py:694-710).  With both at their defaults the draw is the unfiltered one above.  A
         filtered decode is captured and replayed like greedy_predict; sample_step reaches the replay through a device
         word, so every call draws its own stream without a re-capture.
-        ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what the
-        returned probabilities hold then.
-        ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
-        of a plain decode of M scans uses) and is fed to all of them.
-        ``guidance`` as in greedy_predict: the draw is from the guided distribution (row b on the Philox stream row b of a
-        plain decode uses) and is fed to the scan's row and its null row."""
+        ``constraints``, ``consensus``, ``guidance`` as in greedy_predict: the draw is from the constrained, mixed or guided
+        distribution, which is also what the returned probabilities hold then."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         if top_k == 0 and top_p == 1.0:
             return self.greedy_predict(img_input, a0, c0, start_seq, max_len, units, tokenizer,
@@ -1330,59 +1325,31 @@ class NIC(ModelBase):
         """lc_NIC.greedy_predict -> greedy_predict_attention (lc_NIC.py:507-508,577-638).
         Returns (words (B,max_len,1) int64, probs (B,max_len,V), alpha (max_len,B,R,1), s (max_len,B,R,A))
         as numpy arrays; the whole decode runs on the device with no per-step host sync.
-        ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
-        applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
-        softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
-        a neutral object: the decode as it is without the keyword.
-        ``consensus`` (model_base.Consensus(members=G, ...)): one caption per image from G scans of it.  img_input, a0, c0
-        hold G * M rows, member-major (rows [g*M, (g+1)*M): member g; with n_subjects = S the members are the S subject
-        slices and G must be S), start_seq M entries; per token one tnt_consensus_mix_f32 launch takes the place of softmax
-        + argmax and the mixture's first maximum is fed to all members.  words (M, max_len, 1) and probs (M, max_len, V),
-        the mixtures, are per image; alpha and s stay per member row, (max_len, G*M, R, ...).  None: the decode as it is
-        without the keyword.
-        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder runs 2 * B rows,
-        the B scans and behind them their null scans (a0, c0 repeated); per token one tnt_guidance_mix_f32 launch takes
-        the place of softmax + argmax, and the guided distribution's first maximum is fed to both rows.  words and probs,
-        the guided distributions, are per scan; alpha and s stay per member row, (max_len, 2*B, R, ...): the scans' rows
-        first.  ``constraints`` composes (the bans of both rows coincide); consensus and n_subjects > 1 do not.  None or a
-        neutral object: the decode as it is without the keyword."""
+        ``constraints``, ``consensus``, ``guidance``: model_base.DecodeConstraints, Consensus and Guidance, whose docstrings
+        define them.  With consensus (img_input, a0, c0 hold G * M rows, member-major; with n_subjects = S the members are
+        the S subject slices and G must be S) words (M, max_len, 1) and probs (M, max_len, V), the mixtures, are per
+        image; with guidance words and probs, the guided distributions, are per scan.  alpha and s stay per member row,
+        (max_len, G*M, R, ...), under guidance (max_len, 2*B, R, ...) with the scans' rows first."""
         be, a = self.be, self.arena
-        start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], consensus=consensus, training=training)
-        if guide is not None:
-            cons, img_input, a0, c0 = guide
-        else:
-            cons = self._consensus(consensus, img_input, start.shape[0], training=training)
-        assert training is False, "training is set to True"                                  # lc_NIC.py:591
-        if cons is not None:
-            start = start.repeat(cons.G)
-        B = start.shape[0]
-        con = self._constrain(constraints, B, max_len)
+        cons, (img_input, a0, c0), start, M, G, B, con, _, ckey = self._decode_setup(
+            guidance, consensus, constraints, None, img_input, a0, c0, start_seq, max_len, training=training)
         self._stage_inputs((img_input, torch.zeros(B, max_len, dtype=torch.int32), a0, c0))
         R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
         Wl = a.p("lstm/kernel")
-        # decode buffers are static per (B, max_len, return_s) so that the whole loop can be one captured hipGraph
+        # decode buffers are static per (B, max_len) so that the whole loop can be one captured hipGraph
         # (encoder + max_len x {embed, project, attention, LSTM step, head, softmax, argmax}: ~8 launches per token)
-        key = (B, max_len, bool(return_s))
-        bufs = self.__dict__.setdefault("_dec_bufs", {})
-        if cons is not None:                           # the mixtures are M rows per step: probs and ids are the helper's
-            cb = cons.bufs(max_len, max_len)
-            bufs, key = self.__dict__.setdefault("_cons_dec_bufs", {}), key + (cons.G,)
-            if key not in bufs:
-                bufs[key] = (cb["start"], cb["mix"], self._f(max_len, B, R, A) if return_s else None, cb["ids"])
-        if key not in bufs:
-            bufs[key] = (torch.zeros(B, 1, dtype=torch.int32, device=self.device),
-                         torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device),
-                         torch.zeros(max_len, B, R, A, dtype=torch.float32, device=self.device) if return_s else None,
-                         torch.zeros(max_len, B, dtype=torch.int32, device=self.device))
-        start_buf, probs, s_all, ids = bufs[key]
-        start_buf.copy_(start.view(B, 1))
-        if _filter is not None:
-            step_buf = self._sample_step_word(_filter[3])
+        choice = _TokenChoice(self, B, max_len, _filter if _filter is not None else _sample, con, cons)
+        choice.start.copy_(start.view(B, 1))
+        s_all = None
+        if return_s:
+            sbufs = self.__dict__.setdefault("_dec_s", {})
+            if (B, max_len) not in sbufs:
+                sbufs[B, max_len] = self._f(max_len, B, R, A)
+            s_all = sbufs[B, max_len]
 
         def run():
             self._encode(B, False)
-            words = start_buf
+            words = choice.start
             for i in range(max_len):
                 text = self.text[i * B:(i + 1) * B]
                 be.embedding_fwd(a.p("emb_text/embeddings"), words, text, B, 1, Et, Et, V)        # :596,632
@@ -1391,42 +1358,20 @@ class NIC(ModelBase):
                 self._decode_step(i, B, False, s_all[i] if return_s else None)
                 self.gemm_sk(self.Hs[i + 1], a.p("time_distributed_nonlinear/kernel"), self.inter[:B], B, H, U, U, H, H,
                              bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)     # :621
-                logits = probs[i] if cons is None else cb["logits"]
+                logits = choice.logits(i)
                 self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), logits, B, V, H, H, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))                                # :623
-                if con is not None:
-                    con.step(i, logits, ldV, words if i > 0 else None)
-                if cons is not None:                   # mix (+ argmax, or draw + spread) in the place of softmax + argmax
-                    draw = None
-                    if _filter is not None:
-                        draw = lambda p, out, rows, i=i: be.sample_topkp(p, out, rows, V, ldV, _filter[0], _filter[1], _filter[2],
-                                                                         False, self.seed, S_SAMPLE + i, 0, step_buf)
-                    elif _sample is not None:
-                        draw = lambda p, out, rows, i=i: be.sample_rows(p, out, rows, V, ldV, _sample[0], False, self.seed,
-                                                                        S_SAMPLE + i, _sample[1])
-                    cons.choose(logits, probs[i], cb["pick"][i], ids[i], draw)
-                    words = ids[i].view(B, 1)
-                    continue
-                be.softmax_cce(probs[i], None, probs[i], None, None, None, B, V, ldV, 0.0)
-                if _filter is not None:
-                    be.sample_topkp(probs[i], ids[i], B, V, ldV, _filter[0], _filter[1], _filter[2], False, self.seed,
-                                    S_SAMPLE + i, 0, step_buf)
-                elif _sample is None:
-                    be.argmax_rows(probs[i], ids[i], B, V, ldV)                                    # :627
-                else:
-                    be.sample_rows(probs[i], ids[i], B, V, ldV, _sample[0], False, self.seed, S_SAMPLE + i, _sample[1])
-                words = ids[i].view(B, 1)
-        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
-        if _filter is not None:     # the stream step is read from step_buf on the device: captured like the greedy loop
+                words = choice.step(i, logits, words)                                              # :627
+        key = (B, max_len, bool(return_s)) + ((G,) if cons is not None else ())
+        if _filter is not None:     # the stream step is read from the step word on the device: captured like the greedy loop
             self._run_captured(("sample",) + key + tuple(_filter[:3]) + ckey, run)
         elif _sample is None:
             self._run_captured(("greedy",) + key + ckey, run)
         else:                      # the sampling stream step is a launch argument: not captured
             run()
-        if cons is not None:
-            ids = ids[:, :cons.M]                      # member 0's rows: every member holds the common word
+        ids = choice.ids[:, :M]                        # member 0's rows: every member holds the common word
         out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
-        out_probs = probs[:, :, :V].permute(1, 0, 2).contiguous().cpu().numpy()
+        out_probs = choice.probs[:, :, :V].permute(1, 0, 2).contiguous().cpu().numpy()
         # s (the dropout-free tanh activations, 44 MB at the BASELINE shape) is part of the reference's return tuple but
         # only analysis code reads it: return_s=False skips its device-to-host copy (eval_model does)
         return out_words, out_probs, self.alpha[:max_len].cpu().numpy()[..., None], (s_all.cpu().numpy() if return_s else None)
@@ -1524,72 +1469,33 @@ class NIC(ModelBase):
         back-tracked on the host at the end.  Restated by oracle.models.LcNIC.beam_search.
         ``length_penalty`` > 0 reorders the k results by score / ((5 + L) / 6) ** length_penalty and returns that key as
         the scores (model_base.length_normalise); the search itself is unchanged.
-        ``constraints`` (model_base.DecodeConstraints): each live beam row's logits are constrained from the row's own path
-        (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
-        beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
-        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword.
-        ``consensus`` (model_base.Consensus(members=G, ...)): the beams of image m are scored by the mixture of its G scans
-        (with n_subjects = S: of its S subject slices).  The inputs hold G * M rows, member-major, start_seq M entries; the
-        decoder rows are [G][M][k].  Per token one tnt_consensus_mix_f32 launch takes the softmax's place, the expansion
-        runs on the M * k mixed rows, one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the
-        member rows, and the state is gathered by the spread parents.  Sequences and scores are per image.
-        ``diversity`` (model_base.BeamDiversity(groups=Gd, penalty=lambda)): diverse beam search.  The k beams of a sample
-        search as Gd groups of k' = k / Gd; one tnt_beam_step_diverse_f32 launch (U = 0: the state gathers stay) takes
-        the expansion's place, with consensus too, and every group starts from its own copy of the start state.  The
-        results are group-major: group g's k' results sit best first at slots g*k' .. g*k' + k' - 1 (the group index of
-        the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
-        reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
-        None or groups = 1: the search as it is without the keyword.
-        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder rows are
-        [2][B][k], the scans' beams and behind them the null scans'; per token one tnt_guidance_mix_f32 launch takes the
-        softmax's place and the search runs on the B * k guided rows exactly as a consensus of two members does, so the
-        scores are sums of guided log-probabilities.  ``constraints`` composes; consensus, diverse beams and
-        n_subjects > 1 do not.  None or a neutral object: the search as it is without the keyword."""
+        ``constraints``, ``consensus``, ``diversity``, ``guidance``: model_base.DecodeConstraints, Consensus, BeamDiversity
+        and Guidance, whose docstrings define them.  Here the expansion under diversity is tnt_beam_step_diverse_f32 with
+        U = 0 (the state gathers stay).  With consensus the inputs hold G * M rows, member-major (with n_subjects = S: the
+        S subject slices), start_seq M entries, and sequences and scores are per image."""
         length_penalty = check_length_penalty(length_penalty)
         be, a = self.be, self.arena
         k = int(beam_width)
-        div = self._diversity(diversity, k)
-        start = np.asarray(start_seq).reshape(-1)
-        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], k, consensus, div)
-        if guide is not None:
-            cons, img_input, a0, c0 = guide
-        else:
-            cons = self._consensus(consensus, img_input, start.shape[0], k)
-        M = start.shape[0]                            # captions: the expansion runs on M * k rows
-        if cons is not None:
-            start = np.tile(start, cons.G)
-        B = start.shape[0]                            # staged scans: the decoder runs B * k rows, with consensus [G][M][k]
-        Bk, Mk = B * k, M * k
-        con = self._constrain(constraints, Bk, max_len, k, int(end_id))
+        # M captions: the expansion runs on M * k rows; B = G * M staged scans: the decoder runs B * k rows, [G][M][k]
+        cons, (img_input, a0, c0), start, M, _, B, con, div, _ = self._decode_setup(
+            guidance, consensus, constraints, diversity, img_input, a0, c0, start_seq, max_len, k, end_id)
+        end_id, Bk = int(end_id), B * k
         rep = lambda t: np.repeat(np.asarray(t), k, axis=0)
         x = img_input.cpu().numpy() if isinstance(img_input, torch.Tensor) else np.asarray(img_input)
         self._stage_inputs((rep(x), torch.zeros(Bk, max_len, dtype=torch.int32), rep(np.asarray(a0)), rep(np.asarray(c0))))
         R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
         Wl = a.p("lstm/kernel")
-        dev, i32 = self.device, torch.int32
-        words0 = torch.as_tensor(rep(start).astype(np.int32)).to(dev).view(Bk, 1)
-        Gd = div[0] if div is not None else 1
-        # step 0: only the first beam of the sample, or of every group, counts
-        score = [torch.from_numpy(beam_init_scores(M, k, Gd)).to(dev), torch.zeros(Mk, device=dev)]
-        fin = [torch.zeros(Mk, dtype=i32, device=dev), torch.zeros(Mk, dtype=i32, device=dev)]
-        parents = torch.zeros(max_len, Mk, dtype=i32, device=dev)
-        tokens = torch.zeros(max_len, Mk, dtype=i32, device=dev)
         probs = self.logits[:Bk]
-        # what the decoder rows read back: the expansion's own outputs or, with consensus, their spread to the member rows
-        tok_d, par_d, fin_d = tokens, parents, fin
-        if cons is not None:
-            cb = cons.bufs(max_len, 1)
-            mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
-            cb["fin"].zero_()
         hg, cg = self._f(Bk, U), self._f(Bk, U)
         # the expansion launch: tnt_beam_topk_f32, or with diversity tnt_beam_step_diverse_f32 without its reorder (U = 0)
         if div is None:
-            expand = be.beam_topk
+            expand = lambda p, score_in, fin_in, *outs: be.beam_topk(p, score_in, fin_in, M, V, ldV, k, end_id, *outs)
         else:
-            expand = lambda p, s_in, f_in, n, V_, ld, k_, eid, s_out, par, tok, f_out: be.beam_step_diverse(
-                p, ld, s_in, f_in, n, V_, k_, eid, s_out, par, tok, f_out, None, None, 0, 0, None, None, *div)
+            expand = lambda p, score_in, fin_in, *outs: be.beam_step_diverse(
+                p, ldV, score_in, fin_in, M, V, k, end_id, *outs, None, None, 0, 0, None, None, *div)
+        beam = _BeamDecode(self, M, k, max_len, end_id, expand, con, cons, div)
         self._encode(Bk, False)
-        words = words0
+        words = start.repeat_interleave(k).view(Bk, 1)
         for i in range(max_len):
             text = self.text[i * Bk:(i + 1) * Bk]
             be.embedding_fwd(a.p("emb_text/embeddings"), words, text, Bk, 1, Et, Et, V)
@@ -1600,24 +1506,10 @@ class NIC(ModelBase):
                          bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)
             self.gemm_sk(self.inter[:Bk], a.p("time_distributed_softmax/kernel"), probs, Bk, V, H, H, ldV, ldV,
                          bias=a.p("time_distributed_softmax/bias"))
-            cur, nxt = i & 1, (i & 1) ^ 1
-            if con is not None:
-                con.step(i, probs, ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
-            if cons is None:
-                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
-                expand(probs, score[cur], fin[cur], B, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
-            else:   # the mixture in the softmax's place, the expansion on the M*k mixed rows, its choice spread to the members
-                cons.mix(probs, mix)
-                expand(mix, score[cur], fin[cur], M, V, ldV, k, int(end_id), score[nxt], parents[i], tokens[i], fin[nxt])
-                cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
+            words, par = beam.step(i, probs)
             # the surviving beams continue from their parents' LSTM state (row gather by parent)
-            be.embedding_fwd(self.Hs[i + 1], par_d[i].view(Bk, 1), hg, Bk, 1, U, U, Bk)
-            be.embedding_fwd(self.Cs[i + 1], par_d[i].view(Bk, 1), cg, Bk, 1, U, U, Bk)
+            be.embedding_fwd(self.Hs[i + 1], par, hg, Bk, 1, U, U, Bk)
+            be.embedding_fwd(self.Cs[i + 1], par, cg, Bk, 1, U, U, Bk)
             self.Hs[i + 1].copy_(hg)
             self.Cs[i + 1].copy_(cg)
-            words = tok_d[i].view(Bk, 1)
-        final = score[max_len & 1].cpu().numpy().reshape(M, k)
-        seqs = beam_backtrack(parents.cpu().numpy(), tokens.cpu().numpy(), M, k)
-        if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty, Gd)
-        return seqs, final
+        return beam.finish(length_penalty)

@@ -213,7 +213,12 @@ class DecodeConstraints:
       bad_ids               up to 64 token ids banned at every step (<unk>, <pad>, <start>, ...)
       end_id                the tokenizer's <end> index for min_length; -1: beam_search's own end_id
     A banned token has probability exactly 0.  Bad values raise ValueError here, before any launch; what depends on the
-    model or the call (vocabulary size, max_len, beam width) is checked by the decode."""
+    model or the call (vocabulary size, max_len, beam width) is checked by the decode.
+    The decode issues one tnt_decode_constrain_f32 launch per token; the probabilities it returns are the constrained
+    distributions, and a sampled decode draws from them.  beam_search constrains each live beam row's logits from the
+    row's own path (the launch also carries the history across the beam reorder), so its scores are sums of constrained
+    log-probabilities; min_length uses the search's ``end_id`` unless the object names its own (the two must agree).
+    None or a neutral object: the decode as it is without the keyword."""
 
     MAX_LEN = 64        # the kernel holds one history token per lane
     MAX_BAD = 64
@@ -293,6 +298,14 @@ class Consensus:
                "logmean": the renormalised weighted geometric mean
       weights  G finite numbers > 0, normalised here to sum 1; None: 1/G each
     Bad values raise ValueError here, before any launch; what depends on the model or the call is checked by the decode.
+    greedy_predict: per token one tnt_consensus_mix_f32 launch takes the place of softmax + argmax, and the mixture's
+    first maximum is fed to all members.  sample_predict: the draw is from the mixture (row m on the Philox stream row m
+    of a plain decode of M scans uses), and one tnt_consensus_spread_i32 launch carries it to the members.  beam_search:
+    the beams of image m are scored by the mixture of its G scans.  The decoder rows are [G][M][k]; the mix launch takes
+    the softmax's place, the expansion runs on the M * k mixed rows, one spread launch carries token, parent and finished
+    flag to the member rows, and every member's state is gathered by its spread parents.  What a decode returns per
+    caption (words, probabilities: the mixtures, sequences, scores) has M rows.  None: the decode as it is without the
+    keyword.
     One model object decodes all members: mixing several models is out of scope (the row layout leaves room for it), and
     so are NICfc, the ThinkAndTell / ShowAndTell generators and score_captions."""
 
@@ -364,17 +377,6 @@ class _ConsensusDecode:
         """what the step chose on the mixed rows, carried to the member rows"""
         self.be.consensus_spread(token, parent, fin, self.Rm, self.G, token_out, parent_out, fin_out)
 
-    def choose(self, logits, mix, pick, ids, sampler=None):
-        """one token of a greedy (sampler None) or sampled decode: mix, then the argmax inside the mix launch, or
-        ``sampler(mix, pick, Rm)`` on the mixed rows (row r draws from the stream row r of a plain decode draws from) and
-        one spread launch.  ids (rows,) then holds the common word of every member row."""
-        if sampler is None:
-            self.mix(logits, mix, ids)
-        else:
-            self.mix(logits, mix)
-            sampler(mix, pick, self.Rm)
-            self.spread(pick, None, None, ids, None, None)
-
 
 class Guidance:
     """Classifier-free guidance (context-aware / contrastive decoding), for the ``guidance=`` keyword of greedy_predict,
@@ -388,7 +390,14 @@ class Guidance:
       plausibility  in [0, 1) (0: off): tokens whose conditional probability is below plausibility times the conditional
                     maximum are banned (Li et al. 2022), which keeps a large scale from promoting implausible words
     Bad values raise ValueError here, before any launch; what depends on the model or the call (the shape of ``null``
-    against the batch) is checked by the decode.  The decode runs 2 * M decoder rows.  Out of scope: a separately
+    against the batch) is checked by the decode.  The decode runs 2 * M decoder rows, the M scans and behind them their
+    null scans (a0, c0 repeated), in beam_search [2][M][k].  Per token one tnt_guidance_mix_f32 launch takes the place of
+    the softmax (in greedy_predict, of softmax + argmax); the guided distribution's first maximum, or sample_predict's
+    draw from it (row b on the Philox stream row b of a plain decode uses), is fed to both rows, and beam_search runs on
+    the M * k guided rows exactly as a consensus of two members does (spread, state gather by the spread parents), so its
+    scores are sums of guided log-probabilities.  The returned probabilities are the guided distributions.
+    ``constraints`` composes (the bans of both rows coincide); consensus, diverse beams and n_subjects > 1 do not.  None
+    or a neutral object: the decode as it is without the keyword.  Out of scope: a separately
     trained unconditional model as the null member, guidance with consensus or diverse beams, NICfc, the ThinkAndTell /
     ShowAndTell generators and score_captions."""
 
@@ -422,7 +431,7 @@ class Guidance:
 
 class _GuidanceDecode(_ConsensusDecode):
     """The host part of a guided decode (ModelBase._guidance) of ``M`` samples x ``k`` beams: the consensus helper with the
-    two members (scan, null scan) and tnt_guidance_mix_f32 as the mix launch; buffers, spread and choose are inherited."""
+    two members (scan, null scan) and tnt_guidance_mix_f32 as the mix launch; buffers and spread are inherited."""
 
     def __init__(self, model, g, M, k=1):
         self._setup(model, 2, M, k)
@@ -486,7 +495,12 @@ class BeamDiversity:
                earlier groups of the sample chose at this token with the same word.  The carried scores stay sums of
                log-probabilities: the penalty steers the selection only
     groups = 1 is plain beam search, whatever the penalty; penalty = 0 gives Gd equal groups.  Bad values raise ValueError
-    here, before any launch; that groups divides the beam width is checked by the search."""
+    here, before any launch; that groups divides the beam width is checked by the search.
+    One tnt_beam_step_diverse_f32 launch takes the expansion's place (with consensus too, on the M * k mixed rows), and
+    every group starts from its own copy of the start state.  The results are group-major: group g's k' results sit best
+    first at slots g*k' .. g*k' + k' - 1 (the group index of the k slots is np.repeat(np.arange(Gd), k')), group 0 is the
+    plain search of width k', and ``length_penalty`` reorders within a group only.  ``constraints`` composes unchanged.
+    None or groups = 1: the search as it is without the keyword."""
 
     def __init__(self, groups, penalty=0.5):
         if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or groups < 1:
@@ -553,6 +567,123 @@ def length_normalise(seqs, scores, end_id, length_penalty, groups=1):
     order = np.argsort(-key, axis=1, kind="stable")
     return (np.take_along_axis(seqs, order[:, :, None], axis=1),
             np.take_along_axis(key, order, axis=1).astype(np.float32))
+
+
+class _TokenChoice:
+    """The per-token choice of a greedy or sampled decode over ``rows`` decoder rows (ModelBase._decode_setup's B), from
+    the head GEMM's logits to the token that is fed back.  ``mode``: None, the first maximum; (temperature, sample_step),
+    the unfiltered draw (tnt_sample_rows_f32: the stream step is a launch argument, so this decode cannot be captured);
+    (temperature, top_k, top_p, sample_step), the filtered draw (tnt_sample_topkp_f32: the step reaches a replay through
+    the model's step word).  ``con`` / ``cons``: the constraint and member helpers, or None.  Static buffers per (rows,
+    max_len), the member helper's own with one: start (rows, 1) int32, the start tokens; probs (max_len, M, ldV), every
+    step's distributions (with a member helper the mixtures); ids (max_len, rows) int32, the word chosen on every row."""
+
+    def __init__(self, model, rows, max_len, mode, con, cons):
+        be, V, ldV, seed = model.be, model.V, model.ldV, model.seed
+        self.be, self.V, self.ldV, self.rows, self.con, self.cons = be, V, ldV, rows, con, cons
+        if cons is not None:                           # the mixtures are M rows per step, not rows
+            cb = cons.bufs(max_len, max_len)
+            self.start, self.probs, self.ids = cb["start"], cb["mix"], cb["ids"]
+            self.pick, self.member_logits = cb["pick"], cb["logits"]
+        else:
+            bufs = model.__dict__.setdefault("_dec_bufs", {})
+            if (rows, max_len) not in bufs:
+                f, i32 = model._f, torch.int32
+                bufs[rows, max_len] = (f(rows, 1, dtype=i32), f(max_len, rows, ldV), f(max_len, rows, dtype=i32))
+            self.start, self.probs, self.ids = bufs[rows, max_len]
+        self.draw = None                               # draw(p, out, n, i): token i of the n rows of p
+        if mode is not None and len(mode) == 4:
+            step_word = model._sample_step_word(mode[3])
+            self.draw = lambda p, out, n, i: be.sample_topkp(p, out, n, V, ldV, mode[0], mode[1], mode[2], False, seed,
+                                                             S_SAMPLE + i, 0, step_word)
+        elif mode is not None:
+            self.draw = lambda p, out, n, i: be.sample_rows(p, out, n, V, ldV, mode[0], False, seed, S_SAMPLE + i, mode[1])
+
+    def logits(self, i):
+        """where the head GEMM of step i writes: the step's row of probs (softmax in place), or the member rows' slab"""
+        return self.probs[i] if self.cons is None else self.member_logits
+
+    def step(self, i, logits, prev):
+        """decode step i: constrain, then softmax + argmax or draw, or with a member helper the mix (+ argmax inside the
+        launch, or draw on the mixed rows + spread).  ``prev`` (rows, 1): the tokens step i was fed.  Returns the tokens
+        to feed step i + 1, ids[i] as (rows, 1)."""
+        be, cons, ids = self.be, self.cons, self.ids[i]
+        if self.con is not None:
+            self.con.step(i, logits, self.ldV, prev if i > 0 else None)
+        if cons is None:
+            be.softmax_cce(logits, None, logits, None, None, None, self.rows, self.V, self.ldV, 0.0)
+            if self.draw is None:
+                be.argmax_rows(logits, ids, self.rows, self.V, self.ldV)
+            else:
+                self.draw(logits, ids, self.rows, i)
+        elif self.draw is None:
+            cons.mix(logits, self.probs[i], ids)
+        else:               # row r draws from the stream row r of a plain decode draws from; the choice goes to every member
+            cons.mix(logits, self.probs[i])
+            self.draw(self.probs[i], self.pick[i], cons.Rm, i)
+            cons.spread(self.pick[i], None, None, ids, None, None)
+        return ids.view(self.rows, 1)
+
+
+class _BeamDecode:
+    """The bookkeeping of a beam search of ``M`` captions x ``k`` beams: scores and finished flags (ping-pong), every
+    step's parents and tokens, the step from the head GEMM's logits to the tokens and parent rows the decoder continues
+    from, and the finish on the host.  ``expand(p, score_in, fin_in, score_out, parent, token, fin_out)``: the model's
+    expansion launch on the M * k rows of p.  ``con`` / ``cons`` / ``div``: what ModelBase._decode_setup returned.
+    ``bufs``: the dict the model keeps its static buffers of this search in (score, fin, pt and the initial scores are
+    added to it), or None for buffers of this call alone."""
+
+    def __init__(self, model, M, k, max_len, end_id, expand, con, cons, div, bufs=None):
+        self.be, self.V, self.ldV, self.M, self.k, self.max_len, self.end_id = model.be, model.V, model.ldV, M, k, max_len, end_id
+        self.expand, self.con, self.cons, self.mix = expand, con, cons, None
+        self.Gd = div[0] if div is not None else 1
+        bufs = {} if bufs is None else bufs
+        if "score" not in bufs:
+            f, i32 = model._f, torch.int32
+            bufs.update(score=f(2, M * k), fin=f(2, M * k, dtype=i32), pt=f(2, max_len, M * k, dtype=i32))
+        init = "init" if div is None else ("init", self.Gd)
+        if init not in bufs:                           # step 0: only the first beam of the sample, or of every group, counts
+            bufs[init] = torch.from_numpy(beam_init_scores(M, k, self.Gd)).to(model.device)
+        self.score, self.fin, self.pt = bufs["score"], bufs["fin"], bufs["pt"]
+        self.parents, self.tokens = self.pt[0], self.pt[1]
+        self.score[0].copy_(bufs[init])
+        self.fin[0].zero_()
+        # what the decoder rows read back: the expansion's own outputs or, with a member helper, their spread to the member rows
+        self.rows = M * k
+        self.tok_d, self.par_d, self.fin_d = self.tokens, self.parents, self.fin
+        if cons is not None:
+            cb = cons.bufs(max_len, 1)
+            self.rows = cons.rows
+            self.mix, self.tok_d, self.par_d, self.fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
+            cb["fin"].zero_()
+
+    def step(self, i, logits):
+        """search step i on the decoder rows' logits: constrain; the softmax in place, or with a member helper the mixture
+        in its place; the expansion on the M * k rows; with a member helper its choice spread to the member rows.  Returns
+        (tokens, parents) as (rows, 1): what every decoder row is fed next and the row whose state it continues from."""
+        cons, score, fin, parents, tokens = self.cons, self.score, self.fin, self.parents, self.tokens
+        tok_d, par_d, fin_d = self.tok_d, self.par_d, self.fin_d
+        cur, nxt = i & 1, (i & 1) ^ 1
+        if self.con is not None:
+            self.con.step(i, logits, self.ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
+        if cons is None:
+            self.be.softmax_cce(logits, None, logits, None, None, None, self.rows, self.V, self.ldV, 0.0)
+            self.expand(logits, score[cur], fin[cur], score[nxt], parents[i], tokens[i], fin[nxt])
+        else:
+            cons.mix(logits, self.mix)
+            self.expand(self.mix, score[cur], fin[cur], score[nxt], parents[i], tokens[i], fin[nxt])
+            cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
+        return tok_d[i].view(self.rows, 1), par_d[i].view(self.rows, 1)
+
+    def finish(self, length_penalty):
+        """the paths back-tracked on the host from one copy of the parents / tokens: (sequences (M, k, max_len) int64,
+        scores (M, k) float32), length-normalised with ``length_penalty`` > 0"""
+        pt = self.pt.cpu().numpy()
+        final = self.score[self.max_len & 1].cpu().numpy().reshape(self.M, self.k)
+        seqs = beam_backtrack(pt[0], pt[1], self.M, self.k)
+        if length_penalty > 0:
+            return length_normalise(seqs, final, self.end_id, length_penalty, self.Gd)
+        return seqs, final
 
 
 def interleave_gates(w, U):
@@ -1526,6 +1657,32 @@ class ModelBase:
         if div is not None and self.grad_sync is not None:
             raise NotImplementedError("diverse beam search has no data-parallel schedule: decode on one device")
         return div
+
+    def _decode_setup(self, guidance, consensus, constraints, diversity, img_input, a0, c0, start_seq, max_len, beam_width=1,
+                      end_id=-1, training=False):
+        """What greedy_predict, sample_predict and beam_search resolve in front of their loops, in the order that decides
+        which refusal a bad call gets: the start tokens, ``diversity``, ``guidance`` before ``consensus``, ``training``,
+        then ``constraints`` over the decoder's row count.  Returns (cons, (img_input, a0, c0), start, M, G, B, con, div,
+        ckey): the member helper (_GuidanceDecode or _ConsensusDecode) or None; the inputs to stage (doubled under
+        guidance); the start tokens on the device, repeated per member (B,); M captions from G members' B = G * M staged
+        scans (the decoder runs B * beam_width rows, member-major); the constraint helper over those rows or None;
+        (groups, penalty) or None; and the suffix the keywords add to the capture key."""
+        k = beam_width
+        start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
+        M = start.shape[0]
+        div = self._diversity(diversity, k)
+        guide = self._guidance(guidance, img_input, a0, c0, M, k, consensus, div, training)
+        if guide is not None:
+            cons, img_input, a0, c0 = guide
+        else:
+            cons = self._consensus(consensus, img_input, M, k, training)
+        assert training is False, "training is set to True"                                  # lc_NIC.py:591
+        G = cons.G if cons is not None else 1
+        B = G * M
+        con = self._constrain(constraints, B * k, max_len, k, int(end_id))
+        ckey = ((con.key if con is not None else ()) + (cons.key if cons is not None else ())
+                + (("diverse",) + div if div is not None else ()))
+        return cons, (img_input, a0, c0), start.repeat(G) if cons is not None else start, M, G, B, con, div, ckey
 
     def _run_captured(self, key, fn):
         """Run ``fn`` (a fixed launch sequence over static buffers) through a hipGraph:

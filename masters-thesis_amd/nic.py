@@ -19,9 +19,8 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM, S_SAMPLE, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
-                         SelfCritical, check_sampling, check_beam, length_normalise, beam_init_scores,
-                         beam_backtrack)
+                         BN_MOMENTUM, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
+                         SelfCritical, check_sampling, check_beam, _TokenChoice, _BeamDecode)
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -927,20 +926,10 @@ class NIC(ModelBase):
                        consensus=None, guidance=None):
         """NIC.greedy_predict (NIC.py:148-195), inference mode; returns np.ndarray (max_len, B, 1, V).
         A predicted id 0 masks the following LSTM step exactly as the keras Embedding mask does.
-        ``constraints`` (model_base.DecodeConstraints): repetition penalty, no-repeat n-gram, minimum length and bad ids,
-        applied to each step's logits on the device (one tnt_decode_constrain_f32 launch per token, in front of the
-        softmax); the returned probabilities are then the constrained distributions, a banned token's exactly 0.  None or
-        a neutral object: the decode as it is without the keyword.
-        ``consensus`` (model_base.Consensus(members=G, ...)): one caption per image from G scans of it.  img_input, a0, c0
-        hold G * M rows, member-major (rows [g*M, (g+1)*M): member g), start_seq M entries; per token one
-        tnt_consensus_mix_f32 launch takes the place of softmax + argmax, the mixture's first maximum is fed to all members,
-        and a fed 0 masks the next LSTM step on every member.  Returns the mixtures, (max_len, M, 1, V).  None: the decode
-        as it is without the keyword.
-        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder runs 2 * B rows,
-        the B scans and behind them their null scans (a0, c0 repeated); per token one tnt_guidance_mix_f32 launch takes
-        the place of softmax + argmax, and the guided distribution's first maximum is fed to both rows.  Returns the
-        guided distributions, (max_len, B, 1, V).  ``constraints`` composes (the bans of both rows coincide); consensus
-        does not.  None or a neutral object: the decode as it is without the keyword."""
+        ``constraints``, ``consensus``, ``guidance``: model_base.DecodeConstraints, Consensus and Guidance, whose docstrings
+        define them.  The returned probabilities are then the constrained distributions; the mixtures, (max_len, M, 1, V)
+        for the G * M member-major rows of img_input, a0, c0; the guided distributions.  With consensus or guidance a fed
+        0 masks the next LSTM step on every member."""
         probs_all, _ = self._decode(img_input, a0, c0, start_seq, max_len, None, constraints, consensus, guidance)
         return probs_all[:, :, :self.V].cpu().numpy()[:, :, None, :]
 
@@ -952,12 +941,8 @@ class NIC(ModelBase):
         The draw is the Philox stream (seed, S_SAMPLE + position, sample_step), as in lc_nic.NIC.sample_predict.  A
         sampled id 0 masks the following LSTM step exactly as a greedy 0 does.  The decode is captured and replayed like
         greedy_predict; sample_step reaches the replay through a device word.
-        ``constraints`` as in greedy_predict: the draw is from the constrained distribution, which is also what ``probs``
-        holds then.
-        ``consensus`` as in greedy_predict: the draw is from the mixture of the G members (row m on the Philox stream row m
-        of a plain decode of M scans uses) and is fed to all of them; ids and probs are per image (M rows).
-        ``guidance`` as in greedy_predict: the draw is from the guided distribution (row b on the Philox stream row b of a
-        plain decode uses) and is fed to the scan's row and its null row; ``probs`` holds the guided distributions.
+        ``constraints``, ``consensus``, ``guidance`` as in greedy_predict: the draw is from the constrained, mixed or guided
+        distribution, which is also what ``probs`` holds then; with consensus ids and probs are per image (M rows).
         Returns (ids (B, max_len, 1) int64, probs (max_len, B, 1, V))."""
         top_k, top_p, temperature = check_sampling(top_k, top_p, temperature)
         probs_all, ids = self._decode(img_input, a0, c0, start_seq, max_len, (temperature, top_k, top_p, int(sample_step)),
@@ -989,48 +974,18 @@ class NIC(ModelBase):
 
     def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
-        sample_step)); returns the device buffers (probs (max_len, B, ldV), ids (max_len, B) int32 or None).  With
-        constraints on (ModelBase._constrain) the greedy loop keeps its ids per step too: the history is built from them.
-        With consensus on (ModelBase._consensus) the decoder runs the G * M member rows, probs holds the M mixtures per
-        step and ids the common word on every member row.  With guidance on (ModelBase._guidance) the same helper runs
-        the two members (scans, null scans) with tnt_guidance_mix_f32 as its mix launch."""
+        sample_step)); returns the device buffers (probs (max_len, M, ldV), ids (max_len, B) int32) of the step's choice
+        (model_base._TokenChoice).  With consensus or guidance on (ModelBase._decode_setup) the decoder runs the B = G * M
+        member rows, probs holds the M mixtures per step and ids the common word on every member row."""
         be, a = self.be, self.arena
-        start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], consensus=consensus)
-        if guide is not None:
-            cons, img_input, a0, c0 = guide
-        else:
-            cons = self._consensus(consensus, img_input, start.shape[0])
-        if cons is not None:
-            start = start.repeat(cons.G)
-        B = start.shape[0]
-        con = self._constrain(constraints, B, max_len)
+        cons, (img_input, a0, c0), start, _, _, B, con, _, ckey = self._decode_setup(
+            guidance, consensus, constraints, None, img_input, a0, c0, start_seq, max_len)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
         # static decode buffers per (B, max_len): the whole loop is one captured hipGraph
-        key = (B, max_len)
-        bufs = self.__dict__.setdefault("_dec_bufs", {})
-        if cons is not None:                           # the helper's own buffers: the mixtures are M rows per step, not B
-            cb = cons.bufs(max_len, max_len)
-            start_buf, words, probs_all = cb["start"], None, cb["mix"]
-        else:
-            if key not in bufs:
-                bufs[key] = (torch.zeros(B, 1, dtype=torch.int32, device=self.device),
-                             torch.zeros(B, 1, dtype=torch.int32, device=self.device),
-                             torch.zeros(max_len, B, ldV, dtype=torch.float32, device=self.device))
-            start_buf, words, probs_all = bufs[key]
-        start_buf.copy_(start.view(B, 1))
-        ids = None
-        if cons is not None:
-            ids = cb["ids"]
-        elif filt is not None or con is not None:
-            sbufs = self.__dict__.setdefault("_sample_ids", {})
-            if key not in sbufs:
-                sbufs[key] = torch.zeros(max_len, B, dtype=torch.int32, device=self.device)
-            ids = sbufs[key]
-        if filt is not None:
-            step_buf = self._sample_step_word(filt[3])
+        choice = _TokenChoice(self, B, max_len, filt, con, cons)
+        choice.start.copy_(start.view(B, 1))
 
         def run():
             self._decode_encode(B)
@@ -1040,41 +995,22 @@ class NIC(ModelBase):
             c = [self.Cs[0], self.Cs[1]]
             cur = 1
             out = self.Out[0]
-            prev = words
+            words = choice.start
             for i in range(max_len):
-                tok = start_buf if i == 0 else prev
-                be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, B, 1, E, E, V)
+                be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, B, 1, E, E, V)
                 self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-                be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, prev if i > 0 else None, 1, 0, None,
+                be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, words if i > 0 else None, 1, 0, None,
                                  h[1 - cur], c[1 - cur], out, self.gates[0], B, U)
                 cur = 1 - cur
-                logits = probs_all[i] if cons is None else cb["logits"]
+                logits = choice.logits(i)
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), logits, B, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
-                if con is not None:
-                    con.step(i, logits, ldV, prev if i > 0 else None)
-                if cons is not None:                   # mix (+ argmax, or draw + spread) in the place of softmax + argmax
-                    cons.choose(logits, probs_all[i], cb["pick"][i], ids[i], None if filt is None else (
-                        lambda p, out, rows, i=i: be.sample_topkp(p, out, rows, V, ldV, filt[0], filt[1], filt[2], False,
-                                                                  self.seed, S_SAMPLE + i, 0, step_buf)))
-                    prev = ids[i].view(B, 1)
-                    continue
-                be.softmax_cce(probs_all[i], None, probs_all[i], None, None, None, B, V, ldV, 0.0)
-                if filt is None and con is None:
-                    be.argmax_rows(probs_all[i], words, B, V, ldV)
-                elif filt is None:
-                    be.argmax_rows(probs_all[i], ids[i], B, V, ldV)
-                    prev = ids[i].view(B, 1)
-                else:
-                    be.sample_topkp(probs_all[i], ids[i], B, V, ldV, filt[0], filt[1], filt[2], False, self.seed,
-                                    S_SAMPLE + i, 0, step_buf)
-                    prev = ids[i].view(B, 1)
-        ckey = (con.key if con is not None else ()) + (cons.key if cons is not None else ())
+                words = choice.step(i, logits, words)
         if filt is None:
-            self._run_captured(("greedy",) + key + ckey, run)
+            self._run_captured(("greedy", B, max_len) + ckey, run)
         else:
-            self._run_captured(("sample",) + key + tuple(filt[:3]) + ckey, run)
-        return probs_all, ids
+            self._run_captured(("sample", B, max_len) + tuple(filt[:3]) + ckey, run)
+        return choice.probs, choice.ids
 
     # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
     def _score_refuse(self):
@@ -1141,46 +1077,23 @@ class NIC(ModelBase):
         (expansion + reorder of the state by parent into the other state buffer).  The loop is captured and replayed
         like greedy_predict, over static buffers of its own per (B, k, max_len, end_id); the paths are back-tracked on
         the host from one copy of the parents / tokens.
-        ``constraints`` (model_base.DecodeConstraints): each live beam row's logits are constrained from the row's own path
-        (one tnt_decode_constrain_f32 launch per token in front of the softmax, which also carries the history across the
-        beam reorder), so the scores are sums of constrained log-probabilities; min_length uses ``end_id`` unless the
-        object names its own (the two must agree).  None or a neutral object: the search as it is without the keyword.
-        ``consensus`` (model_base.Consensus(members=G, ...)): the beams of image m are scored by the mixture of its G scans.
-        The inputs hold G * M rows, member-major, start_seq M entries; the decoder rows are [G][M][k].  Per token one
-        tnt_consensus_mix_f32 launch takes the softmax's place, tnt_beam_step_f32 expands the M * k mixed rows (U = 0: no
-        fused reorder), one tnt_consensus_spread_i32 launch carries token, parent and finished flag to the member rows,
-        and the state is gathered by the spread parents.  Sequences and scores are per image: (M, k, max_len), (M, k).
-        ``diversity`` (model_base.BeamDiversity(groups=Gd, penalty=lambda)): diverse beam search.  The k beams of a sample
-        search as Gd groups of k' = k / Gd; one tnt_beam_step_diverse_f32 launch takes tnt_beam_step_f32's place (with
-        consensus too, on the M * k mixed rows), and every group starts from its own copy of the start state.  The
-        results are group-major: group g's k' results sit best first at slots g*k' .. g*k' + k' - 1 (the group index of
-        the k slots is np.repeat(np.arange(Gd), k')), group 0 is the plain search of width k', and ``length_penalty``
-        reorders within a group only.  The scores stay sums of log-probabilities.  ``constraints`` composes unchanged.
-        None or groups = 1: the search as it is without the keyword.
-        ``guidance`` (model_base.Guidance(scale, null, plausibility)): classifier-free guidance.  The decoder rows are
-        [2][B][k], the scans' beams and behind them the null scans'; per token one tnt_guidance_mix_f32 launch takes the
-        softmax's place and the search runs on the B * k guided rows exactly as a consensus of two members does (spread,
-        state gather by the spread parents), so the scores are sums of guided log-probabilities.  ``constraints``
-        composes; consensus and diverse beams do not.  None or a neutral object: the search as it is without the keyword.
+        ``constraints``, ``consensus``, ``diversity``, ``guidance``: model_base.DecodeConstraints, Consensus, BeamDiversity
+        and Guidance, whose docstrings define them.  Here the expansion on the mixed rows of consensus or guidance is
+        tnt_beam_step_f32 with U = 0 (no fused reorder), the state being gathered by the spread parents, and with
+        diversity tnt_beam_step_diverse_f32 takes tnt_beam_step_f32's place on the same arguments.  With consensus the
+        inputs hold G * M rows, member-major, start_seq M entries, and sequences and scores are per image: (M, k,
+        max_len), (M, k).
         Returns (sequences (B, k, max_len) int64, best first; scores (B, k) float32 = sum of log-probabilities, or the
         length-normalised key)."""
         k, max_len, end_id, length_penalty = check_beam(beam_width, max_len, end_id, length_penalty, self.V)
         be, a = self.be, self.arena
-        start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
-        div = self._diversity(diversity, k)
-        guide = self._guidance(guidance, img_input, a0, c0, start.shape[0], k, consensus, div)
-        if guide is not None:
-            cons, img_input, a0, c0 = guide
-        else:
-            cons = self._consensus(consensus, img_input, start.shape[0], k)
-        G = cons.G if cons is not None else 1
-        M = start.shape[0]                             # captions: the expansion runs on M * k rows
-        B = G * M                                      # staged scans: the decoder runs B * k rows, with consensus [G][M][k]
-        con = self._constrain(constraints, B * k, max_len, k, end_id)
+        # M captions: the expansion runs on M * k rows; B = G * M staged scans: the decoder runs B * k rows, [G][M][k]
+        cons, (img_input, a0, c0), start, M, G, B, con, div, ckey = self._decode_setup(
+            guidance, consensus, constraints, diversity, img_input, a0, c0, start_seq, max_len, k, end_id)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
         U, E, V, ldV = self.U, self.E, self.V, self.ldV
-        Bk, Mk = B * k, M * k
+        Bk = B * k
         key = (B, k, max_len, end_id) if cons is None else (B, k, max_len, end_id, G)
         bufs = self.__dict__.setdefault("_beam_bufs", {})
         if key not in bufs:
@@ -1188,27 +1101,19 @@ class NIC(ModelBase):
             bufs[key] = dict(
                 rep=torch.arange(B, dtype=i32, device=dev).repeat_interleave(k).view(Bk, 1),
                 start=torch.zeros(Bk, 1, dtype=i32, device=dev),
-                score=f(2, Mk), fin=f(2, Mk, dtype=i32), pt=f(2, max_len, Mk, dtype=i32),
                 h=f(2, Bk, U), c=f(2, Bk, U), emb=f(Bk, E), xz=f(Bk, U, 4), out=f(Bk, U), gates=f(Bk, U, 4),
                 probs=f(Bk, ldV))
         bb = bufs[key]
-        Gd = div[0] if div is not None else 1
-        init = "init" if div is None else ("init", Gd)
-        if init not in bb:                         # step 0: only the first beam of the sample, or of every group, counts
-            bb[init] = torch.from_numpy(beam_init_scores(M, k, Gd)).to(self.device)
-        bb["start"].copy_((start if cons is None else start.repeat(G)).repeat_interleave(k).view(Bk, 1))
-        bb["score"][0].copy_(bb[init])
-        bb["fin"][0].zero_()
-        score, fin, parents, tokens = bb["score"], bb["fin"], bb["pt"][0], bb["pt"][1]
+        bb["start"].copy_(start.repeat_interleave(k).view(Bk, 1))
         h, c, emb, xz, out, probs = bb["h"], bb["c"], bb["emb"], bb["xz"], bb["out"], bb["probs"]
-        # what the decoder rows read back: the expansion's own outputs or, with consensus, their spread to the member rows
-        tok_d, par_d, fin_d = tokens, parents, fin
-        if cons is not None:
-            cb = cons.bufs(max_len, 1)
-            mix, tok_d, par_d, fin_d = cb["mix"][0], cb["ids"], cb["par"], (cb["fin"], cb["fin"])
-            cb["fin"].zero_()
-        # the expansion launch: tnt_beam_step_f32, or with diversity tnt_beam_step_diverse_f32 on the same arguments
-        expand = be.beam_step if div is None else (lambda *args: be.beam_step_diverse(*args, *div))
+        # the expansion launch: tnt_beam_step_f32, or with diversity tnt_beam_step_diverse_f32 on the same arguments.  It
+        # also carries the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]; not on the mixed rows of a
+        # member helper (U = 0), whose member rows gather their state by their own parent rows
+        fused = cons is None
+        state = (h[1], c[1], U, U, h[0], c[0]) if fused else (None, None, 0, 0, None, None)
+        launch, tail = (be.beam_step, state) if div is None else (be.beam_step_diverse, state + div)
+        expand = lambda p, score_in, fin_in, *outs: launch(p, ldV, score_in, fin_in, M, V, k, end_id, *outs, *tail)
+        beam = _BeamDecode(self, M, k, max_len, end_id, expand, con, cons, div, bb)
 
         def run():
             self._decode_encode(B)
@@ -1216,37 +1121,17 @@ class NIC(ModelBase):
             # the B rows' state after the feature step -> the B*k beam rows (row gather b*k + j <- b)
             be.embedding_fwd(self.Hs[1], bb["rep"], h[0], Bk, 1, U, U, B)
             be.embedding_fwd(self.Cs[1], bb["rep"], c[0], Bk, 1, U, U, B)
+            words = bb["start"]
             for i in range(max_len):
-                tok = bb["start"] if i == 0 else tok_d[i - 1].view(Bk, 1)
-                be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, Bk, 1, E, E, V)
+                be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, Bk, 1, E, E, V)
                 self.gemm_sk(emb, Wl, xz, Bk, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-                be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, tok if i > 0 else None, 1, 0, None,
+                be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, words if i > 0 else None, 1, 0, None,
                                  h[1], c[1], out, bb["gates"], Bk, U)
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, Bk, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
-                cur, nxt = i & 1, (i & 1) ^ 1
-                if con is not None:
-                    con.step(i, probs, ldV, tok_d[i - 1] if i > 0 else None, par_d[i - 1] if i > 0 else None, fin_d[cur])
-                if cons is not None:
-                    # the mixture in the softmax's place; the expansion on the M*k mixed rows without its fused reorder; its
-                    # choice spread to the member rows; every member's state (h[1], c[1]) gathered by its own parent rows
-                    cons.mix(probs, mix)
-                    expand(mix, ldV, score[cur], fin[cur], M, V, k, end_id, score[nxt], parents[i], tokens[i],
-                           fin[nxt], None, None, 0, 0, None, None)
-                    cons.spread(tokens[i], parents[i], fin[nxt], tok_d[i], par_d[i], fin_d[nxt])
-                    be.embedding_fwd(h[1], par_d[i].view(Bk, 1), h[0], Bk, 1, U, U, Bk)
-                    be.embedding_fwd(c[1], par_d[i].view(Bk, 1), c[0], Bk, 1, U, U, Bk)
-                    continue
-                be.softmax_cce(probs, None, probs, None, None, None, Bk, V, ldV, 0.0)
-                # expansion, and the surviving beams' state (h[1], c[1] by parent) back into h[0], c[0]
-                expand(probs, ldV, score[cur], fin[cur], B, V, k, end_id, score[nxt], parents[i], tokens[i],
-                       fin[nxt], h[1], c[1], U, U, h[0], c[0])
-        ckey = ((con.key if con is not None else ()) + (cons.key if cons is not None else ())
-                + (("diverse",) + div if div is not None else ()))
+                words, par = beam.step(i, probs)
+                if not fused:
+                    be.embedding_fwd(h[1], par, h[0], Bk, 1, U, U, Bk)
+                    be.embedding_fwd(c[1], par, c[0], Bk, 1, U, U, Bk)
         self._run_captured(("beam",) + key + ckey, run)
-        pt = bb["pt"].cpu().numpy()
-        final = score[max_len & 1].cpu().numpy().reshape(M, k)
-        seqs = beam_backtrack(pt[0], pt[1], M, k)
-        if length_penalty > 0:
-            return length_normalise(seqs, final, end_id, length_penalty, Gd)
-        return seqs, final
+        return beam.finish(length_penalty)
