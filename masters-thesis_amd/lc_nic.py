@@ -519,32 +519,77 @@ class NIC(ModelBase):
                          self.ctx_d[i], Wl[:D], D, None, 0, 0, None, self.Hs[i + 1], self.Cs[i + 1], None,
                          self.gates[i], B, U, xz_bias=xz_bias)
 
+    def _token_step(self, i, words, B, logits, s_out=None):
+        """this model's half of decoded token i (lc_NIC.py:596-623): the Embedding of the B fed ``words``, the text half of
+        the input projection, attention -> LSTM step in inference mode, the head into ``logits``"""
+        be, a = self.be, self.arena
+        D, U, Et = self.D, self.U, self.Et
+        rows = slice(i * B, (i + 1) * B)
+        be.embedding_fwd(a.p("emb_text/embeddings"), words, self.text[rows], B, 1, Et, Et, self.V)
+        self.gemm_sk(self.text[rows], a.p("lstm/kernel")[D:], self.XZ[rows], B, 4 * U, Et, Et, 4 * U, 4 * U,
+                     bias=None if self.use_layer_norm else a.p("lstm/bias"))      # LN cell: bias behind the norms
+        self._decode_step(i, B, False, s_out)
+        self._head_inter(self.Hs[i + 1], self.inter[:B], B)
+        self._head_out(self.inter[:B], logits, B)
+
+    def _text_front(self, B, T, training, fed=None):
+        """The text front of a forward pass (lc_NIC.py:233 and the Dropouts behind it): the Embedding of all T caption
+        columns, the text Dropout, the text half of the per-call LSTM input mask over (B, 1, D + Et), the text half of the
+        input projection into XZ (one epilogue-free GEMM; the bias is added in the step kernel), the stored attention
+        keep-masks.  ``fed``: None = teacher-forced, "ss" = scheduled sampling (always training), "naive" = free-running.
+        Embedding + text Dropout are one launch when training with r_text > 0 and Et % 4 == 0 (_ss_check / _naive_check
+        guarantee the layout); the LSTM input mask rides in it when the fed modes have r_lstm > 0, and teacher-forced
+        only with `fused_text_masks` (D % 4 == 0 holds by construction), which the fed modes do not consult.  Otherwise
+        the text Dropout covers all n = T*B rows, geometry (B, Et, 0), and the LSTM input mask all n rows with
+        rows_per_site=B -- free-running: step 0's B rows only, without rows_per_site.  XZ is projected for all n rows
+        teacher-forced, for step 0's B rows in the fed modes: their feedback launches write the later rows of ``text``
+        and ``XZ``.  The keep-masks are generated here unless a training step staged them with its batch, outside the
+        captured sequence (_stage_mask_job)."""
+        be, a = self.be, self.arena
+        D, U, Et, V = self.D, self.U, self.Et, self.V
+        n = T * B
+        sd, ds = self.seed, self.drop_step
+        emb = a.p("emb_text/embeddings")
+        lstm_in_mask = training and self.r_lstm > 0 and not self.use_layer_norm
+        if training and self.r_text > 0 and Et % 4 == 0:
+            ride = lstm_in_mask and (fed is not None or (D % 4 == 0 and getattr(self, "fused_text_masks", True)))
+            be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
+                                  mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if ride else None)
+            lstm_in_mask = lstm_in_mask and not ride
+        else:
+            be.embedding_fwd(emb, self.cap, self.text, B, T, Et, Et, V)
+            if training and self.r_text > 0:
+                be.dropout(self.text, self.text, n, Et, Et, B, Et, 0, self.r_text, sd, S_TEXT, 0, ds)
+        if lstm_in_mask and fed == "naive":
+            be.dropout(self.text, self.text, B, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds)
+        elif lstm_in_mask:
+            be.dropout(self.text, self.text, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds, rows_per_site=B)
+        m = n if fed is None else B
+        self.gemm_sk(self.text[:m], a.p("lstm/kernel")[D:], self.XZ[:m], m, 4 * U, Et, Et, 4 * U, 4 * U)
+        if training and self._keep_stored and not self.__dict__.get("_masks_staged"):
+            be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
+
+    def _head_inter(self, h, inter, n, ipre=None):
+        """dense_inter over n rows (lc_NIC.py:141,258): inter = LeakyReLU(h W + b); ``ipre`` keeps the pre-activation
+        for the backward pass (None: the inference form)"""
+        a, U, H = self.arena, self.U, self.H
+        self.gemm_sk(h, a.p("time_distributed_nonlinear/kernel"), inter, n, H, U, U, H, H,
+                     bias=a.p("time_distributed_nonlinear/bias"), pre=ipre, act=ACT_LEAKY, slope=0.2)
+
+    def _head_out(self, inter, logits, n):
+        """dense_out over n rows (lc_NIC.py:261): the logits; the softmax is the caller's"""
+        a, V, H, ldV = self.arena, self.V, self.H, self.ldV
+        self.gemm_sk(inter, a.p("time_distributed_softmax/kernel"), logits, n, V, H, H, ldV, ldV,
+                     bias=a.p("time_distributed_softmax/bias"))
+
     def _forward(self, B, T, training):
         be, a = self.be, self.arena
-        R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
+        R, D, A, U, Et, H = self.R, self.D, self.A, self.U, self.Et, self.H
         n = T * B
         sd, ds = self.seed, self.drop_step
         self._encode(B, training)
-        lstm_in_mask = training and self.r_lstm > 0 and not self.use_layer_norm
-        if training and self.r_text > 0 and Et % 4 == 0:     # lc_NIC.py:233 + its Dropout in one launch
-            # ... and the text half of the per-call LSTM input mask over (B, 1, D + Et) behind it, when the layout allows
-            ride = lstm_in_mask and D % 4 == 0 and getattr(self, "fused_text_masks", True)
-            be.embedding_fwd_drop(a.p("emb_text/embeddings"), self.cap, None, self.text, B, T, Et, Et, V, self.r_text,
-                                  sd, S_TEXT, 0, ds, mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if ride else None)
-            lstm_in_mask = lstm_in_mask and not ride
-        else:
-            be.embedding_fwd(a.p("emb_text/embeddings"), self.cap, self.text, B, T, Et, Et, V)       # lc_NIC.py:233
-            if training and self.r_text > 0:
-                be.dropout(self.text, self.text, n, Et, Et, B, Et, 0, self.r_text, sd, S_TEXT, 0, ds)
-        if lstm_in_mask:                                                   # text half of the per-call LSTM input mask over (B,1,D+Et)
-            be.dropout(self.text, self.text, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds,
-                       rows_per_site=B)
+        self._text_front(B, T, training)
         Wl = a.p("lstm/kernel")
-        # text half of the input projection for all T steps: one epilogue-free GEMM; bias added in the step kernel
-        self.gemm_sk(self.text, Wl[D:], self.XZ, n, 4 * U, Et, Et, 4 * U, 4 * U)
-        if training and self._keep_stored and not self.__dict__.get("_masks_staged"):
-            # (a training step has them generated with its batch staging, outside the captured sequence: _stage_mask_job)
-            be.dropout_mask4(self.att_keep, B * R * A, T, self.r_attn, sd, S_ATTN, 0, ds)
         if self._lc_seq_ok():
             # the T attention -> LSTM steps as ONE persistent launch (tnt_lc_seq_fwd_f32), XCD-local data-polling hand-offs
             r_in = self.r_lstm if training else 0.0
@@ -569,8 +614,7 @@ class NIC(ModelBase):
             be.dropout(hs, self.Hd, n, U, U, 0, U, 0, self.r_lstm, sd, S_LSTM_OUT, 0, ds, rows_per_site=B)
             hs = self.Hd
         self._hs_used = hs
-        self.gemm_sk(hs, a.p("time_distributed_nonlinear/kernel"), self.inter, n, H, U, U, H, H,
-                bias=a.p("time_distributed_nonlinear/bias"), pre=self.ipre, act=ACT_LEAKY, slope=0.2)
+        self._head_inter(hs, self.inter, n, self.ipre)
         inter = self.inter
         self._metric_parts_ready = False
         if training and self.r_out > 0:
@@ -585,8 +629,7 @@ class NIC(ModelBase):
                 be.dropout(self.inter, self.inter_d, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds)
             inter = self.inter_d
         self._inter_used = inter
-        self.gemm_sk(inter, a.p("time_distributed_softmax/kernel"), self.logits, n, V, H, H, ldV, ldV,
-                bias=a.p("time_distributed_softmax/bias"))                                     # :261
+        self._head_out(inter, self.logits, n)
 
     def _naive_check(self):
         """the combinations the free-running decoder is built for; anything else refuses instead of running another mode"""
@@ -629,21 +672,8 @@ class NIC(ModelBase):
         D, U, Et, V, H, ldV = self.D, self.U, self.Et, self.V, self.H, self.ldV
         sd, ds = self.seed, self.drop_step
         self._encode(B, True)
+        self._text_front(B, T, True, "ss")
         emb, Wl = a.p("emb_text/embeddings"), a.p("lstm/kernel")
-        lstm_in = self.r_lstm > 0
-        if self.r_text > 0:            # (D % 16 == 0: the LSTM input mask always rides in the Embedding launch)
-            be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
-                                  mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if lstm_in else None)
-        else:
-            be.embedding_fwd(emb, self.cap, self.text, B, T, Et, Et, V)
-            if lstm_in:
-                be.dropout(self.text, self.text, T * B, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds,
-                           rows_per_site=B)
-        self.gemm_sk(self.text[:B], Wl[D:], self.XZ[:B], B, 4 * U, Et, Et, 4 * U, 4 * U)
-        if self._keep_stored and not self.__dict__.get("_masks_staged"):
-            be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
-        Wi, bi = a.p("time_distributed_nonlinear/kernel"), a.p("time_distributed_nonlinear/bias")
-        Wo, bo = a.p("time_distributed_softmax/kernel"), a.p("time_distributed_softmax/bias")
         for t in range(T):
             rows = slice(t * B, (t + 1) * B)
             self._decode_step(t, B, True, xz_bias=a.p("lstm/bias"))
@@ -651,12 +681,12 @@ class NIC(ModelBase):
             if self.r_lstm > 0:                                     # :256, site S_LSTM_OUT + t on the step's B rows
                 be.dropout(h, self.Hd[rows], B, U, U, 0, U, 0, self.r_lstm, sd, S_LSTM_OUT + t, 0, ds)
                 h = self.Hd[rows]
-            self.gemm_sk(h, Wi, self.inter[rows], B, H, U, U, H, H, bias=bi, pre=self.ipre[rows], act=ACT_LEAKY, slope=0.2)
+            self._head_inter(h, self.inter[rows], B, self.ipre[rows])
             inter = self.inter[rows]
             if self.r_out > 0:                                      # element (b*T + t)*H + j of the logical (B, T, H)
                 be.dropout(inter, self.inter_d[rows], B, H, H, 0, T * H, t * H, self.r_out, sd, S_OUT, 0, ds)
                 inter = self.inter_d[rows]
-            self.gemm_sk(inter, Wo, self.logits[rows], B, V, H, H, ldV, ldV, bias=bo)
+            self._head_out(inter, self.logits[rows], B)
             if t + 1 < T:
                 col, nxt = t + 1, slice((t + 1) * B, (t + 2) * B)
                 be.scheduled_feedback2(self.logits[rows], ldV, V, emb, Et, Wl[D:], 4 * U, 4 * U, self.cap, T, col,
@@ -676,23 +706,14 @@ class NIC(ModelBase):
         of the next step's input projection).  The fed ids go to column i + 1 of ``self.cap`` in place: column 0 keeps
         the staged start token, and the backward pass scatters the Embedding gradient to exactly these ids."""
         be, a = self.be, self.arena
-        D, U, Et, V, H, ldV = self.D, self.U, self.Et, self.V, self.H, self.ldV
+        D, U, Et, V, ldV = self.D, self.U, self.Et, self.V, self.ldV
         sd, ds = self.seed, self.drop_step
         self._encode(B, training, feat2=True)                                               # :180-184
-        emb, Wl = a.p("emb_text/embeddings"), a.p("lstm/kernel")
-        lstm_in = training and self.r_lstm > 0
         # step 0's input: the start token through the Embedding, the text Dropout (:187-189) and step 0's LSTM input mask,
         # as the teacher-forced step forms it (one launch over all T caption columns; rows 1.. are replaced by the fed ones)
-        if training and self.r_text > 0:
-            be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
-                                  mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if lstm_in else None)
-        else:
-            be.embedding_fwd(emb, self.cap, self.text, B, T, Et, Et, V)
-            if lstm_in:
-                be.dropout(self.text, self.text, B, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds)
-        self.gemm_sk(self.text[:B], Wl[D:], self.XZ[:B], B, 4 * U, Et, Et, 4 * U, 4 * U)
-        if training and self._keep_stored and not self.__dict__.get("_masks_staged"):
-            be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
+        self._text_front(B, T, training, "naive")
+        emb, Wl = a.p("emb_text/embeddings"), a.p("lstm/kernel")
+        lstm_in = training and self.r_lstm > 0
         r_lo, r_o = (self.r_lstm, self.r_out) if training else (0.0, 0.0)
         for i in range(T):                                                                  # :191-219
             rows = slice(i * B, (i + 1) * B)
@@ -704,10 +725,8 @@ class NIC(ModelBase):
                 be.dropout(h, self.Hd[rows], B, U, U, 0, U, 0, max(r_lo, r_o), sd, S_LSTM_OUT + i if r_lo > 0 else S_NOUT + i, 0, ds)
             if r_lo > 0 or r_o > 0:
                 h = self.Hd[rows]
-            self.gemm_sk(h, a.p("time_distributed_nonlinear/kernel"), self.inter[rows], B, H, U, U, H, H,
-                         bias=a.p("time_distributed_nonlinear/bias"), pre=self.ipre[rows], act=ACT_LEAKY, slope=0.2)   # :209
-            self.gemm_sk(self.inter[rows], a.p("time_distributed_softmax/kernel"), self.logits[rows], B, V, H, H, ldV, ldV,
-                         bias=a.p("time_distributed_softmax/bias"))                                                 # :211
+            self._head_inter(h, self.inter[rows], B, self.ipre[rows])                       # :209
+            self._head_out(self.inter[rows], self.logits[rows], B)                          # :211
             if i + 1 < T:                                                                   # :215-217
                 nxt = slice((i + 1) * B, (i + 2) * B)
                 be.greedy_feedback(self.logits[rows], ldV, V, emb, Et, Wl[D:], 4 * U, 4 * U, self.cap, T, i + 1, self.text[nxt],
@@ -757,23 +776,26 @@ class NIC(ModelBase):
     def _backward(self, B, T):
         """tape.gradient (lc_NIC.py:386-387) as four launch groups, in the order the gradients become final -- the
         data-parallel schedule (dp.PipelinedAttentionSync) issues one all-reduce bucket after each."""
-        naive = not self.teacher_forcing       # the free-running step: its own head and text branch, the same chain
-        (self._bwd_head_naive if naive else self._bwd_head)(B, T)
+        self._bwd_head(B, T)
         self._bwd_chain(B, T)
         # the text branch (input Dropout', sparse Embedding scatter) and the front branch (attention parameters, BatchNorm,
         # region-wise encoder) only share the chain's outputs: with `branch_streams` they are two parallel branches of the step
         with self.side(0 if getattr(self, "branch_streams", False) else -1):
-            (self._bwd_emb_naive if naive else self._bwd_emb)(B, T)
+            self._bwd_emb(B, T)
         self._bwd_front(B, T)
         self.join()
 
     def _bwd_head(self, B, T):
-        """vocabulary head: gradients of time_distributed_softmax / time_distributed_nonlinear, dHs."""
+        """vocabulary head: gradients of time_distributed_softmax / time_distributed_nonlinear, dHs.  The free-running
+        step (teacher_forcing=False) has no Dropout between dense_inter and dense_out: its fused tail runs at rate 0 and
+        whatever `fused_head_tail` says, and the LSTM-output and the output Dropout' both act on dHs (lc_NIC.py:205-211)."""
         be, a = self.be, self.arena
         U, V, H, ldV = self.U, self.V, self.H, self.ldV
         n = T * B
         sd, ds = self.seed, self.drop_step
-        dlog, inter, hs = self.logits, self._inter_used, self._hs_used
+        naive = not self.teacher_forcing
+        dlog, inter, hs = self.logits, self._inter_used, self._hs_used         # (free-running: _inter_used is self.inter)
+        tB, r_tail = (0, 0.0) if naive else (B, self.r_out)
         dhs_done = False
         # kernel gradient and input gradient of the softmax layer, the two independent readers of dlogits: ONE launch
         if not (getattr(self, "g3_riders", True) and self.gemm3_pair(
@@ -782,11 +804,12 @@ class NIC(ModelBase):
                      transB=True))):
             self.gemm_sk(inter, dlog, a.g("time_distributed_softmax/kernel"), H, V, n, H, ldV, ldV, transA=True)
             self.gemm_sk(dlog, a.p("time_distributed_softmax/kernel"), self.dinter, n, H, V, ldV, ldV, H, transB=True)
-        if getattr(self, "fused_head_tail", True) and hasattr(be, "bias_act_drop_bwd") and n <= 2048 and H % 4 == 0:
+        if ((naive or getattr(self, "fused_head_tail", True)) and hasattr(be, "bias_act_drop_bwd") and n <= 2048
+                and H % 4 == 0):
             # dropout' + LeakyReLU' + the nonlinear layer's bias gradient in one pass over dinter, with the softmax layer's
             # bias gradient (column sums of dlogits) riding in the same launch: 1 launch instead of 4
             be.bias_act_drop_bwd(self.dinter, self.ipre, self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H,
-                                 ACT_LEAKY, 0.2, B, H, 0, self.r_out, sd, S_OUT, ds,
+                                 ACT_LEAKY, 0.2, tB, H, 0, r_tail, sd, S_OUT, ds,
                                  extra=(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV))
             # kernel gradient and input gradient of the nonlinear layer, the two readers of dinter: ONE launch
             if getattr(self, "g3_riders", True) and self.gemm3_pair(
@@ -799,16 +822,25 @@ class NIC(ModelBase):
                 self.gemm_sk(hs, self.dinter, a.g("time_distributed_nonlinear/kernel"), U, H, n, U, H, H, transA=True)
         else:
             be.colsum(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV, self.work)
-            if self.r_out > 0:
-                be.dropout(self.dinter, self.dinter, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds)
+            if r_tail > 0:
+                be.dropout(self.dinter, self.dinter, n, H, H, B, H, 0, r_tail, sd, S_OUT, 0, ds)
             be.act_bwd(self.ipre, self.dinter, self.dinter, n * H, ACT_LEAKY, 0.2)
             self.gemm_sk(hs, self.dinter, a.g("time_distributed_nonlinear/kernel"), U, H, n, U, H, H, transA=True)
             be.colsum(self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H, self.work)
         if not dhs_done:
             self.gemm_sk(self.dinter, a.p("time_distributed_nonlinear/kernel"), self.dHs, n, U, H, H, H, U, transB=True)
-        self._dout_masked = not (self.r_lstm > 0 and self._lc_seq_bwd_ok() and (int(getattr(self, "fuse_out_drop", 3)) & 2))
-        if self.r_lstm > 0 and self._dout_masked:           # (else Dropout' rides in the backward chain: tnt_lc_seq_bwd_drop_f32)
-            be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, self.r_lstm, sd, S_LSTM_OUT, 0, ds, rows_per_site=B)
+        r_lo, r_o = self.r_lstm, self.r_out
+        if not naive:
+            self._dout_masked = not (r_lo > 0 and self._lc_seq_bwd_ok() and (int(getattr(self, "fuse_out_drop", 3)) & 2))
+            if r_lo > 0 and self._dout_masked:              # (else Dropout' rides in the backward chain: tnt_lc_seq_bwd_drop_f32)
+                be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, r_lo, sd, S_LSTM_OUT, 0, ds, rows_per_site=B)
+            return
+        self._dout_masked = True            # both masks are applied here, none rides in the backward chain
+        if r_lo > 0 and r_o > 0:
+            be.dropout2(self.dHs, self.dHs, n, U, U, (0, U, 0, B, r_lo, S_LSTM_OUT), (0, U, 0, B, r_o, S_NOUT), sd, 0, ds)
+        elif r_lo > 0 or r_o > 0:
+            be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, max(r_lo, r_o), sd, S_LSTM_OUT if r_lo > 0 else S_NOUT, 0, ds,
+                       rows_per_site=B)
 
     def _lc_seq_bwd_ok(self):
         """the persistent backward-chain kernel applies (tnt_lc_seq_bwd_f32: the forward chain's shape limits)."""
@@ -937,16 +969,19 @@ class NIC(ModelBase):
         be.colsum(self.dZ, a.g("lstm/bias"), n, 4 * U, 4 * U, self.work)
 
     def _bwd_emb(self, B, T):
-        """text branch: dtext = dZ Wl_text^T, its dropouts, the embedding scatter (+ IndexedSlices norm)."""
+        """text branch: dtext = dZ Wl_text^T, its dropouts, the embedding scatter (+ IndexedSlices norm).  Free-running
+        (teacher_forcing=False): the LSTM input mask' on every step's text rows, the text Dropout' on step 0's only (the
+        fed tokens have none, lc_NIC.py:217), the scatter to the fed ids."""
         be, a = self.be, self.arena
         D, U, Et, V = self.D, self.U, self.Et, self.V
         n = T * B
         sd, ds = self.seed, self.drop_step
+        naive = not self.teacher_forcing
         Wl = a.p("lstm/kernel")
         if not self.__dict__.pop("_dtext_done", False):
             self.gemm_sk(self.dZK if self.use_layer_norm else self.dZ, Wl[D:], self.dtext, n, Et, 4 * U, 4 * U, 4 * U, Et, transB=True)
         lstm_in = self.r_lstm > 0 and not self.use_layer_norm
-        if (lstm_in and self.r_text > 0 and Et % 4 == 0 and D % 4 == 0 and hasattr(be, "dropout2")
+        if (not naive and lstm_in and self.r_text > 0 and Et % 4 == 0 and D % 4 == 0 and hasattr(be, "dropout2")
                 and getattr(self, "fused_text_masks", True)):
             # the LSTM input mask and the Embedding Dropout of the text rows in one pass
             be.dropout2(self.dtext, self.dtext, n, Et, Et, (0, D + Et, D, B, self.r_lstm, S_LSTM_IN),
@@ -955,64 +990,10 @@ class NIC(ModelBase):
             if lstm_in:
                 be.dropout(self.dtext, self.dtext, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds,
                            rows_per_site=B)
-            if self.r_text > 0:
+            if self.r_text > 0 and naive:      # step 0's rows of the logical (B, T, Et) mask the forward's Embedding launch applied
+                be.dropout(self.dtext[:B], self.dtext[:B], B, Et, Et, 0, T * Et, 0, self.r_text, sd, S_TEXT, 0, ds)
+            elif self.r_text > 0:
                 be.dropout(self.dtext, self.dtext, n, Et, Et, B, Et, 0, self.r_text, sd, S_TEXT, 0, ds)
-        self._emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
-        self._embedding_bwd(self.dtext, self.cap, "emb_text/embeddings", B, T, Et, Et, V)
-
-    def _bwd_head_naive(self, B, T):
-        """vocabulary head of the free-running step: no Dropout between dense_inter and dense_out; the LSTM-output and the
-        output Dropout' both act on dHs (lc_NIC.py:205-211)."""
-        be, a = self.be, self.arena
-        U, V, H, ldV = self.U, self.V, self.H, self.ldV
-        n = T * B
-        sd, ds = self.seed, self.drop_step
-        dlog, inter, hs = self.logits, self.inter, self._hs_used
-        if not (getattr(self, "g3_riders", True) and self.gemm3_pair(
-                dict(A=inter, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=H, N=V, K=n, lda=H, ldb=ldV, ldc=ldV, transA=True),
-                dict(A=dlog, B=a.p("time_distributed_softmax/kernel"), C=self.dinter, M=n, N=H, K=V, lda=ldV, ldb=ldV, ldc=H,
-                     transB=True))):
-            self.gemm_sk(inter, dlog, a.g("time_distributed_softmax/kernel"), H, V, n, H, ldV, ldV, transA=True)
-            self.gemm_sk(dlog, a.p("time_distributed_softmax/kernel"), self.dinter, n, H, V, ldV, ldV, H, transB=True)
-        dhs_done = False
-        if hasattr(be, "bias_act_drop_bwd") and n <= 2048 and H % 4 == 0:
-            # LeakyReLU' + both bias gradients in one launch (rate 0: no Dropout on this side)
-            be.bias_act_drop_bwd(self.dinter, self.ipre, self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H,
-                                 ACT_LEAKY, 0.2, 0, H, 0, 0.0, sd, S_OUT, ds,
-                                 extra=(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV))
-            dhs_done = bool(getattr(self, "g3_riders", True) and self.gemm3_pair(
-                dict(A=hs, B=self.dinter, C=a.g("time_distributed_nonlinear/kernel"), M=U, N=H, K=n, lda=U, ldb=H, ldc=H,
-                     transA=True, small=True),
-                dict(A=self.dinter, B=a.p("time_distributed_nonlinear/kernel"), C=self.dHs, M=n, N=U, K=H, lda=H, ldb=H, ldc=U,
-                     transB=True, small=True)))
-        else:
-            be.colsum(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV, self.work)
-            be.act_bwd(self.ipre, self.dinter, self.dinter, n * H, ACT_LEAKY, 0.2)
-            be.colsum(self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H, self.work)
-        if not dhs_done:
-            self.gemm_sk(hs, self.dinter, a.g("time_distributed_nonlinear/kernel"), U, H, n, U, H, H, transA=True)
-            self.gemm_sk(self.dinter, a.p("time_distributed_nonlinear/kernel"), self.dHs, n, U, H, H, H, U, transB=True)
-        self._dout_masked = True            # both masks are applied here, none rides in the backward chain
-        r_lo, r_o = self.r_lstm, self.r_out
-        if r_lo > 0 and r_o > 0:
-            be.dropout2(self.dHs, self.dHs, n, U, U, (0, U, 0, B, r_lo, S_LSTM_OUT), (0, U, 0, B, r_o, S_NOUT), sd, 0, ds)
-        elif r_lo > 0 or r_o > 0:
-            be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, max(r_lo, r_o), sd, S_LSTM_OUT if r_lo > 0 else S_NOUT, 0, ds,
-                       rows_per_site=B)
-
-    def _bwd_emb_naive(self, B, T):
-        """text branch of the free-running step: the LSTM input mask' on every step's text rows, the text Dropout' on step
-        0's only (the fed tokens have none, lc_NIC.py:217), the Embedding scatter to the fed ids."""
-        be, a = self.be, self.arena
-        D, U, Et, V = self.D, self.U, self.Et, self.V
-        n = T * B
-        sd, ds = self.seed, self.drop_step
-        if not self.__dict__.pop("_dtext_done", False):
-            self.gemm_sk(self.dZ, a.p("lstm/kernel")[D:], self.dtext, n, Et, 4 * U, 4 * U, 4 * U, Et, transB=True)
-        if self.r_lstm > 0:
-            be.dropout(self.dtext, self.dtext, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds, rows_per_site=B)
-        if self.r_text > 0:          # step 0's rows of the logical (B, T, Et) mask the forward's Embedding launch applied
-            be.dropout(self.dtext[:B], self.dtext[:B], B, Et, Et, 0, T * Et, 0, self.r_text, sd, S_TEXT, 0, ds)
         self._emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
         self._embedding_bwd(self.dtext, self.cap, "emb_text/embeddings", B, T, Et, Et, V)
 
@@ -1330,12 +1311,9 @@ class NIC(ModelBase):
         the S subject slices and G must be S) words (M, max_len, 1) and probs (M, max_len, V), the mixtures, are per
         image; with guidance words and probs, the guided distributions, are per scan.  alpha and s stay per member row,
         (max_len, G*M, R, ...), under guidance (max_len, 2*B, R, ...) with the scans' rows first."""
-        be, a = self.be, self.arena
         cons, (img_input, a0, c0), start, M, G, B, con, _, ckey = self._decode_setup(
             guidance, consensus, constraints, None, img_input, a0, c0, start_seq, max_len, training=training)
         self._stage_inputs((img_input, torch.zeros(B, max_len, dtype=torch.int32), a0, c0))
-        R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
-        Wl = a.p("lstm/kernel")
         # decode buffers are static per (B, max_len) so that the whole loop can be one captured hipGraph
         # (encoder + max_len x {embed, project, attention, LSTM step, head, softmax, argmax}: ~8 launches per token)
         choice = _TokenChoice(self, B, max_len, _filter if _filter is not None else _sample, con, cons)
@@ -1344,23 +1322,15 @@ class NIC(ModelBase):
         if return_s:
             sbufs = self.__dict__.setdefault("_dec_s", {})
             if (B, max_len) not in sbufs:
-                sbufs[B, max_len] = self._f(max_len, B, R, A)
+                sbufs[B, max_len] = self._f(max_len, B, self.R, self.A)
             s_all = sbufs[B, max_len]
 
         def run():
             self._encode(B, False)
             words = choice.start
             for i in range(max_len):
-                text = self.text[i * B:(i + 1) * B]
-                be.embedding_fwd(a.p("emb_text/embeddings"), words, text, B, 1, Et, Et, V)        # :596,632
-                self.gemm_sk(text, Wl[D:], self.XZ[i * B:(i + 1) * B], B, 4 * U, Et, Et, 4 * U, 4 * U,
-                             bias=None if self.use_layer_norm else a.p("lstm/bias"))      # LN cell: bias behind the norms
-                self._decode_step(i, B, False, s_all[i] if return_s else None)
-                self.gemm_sk(self.Hs[i + 1], a.p("time_distributed_nonlinear/kernel"), self.inter[:B], B, H, U, U, H, H,
-                             bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)     # :621
                 logits = choice.logits(i)
-                self.gemm_sk(self.inter[:B], a.p("time_distributed_softmax/kernel"), logits, B, V, H, H, ldV, ldV,
-                             bias=a.p("time_distributed_softmax/bias"))                                # :623
+                self._token_step(i, words, B, logits, s_all[i] if return_s else None)     # :596-623
                 words = choice.step(i, logits, words)                                              # :627
         key = (B, max_len, bool(return_s)) + ((G,) if cons is not None else ())
         if _filter is not None:     # the stream step is read from the step word on the device: captured like the greedy loop
@@ -1371,7 +1341,7 @@ class NIC(ModelBase):
             run()
         ids = choice.ids[:, :M]                        # member 0's rows: every member holds the common word
         out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
-        out_probs = choice.probs[:, :, :V].permute(1, 0, 2).contiguous().cpu().numpy()
+        out_probs = choice.probs[:, :, :self.V].permute(1, 0, 2).contiguous().cpu().numpy()
         # s (the dropout-free tanh activations, 44 MB at the BASELINE shape) is part of the reference's return tuple but
         # only analysis code reads it: return_s=False skips its device-to-host copy (eval_model does)
         return out_words, out_probs, self.alpha[:max_len].cpu().numpy()[..., None], (s_all.cpu().numpy() if return_s else None)
@@ -1426,7 +1396,7 @@ class NIC(ModelBase):
         input projection of the T-1 steps; the attention -> LSTM steps as the persistent chain or per step, in inference
         mode; the two head GEMMs; and tnt_caption_score_f32 on the logits (no softmax launch)."""
         be, a = self.be, self.arena
-        Rg, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
+        Rg, D, A, U, Et, V, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.ldV
         R, steps = B * Cr, T - 1
         n = steps * R
         if first:
@@ -1451,10 +1421,8 @@ class NIC(ModelBase):
                                       keep4=None)
                 be.lstm_step_fwd(xz[i * R:(i + 1) * R], hs[i], cs[i], Ur, v["ctx_d"], Wl[:D], D, None, 0, 0, None,
                                  hs[i + 1], cs[i + 1], None, v["gates"], R, U, xz_bias=bl)
-        self.gemm_sk(hs[1:].view(n, U), a.p("time_distributed_nonlinear/kernel"), v["inter"], n, H, U, U, H, H,
-                     bias=a.p("time_distributed_nonlinear/bias"), pre=v["ipre"], act=ACT_LEAKY, slope=0.2)
-        self.gemm_sk(v["inter"], a.p("time_distributed_softmax/kernel"), v["logits"], n, V, H, H, ldV, ldV,
-                     bias=a.p("time_distributed_softmax/bias"))
+        self._head_inter(hs[1:].view(n, U), v["inter"], n, v["ipre"])
+        self._head_out(v["inter"], v["logits"], n)
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
 
     def beam_search(self, img_input, a0, c0, start_seq, max_len, beam_width=5, end_id=-1, units=None, tokenizer=None,
@@ -1474,7 +1442,7 @@ class NIC(ModelBase):
         U = 0 (the state gathers stay).  With consensus the inputs hold G * M rows, member-major (with n_subjects = S: the
         S subject slices), start_seq M entries, and sequences and scores are per image."""
         length_penalty = check_length_penalty(length_penalty)
-        be, a = self.be, self.arena
+        be = self.be
         k = int(beam_width)
         # M captions: the expansion runs on M * k rows; B = G * M staged scans: the decoder runs B * k rows, [G][M][k]
         cons, (img_input, a0, c0), start, M, _, B, con, div, _ = self._decode_setup(
@@ -1483,8 +1451,7 @@ class NIC(ModelBase):
         rep = lambda t: np.repeat(np.asarray(t), k, axis=0)
         x = img_input.cpu().numpy() if isinstance(img_input, torch.Tensor) else np.asarray(img_input)
         self._stage_inputs((rep(x), torch.zeros(Bk, max_len, dtype=torch.int32), rep(np.asarray(a0)), rep(np.asarray(c0))))
-        R, D, A, U, Et, V, H, ldV = self.R, self.D, self.A, self.U, self.Et, self.V, self.H, self.ldV
-        Wl = a.p("lstm/kernel")
+        U, V, ldV = self.U, self.V, self.ldV
         probs = self.logits[:Bk]
         hg, cg = self._f(Bk, U), self._f(Bk, U)
         # the expansion launch: tnt_beam_topk_f32, or with diversity tnt_beam_step_diverse_f32 without its reorder (U = 0)
@@ -1497,15 +1464,7 @@ class NIC(ModelBase):
         self._encode(Bk, False)
         words = start.repeat_interleave(k).view(Bk, 1)
         for i in range(max_len):
-            text = self.text[i * Bk:(i + 1) * Bk]
-            be.embedding_fwd(a.p("emb_text/embeddings"), words, text, Bk, 1, Et, Et, V)
-            self.gemm_sk(text, Wl[D:], self.XZ[i * Bk:(i + 1) * Bk], Bk, 4 * U, Et, Et, 4 * U, 4 * U,
-                         bias=None if self.use_layer_norm else a.p("lstm/bias"))
-            self._decode_step(i, Bk, False, None)
-            self.gemm_sk(self.Hs[i + 1], a.p("time_distributed_nonlinear/kernel"), self.inter[:Bk], Bk, H, U, U, H, H,
-                         bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)
-            self.gemm_sk(self.inter[:Bk], a.p("time_distributed_softmax/kernel"), probs, Bk, V, H, H, ldV, ldV,
-                         bias=a.p("time_distributed_softmax/bias"))
+            self._token_step(i, words, Bk, probs)
             words, par = beam.step(i, probs)
             # the surviving beams continue from their parents' LSTM state (row gather by parent)
             be.embedding_fwd(self.Hs[i + 1], par, hg, Bk, 1, U, U, Bk)

@@ -38,9 +38,9 @@ def make_pair(rng, rates, norm="batch", seed=11, depth=0, use_layer_norm=False, 
 
 @pytest.mark.parametrize("rates,norm", [((0,) * 6, "batch"), ((0.1, 0.2, 0.2, 0.2, 0.2, 0.2), "batch"),
                                         ((0, 0.2, 0, 0.2, 0, 0), "layer")])
-def test_train_steps_match_oracle(rates, norm):
+def test_train_steps_match_oracle(rates, norm, **dims):
     rng = np.random.default_rng(41)
-    model, orc, d = make_pair(rng, rates, norm)
+    model, orc, d = make_pair(rng, rates, norm, **dims)
     model.compile(Adam(learning_rate=1e-3, beta_1=0.9, beta_2=0.98, epsilon=1e-8, clipnorm=0.1))
     opt = M.AdamState(orc.p, lr=1e-3, clipnorm=0.1)
     for step in range(3):
@@ -56,6 +56,15 @@ def test_train_steps_match_oracle(rates, norm):
             # Adam sees is rounding noise, which it normalises to O(lr) steps -- only bound it
             atol = 3e-3 * (step + 1) if k == "attention/V/bias" else 3e-6
             assert np.allclose(w, v, rtol=2e-4, atol=atol), (step, k, np.abs(w - v).max())
+
+
+@pytest.mark.parametrize("rates", [(0,) * 6, (0.1, 0.2, 0.2, 0.2, 0.2, 0.2)])
+def test_train_steps_match_oracle_unfused_head_tail(rates, monkeypatch):
+    """dense_inter width % 4 != 0: the head backward takes its unfused tail (column sums, output Dropout', LeakyReLU', the
+    two products of the nonlinear layer as separate launches); B=3, T=4"""
+    monkeypatch.setattr(NIC, "H", 30)
+    monkeypatch.setattr(M.LcNIC, "H", 30)
+    test_train_steps_match_oracle(rates, "batch", B=3, T=4)
 
 
 def test_gradients_call_test_step_greedy():

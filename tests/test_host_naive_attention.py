@@ -137,9 +137,9 @@ def test_restatement_gradients_equal_autograd(rates):
 
 # ---------------------------------------------------------------------------------------------------- model vs restatement
 @pytest.mark.parametrize("rates,depth", [(RATES[0], 0), (RATES[1], 0), (RATES[1], 1)])
-def test_train_steps_match_restatement(rates, depth):
+def test_train_steps_match_restatement(rates, depth, **dims):
     rng = np.random.default_rng(41)
-    model, orc, d = make_pair(rng, rates, depth=depth)
+    model, orc, d = make_pair(rng, rates, depth=depth, **dims)
     model.compile(Adam(learning_rate=1e-3, beta_1=0.9, beta_2=0.98, epsilon=1e-8, clipnorm=0.1))
     opt = M.AdamState(orc.p, lr=1e-3, clipnorm=0.1)
     for step in range(3):
@@ -157,6 +157,15 @@ def test_train_steps_match_restatement(rates, depth):
             w = model.get_weight(k)
             atol = 3e-3 * (step + 1) if k == "attention/V/bias" else 3e-6
             assert np.allclose(w, v, rtol=2e-4, atol=atol), (step, k, np.abs(w - v).max())
+
+
+@pytest.mark.parametrize("rates", RATES)
+def test_train_steps_match_restatement_unfused_head_tail(rates, monkeypatch):
+    """dense_inter width % 4 != 0: the head backward takes its unfused tail (column sums, LeakyReLU', the two products of
+    the nonlinear layer as separate launches); B=3, T=4"""
+    monkeypatch.setattr(NIC, "H", 30)
+    monkeypatch.setattr(M.LcNIC, "H", 30)
+    test_train_steps_match_restatement(rates, 0, B=3, T=4)
 
 
 def test_inference_matches_greedy_predict_and_test_step():
