@@ -612,6 +612,33 @@ int32_t tnt_softmax_cce_smooth_f32(const float* logits, const int32_t* target, f
                                    float* loss_row, float* correct_row, float* dlogits,
                                    int32_t rows, int32_t V, int32_t ld, float gscale,
                                    float label_smoothing, void* stream);
+/* ---- the same head with token-level unlikelihood (Welleck et al. 2020, "Neural Text Generation with Unlikelihood
+ * Training"), one launch (unlikely.hip): besides raising p of the target word, every position lowers p of the words
+ * that occurred earlier in the same caption.
+ * Layout: logits [rows][ld], rows = T * B in t-major order: row r is position t = r / B of caption b = r % B; target
+ *   int32[T * B] in the same order; V valid columns; p = softmax(x) over them.
+ * Negative candidates of row (t, b): C = { target[j * B + b] : 0 <= j < t } taken as a set (a word that occurred twice
+ *   counts once), without y = target[t * B + b], without id 0 (the padding) and without ids outside [0, V).  Row t = 0
+ *   has none.  A padding position (y = 0) behind the end of a caption keeps its candidates.  The prefix is always what
+ *   `target` holds, whatever ids were fed to the model.
+ *   ce        = -log(clip(p_y, 1e-7, 1 - 1e-7))          exactly tnt_softmax_cce_f32(from_logits=0, mask_zero=0)
+ *   ul        = -sum_{c in C} log(max(1 - p_c, 1e-7))
+ *   loss_row  = ce + alpha ul
+ *   m_y       = 1 where the clip of ce is inactive, else 0;   m_c = 1 where 1 - p_c >= 1e-7, else 0
+ *   q_c       = m_c p_c / (1 - p_c);   Q = sum_{c in C} q_c
+ *   dlogits_v = gscale (m_y (p_v - [v == y]) + alpha ([v in C] q_v - p_v Q))
+ * A target id outside [0, V) matches no class (p_y = 0: ce = -log(1e-7), m_y = 0).
+ * correct_row and probs as in tnt_softmax_cce_f32 (first maximum wins).  A row without candidates, or alpha = 0, is
+ * tnt_softmax_cce_f32 up to rounding.  Shared with it: every output is nullable (target null: probs only, loss_row /
+ * correct_row are not written and dlogits, if given, is zero); probs or dlogits may alias logits; pad columns [V, ld)
+ * of logits are ignored and those of an output are left as they were or written as zero (inside the register kernel's
+ * window).  alpha is finite and >= 0; 1 <= T <= 64 (one wave holds a caption's prefix); B == 0 is a no-op.  TNT_BADARG
+ * for B < 0, T < 1 or T > 64, V <= 0, ld < V, null logits, alpha negative or not finite: a rejected call launches
+ * nothing. */
+int32_t tnt_softmax_cce_unlikely_f32(const float* logits, const int32_t* target, float* probs,
+                                     float* loss_row, float* correct_row, float* dlogits,
+                                     int32_t B, int32_t T, int32_t V, int32_t ld, float gscale,
+                                     float alpha, void* stream);
 /* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v (first max wins).
  * B == 0 or T == 0 is a no-op; TNT_BADARG for B < 0, T < 0, V <= 0, null pointers. */
 int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T,

@@ -70,6 +70,7 @@ SIGNATURES = {
     "tnt_softmax_cce_f32": [P, P, P, P, P, P, I32, I32, I32, F32, I32, I32, P],
     "tnt_softmax_cce_live_f32": [P, P, P, P, P, P, I32, I32, I32, F32, P, P, P],
     "tnt_softmax_cce_smooth_f32": [P, P, P, P, P, P, I32, I32, I32, F32, F32, P],
+    "tnt_softmax_cce_unlikely_f32": [P, P, P, P, P, P, I32, I32, I32, I32, F32, F32, P],
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],

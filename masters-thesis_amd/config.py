@@ -40,7 +40,8 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
                     config["output_reg"], seed=config.get("seed", 42), **kw)
     else:
         raise ValueError(f"unknown mode {mode!r}")
-    # label_smoothing: an optional key of this library's (the reference's config has none), default 0
-    loss = CategoricalCrossentropy(from_logits=False, reduction="none", label_smoothing=config.get("label_smoothing", 0.0))
+    # label_smoothing, unlikelihood: optional keys of this library's (the reference's config has none), default 0
+    loss = CategoricalCrossentropy(from_logits=False, reduction="none", label_smoothing=config.get("label_smoothing", 0.0),
+                                   unlikelihood=config.get("unlikelihood", 0.0))
     model.compile(build_optimizer(config), loss, run_eagerly=True)
     return model

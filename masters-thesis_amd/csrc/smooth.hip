@@ -14,7 +14,7 @@
 // read once and written once; the generic kernel re-reads it (from the L2) for each of its four passes.
 // Pad columns [V, ld): as in seqops.hip (masked to -inf as they are read; written as zero inside the register window,
 // neither read nor written otherwise).
-#include "tnt_common.h"
+#include "tnt_rowhead.h"
 
 namespace {
 
@@ -70,36 +70,12 @@ __global__ __launch_bounds__(256) void softmax_cce_smooth_reg_kernel(const float
   const int row = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long)row * ld;
   float4 d[NV4], e[NV4];
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-    const int j = 4 * (tid + 256 * i);
-    d[i] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    if (j < ld) {
-      d[i] = *reinterpret_cast<const float4*>(x + j);
-      if (j + 1 >= V) d[i].y = -INFINITY;
-      if (j + 2 >= V) d[i].z = -INFINITY;
-      if (j + 3 >= V) d[i].w = -INFINITY;
-      if (j >= V) d[i].x = -INFINITY;
-    }
-    m = fmaxf(m, fmaxf(fmaxf(d[i].x, d[i].y), fmaxf(d[i].z, d[i].w)));
-  }
+  float m = tnt_row_load_max<NV4>(x, tid, V, ld, d);
   m = tnt_wave_max(m);
   if ((tid & 63) == 0) shm[tid >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
-  // first index holding the maximum (np.argmax / tf.argmax rule)
-  int am = 0x7fffffff;
-#pragma unroll
-  for (int i = NV4 - 1; i >= 0; --i) {
-    const int j = 4 * (tid + 256 * i);
-    if (d[i].w == m) am = j + 3;
-    if (d[i].z == m) am = j + 2;
-    if (d[i].y == m) am = j + 1;
-    if (d[i].x == m) am = j;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+  int am = tnt_row_first_max<NV4>(d, m, tid);      // first index holding the maximum (np.argmax / tf.argmax rule)
   if ((tid & 63) == 0) shi[tid >> 6] = am;
   const int y = target ? target[row] : -1;
   const bool has_y = y >= 0 && y < V;
@@ -162,24 +138,12 @@ __global__ __launch_bounds__(256) void softmax_cce_smooth_kernel(const float* lo
   __shared__ int shi[4], shc[4];
   const int row = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long)row * ld;
-  float m = -INFINITY;
-  int am = 0x7fffffff;
-  for (int j = tid; j < V; j += 256) {
-    const float v = x[j];
-    if (v > m) { m = v; am = j; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                         // larger value wins; ties -> smaller index
-    const float bv = __shfl_xor(m, o, 64);
-    const int bi = __shfl_xor(am, o, 64);
-    if (bv > m || (bv == m && bi < am)) { m = bv; am = bi; }
-  }
+  float m;
+  int am;
+  tnt_row_scan_argmax(x, V, tid, m, am);
   if ((tid & 63) == 0) { shm[tid >> 6] = m; shi[tid >> 6] = am; }
   __syncthreads();
-  m = shm[0]; am = shi[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (shm[k] > m || (shm[k] == m && shi[k] < am)) { m = shm[k]; am = shi[k]; }
+  tnt_row_combine_argmax(shm, shi, m, am);
   const int y = target ? target[row] : -1;
   const bool has_y = y >= 0 && y < V;
   const float xy = has_y ? x[y] : -INFINITY;                 // before any thread overwrites the row (aliasing)

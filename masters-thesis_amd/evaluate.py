@@ -142,6 +142,17 @@ def distinct_n(captions, n):
     return len(set(grams)) / len(grams) if grams else 0.0
 
 
+def repeat_rate(captions):
+    """The share of tokens that repeat an earlier token of the same caption, over a list of token sequences (lists of
+    words or ids, cut at the end token as ``ids_to_captions`` cuts, like those ``distinct_n`` takes): sum over the
+    captions of (length - number of distinct tokens), divided by the total number of tokens; 0.0 when there is no
+    token.  This is the quantity ``CategoricalCrossentropy(unlikelihood=...)`` acts on: every repeated token was a
+    negative candidate at its position.  Host only."""
+    caps = [list(c) for c in captions]
+    total = sum(len(c) for c in caps)
+    return sum(len(c) - len(set(c)) for c in caps) / total if total else 0.0
+
+
 def simple_eval(model, betas, target, tokenizer=None, temperature=1.0, sample_step=0, end_token="<end>", top_k=0,
                 top_p=1.0, constraints=None):
     """ThinkAndTell/evaluate.py:261-284 (`simple_eval`): one teacher-forced forward of the caption generator, then one

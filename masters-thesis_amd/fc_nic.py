@@ -29,6 +29,7 @@ from .ops import ACT_LEAKY
 class NICfc(_DenseNIC):
     H = 256                                                       # lc_NIC.py:141
     BN = "dense_in_bn"
+    SUPPORTS_UNLIKELIHOOD = False       # the unlikelihood head is wired for the two caption models, nic.NIC and lc_nic.NIC
 
     def __init__(self, input_size, units, embedding_features, embedding_text, vocab_size, max_length, dropout_input,
                  dropout_features, dropout_text, dropout_lstm, dropout_out, input_reg, lstm_reg, output_reg, **kw):

@@ -745,6 +745,8 @@ class NIC(ModelBase):
             be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
                                   self.logits if want_grad else None, n, self.V, self.ldV,
                                   1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
+        elif self.unlikelihood > 0:
+            self._loss_unlikely(B, T, want_grad)
         elif want_grad:
             be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V, self.ldV,
                            1.0 / (n * self.dp_world))

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .optimizers import Adam, loss_label_smoothing
+from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -746,6 +746,8 @@ class ModelBase:
     GUARD = 7       # slot of ``met`` that carries the device guard word of the step (see Metrics)
     METRIC_RING = 1024      # rows of the metrics ring: a step's Metrics stay readable for this many further training steps
     SUPPORTS_LABEL_SMOOTHING = True     # False where the step does not go through the compile loss (ThinkAndTell generators)
+    SUPPORTS_UNLIKELIHOOD = True        # False where the loss is not the (t, b)-ordered caption head (those, and NICfc)
+    UNLIKELIHOOD_MAX_T = 64             # loss positions per caption: one wave holds a caption's prefix
     # subclasses fill: self.layers_spec = OrderedDict(layer -> [weight names]),
     # self.keras_shapes = {full name: keras shape}
     def __init__(self, device=None, seed=42, use_graph=True, grad_sync=None):
@@ -758,6 +760,7 @@ class ModelBase:
         self.optimizer = None
         self.loss = None
         self.label_smoothing = 0.0          # of the compile loss (CategoricalCrossentropy(label_smoothing=...))
+        self.unlikelihood = 0.0             # of the compile loss (CategoricalCrossentropy(unlikelihood=...))
         self.built = False
         self.stop_training = False
         self._graphs = {}
@@ -773,14 +776,35 @@ class ModelBase:
         if eps > 0 and getattr(self, "self_critical", None) is not None:
             raise ValueError("label_smoothing > 0 does not apply to a self_critical model: its loss is the "
                              "advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        alpha = loss_unlikelihood(loss)
+        if alpha > 0 and not self.SUPPORTS_UNLIKELIHOOD:
+            raise NotImplementedError(f"{type(self).__name__} does not compute its loss with the caption head over "
+                                      "(position, caption) rows: unlikelihood > 0 is not implemented for it")
+        if alpha > 0 and eps > 0:
+            raise ValueError("unlikelihood > 0 together with label_smoothing > 0 is not implemented: one head kernel "
+                             "computes one of the two")
+        if alpha > 0 and getattr(self, "self_critical", None) is not None:
+            raise ValueError("unlikelihood > 0 does not apply to a self_critical model: its loss is the "
+                             "advantage-weighted tnt_scst_cce_f32, not the compile loss")
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
         # fixed here, not read per step: the head launch sits inside captured graphs
-        if eps != self.label_smoothing:
+        if eps != self.label_smoothing or alpha != self.__dict__.get("unlikelihood", 0.0):
             self._graphs = {}
         self.label_smoothing = eps
+        self.unlikelihood = alpha
         if self.built:
             self._init_optimizer_state()
+
+    def _loss_unlikely(self, B, T, want_grad):
+        """the head launch of _loss_metrics under unlikelihood > 0, training form (dlogits in place) or evaluation form
+        (probabilities in place, gscale 0): the same objective in both, as under label smoothing.  _stage_batch has refused
+        a caption that is too long before any launch of the step."""
+        assert T <= self.UNLIKELIHOOD_MAX_T
+        n = T * B
+        self.be.softmax_cce_unlikely(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
+                                     self.logits if want_grad else None, B, T, self.V, self.ldV,
+                                     1.0 / (n * self.dp_world) if want_grad else 0.0, self.unlikelihood)
 
     @property
     def be(self):
@@ -1375,6 +1399,10 @@ class ModelBase:
         (tnt_stage_batch_f32 / _h16);
         anything else (numpy, one-hot targets, other dtypes) takes the general per-tensor path."""
         x, cap, a0, c0 = inputs[:4]
+        if target is not None and self.unlikelihood > 0 and np.shape(cap)[-1] > self.UNLIKELIHOOD_MAX_T:
+            # a step with a loss: refused here, in front of every launch (and so outside any capture)
+            raise ValueError(f"unlikelihood training holds a caption's prefix in one wave: at most {self.UNLIKELIHOOD_MAX_T} "
+                             f"loss positions per caption, got {np.shape(cap)[-1]}")
         ts = [x, cap, a0, c0] + ([target] if target is not None else [])
         dev = self.device
         same = lambda t: t.device.type == dev.type and (t.device.index or 0) == (dev.index or 0)

@@ -259,15 +259,16 @@ class NIC(ModelBase):
         of Out, logits, loss and dlogits; the loss is not masked, so they count -- once, weighted by their multiplicity.
         Taken by train_step where the step is the persistent chains + the gemm3 products of one process and nothing else
         writes or reads the head's buffers by position: no scheduled sampling, self-critical step, AGC, label smoothing,
-        data parallel.  Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the
-        position-ordered buffers."""
+        unlikelihood (its candidates are a row's earlier positions, which the compacted rows have lost), data parallel.
+        Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the position-ordered
+        buffers."""
         be = self.be
         ok = (getattr(self, "compact_head", True) and self.__dict__.get("_seq_lstm") and self.__dict__.get("seq_xch") is not None
               and hasattr(be, "stage_batch_map") and hasattr(be, "softmax_cce_live") and hasattr(be, "gemm3")
               and getattr(self, "use_gemm3", True) and getattr(self, "g3_riders", True)
               and self.grad_sync is None and int(self.__dict__.get("dp_world", 1) or 1) == 1
               and self.scheduled_sampling is None and self.self_critical is None and not self.__dict__.get("agc")
-              and not self.label_smoothing and self.U % 4 == 0)
+              and not self.label_smoothing and not self.unlikelihood and self.U % 4 == 0)
         if not ok:
             return None
         return (self.head_pos, self.head_w, self.head_tgt, self.head_live, self.loss_row, self.corr_row)
@@ -434,6 +435,8 @@ class NIC(ModelBase):
             be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
                                   self.logits if want_grad else None, n, self.V, self.ldV,
                                   1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
+        elif self.unlikelihood > 0:
+            self._loss_unlikely(B, T, want_grad)
         elif want_grad:
             be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
                            self.ldV, 1.0 / (n * self.dp_world))

@@ -319,6 +319,12 @@ class HipBackend:
         self._call(self.lib.tnt_softmax_cce_smooth_f32, "tnt_softmax_cce_smooth_f32", _p(logits), _p(target), _p(probs), _p(loss_row),
                    _p(correct_row), _p(dlogits), rows, V, ld, gscale, float(label_smoothing), self._s())
 
+    def softmax_cce_unlikely(self, logits, target, probs, loss_row, correct_row, dlogits, B, T, V, ld, gscale, alpha):
+        """the head with token-level unlikelihood over each caption's own prefix in the same single launch: rows = T * B,
+        t-major (tnt_softmax_cce_unlikely_f32; definition in include/tnt_hip.h)"""
+        self._call(self.lib.tnt_softmax_cce_unlikely_f32, "tnt_softmax_cce_unlikely_f32", _p(logits), _p(target), _p(probs),
+                   _p(loss_row), _p(correct_row), _p(dlogits), B, T, V, ld, gscale, float(alpha), self._s())
+
     def onehot_argmax(self, onehot, ids_tmajor, B, T, V):
         self._call(self.lib.tnt_onehot_argmax_f32, "tnt_onehot_argmax_f32", _p(onehot), _p(ids_tmajor), B, T, V, self._s())
 
