@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from .arena import ParamArena
-from .model_base import (Metrics, S_IN, S_TEXT, S_OUT, S_LSTM_IN, S_LSTM_OUT, BN_EPS, BN_MOMENTUM)
-from .nic import NIC as _DenseNIC, _r4
+from .model_base import (Metrics, _r4, S_IN, S_TEXT, S_OUT, S_LSTM_IN, S_LSTM_OUT, BN_EPS, BN_MOMENTUM)
+from .nic import NIC as _DenseNIC
 from .ops import ACT_LEAKY
 
 
@@ -95,25 +95,6 @@ class NICfc(_DenseNIC):
         self.set_weight("time_distributed_nonlinear/kernel", tn((U, H), np.sqrt(2.0 / (U + H))))
         self.set_weight("time_distributed_softmax/kernel", tn((H, V), np.sqrt(2.0 / (H + V))))
         self.set_weight(f"{self.BN}/gamma", np.ones(Ef))
-
-    def set_weight(self, name, arr):
-        arr = np.asarray(arr, dtype=np.float32)
-        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
-        if name == f"{self.BN}/moving_mean":
-            self.mov_mean.copy_(torch.from_numpy(arr)); return
-        if name == f"{self.BN}/moving_variance":
-            self.mov_var.copy_(torch.from_numpy(arr)); return
-        if name == "time_distributed_softmax/kernel":
-            pad = np.zeros((self.H, self.ldV), np.float32); pad[:, :self.V] = arr
-            self.arena.p(name).copy_(torch.from_numpy(pad)); return
-        super().set_weight(name, arr)
-
-    def get_weight(self, name):
-        if name == f"{self.BN}/moving_mean":
-            return self.mov_mean.cpu().numpy().copy()
-        if name == f"{self.BN}/moving_variance":
-            return self.mov_var.cpu().numpy().copy()
-        return self._unpack(name, self.arena.p(name))
 
     # ------------------------------------------------------------------ buffers
     def _build(self, B, T):
@@ -265,9 +246,7 @@ class NICfc(_DenseNIC):
         if self.grad_sync is None:
             ring = self._run_step(self._run_captured, ("train", B, T), lambda: self._train_and_update_graph(B, T))
         else:
-            self._run_captured(("train_fb", B, T), lambda: self._train_graph(B, T))
-            self.grad_sync(self)
-            self._run_captured(("train_up", B, T), self._update_graph)
+            self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         return self._metrics_from(m, loss=0, L2=2, accuracy=1, lr=self.lr_dev.clone()[0])
@@ -278,8 +257,7 @@ class NICfc(_DenseNIC):
 
         def run():
             self._forward(B, T, training)
-            self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
-            return self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
+            return self._probs(B, T)
         return self._guarded(run), None
 
     call = call_fc = __call__

@@ -22,19 +22,15 @@ import numpy as np
 import torch
 
 from .arena import ParamArena
-from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN,
-                         S_LSTM_IN, S_LSTM_OUT, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, BN_EPS, BN_MOMENTUM,
-                         ScheduledSampling, check_sampling, check_length_penalty, _TokenChoice, _BeamDecode)
+from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN, S_LSTM_IN, S_LSTM_OUT, S_SS_COIN,
+                         S_SS_DRAW, BN_EPS, BN_MOMENTUM, ScheduledSampling, check_sampling, check_length_penalty,
+                         _TokenChoice, _BeamDecode)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
 S_DEEP = 6            # + i: feature dropout behind deep stage i of the depth-n encoder (deep_layers.py:58)
 S_NOUT = 144          # + i: output Dropout of step i of the free-running decoder, on the U-wide LSTM output (lc_NIC.py:207)
 from .ops import ACT_LEAKY
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 def synthetic_groups(n_voxels, n_regions, out_dim, seed=42, overlap=0.0):
@@ -262,56 +258,14 @@ class NIC(ModelBase):
         self.set_weight("time_distributed_nonlinear/kernel", tn((U, H), np.sqrt(2.0 / (U + H))))
         self.set_weight("time_distributed_softmax/kernel", tn((H, V), np.sqrt(2.0 / (H + V))))
 
-    def set_weight(self, name, arr):
-        arr = np.asarray(arr, dtype=np.float32)
-        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
-        for q, bn in self._bn_slots():
-            if name == f"{bn}/moving_mean":
-                self.mov_mean[q].copy_(torch.from_numpy(arr)); return
-            if name == f"{bn}/moving_variance":
-                self.mov_var[q].copy_(torch.from_numpy(arr)); return
-        dst = self.arena.p(name)
-        if name.startswith("lstm/") and arr.shape[-1] == 4 * self.U:
-            arr = interleave_gates(arr, self.U)
-        elif name == "time_distributed_softmax/kernel":
-            pad = np.zeros((self.H, self.ldV), np.float32); pad[:, :self.V] = arr; arr = pad
-        elif name == "time_distributed_softmax/bias":
-            pad = np.zeros(self.ldV, np.float32); pad[:self.V] = arr; arr = pad
-        dst.copy_(torch.from_numpy(np.ascontiguousarray(arr)).view(dst.shape))
-
-    def _unpack(self, name, t):
-        arr = t.detach().cpu().numpy()
-        if name.startswith("lstm/") and not name.startswith("lstm/state_norm"):
-            return deinterleave_gates(arr)
-        if name == "time_distributed_softmax/kernel":
-            return np.ascontiguousarray(arr[:, :self.V])
-        if name == "time_distributed_softmax/bias":
-            return np.ascontiguousarray(arr[:self.V])
-        return arr.reshape(self.keras_shapes[name]).copy()
-
     def _bn_slots(self):
         """(slot of mov_mean / mov_var, keras layer name) of every BatchNormalization of the encoder"""
         return [(q, self.bn_name(q)) for q in range(self.S)] + [(self.S + i, f"input_bn/deep{i}") for i in range(self.depth)]
 
-    def get_weight(self, name):
-        for q, bn in self._bn_slots():
-            if name == f"{bn}/moving_mean":
-                return self.mov_mean[q].cpu().numpy().copy()
-            if name == f"{bn}/moving_variance":
-                return self.mov_var[q].cpu().numpy().copy()
-        return self._unpack(name, self.arena.p(name))
-
-    def get_gradient(self, name):
-        return self._unpack(name, self.arena.g(name))
-
-    def state_tensors(self):
-        return list(self.mov_mean) + list(self.mov_var)
-
-    @property
-    def losses(self):
-        a = self.arena
-        self._norms_and_l2(self.met[2:3])
-        return [a.seg_l2[e.seg] * a.wsq[e.seg] for e in a.entries.values() if e.l2 > 0]
+    def _state_map(self):
+        slots = self._bn_slots()        # every moving mean, then every moving variance
+        return OrderedDict([(f"{bn}/moving_mean", self.mov_mean[q]) for q, bn in slots]
+                           + [(f"{bn}/moving_variance", self.mov_var[q]) for q, bn in slots])
 
     # ------------------------------------------------------------------ buffers
     def _build(self, B, T):
@@ -1095,24 +1049,6 @@ class NIC(ModelBase):
         self._loss_metrics(B, T, True)
         self._backward(B, T)
 
-    def _update_graph(self):
-        self._apply_agc()
-        self._norms_and_l2(self.met[2:3])
-        self._apply_optimizer()
-
-    def _train_and_update_graph(self, B, T):
-        """the single-process step as one launch sequence: the loss / accuracy totals ride in the step-finalize launch"""
-        if not getattr(self, "fused_update", True):          # A/B switch (tools/ab_attr.py): the unfused launch sequence
-            self._train_graph(B, T)
-            self._update_graph()
-            return
-        self._defer_sum2 = True
-        try:
-            self._train_graph(B, T)
-        finally:
-            self._defer_sum2 = False
-        self._update_fused(self.met[2:3])
-
     def _stage_mask_job(self):
         if not (self._keep_stored and getattr(self, "stage_masks", True)):
             return None
@@ -1139,32 +1075,18 @@ class NIC(ModelBase):
             raise RuntimeError("compile() the model before train_step")
         if not self.teacher_forcing and self.grad_sync is not None:
             raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
-        if self.scheduled_sampling is not None and self.grad_sync is not None:
-            raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
+        self._ss_refuse()
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
-        if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
-            raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
-                             f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
+        self._ss_refuse(T)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
         ring = False
         if self.grad_sync is None:
-            # The step is replayed as a recorded launch plan (ModelBase._run_planned), not as a hipGraph: with 15 (dense) / 32
-            # (attention) launches a step the host re-issues them in ~15 % of the step's time and every launch starts ~0.2-0.4 us
-            # earlier than as a graph node (0.4650 -> 0.4588 and 0.5666 -> 0.5626 ms/step, tools/probe/plan_bench.py: separate
-            # models, repeated, spread 0.0005).  ``plan_step = False`` restores the graph.  A plan re-issues backend launches
-            # only, so it is used where the step is nothing else: the sparse Embedding backward (the dense form hands its ids on
-            # with a tensor copy, which a graph captures and a plan would drop).
-            plan = (getattr(self, "plan_step", True) and self.Et % 4 == 0 and getattr(self, "sparse_emb_bwd", True)
-                    and hasattr(self.be, "embedding_bwd_sparse"))
-            run = self._run_planned if plan else self._run_captured
-            ring = self._run_step(run, ("train", B, T), lambda: self._train_and_update_graph(B, T))
+            ring = self._run_step(self._step_runner(self.Et), ("train", B, T), lambda: self._train_and_update_graph(B, T))
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
         else:
-            self._run_captured(("train_fb", B, T), lambda: self._train_graph(B, T))
-            self.grad_sync(self)
-            self._run_captured(("train_up", B, T), self._update_graph)
+            self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
         return self._metrics(True, ring)
 
@@ -1189,7 +1111,7 @@ class NIC(ModelBase):
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
-        be, a, sp = self.be, self.arena, self.arena.spans
+        be, a = self.be, self.arena
         if self.__dict__.get("ew") is None:
             self.ew = torch.zeros_like(a.theta)
         n_alpha = T * B * self.R
@@ -1203,14 +1125,13 @@ class NIC(ModelBase):
             finally:
                 self._alpha_mse = 0.0
             self._norms_and_l2(None)
-            be.sam(a.theta, a.grad, self.ew, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.nseg, sp.nspan, rho, 0,
-                   sq_override=a.sq_override)
+            self._sam_move(rho, 0, a.sq_override)
             self._forward(B, T, True)
             self._loss_metrics(B, T, True)
             be.sqdiff_mean(self.alpha, self.met[3:4], n_alpha, 1.0)
             self._backward(B, T)
             self._norms_and_l2(self.met[2:3])          # L2 as the reference reports it: at the perturbed weights
-            be.sam(a.theta, a.grad, self.ew, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.nseg, sp.nspan, rho, 1)
+            self._sam_move(rho, 1)
             self._apply_agc()
             self._norms_and_l2(None)                   # clip norms of the second gradient at the restored weights
             self._apply_optimizer()
@@ -1251,9 +1172,7 @@ class NIC(ModelBase):
 
         def run():
             self._forward(B, T, training)
-            self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
-            probs = self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
-            return probs, self.alpha.clone().unsqueeze(-1)
+            return self._probs(B, T), self.alpha.clone().unsqueeze(-1)
         return self._guarded(run)
 
     def call_naive_attention(self, data, training=False, return_ids=False):
@@ -1268,9 +1187,7 @@ class NIC(ModelBase):
         def run():
             self._forward_naive(B, T, training)
             self.be.argmax_rows(self.logits[(T - 1) * B:], self.last_ids, B, self.V, self.ldV)
-            self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
-            probs = self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
-            out = (probs, self.alpha.clone().unsqueeze(-1))
+            out = (self._probs(B, T), self.alpha.clone().unsqueeze(-1))
             if return_ids:
                 out += (torch.cat([self.cap[:, 1:], self.last_ids.view(B, 1)], dim=1),)
             return out

@@ -686,16 +686,79 @@ class _BeamDecode:
         return seqs, final
 
 
+def _r4(n):
+    return (n + 3) // 4 * 4
+
+
+def _interleave(w, U, g):
+    """keras [.., gU] (g gate blocks) -> kernel layout [.., U, 4], slots g.. zero."""
+    out = np.zeros(w.shape[:-1] + (U, 4), w.dtype)
+    out[..., :g] = np.moveaxis(w.reshape(*w.shape[:-1], g, U), -2, -1)
+    return out
+
+
+def _deinterleave(w, g):
+    """kernel layout [.., U, 4] -> keras [.., gU]."""
+    return np.ascontiguousarray(np.moveaxis(w[..., :g], -1, -2)).reshape(*w.shape[:-2], -1)
+
+
 def interleave_gates(w, U):
     """keras [.., 4U] (i,f,c~,o blocks) -> kernel layout [.., U, 4]."""
-    w = np.asarray(w)
-    return np.ascontiguousarray(np.moveaxis(w.reshape(*w.shape[:-1], 4, U), -2, -1))
+    return _interleave(np.asarray(w), U, 4)
 
 
 def deinterleave_gates(w):
     """kernel layout [.., U, 4] -> keras [.., 4U]."""
-    w = np.asarray(w)
-    return np.ascontiguousarray(np.moveaxis(w, -1, -2)).reshape(*w.shape[:-2], -1)
+    return _deinterleave(np.asarray(w), 4)
+
+
+def interleave3(w, U):
+    """keras [.., 3U] gate blocks (z, r, h) -> interleaved [.., U, 4] with a zero fourth slot."""
+    return _interleave(np.asarray(w, np.float32), U, 3)
+
+
+def deinterleave3(w):
+    return _deinterleave(np.asarray(w), 3)
+
+
+def _layout(name, keras, device):
+    """How a variable of keras shape ``keras`` is stored under the shape ``device`` it was added to the arena with:
+    ("copy", 0) equal shapes; ("gates", g) g = 3 or 4 gate blocks [.., gU] interleaved as [.., U, 4]; ("pad", 0) the last
+    axis zero-padded (the vocabulary axis, V to ldV); ("reshape", 0) the same elements in the same order."""
+    keras, device = tuple(keras), tuple(device)
+    if keras == device:
+        return "copy", 0
+    if (len(device) == len(keras) + 1 and device[-1] == 4 and device[:-2] == keras[:-1]
+            and keras[-1] in (3 * device[-2], 4 * device[-2])):
+        return "gates", keras[-1] // device[-2]
+    if len(device) == len(keras) and device[:-1] == keras[:-1] and device[-1] > keras[-1]:
+        return "pad", 0
+    if int(np.prod(keras)) == int(np.prod(device)):
+        return "reshape", 0
+    raise ValueError(f"{name}: no device layout takes the keras shape {keras} to the arena shape {device}")
+
+
+def pack(arr, device_shape, name="?"):
+    """keras-layout array -> the float32 array of ``device_shape`` the arena stores (_layout)."""
+    arr = np.asarray(arr, dtype=np.float32)
+    kind, g = _layout(name, arr.shape, device_shape)
+    if kind == "gates":
+        return _interleave(arr, device_shape[-2], g)
+    if kind == "pad":
+        out = np.zeros(tuple(device_shape), np.float32)
+        out[..., :arr.shape[-1]] = arr
+        return out
+    return np.ascontiguousarray(arr).reshape(tuple(device_shape))
+
+
+def unpack(arr, keras_shape, name="?"):
+    """pack's inverse: the stored array -> a fresh array in the keras layout."""
+    kind, g = _layout(name, keras_shape, arr.shape)
+    if kind == "gates":
+        return _deinterleave(arr, g)
+    if kind == "pad":
+        return arr[..., :keras_shape[-1]].copy()
+    return arr.reshape(tuple(keras_shape)).copy()
 
 
 class _LayerView:
@@ -1294,6 +1357,42 @@ class ModelBase:
                            a.sq, a.wsq, l2_out, sp.nspan, a.nseg)
 
     # ------------------------------------------------------------------ weights
+    def _state_map(self):
+        """keras name -> device tensor of the variables kept outside the arena (BatchNorm moving statistics), in the order
+        dp.py broadcasts them"""
+        return {}
+
+    def state_tensors(self):
+        """Non-trainable device state (BatchNorm moving statistics)."""
+        return list(self._state_map().values())
+
+    def set_weight(self, name, arr):
+        arr = np.asarray(arr, dtype=np.float32)
+        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
+        dst = self._state_map().get(name)
+        if dst is None:
+            dst = self.arena.p(name)
+        dst.copy_(torch.from_numpy(pack(arr, dst.shape, name)))
+
+    def _unpack(self, name, t):
+        return unpack(t.detach().cpu().numpy(), self.keras_shapes[name], name)
+
+    def get_weight(self, name):
+        t = self._state_map().get(name)
+        return self._unpack(name, self.arena.p(name) if t is None else t)
+
+    def get_gradient(self, name):
+        """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
+        optimizer kernels add on the fly)."""
+        return self._unpack(name, self.arena.g(name))
+
+    @property
+    def losses(self):
+        """[lambda*||W||^2 ...] as self.losses (NIC.py:242-243)."""
+        a = self.arena
+        self._norms_and_l2(self.met[2:3])
+        return [a.seg_l2[e.seg] * a.wsq[e.seg] for e in a.entries.values() if e.l2 > 0]
+
     @property
     def trainable_variables(self):
         return [(n, self.get_weight(n)) for n in self.trainable_names()]
@@ -1759,6 +1858,68 @@ class ModelBase:
         for f, name, args in st[1]:
             if f(*args) != 0:
                 raise RuntimeError(f"{name} failed while replaying launch plan {key}")
+
+    # ------------------------------------------------------------------ training-step scaffold (the model supplies _train_graph)
+    def _update_graph(self):
+        self._apply_agc()
+        self._norms_and_l2(self.met[2:3])
+        self._apply_optimizer()
+
+    def _train_and_update_graph(self, B, T):
+        """the single-process step as one launch sequence: the loss / accuracy totals ride in the step-finalize launch"""
+        if not getattr(self, "fused_update", True):          # A/B switch (tools/ab_attr.py): the unfused launch sequence
+            self._train_graph(B, T)
+            self._update_graph()
+            return
+        self._defer_sum2 = True
+        try:
+            self._train_graph(B, T)
+        finally:
+            self._defer_sum2 = False
+        self._update_fused(self.met[2:3])
+
+    def _train_step_dp(self, B, T, fb, up):
+        """the generic data-parallel schedule: forward+backward | all-reduce of the flat gradient | update"""
+        self._run_captured(("train_fb", B, T), fb)
+        self.grad_sync(self)
+        self._run_captured(("train_up", B, T), up)
+
+    # The single-process step is replayed as a recorded launch plan (_run_planned), not as a hipGraph: with 15 (dense) / 32
+    # (attention) launches a step the host re-issues them in ~15 % of the step's time and every launch starts ~0.2-0.4 us
+    # earlier than as a graph node (0.4650 -> 0.4588 and 0.5666 -> 0.5626 ms/step, tools/probe/plan_bench.py: separate
+    # models, repeated, spread 0.0005).  ``plan_step = False`` restores the graph.  A plan re-issues backend launches
+    # only, so it is used where the step is nothing else: the sparse Embedding backward (the dense form hands its ids on
+    # with a tensor copy, which a graph captures and a plan would drop).
+    def _step_runner(self, E=None):
+        """_run_planned where the training step is backend launches only, else _run_captured.  ``E``: the text-embedding
+        width (default self.E)"""
+        plan = (getattr(self, "plan_step", True) and (self.E if E is None else E) % 4 == 0
+                and getattr(self, "sparse_emb_bwd", True) and hasattr(self.be, "embedding_bwd_sparse"))
+        return self._run_planned if plan else self._run_captured
+
+    def _ss_refuse(self, T=None):
+        """what a scheduled-sampling train_step refuses: in front of the staging a data-parallel schedule, behind it
+        (``T``: the staged caption length) a caption with more token positions than the Philox sites hold"""
+        if self.scheduled_sampling is None:
+            return
+        if T is None:
+            if self.grad_sync is not None:
+                raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
+        elif T - 1 > SS_MAX_POSITIONS:
+            raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
+                             f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
+
+    def _probs(self, B, T):
+        """softmax over the logits in place (one launch); returns the probabilities as (B, T, V)"""
+        self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
+        return self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
+
+    def _sam_move(self, rho, phase, sq_override=None):
+        """the weight move of a sharpness-aware step (tnt_sam_f32): phase 0 steps to theta + rho * g / ||g|| and keeps the
+        offset in ``ew``, phase 1 steps back"""
+        a, sp = self.arena, self.arena.spans
+        self.be.sam(a.theta, a.grad, self.ew, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.nseg, sp.nspan, rho, phase,
+                    sq_override=sq_override)
 
     # ------------------------------------------------------------------ caption scoring
     def score_captions(self, img_input, a0, c0, captions, end_id=-1, normalise=None, return_tokens=False, max_rows=None):

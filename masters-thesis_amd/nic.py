@@ -18,19 +18,17 @@ import numpy as np
 import torch
 
 from .arena import ParamArena
-from .model_base import (ModelBase, Metrics, interleave_gates, deinterleave_gates, S_IN, S_FEAT, S_LSTM_IN, BN_EPS,
-                         BN_MOMENTUM, S_SS_COIN, S_SS_DRAW, SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling,
-                         SelfCritical, check_sampling, check_beam, _TokenChoice, _BeamDecode)
+from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
+                         SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
+                         _TokenChoice, _BeamDecode)
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
 
 
-def _r4(n):
-    return (n + 3) // 4 * 4
-
-
 class NIC(ModelBase):
+    BN = "batch_norm"       # the BatchNormalization layer that owns the moving statistics (fc_nic: its own)
+
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
                  **kw):
@@ -119,38 +117,8 @@ class NIC(ModelBase):
         self.set_weight("time_distributed_softmax/kernel", tn((U, V), np.sqrt(2.0 / (U + V))))
         self.set_weight("batch_norm/gamma", np.ones(E))
 
-    def set_weight(self, name, arr):
-        arr = np.asarray(arr, dtype=np.float32)
-        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
-        if name == "batch_norm/moving_mean":
-            self.mov_mean.copy_(torch.from_numpy(arr)); return
-        if name == "batch_norm/moving_variance":
-            self.mov_var.copy_(torch.from_numpy(arr)); return
-        dst = self.arena.p(name)
-        if name.startswith("lstm/"):
-            arr = interleave_gates(arr, self.U)
-        elif name == "time_distributed_softmax/kernel":
-            pad = np.zeros((self.U, self.ldV), np.float32); pad[:, :self.V] = arr; arr = pad
-        elif name == "time_distributed_softmax/bias":
-            pad = np.zeros(self.ldV, np.float32); pad[:self.V] = arr; arr = pad
-        dst.copy_(torch.from_numpy(np.ascontiguousarray(arr)).view(dst.shape))
-
-    def _unpack(self, name, t):
-        arr = t.detach().cpu().numpy()
-        if name.startswith("lstm/"):
-            return deinterleave_gates(arr)
-        if name == "time_distributed_softmax/kernel":
-            return np.ascontiguousarray(arr[:, :self.V])
-        if name == "time_distributed_softmax/bias":
-            return np.ascontiguousarray(arr[:self.V])
-        return arr.copy()
-
-    def get_weight(self, name):
-        if name == "batch_norm/moving_mean":
-            return self.mov_mean.cpu().numpy().copy()
-        if name == "batch_norm/moving_variance":
-            return self.mov_var.cpu().numpy().copy()
-        return self._unpack(name, self.arena.p(name))
+    def _state_map(self):
+        return {f"{self.BN}/moving_mean": self.mov_mean, f"{self.BN}/moving_variance": self.mov_var}
 
     def get_gradient(self, name):
         """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
@@ -162,7 +130,7 @@ class NIC(ModelBase):
             x, dpre, rows = st
             self.be.dense_dw_skinny(x, dpre, self.arena.g(name), self.N, self.E, rows, self.ldx)
             self._enc_grad_stale = None
-        return self._unpack(name, self.arena.g(name))
+        return super().get_gradient(name)
 
     def _enc_update_fused(self, rows):
         """True when the encoder kernel's gradient is consumed inside the optimizer launches instead of being written
@@ -174,17 +142,6 @@ class NIC(ModelBase):
                     and self.arena.entries["dense_img/kernel"].seg == 0
                     # one norm-partial slot per workgroup inside the variable's own span slots
                     and min((self.N + 15) // 16, 256) * (self.E // 512) <= self.arena.spans.first_host[1])
-
-    def state_tensors(self):
-        """Non-trainable device state (BatchNorm moving statistics)."""
-        return [self.mov_mean, self.mov_var]
-
-    @property
-    def losses(self):
-        """[lambda*||W||^2 ...] as self.losses (NIC.py:242-243)."""
-        a = self.arena
-        self._norms_and_l2(self.met[2:3])
-        return [a.seg_l2[e.seg] * a.wsq[e.seg] for e in a.entries.values() if e.l2 > 0]
 
     # ------------------------------------------------------------------ buffers
     def _build(self, B, T):
@@ -691,53 +648,20 @@ class NIC(ModelBase):
         self._loss_metrics(B, T, True)
         self._backward(B, T)
 
-    def _update_graph(self):
-        self._apply_agc()
-        self._norms_and_l2(self.met[2:3])
-        self._apply_optimizer()
-
-    def _train_and_update_graph(self, B, T):
-        """the single-process step as one launch sequence: the loss / accuracy totals ride in the step-finalize launch"""
-        if not getattr(self, "fused_update", True):          # A/B switch (tools/ab_attr.py): the unfused launch sequence
-            self._train_graph(B, T)
-            self._update_graph()
-            return
-        self._defer_sum2 = True
-        try:
-            self._train_graph(B, T)
-        finally:
-            self._defer_sum2 = False
-        self._update_fused(self.met[2:3])
-
-    def _step_runner(self):
-        """_run_planned where the training step is backend launches only (see train_step), else _run_captured"""
-        plan = (getattr(self, "plan_step", True) and self.E % 4 == 0 and getattr(self, "sparse_emb_bwd", True)
-                and hasattr(self.be, "embedding_bwd_sparse"))
-        return self._run_planned if plan else self._run_captured
-
     def train_step(self, data):
         """NIC.train_step (NIC.py:198-252): data = ((betas, cap, a0, c0), target).  With ``self_critical`` set, the
         self-critical step (train_step_scst) instead."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
-        if self.scheduled_sampling is not None and self.grad_sync is not None:
-            raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
+        self._ss_refuse()
         if self.self_critical is not None:
             return self.train_step_scst(data)
         B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None)
-        if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
-            raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
-                             f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
+        self._ss_refuse(T)
         self._sync_lr()
         self._enc_grad_stale = None
         ring = False
-        if self.grad_sync is None:
-            # The step is replayed as a recorded launch plan (ModelBase._run_planned), not as a hipGraph: with 15 (dense) / 32
-            # (attention) launches a step the host re-issues them in ~15 % of the step's time and every launch starts ~0.2-0.4 us
-            # earlier than as a graph node (0.4650 -> 0.4588 and 0.5666 -> 0.5626 ms/step, tools/probe/plan_bench.py: separate
-            # models, repeated, spread 0.0005).  ``plan_step = False`` restores the graph.  A plan re-issues backend launches
-            # only, so it is used where the step is nothing else: the sparse Embedding backward (the dense form hands its ids on
-            # with a tensor copy, which a graph captures and a plan would drop).
+        if self.grad_sync is None:      # replayed as a launch plan or a hipGraph: ModelBase._step_runner
             compact = bool(self.__dict__.get("_head_map_fresh"))      # the staging launch built the head's row map
             key = ("train", B, T, "compact") if compact else ("train", B, T)
             if compact and self._head_live_est is None and self._graphs.get(key) is None:
@@ -751,10 +675,8 @@ class NIC(ModelBase):
             self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
-        else:       # data parallel: forward+backward | all-reduce of the flat gradient | update
-            self._run_captured(("train_fb", B, T), lambda: self._train_graph(B, T))
-            self.grad_sync(self)
-            self._run_captured(("train_up", B, T), self._update_graph)
+        else:
+            self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         return self._metrics_from(m, loss=0, L2=2, accuracy=1)
@@ -919,8 +841,7 @@ class NIC(ModelBase):
 
         def run():
             self._forward(B, T, training)
-            self.be.softmax_cce(self.logits, None, self.logits, None, None, None, T * B, self.V, self.ldV, 0.0)
-            return self.logits.view(T, B, self.ldV)[:, :, :self.V].permute(1, 0, 2).contiguous()
+            return self._probs(B, T)
         return self._guarded(run)
 
     call = __call__

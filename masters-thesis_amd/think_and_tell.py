@@ -19,12 +19,8 @@ import numpy as np
 import torch
 
 from .arena import ParamArena
-from .model_base import ModelBase, Metrics, interleave_gates, deinterleave_gates, S_FEAT, S_OUT
+from .model_base import ModelBase, Metrics, _r4, S_FEAT, S_OUT
 from .ops import ACT_RELU, ACT_TANH
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 class Encoder:
@@ -101,37 +97,6 @@ class CaptionGenerator(ModelBase):
         self.set_weight("fc_vocab/kernel", glorot((U, V)))
         if self.optimizer is not None:
             self._init_optimizer_state()
-
-    def set_weight(self, name, arr):
-        arr = np.asarray(arr, dtype=np.float32)
-        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
-        dst = self.arena.p(name)
-        if name.startswith("lstm/"):
-            arr = interleave_gates(arr, self.U)
-        elif name == "fc_vocab/kernel":
-            pad = np.zeros((self.U, self.ldV), np.float32); pad[:, :self.V] = arr; arr = pad
-        elif name == "fc_vocab/bias":
-            pad = np.zeros(self.ldV, np.float32); pad[:self.V] = arr; arr = pad
-        dst.copy_(torch.from_numpy(np.ascontiguousarray(arr)).view(dst.shape))
-
-    def _unpack(self, name, t):
-        arr = t.detach().cpu().numpy()
-        if name.startswith("lstm/"):
-            return deinterleave_gates(arr)
-        if name == "fc_vocab/kernel":
-            return np.ascontiguousarray(arr[:, :self.V])
-        if name == "fc_vocab/bias":
-            return np.ascontiguousarray(arr[:self.V])
-        return arr.copy()
-
-    def get_weight(self, name):
-        return self._unpack(name, self.arena.p(name))
-
-    def get_gradient(self, name):
-        return self._unpack(name, self.arena.g(name))
-
-    def state_tensors(self):
-        return []
 
     # ------------------------------------------------------------------ buffers
     def _build(self, B, T):
@@ -321,9 +286,7 @@ class CaptionGenerator(ModelBase):
         if self.grad_sync is None:
             self._run_captured(("train", B, T), lambda: (fb(), up()))
         else:
-            self._run_captured(("train_fb", B, T), fb)
-            self.grad_sync(self)
-            self._run_captured(("train_up", B, T), up)
+            self._train_step_dp(B, T, fb, up)
         self.optimizer.iterations += 1
         return self._result()
 
@@ -335,20 +298,17 @@ class CaptionGenerator(ModelBase):
         img, target = self._unpack_batch(data)
         B, T = self._stage(img, target)
         self._sync_lr()
-        be, a, sp = self.be, self.arena, self.arena.spans
         if self.ew is None:
-            self.ew = torch.zeros_like(a.theta)
+            self.ew = torch.zeros_like(self.arena.theta)
 
         def run():
             gs = self._grad_scale(B, T)
             self._forward(B, T, True); self._loss(B, T, True, gs); self._backward(B, T)
             self._norms_and_l2(None)
-            be.sam(a.theta, a.grad, self.ew, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.nseg, sp.nspan,
-                   rho, 0)
+            self._sam_move(rho, 0)
             self._forward(B, T, True); self._loss(B, T, True, gs); self._backward(B, T)
             self._norms_and_l2(self.met[2:3])       # L2 metric at the perturbed weights, as the reference reports it
-            be.sam(a.theta, a.grad, self.ew, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.nseg, sp.nspan,
-                   rho, 1)
+            self._sam_move(rho, 1)
             self._norms_and_l2(None)                # clip norms of the SAM gradient at the restored weights
             self._apply_optimizer()
         self._run_captured(("sam", B, T), run)

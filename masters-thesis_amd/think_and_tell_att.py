@@ -18,22 +18,10 @@ import numpy as np
 import torch
 
 from .arena import ParamArena
-from .model_base import Metrics, S_FEAT, S_OUT
+from .model_base import Metrics, _r4, S_FEAT, S_OUT
+from .model_base import interleave3, deinterleave3      # noqa: F401 -- the GRU gate layout stays importable from this module
 from .ops import ACT_RELU
-from .think_and_tell import CaptionGenerator as _CaptionGeneratorLSTM, _r4
-
-
-def interleave3(w, U):
-    """keras [.., 3U] gate blocks (z, r, h) -> interleaved [.., U, 4] with a zero fourth slot."""
-    lead = w.shape[:-1]
-    out = np.zeros(lead + (U, 4), np.float32)
-    out[..., :3] = np.moveaxis(np.asarray(w, np.float32).reshape(*lead, 3, U), -2, -1)
-    return out
-
-
-def deinterleave3(w):
-    lead, U = w.shape[:-2], w.shape[-2]
-    return np.ascontiguousarray(np.moveaxis(w[..., :3], -1, -2)).reshape(*lead, 3 * U)
+from .think_and_tell import CaptionGenerator as _CaptionGeneratorLSTM
 
 
 class Encoder:
@@ -54,8 +42,6 @@ class Decoder:
 
 
 class CaptionGenerator(_CaptionGeneratorLSTM):
-    GRU = ("gru/kernel", "gru/recurrent_kernel", "gru/bias")
-
     def __init__(self, encoder, decoder, tokenizer=None, max_length=15, **kw):
         super().__init__(encoder, decoder, tokenizer, max_length, **kw)
         self.sat = False
@@ -90,20 +76,6 @@ class CaptionGenerator(_CaptionGeneratorLSTM):
         self.set_weight("fc_vocab/kernel", glorot((U, V)))
         if self.optimizer is not None:
             self._init_optimizer_state()
-
-    def set_weight(self, name, arr):
-        arr = np.asarray(arr, dtype=np.float32)
-        assert tuple(arr.shape) == tuple(self.keras_shapes[name]), (name, arr.shape, self.keras_shapes[name])
-        if name in self.GRU:
-            dst = self.arena.p(name)
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(interleave3(arr, self.U))).view(dst.shape))
-            return
-        super().set_weight(name, arr)
-
-    def _unpack(self, name, t):
-        if name in self.GRU:
-            return deinterleave3(t.detach().cpu().numpy())
-        return super()._unpack(name, t)
 
     # ------------------------------------------------------------------ buffers
     def _build(self, B, T):
