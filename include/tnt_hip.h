@@ -1064,6 +1064,32 @@ int32_t tnt_sam_f32(float* theta, float* grad, float* ew, const int32_t* span_se
  * weights, moments, t and the dropout stream exactly as they were, so the caller can redo it. */
 int32_t tnt_step_tick(int64_t* adam_t, uint32_t* drop_step, const float* lr, float* lr_t,
                       float beta1, float beta2, const uint32_t* guard, void* stream);
+/* Weight averaging over the parameter arena (average.hip), one launch behind the optimizer update: an exponential moving
+ * average (kind 0; tfa.optimizers.MovingAverage) or an equal-weight running mean (kind 1; tfa.optimizers.SWA) of theta in
+ * avg; restated by tests/average_oracle.py.  This library's definition.  Every decision is taken on the device when the
+ * launch runs, from *step (int64: the updates applied so far, the model's adam_t after its tick) and *guard, so a
+ * recorded plan or a hipGraph replays with the live values; the scalars are uniform over the launch:
+ *  - guard (nullable) non-zero: nothing is read or written.
+ *  - t = *step, s = max(start_step, 1).  t <= s: the launch copies, avg[i] = theta[i].  The average is seeded by the
+ *    parameters after update s and never depends on what avg held before.
+ *  - otherwise r = t - s; r % every != 0: nothing happens; else k = r / every (>= 1) samples follow the seed and
+ *      kind 0: d = momentum; with dynamic != 0, d = min(momentum, (1 + k) / (10 + k))   (tfa's dynamic_decay)
+ *      kind 1: d = k / (k + 1)                                   (the mean of the seed and the k later samples)
+ *    in float64; c = (float)(1.0 - d); avg[i] = fmaf(c, theta[i] - avg[i], avg[i]) in float32: two roundings per element.
+ * theta is never written.  momentum is a HOST pointer to one float64, read during the call (the scalars this ABI passes
+ * by value are 32/64-bit integers and float; a float64 travels by address, as tnt_scheduled_feedback_f32's sched does --
+ * here from host memory, so that the entry can check it).  TNT_BADARG, and no launch, for n < 0, null theta / avg / step
+ * / momentum, theta or avg not 16-byte aligned, theta and avg overlapping, kind other than 0 / 1, momentum outside
+ * [0, 1) or NaN, start_step < 0, every < 1.  n == 0 is a no-op.  Float4 main path over a grid-stride range, n % 4 tail;
+ * avg moves non-temporally under the TNT_STREAM_NT policy of the optimizer kernels; no atomics, LDS or scratch; every
+ * address is written by one thread. */
+int32_t tnt_weight_average_f32(const float* theta, float* avg, int64_t n, const int64_t* step, int32_t kind,
+                               const double* momentum, int32_t dynamic, int64_t start_step, int32_t every,
+                               const uint32_t* guard, void* stream);
+/* a <-> b over n floats, every element moved by one thread (ModelBase.swap_weights: captured graphs and plans hold the
+ * buffers' addresses, so the contents move).  TNT_BADARG, and no launch, for n < 0, a null or not 16-byte aligned
+ * pointer, overlapping buffers.  n == 0 is a no-op. */
+int32_t tnt_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 /* ---- region-wise encoder: layers.LocallyDense.call (layers.py:43-48) ------------
  * CSR groups: idx[goff[r] .. goff[r+1]) are the voxel columns of group r; W is the

@@ -143,6 +143,8 @@ SIGNATURES = {
     "tnt_agc_f32": [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, F32, F32, P],
     "tnt_colsq_f32": [P, P, I32, I32, I32, P],
     "tnt_step_tick": [P, P, P, P, F32, F32, P, P],
+    "tnt_weight_average_f32": [P, P, I64, P, I32, P, I32, I64, I32, P, P],
+    "tnt_swap_f32": [P, P, I64, P],
     "tnt_sam_f32": [P, P, P, P, P, P, P, P, P, I32, I32, F32, I32, P],
     "tnt_gemm_f32_tile": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, I32, I32, P],
     "tnt_block_dense_dx_f32": [P, P, P, I32, I32, I32, I32, P],

@@ -86,7 +86,27 @@ class ModelCheckpoint(Callback):
             self.best = self.sign * cur
         path = self.filepath.format(epoch=epoch + 1, **logs)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        self._save(path)
+
+    def _save(self, path):
         self.model.save_weights(path)
+
+
+class AverageModelCheckpoint(ModelCheckpoint):
+    """tfa.callbacks.AverageModelCheckpoint(update_weights, filepath, ...): ModelCheckpoint for a model compiled with
+    optimizers.MovingAverage / SWA that writes the averaged weights (``save_weights(path, averaged=True)``).
+    ``update_weights=True`` also makes them the model's weights (``assign_average_vars``), as tfa's callback does;
+    False leaves the model as it is."""
+
+    def __init__(self, update_weights, filepath, monitor="val_loss", verbose=0, save_weights_only=True, save_best_only=False,
+                 mode="min", period=1):
+        super().__init__(filepath, monitor, verbose, save_weights_only, save_best_only, mode, period)
+        self.update_weights = bool(update_weights)
+
+    def _save(self, path):
+        if self.update_weights:
+            self.model.assign_average_vars()
+        self.model.save_weights(path, averaged=True)
 
 
 class EarlyStopping(Callback):

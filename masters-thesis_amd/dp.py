@@ -431,6 +431,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if getattr(model, "self_critical", None) is not None:
         # nic.NIC(self_critical=...): the step's host round trip has no data-parallel schedule
         raise NotImplementedError("data parallel self-critical training is not supported: train it on one device")
+    if model.__dict__.get("average") is not None:
+        # compile(optimizers.MovingAverage / SWA): the averaging launch has no place in the data-parallel schedules
+        raise NotImplementedError(model.AVERAGE_DP_REFUSAL)
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.__dict__.get("agc") and world > 1:

@@ -9,13 +9,13 @@ launches and owns buffers; it contains no arithmetic of the hot path.
 """
 import time
 from collections import OrderedDict
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 
 import numpy as np
 import torch
 
 from . import ops
-from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood
+from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood, optimizer_average
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -824,6 +824,7 @@ class ModelBase:
         self.loss = None
         self.label_smoothing = 0.0          # of the compile loss (CategoricalCrossentropy(label_smoothing=...))
         self.unlikelihood = 0.0             # of the compile loss (CategoricalCrossentropy(unlikelihood=...))
+        self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
         self.built = False
         self.stop_training = False
         self._graphs = {}
@@ -849,6 +850,9 @@ class ModelBase:
         if alpha > 0 and getattr(self, "self_critical", None) is not None:
             raise ValueError("unlikelihood > 0 does not apply to a self_critical model: its loss is the "
                              "advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        avg = optimizer_average(optimizer)
+        if avg is not None and self.grad_sync is not None:
+            raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
         # fixed here, not read per step: the head launch sits inside captured graphs
@@ -856,6 +860,10 @@ class ModelBase:
             self._graphs = {}
         self.label_smoothing = eps
         self.unlikelihood = alpha
+        # the averaging launch sits inside the same plans / graphs, and its settings are launch arguments
+        if avg != self.__dict__.get("average"):
+            self._graphs = {}
+        self.average = avg
         if self.built:
             self._init_optimizer_state()
 
@@ -884,9 +892,24 @@ class ModelBase:
         self.lr_dev = torch.tensor([self.optimizer.lr], dtype=torch.float32, device=self.device)
         self.lr_t_dev = self._f(1)
         self._lr_host = self.optimizer.lr
+        # the weight average (optimizers.MovingAverage / SWA): one more slot over the whole arena, padding included (zero in
+        # both buffers, and it stays zero).  The first averaging launch overwrites it with the parameters after update
+        # max(start_step, 1); until then it holds the initial ones
+        self.opt_avg = a.theta.clone() if self.__dict__.get("average") is not None else None
+        self._swapped = False
         self._graphs = {}
 
+    AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
+                          "schedules update the arena in slices and the row-sharded encoder finishes its update behind "
+                          "_update_fused, so one averaging launch behind the update has no single place there.  Train it on "
+                          "one device")
+
     def _sync_lr(self):
+        """in front of the update of every training step: the host-set learning rate to the device -- and the refusal of a
+        step while the average sits in the weights (swap_weights / averaged_weights)"""
+        if self.__dict__.get("_swapped"):
+            raise RuntimeError("the averaged weights are swapped in (swap_weights / averaged_weights): a training step would "
+                               "train the average and average the raw weights.  Swap back first")
         if self.optimizer.lr != self._lr_host:
             self.lr_dev.fill_(self.optimizer.lr)
             self._lr_host = self.optimizer.lr
@@ -904,6 +927,20 @@ class ModelBase:
             be.step_tick(self.adam_t, self.drop_step, self.lr_dev, None, 0.0, 0.0, guard=gd)
             be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
                    sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+        # the tick precedes the update here: adam_t is the number of applied updates when the averaging launch starts
+        self._average_update()
+
+    def _average_update(self):
+        """The averaging launch of a step (tnt_weight_average_f32 over the whole arena): the step's last launch, behind its
+        last update launch and inside the same recorded plan / graph.  Copy, skip or blend is decided on the device from
+        adam_t, which must equal the number of applied updates by then, and from the guard word.  Nothing without an
+        averaging optimizer."""
+        av = self.__dict__.get("average")
+        if av is None:
+            return
+        a = self.arena
+        self.be.weight_average(a.theta, self.opt_avg, a.total, self.adam_t, av.kind_id, av.momentum, av.dynamic, av.start_step,
+                               av.every, guard=self._guard_word())
 
     def _update_fused(self, l2_out, skip_first=False):
         """single-process update: [AGC] -> span norms -> ONE finalize launch (per-variable norms, L2 metric, the step's
@@ -995,6 +1032,9 @@ class ModelBase:
                                              beta1=opt.beta_1, beta2=opt.beta_2, guard=gd, **kw)
             be.adam_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
                         a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], **self._ring_args())
+            # the counters tick when the last workgroup of the Adam launch arrives, behind the encoder's update: adam_t is
+            # the number of applied updates when the averaging launch starts
+            self._average_update()
             return
         be.step_finalize(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, adam_t=self.adam_t,
                          drop_step=self.drop_step, lr=self.lr_dev, lr_t=self.lr_t_dev if adam else None,
@@ -1011,6 +1051,8 @@ class ModelBase:
         else:
             be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
                    sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+        # the finalize launch ticked in front of the update launches: adam_t is the number of applied updates here too
+        self._average_update()
 
     # ------------------------------------------------------------------ BatchNorm, optionally synchronised across replicas
     def _sync_bn_on(self):
@@ -1411,28 +1453,76 @@ class ModelBase:
                 raise KeyError(n)
 
     def get_optimizer_slot(self, name, slot):
-        """Adam first ('m') / second ('v') moment (SGD: 'm' = momentum) of one trainable, in the keras layout."""
-        buf = self.opt_m if slot == "m" else self.opt_v
+        """Adam first ('m') / second ('v') moment (SGD: 'm' = momentum) of one trainable, or its weight average
+        ('average', with optimizers.MovingAverage / SWA; the same values while it is swapped in), in the keras layout."""
+        if slot == "average":
+            buf = self._average_buf("get_optimizer_slot(..., 'average')")
+            buf = self.arena.theta if self._swapped else buf
+        else:
+            buf = self.opt_m if slot == "m" else self.opt_v
         return self._unpack(name, self.arena.slot(buf, name))
+
+    # ------------------------------------------------------------------ weight average (optimizers.MovingAverage / SWA)
+    def _average_buf(self, what):
+        """opt_avg; ValueError on a model compiled without averaging"""
+        if self.__dict__.get("average") is None:
+            raise ValueError(f"{what} needs a model compiled with an averaging optimizer (optimizers.MovingAverage / SWA)")
+        if self.__dict__.get("opt_avg") is None:
+            raise RuntimeError(f"{what}: the average exists once the optimizer state does, from the first training step on")
+        return self.opt_avg
+
+    def swap_weights(self):
+        """Exchanges the weights and their average in place (tnt_swap_f32): what every launch reads as the weights is the
+        average until the next call.  Captured graphs and launch plans hold the buffers' addresses, so the contents move,
+        not the tensors, and nothing is re-captured; no decode or evaluation path keeps a buffer derived from the weights
+        across calls.  BatchNorm moving statistics are not averaged and stay.  While swapped a training step is refused."""
+        avg = self._average_buf("swap_weights")
+        self.be.swap(self.arena.theta, avg, self.arena.total)
+        self._swapped = not self._swapped
+
+    @contextmanager
+    def averaged_weights(self):
+        """``with model.averaged_weights():`` predict / evaluate with the averaged weights: swaps in, and swaps back on the
+        way out, also on an exception."""
+        self._average_buf("averaged_weights")
+        if self._swapped:
+            raise RuntimeError("the averaged weights are already swapped in")
+        self.swap_weights()
+        try:
+            yield self
+        finally:
+            self.swap_weights()
+
+    def assign_average_vars(self):
+        """tfa's name: the average becomes the weights (a copy; the average stays), for the end of training."""
+        avg = self._average_buf("assign_average_vars")
+        if self._swapped:
+            raise RuntimeError("the averaged weights are swapped in: swap back before assign_average_vars")
+        self.arena.theta.copy_(avg)
 
     def get_layer(self, name):
         if name not in self.layers_spec:
             raise ValueError(f"No such layer: {name}")
         return _LayerView(self, name, self.layers_spec[name])
 
-    def save_weights(self, path):
-        """ModelCheckpoint(save_weights_only=True) target (main.py:168-190).  ``*.h5`` / ``*.hdf5``: a Keras weight file
+    def save_weights(self, path, averaged=False):
+        """ModelCheckpoint(save_weights_only=True) target (main.py:168-190).  ``averaged=True`` (optimizers.MovingAverage /
+        SWA): the trainables are written from their weight average, BatchNorm moving statistics as they are.  ``*.h5`` / ``*.hdf5``: a Keras weight file
         (layer_names / weight_names attributes, one float32 dataset per weight, keras layouts), written by the
         pure-Python h5lite module -- readable by h5py / Keras ``load_weights(by_name=True)`` wherever the layer names
         agree.  Anything else: ``.npz`` with the same names and layouts."""
         path = str(path)
+        get = self.get_weight
+        if averaged:
+            self._average_buf("save_weights(averaged=True)")
+            get = lambda n: self.get_optimizer_slot(n, "average") if n in self.arena.entries else self.get_weight(n)
         if path.endswith((".h5", ".hdf5")):
             from . import h5lite
-            layers = OrderedDict((layer, [(f"{layer}/{w}:0", self.get_weight(f"{layer}/{w}")) for w in ws])
+            layers = OrderedDict((layer, [(f"{layer}/{w}:0", get(f"{layer}/{w}")) for w in ws])
                                  for layer, ws in self.layers_spec.items())
             h5lite.write_keras_weights(path, layers)
             return
-        arrs = {k.replace("/", "__"): v for k, v in self.get_weights_dict().items()}
+        arrs = {n.replace("/", "__"): get(n) for n in self.keras_shapes}
         with open(path, "wb") as f:
             np.savez(f, **arrs)
 
@@ -2038,7 +2128,7 @@ class ModelBase:
 
     # ------------------------------------------------------------------ fit loop
     def fit(self, x=None, epochs=1, steps_per_epoch=None, batch_size=None, callbacks=None, validation_data=None,
-            validation_steps=None, initial_epoch=0, verbose=1, keras_last_batch_logs=False, **kw):
+            validation_steps=None, initial_epoch=0, verbose=1, keras_last_batch_logs=False, validation_averaged=False, **kw):
         """model.fit(generator, epochs, steps_per_epoch, batch_size, callbacks, validation_data,
         validation_steps, initial_epoch) -- main.py:269-281.  Honours the keras callback protocol
         (on_train_begin, on_epoch_begin, on_train_batch_end, on_test_batch_end, on_epoch_end,
@@ -2049,7 +2139,12 @@ class ModelBase:
         ModelCheckpoint(save_best_only) / EarlyStopping on ``val_loss``); the mean is the default because it is
         what those callbacks are meant to see.
         Data parallel: the epoch logs are averaged over the ranks and ``stop_training`` is OR-ed before the
-        callbacks' decision takes effect, so every rank leaves the loop in the same epoch."""
+        callbacks' decision takes effect, so every rank leaves the loop in the same epoch.
+        ``validation_averaged=True`` (optimizers.MovingAverage / SWA): the validation pass of every epoch runs inside
+        ``averaged_weights()``, so the ``val_*`` logs are the averaged model's."""
+        if validation_averaged and self.__dict__.get("average") is None:
+            raise ValueError("fit(validation_averaged=True) needs a model compiled with an averaging optimizer "
+                             "(optimizers.MovingAverage / SWA)")
         callbacks = list(callbacks or [])
         for cb in callbacks:
             if hasattr(cb, "set_model"):
@@ -2077,15 +2172,16 @@ class ModelBase:
             if validation_data is not None:
                 nv = len(validation_data) if validation_steps is None else validation_steps
                 vs, vlast = {}, {}
-                for b in range(nv):
-                    try:
-                        logs = self.test_step(validation_data[b]).as_floats()
-                    except DeviceGuardError:
-                        logs = self.test_step(validation_data[b]).as_floats()
-                    for k, v in logs.items():
-                        vs[k] = vs.get(k, 0.0) + v
-                    vlast = logs
-                    _call(callbacks, "on_test_batch_end", b, logs)
+                with (self.averaged_weights() if validation_averaged else nullcontext()):
+                    for b in range(nv):
+                        try:
+                            logs = self.test_step(validation_data[b]).as_floats()
+                        except DeviceGuardError:
+                            logs = self.test_step(validation_data[b]).as_floats()
+                        for k, v in logs.items():
+                            vs[k] = vs.get(k, 0.0) + v
+                        vlast = logs
+                        _call(callbacks, "on_test_batch_end", b, logs)
                 elogs.update({f"val_{k}": v for k, v in vlast.items()} if keras_last_batch_logs else
                              {f"val_{k}": v / max(nv, 1) for k, v in vs.items()})
             if self.dp_world > 1:

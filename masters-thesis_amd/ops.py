@@ -711,6 +711,20 @@ class HipBackend:
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
 
+    def weight_average(self, theta, avg, n, step, kind, momentum, dynamic, start_step, every, guard=None):
+        """one averaging launch over n parameters (tnt_weight_average_f32; definition in include/tnt_hip.h): copy, skip
+        or blend decided on the device from ``step`` (the updates applied so far) and ``guard``; kind 0 EMA, 1 SWA"""
+        # the entry reads momentum through a host pointer; one float64 per distinct value, alive as long as the backend
+        # (recorded launch plans re-issue the call)
+        keep = self.__dict__.setdefault("_f64", {})
+        mom = keep.setdefault(float(momentum), _ct.c_double(float(momentum)))
+        self._call(self.lib.tnt_weight_average_f32, "tnt_weight_average_f32", _p(theta), _p(avg), int(n), _p(step), int(kind),
+                   _ct.addressof(mom), int(bool(dynamic)), int(start_step), int(every), _p(guard), self._s())
+
+    def swap(self, a, b, n):
+        """a <-> b over n floats, in place (tnt_swap_f32)"""
+        self._call(self.lib.tnt_swap_f32, "tnt_swap_f32", _p(a), _p(b), int(n), self._s())
+
     def block_dense_dx(self, dpre, W, dx, B, R, Din, Dout):
         self._call(self.lib.tnt_block_dense_dx_f32, "tnt_block_dense_dx_f32", _p(dpre), _p(W), _p(dx), B, R, Din, Dout, self._s())
 

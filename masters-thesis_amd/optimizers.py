@@ -49,6 +49,124 @@ class SGD:
         self.lr = float(v)
 
 
+class Average:
+    """What an averaging wrapper hands ``ModelBase.compile`` (its ``average`` attribute): the arguments of the averaging
+    launch, tnt_weight_average_f32 (definition in include/tnt_hip.h).  kind "ema" / "swa"; momentum: the EMA decay;
+    dynamic: tfa's dynamic_decay; start_step: the update that seeds the average (at least the first); every: one sample
+    per ``every`` updates behind the seed."""
+
+    KINDS = ("ema", "swa")
+    __slots__ = ("kind", "momentum", "dynamic", "start_step", "every")
+
+    def __init__(self, kind, momentum, dynamic, start_step, every):
+        if kind not in self.KINDS:
+            raise ValueError(f"average kind must be one of {self.KINDS}, got {kind!r}")
+        self.kind, self.momentum, self.dynamic = kind, check_average_decay(momentum), bool(dynamic)
+        self.start_step = _check_count("start_step", start_step, 0)
+        self.every = _check_count("every", every, 1)
+
+    @property
+    def kind_id(self):
+        return self.KINDS.index(self.kind)
+
+    def key(self):
+        return (self.kind, self.momentum, self.dynamic, self.start_step, self.every)
+
+    def __eq__(self, other):
+        return isinstance(other, Average) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return (f"Average(kind={self.kind!r}, momentum={self.momentum}, dynamic={self.dynamic}, start_step={self.start_step}, "
+                f"every={self.every})")
+
+
+def _delegate(name):
+    def get(self):
+        return getattr(self._optimizer, name)
+
+    def put(self, v):
+        setattr(self._optimizer, name, v)
+    return property(get, put)
+
+
+class _AveragedOptimizer:
+    """An Adam / SGD descriptor with a weight average beside it.  The update is the wrapped optimizer's, unchanged: the
+    hyper-parameters are read from and written to the wrapped object (so LearningRateScheduler keeps working), and
+    ``average`` tells ``ModelBase.compile`` to keep one more slot, ``opt_avg``, that one tnt_weight_average_f32 launch
+    advances behind every update (ModelBase._average_update)."""
+
+    kind = _delegate("kind")
+    lr = _delegate("lr")
+    learning_rate = _delegate("learning_rate")
+    beta_1 = _delegate("beta_1")
+    beta_2 = _delegate("beta_2")
+    epsilon = _delegate("epsilon")
+    clipnorm = _delegate("clipnorm")
+    momentum = _delegate("momentum")
+    iterations = _delegate("iterations")
+
+    def __init__(self, optimizer, average):
+        if getattr(optimizer, "average", None) is not None:
+            raise ValueError(f"{type(self).__name__} wraps an Adam or SGD descriptor, not another averaging wrapper")
+        if getattr(optimizer, "kind", None) not in ("adam", "sgd"):
+            raise ValueError(f"{type(self).__name__} wraps an Adam or SGD descriptor, got {optimizer!r}")
+        self._optimizer, self.average = optimizer, average
+
+
+class MovingAverage(_AveragedOptimizer):
+    """tfa.optimizers.MovingAverage(optimizer, average_decay, num_updates, start_step, dynamic_decay): an exponential
+    moving average of the trained parameters, avg += (1 - d) (theta - avg) behind every update, d = average_decay; with
+    ``dynamic_decay`` d = min(average_decay, (1 + k) / (10 + k)) for the k-th sample.  The average is seeded with the
+    parameters after update max(start_step, 1) -- it never holds the initial weights -- and ``every`` (this library's
+    own) takes one sample per ``every`` updates.  ``num_updates`` is refused: the dynamic rule counts its own samples.
+    Use: model.compile(MovingAverage(Adam(...))), then model.averaged_weights() / swap_weights() /
+    assign_average_vars() / save_weights(path, averaged=True) / callbacks.AverageModelCheckpoint."""
+
+    def __init__(self, optimizer, average_decay=0.99, num_updates=None, start_step=0, dynamic_decay=False, every=1):
+        if num_updates is not None:
+            raise NotImplementedError("num_updates is not implemented: dynamic_decay counts the samples the average has taken")
+        super().__init__(optimizer, Average("ema", average_decay, dynamic_decay, start_step, every))
+
+
+class SWA(_AveragedOptimizer):
+    """tfa.optimizers.SWA(optimizer, start_averaging, average_period): stochastic weight averaging (Izmailov et al. 2018),
+    the equal-weight mean of the parameters after update max(start_averaging, 1) and after every ``average_period``-th
+    update behind it.  Use as MovingAverage."""
+
+    def __init__(self, optimizer, start_averaging=0, average_period=10):
+        super().__init__(optimizer, Average("swa", 0.0, False, start_averaging, average_period))
+
+
+def check_average_decay(d):
+    """the value as a float; ValueError unless 0 <= d < 1 (NaN included)"""
+    try:
+        v = float(d)
+    except (TypeError, ValueError):
+        raise ValueError(f"average_decay must be a number in [0, 1), got {d!r}") from None
+    if isinstance(d, bool) or not 0.0 <= v < 1.0:
+        raise ValueError(f"average_decay must be in [0, 1), got {d!r}")
+    return v
+
+
+def _check_count(name, v, lo):
+    """the value as an int; ValueError unless it is an integer >= lo (bool excluded)"""
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo or v >= 2 ** 31:
+        raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
+    return int(v)
+
+
+def optimizer_average(optimizer):
+    """the Average of a compile() optimizer argument: None for a plain descriptor"""
+    avg = getattr(optimizer, "average", None)
+    if avg is not None and not isinstance(avg, Average):
+        raise ValueError(f"optimizer.average must be an optimizers.Average or None, got {avg!r}")
+    return avg
+
+
 class CategoricalCrossentropy:
     """tf.keras.losses.CategoricalCrossentropy(from_logits=False, reduction='none') -- main.py:107-110.
     Only this configuration is implemented by the fused softmax+CE kernel.  ``label_smoothing`` (keras: the target
