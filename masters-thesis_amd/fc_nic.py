@@ -23,6 +23,7 @@ import torch
 from .arena import ParamArena
 from .model_base import (Metrics, _r4, S_IN, S_TEXT, S_OUT, S_LSTM_IN, S_LSTM_OUT, BN_EPS, BN_MOMENTUM)
 from .nic import NIC as _DenseNIC
+from .lstm_layer import lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY
 
 
@@ -163,14 +164,8 @@ class NICfc(_DenseNIC):
             be.dropout(self.text, self.text, n, E, E, B, E, 0, self.r_lstm, sd, S_LSTM_IN + 1, 0, ds)
         self.gemm_sk(self.text, a.p("lstm/kernel"), self.XZ, n, 4 * U, E, E, 4 * U, 4 * U)   # bias: in the step kernel
         Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
-        if self._seq_lstm:       # the T masked steps (:318) as one persistent launch, see nic.NIC._forward
-            be.lstm_seq_fwd(self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 0, self.Out, self.gates, T, B, U, self.seq_sync,
-                            self._guard_out())
-        else:
-            for t in range(T):                                                                      # :318
-                be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, self.cap, T, t,
-                                 self.Out[t - 1] if t > 0 else None, self.Hs[t + 1], self.Cs[t + 1], self.Out[t],
-                                 self.gates[t], B, U, xz_bias=bl)
+        lstm_layer_fwd(be, self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 0, self.Out, self.gates, T, B, U,
+                       chain=self._seq_chain())                                                     # :318, the T masked steps
         out = self.Out
         if training and self.r_lstm > 0:                                                            # :321
             be.dropout(self.Out, self.Out_d, n, U, U, B, U, 0, self.r_lstm, sd, S_LSTM_OUT, 0, ds)
@@ -204,19 +199,8 @@ class NICfc(_DenseNIC):
         self.gemm_sk(self.dinter, a.p("time_distributed_nonlinear/kernel"), self.dOut, n, U, H, H, H, U, transB=True)
         if self.r_lstm > 0:
             be.dropout(self.dOut, self.dOut, n, U, U, B, U, 0, self.r_lstm, sd, S_LSTM_OUT, 0, ds)
-        Ur = a.p("lstm/recurrent_kernel")
-        dOut = self.dOut.view(T, B, U)
-        seqb = self._seq_lstm and self.seq_xch is not None
-        if seqb:       # BPTT as one persistent launch, see nic.NIC._bwd_seq_lstm
-            be.lstm_seq_bwd(Ur, dOut, self.cap, T, 0, self.gates, self.Cs, self.dZ, self.seq_xch, T, B, U, self.seq_sync,
-                            self._guard_out())
-        else:
-            for t in range(T - 1, -1, -1):
-                last = t == T - 1
-                be.lstm_step_bwd(None if last else self.dZ[(t + 1) * B:(t + 2) * B], Ur, None if last else self.da_pass,
-                                 None, None if last else self.dc, None if last else self.dout, dOut[t], self.cap, T, t,
-                                 self.gates[t], self.Cs[t + 1], self.Cs[t], self.dZ[t * B:(t + 1) * B], self.da_pass,
-                                 self.dc, self.dout, B, U)
+        lstm_layer_bwd(be, a.p("lstm/recurrent_kernel"), self.dOut, self.cap, T, 0, self.gates, self.Cs, self.dZ,
+                       (self.da_pass, self.dc, self.dout), T, B, U, chain=self._seq_chain(bwd=True))
         hprev = self.Hs[:T].view(n, U)
         self.gemm_sk(hprev, self.dZ, a.g("lstm/recurrent_kernel"), U, 4 * U, n, U, 4 * U, 4 * U, transA=True)
         self.gemm_sk(self.text, self.dZ, a.g("lstm/kernel"), E, 4 * U, n, E, 4 * U, 4 * U, transA=True)
@@ -274,22 +258,17 @@ class NICfc(_DenseNIC):
         start = self._to_dev(np.asarray(start_seq).reshape(-1), torch.int32)
         B = start.shape[0]
         self._stage_inputs((img_input, torch.zeros(B, max(1, max_len), dtype=torch.int32), a0, c0))
-        U, E, V, H, ldV = self.U, self.E, self.V, self.H, self.ldV
+        U, V, H, ldV = self.U, self.V, self.H, self.ldV
         self._encode(B, False)
-        Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
         xz, emb = self.XZ[:B], self.text[:B]
         h, c = [self.Hs[0], self.Hs[1]], [self.Cs[0], self.Cs[1]]
-        self.gemm_sk(self.feat, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-        be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, None, 0, 0, None, h[1], c[1], None, self.gates[0], B, U)   # :520
+        self._feature_step(self.feat, B, xz, h[0], c[0], h[1], c[1], self.gates[0])                   # :520
         cur = 1
         words = start.clone().view(B, 1)
         ids = torch.zeros(max_len, B, dtype=torch.int32, device=self.device)
         probs = self.logits[:B]
         for i in range(max_len):
-            be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, B, 1, E, E, V)
-            self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-            be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, words if i > 0 else None, 1, 0, None, h[1 - cur],
-                             c[1 - cur], None, self.gates[0], B, U)                                   # :529
+            self._text_step(words, i == 0, B, emb, xz, h[cur], c[cur], h[1 - cur], c[1 - cur], None, self.gates[0])   # :529
             cur = 1 - cur
             self.gemm_sk(h[cur], a.p("time_distributed_nonlinear/kernel"), self.inter[:B], B, H, U, U, H, H,
                          bias=a.p("time_distributed_nonlinear/bias"), act=ACT_LEAKY, slope=0.2)       # :531

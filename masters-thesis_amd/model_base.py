@@ -1655,6 +1655,13 @@ class ModelBase:
         """Where the persistent kernel reports its error code for the host: slot GUARD of the metrics buffer."""
         return self.met[self.GUARD:self.GUARD + 1]
 
+    def _seq_chain(self, bwd=False):
+        """The ``chain`` argument of lstm_layer_fwd / lstm_layer_bwd (``bwd``: with the BPTT's exchange buffer) while the
+        persistent kernel is in use, else None: the per-step kernels."""
+        if not self._seq_lstm or (bwd and self.seq_xch is None):
+            return None
+        return (self.seq_sync, self._guard_out()) + ((self.seq_xch,) if bwd else ())
+
     def _run_step(self, run, key, fn):
         """``run(key, fn)`` (_run_captured / _run_planned) for a training step; returns whether that step's finalize launch
         filed the metrics vector in the ring (known when ``fn`` actually runs -- eager or under capture --, remembered per

@@ -21,6 +21,7 @@ from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
                          _TokenChoice, _BeamDecode)
+from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
@@ -319,20 +320,9 @@ class NIC(ModelBase):
             self.gemm_sk(xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U)
         Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
         compact = bool(training and self.__dict__.get("_compact"))       # _head_map_bufs: Out and logits hold the distinct rows
-        if self._seq_lstm:
-            # both LSTM calls (NIC.py:138,140) as ONE persistent launch: the T+1 dependent steps pay an XCD-local barrier
-            # each instead of a kernel launch, the recurrent weights stay in VGPRs (tnt_lstm_seq_fwd_f32)
-            be.lstm_seq_fwd(self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 1, self.Out, self.gates, T + 1, B, U,
-                            self.seq_sync, self._guard_out(), **(dict(out_pos=self.head_pos) if compact else {}))
-        else:
-            # lstm call 1: the feature, one unmasked step (NIC.py:138)
-            be.lstm_step_fwd(self.XZ[:B], self.Hs[0], self.Cs[0], Ur, None, None, 0, None, 0, 0, None, self.Hs[1],
-                             self.Cs[1], None, self.gates[0], B, U, xz_bias=bl)
-            # lstm call 2: the text, masked by the Embedding mask (NIC.py:140)
-            for t in range(1, T + 1):
-                be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, self.cap, T,
-                                 t - 1, self.Out[t - 2] if t > 1 else None, self.Hs[t + 1], self.Cs[t + 1],
-                                 self.Out[t - 1], self.gates[t], B, U, xz_bias=bl)
+        # both LSTM calls: the feature, one unmasked step (NIC.py:138), and the text, masked by the Embedding mask (:140)
+        lstm_layer_fwd(be, self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 1, self.Out, self.gates, T + 1, B, U,
+                       chain=self._seq_chain(), out_pos=self.head_pos if compact else None)
         if compact:
             # rows [0, live) only; the tile is planned for the live count seen at the warm-up step (any count is correct)
             self.gemm3(self.Out, a.p("time_distributed_softmax/kernel"), self.logits, T * B, V, U, U, ldV, ldV,
@@ -363,13 +353,12 @@ class NIC(ModelBase):
         Wo, bo = a.p("time_distributed_softmax/kernel"), a.p("time_distributed_softmax/bias")
         table = a.p("emb_text/embeddings")
         self.gemm_sk(xin, Wl, self.XZ, 2 * B, 4 * U, E, E, 4 * U, 4 * U)
-        be.lstm_step_fwd(self.XZ[:B], self.Hs[0], self.Cs[0], Ur, None, None, 0, None, 0, 0, None, self.Hs[1],
-                         self.Cs[1], None, self.gates[0], B, U, xz_bias=bl)
+        step = lambda s: lstm_layer_step_fwd(be, s, self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 1, self.Out, self.gates,
+                                             B, U)
+        step(0)
         rate = self.r_lstm if drop_l else 0.0
         for t in range(1, T + 1):
-            be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, self.cap, T,
-                             t - 1, self.Out[t - 2] if t > 1 else None, self.Hs[t + 1], self.Cs[t + 1],
-                             self.Out[t - 1], self.gates[t], B, U, xz_bias=bl)
+            step(t)
             logits = self.logits[(t - 1) * B:t * B]
             self.gemm_sk(self.Out[t - 1], Wo, logits, B, V, U, U, ldV, ldV, bias=bo)
             if t < T:
@@ -471,23 +460,9 @@ class NIC(ModelBase):
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
         R1 = (T + 1) * B
         sd, ds = self.seed, self.drop_step
-        Ur = a.p("lstm/recurrent_kernel")
-        dOut = self.dOut.view(T, B, U)
-        if self._seq_lstm and self.seq_xch is not None:
-            # the T+1 dependent backward steps as ONE persistent launch (tnt_lstm_seq_bwd_f32): weights stationary, the
-            # recurrent product pushed as partial tiles through the XCD's L2
-            be.lstm_seq_bwd(Ur, dOut, self.cap, T, 1, self.gates, self.Cs, self.dZ, self.seq_xch, T + 1, B, U, self.seq_sync,
-                            self._guard_out(), **(dict(dout_pos=self.head_pos) if self.__dict__.get("_compact") else {}))
-        else:
-            for t in range(T, 0, -1):
-                first = t == T
-                be.lstm_step_bwd(None if first else self.dZ[(t + 1) * B:(t + 2) * B], Ur,
-                                 None if first else self.da_pass, None, None if first else self.dc,
-                                 None if first else self.dout, dOut[t - 1], self.cap, T, t - 1, self.gates[t],
-                                 self.Cs[t + 1], self.Cs[t], self.dZ[t * B:(t + 1) * B], self.da_pass, self.dc, self.dout,
-                                 B, U)
-            be.lstm_step_bwd(self.dZ[B:2 * B], Ur, self.da_pass, None, self.dc, None, None, None, 0, 0, self.gates[0],
-                             self.Cs[1], self.Cs[0], self.dZ[:B], None, None, None, B, U)
+        lstm_layer_bwd(be, a.p("lstm/recurrent_kernel"), self.dOut, self.cap, T, 1, self.gates, self.Cs, self.dZ,
+                       (self.da_pass, self.dc, self.dout), T + 1, B, U, chain=self._seq_chain(bwd=True),
+                       dout_pos=self.head_pos if self.__dict__.get("_compact") else None, pass_out_last=False)
         xin = self._xin_used
         self._dxin_done = False
         if getattr(self, "g3_riders", True) and E == U:
@@ -731,17 +706,14 @@ class NIC(ModelBase):
         position i into greedy[i], on slices of the step's buffers (rows [0, B) of enc_y, Xin, XZ, Hs[1..2], Cs[1..2],
         gates[0], Out[0], logits) before the rollout overwrites them"""
         be, a, st = self.be, self.arena, self._scst
-        U, E, V, ldV = self.U, self.E, self.V, self.ldV
+        U, V, ldV = self.U, self.V, self.ldV
         h, c = [self.Hs[1][:B], self.Hs[2][:B]], [self.Cs[1][:B], self.Cs[2][:B]]
         self._decode_encode(B, (st["x"], st["h0"], st["c0"], h[0], c[0]))
-        Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
         xz, emb, out, probs, ids = self.XZ[:B], self.Xin[B:2 * B], self.Out[0][:B], self.logits[:B], st["greedy"]
         for i in range(T):
             tok = st["start"] if i == 0 else ids[i - 1].view(B, 1)
-            be.embedding_fwd(a.p("emb_text/embeddings"), tok, emb, B, 1, E, E, V)
-            self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-            be.lstm_step_fwd(xz, h[i & 1], c[i & 1], Ur, None, None, 0, tok if i > 0 else None, 1, 0, None,
-                             h[(i & 1) ^ 1], c[(i & 1) ^ 1], out, self.gates[0][:B], B, U)
+            self._text_step(tok, i == 0, B, emb, xz, h[i & 1], c[i & 1], h[(i & 1) ^ 1], c[(i & 1) ^ 1], out,
+                            self.gates[0][:B])
             self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, B, V, U, U, ldV, ldV,
                          bias=a.p("time_distributed_softmax/bias"))
             be.softmax_cce(probs, None, probs, None, None, None, B, V, ldV, 0.0)
@@ -881,7 +853,7 @@ class NIC(ModelBase):
         B rows: the state after the feature step is Hs[1], Cs[1].  ``src`` = (x, h0, c0, h1, c1): other input rows and
         initial state, and where the state after the feature step goes"""
         be, a = self.be, self.arena
-        N, U, E = self.N, self.U, self.E
+        N, E = self.N, self.E
         x, h0, c0, h1, c1 = src if src is not None else (self.x, self.Hs[0], self.Cs[0], self.Hs[1], self.Cs[1])
         self.gemm_sk(x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
                      pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
@@ -891,10 +863,25 @@ class NIC(ModelBase):
         else:
             be.layernorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.Xin, self.xhat,
                              self.inv_std, B, E, E, BN_EPS)
-        xz = self.XZ[:B]
-        self.gemm_sk(self.Xin, a.p("lstm/kernel"), xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
-        be.lstm_step_fwd(xz, h0, c0, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h1, c1, None,
-                         self.gates[0], B, U)
+        self._feature_step(self.Xin, B, self.XZ[:B], h0, c0, h1, c1, self.gates[0])
+
+    def _feature_step(self, feat, rows, xz, h_in, c_in, h_out, c_out, gates):
+        """the feature step of a decode: the input projection of the encoded rows ``feat`` with the LSTM bias, and one
+        unmasked LSTM step h_in, c_in -> h_out, c_out"""
+        a, U, E = self.arena, self.U, self.E
+        self.gemm_sk(feat, a.p("lstm/kernel"), xz, rows, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
+        self.be.lstm_step_fwd(xz, h_in, c_in, a.p("lstm/recurrent_kernel"), None, None, 0, None, 0, 0, None, h_out, c_out,
+                              None, gates, rows, U)
+
+    def _text_step(self, words, first, rows, emb, xz, h_in, c_in, h_out, c_out, out, gates):
+        """the token step of a decode, three launches: the Embedding gather of the fed ``words`` into ``emb``, its input
+        projection with the LSTM bias, and one LSTM step h_in, c_in -> h_out, c_out, `out`, masked by a fed 0 as by the
+        keras Embedding mask (a masked row carries its state) unless ``first``: the start token always advances"""
+        a, U, E = self.arena, self.U, self.E
+        self.be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, rows, 1, E, E, self.V)
+        self.gemm_sk(emb, a.p("lstm/kernel"), xz, rows, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
+        self.be.lstm_step_fwd(xz, h_in, c_in, a.p("lstm/recurrent_kernel"), None, None, 0, None if first else words, 1, 0,
+                              None, h_out, c_out, out, gates, rows, U)
 
     def _decode(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
         """the decode loop of greedy_predict (filt None: argmax) and sample_predict (filt = (temperature, top_k, top_p,
@@ -906,14 +893,13 @@ class NIC(ModelBase):
             guidance, consensus, constraints, None, img_input, a0, c0, start_seq, max_len)
         cap = torch.zeros(B, 1, dtype=torch.int32, device=self.device)
         self._stage_inputs((img_input, cap, a0, c0))
-        N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
+        U, V, ldV = self.U, self.V, self.ldV
         # static decode buffers per (B, max_len): the whole loop is one captured hipGraph
         choice = _TokenChoice(self, B, max_len, filt, con, cons)
         choice.start.copy_(start.view(B, 1))
 
         def run():
             self._decode_encode(B)
-            Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
             xz, emb = self.XZ[:B], self.Xin[B:2 * B]
             h = [self.Hs[0], self.Hs[1]]
             c = [self.Cs[0], self.Cs[1]]
@@ -921,10 +907,7 @@ class NIC(ModelBase):
             out = self.Out[0]
             words = choice.start
             for i in range(max_len):
-                be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, B, 1, E, E, V)
-                self.gemm_sk(emb, Wl, xz, B, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-                be.lstm_step_fwd(xz, h[cur], c[cur], Ur, None, None, 0, words if i > 0 else None, 1, 0, None,
-                                 h[1 - cur], c[1 - cur], out, self.gates[0], B, U)
+                self._text_step(words, i == 0, B, emb, xz, h[cur], c[cur], h[1 - cur], c[1 - cur], out, self.gates[0])
                 cur = 1 - cur
                 logits = choice.logits(i)
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), logits, B, V, U, U, ldV, ldV,
@@ -979,12 +962,8 @@ class NIC(ModelBase):
         be.embedding_fwd(a.p("emb_text/embeddings"), cap, v["xin"], R, T, E, E, V)      # t-major; rows [0, n) are used
         self.gemm_sk(v["xin"], a.p("lstm/kernel"), xz, n, 4 * U, E, E, 4 * U, 4 * U)
         Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
-        if v["seq"]:
-            be.lstm_seq_fwd(xz, hs, cs, Ur, bl, cap, T, 0, out, v["gates"], steps, R, U, self.seq_sync, self._guard_out())
-        else:
-            for t in range(steps):
-                be.lstm_step_fwd(xz[t * R:(t + 1) * R], hs[t], cs[t], Ur, None, None, 0, cap, T, t,
-                                 out[t - 1] if t > 0 else None, hs[t + 1], cs[t + 1], out[t], v["gates"], R, U, xz_bias=bl)
+        lstm_layer_fwd(be, xz, hs, cs, Ur, bl, cap, T, 0, out, v["gates"], steps, R, U,
+                       chain=self._seq_chain() if v["seq"] else None)
         self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), v["logits"], n, V, U, U, ldV, ldV,
                      bias=a.p("time_distributed_softmax/bias"))
         be.caption_score(v["logits"], ldV, V, cap, T, steps, R, end_id, v["tok_lp"], v["cap_lp"], v["cap_len"])
@@ -1041,16 +1020,12 @@ class NIC(ModelBase):
 
         def run():
             self._decode_encode(B)
-            Wl, bl, Ur = a.p("lstm/kernel"), a.p("lstm/bias"), a.p("lstm/recurrent_kernel")
             # the B rows' state after the feature step -> the B*k beam rows (row gather b*k + j <- b)
             be.embedding_fwd(self.Hs[1], bb["rep"], h[0], Bk, 1, U, U, B)
             be.embedding_fwd(self.Cs[1], bb["rep"], c[0], Bk, 1, U, U, B)
             words = bb["start"]
             for i in range(max_len):
-                be.embedding_fwd(a.p("emb_text/embeddings"), words, emb, Bk, 1, E, E, V)
-                self.gemm_sk(emb, Wl, xz, Bk, 4 * U, E, E, 4 * U, 4 * U, bias=bl)
-                be.lstm_step_fwd(xz, h[0], c[0], Ur, None, None, 0, words if i > 0 else None, 1, 0, None,
-                                 h[1], c[1], out, bb["gates"], Bk, U)
+                self._text_step(words, i == 0, Bk, emb, xz, h[0], c[0], h[1], c[1], out, bb["gates"])
                 self.gemm_sk(out, a.p("time_distributed_softmax/kernel"), probs, Bk, V, U, U, ldV, ldV,
                              bias=a.p("time_distributed_softmax/bias"))
                 words, par = beam.step(i, probs)

@@ -20,6 +20,7 @@ import torch
 
 from .arena import ParamArena
 from .model_base import ModelBase, Metrics, _r4, S_FEAT, S_OUT
+from .lstm_layer import lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_RELU, ACT_TANH
 
 
@@ -167,15 +168,11 @@ class CaptionGenerator(ModelBase):
         be.embedding_fwd(a.p("embedding/embeddings"), self.cap, self.Xin[B:], B, T, E, E, V)
         self.gemm_sk(self.Xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U, bias=a.p("lstm/bias"))
         Ur = a.p("lstm/recurrent_kernel")
-        mask = self.lenmask if self.sat else None
-        if self._seq_lstm and mask is None:     # unmasked sequence: one persistent launch (tnt_lstm_seq_fwd_f32); the masked
-            # ShowAndTell form zeroes masked outputs instead of repeating them and stays on the step kernel
-            be.lstm_seq_fwd(self.XZ, self.Hs, self.Cs, Ur, None, None, 0, 0, self.Out, self.gates, T + 1, B, U, self.seq_sync,
-                            self._guard_out())
-        else:
-            for t in range(T + 1):
-                be.lstm_step_fwd(self.XZ[t * B:(t + 1) * B], self.Hs[t], self.Cs[t], Ur, None, None, 0, mask, T + 1, t, None,
-                                 self.Hs[t + 1], self.Cs[t + 1], self.Out[t * B:(t + 1) * B], self.gates[t], B, U)
+        # the unmasked sequence may run as the persistent chain; the length mask of ShowAndTell zeroes masked outputs
+        # instead of repeating them (carry_out=False) and stays on the step kernel
+        mask, mask_T = (self.lenmask, T + 1) if self.sat else (None, 0)
+        lstm_layer_fwd(be, self.XZ, self.Hs, self.Cs, Ur, None, mask, mask_T, 0, self.Out, self.gates, T + 1, B, U,
+                       chain=None if self.sat else self._seq_chain(), carry_out=False)
         hd = self.Out
         if training and self.r_dec > 0:
             be.dropout(self.Out, self.Hd, R1, U, U, B, U, 0, self.r_dec, sd, S_OUT, 0, ds)
@@ -223,18 +220,9 @@ class CaptionGenerator(ModelBase):
         if self.r_dec > 0:
             be.dropout(self.dOut, self.dOut, R1, U, U, B, U, 0, self.r_dec, sd, S_OUT, 0, ds)
         Ur = a.p("lstm/recurrent_kernel")
-        mask = self.lenmask if self.sat else None
-        seqb = self._seq_lstm and mask is None and self.seq_xch is not None
-        if seqb:       # BPTT as one persistent launch (unmasked decoder), see nic.NIC._bwd_seq_lstm
-            be.lstm_seq_bwd(Ur, self.dOut, None, 0, 0, self.gates, self.Cs, self.dZ, self.seq_xch, T + 1, B, U, self.seq_sync,
-                            self._guard_out())
-        else:
-            for t in range(T, -1, -1):
-                first = t == T
-                be.lstm_step_bwd(None if first else self.dZ[(t + 1) * B:(t + 2) * B], Ur, None if first else self.da_pass,
-                                 None, None if first else self.dc, None, self.dOut[t * B:(t + 1) * B], mask, T + 1, t,
-                                 self.gates[t], self.Cs[t + 1], self.Cs[t], self.dZ[t * B:(t + 1) * B], self.da_pass,
-                                 self.dc, None, B, U)
+        mask, mask_T = (self.lenmask, T + 1) if self.sat else (None, 0)
+        lstm_layer_bwd(be, Ur, self.dOut, mask, mask_T, 0, self.gates, self.Cs, self.dZ, (self.da_pass, self.dc, None), T + 1, B,
+                       U, chain=None if self.sat else self._seq_chain(bwd=True))
         self.gemm_sk(self.Hs, self.dZ, a.g("lstm/recurrent_kernel"), U, 4 * U, R1, U, 4 * U, 4 * U, transA=True)
         self.gemm_sk(self.Xin, self.dZ, a.g("lstm/kernel"), E, 4 * U, R1, E, 4 * U, 4 * U, transA=True)
         be.colsum(self.dZ, a.g("lstm/bias"), R1, 4 * U, 4 * U, self.work)

@@ -46,6 +46,7 @@ import numpy as np
 import pytest
 import torch
 
+from masters_thesis_amd.lstm_layer import lstm_layer_fwd, lstm_layer_bwd
 from oracle import ops as O
 from test_gpu_ops import close, dev, il, unil
 
@@ -355,31 +356,22 @@ def chain_bwd_launch(be, n, d, gates, cs, junk=None, pos=None, dout=None):
 
 
 def step_chain_fwd(be, n, d):
-    """the same sequence as S launches of the step kernel, driven the way nic.NIC drives them"""
+    """the same sequence as S launches of the step kernel: the models' own per-step loop (lstm_layer.lstm_layer_fwd)"""
     S, B, U = n.S, n.B, n.U
     Hs, Cs = torch.zeros(S + 1, B, U, device="cuda"), torch.zeros(S + 1, B, U, device="cuda")
     Hs[0], Cs[0] = d.h0, d.c0
     Out, G = torch.zeros(max(n.nseq, 1), B, U, device="cuda"), torch.zeros(S, B, U, 4, device="cuda")
-    for s in range(S):
-        t = s - n.s0
-        be.lstm_step_fwd(d.xz[s], Hs[s], Cs[s], d.Ur, None, None, 0, d.ids if t >= 0 else None, n.mask_T, max(t, 0),
-                         Out[t - 1] if (t > 0 and d.ids is not None) else None, Hs[s + 1], Cs[s + 1], Out[t] if t >= 0 else None,
-                         G[s], B, U, xz_bias=d.bl)
+    lstm_layer_fwd(be, d.xz, Hs, Cs, d.Ur, d.bl, d.ids, n.mask_T, n.s0, Out, G, S, B, U, chain=None)
     return Hs, Cs, Out, G
 
 
 def step_chain_bwd(be, n, d, G, Cs):
-    """BPTT as S launches of the step kernel, driven as nic.NIC._bwd_seq_lstm drives them"""
+    """BPTT as S launches of the step kernel: the models' own per-step loop (lstm_layer.lstm_layer_bwd)"""
     S, B, U = n.S, n.B, n.U
     dZ = torch.zeros(S, B, U, 4, device="cuda")
     z = lambda: torch.zeros(B, U, device="cuda")
     dap, dcp, dop = z(), z(), z()
-    for s in range(S - 1, -1, -1):
-        first, seq = s == S - 1, s >= n.s0
-        be.lstm_step_bwd(None if first else dZ[s + 1], d.Ur, None if first else dap, None, None if first else dcp,
-                         (None if first else dop) if seq else None, d.dOut[s - n.s0] if seq else None,
-                         d.ids if seq else None, n.mask_T, s - n.s0 if seq else 0, G[s], Cs[s + 1], Cs[s], dZ[s],
-                         dap, dcp, dop if seq else None, B, U)
+    lstm_layer_bwd(be, d.Ur, d.dOut, d.ids, n.mask_T, n.s0, G, Cs, dZ, (dap, dcp, dop), S, B, U, chain=None)
     return dZ
 
 
