@@ -321,6 +321,20 @@ int32_t tnt_dense_fwd_stream_f32(const float* x, const float* w, float* part, in
 int32_t tnt_dense_fwd_stream_gram_f32(const float* x, const float* w, float* part, float* gx_part, float* w2_part,
                                       int32_t B, int32_t E, int32_t K, int32_t ldx, int32_t ldw, int32_t nsplit,
                                       void* stream);
+/* tnt_dense_fwd_stream_gram_f32 on the caller's own batch x [B][N] (contiguous rows: ldx = K = N) with ALL of
+ * tnt_stage_batch_map_f32's job riding in the same launch, as extra workgroups beside the forward's: the copy of x into
+ * x_dst [B][ldx_dst] (which the end of the step reads), cap, tgt (time-major), a0 -> h0, c0 -> c0_dst, and the row map
+ * (pos, row_weight, tgt_compact, live, loss_row, corr_row; the last two nullable).  Every output is bit-identical to
+ * tnt_stage_batch_map_f32 followed by tnt_dense_fwd_stream_gram_f32 on the staged copy; neither role reads what the other
+ * writes.  B <= 64, N % 16 == 0, E % 32 == 0, E >= 512, x, w, part (and x_dst when ldx_dst % 4 == 0) 16-byte aligned:
+ * anything else is refused (non-zero) before any launch, and the caller takes the two launches instead. */
+int32_t tnt_dense_fwd_stream_gram_stage_f32(const float* x, const float* w, float* part, float* gx_part, float* w2_part,
+                                            int32_t B, int32_t E, int32_t N, int32_t ldw, int32_t nsplit, float* x_dst,
+                                            int32_t ldx_dst, const int32_t* cap, int32_t* cap_dst, const int32_t* tgt,
+                                            int32_t* tgt_tmajor, const float* a0, float* h0, const float* c0,
+                                            float* c0_dst, int32_t T, int32_t U, int32_t* pos, float* row_weight,
+                                            int32_t* tgt_compact, int32_t* live, float* loss_row, float* corr_row,
+                                            void* stream);
 /* ... and the finish, after the backward pass produced dpre [Bk][E] (gradient w.r.t. the pre-activation pre [Bk][E]
  * = x w + bias): for g = x^T dpre (NIC.py:248-249) the clipnorm input sum (g + 2 l2 w)^2 = ||g||^2 + 4 l2 <g, w> +
  * 4 l2^2 ||w||^2 with ||g||^2 = sum (x x^T) o (dpre dpre^T) and <g, w> = sum dpre o (pre - bias), written as span

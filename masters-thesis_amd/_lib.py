@@ -96,6 +96,8 @@ SIGNATURES = {
     "tnt_dense_dw_sqnorm_f32": [P, P, P, F32, P, I32, I32, I32, I32, I32, P],
     "tnt_dense_dw_adam_f32": [P, P, P, P, P, F32, P, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P],
     "tnt_dense_fwd_stream_gram_f32": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P],
+    "tnt_dense_fwd_stream_gram_stage_f32": [P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P, P, P, P, P, P, P, P, I32, I32,
+                                            P, P, P, P, P, P, P],
     "tnt_dense_gram_norm_f32": [P, P, P, P, I32, P, I32, F32, P, I32, I32, I32, P],
     "tnt_dense_gram_norm_spans_f32": [P, P, P, P, I32, P, I32, F32, P, I32, I32, I32, P, P, P, P, P, P, P, I32, P],
     "tnt_dense_fwd_stream_f32": [P, P, P, I32, I32, I32, I32, I32, I32, P],

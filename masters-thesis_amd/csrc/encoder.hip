@@ -11,6 +11,8 @@
 // the transposed operand (dW_r = X_r^T dpre_r), so x is never re-laid-out in HBM.
 #include "tnt_common.h"
 #include "tnt_fin.h"
+#include "tnt_stage.h"
+#include <type_traits>
 
 namespace {
 
@@ -542,6 +544,8 @@ namespace {
 constexpr int DF_CW = 32;            // output columns per workgroup
 
 struct DfArgs { const float* x; const float* w; float* part; int B, E, K, ldx, ldw, nsplit; float* gx_part; float* w2_part; };
+// STAGE: the forward's arguments + those of the batch staging that rides behind its nmain workgroups
+struct DfStageArgs : DfArgs { StageArgs<float> st; int nmain; };
 
 // GRAM (training, when the optimizer step will consume the kernel's gradient X^T D without writing it): two by-products
 // that let its clip-by-norm factor be computed from 64 x 64 matrices instead of a pass over the 10 M-element gradient --
@@ -550,9 +554,25 @@ struct DfArgs { const float* x; const float* w; float* part; int B, E, K, ldx, l
 //                           k-tile from registers already loaded; the 16 column groups of a split take one tile each;
 //   w2_part[workgroup]      sum of squares of the W elements the workgroup streamed (each element exactly once).
 // ||X^T D||_F^2 = sum_{b,b'} (X X^T)[b,b'] (D D^T)[b,b'];  tnt_dense_gram_norm_f32 finishes the job.
-template <int NW, int DEPTH, bool GRAM>
-__global__ __launch_bounds__(64 * NW) void dense_fwd_stream_kernel(DfArgs a) {
+// STAGE (tnt_dense_fwd_stream_gram_stage_f32; a compile-time switch: the launches without it run the code they always ran):
+// the launch also does tnt_stage_batch_map_f32's job, as rider workgroups behind the nmain = gridDim.x of the forward -- first
+// the row-map workgroup (the longest rider), then st.ncopy copy workgroups.  The forward reads x where the caller left it;
+// the riders copy that x to st.xd for the end of the step (dense_dw_skinny_kernel) and write nothing the forward reads, and the
+// forward writes nothing they read: no flag, fence or counter between the roles.  The forward holds one wave per SIMD in
+// registers that leave room for a second, so a rider workgroup runs on every CU beside it.
+template <int NW, int DEPTH, bool GRAM, bool STAGE = false>
+__global__ __launch_bounds__(64 * NW) void dense_fwd_stream_kernel(std::conditional_t<STAGE, DfStageArgs, DfArgs> a) {
   __shared__ float red[NW][64][DF_CW + 4];
+  if constexpr (STAGE) {
+    static_assert(NW == 4, "the staging code expects 256 threads");
+    static_assert(sizeof(red) >= (3 * STAGE_MAP_LDS + 257) * sizeof(int), "the row map's LDS arrays live in red");
+    if ((int)blockIdx.x >= a.nmain) {           // uniform per workgroup: riders never reach the forward's barriers
+      const int rider = blockIdx.x - a.nmain;
+      if (rider == 0) stage_rowmap_block(a.st, reinterpret_cast<int*>(&red[0][0][0]));
+      else stage_copy(a.st, rider - 1);
+      return;
+    }
+  }
   const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, ln = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   // Workgroup -> (column group, K split).  Workgroups are dealt round-robin to the 8 XCDs, each with its own L2:
@@ -730,6 +750,48 @@ static int32_t dense_fwd_stream_launch(const float* x, const float* w, float* pa
 extern "C" int32_t tnt_dense_fwd_stream_f32(const float* x, const float* w, float* part, int32_t B, int32_t E,
                                             int32_t K, int32_t ldx, int32_t ldw, int32_t nsplit, void* stream) {
   return dense_fwd_stream_launch(x, w, part, nullptr, nullptr, B, E, K, ldx, ldw, nsplit, stream);
+}
+
+/* see include/tnt_hip.h */
+extern "C" int32_t tnt_dense_fwd_stream_gram_stage_f32(const float* x, const float* w, float* part, float* gx_part,
+                                                       float* w2_part, int32_t B, int32_t E, int32_t N, int32_t ldw,
+                                                       int32_t nsplit, float* x_dst, int32_t ldx_dst, const int32_t* cap,
+                                                       int32_t* cap_dst, const int32_t* tgt, int32_t* tgt_tmajor,
+                                                       const float* a0, float* h0, const float* c0, float* c0_dst,
+                                                       int32_t T, int32_t U, int32_t* pos, float* row_weight,
+                                                       int32_t* tgt_compact, int32_t* live, float* loss_row,
+                                                       float* corr_row, void* stream) {
+  // the forward's checks (dense_fwd_stream_launch + the Gram form's), with x read in place: ldx = N
+  if (B <= 0 || B > 64 || N < 16 || N % 16 != 0) return TNT_BADARG(6);
+  if (E <= 0 || E % DF_CW != 0 || E / DF_CW < 16 || ldw < E || ldw % 2 != 0 || nsplit <= 0 || nsplit > 64) return TNT_BADARG(5);
+  if (gx_part == nullptr || w2_part == nullptr) return TNT_BADARG(4);
+  if (!tnt_aligned16(x) || !tnt_aligned16(w) || !tnt_aligned16(part)) return TNT_BADARG(1);
+  if ((long)B * N * 4 >= (1L << 32) || 16L * ldw * 4 >= (1L << 32)) return TNT_BADARG(4);        // 32-bit lane offsets
+  // the staging's checks (stage_batch_launch with a row map)
+  if (T <= 0 || U <= 0 || ldx_dst < N) return TNT_BADARG(11);
+  if (x_dst == nullptr || cap == nullptr || cap_dst == nullptr || a0 == nullptr || h0 == nullptr || c0 == nullptr ||
+      c0_dst == nullptr)
+    return TNT_BADARG(11);
+  if (pos == nullptr || row_weight == nullptr || tgt_compact == nullptr || live == nullptr || tgt == nullptr ||
+      tgt_tmajor == nullptr)
+    return TNT_BADARG(19);
+  if (ldx_dst % 4 == 0 && !tnt_aligned16(x_dst)) return TNT_BADARG(1);
+  DfStageArgs a{};
+  a.x = x; a.w = w; a.part = part; a.B = B; a.E = E; a.K = N; a.ldx = N; a.ldw = ldw; a.nsplit = nsplit;
+  a.gx_part = gx_part; a.w2_part = w2_part;
+  StageArgs<float>& s = a.st;
+  s.x = x; s.xd = x_dst; s.cap = cap; s.capd = cap_dst; s.tgt = tgt; s.tgtd = tgt_tmajor; s.a0 = a0; s.h0 = h0; s.c0 = c0;
+  s.c0d = c0_dst; s.B = B; s.T = T; s.N = N; s.ldx = ldx_dst; s.U = U;
+  s.map_pos = pos; s.map_w = row_weight; s.map_tgt = tgt_compact; s.map_live = live; s.map_loss = loss_row; s.map_corr = corr_row;
+  // one float4 (or one float, when the padded rows of x_dst are not 16-byte rows) per thread, as the staging launch deals them
+  long nc = ((long)B * N / (ldx_dst % 4 == 0 ? 4 : 1) + 255) / 256;
+  s.ncopy = (int)(nc > 2048 ? 2048 : nc);
+  s.nstage = s.ncopy;
+  a.nmain = (E / DF_CW) * nsplit;
+  hipLaunchKernelGGL((dense_fwd_stream_kernel<4, 4, true, true>), dim3(a.nmain + 1 + s.ncopy), dim3(256), 0,
+                     tnt_stream(stream), a);
+  TNT_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int32_t tnt_dense_fwd_stream_gram_f32(const float* x, const float* w, float* part, float* gx_part,

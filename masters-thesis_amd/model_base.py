@@ -1582,7 +1582,12 @@ class ModelBase:
         with the staging of a training batch (nic.NIC: compact_head), else None"""
         return None
 
-    def _stage_batch(self, inputs, target, n_cols, masks=False, head_map=False):
+    def _stage_fwd_args(self, B):
+        """(w, part, gx_part, w2_part, E, ldw, nsplit) when the model's training forward begins with the streaming encoder
+        product of the staged batch and wants it in the staging launch (nic.NIC: stage_fwd), else None"""
+        return None
+
+    def _stage_batch(self, inputs, target, n_cols, masks=False, head_map=False, fwd=False):
         """(inputs, target) -> static buffers.  A batch that already sits on the model's device in the staged
         dtypes (float32 -- or float16 "on-wire" -- betas, float32 states, int32 ids, contiguous) goes through ONE launch
         (tnt_stage_batch_f32 / _h16);
@@ -1601,6 +1606,7 @@ class ModelBase:
         ok = ok and x.dim() == 2 and cap.dim() == 2 and x.shape == (cap.shape[0], n_cols)
         ok = ok and (target is None or (target.dtype == torch.int32 and target.shape == cap.shape))
         self._head_map_fresh = False
+        self._stage_fwd_done = False
         if not ok:
             B, T = self._stage_inputs(inputs)
             if target is not None:
@@ -1619,7 +1625,14 @@ class ModelBase:
             kw["masks"] = mk
         hm = self._head_map_bufs(B, T) if (head_map and target is not None and mk is None and xT is None
                                            and x.dtype == torch.float32) else None
-        if hm is not None:
+        sf = self._stage_fwd_args(B) if (fwd and hm is not None and n_cols == self.ldx) else None
+        if sf is not None and self.be.dense_fwd_stream_gram_stage(x, *sf[:4], B, sf[4], n_cols, sf[5], sf[6], self.x, self.ldx,
+                                                                  cap, self.cap, target, self.tgt, a0, self.Hs[0], c0,
+                                                                  self.Cs[0], T, self.U, *hm):
+            # ... and both ride behind the encoder forward, which reads the caller's x in place: the step's first launch is
+            # the forward, and _forward leaves its own out (False: the entry refused these arguments, e.g. their alignment)
+            self._head_map_fresh = self._stage_fwd_done = True
+        elif hm is not None:
             # the head's row map (which caption positions repeat an earlier row) rides in the staging launch: the step that
             # follows runs its vocabulary head over the distinct rows only
             self.be.stage_batch_map(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,

@@ -133,11 +133,13 @@ class NIC(ModelBase):
             self._enc_grad_stale = None
         return super().get_gradient(name)
 
-    def _enc_update_fused(self, rows):
+    def _enc_update_fused(self, rows, defer=None):
         """True when the encoder kernel's gradient is consumed inside the optimizer launches instead of being written
-        out (tnt_dense_dw_sqnorm_f32 / tnt_dense_dw_adam_f32): the single-process fused step with Adam, no AGC."""
+        out (tnt_dense_dw_sqnorm_f32 / tnt_dense_dw_adam_f32): the single-process fused step with Adam, no AGC.
+        ``defer``: asked ahead of the step (_stage_fwd_args) -- whether that step will be the fused one."""
         opt = self.optimizer
-        return bool(self.__dict__.get("_defer_sum2") and self.dp_world == 1 and getattr(self, "fuse_enc_update", True)
+        defer = self.__dict__.get("_defer_sum2") if defer is None else defer
+        return bool(defer and self.dp_world == 1 and getattr(self, "fuse_enc_update", True)
                     and opt is not None and opt.kind == "adam" and not self.__dict__.get("agc") and rows <= 64
                     and self.E % 512 == 0 and hasattr(self.be, "dense_dw_adam") and hasattr(self.be, "step_finalize")
                     and self.arena.entries["dense_img/kernel"].seg == 0
@@ -231,6 +233,29 @@ class NIC(ModelBase):
             return None
         return (self.head_pos, self.head_w, self.head_tgt, self.head_live, self.loss_row, self.corr_row)
 
+    def _gram_fwd(self, B, defer=None):
+        """the training forward leaves X X^T and sum W^2 behind (tnt_dense_fwd_stream_gram_f32): the optimizer step takes the
+        encoder kernel's gradient X^T dpre without writing it, and its clip-by-norm factor follows from these"""
+        return (self._fused_tail(B) and self.enc_part is not None and self._enc_update_fused(B, defer)
+                and getattr(self, "gram_norm", True) and self.N % 16 == 0 and self.E >= 512
+                and hasattr(self.be, "dense_gram_norm"))
+
+    def _gram_bufs(self):
+        if self.enc_gx is None:
+            self.enc_gx, self.enc_w2 = self._f(ENC_SPLITS * 64 * 64), self._f(ENC_SPLITS * (self.E // 32))
+
+    def _stage_fwd_args(self, B):
+        """``stage_fwd`` (default on): train_step's staging launch and the encoder forward are ONE launch
+        (tnt_dense_fwd_stream_gram_stage_f32) where the step's first kernel is the Gram form of the streaming forward on
+        the staged betas themselves (no input Dropout), and the step is the single-process fused one.  Everything else
+        keeps the two launches."""
+        ok = (getattr(self, "stage_fwd", True) and self.r_in == 0 and hasattr(self.be, "dense_fwd_stream_gram_stage")
+              and self._gram_fwd(B, defer=bool(getattr(self, "fused_update", True))))
+        if not ok:
+            return None
+        self._gram_bufs()
+        return (self.arena.p("dense_img/kernel"), self.enc_part, self.enc_gx, self.enc_w2, self.E, self.E, ENC_SPLITS)
+
     def _fused_tail(self, B):
         """one-launch encoder tail (tnt_enc_tail_*): BatchNorm encoder, batch <= 256 rows, E % 4 == 0"""
         return (self.norm == "batch" and B <= 256 and self.E % 4 == 0 and getattr(self, "fuse_tail", True)
@@ -255,16 +280,18 @@ class NIC(ModelBase):
         if stream:      # :125-128 + the feature step's LSTM input dropout: the streaming product's K-split partials are
             #             summed (+ bias, LeakyReLU) by the tail kernel, which holds whole columns for the batch statistics
             self._enc_gram = None
-            if (training and self._enc_update_fused(B) and getattr(self, "gram_norm", True) and N % 16 == 0 and E >= 512
-                    and hasattr(be, "dense_gram_norm")):
+            staged = bool(training and self.__dict__.get("_stage_fwd"))      # train_step: the staging launch ran this product
+            if training and self._gram_fwd(B):
                 # the optimizer step will take this kernel's gradient X^T dpre without writing it: leave X X^T and
                 # sum W^2 behind, from which (with dpre) its clip-by-norm factor follows (tnt_dense_gram_norm_f32)
-                if self.enc_gx is None:
-                    self.enc_gx, self.enc_w2 = self._f(ENC_SPLITS * 64 * 64), self._f(ENC_SPLITS * (E // 32))
-                be.dense_fwd_stream_gram(x, a.p("dense_img/kernel"), self.enc_part, self.enc_gx, self.enc_w2, B, E, N,
-                                         self.ldx, E, ENC_SPLITS)
+                self._gram_bufs()
+                if not staged:
+                    be.dense_fwd_stream_gram(x, a.p("dense_img/kernel"), self.enc_part, self.enc_gx, self.enc_w2, B, E, N,
+                                             self.ldx, E, ENC_SPLITS)
                 self._enc_gram = (self.enc_pre, a.p("dense_img/bias"), self.enc_gx, ENC_SPLITS, self.enc_w2,
                                   ENC_SPLITS * (E // 32))
+            elif staged:
+                raise RuntimeError("the staging launch ran the Gram form of the encoder forward, which this step does not take")
             else:
                 be.dense_fwd_stream(x, a.p("dense_img/kernel"), self.enc_part, B, E, N, self.ldx, E, ENC_SPLITS)
             emb_ride = E % 4 == 0 and hasattr(be, "enc_tail_fwd_sk_emb") and getattr(self, "emb_ride", True)
@@ -631,22 +658,27 @@ class NIC(ModelBase):
         self._ss_refuse()
         if self.self_critical is not None:
             return self.train_step_scst(data)
-        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None)
+        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None, fwd=self.grad_sync is None)
         self._ss_refuse(T)
         self._sync_lr()
         self._enc_grad_stale = None
         ring = False
         if self.grad_sync is None:      # replayed as a launch plan or a hipGraph: ModelBase._step_runner
             compact = bool(self.__dict__.get("_head_map_fresh"))      # the staging launch built the head's row map
+            staged = bool(self.__dict__.get("_stage_fwd_done"))     # ... and ran the encoder forward: the step leaves it out
             key = ("train", B, T, "compact") if compact else ("train", B, T)
+            seen = self.__dict__.setdefault("_plan_staged", {})
+            if self._graphs.get(key) is not None and seen.get(key) != staged:
+                del self._graphs[key]       # recorded with / without the forward (the entry refuses by alignment): start over
+            seen[key] = staged
             if compact and self._head_live_est is None and self._graphs.get(key) is None:
                 # the eager warm-up step synchronises anyway: read the live count once, for the head forward's tile only
                 self._head_live_est = int(self.head_live.item())
-            self._compact = compact
+            self._compact, self._stage_fwd = compact, staged
             try:
                 ring = self._run_step(self._step_runner(), key, lambda: self._train_and_update_graph(B, T))
             finally:
-                self._compact = False
+                self._compact = self._stage_fwd = False
             self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)

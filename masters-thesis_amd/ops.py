@@ -55,15 +55,24 @@ class HipBackend:
 
     _rec = None     # while a launch plan is being recorded: list of (c function, name, argument tuple)
 
-    def _call(self, fn, name, *args):
+    def _call(self, fn, name, *args, may_refuse=False):
         """Every C-ABI launch goes through here: checks the return code and, while a plan is being recorded
         (ModelBase._run_planned), keeps the bound call so the same launch can be re-issued without the Python
-        argument plumbing."""
-        if self._rec is not None:
-            self._rec.append((fn, name, args))
-        rc = fn(*args)
+        argument plumbing.  ``may_refuse``: an entry point whose caller has another way -- a refusal of the arguments
+        (TNT_BADARG: nothing was launched) returns False and is not recorded."""
+        if may_refuse:
+            rc = fn(*args)
+            if rc <= -1000:
+                return False
+            if self._rec is not None:
+                self._rec.append((fn, name, args))
+        else:
+            if self._rec is not None:
+                self._rec.append((fn, name, args))
+            rc = fn(*args)
         if rc != 0:
             raise _lib.KernelLibraryError(f"{name} failed with code {rc}")
+        return True
 
     @staticmethod
     def _s():
@@ -386,6 +395,17 @@ class HipBackend:
     def dense_fwd_stream_gram(self, x, w, part, gx_part, w2_part, B, E, K, ldx, ldw, nsplit):
         self._call(self.lib.tnt_dense_fwd_stream_gram_f32, "tnt_dense_fwd_stream_gram_f32", _p(x), _p(w), _p(part), _p(gx_part),
                    _p(w2_part), B, E, K, ldx, ldw, nsplit, self._s())
+
+    def dense_fwd_stream_gram_stage(self, x, w, part, gx_part, w2_part, B, E, N, ldw, nsplit, x_dst, ldx_dst, cap, cap_dst, tgt,
+                                    tgt_tmajor, a0, h0, c0, c0_dst, T, U, pos, row_weight, tgt_compact, live, loss_row=None,
+                                    corr_row=None):
+        """dense_fwd_stream_gram on the caller's x with stage_batch_map's job riding in the same launch
+        (tnt_dense_fwd_stream_gram_stage_f32).  Returns False, with nothing launched, when the entry refuses the
+        arguments (alignment, shape): the caller then issues the two launches."""
+        return self._call(self.lib.tnt_dense_fwd_stream_gram_stage_f32, "tnt_dense_fwd_stream_gram_stage_f32", _p(x), _p(w),
+                          _p(part), _p(gx_part), _p(w2_part), B, E, N, ldw, nsplit, _p(x_dst), ldx_dst, _p(cap), _p(cap_dst),
+                          _p(tgt), _p(tgt_tmajor), _p(a0), _p(h0), _p(c0), _p(c0_dst), T, U, _p(pos), _p(row_weight),
+                          _p(tgt_compact), _p(live), _p(loss_row), _p(corr_row), self._s(), may_refuse=True)
 
     def dense_gram_norm(self, dpre, pre, bias, gx_part, nsplit, w2_part, nw2, l2, partial, nslot, Bk, E, spans=None, lr_job=None,
                         skip=None):
