@@ -592,12 +592,15 @@ __global__ __launch_bounds__(64 * NW) void dense_fwd_stream_kernel(std::conditio
   const int nt = q < Tfull ? (Tfull - q + nslot - 1) / nslot : 0;
   // Addresses = uniform tile base (scalar registers, scalar arithmetic) + a per-lane byte offset that never changes:
   // the loop issues no vector address arithmetic at all.  Rows past B read row B-1 (their outputs are never stored:
-  // an output row of the MFMA depends on the same row of A only).
+  // an output row of the MFMA depends on the same row of A only).  The lane's k quad inside a tile is clamped to K (kc: the
+  // identity whenever a full tile exists).  With K < 16 there is none, every wave slot is empty (nt == 0), and the ring's
+  // prologue, which loads "tile 0" regardless, then stays inside the K columns of x and the K rows of W.
+  const int kc = min(kq, a.K / 4 - 1);
   unsigned aoff[4], boff[4];
 #pragma unroll
-  for (int rt = 0; rt < 4; ++rt) aoff[rt] = ((unsigned)min(rb + rt * 16 + ln, a.B - 1) * a.ldx + kq * 4) * 4u;
+  for (int rt = 0; rt < 4; ++rt) aoff[rt] = ((unsigned)min(rb + rt * 16 + ln, a.B - 1) * a.ldx + kc * 4) * 4u;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) boff[j] = ((unsigned)(kq * 4 + j) * a.ldw + c0 + 2 * ln) * 4u;
+  for (int j = 0; j < 4; ++j) boff[j] = ((unsigned)(kc * 4 + j) * a.ldw + c0 + 2 * ln) * 4u;
   floatx4 acc[4][2];
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt)
