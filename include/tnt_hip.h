@@ -1104,6 +1104,38 @@ int32_t tnt_weight_average_f32(const float* theta, float* avg, int64_t n, const 
  * buffers' addresses, so the contents move).  TNT_BADARG, and no launch, for n < 0, a null or not 16-byte aligned
  * pointer, overlapping buffers.  n == 0 is a no-op. */
 int32_t tnt_swap_f32(float* a, float* b, int64_t n, void* stream);
+/* Learning-rate schedule evaluated on the device (schedule.hip): lr[0] = (float) schedule(*step), one thread, in front of
+ * the first launch of a training step that reads lr; restated by tests/lr_schedule_oracle.py.  *step (int64: the updates
+ * applied so far, the model's adam_t; the first update sees 0, a negative value counts as 0) and params[0..16) (float64)
+ * are read on the device when the launch runs, so a recorded plan or a hipGraph replays with the live counter -- Keras's
+ * lr = schedule(optimizer.iterations) with no device-to-host sync.  There is no guard argument: a step whose guard word
+ * tripped does not advance adam_t, so the next step computes the same value again.
+ * Layout.  params[0] = kind id, params[1] = w, the warm-up steps (0: none), params[2] = the warm-up's start value,
+ * params[3..16) = the kind's fields f[0..13); unused fields are 0.  Kind 6 alone has no warm-up fields.
+ *   0 constant               f = lr0
+ *   1 ExponentialDecay       f = lr0, D, rate, staircase     lr0 * pow(rate, p)
+ *   2 InverseTimeDecay       f = lr0, D, rate, staircase     lr0 / (1 + rate * p)
+ *                            p = s / D in float64, with staircase != 0 the integer quotient s / D
+ *   3 CosineDecay            f = lr0, D, alpha               c = min(s, D) / D;  lr0 * ((1 - alpha) * 0.5 * (1 + cos(pi * c)) + alpha)
+ *   4 CosineDecayRestarts    f = lr0, first, t_mul, m_mul, alpha
+ *                            P = first, r = s, m = 1; while r >= P: r -= P, P *= t_mul, m *= m_mul   (float64: + * and a
+ *                            comparison only, so host and device leave the loop in the same trip); t_mul == 1 takes the
+ *                            closed form r = s % first, m = pow(m_mul, s / first) in integers;
+ *                            lr0 * ((1 - alpha) * m * 0.5 * (1 + cos(pi * r / P)) + alpha)
+ *   5 PolynomialDecay        f = lr0, D, end, power, cycle   cycle != 0: D' = D * max(1, ceil(s / D)) in integers, s' = s;
+ *                            else D' = D, s' = min(s, D);  (lr0 - end) * pow(1 - s' / D', power) + end
+ *   6 PiecewiseConstantDecay params[1..8) = 7 boundaries, params[8..16) = 8 values: values[i] of the first i with
+ *                            s <= boundaries[i], else values[7]; unused boundaries hold +inf, unused values the last value
+ *   7 PiecewiseConstantDecay under a warm-up: f[0..6) = 6 boundaries, f[6..13) = 7 values, the same rule
+ * Warm-up (w >= 1; kinds 0 - 5 and 7): s < w gives start + (a0 - start) * s / w with a0 = the kind at 0 updates, from w on
+ * the kind at s - w updates; continuous at w.  Every expression is evaluated in float64 in the written order, products
+ * and sums rounded separately (no fused multiply-add), left to right, and the result is rounded once to float32: the
+ * kinds without pow / cos give the bits of the same expression on the host.  D, first, w and the boundaries are
+ * integers >= 1 stored as float64; the caller validates the hyper-parameters (masters_thesis_amd.schedules).  An unknown
+ * kind, a D or first below 1, a w that is no integer >= 0 and a restart loop that has not ended after 4096 trips (the
+ * descriptor admits t_mul = 1 or >= 1.05: under 900) store NaN.  TNT_BADARG, and no launch, for a null step, params or
+ * lr.  No atomics, LDS or scratch. */
+int32_t tnt_lr_schedule_f32(const int64_t* step, const double* params, float* lr, void* stream);
 
 /* ---- region-wise encoder: layers.LocallyDense.call (layers.py:43-48) ------------
  * CSR groups: idx[goff[r] .. goff[r+1]) are the voxel columns of group r; W is the

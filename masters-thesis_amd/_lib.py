@@ -147,6 +147,7 @@ SIGNATURES = {
     "tnt_step_tick": [P, P, P, P, F32, F32, P, P],
     "tnt_weight_average_f32": [P, P, I64, P, I32, P, I32, I64, I32, P, P],
     "tnt_swap_f32": [P, P, I64, P],
+    "tnt_lr_schedule_f32": [P, P, P, P],
     "tnt_sam_f32": [P, P, P, P, P, P, P, P, P, I32, I32, F32, I32, P],
     "tnt_gemm_f32_tile": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, I32, I32, P],
     "tnt_block_dense_dx_f32": [P, P, P, I32, I32, I32, I32, P],

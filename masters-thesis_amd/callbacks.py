@@ -9,6 +9,8 @@ on_train_end`` and sets ``.model``; any object with these methods works (the ref
 import csv
 import os
 
+from .optimizers import optimizer_schedule
+
 
 class Callback:
     def __init__(self):
@@ -53,8 +55,74 @@ class LearningRateScheduler(Callback):
         super().__init__()
         self.schedule = schedule
 
+    def set_model(self, model):
+        super().set_model(model)
+        _refuse_schedule(self)
+
+    def on_train_begin(self, logs=None):
+        _refuse_schedule(self)
+
     def on_epoch_begin(self, epoch, logs=None):
         self.model.optimizer.lr = float(self.schedule(epoch))
+
+
+def _refuse_schedule(cb):
+    """keras: a callback that sets the learning rate refuses an optimizer whose learning rate is a schedule object"""
+    opt = getattr(cb.model, "optimizer", None)
+    if optimizer_schedule(opt) is not None:
+        raise TypeError(f"{type(cb).__name__} sets optimizer.lr, but the optimizer's learning rate is the schedule "
+                        f"{opt.lr!r}: use one or the other")
+
+
+class ReduceLROnPlateau(Callback):
+    """tf.keras.callbacks.ReduceLROnPlateau(monitor, factor, patience, min_delta, min_lr, cooldown, mode) -- commented out
+    in the reference's main*.py.  Host only, once per epoch, through ``optimizer.lr``: when ``monitor`` has not improved
+    by more than ``min_delta`` for ``patience`` epochs, lr = max(lr * factor, min_lr), and ``cooldown`` epochs pass before
+    the count starts again.  mode "min" / "max"; "auto" is "max" for a monitor with "acc" in its name."""
+
+    def __init__(self, monitor="val_loss", factor=0.1, patience=10, verbose=0, mode="auto", min_delta=1e-4, cooldown=0,
+                 min_lr=0.0):
+        super().__init__()
+        if not 0.0 <= factor < 1.0:
+            raise ValueError(f"ReduceLROnPlateau does not support a factor outside [0, 1), got {factor!r}")
+        if mode not in ("auto", "min", "max"):
+            raise ValueError(f"mode must be 'auto', 'min' or 'max', got {mode!r}")
+        if patience < 0 or cooldown < 0 or min_lr < 0 or min_delta < 0:
+            raise ValueError("patience, cooldown, min_lr and min_delta must be >= 0")
+        self.monitor, self.factor, self.patience, self.min_delta = monitor, float(factor), int(patience), float(min_delta)
+        self.cooldown, self.min_lr = int(cooldown), float(min_lr)
+        self.sign = -1 if (mode == "max" or (mode == "auto" and "acc" in monitor)) else 1
+        self._reset()
+
+    def _reset(self):
+        self.best, self.wait, self.cooldown_counter = float("inf"), 0, 0
+
+    def set_model(self, model):
+        super().set_model(model)
+        _refuse_schedule(self)
+
+    def on_train_begin(self, logs=None):
+        _refuse_schedule(self)
+        self._reset()
+
+    def on_epoch_end(self, epoch, logs=None):
+        cur = (logs or {}).get(self.monitor)
+        if logs is not None:
+            logs["lr"] = self.model.optimizer.lr
+        if cur is None:
+            return
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if self.sign * cur < self.best - self.min_delta:
+            self.best, self.wait = self.sign * cur, 0
+        elif self.cooldown_counter == 0:
+            self.wait += 1
+            if self.wait >= self.patience:
+                old = self.model.optimizer.lr
+                if old > self.min_lr:
+                    self.model.optimizer.lr = max(old * self.factor, self.min_lr)
+                    self.cooldown_counter, self.wait = self.cooldown, 0
 
 
 class ModelCheckpoint(Callback):

@@ -3,6 +3,7 @@ yaml.safe_load at main.py:36-38) is accepted unchanged; ``build_model`` construc
 the way main.py:113-134 does."""
 import yaml
 
+from . import schedules
 from .optimizers import Adam, SGD, CategoricalCrossentropy
 
 
@@ -13,10 +14,14 @@ def load_config(path):
 
 def build_optimizer(config):
     """main.py:96-104 (the Adam learning rate is hard-coded to 1e-4 there; config['alpha'] holds the same value)."""
+    # lr_schedule: an optional key of this library's (main.py:81-84 builds its schedule in code): ``kind`` plus that
+    # optimizers.schedules class's arguments, optional warmup_steps / warmup_start.  It takes the learning rate's place
+    sched = schedules.from_config(config["lr_schedule"]) if config.get("lr_schedule") is not None else None
     if config["optimizer"] == "Adam":
-        return Adam(learning_rate=0.0001, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9, clipnorm=config["clipnorm"])
+        return Adam(learning_rate=0.0001 if sched is None else sched, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9,
+                    clipnorm=config["clipnorm"])
     if config["optimizer"] == "SGD":
-        return SGD(learning_rate=config["alpha"], momentum=0.9, nesterov=False)
+        return SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False)
     raise ValueError("No optimizer specified")
 
 

@@ -1065,7 +1065,10 @@ class NIC(ModelBase):
                 tag, k = chr(ord("A") + q), 8 + 4 * q
                 out[f"loss{tag}"], out[f"accuracy{tag}"], out[f"attention{tag}"] = m[k], m[k + 1], m[k + 2]
         if with_lr:
-            out["lr"] = torch.tensor(self._lr_host, dtype=torch.float32)      # host-set (ModelBase._sync_lr): no device copy
+            if self.__dict__.get("lr_schedule") is not None:
+                self._lr_metric(out)                                          # computed on the device: read from there
+            else:
+                out["lr"] = torch.tensor(self._lr_host, dtype=torch.float32)  # host-set (ModelBase._sync_lr): no device copy
         out._ring = self.__dict__.get("_last_ring")
         return out.guarded(self, m[self.GUARD]) if self.__dict__.get("_seq_lstm") else out
 

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood, optimizer_average
+from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood, optimizer_average, optimizer_schedule
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -825,6 +825,8 @@ class ModelBase:
         self.label_smoothing = 0.0          # of the compile loss (CategoricalCrossentropy(label_smoothing=...))
         self.unlikelihood = 0.0             # of the compile loss (CategoricalCrossentropy(unlikelihood=...))
         self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
+        self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
+        self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
         self.built = False
         self.stop_training = False
         self._graphs = {}
@@ -864,6 +866,11 @@ class ModelBase:
         if avg != self.__dict__.get("average"):
             self._graphs = {}
         self.average = avg
+        # so does the schedule's launch (tnt_lr_schedule_f32); its parameters live in a device buffer of the model's
+        sched = optimizer_schedule(self.optimizer)
+        if sched != self.__dict__.get("lr_schedule"):
+            self._graphs = {}
+        self.lr_schedule = sched
         if self.built:
             self._init_optimizer_state()
 
@@ -889,9 +896,12 @@ class ModelBase:
         self.opt_m = torch.zeros_like(a.theta)
         self.opt_v = torch.zeros_like(a.theta) if self.optimizer.kind == "adam" else None
         self.adam_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.tensor([self.optimizer.lr], dtype=torch.float32, device=self.device)
+        sched = self.__dict__.get("lr_schedule")
+        # with a schedule the host never writes lr_dev again: every step's tnt_lr_schedule_f32 launch does, from adam_t
+        self.lr_dev = torch.tensor([self.optimizer.lr if sched is None else sched(0)], dtype=torch.float32, device=self.device)
         self.lr_t_dev = self._f(1)
-        self._lr_host = self.optimizer.lr
+        self._lr_host = self.optimizer.lr if sched is None else None
+        self._set_lr_schedule(sched)
         # the weight average (optimizers.MovingAverage / SWA): one more slot over the whole arena, padding included (zero in
         # both buffers, and it stays zero).  The first averaging launch overwrites it with the parameters after update
         # max(start_step, 1); until then it holds the initial ones
@@ -910,15 +920,63 @@ class ModelBase:
         if self.__dict__.get("_swapped"):
             raise RuntimeError("the averaged weights are swapped in (swap_weights / averaged_weights): a training step would "
                                "train the average and average the raw weights.  Swap back first")
+        sched = optimizer_schedule(self.optimizer)
+        if sched != self.__dict__.get("lr_schedule"):
+            # optimizer.learning_rate was assigned since compile (a float in place of the schedule, or another schedule):
+            # the step's launch sequence changes, so it is recorded again
+            self._set_lr_schedule(sched)
+            self._lr_host = None
+            self._graphs = {}
+        if sched is not None:
+            return
         if self.optimizer.lr != self._lr_host:
             self.lr_dev.fill_(self.optimizer.lr)
             self._lr_host = self.optimizer.lr
+
+    # ------------------------------------------------------------------ learning-rate schedule (optimizers.schedules)
+    def _set_lr_schedule(self, sched):
+        """the schedule of the training steps from here on, its 16 float64 parameters in a device buffer of the model's"""
+        self.lr_schedule = sched
+        self.lr_params = None if sched is None else torch.tensor(sched.params(), dtype=torch.float64, device=self.device)
+
+    def _lr_schedule_launch(self):
+        """The schedule's launch of a step (tnt_lr_schedule_f32: lr_dev = schedule(adam_t), adam_t the updates applied so
+        far), inside the same recorded plan / graph and in front of the step's first launch that reads lr_dev.  No guard: a
+        step whose guard word tripped leaves adam_t, so the next step computes the same value.  Nothing with a float
+        learning rate."""
+        if self.__dict__.get("lr_schedule") is not None:
+            self.be.lr_schedule(self.adam_t, self.lr_params, self.lr_dev)
+
+    def _lr_metric(self, out):
+        """with a schedule: the ``lr`` entry of a training step's metrics is the float32 its update used, read from the
+        device with the other metrics (a copy of lr_dev behind the step)"""
+        if self.__dict__.get("lr_schedule") is not None:
+            out["lr"] = self.lr_dev.clone()[0]
+        return out
+
+    @property
+    def iterations(self):
+        """keras's optimizer.iterations: the updates applied so far, read from the device counter (a guarded step does not
+        count); what the learning-rate schedule, scheduled sampling and the weight average see"""
+        t = self.__dict__.get("adam_t")
+        return 0 if t is None else int(t[0])
+
+    def set_iterations(self, n):
+        """Writes the update counter, and nothing else (the dropout stream's counter stays): a run continued from
+        load_weights with fit(initial_epoch=) puts the learning-rate schedule where it left off.  Adam's bias correction
+        reads the same counter."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"iterations must be an int >= 0, got {n!r}")
+        if self.__dict__.get("adam_t") is None:
+            raise RuntimeError("set_iterations: the counter exists once the optimizer state does (compile and build the model)")
+        self.adam_t.fill_(int(n))
 
     def _apply_optimizer(self):
         """per-variable clipnorm + Adam/SGD (optimizer.apply_gradients, lc_NIC.py:389)."""
         be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
         clip = opt.clipnorm if opt.clipnorm is not None else 0.0
         gd = self._guard_word()
+        self._lr_schedule_launch()
         if opt.kind == "adam":
             be.step_tick(self.adam_t, self.drop_step, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2, guard=gd)
             be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
@@ -965,6 +1023,8 @@ class ModelBase:
         gd = self._guard_word()
         adam = opt.kind == "adam"
         enc = self.__dict__.pop("_enc_fused", None)
+        # lr_dev is first read by the norm launch that carries the lr job, else by the finalize launch: the schedule goes here
+        self._lr_schedule_launch()
         # no finalize launch (tnt_adam_fin_f32): the norm launch leaves lr_t, the update launches sum the clip norms they need
         # from the span partials themselves, one extra workgroup of the Adam launch files the scalars, the counters tick at its end
         fin = adam and hasattr(be, "adam_fin") and getattr(self, "fused_finalize", True)
@@ -1152,6 +1212,7 @@ class ModelBase:
 
     def _tick(self):
         opt, gd = self.optimizer, self._guard_word()
+        self._lr_schedule_launch()
         if opt.kind == "adam":
             self.be.step_tick(self.adam_t, self.drop_step, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2, guard=gd)
         else:

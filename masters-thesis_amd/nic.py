@@ -686,7 +686,7 @@ class NIC(ModelBase):
             self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
-        return self._metrics_from(m, loss=0, L2=2, accuracy=1)
+        return self._lr_metric(self._metrics_from(m, loss=0, L2=2, accuracy=1))
 
     # ------------------------------------------------------------------ self-critical sequence training
     def _scst_bufs(self, B, T):
@@ -824,8 +824,8 @@ class NIC(ModelBase):
         self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
-        return self._metrics_from(m, loss=0, L2=2, reward=float(reward.mean()), baseline=float(base.mean()),
-                                  sample_len=float(counted.mean()))
+        return self._lr_metric(self._metrics_from(m, loss=0, L2=2, reward=float(reward.mean()), baseline=float(base.mean()),
+                                                  sample_len=float(counted.mean())))
 
     def test_step(self, data):
         """NIC.test_step (NIC.py:254-299)."""

@@ -741,6 +741,12 @@ class HipBackend:
         self._call(self.lib.tnt_weight_average_f32, "tnt_weight_average_f32", _p(theta), _p(avg), int(n), _p(step), int(kind),
                    _ct.addressof(mom), int(bool(dynamic)), int(start_step), int(every), _p(guard), self._s())
 
+    def lr_schedule(self, step, params, lr):
+        """lr[0] = float32(schedule(*step)) (tnt_lr_schedule_f32; definition and parameter layout in include/tnt_hip.h):
+        ``step`` the int64 update counter, ``params`` the 16 float64 of schedules.LearningRateSchedule.params(), both read
+        on the device"""
+        self._call(self.lib.tnt_lr_schedule_f32, "tnt_lr_schedule_f32", _p(step), _p(params), _p(lr), self._s())
+
     def swap(self, a, b, n):
         """a <-> b over n floats, in place (tnt_swap_f32)"""
         self._call(self.lib.tnt_swap_f32, "tnt_swap_f32", _p(a), _p(b), int(n), self._s())

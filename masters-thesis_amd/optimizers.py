@@ -3,50 +3,60 @@
 They carry hyper-parameters only; the arithmetic is the multi-tensor HIP kernels in
 csrc/optim.hip driven by the model (reference construction: AttemptFour/main.py:97-110).
 """
+from . import schedules
+from .schedules import LearningRateSchedule
 
 
-class Adam:
+class _LearningRate:
+    """``lr`` / ``learning_rate`` of a descriptor: a float, or a schedules.LearningRateSchedule (main.py:81-84), which
+    ``learning_rate`` and ``lr`` then return as the object.  A model compiled with a schedule evaluates it on the device
+    per update (ModelBase._lr_schedule_launch); assigning a float replaces the schedule."""
+
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, v):
+        self._lr = v if isinstance(v, LearningRateSchedule) else float(v)
+
+    learning_rate = lr
+
+
+def optimizer_schedule(optimizer):
+    """the LearningRateSchedule a descriptor holds as its learning rate, or None for a float"""
+    lr = getattr(optimizer, "lr", None)
+    return lr if isinstance(lr, LearningRateSchedule) else None
+
+
+class Adam(_LearningRate):
     """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm) -- main.py:97.
+    ``learning_rate``: a float or an ``optimizers.schedules`` object.
     ``clipnorm`` is per variable; None disables it (the TF<=2.3 behaviour of a
     custom tape.gradient -> apply_gradients step)."""
 
     kind = "adam"
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, **kw):
-        self.lr = float(kw.pop("lr", learning_rate))
+        self.lr = kw.pop("lr", learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.clipnorm = None if clipnorm is None else float(clipnorm)
         self.iterations = 0
 
-    @property
-    def learning_rate(self):
-        return self.lr
 
-    @learning_rate.setter
-    def learning_rate(self, v):
-        self.lr = float(v)
-
-
-class SGD:
-    """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False) -- main.py:100-102."""
+class SGD(_LearningRate):
+    """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False) -- main.py:100-102.  ``learning_rate``: a float
+    or an ``optimizers.schedules`` object."""
 
     kind = "sgd"
 
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, **kw):
         if nesterov:
             raise NotImplementedError("nesterov momentum is not used by the reference path")
-        self.lr = float(kw.pop("lr", learning_rate))
+        self.lr = kw.pop("lr", learning_rate)
         self.momentum = float(momentum)
         self.clipnorm = None if clipnorm is None else float(clipnorm)
         self.iterations = 0
-
-    @property
-    def learning_rate(self):
-        return self.lr
-
-    @learning_rate.setter
-    def learning_rate(self, v):
-        self.lr = float(v)
 
 
 class Average:

@@ -276,7 +276,7 @@ class CaptionGenerator(ModelBase):
         else:
             self._train_step_dp(B, T, fb, up)
         self.optimizer.iterations += 1
-        return self._result()
+        return self._lr_metric(self._result())
 
     def train_step_SAM(self, data, rho=0.05):
         """Sharpness-aware step (ThinkAndTell/model.py:166-233): ascent by rho*g/||g||, second gradient
@@ -301,7 +301,7 @@ class CaptionGenerator(ModelBase):
             self._apply_optimizer()
         self._run_captured(("sam", B, T), run)
         self.optimizer.iterations += 1
-        return self._result()
+        return self._lr_metric(self._result())
 
     def test_step(self, data):
         img, target = self._unpack_batch(data)
