@@ -6,6 +6,7 @@
 // np.argmax in the greedy decoders (lc_NIC.py:627; NIC.py:192).
 #include "tnt_common.h"
 #include "tnt_rng.h"
+#include "tnt_rowhead.h"   // the NV4 ladder only (tnt_row_ladder); the head kernels below keep their own text
 
 namespace {
 
@@ -716,21 +717,17 @@ extern "C" int32_t tnt_softmax_cce_f32(const float* logits, const int32_t* targe
   hipStream_t s = tnt_stream(stream);
   const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
                   (!dlogits || tnt_aligned16(dlogits));
-  const int nv4 = (V + 1023) / 1024;
   const int* live = nullptr;             // the plain head: every row, unit weights
   const float* wrow = nullptr;
-#define TNT_SMX(N)                                                                                              \
-  hipLaunchKernelGGL((softmax_cce_reg_kernel<N>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, \
-                     correct_row, dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow)
-  if (al && nv4 == 1) TNT_SMX(1);
-  else if (al && nv4 == 2) TNT_SMX(2);
-  else if (al && nv4 <= 4) TNT_SMX(4);
-  else if (al && nv4 <= 5) TNT_SMX(5);
-  else if (al && nv4 <= 8) TNT_SMX(8);
-  else
-    hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
-                       dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow);
-#undef TNT_SMX
+  tnt_row_ladder(al, V, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N > 0)
+      hipLaunchKernelGGL((softmax_cce_reg_kernel<N>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row,
+                         correct_row, dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow);
+    else
+      hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
+                         dlogits, rows, V, ld, gscale, from_logits, mask_zero, live, wrow);
+  });
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -748,19 +745,15 @@ extern "C" int32_t tnt_softmax_cce_live_f32(const float* logits, const int32_t* 
   hipStream_t s = tnt_stream(stream);
   const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
                   (!dlogits || tnt_aligned16(dlogits));
-  const int nv4 = (V + 1023) / 1024;
-#define TNT_SMXL(N)                                                                                             \
-  hipLaunchKernelGGL((softmax_cce_reg_kernel<N, true>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, \
-                     correct_row, dlogits, rows, V, ld, gscale, 0, 0, live, row_weight)
-  if (al && nv4 == 1) TNT_SMXL(1);
-  else if (al && nv4 == 2) TNT_SMXL(2);
-  else if (al && nv4 <= 4) TNT_SMXL(4);
-  else if (al && nv4 <= 5) TNT_SMXL(5);
-  else if (al && nv4 <= 8) TNT_SMXL(8);
-  else
-    hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
-                       dlogits, rows, V, ld, gscale, 0, 0, live, row_weight);
-#undef TNT_SMXL
+  tnt_row_ladder(al, V, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N > 0)
+      hipLaunchKernelGGL((softmax_cce_reg_kernel<N, true>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row,
+                         correct_row, dlogits, rows, V, ld, gscale, 0, 0, live, row_weight);
+    else
+      hipLaunchKernelGGL(softmax_cce_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, correct_row,
+                         dlogits, rows, V, ld, gscale, 0, 0, live, row_weight);
+  });
   TNT_LAUNCH_CHECK();
   return 0;
 }

@@ -1,8 +1,10 @@
 // Softmax + CategoricalCrossentropy(from_logits=False) + token-level unlikelihood (Welleck et al. 2020) in one launch
 // (tnt_softmax_cce_unlikely_f32; definition in include/tnt_hip.h, restated by tests/unlikelihood_oracle.py).
 //
-// Same structure as softmax_cce_reg_kernel / softmax_cce_kernel (seqops.hip): one 256-thread workgroup per row, max and
-// first-maximum index, exp-sum, one write; two barriers, as there.  What the unlikelihood term adds:
+// One 256-thread workgroup per row; the row walk (load + max, first-maximum index, exp-sum), the block reductions and the
+// kernel ladder come from tnt_rowhead.h, and the one kernel template below holds what is the unlikelihood term's own.
+// Two barriers, as in the plain head (seqops.hip): tnt_rowhead.h's reductions carry one each and none behind the combine.
+// What the unlikelihood term adds:
 //   * the candidate set C of row (t, b), the distinct ids of target[0 .. t-1][b] without y, 0 and ids outside [0, V).
 //     Wave 0 forms it between the two barriers: lane j < t holds target[j * B + b] (loaded at the top of the kernel, so
 //     that load's latency hides behind the row load), duplicates go by wave shuffles (first occurrence wins), the
@@ -96,69 +98,10 @@ __device__ __forceinline__ float ul_cand_grad(const UlCand& c, int k, const UlRo
   return (r.coef * pc + alpha * ul_q(pc)) * gs;
 }
 
-// register-resident: V <= 1024 * NV4, ld % 4 == 0, 16-byte aligned rows
+// NV4 >= 1: register-resident row (V <= 1024 * NV4, ld % 4 == 0, 16-byte aligned rows), which also zeroes the pad columns
+// inside its window; NV4 == 0: re-reading row (any V, ld, alignment), which neither reads nor writes a pad column.
+// Column c belongs to the thread that stores it: (c >> 2) & 255 on the register row, c & 255 on the re-reading row.
 template <int NV4>
-__global__ __launch_bounds__(256) void softmax_cce_unlikely_reg_kernel(const float* logits, const int* target, float* probs,
-                                                                       float* loss_row, float* correct_row, float* dlogits,
-                                                                       int B, int V, int ld, float gscale, float alpha) {
-  __shared__ float shm[4], shz[4];
-  __shared__ int shi[4];
-  __shared__ UlCand cand;
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const float* x = logits + (long)row * ld;
-  const int t = row / B, b = row - t * B;
-  const bool form = target != nullptr && alpha > 0.f && t > 0;
-  const int y = target ? target[row] : -1;
-  int cid = 0;
-  if (form && tid < t) cid = target[tid * B + b];            // t <= 63: lanes of wave 0
-  if (tid == 0 && !form) cand.n = 0;
-  float4 v[NV4];
-  float m = tnt_row_load_max<NV4>(x, tid, V, ld, v);
-  m = tnt_wave_max(m);
-  if ((tid & 63) == 0) shm[tid >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
-  int am = tnt_row_first_max<NV4>(v, m, tid);
-  if ((tid & 63) == 0) shi[tid >> 6] = am;
-  const bool has_y = y >= 0 && y < V;
-  const float xy = has_y ? x[y] : -INFINITY;                 // before any thread overwrites the row (aliasing)
-  if (form && tid < 64) ul_form_candidates(cand, x, cid, t, y, V, tid);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-    v[i].x = expf(v[i].x - m); v[i].y = expf(v[i].y - m); v[i].z = expf(v[i].z - m); v[i].w = expf(v[i].w - m);
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  }
-  s = tnt_wave_sum(s);
-  if ((tid & 63) == 0) shz[tid >> 6] = s;
-  __syncthreads();                                           // also: the candidates are in LDS
-  const float Z = (shz[0] + shz[1]) + (shz[2] + shz[3]);
-  am = min(min(shi[0], shi[1]), min(shi[2], shi[3]));
-  const float invZ = 1.f / Z;
-  const UlRow r = ul_row_tail(cand, row, y, has_y, xy, m, invZ, am, alpha, target != nullptr, loss_row, correct_row);
-  const float gs = target ? gscale : 0.f;                    // no target: no loss to differentiate, zero rows
-  float* drow = dlogits ? dlogits + (long)row * ld : nullptr;
-  float* prow = (probs && probs != dlogits) ? probs + (long)row * ld : nullptr;
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-    const int j = 4 * (tid + 256 * i);
-    if (j >= ld) continue;
-    const float4 p = make_float4(v[i].x * invZ, v[i].y * invZ, v[i].z * invZ, v[i].w * invZ);
-    if (drow)
-      *reinterpret_cast<float4*>(drow + j) = make_float4(r.coef * p.x * gs, r.coef * p.y * gs, r.coef * p.z * gs, r.coef * p.w * gs);
-    if (prow) *reinterpret_cast<float4*>(prow + j) = p;
-  }
-  if (!drow) return;
-  // the threads that own column y and the candidate columns patch them after their own vector store
-  if (has_y && ((y >> 2) & 255) == tid) drow[y] = (r.coef * r.py - r.my) * gs;
-  const int nc = cand.n;
-  for (int k = 0; k < nc; ++k) {
-    const int c = cand.id[k];
-    if (((c >> 2) & 255) == tid) drow[c] = ul_cand_grad(cand, k, r, m, invZ, alpha, gs);
-  }
-}
-
-// generic: any V, ld, alignment.  Neither reads nor writes a pad column.
 __global__ __launch_bounds__(256) void softmax_cce_unlikely_kernel(const float* logits, const int* target, float* probs,
                                                                    float* loss_row, float* correct_row, float* dlogits,
                                                                    int B, int V, int ld, float gscale, float alpha) {
@@ -171,39 +114,52 @@ __global__ __launch_bounds__(256) void softmax_cce_unlikely_kernel(const float* 
   const bool form = target != nullptr && alpha > 0.f && t > 0;
   const int y = target ? target[row] : -1;
   int cid = 0;
-  if (form && tid < t) cid = target[tid * B + b];
+  if (form && tid < t) cid = target[tid * B + b];            // t <= 63: lanes of wave 0
   if (tid == 0 && !form) cand.n = 0;
-  float m;
+  TntRow<NV4> w{x, V};
   int am;
-  tnt_row_scan_argmax(x, V, tid, m, am);
-  if ((tid & 63) == 0) { shm[tid >> 6] = m; shi[tid >> 6] = am; }
-  __syncthreads();
-  tnt_row_combine_argmax(shm, shi, m, am);
+  const float m = w.max_first(shm, shi, am);                 // the first barrier
   const bool has_y = y >= 0 && y < V;
   const float xy = has_y ? x[y] : -INFINITY;                 // before any thread overwrites the row (aliasing)
   if (form && tid < 64) ul_form_candidates(cand, x, cid, t, y, V, tid);
-  float s = 0.f;
-  for (int j = tid; j < V; j += 256) s += expf(x[j] - m);
-  s = tnt_wave_sum(s);
-  if ((tid & 63) == 0) shz[tid >> 6] = s;
-  __syncthreads();                    // also: the candidates' logits are in LDS, and every read of the row above precedes every write below
-  const float Z = (shz[0] + shz[1]) + (shz[2] + shz[3]);
+  // the second barrier; also: the candidates and their logits are in LDS, and every read of the row above precedes every
+  // write below
+  const float Z = tnt_block_sum4(w.exp_sum(m), shz);
+  am = w.first(shi, am);
   const float invZ = 1.f / Z;
   const UlRow r = ul_row_tail(cand, row, y, has_y, xy, m, invZ, am, alpha, target != nullptr, loss_row, correct_row);
-  const float gs = target ? gscale : 0.f;
-  if (!dlogits && !probs) return;
-  // logits may alias probs/dlogits: every thread reads its own elements before overwriting them
-  for (int j = tid; j < V; j += 256) {
-    const float p = expf(x[j] - m) * invZ;
-    if (dlogits) dlogits[(long)row * ld + j] = (j == y) ? (r.coef * r.py - r.my) * gs : r.coef * p * gs;
-    if (probs && probs != dlogits) probs[(long)row * ld + j] = p;
+  const float gs = target ? gscale : 0.f;                    // no target: no loss to differentiate, zero rows
+  float* drow = dlogits ? dlogits + (long)row * ld : nullptr;
+  float* prow = (probs && probs != dlogits) ? probs + (long)row * ld : nullptr;
+  if constexpr (NV4 > 0) {
+#pragma unroll
+    for (int i = 0; i < NV4; ++i) {
+      const int j = 4 * (tid + 256 * i);
+      if (j >= ld) continue;
+      const float4 e = w.d[i];
+      const float4 p = make_float4(e.x * invZ, e.y * invZ, e.z * invZ, e.w * invZ);
+      if (drow)
+        *reinterpret_cast<float4*>(drow + j) = make_float4(r.coef * p.x * gs, r.coef * p.y * gs, r.coef * p.z * gs, r.coef * p.w * gs);
+      if (prow) *reinterpret_cast<float4*>(prow + j) = p;
+    }
+  } else {
+    if (!drow && !prow) return;
+    // logits may alias probs/dlogits: every thread reads its own elements before overwriting them
+    for (int j = tid; j < V; j += 256) {
+      const float p = expf(x[j] - m) * invZ;
+      if (drow) drow[j] = r.coef * p * gs;
+      if (prow) prow[j] = p;
+    }
   }
-  if (!dlogits) return;
-  // column c belongs to thread c % 256, which patches it after its own store
+  if (!drow) return;
+  // the threads that own column y and the candidate columns patch them after their own store (same thread, same address:
+  // program order)
+  const auto owner = [](int c) { return NV4 > 0 ? (c >> 2) & 255 : c & 255; };
+  if (has_y && owner(y) == tid) drow[y] = (r.coef * r.py - r.my) * gs;
   const int nc = cand.n;
   for (int k = 0; k < nc; ++k) {
     const int c = cand.id[k];
-    if ((c & 255) == tid) dlogits[(long)row * ld + c] = ul_cand_grad(cand, k, r, m, invZ, alpha, gs);
+    if (owner(c) == tid) drow[c] = ul_cand_grad(cand, k, r, m, invZ, alpha, gs);
   }
 }
 
@@ -224,19 +180,10 @@ extern "C" int32_t tnt_softmax_cce_unlikely_f32(const float* logits, const int32
   hipStream_t s = tnt_stream(stream);
   const bool al = (ld % 4 == 0) && tnt_aligned16(logits) && (!probs || tnt_aligned16(probs)) &&
                   (!dlogits || tnt_aligned16(dlogits));
-  const int nv4 = (V + 1023) / 1024;
-#define TNT_UNLIKELY(N)                                                                                                  \
-  hipLaunchKernelGGL((softmax_cce_unlikely_reg_kernel<N>), dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row, \
-                     correct_row, dlogits, B, V, ld, gscale, alpha)
-  if (al && nv4 == 1) TNT_UNLIKELY(1);
-  else if (al && nv4 == 2) TNT_UNLIKELY(2);
-  else if (al && nv4 <= 4) TNT_UNLIKELY(4);
-  else if (al && nv4 <= 5) TNT_UNLIKELY(5);
-  else if (al && nv4 <= 8) TNT_UNLIKELY(8);
-  else
-    hipLaunchKernelGGL(softmax_cce_unlikely_kernel, dim3(rows), dim3(256), 0, s, logits, target, probs, loss_row,
-                       correct_row, dlogits, B, V, ld, gscale, alpha);
-#undef TNT_UNLIKELY
+  tnt_row_ladder(al, V, [&](auto n) {
+    hipLaunchKernelGGL((softmax_cce_unlikely_kernel<decltype(n)::value>), dim3(rows), dim3(256), 0, s, logits, target, probs,
+                       loss_row, correct_row, dlogits, B, V, ld, gscale, alpha);
+  });
   TNT_LAUNCH_CHECK();
   return 0;
 }

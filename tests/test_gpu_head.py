@@ -23,9 +23,9 @@ FLT_MIN = 2.0 ** -126           # below this a result may be a flushed / rounded
 SENT = 1234.5                   # sentinel in every output buffer: no output of the kernel can take this value
 CLIP = O.CCE_EPS
 
-# the dispatch ladder of tnt_softmax_cce_f32 (seqops.hip): (largest nv4 = ceil(V / 1024) of the bucket, NV4 of the
-# register kernel it launches); anything past the last bucket, and any unaligned call, runs the generic kernel.
-# tests/test_host_softmax_dispatch.py checks this table and V_LIST against the source.
+# the dispatch ladder of every softmax head, tnt_row_ladder (csrc/tnt_rowhead.h), restated: (largest nv4 = ceil(V / 1024)
+# of the bucket, NV4 of the register kernel it launches); anything past the last bucket, and any unaligned call, runs the
+# generic kernel.  tests/test_host_softmax_dispatch.py checks this table and V_LIST against the source.
 SMX_LADDER = ((1, 1), (2, 2), (4, 4), (5, 5), (8, 8))
 V_LIST = [1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2048, 2049, 4096, 4097, 5001, 5120, 5121,
           8192, 8193, 16384, 40000]

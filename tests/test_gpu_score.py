@@ -1,5 +1,6 @@
 """Caption log-likelihood scoring on the GPU: tnt_caption_score_f32 against the float64 restatement over the grid of
-vocabularies, leading dimensions and rows that test_gpu_scst.py uses (plus a vocabulary for the generic path), with
+vocabularies, leading dimensions, layouts and rows that test_gpu_scst.py uses (plus a vocabulary for the generic path), with
+NaN / 1e30 in the pad columns,
 every terminator kind by row and the optional outputs on and off; score_captions of both caption models against the
 float64 oracle at a small shape and at the BASELINE shape; ranking; captured replay; and training after scoring."""
 import numpy as np
@@ -7,6 +8,7 @@ import pytest
 import torch
 
 from helpers import synth_batch
+from test_gpu_head import fill_pad, layouts
 from score_oracle import (END, SMALL, build_pair, caption_score, ident_case, make_captions, rank_margin_check, ranks, scans,
                           score_model)
 
@@ -28,32 +30,42 @@ def bound(want):
     return 1e-4 * np.maximum(1.0, np.abs(want))
 
 
-def launch(be, x, ld, V, cap, steps, end_id, tok_on=True, len_on=True):
+def launch(be, x, ld, V, cap, steps, end_id, tok_on=True, len_on=True, shift=0):
     R, T = cap.shape
     tok = torch.full((steps * R,), -9.0, device="cuda") if tok_on else None
     lp = torch.full((R,), -9.0, device="cuda")
     ln = torch.full((R,), -9, dtype=torch.int32, device="cuda") if len_on else None
-    logits = dev(x)
+    buf = torch.full((shift + x.size,), -7.0, device="cuda")                            # the view starts `shift` floats in
+    logits = buf[shift:].view(x.shape)
+    logits.copy_(dev(x))
     be.caption_score(logits, ld, V, dev(cap), T, steps, R, end_id, tok, lp, ln)
     torch.cuda.synchronize()
     assert np.array_equal(logits.cpu().numpy(), x, equal_nan=True)                       # read-only
     return (tok.cpu().numpy() if tok_on else None), lp.cpu().numpy(), (ln.cpu().numpy() if len_on else None)
 
 
-@pytest.mark.parametrize("V,ld", [(13, 16), (13, 16 + 3), (5001, 5004), (5001, 5001 + 7), (5001, 5012), (9000, 9000)])
-@pytest.mark.parametrize("R", [6, 64, 320])
-def test_kernel_matches_float64(be, V, ld, R):
-    rng = np.random.default_rng(V + R + ld)
+# both sides of every bound of the kernel ladder (tnt_row_ladder, csrc/tnt_rowhead.h): every caption_score_row_kernel<NV4> and
+# caption_score_cap_kernel<NV4> and, in the "odd" and "shift" layouts, their re-reading forms at the same V
+LADDER_V = (1024, 1025, 2048, 2049, 4096, 4097, 5120, 5121, 8192, 8193)
+# (R, V, ld, float offset of the logits view); the ids of the first group are those of the former (V, ld) x R grid
+KERNEL_CASES = [pytest.param(R, V, ld, 0, id=f"{R}-{V}-{ld}") for R in (6, 64, 320)
+                for V, ld in ((13, 16), (13, 16 + 3), (5001, 5004), (5001, 5001 + 7), (5001, 5012), (9000, 9000))]
+KERNEL_CASES += [pytest.param(6, V, ld, shift, id=f"6-{V}-{name}") for V in LADDER_V for name, ld, shift in layouts(V)]
+
+
+@pytest.mark.parametrize("R,V,ld,shift", KERNEL_CASES)
+def test_kernel_matches_float64(be, R, V, ld, shift):
+    rng = np.random.default_rng(V + R + ld + shift)
     T = 6
     for end_id, steps in ((END, T - 1), (-1, T - 1), (END, 3)):
         cap = make_captions(rng, R, T, V, end_id)
         x = (rng.standard_normal((steps * R, ld)) * 3).astype(np.float32)
         want_tok, want_lp, want_len = caption_score(x[:, :V].astype(np.float64), cap, end_id, steps)
-        x[:, V:] = 1e30                                      # pad columns: a sentinel that would swamp any row that read it
+        fill_pad(x, V)                                       # pad columns: NaN / 1e30 would swamp any row that used them
         x[(want_tok == 0).reshape(-1)] = np.nan              # rows that do not count: never read
         outs = []
         for tok_on, len_on in ((True, True), (False, True), (True, False), (False, False)):
-            tok, lp, ln = launch(be, x, ld, V, cap, steps, end_id, tok_on, len_on)
+            tok, lp, ln = launch(be, x, ld, V, cap, steps, end_id, tok_on, len_on, shift)
             if tok_on:
                 assert np.allclose(tok, want_tok.reshape(-1), rtol=1e-5, atol=1e-5)
                 assert np.all(tok[(want_tok == 0).reshape(-1)] == 0.0)
@@ -63,7 +75,7 @@ def test_kernel_matches_float64(be, V, ld, R):
             outs.append(lp)
         for lp in outs[1:]:                                  # with or without tok_lp, run to run: the same bits
             assert np.array_equal(lp, outs[0])
-        assert np.array_equal(launch(be, x, ld, V, cap, steps, end_id)[1], outs[0])
+        assert np.array_equal(launch(be, x, ld, V, cap, steps, end_id, shift=shift)[1], outs[0])
         assert 0 < (want_tok != 0).sum() < want_tok.size
 
 

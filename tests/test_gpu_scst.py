@@ -1,5 +1,6 @@
 """Self-critical sequence training on the GPU: tnt_scst_cce_f32 against the float64 restatement over a grid of
-vocabularies, leading dimensions, rows, advantages and terminator positions; nic.NIC's SCST step against the float64
+vocabularies (both sides of every bound of the kernel ladder, in the four layouts of test_gpu_head.layouts), leading
+dimensions, rows, advantages and terminator positions, with NaN / 1e30 in the pad columns; nic.NIC's SCST step against the float64
 step of tests/scst_oracle.py at a small shape; config 2 with K = 4 "mean" and K = 1 "greedy"; launch-plan replay against
 hipGraph replay; and a small synthetic task on which the sampled reward rises."""
 import numpy as np
@@ -7,6 +8,7 @@ import pytest
 import torch
 
 from helpers import synth_batch
+from test_gpu_head import fill_pad, layouts
 from scst_oracle import SCSTNICDense, expand, greedy, policy_grads, rollout, scst_cce
 
 pytestmark = pytest.mark.gpu
@@ -38,23 +40,37 @@ def _ids(R, T, V, rng):
     return fed, last
 
 
-@pytest.mark.parametrize("V,ld", [(13, 16), (13, 16 + 3), (5001, 5004), (5001, 5001 + 7), (5001, 5012)])
-@pytest.mark.parametrize("R", [6, 64, 320])
-def test_kernel_matches_float64(be, V, ld, R):
-    rng = np.random.default_rng(V + R + ld)
+# both sides of every bound of the kernel ladder (tnt_row_ladder, csrc/tnt_rowhead.h): every scst_cce_kernel<NV4> and, in
+# the "odd" and "shift" layouts, the re-reading kernel at the same V
+LADDER_V = (1024, 1025, 2048, 2049, 4096, 4097, 5120, 5121, 8192, 8193)
+# (R, V, ld, float offset of the logits view); the ids of the first group are those of the former (V, ld) x R grid
+KERNEL_CASES = [pytest.param(R, V, ld, 0, id=f"{R}-{V}-{ld}") for R in (6, 64, 320)
+                for V, ld in ((13, 16), (13, 16 + 3), (5001, 5004), (5001, 5001 + 7), (5001, 5012))]
+KERNEL_CASES += [pytest.param(6, V, ld, shift, id=f"6-{V}-{name}") for V in LADDER_V for name, ld, shift in layouts(V)]
+
+
+@pytest.mark.parametrize("R,V,ld,shift", KERNEL_CASES)
+def test_kernel_matches_float64(be, R, V, ld, shift):
+    rng = np.random.default_rng(V + R + ld + shift)
     T = 5
     fed, last = _ids(R, T, V, rng)
     adv = rng.standard_normal(R).astype(np.float32)
     adv[rng.integers(0, R, max(1, R // 5))] = 0.0                            # zero advantages
     adv[0], adv[min(3, R - 1)] = 1.5, -2.0
     x = (rng.standard_normal((T * R, ld)) * 3).astype(np.float32)
-    x[:, V:] = 123.0                                                          # pad columns: never read, never written
+    fill_pad(x, V)                                                            # pad columns: never used, never written
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def view(fill):                                                           # a (T R, ld) view `shift` floats into its buffer
+        buf = torch.full((shift + T * R * ld,), fill, device="cuda")
+        return buf, buf[shift:].view(T * R, ld)
+
     want_loss, want_lp, want_d, m = scst_cce(x[:, :V].astype(np.float64), fed, last, adv, END, 1.0 / R)
     for lp_on in (True, False):
         for alias in (True, False):
-            logits = dev(x)
-            out = logits if alias else torch.full_like(logits, -5.0)
+            lbuf, logits = view(-7.0)
+            logits.copy_(dev(x))
+            obuf, out = (lbuf, logits) if alias else view(-5.0)
             loss_row = torch.full((T * R,), -9.0, device="cuda")
             lp_row = torch.full((T * R,), -9.0, device="cuda") if lp_on else None
             be.scst_cce(logits, ld, V, dev(fed), T, dev(last), dev(adv), END, loss_row, lp_row, out, R, 1.0 / R)
@@ -62,7 +78,10 @@ def test_kernel_matches_float64(be, V, ld, R):
             d = out.cpu().numpy()
             tol = 2e-5 * np.abs(want_d).max() + 1e-7
             assert np.abs(d[:, :V] - want_d).max() <= tol, (lp_on, alias)
-            assert np.all(d[:, V:] == (123.0 if alias else -5.0))
+            assert np.array_equal(d[:, V:], x[:, V:] if alias else np.full_like(x[:, V:], -5.0), equal_nan=True)
+            assert np.all(obuf[:shift].cpu().numpy() == (-7.0 if alias else -5.0))
+            if not alias:
+                assert np.array_equal(logits.cpu().numpy(), x, equal_nan=True)
             zero = (m.T.reshape(-1) == 0) | (np.repeat(adv[None, :], T, 0).reshape(-1) == 0)
             assert not d[zero, :V].any()
             assert np.allclose(loss_row.cpu().numpy(), want_loss, rtol=1e-5, atol=1e-5)

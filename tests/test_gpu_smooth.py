@@ -1,8 +1,8 @@
 """The label-smoothed head (tnt_softmax_cce_smooth_f32, csrc/smooth.hip) on a real MI355X against float64
 (tests/smooth_oracle.py).
 
-The entry point has the dispatch of tnt_softmax_cce_f32: softmax_cce_smooth_reg_kernel<NV4> for 16-byte-aligned rows with
-ld % 4 == 0 and ceil(V / 1024) inside a bucket of test_gpu_head.SMX_LADDER, softmax_cce_smooth_kernel (generic) for
+The entry point has the dispatch of tnt_softmax_cce_f32: softmax_cce_smooth_kernel<NV4> for 16-byte-aligned rows with
+ld % 4 == 0 and ceil(V / 1024) inside a bucket of test_gpu_head.SMX_LADDER, softmax_cce_smooth_kernel<0> (generic) for
 everything else.  V_LIST has both sides of every bucket bound, and every V runs in the four layouts of
 test_gpu_head.layouts, so on the register kernel (where it exists) and on the generic one.  Every output is checked
 element by element against the bounds derived below; pad columns hold NaN / +1e30 and every output buffer a sentinel,

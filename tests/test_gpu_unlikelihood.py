@@ -1,8 +1,8 @@
 """The unlikelihood head (tnt_softmax_cce_unlikely_f32, csrc/unlikely.hip) on a real MI355X against float64
 (tests/unlikelihood_oracle.py).
 
-The entry point has the dispatch of tnt_softmax_cce_f32: softmax_cce_unlikely_reg_kernel<NV4> for 16-byte-aligned rows
-with ld % 4 == 0 and ceil(V / 1024) inside a bucket of test_gpu_head.SMX_LADDER, softmax_cce_unlikely_kernel (generic) for
+The entry point has the dispatch of tnt_softmax_cce_f32: softmax_cce_unlikely_kernel<NV4> for 16-byte-aligned rows
+with ld % 4 == 0 and ceil(V / 1024) inside a bucket of test_gpu_head.SMX_LADDER, softmax_cce_unlikely_kernel<0> (generic) for
 everything else.  Every V runs in the four layouts of test_gpu_head.layouts, so on the register kernel (where it exists)
 and on the generic one, with (B, T) = (1, 1), (3, 5) and (2, 64): no prefix, a short one, the full wave.  The separate
 outputs of every layout are checked element by element against the bounds derived below; the four other output forms

@@ -1,27 +1,38 @@
-"""Keeps tests/test_gpu_head.py complete: the dispatch of tnt_softmax_cce_f32 (seqops.hip) is parsed -- its nv4 bucket
-ladder and the softmax_cce_reg_kernel<N> each bucket launches -- and the GPU test's V_LIST must reach every bucket on
-both sides of each bound and the generic kernel past the last one; its SMX_LADDER (which kernel, hence which pad
+"""Keeps tests/test_gpu_head.py complete: the dispatch of tnt_softmax_cce_f32 is parsed -- the nv4 bucket ladder of
+tnt_row_ladder (tnt_rowhead.h), which seqops.hip and every other softmax head call, and the softmax_cce_reg_kernel<N> /
+generic kernel that tnt_softmax_cce_f32 launches for the N it is handed -- and the GPU test's V_LIST must reach every bucket
+on both sides of each bound and the generic kernel past the last one; its SMX_LADDER (which kernel, hence which pad
 contract, it expects) must equal the source's.  A new bucket or a moved bound fails here until the GPU test covers it.
-CPU-only: both files are parsed, not imported."""
+CPU-only: the files are parsed, not imported."""
 import ast
 import os
 import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SEQOPS = os.path.join(os.path.dirname(HERE), "masters-thesis_amd", "csrc", "seqops.hip")
+CSRC = os.path.join(os.path.dirname(HERE), "masters-thesis_amd", "csrc")
+SEQOPS = os.path.join(CSRC, "seqops.hip")
+ROWHEAD = os.path.join(CSRC, "tnt_rowhead.h")
 GPU_TEST = os.path.join(HERE, "test_gpu_head.py")
 
 
 def _dispatch():
+    src = open(ROWHEAD).read()
+    start = src.index("static inline void tnt_row_ladder(")
+    body = src[start:src.index("\n}\n", start)]
+    per = re.search(r"const int nv4 = \(V \+ (\d+)\) / (\d+);", body)
+    assert per and int(per.group(1)) + 1 == int(per.group(2)), "nv4 = ceil(V / W) not found in tnt_row_ladder"
+    ladder = [(op, int(b), int(n))
+              for op, b, n in re.findall(r"if \(aligned && nv4 (==|<=) (\d+)\) launch\(tnt_nv4<(\d+)>\{\}\);", body)]
+    assert ladder, "register-row ladder not found in tnt_row_ladder"
+    # every launch is one rung of the ladder, and the re-reading row (N = 0) is the final else
+    assert body.count("launch(tnt_nv4<") - 1 == len(ladder), "a launch outside the parsed ladder"
+    assert re.search(r"else launch\(tnt_nv4<0>\{\}\);\s*$", body), "the re-reading row is not the final else"
+    # tnt_softmax_cce_f32 takes that ladder: register kernel <N> for N > 0, the generic kernel for N = 0, nothing else
     src = open(SEQOPS).read()
     start = src.index('extern "C" int32_t tnt_softmax_cce_f32(')
     body = src[start:src.index("\n}\n", start)]
-    per = re.search(r"const int nv4 = \(V \+ (\d+)\) / (\d+);", body)
-    assert per and int(per.group(1)) + 1 == int(per.group(2)), "nv4 = ceil(V / W) not found in tnt_softmax_cce_f32"
-    ladder = [(op, int(b), int(n)) for op, b, n in re.findall(r"if \(al && nv4 (==|<=) (\d+)\) TNT_SMX\((\d+)\);", body)]
-    assert ladder, "register-kernel ladder not found in tnt_softmax_cce_f32"
-    # every TNT_SMX use is one rung of the ladder, and the generic kernel is the final else
-    assert body.count("TNT_SMX(") - 1 == len(ladder), "a TNT_SMX launch outside the parsed ladder"
+    assert body.count("tnt_row_ladder(al, V,") == 1 and body.count("hipLaunchKernelGGL(") == 2
+    assert re.search(r"if constexpr \(N > 0\)\s+hipLaunchKernelGGL\(\(softmax_cce_reg_kernel<N>\),", body)
     assert re.search(r"else\s+hipLaunchKernelGGL\(softmax_cce_kernel,", body), "generic kernel is not the final else"
     return int(per.group(2)), ladder
 
