@@ -653,6 +653,36 @@ int32_t tnt_softmax_cce_unlikely_f32(const float* logits, const int32_t* target,
                                      float* loss_row, float* correct_row, float* dlogits,
                                      int32_t B, int32_t T, int32_t V, int32_t ld, float gscale,
                                      float alpha, void* stream);
+/* ---- the same head with per-class token weights (keras fit(class_weight=)), the focal factor (Lin et al. 2017, "Focal
+ * Loss for Dense Object Detection"; keras CategoricalFocalCrossentropy) and an optional normalisation by the weight sum
+ * (the padding-masked, length-normalised caption loss), one launch (weighted.hip).  class_weight: float32[V] in device
+ * memory, nullable (every weight 1), read when the launch runs.  With p = softmax(x) over the V valid columns and
+ * y = target[r]:
+ *   w_r       = class_weight[y] if class_weight is given and 0 <= y < V, else 1
+ *   pc        = clip(p_y, 1e-7, 1 - 1e-7), p_y = 0 for y outside [0, V);   ce = -log pc
+ *   m_y       = 1 where that clip is inactive, else 0          (these three: tnt_softmax_cce_f32(from_logits=0, mask_zero=0))
+ *   f         = (1 - pc)^gamma;   g = f + gamma pc (1 - pc)^(gamma - 1) ce;   gamma == 0: f = g = 1 exactly (a branch, no powf)
+ *               (computed as q = (1 - pc)^(gamma - 1), f = q (1 - pc); q is 1 resp. 1 - pc for gamma 1 and 2, without powf)
+ *   W         = sum_r w_r over all `rows`;   k = 1 if normalise == 0, else rows / W, or 0 if W == 0
+ *   loss_row[r]    = k w_r f ce
+ *   correct_row[r] = [argmax == y] if normalise == 0, else k w_r [argmax == y]         (first maximum wins)
+ *   dlogits[r][v]  = gscale k w_r m_y g (p_v - [v == y])
+ * so the mean of loss_row over the rows is sum(w l) / rows (normalise = 0, keras's class_weight rule) or sum(w l) / sum(w)
+ * (normalise = 1), and in the latter the mean of correct_row is the accuracy over the weighted tokens.  A row with w_r == 0
+ * gives exactly 0 in loss_row, correct_row (normalise = 1) and dlogits, whatever k and its logits are.
+ * W is float32, formed inside the launch in a fixed order that is part of the definition: accumulator t of 256 adds
+ * w_t, w_(t+256), ... in ascending order starting from 0; the 64 accumulators of a wave (t / 64) are combined by the
+ * butterfly lane ^ 32, 16, 8, 4, 2, 1; the four waves as (W0 + W1) + (W2 + W3).  k = (float)rows / W.  Without
+ * class_weight W = rows and k = 1 exactly.  A weight is expected finite and >= 0 (the host checks; the kernel does not).
+ * Shared with tnt_softmax_cce_f32: every output is nullable (target null: probs only, loss_row / correct_row are not
+ * written and dlogits, if given, is zero); probs or dlogits may alias logits; pad columns [V, ld) of logits are ignored
+ * and those of an output are left as they were or written as zero (inside the register kernel's window); rows == 0 is a
+ * no-op.  TNT_BADARG for rows < 0, V <= 0, ld < V, null logits, gamma negative or not finite, normalise outside {0, 1}: a
+ * rejected call launches nothing. */
+int32_t tnt_softmax_cce_weighted_f32(const float* logits, const int32_t* target, const float* class_weight,
+                                     float* probs, float* loss_row, float* correct_row, float* dlogits,
+                                     int32_t rows, int32_t V, int32_t ld, float gscale,
+                                     float gamma, int32_t normalise, void* stream);
 /* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v (first max wins).
  * B == 0 or T == 0 is a no-op; TNT_BADARG for B < 0, T < 0, V <= 0, null pointers. */
 int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T,

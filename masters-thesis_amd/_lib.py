@@ -17,6 +17,9 @@ LIB_PATH = os.environ.get("TNT_HIP_LIB") or os.path.join(_HERE, "csrc", "libtnt_
 P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
+# the tnt_version() this table was written against (csrc/rowops.hip); the two move together
+TNT_VERSION = 122
+
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
     "tnt_version": [],
@@ -71,6 +74,7 @@ SIGNATURES = {
     "tnt_softmax_cce_live_f32": [P, P, P, P, P, P, I32, I32, I32, F32, P, P, P],
     "tnt_softmax_cce_smooth_f32": [P, P, P, P, P, P, I32, I32, I32, F32, F32, P],
     "tnt_softmax_cce_unlikely_f32": [P, P, P, P, P, P, I32, I32, I32, I32, F32, F32, P],
+    "tnt_softmax_cce_weighted_f32": [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, I32, P],
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],
@@ -185,6 +189,8 @@ def load():
             raise KernelLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
         fn.restype = I32
+    if lib.tnt_version() < TNT_VERSION:
+        raise KernelLibraryError(f"{LIB_PATH} is tnt_version {lib.tnt_version()}, older than the {TNT_VERSION} this binding needs: rebuild it")
     _lib = lib
     return lib
 

@@ -1,9 +1,9 @@
 // How a 256-thread workgroup walks one logits row of a softmax head: loading the row, its maximum, the FIRST index holding
 // it (np.argmax / tf.argmax rule), the exp-sum, the four-wave block reductions, and the host-side ladder that picks the
-// row kind from V and the alignment.  Used by smooth.hip, unlikely.hip, scst.hip and score.hip, whose kernels exist once
-// as a template over the row kind and keep only their own write phase.  seqops.hip takes the ladder alone: the kernels of
-// tnt_softmax_cce_f32 / tnt_softmax_cce_live_f32 run on the benchmarked training step and keep their own text, so that a
-// change here can never move them.
+// row kind from V and the alignment.  Used by smooth.hip, unlikely.hip, weighted.hip, scst.hip and score.hip, whose kernels
+// exist once as a template over the row kind and keep only their own write phase.  seqops.hip takes the ladder alone: the
+// kernels of tnt_softmax_cce_f32 / tnt_softmax_cce_live_f32 run on the benchmarked training step and keep their own text,
+// so that a change here can never move them.
 #pragma once
 #include <type_traits>
 #include "tnt_common.h"

@@ -276,3 +276,55 @@ class PinnedPrefetcher:
         nxt = index + 1
         self._next = (nxt, self._submit(nxt, consumed)) if nxt < len(self.gen) else None
         return ((x, cap, a0, c0), tgt)
+
+
+TOKEN_WEIGHT_SCHEMES = ("inverse", "inverse_sqrt", "effective")
+
+
+def token_class_weights(captions, vocab_size, scheme="inverse_sqrt", beta=0.999, pad_weight=0.0, clip=None, mean_one=True):
+    """Class weights for ``CategoricalCrossentropy(class_weight=...)`` / ``fit(class_weight=...)`` from the integer caption
+    array of a corpus (any shape; id 0 is the padding): frequent words weigh less, so that "a", "of", "man" do not dominate
+    the words that carry a scan's content.  With n_v the number of occurrences of id v:
+      "inverse"       1 / n_v
+      "inverse_sqrt"  1 / sqrt(n_v)
+      "effective"     (1 - beta) / (1 - beta^n_v)     (Cui et al. 2019, class-balanced loss; 0 < beta < 1)
+    A class that never occurs gets the weight of n_v = 1.  ``mean_one``: the weights of the ids 1 .. V-1 are scaled so that
+    their mean over the corpus's non-padding tokens, sum_v n_v w_v / sum_v n_v, is 1 -- the loss scale, and so the learning
+    rate, stay comparable with the unweighted loss.  ``clip`` = (lo, hi): those weights are then clipped to [lo, hi] (in the
+    scaled units; the mean is not restored).  ``w[0] = pad_weight`` last.  float64 inside, float32 out, deterministic."""
+    V = int(vocab_size)
+    if V < 1:
+        raise ValueError(f"vocab_size must be >= 1, got {vocab_size!r}")
+    if scheme not in TOKEN_WEIGHT_SCHEMES:
+        raise ValueError(f"scheme must be one of {TOKEN_WEIGHT_SCHEMES}, got {scheme!r}")
+    ids = np.asarray(captions)
+    if ids.dtype.kind not in "iu":
+        raise ValueError(f"captions must be an integer array, got dtype {ids.dtype}")
+    ids = ids.reshape(-1).astype(np.int64)
+    if ids.size and (ids.min() < 0 or ids.max() >= V):
+        raise ValueError(f"captions hold ids outside [0, {V})")
+    pad = float(pad_weight)
+    if not 0.0 <= pad < float("inf"):
+        raise ValueError(f"pad_weight must be finite and >= 0, got {pad_weight!r}")
+    count = np.bincount(ids, minlength=V).astype(np.float64)
+    n = np.maximum(count, 1.0)
+    if scheme == "inverse":
+        w = 1.0 / n
+    elif scheme == "inverse_sqrt":
+        w = 1.0 / np.sqrt(n)
+    else:
+        b = float(beta)
+        if not 0.0 < b < 1.0:
+            raise ValueError(f"beta must be in (0, 1), got {beta!r}")
+        w = (1.0 - b) / -np.expm1(n * np.log(b))
+    if mean_one:
+        tokens = count[1:].sum()
+        if tokens > 0:
+            w = w * (tokens / (count[1:] * w[1:]).sum())
+    if clip is not None:
+        lo, hi = (float(c) for c in clip)
+        if not 0.0 <= lo <= hi < float("inf"):
+            raise ValueError(f"clip must be (lo, hi) with 0 <= lo <= hi, both finite, got {clip!r}")
+        w = np.clip(w, lo, hi)
+    w[0] = pad
+    return w.astype(np.float32)

@@ -434,6 +434,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.__dict__.get("average") is not None:
         # compile(optimizers.MovingAverage / SWA): the averaging launch has no place in the data-parallel schedules
         raise NotImplementedError(model.AVERAGE_DP_REFUSAL)
+    if model.__dict__.get("loss_normalise", "count") == "weights":
+        # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
+        raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.__dict__.get("agc") and world > 1:

@@ -701,6 +701,8 @@ class NIC(ModelBase):
                                   1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
         elif self.unlikelihood > 0:
             self._loss_unlikely(B, T, want_grad)
+        elif self._token_weights_on():
+            self._loss_weighted(B, T, want_grad)
         elif want_grad:
             be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V, self.ldV,
                            1.0 / (n * self.dp_world))

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .optimizers import Adam, loss_label_smoothing, loss_unlikelihood, optimizer_average, optimizer_schedule
+from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_focal_gamma, loss_label_smoothing, loss_normalise,
+                         loss_unlikelihood, optimizer_average, optimizer_schedule)
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -811,6 +812,7 @@ class ModelBase:
     SUPPORTS_LABEL_SMOOTHING = True     # False where the step does not go through the compile loss (ThinkAndTell generators)
     SUPPORTS_UNLIKELIHOOD = True        # False where the loss is not the (t, b)-ordered caption head (those, and NICfc)
     UNLIKELIHOOD_MAX_T = 64             # loss positions per caption: one wave holds a caption's prefix
+    SUPPORTS_TOKEN_WEIGHTS = True       # class_weight / focal_gamma / normalise: as SUPPORTS_UNLIKELIHOOD
     # subclasses fill: self.layers_spec = OrderedDict(layer -> [weight names]),
     # self.keras_shapes = {full name: keras shape}
     def __init__(self, device=None, seed=42, use_graph=True, grad_sync=None):
@@ -824,6 +826,10 @@ class ModelBase:
         self.loss = None
         self.label_smoothing = 0.0          # of the compile loss (CategoricalCrossentropy(label_smoothing=...))
         self.unlikelihood = 0.0             # of the compile loss (CategoricalCrossentropy(unlikelihood=...))
+        self.focal_gamma = 0.0              # of the compile loss (CategoricalCrossentropy(focal_gamma=...))
+        self.loss_normalise = "count"       # of the compile loss (CategoricalCrossentropy(normalise=...))
+        self.class_weight = None            # host copy of the token weights (compile loss / set_class_weight / fit), or None
+        self.cw_dev = None                  # the same V floats on the device: an argument of the weighted head launch
         self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
         self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
         self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
@@ -852,6 +858,9 @@ class ModelBase:
         if alpha > 0 and getattr(self, "self_critical", None) is not None:
             raise ValueError("unlikelihood > 0 does not apply to a self_critical model: its loss is the "
                              "advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        gamma, mode = loss_focal_gamma(loss), loss_normalise(loss)
+        cw = loss_class_weight(loss, getattr(self, "V", None))
+        self._check_token_weights(cw is not None, gamma, mode, eps, alpha)
         avg = optimizer_average(optimizer)
         if avg is not None and self.grad_sync is not None:
             raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
@@ -862,6 +871,11 @@ class ModelBase:
             self._graphs = {}
         self.label_smoothing = eps
         self.unlikelihood = alpha
+        # so are gamma, the mode and whether there are weights; the weights themselves are the contents of a device buffer
+        if gamma != self.__dict__.get("focal_gamma", 0.0) or mode != self.__dict__.get("loss_normalise", "count"):
+            self._graphs = {}
+        self.focal_gamma, self.loss_normalise = gamma, mode
+        self._store_class_weight(cw)
         # the averaging launch sits inside the same plans / graphs, and its settings are launch arguments
         if avg != self.__dict__.get("average"):
             self._graphs = {}
@@ -873,6 +887,69 @@ class ModelBase:
         self.lr_schedule = sched
         if self.built:
             self._init_optimizer_state()
+
+    def _check_token_weights(self, has_weights, gamma, mode, eps, alpha):
+        """the refusals of class_weight / focal_gamma / normalise="weights" (compile, set_class_weight, dp.attach); neutral
+        settings pass everywhere"""
+        if not (has_weights or gamma > 0 or mode == "weights"):
+            return
+        what = "class_weight / focal_gamma / normalise=\"weights\""
+        if not self.SUPPORTS_TOKEN_WEIGHTS:
+            raise NotImplementedError(f"{type(self).__name__} does not compute its loss with the caption head over "
+                                      f"(position, caption) rows: {what} is not implemented for it")
+        if eps > 0 or alpha > 0:
+            raise ValueError(f"{what} together with label_smoothing > 0 or unlikelihood > 0 is not implemented: one head "
+                             "kernel computes one of them")
+        if getattr(self, "self_critical", None) is not None:
+            raise ValueError(f"{what} does not apply to a self_critical model: its loss is the advantage-weighted "
+                             "tnt_scst_cce_f32, not the compile loss")
+        if mode == "weights" and (self.grad_sync is not None or int(self.__dict__.get("dp_world", 1) or 1) > 1):
+            raise NotImplementedError(self.WEIGHTS_DP_REFUSAL)
+        if mode == "weights" and int(getattr(self, "S", 1)) > 1:
+            raise NotImplementedError("normalise=\"weights\" with n_subjects > 1 is not implemented: the per-subject metrics "
+                                      "divide each subject's sums by its position count Bs * T, not by its weight sum.  "
+                                      "normalise=\"count\" works")
+
+    WEIGHTS_DP_REFUSAL = ("normalise=\"weights\" is not implemented under data parallel: the weight sum the loss is divided by is "
+                          "formed per rank inside the head launch, so the ranks' gradients would carry different "
+                          "denominators.  normalise=\"count\" works")
+
+    def _token_weights_on(self):
+        """whether the head launch is tnt_softmax_cce_weighted_f32 (any non-neutral setting)"""
+        return self.class_weight is not None or self.focal_gamma > 0 or self.loss_normalise == "weights"
+
+    def _store_class_weight(self, cw):
+        """cw: None or a float32 array of V weights.  The device buffer is written in place where it exists, so a recorded
+        plan or a captured graph that holds its address reads the new weights; only a change between no weights and
+        weights changes the launch and drops the recordings."""
+        if (cw is None) != (self.__dict__.get("class_weight") is None):
+            self._graphs = {}
+        if cw is None:
+            self.class_weight, self.cw_dev = None, None
+            return
+        host = torch.from_numpy(np.ascontiguousarray(cw, dtype=np.float32))
+        if self.__dict__.get("cw_dev") is None:
+            self.cw_dev = host.to(self.device)
+        else:
+            self.cw_dev.copy_(host)
+        self.class_weight = np.array(cw, dtype=np.float32)
+
+    def set_class_weight(self, class_weight):
+        """Replace the token weights of a compiled model: an array-like of V weights, an ``{id: weight}`` dict (missing ids
+        weigh 1) or None.  The next step, a replay of a recorded plan or graph included, uses them."""
+        self._check_token_weights(class_weight is not None, self.focal_gamma, self.loss_normalise, self.label_smoothing,
+                                  self.unlikelihood)
+        self._store_class_weight(None if class_weight is None else check_class_weight(class_weight, self.V))
+
+    def _loss_weighted(self, B, T, want_grad):
+        """the head launch of _loss_metrics under token weights / the focal factor / normalise="weights", training form
+        (dlogits in place) or evaluation form (probabilities in place, gscale 0): the same objective in both, as under
+        label smoothing"""
+        n = T * B
+        self.be.softmax_cce_weighted(self.logits, self.tgt, self.cw_dev, None if want_grad else self.logits, self.loss_row,
+                                     self.corr_row, self.logits if want_grad else None, n, self.V, self.ldV,
+                                     1.0 / (n * self.dp_world) if want_grad else 0.0, self.focal_gamma,
+                                     self.loss_normalise == "weights")
 
     def _loss_unlikely(self, B, T, want_grad):
         """the head launch of _loss_metrics under unlikelihood > 0, training form (dlogits in place) or evaluation form
@@ -2209,7 +2286,8 @@ class ModelBase:
 
     # ------------------------------------------------------------------ fit loop
     def fit(self, x=None, epochs=1, steps_per_epoch=None, batch_size=None, callbacks=None, validation_data=None,
-            validation_steps=None, initial_epoch=0, verbose=1, keras_last_batch_logs=False, validation_averaged=False, **kw):
+            validation_steps=None, initial_epoch=0, verbose=1, keras_last_batch_logs=False, validation_averaged=False,
+            class_weight=None, **kw):
         """model.fit(generator, epochs, steps_per_epoch, batch_size, callbacks, validation_data,
         validation_steps, initial_epoch) -- main.py:269-281.  Honours the keras callback protocol
         (on_train_begin, on_epoch_begin, on_train_batch_end, on_test_batch_end, on_epoch_end,
@@ -2222,7 +2300,11 @@ class ModelBase:
         Data parallel: the epoch logs are averaged over the ranks and ``stop_training`` is OR-ed before the
         callbacks' decision takes effect, so every rank leaves the loop in the same epoch.
         ``validation_averaged=True`` (optimizers.MovingAverage / SWA): the validation pass of every epoch runs inside
-        ``averaged_weights()``, so the ``val_*`` logs are the averaged model's."""
+        ``averaged_weights()``, so the ``val_*`` logs are the averaged model's.
+        ``class_weight`` (keras: an ``{id: weight}`` dict; an array of V weights is accepted too): ``set_class_weight`` before
+        the first step; None leaves the model's weights as they are."""
+        if class_weight is not None:
+            self.set_class_weight(class_weight)
         if validation_averaged and self.__dict__.get("average") is None:
             raise ValueError("fit(validation_averaged=True) needs a model compiled with an averaging optimizer "
                              "(optimizers.MovingAverage / SWA)")

@@ -219,7 +219,8 @@ class NIC(ModelBase):
         of Out, logits, loss and dlogits; the loss is not masked, so they count -- once, weighted by their multiplicity.
         Taken by train_step where the step is the persistent chains + the gemm3 products of one process and nothing else
         writes or reads the head's buffers by position: no scheduled sampling, self-critical step, AGC, label smoothing,
-        unlikelihood (its candidates are a row's earlier positions, which the compacted rows have lost), data parallel.
+        unlikelihood (its candidates are a row's earlier positions, which the compacted rows have lost), token weights /
+        focal loss / normalise="weights" (the weighted head has no row-multiplicity form), data parallel.
         Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the position-ordered
         buffers."""
         be = self.be
@@ -228,7 +229,7 @@ class NIC(ModelBase):
               and getattr(self, "use_gemm3", True) and getattr(self, "g3_riders", True)
               and self.grad_sync is None and int(self.__dict__.get("dp_world", 1) or 1) == 1
               and self.scheduled_sampling is None and self.self_critical is None and not self.__dict__.get("agc")
-              and not self.label_smoothing and not self.unlikelihood and self.U % 4 == 0)
+              and not self.label_smoothing and not self.unlikelihood and not self._token_weights_on() and self.U % 4 == 0)
         if not ok:
             return None
         return (self.head_pos, self.head_w, self.head_tgt, self.head_live, self.loss_row, self.corr_row)
@@ -410,6 +411,8 @@ class NIC(ModelBase):
                                   1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
         elif self.unlikelihood > 0:
             self._loss_unlikely(B, T, want_grad)
+        elif self._token_weights_on():
+            self._loss_weighted(B, T, want_grad)
         elif want_grad:
             be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
                            self.ldV, 1.0 / (n * self.dp_world))

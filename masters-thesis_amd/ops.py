@@ -328,6 +328,15 @@ class HipBackend:
         self._call(self.lib.tnt_softmax_cce_smooth_f32, "tnt_softmax_cce_smooth_f32", _p(logits), _p(target), _p(probs), _p(loss_row),
                    _p(correct_row), _p(dlogits), rows, V, ld, gscale, float(label_smoothing), self._s())
 
+    def softmax_cce_weighted(self, logits, target, class_weight, probs, loss_row, correct_row, dlogits, rows, V, ld, gscale,
+                             gamma=0.0, normalise=False):
+        """the head with per-class token weights (class_weight: V floats on the device, or None), the focal factor
+        (1 - p_y)^gamma and, with normalise, the division by the weight sum, in the same single launch
+        (tnt_softmax_cce_weighted_f32; definition in include/tnt_hip.h)"""
+        self._call(self.lib.tnt_softmax_cce_weighted_f32, "tnt_softmax_cce_weighted_f32", _p(logits), _p(target), _p(class_weight),
+                   _p(probs), _p(loss_row), _p(correct_row), _p(dlogits), rows, V, ld, gscale, float(gamma), int(normalise),
+                   self._s())
+
     def softmax_cce_unlikely(self, logits, target, probs, loss_row, correct_row, dlogits, B, T, V, ld, gscale, alpha):
         """the head with token-level unlikelihood over each caption's own prefix in the same single launch: rows = T * B,
         t-major (tnt_softmax_cce_unlikely_f32; definition in include/tnt_hip.h)"""

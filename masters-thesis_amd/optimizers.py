@@ -188,14 +188,57 @@ class CategoricalCrossentropy:
     loss = ce - alpha * sum_{c in prefix} log(1 - p_c), from one tnt_softmax_cce_unlikely_f32 launch in place of
     tnt_softmax_cce_f32 (definition in include/tnt_hip.h).  The ``loss`` metric of train_step and test_step is then the
     mean of ce + alpha * ul, with no metric key of its own; the plain likelihood of a caption is what
-    ``evaluate.caption_perplexity`` reports.  Not together with ``label_smoothing``."""
+    ``evaluate.caption_perplexity`` reports.  Not together with ``label_smoothing``.
 
-    def __init__(self, from_logits=False, reduction="none", label_smoothing=0.0, unlikelihood=0.0):
+    ``class_weight`` (keras ``fit(class_weight=...)``: an array-like of one weight per class, or an ``{id: weight}`` dict in
+    which a missing id weighs 1), ``focal_gamma`` (keras CategoricalFocalCrossentropy's gamma) and ``normalise``: position
+    r with target y contributes w_y (1 - p_y)^gamma ce, and the ``loss`` metric is the sum of that over the positions
+    divided by their count (``normalise="count"``, keras's rule) or by the sum of their weights (``"weights"``: with
+    ``class_weight={0: 0}`` the mean over the non-padding tokens, and ``accuracy`` the accuracy over them).  One
+    tnt_softmax_cce_weighted_f32 launch in place of tnt_softmax_cce_f32 (definition in include/tnt_hip.h), in training
+    and evaluation.  Not together with ``label_smoothing`` or ``unlikelihood``; ``model.set_class_weight`` replaces the
+    weights of a compiled model."""
+
+    def __init__(self, from_logits=False, reduction="none", label_smoothing=0.0, unlikelihood=0.0, class_weight=None,
+                 focal_gamma=0.0, normalise="count"):
         if from_logits:
             raise NotImplementedError("the reference path uses from_logits=False")
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.unlikelihood = check_unlikelihood(unlikelihood)
+        self.class_weight = class_weight if class_weight is None else check_class_weight(class_weight)
+        self.focal_gamma = check_focal_gamma(focal_gamma)
+        self.normalise = check_normalise(normalise)
         self.from_logits, self.reduction = from_logits, reduction
+
+
+class CategoricalFocalCrossentropy(CategoricalCrossentropy):
+    """tf.keras.losses.CategoricalFocalCrossentropy(alpha=0.25, gamma=2.0, from_logits=False): every class weighs ``alpha``
+    and the focal exponent is ``gamma``, i.e. CategoricalCrossentropy(class_weight=<alpha everywhere>, focal_gamma=gamma).
+    The uniform weight is expanded to the model's vocabulary by ``ModelBase.compile``."""
+
+    def __init__(self, alpha=0.25, gamma=2.0, from_logits=False, reduction="none", normalise="count"):
+        super().__init__(from_logits=from_logits, reduction=reduction, focal_gamma=gamma, normalise=normalise)
+        try:
+            a = float(alpha)
+        except (TypeError, ValueError):
+            raise ValueError(f"alpha must be a finite number >= 0, got {alpha!r}") from None
+        if not 0.0 <= a < float("inf"):
+            raise ValueError(f"alpha must be finite and >= 0, got {alpha!r}")
+        self.alpha, self.gamma = a, self.focal_gamma
+        self.class_weight = UniformClassWeight(a)
+
+
+class UniformClassWeight:
+    """the same weight for every class of a vocabulary whose size the loss object does not know"""
+
+    def __init__(self, value):
+        self.value = float(value)
+
+    def __eq__(self, other):
+        return isinstance(other, UniformClassWeight) and other.value == self.value
+
+    def __hash__(self):
+        return hash(("UniformClassWeight", self.value))
 
 
 def check_label_smoothing(eps):
@@ -228,3 +271,82 @@ def check_unlikelihood(alpha):
 def loss_unlikelihood(loss):
     """unlikelihood of a compile() loss argument: None, or an object without the attribute, means 0"""
     return check_unlikelihood(getattr(loss, "unlikelihood", 0.0) if loss is not None else 0.0)
+
+
+def check_class_weight(w, vocab_size=None):
+    """class weights as keras's fit(class_weight=) takes them, checked: an ``{id: weight}`` dict (returned as a dict with int
+    keys and float values) or an array-like of one weight per class (returned as a float32 array); with ``vocab_size``
+    either form becomes the float32 array of that length, ids a dict does not name weighing 1.  ValueError unless every
+    weight is finite and >= 0 (NaN included), every id an integer in [0, vocab_size), and an array's length vocab_size."""
+    import numbers
+    import numpy as np
+    if isinstance(w, UniformClassWeight):
+        return w if vocab_size is None else np.full(int(vocab_size), w.value, np.float32)
+    if isinstance(w, dict):
+        out = {}
+        for k, v in w.items():
+            if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 0:
+                raise ValueError(f"class_weight ids must be integers >= 0, got {k!r}")
+            if vocab_size is not None and k >= vocab_size:
+                raise ValueError(f"class_weight names id {k!r}, outside the vocabulary of {vocab_size} classes")
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"class_weight[{k!r}] must be a finite number >= 0, got {v!r}") from None
+            if not 0.0 <= f < float("inf"):
+                raise ValueError(f"class_weight[{k!r}] must be finite and >= 0, got {v!r}")
+            out[int(k)] = f
+        if vocab_size is None:
+            return out
+        arr = np.ones(int(vocab_size), np.float32)
+        for k, f in out.items():
+            arr[k] = f
+        return arr
+    try:
+        arr = np.asarray(w, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"class_weight must be an array-like of weights or an {{id: weight}} dict, got {w!r}") from None
+    if arr.ndim != 1 or arr.size == 0:
+        raise ValueError(f"class_weight must hold one weight per class, got an array of shape {arr.shape}")
+    if not (np.isfinite(arr).all() and (arr >= 0).all()):
+        raise ValueError("every class weight must be finite and >= 0")
+    if vocab_size is not None and arr.size != vocab_size:
+        raise ValueError(f"class_weight holds {arr.size} weights for a vocabulary of {vocab_size} classes")
+    return arr.astype(np.float32)
+
+
+def loss_class_weight(loss, vocab_size=None):
+    """class_weight of a compile() loss argument: None, or an object without the attribute, means none"""
+    w = getattr(loss, "class_weight", None) if loss is not None else None
+    return None if w is None else check_class_weight(w, vocab_size)
+
+
+def check_focal_gamma(gamma):
+    """the value as a float; ValueError unless it is finite and >= 0 (NaN included)"""
+    try:
+        v = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"focal_gamma must be a finite number >= 0, got {gamma!r}") from None
+    if isinstance(gamma, bool) or not 0.0 <= v < float("inf"):
+        raise ValueError(f"focal_gamma must be finite and >= 0, got {gamma!r}")
+    return v
+
+
+def loss_focal_gamma(loss):
+    """focal_gamma of a compile() loss argument: None, or an object without the attribute, means 0"""
+    return check_focal_gamma(getattr(loss, "focal_gamma", 0.0) if loss is not None else 0.0)
+
+
+NORMALISE_MODES = ("count", "weights")
+
+
+def check_normalise(mode):
+    """``"count"`` or ``"weights"``; ValueError otherwise"""
+    if not isinstance(mode, str) or mode not in NORMALISE_MODES:
+        raise ValueError(f'normalise must be "count" or "weights", got {mode!r}')
+    return mode
+
+
+def loss_normalise(loss):
+    """normalise of a compile() loss argument: None, or an object without the attribute, means ``"count"``"""
+    return check_normalise(getattr(loss, "normalise", "count") if loss is not None else "count")

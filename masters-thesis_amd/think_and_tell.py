@@ -45,6 +45,7 @@ class Decoder:
 class CaptionGenerator(ModelBase):
     SUPPORTS_LABEL_SMOOTHING = False    # loss_function is the masked sparse from-logits form, not the compile loss
     SUPPORTS_UNLIKELIHOOD = False
+    SUPPORTS_TOKEN_WEIGHTS = False
 
     def __init__(self, encoder, decoder, tokenizer=None, max_length=15, **kw):
         super().__init__(**kw)
