@@ -1222,6 +1222,20 @@ int32_t tnt_attention_step_bwd_f32(const float* dctx_d, const float* F, const fl
                                    const uint32_t* step_dev, const float* dz, const float* Wc,
                                    const float* dctx_part, int32_t nparts, const uint8_t* keep4,
                                    float alpha_mse_coef, int32_t fresh, void* stream);
+/* the same launch with an external gradient of the attention weights as a rider: ext != NULL adds ext[b * ext_bs + r]
+ * (ext_bs >= 0, in floats) to dalpha[b][r] next to the alpha_mse term, before the softmax backward.  The caller passes
+ * the slab of this step.  ext == NULL is tnt_attention_step_bwd_f32, bit for bit (that entry forwards here). */
+int32_t tnt_attention_step_bwd_ext_f32(const float* dctx_d, const float* F, const float* P,
+                                       const float* W2, const float* v, const float* qpre,
+                                       const float* alpha, float* dP, float* dF, float* dvb,
+                                       float* dqpre, float* dh, int32_t B, int32_t R, int32_t D,
+                                       int32_t A, int32_t U, float slope, float rate_attn,
+                                       float rate_in, int32_t in_lwidth, uint64_t seed,
+                                       uint32_t site_attn, uint32_t site_in, uint32_t step,
+                                       const uint32_t* step_dev, const float* dz, const float* Wc,
+                                       const float* dctx_part, int32_t nparts, const uint8_t* keep4,
+                                       float alpha_mse_coef, int32_t fresh, const float* ext, int32_t ext_bs,
+                                       void* stream);
 
 /* ---- the forward chain of the attention captioner as ONE persistent launch (lc_NIC.py:244-256): for i < T:
  * tnt_attention_step_fwd_f32(h = hs[i], ..., qpre[i], alpha[i], ctx[i], ctx_d[i], keep4 + i * keep_stride, sites + i) then
@@ -1278,6 +1292,20 @@ int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const float* W2,
                                 float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
                                 uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
                                 uint32_t site_out0, uint32_t* sync, float* guard_out, void* stream);
+/* the _drop launch (rate_out = 0: the plain one) with an external gradient of the attention weights as a rider: step i adds
+ * ext[i * ext_ts + b * ext_bs + r] to dalpha[b][r] next to the alpha_mse term (element strides >= 0; the last element read,
+ * (T-1) ext_ts + (B-1) ext_bs + R - 1, must lie below 2^29).  tnt_attention_coverage_f32 writes ext with strides (0, R) for
+ * axis 0 and (R, 0) for axis 1; a full [T][B][R] gradient has (B R, R).  ext == NULL: the two entries above, bit for bit
+ * (they forward here). */
+int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+                               const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
+                               float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
+                               const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
+                               int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
+                               float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
+                               uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
+                               uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, uint32_t* sync,
+                               float* guard_out, void* stream);
 
 /* ---- the attention layer's hoisted first Dense (P = LeakyReLU(F W1 + b1), attention.py:32) backward, behind the chain:
  * with dP [rows][A] the score gradient accumulated over the T steps and Ppre its pre-activation:
@@ -1305,6 +1333,22 @@ int32_t tnt_attention_metric_parts(int32_t T, int32_t R);
 int32_t tnt_attention_metric_f32(const float* alpha, float* out, float* work,
                                  int32_t T, int32_t B, int32_t R,
                                  int64_t tstride /* floats between timesteps; 0 = B*R */, void* stream);
+
+/* ---- attention coverage penalty ("doubly stochastic attention", Xu et al. 2015, section 4.2.1).  alpha [T][B][R] are the
+ * attention weights of all steps (tstride floats between steps; <= 0 = B R).
+ *   axis 0 ("time", Xu et al.):  s[b][r] = sum_t alpha[t][b][r],  N = B R
+ *   axis 1 ("batch", the line of lc_NIC.py:365-367, whose axis=1 of the stacked (T, B, R, 1) scores is the batch axis):
+ *                                s[t][r] = sum_b alpha[t][b][r],  N = T R; its value is tnt_attention_metric_f32's
+ *   coverage = (1 / N) sum (1 - s)^2            (keras MeanSquaredError of s against ones)
+ * The term a training step adds to its loss is weight * coverage, so
+ *   d / d alpha[t][b][r] = (2 weight / N) (s - 1),  s the sum that holds the element.
+ * The launch writes ext[b R + r] (axis 0) or ext[t R + r] (axis 1) = coef * (s - 1) -- the caller passes coef = 2 weight / N
+ * and hands ext to tnt_lc_seq_bwd_ext_f32 / tnt_attention_step_bwd_ext_f32 with strides (ext_ts, ext_bs) = (0, R) or (R, 0)
+ * -- and out[0] = coverage, unweighted.  ext == NULL: the value only (evaluation); out == NULL: ext only (one launch).
+ * Every sum is taken in ascending index order in float32 and the partial sums of (1 - s)^2 meet in a fixed order: no
+ * atomics, the same bits every time.  work: rows * ceil(R / 256) floats with rows = B for axis 0 and T for axis 1. */
+int32_t tnt_attention_coverage_f32(const float* alpha, int64_t tstride, int32_t T, int32_t B, int32_t R, int32_t axis,
+                                   float coef, float* ext, float* out, float* work, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ the way main.py:113-134 does."""
 import yaml
 
 from . import schedules
+from .model_base import AttentionCoverage
 from .optimizers import Adam, SGD, CategoricalCrossentropy
 
 
@@ -38,6 +39,12 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
                       config["output_reg"], seed=config.get("seed", 42), **kw)
     elif mode == "attention":
         from .lc_nic import NIC
+        # attention_coverage: {weight: , axis: }: an optional key of this library's (model_base.AttentionCoverage)
+        cov = config.get("attention_coverage")
+        if cov is not None and "attention_coverage" not in kw:
+            if not isinstance(cov, dict) or not set(cov) <= {"weight", "axis"} or "weight" not in cov:
+                raise ValueError(f"attention_coverage must be a mapping with weight and optionally axis, got {cov!r}")
+            kw["attention_coverage"] = AttentionCoverage(cov["weight"], cov.get("axis", "time"))
         model = NIC(groups, config["units"], config["embedding_features"], config["embedding_text"],
                     config["attn_units"], vocab_size, config["max_length"], config["dropout_input"],
                     config["dropout_features"], config["dropout_text"], config["dropout_attn"], config["dropout_lstm"],

@@ -55,6 +55,10 @@ struct AttArgs {
   // backward only: dalpha[r] += alpha_mse * (alpha[r] - 1) -- the gradient of c * sum (1 - alpha)^2 with alpha_mse = 2c
   // (lc_NIC.train_step_sam adds MSE(ones, attention_scores) to the loss of its first pass, lc_NIC.py:751-752,766)
   float alpha_mse;
+  // backward only, nullable: a gradient that reaches the attention weights from outside the chain (the coverage penalty,
+  // tnt_attention_coverage_f32): dalpha[r] += ext[i * ext_ts + b * ext_bs + r] in step i of a chain (element strides); the
+  // per-step kernels are handed the step's slab, so they add ext[b * ext_bs + r].  NULL: nothing is read or added.
+  const float* ext; int ext_ts, ext_bs;
   // backward only: 1 = the accumulators dP / dF / dvb are written, not added to (the first executed step of a chain: saves
   // the caller a zero fill of the three buffers)
   int fresh;
@@ -225,7 +229,11 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(AttArgs g) {
         g.dF[e] = dfv[u] + als[r] * dcs[d];
       }
       t = group_sum<AP>(t);
-      if (d == 0 && r < g.R) das[r] = t + g.alpha_mse * (als[r] - 1.f);
+      if (d == 0 && r < g.R) {
+        float da = t + g.alpha_mse * (als[r] - 1.f);
+        if (g.ext) da += g.ext[(long)b * g.ext_bs + r];
+        das[r] = da;
+      }
     }
   }
   __syncthreads();
@@ -615,7 +623,11 @@ __global__ __launch_bounds__(WT) void attention_bwd_wide_kernel(AttArgs g) {
                                                            dfv[p].z + al * dc4.z, dfv[p].w + al * dc4.w);
       }
       t = adj_sum<G4>(t);
-      if (c4 == 0 && r < R) das[r] = t + g.alpha_mse * (als[r] - 1.f);
+      if (c4 == 0 && r < R) {
+        float da = t + g.alpha_mse * (als[r] - 1.f);
+        if (g.ext) da += g.ext[(long)b * g.ext_bs + r];
+        das[r] = da;
+      }
     }
     __syncthreads();
   }
@@ -739,20 +751,23 @@ extern "C" int32_t tnt_attention_step_fwd_f32(const float* h, const float* F, co
   return 0;
 }
 
-extern "C" int32_t tnt_attention_step_bwd_f32(const float* dctx_d, const float* F, const float* P, const float* W2,
-                                              const float* v, const float* qpre, const float* alpha, float* dP, float* dF,
-                                              float* dvb, float* dqpre, float* dh, int32_t B, int32_t R, int32_t D,
-                                              int32_t A, int32_t U, float slope, float rate_attn, float rate_in,
-                                              int32_t in_lwidth, uint64_t seed, uint32_t site_attn, uint32_t site_in,
-                                              uint32_t step, const uint32_t* step_dev, const float* dz, const float* Wc,
-                                              const float* dctx_part, int32_t nparts, const uint8_t* keep4,
-                                              float alpha_mse_coef, int32_t fresh, void* stream) {
+extern "C" int32_t tnt_attention_step_bwd_ext_f32(const float* dctx_d, const float* F, const float* P, const float* W2,
+                                                  const float* v, const float* qpre, const float* alpha, float* dP, float* dF,
+                                                  float* dvb, float* dqpre, float* dh, int32_t B, int32_t R, int32_t D,
+                                                  int32_t A, int32_t U, float slope, float rate_attn, float rate_in,
+                                                  int32_t in_lwidth, uint64_t seed, uint32_t site_attn, uint32_t site_in,
+                                                  uint32_t step, const uint32_t* step_dev, const float* dz, const float* Wc,
+                                                  const float* dctx_part, int32_t nparts, const uint8_t* keep4,
+                                                  float alpha_mse_coef, int32_t fresh, const float* ext, int32_t ext_bs,
+                                                  void* stream) {
   if (int32_t rc = check_dims(B, R, D, A, U)) return rc;
+  if (ext != nullptr && ext_bs < 0) return TNT_BADARG(35);
   if (dz != nullptr && (U % 16 != 0 || Wc == nullptr)) return TNT_BADARG(27);
   if (dz == nullptr && dctx_d == nullptr && dctx_part == nullptr) return TNT_BADARG(1);
   if (dctx_part != nullptr && (nparts <= 0 || nparts * D > 1024)) return TNT_BADARG(30);
   AttArgs g{};
   g.dz = dz; g.Wc = Wc; g.dctx_part = dctx_part; g.nparts = nparts; g.keep4 = keep4; g.alpha_mse = alpha_mse_coef; g.fresh = fresh != 0;
+  g.ext = ext; g.ext_ts = 0; g.ext_bs = ext != nullptr ? ext_bs : 0;
   g.dctx_d = dctx_d; g.F = F; g.P = P; g.W2 = W2; g.v = v; g.qpre_in = qpre; g.alpha_in = alpha; g.dP = dP; g.dF = dF;
   g.dvb = dvb; g.dqpre = dqpre; g.dh = dh; g.B = B; g.R = R; g.D = D; g.A = A; g.U = U; g.in_lwidth = in_lwidth;
   g.slope = slope; g.rate_attn = rate_attn; g.rate_in = rate_in; g.seed = seed; g.site_attn = site_attn;
@@ -771,6 +786,19 @@ extern "C" int32_t tnt_attention_step_bwd_f32(const float* dctx_d, const float* 
   return 0;
 }
 
+extern "C" int32_t tnt_attention_step_bwd_f32(const float* dctx_d, const float* F, const float* P, const float* W2,
+                                              const float* v, const float* qpre, const float* alpha, float* dP, float* dF,
+                                              float* dvb, float* dqpre, float* dh, int32_t B, int32_t R, int32_t D,
+                                              int32_t A, int32_t U, float slope, float rate_attn, float rate_in,
+                                              int32_t in_lwidth, uint64_t seed, uint32_t site_attn, uint32_t site_in,
+                                              uint32_t step, const uint32_t* step_dev, const float* dz, const float* Wc,
+                                              const float* dctx_part, int32_t nparts, const uint8_t* keep4,
+                                              float alpha_mse_coef, int32_t fresh, void* stream) {
+  return tnt_attention_step_bwd_ext_f32(dctx_d, F, P, W2, v, qpre, alpha, dP, dF, dvb, dqpre, dh, B, R, D, A, U, slope, rate_attn,
+                                        rate_in, in_lwidth, seed, site_attn, site_in, step, step_dev, dz, Wc, dctx_part, nparts,
+                                        keep4, alpha_mse_coef, fresh, nullptr, 0, stream);
+}
+
 extern "C" int32_t tnt_attention_metric_parts(int32_t T, int32_t R) { return T * ((R + 63) / 64); }
 
 extern "C" int32_t tnt_attention_metric_f32(const float* alpha, float* out, float* work, int32_t T, int32_t B,
@@ -784,6 +812,60 @@ extern "C" int32_t tnt_attention_metric_f32(const float* alpha, float* out, floa
   if (out == nullptr) return 0;           // the caller totals work[0 .. T * nc) * 1 / (T R) (tnt_step_finalize_f32's x2 job)
   hipLaunchKernelGGL(attention_metric_final_kernel, dim3(1), dim3(64), 0, tnt_stream(stream), work, out, T * nc,
                      1.f / ((float)T * (float)R));
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The coverage ("doubly stochastic attention") penalty of Xu et al. 2015, section 4.2.1 (definition: include/tnt_hip.h).
+// A row is one sample (axis 0: the sum runs over the T steps) or one step (axis 1: over the B samples, the reference's own
+// line, lc_NIC.py:365-367); workgroup (row, c) holds 256 regions of it, one per thread, so every load of a summand is
+// coalesced over r.  A thread adds its n summands in ascending order, 8 loads in flight; it writes coef * (s - 1) to ext
+// and the workgroup leaves sum (s - 1)^2 of its regions in partial[row * nc + c] (waves in order).  No atomics.
+namespace {
+__global__ __launch_bounds__(256) void attention_coverage_kernel(const float* alpha, float* ext, float* partial, int n,
+                                                                 long sstride, long rstride, int R, float coef) {
+  __shared__ float sw[4];
+  const int row = blockIdx.x, c = blockIdx.y, r = c * 256 + (int)threadIdx.x;
+  float acc = 0.f;
+  if (r < R) {
+    const float* p = alpha + (long)row * rstride + r;
+    float s = 0.f;
+    int k = 0;
+    for (; k + 8 <= n; k += 8) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = p[(long)(k + u) * sstride];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += x[u];
+    }
+    for (; k < n; ++k) s += p[(long)k * sstride];
+    const float d = s - 1.f;
+    if (ext) ext[(long)row * R + r] = coef * d;
+    acc = d * d;
+  }
+  acc = tnt_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[row * gridDim.y + c] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+}
+}  // namespace
+
+extern "C" int32_t tnt_attention_coverage_f32(const float* alpha, int64_t tstride, int32_t T, int32_t B, int32_t R,
+                                              int32_t axis, float coef, float* ext, float* out, float* work, void* stream) {
+  if (alpha == nullptr) return TNT_BADARG(1);
+  if (T <= 0 || B <= 0 || R <= 0) return TNT_BADARG(3);
+  if (tstride <= 0) tstride = (int64_t)B * R;
+  if (tstride < (int64_t)B * R) return TNT_BADARG(2);
+  if (axis != 0 && axis != 1) return TNT_BADARG(6);
+  if (work == nullptr) return TNT_BADARG(10);
+  const int rows = axis == 0 ? B : T, n = axis == 0 ? T : B, nc = (R + 255) / 256;
+  hipLaunchKernelGGL(attention_coverage_kernel, dim3(rows, nc), dim3(256), 0, tnt_stream(stream), alpha, ext, work, n,
+                     axis == 0 ? (long)tstride : (long)R, axis == 0 ? (long)R : (long)tstride, R, coef);
+  TNT_LAUNCH_CHECK();
+  if (out == nullptr) return 0;
+  hipLaunchKernelGGL(attention_metric_final_kernel, dim3(1), dim3(64), 0, tnt_stream(stream), work, out, rows * nc,
+                     1.f / ((float)rows * (float)R));
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -1857,6 +1939,11 @@ __global__ __launch_bounds__(1024) void lc_seq_bwd_kernel(LcSeqBwdArgs a) {
     const __amdgpu_buffer_rsrc_t qi_rsrc = tnt_rsrc(g.qpre_in, (unsigned)((long)T * B * A * 4));
     const __amdgpu_buffer_rsrc_t qo_rsrc = tnt_rsrc(g.dqpre, (unsigned)((long)T * B * A * 4));
     const unsigned al_off = (unsigned)((ab * R + rl) * 4), kp_off = (unsigned)((ab * R + rl) * (A >> 2) + c4);
+    // the external dalpha rider (AttArgs::ext): a uniform switch; without it the resource is empty and nothing is loaded
+    const bool has_ext = g.ext != nullptr;
+    const __amdgpu_buffer_rsrc_t ex_rsrc =
+        tnt_rsrc(g.ext, has_ext ? (unsigned)(((long)(T - 1) * g.ext_ts + (long)(B - 1) * g.ext_bs + R) * 4) : 0u);
+    const unsigned ex_off = (unsigned)((ab * g.ext_bs + rl) * 4);
     if (live) for (int i0 = T - 1; i0 >= 0; --i0) {
       const int i = __builtin_amdgcn_readfirstlane(i0);
       const int pi = (T - 1 - i) % 3, pn = (pi + 1) % 3;
@@ -1870,12 +1957,13 @@ __global__ __launch_bounds__(1024) void lc_seq_bwd_kernel(LcSeqBwdArgs a) {
       constexpr int NWP = 16 * G4 / 64;                      // polling waves
       const int ppart = tid / G4;                            // (c = c4)
       const bool pmine = tid < 16 * G4 && cokD;
-      float al[NP];
+      float al[NP], ex[NP];
       uint32_t mk[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const int r = p * RPP + rl;
         al[p] = r < R ? lc_ld1(al_rsrc, al_off + (unsigned)(p * RPP * 4), (unsigned)(i * B * R * 4)) : 0.f;
+        ex[p] = (has_ext && r < R) ? lc_ld1(ex_rsrc, ex_off + (unsigned)(p * RPP * 4), (unsigned)(i * g.ext_ts * 4)) : 0.f;
         mk[p] = (stored && cokA && r < R) ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(kp_rsrc, (int)(kp_off + (unsigned)(p * RPP * (A >> 2))),
                                                                                             (int)((long)i * a.keep_stride), 0) : 0xFu;
       }
@@ -1944,6 +2032,7 @@ __global__ __launch_bounds__(1024) void lc_seq_bwd_kernel(LcSeqBwdArgs a) {
       for (int p = 0; p < NP; ++p) {
         const float t = dc4.x * fv[p].x + dc4.y * fv[p].y + dc4.z * fv[p].z + dc4.w * fv[p].w;
         da[p] = adj_sum<G4>(t) + g.alpha_mse * (al[p] - 1.f);           // rows past R: al = 0, nothing of them is used
+        if (has_ext) da[p] += ex[p];
         dot += al[p] * da[p];
       }
       dot = tnt_wave_sum(dot) * (1.f / G4);                  // every row sits in G4 lanes: exact scaling
@@ -2495,18 +2584,22 @@ extern "C" int32_t tnt_lc_seq_bwd_work_floats(int32_t B, int32_t U) {
   return 3 * nrb * 32 * 32 * 256 + 3 * B * U + 3 * nrb * 16 * 16 * 64;
 }
 
-extern "C" int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+extern "C" int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
                                       const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
                                       float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
                                       const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
                                       int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
                                       float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
                                       uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
-                                      uint32_t site_out0, uint32_t* sync, float* guard_out, void* stream) {
+                                      uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, uint32_t* sync,
+                                      float* guard_out, void* stream) {
   if (T <= 0 || sync == nullptr || work == nullptr || U != 512 || B <= 0 || B > 128) return TNT_BADARG(24);
   if (!(rate_out >= 0.f && rate_out < 1.f)) return TNT_BADARG(36);
   if (!wide_ok(R, D, A) || R > 512 || D > 64 || A > 64) return TNT_BADARG(21);
   if ((long)(T + 1) * B * U * 4 >= (1L << 32)) return TNT_BADARG(19);
+  // the rider is read through a buffer resource: its last element, ext[(T-1) ext_ts + (B-1) ext_bs + R - 1], sets the size
+  if (ext != nullptr && (ext_ts < 0 || ext_bs < 0 || ((long)(T - 1) * ext_ts + (long)(B - 1) * ext_bs + R) * 4 >= (1L << 31)))
+    return TNT_BADARG(37);
   if (!tnt_aligned16(P) || !tnt_aligned16(F) || !tnt_aligned16(W2) || !tnt_aligned16(v) || !tnt_aligned16(dP) ||
       !tnt_aligned16(dF) || !tnt_aligned16(Wc) || !tnt_aligned16(Ur) || !tnt_aligned16(gates) || !tnt_aligned16(dz) ||
       !tnt_aligned16(work)) return TNT_BADARG(1);
@@ -2516,6 +2609,7 @@ extern "C" int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const
   g.dqpre = dqpre; g.B = B; g.R = R; g.D = D; g.A = A; g.U = U; g.in_lwidth = in_lwidth; g.slope = slope;
   g.rate_attn = rate_attn; g.rate_in = rate_in; g.seed = seed; g.site_attn = site_attn0; g.site_in = site_in0; g.step = 0;
   g.step_dev = step_dev; g.alpha_mse = alpha_mse_coef;
+  g.ext = ext; g.ext_ts = ext != nullptr ? ext_ts : 0; g.ext_bs = ext != nullptr ? ext_bs : 0;
   static const bool rb16 = getenv("TNT_SEQ_RB16") && atoi(getenv("TNT_SEQ_RB16")) != 0;               // A/B switch
   const bool rb8 = B <= 64 && !rb16;
   const int64_t nrb = rb8 ? (B + 7) / 8 : (B + 15) / 16;
@@ -2538,6 +2632,19 @@ extern "C" int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const
   hipLaunchKernelGGL(kern, dim3(256), dim3(1024), LB_LDS_BYTES, tnt_stream(stream), a);
   TNT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+                                      const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
+                                      float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
+                                      const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
+                                      int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
+                                      float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
+                                      uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
+                                      uint32_t site_out0, uint32_t* sync, float* guard_out, void* stream) {
+  return tnt_lc_seq_bwd_ext_f32(F, P, W2, v, qpre, alpha, keep4, keep_stride, dP, dF, dvb, dqpre, Ur, Wc, dout, gates, cs, dz,
+                                work, T, B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, seed, site_attn0, site_in0,
+                                step_dev, alpha_mse_coef, rate_out, site_out0, nullptr, 0, 0, sync, guard_out, stream);
 }
 
 extern "C" int32_t tnt_lc_seq_bwd_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,

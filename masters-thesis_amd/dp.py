@@ -437,6 +437,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.__dict__.get("loss_normalise", "count") == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)
+    if model.__dict__.get("attention_coverage") is not None:
+        # lc_nic.NIC(attention_coverage=...): the sum over the batch axis is not a per-rank quantity
+        raise NotImplementedError(model.COVERAGE_DP_REFUSAL)
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.__dict__.get("agc") and world > 1:

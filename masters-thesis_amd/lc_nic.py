@@ -24,13 +24,13 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN, S_LSTM_IN, S_LSTM_OUT, S_SS_COIN,
                          S_SS_DRAW, BN_EPS, BN_MOMENTUM, ScheduledSampling, check_sampling, check_length_penalty,
-                         _TokenChoice, _BeamDecode)
+                         _TokenChoice, _BeamDecode, AttentionCoverage)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
 S_DEEP = 6            # + i: feature dropout behind deep stage i of the depth-n encoder (deep_layers.py:58)
 S_NOUT = 144          # + i: output Dropout of step i of the free-running decoder, on the U-wide LSTM output (lc_NIC.py:207)
-from .ops import ACT_LEAKY
+from .ops import ACT_LEAKY, attention_coverage_work_floats
 
 
 def synthetic_groups(n_voxels, n_regions, out_dim, seed=42, overlap=0.0):
@@ -71,8 +71,13 @@ class NIC(ModelBase):
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
-                 teacher_forcing=True, scheduled_sampling=None, **kw):
+                 teacher_forcing=True, scheduled_sampling=None, attention_coverage=None, **kw):
         super().__init__(**kw)
+        # attention_coverage (model_base.AttentionCoverage): train_step differentiates CE + L2 + weight * coverage and the
+        # steps report ``coverage`` (_coverage_launch); None or weight 0 builds nothing and issues no launch
+        if attention_coverage is not None and not isinstance(attention_coverage, AttentionCoverage):
+            raise ValueError(f"attention_coverage must be None or a model_base.AttentionCoverage, got {attention_coverage!r}")
+        self.attention_coverage = attention_coverage if attention_coverage is not None and attention_coverage.weight > 0 else None
         # teacher_forcing=False: __call__ / train_step / test_step / fit run lc_NIC.call_naive_attention (lc_NIC.py:175-221),
         # the decoder fed its own greedy predictions (call_naive_attention's docstring)
         self.teacher_forcing = bool(teacher_forcing)
@@ -227,6 +232,7 @@ class NIC(ModelBase):
         self._shape = None
         if not self.teacher_forcing:
             self._naive_check()
+        self._coverage_check()
 
     # ------------------------------------------------------------------ weights
     def _init_weights(self, rng):
@@ -346,6 +352,10 @@ class NIC(ModelBase):
         self.work = f(max(D, A, 4 * U, ldV, H) * (2 * nch + 1))
         self.rowsq = f(n)
         self.metric_part = f(T * ((self.R + 63) // 64))      # partial sums of the attention metric (tnt_attention_metric_parts)
+        cov = self.attention_coverage
+        if cov is not None:     # the coverage gradient rider [rows][R] and the partials of the value (tnt_attention_coverage_f32)
+            self.cov_ext = f(cov.rows(T, B) * R)
+            self.cov_work = f(attention_coverage_work_floats(T, B, R, cov.axis_id))
         self._alloc_splitk([(n, H, V), (n, Et, 4 * U), (n, U, H), (D, 4 * U, n), (U, A, n), (D, A, B * R)])
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
@@ -584,6 +594,38 @@ class NIC(ModelBase):
             inter = self.inter_d
         self._inter_used = inter
         self._head_out(inter, self.logits, n)
+
+    COVERAGE_DP_REFUSAL = ("attention_coverage has no data-parallel schedule: the sum over the batch axis is not a per-rank "
+                           "quantity, and the sum over time would need the ranks' gradient scales.  Train it on one device")
+
+    def _coverage_check(self):
+        """the combinations the coverage penalty is built for; anything else refuses instead of training another loss"""
+        if self.attention_coverage is None:
+            return
+        if not self.teacher_forcing:
+            raise NotImplementedError("attention_coverage is built for the teacher-forced step: not for teacher_forcing=False "
+                                      "(the free-running decoder)")
+        if self.scheduled_sampling is not None:
+            raise NotImplementedError("attention_coverage is built for the teacher-forced step: not for scheduled_sampling")
+        if self.S != 1:
+            raise NotImplementedError("attention_coverage is a single-subject term: n_subjects > 1 is not supported")
+        if self.use_layer_norm:
+            raise NotImplementedError("attention_coverage is not built for the LayerNormLSTMCell (use_layer_norm=True)")
+        if self.grad_sync is not None:
+            raise NotImplementedError(self.COVERAGE_DP_REFUSAL)
+
+    def _coverage_launch(self, B, T, want_grad):
+        """tnt_attention_coverage_f32 on the finished attention weights of the step: ``coverage`` into met[4], and with
+        ``want_grad`` the gradient rider of the backward chain into cov_ext; a model without the term launches nothing"""
+        cov = self.attention_coverage
+        if cov is None:
+            return
+        self.be.attention_coverage(self.alpha, T, B, self.R, cov.axis_id, cov.coef(T, B, self.R) if want_grad else 0.0,
+                                   self.cov_ext if want_grad else None, self.met[4:5], self.cov_work)
+
+    def _coverage_key(self):
+        cov = self.attention_coverage
+        return cov.key if cov is not None else ()
 
     def _naive_check(self):
         """the combinations the free-running decoder is built for; anything else refuses instead of running another mode"""
@@ -824,7 +866,9 @@ class NIC(ModelBase):
                           self.dP, self.dF, self.dvb, self.dqpre, Ur, Wl[:D], self.dHs, self.gates, self.Cs, self.dZ,
                           self.lc_xch, T, B, R, D, A, U, 0.2, self.r_attn, self.r_lstm, D + Et, sd, S_ATTN, S_LSTM_IN, ds,
                           self._alpha_mse, self.seq_sync, self._guard_out(),
-                          out_drop=None if self.__dict__.get("_dout_masked", True) else (self.r_lstm, S_LSTM_OUT))
+                          out_drop=None if self.__dict__.get("_dout_masked", True) else (self.r_lstm, S_LSTM_OUT),
+                          **({} if self.attention_coverage is None
+                             else dict(ext=(self.cov_ext,) + self.attention_coverage.strides(R))))
         else:
             self._bwd_chain_steps(B, T, Wl, Ur, W2, v)
         hprev = self.Hs[:T].view(n, U)
@@ -863,8 +907,12 @@ class NIC(ModelBase):
         be = self.be
         R, D, A, U, Et = self.R, self.D, self.A, self.U, self.Et
         sd, ds = self.seed, self.drop_step
+        cov = self.attention_coverage
+        ext_ts, ext_bs = cov.strides(R) if cov is not None else (0, 0)
         for i in range(T - 1, -1, -1):
             last = i == T - 1
+            # the coverage gradient of this step's attention weights: its slab of the rider (every step's for axis="time")
+            ext = {} if cov is None else dict(ext=self.cov_ext[i * ext_ts:], ext_bs=ext_bs)
             # dctx_i = dZ_i @ Wc^T: every LSTM-backward workgroup leaves the partial of its 16 units, the attention
             # backward sums the U/16 parts (instead of running the whole product per sample on its own critical path)
             parts = (U // 16) * D <= 1024 and getattr(self, "ctx_parts", True)
@@ -878,13 +926,13 @@ class NIC(ModelBase):
                                       self.dvb, self.dqpre[i], self.dh_att, B, R, D, A, U, 0.2, self.r_attn, self.r_lstm,
                                       D + Et, sd, S_ATTN + i, S_LSTM_IN + i, 0, ds, dctx_part=self.dctx_part,
                                       nparts=U // 16, keep4=self.att_keep[i] if self._keep_stored else None,
-                                      alpha_mse=self._alpha_mse, fresh=last)
+                                      alpha_mse=self._alpha_mse, fresh=last, **ext)
             else:
                 be.attention_step_bwd(None, self.F, self.P, W2, v, self.qpre[i], self.alpha[i], self.dP, self.dF,
                                       self.dvb, self.dqpre[i], self.dh_att, B, R, D, A, U, 0.2, self.r_attn, self.r_lstm,
                                       D + Et, sd, S_ATTN + i, S_LSTM_IN + i, 0, ds, dz=self.dZ[i * B:(i + 1) * B],
                                       Wc=Wl[:D], keep4=self.att_keep[i] if self._keep_stored else None,
-                                      alpha_mse=self._alpha_mse, fresh=last)
+                                      alpha_mse=self._alpha_mse, fresh=last, **ext)
 
     def _bwd_chain_ln(self, B, T):
         """The T-step chain with the LayerNormLSTMCell (reverse of _decode_step's LayerNorm branch).  Per step: cell
@@ -1049,6 +1097,7 @@ class NIC(ModelBase):
         else:
             (self._forward if self.teacher_forcing else self._forward_naive)(B, T, True)
         self._loss_metrics(B, T, True)
+        self._coverage_launch(B, T, True)          # behind the forward chain, in front of the backward chain that reads it
         self._backward(B, T)
 
     def _stage_mask_job(self):
@@ -1061,6 +1110,8 @@ class NIC(ModelBase):
         m = self._met_snapshot(ring)
         if self.S == 1:
             out = Metrics(loss=m[0], L2=m[2], accuracy=m[1], attention=m[3])
+            if self.attention_coverage is not None:
+                out["coverage"] = m[4]              # unweighted; ``loss`` stays the cross-entropy
         else:       # keys of ms2_NIC.train_step's return dict (ms2_NIC.py:366-374), A, B, C ... per subject
             out = Metrics(loss=m[0], L2=m[2])
             for q in range(self.S):
@@ -1081,13 +1132,15 @@ class NIC(ModelBase):
         if not self.teacher_forcing and self.grad_sync is not None:
             raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
         self._ss_refuse()
+        self._coverage_check()                      # (grad_sync may have been attached since the constructor)
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._ss_refuse(T)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
         ring = False
         if self.grad_sync is None:
-            ring = self._run_step(self._step_runner(self.Et), ("train", B, T), lambda: self._train_and_update_graph(B, T))
+            ring = self._run_step(self._step_runner(self.Et), ("train", B, T) + self._coverage_key(),
+                                  lambda: self._train_and_update_graph(B, T))
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
         else:
@@ -1113,6 +1166,9 @@ class NIC(ModelBase):
             raise NotImplementedError("train_step_sam is a single-subject step (lc_NIC.py)")
         if self.scheduled_sampling is not None:
             raise NotImplementedError("train_step_sam is a teacher-forced step: not built for scheduled_sampling")
+        if self.attention_coverage is not None:
+            raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
+                                      "gradient of its first pass): not built for attention_coverage")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
@@ -1155,10 +1211,11 @@ class NIC(ModelBase):
         def run():
             (self._forward if self.teacher_forcing else self._forward_naive)(B, T, train_flag)
             self._loss_metrics(B, T, False)
+            self._coverage_launch(B, T, False)      # the value only
             self._norms_and_l2(self.met[2:3])
             if train_flag:
                 self.be.step_tick(None, self.drop_step, None, None, 0.0, 0.0)
-        self._run_captured(("test", B, T), run)
+        self._run_captured(("test", B, T) + self._coverage_key(), run)
         return self._metrics(False)
 
     def __call__(self, data, training=False):

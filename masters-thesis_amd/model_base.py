@@ -33,6 +33,59 @@ BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 SCORE_LOGITS_BYTES = 256 << 20      # score_captions: default bound on the logits of one decoder pass (sets max_rows)
 
 
+class AttentionCoverage:
+    """The coverage ("doubly stochastic attention") penalty of Show, Attend and Tell (Xu et al. 2015, section 4.2.1) for
+    the train_step of lc_nic.NIC; the definition is tnt_attention_coverage_f32's (include/tnt_hip.h).  With alpha [T][B][R]
+    the attention weights of a step's T decoder positions,
+      axis="time"  (Xu et al.):  s[b][r] = sum_t alpha[t][b][r]
+      axis="batch" (the reference's own line, lc_NIC.py:365-367, whose axis=1 is the batch axis): s[t][r] = sum_b alpha[t][b][r]
+    coverage = mean (1 - s)^2, and the step differentiates CE + L2 + weight * coverage.  The step's metrics gain the
+    unweighted ``coverage``; ``loss`` stays the cross-entropy.  weight = 0 is the model without the term.
+    Bad parameters raise ValueError here, before any launch."""
+
+    AXES = ("time", "batch")
+
+    def __init__(self, weight, axis="time"):
+        if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight):
+            raise ValueError(f"attention coverage weight must be a finite number, got {weight!r}")
+        if weight < 0:
+            raise ValueError(f"attention coverage weight must be >= 0, got {weight!r}")
+        if axis not in self.AXES:
+            raise ValueError(f"attention coverage axis must be one of {self.AXES}, got {axis!r}")
+        self.weight, self.axis = float(weight), axis
+
+    @property
+    def axis_id(self):
+        """the kernel's axis argument: 0 = time, 1 = batch"""
+        return self.AXES.index(self.axis)
+
+    @property
+    def key(self):
+        """what a recorded plan or a captured graph of the step depends on"""
+        return ("coverage", self.weight, self.axis)
+
+    def rows(self, T, B):
+        """the number of sums per region: B over time, T over the batch"""
+        return B if self.axis == "time" else T
+
+    def coef(self, T, B, R):
+        """2 weight / N, the factor of (s - 1) in the gradient"""
+        return 2.0 * self.weight / (self.rows(T, B) * R)
+
+    def strides(self, R):
+        """(ext_ts, ext_bs): the element strides of the gradient rider between steps and between samples"""
+        return (0, R) if self.axis == "time" else (R, 0)
+
+    def __eq__(self, other):
+        return isinstance(other, AttentionCoverage) and self.key == other.key
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        return f"AttentionCoverage(weight={self.weight!r}, axis={self.axis!r})"
+
+
 class ScheduledSampling:
     """Scheduled sampling (Bengio et al. 2015) for the train_step of nic.NIC and lc_nic.NIC; the definitions are
     tnt_scheduled_feedback_f32's and tnt_scheduled_feedback2_f32's (include/tnt_hip.h).  At each step, each caption row is

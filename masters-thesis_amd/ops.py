@@ -491,8 +491,19 @@ class HipBackend:
 
     def lc_seq_bwd(self, F, P, W2, v, qpre, alpha, keep4, keep_stride, dP, dF, dvb, dqpre, Ur, Wc, dout, gates, cs, dz, work, T,
                    B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, seed, site_attn0, site_in0, step_dev, alpha_mse, sync,
-                   guard_out=None, out_drop=None):
-        """out_drop = (rate, site0): dout is the gradient of the DROPPED outputs (tnt_lc_seq_bwd_drop_f32)."""
+                   guard_out=None, out_drop=None, ext=None):
+        """out_drop = (rate, site0): dout is the gradient of the DROPPED outputs (tnt_lc_seq_bwd_drop_f32).
+        ext = (buffer, ext_ts, ext_bs): an external gradient of the attention weights rides along (tnt_lc_seq_bwd_ext_f32,
+        with or without out_drop)."""
+        if ext is not None:
+            buf, ext_ts, ext_bs = ext
+            rate_out, site_out0 = out_drop if out_drop is not None else (0.0, 0)
+            self._call(self.lib.tnt_lc_seq_bwd_ext_f32, "tnt_lc_seq_bwd_ext_f32", _p(F), _p(P), _p(W2), _p(v), _p(qpre),
+                       _p(alpha), _p(keep4), int(keep_stride), _p(dP), _p(dF), _p(dvb), _p(dqpre), _p(Ur), _p(Wc), _p(dout),
+                       _p(gates), _p(cs), _p(dz), _p(work), T, B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, int(seed),
+                       int(site_attn0), int(site_in0), _p(step_dev), float(alpha_mse), float(rate_out), int(site_out0),
+                       _p(buf), int(ext_ts), int(ext_bs), _p(sync), _p(guard_out), self._s())
+            return
         if out_drop is not None:
             rate_out, site_out0 = out_drop
             self._call(self.lib.tnt_lc_seq_bwd_drop_f32, "tnt_lc_seq_bwd_drop_f32", _p(F), _p(P), _p(W2), _p(v), _p(qpre),
@@ -780,7 +791,15 @@ class HipBackend:
 
     def attention_step_bwd(self, dctx_d, F, P, W2, v, qpre, alpha, dP, dF, dvb, dqpre, dh, B, R, D, A, U, slope,
                            rate_attn, rate_in, in_lwidth, seed, site_attn, site_in, step, step_dev=None, dz=None,
-                           Wc=None, dctx_part=None, nparts=0, keep4=None, alpha_mse=0.0, fresh=False):
+                           Wc=None, dctx_part=None, nparts=0, keep4=None, alpha_mse=0.0, fresh=False, ext=None, ext_bs=0):
+        """ext (this step's slab) / ext_bs: an external gradient of the attention weights rides along
+        (tnt_attention_step_bwd_ext_f32)"""
+        if ext is not None:
+            self._call(self.lib.tnt_attention_step_bwd_ext_f32, "tnt_attention_step_bwd_ext_f32", _p(dctx_d), _p(F), _p(P),
+                       _p(W2), _p(v), _p(qpre), _p(alpha), _p(dP), _p(dF), _p(dvb), _p(dqpre), _p(dh), B, R, D, A, U, slope,
+                       rate_attn, rate_in, in_lwidth, seed, site_attn, site_in, step, _p(step_dev), _p(dz), _p(Wc),
+                       _p(dctx_part), nparts, _p(keep4), float(alpha_mse), int(bool(fresh)), _p(ext), int(ext_bs), self._s())
+            return
         self._call(self.lib.tnt_attention_step_bwd_f32, "tnt_attention_step_bwd_f32", _p(dctx_d), _p(F), _p(P), _p(W2), _p(v), _p(qpre), _p(alpha),
                                                        _p(dP), _p(dF), _p(dvb), _p(dqpre), _p(dh), B, R, D, A, U,
                                                        slope, rate_attn, rate_in, in_lwidth, seed, site_attn, site_in,
@@ -792,6 +811,17 @@ class HipBackend:
 
     def attention_metric(self, alpha, out, work, T, B, R, tstride=0):
         self._call(self.lib.tnt_attention_metric_f32, "tnt_attention_metric_f32", _p(alpha), _p(out), _p(work), T, B, R, tstride, self._s())
+
+    def attention_coverage(self, alpha, T, B, R, axis, coef, ext, out, work, tstride=0):
+        """axis 0 = time, 1 = batch; ext / out nullable; work: attention_coverage_work_floats(T, B, R, axis) floats"""
+        self._call(self.lib.tnt_attention_coverage_f32, "tnt_attention_coverage_f32", _p(alpha), int(tstride), T, B, R, int(axis),
+                   float(coef), _p(ext), _p(out), _p(work), self._s())
+
+
+def attention_coverage_work_floats(T, B, R, axis):
+    """floats of ``work`` of tnt_attention_coverage_f32 (the formula of include/tnt_hip.h): one partial per 256 regions of a
+    row, rows = B for axis 0 (time) and T for axis 1 (batch)"""
+    return (B if axis == 0 else T) * ((R + 255) // 256)
 
 
 _backend = None
