@@ -1076,6 +1076,46 @@ int32_t tnt_sgd_f32(float* theta, float* mom, const float* grad, const int32_t* 
                     const int64_t* span_off, const int32_t* span_len, const float* seg_l2,
                     const float* sq, const float* sq_override, int32_t nspan, float lr,
                     const float* lr_dev, float momentum, float clipnorm, const uint32_t* guard, void* stream);
+/* ---- decoupled weight decay (tf.keras.optimizers.AdamW and the `weight_decay=` argument of every keras >= 2.11
+ * optimizer; the rule of torch.optim.AdamW) inside the update launches.  For a variable s with decay wd_s >= 0 and the
+ * current learning rate lr (the float32 at `lr`, written by tnt_lr_schedule_f32 or by the host) one update does
+ *     g  = (grad + 2 lambda_s theta) * clip_scale            unchanged: the coupled L2 stays, and stays in the clip norm
+ *     m, v as in tnt_adam_f32
+ *     theta' = (theta - (lr * wd_s) * theta) - lr_t * m / (sqrt(v) + eps)      Adam; lr_t as in tnt_adam_f32
+ *     theta' = (theta - (lr * wd_s) * theta) + (mu * mom - lr * g)             SGD with momentum mu
+ * lr * wd_s is one float32 product formed per workgroup; the decay uses the theta the gradient was taken at (what the
+ * kernel has loaded) and enters neither the clip norm, nor m / v, nor the L2 metric; wd_s == 0 leaves the variable's update
+ * bit for bit what the plain entry computes; a tripped guard word leaves everything untouched; `lr` is read on the device
+ * when the launch runs, so a replayed launch plan or hipGraph decays with the live, scheduled rate.  Each entry is its
+ * plain counterpart's kernel with the decay switched on at compile time, and takes the counterpart's arguments plus
+ *     tnt_adamw_ring_f32          lr, seg_wd [one float per variable, indexed like seg_l2]     (ring NULL: no metrics ring)
+ *     tnt_adamw_fin_f32           seg_wd; lr is fin->lr, which the descriptor already carries
+ *     tnt_sgdw_f32                seg_wd; `lr` is tnt_sgd_f32's lr_dev and must be given (there is no host-side lr)
+ *     tnt_dense_dw_adamw_f32, tnt_dense_dw_adamw_fin_f32      lr, wd: the one variable's decay, a finite float >= 0
+ * TNT_BADARG, and no launch, for a null lr or seg_wd and for a negative or non-finite wd. */
+int32_t tnt_adamw_ring_f32(float* theta, float* m, float* v, const float* grad,
+                           const int32_t* span_seg, const int64_t* span_off, const int32_t* span_len,
+                           const float* seg_l2, const float* sq, const float* sq_override,
+                           int32_t nspan, float lr_t, const float* lr_t_dev, float beta1, float beta2,
+                           float eps, float clipnorm, const uint32_t* guard, const float* met, int32_t nmet, float* ring,
+                           int32_t ring_rows, uint32_t* ring_t, const float* lr, const float* seg_wd, void* stream);
+int32_t tnt_adamw_fin_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                          const int64_t* span_off, const int32_t* span_len, const float* sq_override, int32_t nspan, float eps,
+                          float clipnorm, const tnt_finalize_desc* fin, const float* met, int32_t nmet, float* ring,
+                          int32_t ring_rows, uint32_t* ring_t, const float* seg_wd, void* stream);
+int32_t tnt_sgdw_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                     const int64_t* span_off, const int32_t* span_len, const float* seg_l2,
+                     const float* sq, const float* sq_override, int32_t nspan, const float* lr, float momentum,
+                     float clipnorm, const uint32_t* guard, const float* seg_wd, void* stream);
+int32_t tnt_dense_dw_adamw_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                               const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                               float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N, int32_t E,
+                               int32_t Bk, int32_t ldx, const float* lr, float wd, void* stream);
+int32_t tnt_dense_dw_adamw_fin_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                   const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                   const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                   const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx, const float* lr,
+                                   float wd, void* stream);
 /* ---- adaptive gradient clipping, unit-wise (AttemptFour/Model/agc.py:20-38; call site lc_NIC.py:388) ----
  * Applied in place to the flat gradient arena before the norms / clip-by-norm / Adam: per variable v (table entry:
  * arena offset var_off, row stride var_ld, L2 lambda var_lam) and per unit = output column of a keras (in, out) kernel

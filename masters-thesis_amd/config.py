@@ -5,7 +5,7 @@ import yaml
 
 from . import schedules
 from .model_base import AttentionCoverage
-from .optimizers import Adam, SGD, CategoricalCrossentropy
+from .optimizers import Adam, AdamW, SGD, CategoricalCrossentropy
 
 
 def load_config(path):
@@ -18,12 +18,25 @@ def build_optimizer(config):
     # lr_schedule: an optional key of this library's (main.py:81-84 builds its schedule in code): ``kind`` plus that
     # optimizers.schedules class's arguments, optional warmup_steps / warmup_start.  It takes the learning rate's place
     sched = schedules.from_config(config["lr_schedule"]) if config.get("lr_schedule") is not None else None
-    if config["optimizer"] == "Adam":
-        return Adam(learning_rate=0.0001 if sched is None else sched, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9,
-                    clipnorm=config["clipnorm"])
-    if config["optimizer"] == "SGD":
-        return SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False)
-    raise ValueError("No optimizer specified")
+    # weight_decay / weight_decay_exclude (a list of name substrings): optional keys of this library's, decoupled weight
+    # decay (optimizers._WeightDecay); ``optimizer: AdamW`` is Adam as above with keras's default decay 0.004 unless given
+    wd, excl = config.get("weight_decay"), config.get("weight_decay_exclude")
+    if excl is not None and (isinstance(excl, str) or not isinstance(excl, (list, tuple))):
+        raise ValueError(f"weight_decay_exclude must be a list of name substrings, got {excl!r}")
+    if config["optimizer"] in ("Adam", "AdamW"):
+        kw = dict(learning_rate=0.0001 if sched is None else sched, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9,
+                  clipnorm=config["clipnorm"])
+        if config["optimizer"] == "AdamW":
+            opt = AdamW(weight_decay=0.004 if wd is None else wd, **kw)
+        else:
+            opt = Adam(weight_decay=wd, **kw)
+    elif config["optimizer"] == "SGD":
+        opt = SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False, weight_decay=wd)
+    else:
+        raise ValueError("No optimizer specified")
+    if excl:
+        opt.exclude_from_weight_decay(var_names=list(excl))
+    return opt
 
 
 def build_model(config, groups, mode="attention", input_size=None, **kw):

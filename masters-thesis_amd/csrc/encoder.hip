@@ -312,6 +312,8 @@ struct DwArgs {
   // EPI 2 without a finalize launch in front (tnt_dense_dw_adam_fin_f32): the variable's clip norm is summed here, by
   // every wave, from its span partials fin_partial[2 k], fin_k0 <= k < fin_k1 (tnt_seg_sums: the canonical order)
   const float* fin_partial; int fin_k0, fin_k1;
+  // EPI 2 with WD (tnt_dense_dw_adamw_f32 / _fin_f32): decoupled weight decay of the one variable, lr read on the device
+  const float* lr_dev; float wd;
 };
 
 // PERM (every wave has all its TPW tiles, TPW = 2 or 4): MFMA column n of tile j is output column TPW n + j of the
@@ -325,9 +327,11 @@ struct DwArgs {
 //   2  clip + Adam on the strip as it leaves the MFMAs: theta, m, v stream through registers one strip ahead (their
 //      loads are issued before the previous strip's stores, so waiting for them never drains the stores), g is never
 //      stored -- 24 bytes per parameter instead of 4 (dW write) + 8 (norm pass) + 28 (Adam).
-template <int TPW, bool PERM, int EPI = 0, bool NTM = false>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
+//      WD: the step is taken from theta - (lr * wd) * theta (decoupled weight decay, tnt_decayed in tnt_fin.h).
+template <int TPW, bool PERM, int EPI = 0, bool NTM = false, bool WD = false>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
 __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
   static_assert(EPI == 0 || (PERM && TPW == 4), "fused epilogues use the vector row layout");
+  static_assert(!WD || EPI == 2, "the decay belongs to the fused update");
   constexpr int DW_MAXT = TPW;
   if (EPI == 2 && a.guard && a.guard[0] != 0u) return;       // the step's forward pass was invalid: leave the model untouched
   __shared__ float As[2][DW_KS * 4 * DW_LDA];
@@ -418,7 +422,7 @@ __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
   // fused epilogues: this lane's 4 rows x 4 adjacent columns of theta / m / v for a strip
   const long eoff = (long)(lk * 4) * a.E + t0 * 16 + TPW * lc;
   float4 th[4], mm[4], vv[4], thn[4], mmn[4], vvn[4];
-  float q = 0.f, wq = 0.f, cs = 1.f, lr_t = 0.f;
+  float q = 0.f, wq = 0.f, cs = 1.f, lr_t = 0.f, dk = 0.f;
   auto tload = [&](int st, float4* t, float4* m_, float4* v_) {
     const int sc = min(st, nstrip - 1);
 #pragma unroll
@@ -442,6 +446,7 @@ __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
       cs = a.clipnorm / fmaxf(sqrtf(sqv), a.clipnorm);
     }
     lr_t = a.lr_t_dev[0];
+    if (WD) dk = a.lr_dev[0] * a.wd;
   }
   __syncthreads();
   for (; s < nstrip; s += gridDim.x, cur ^= 1) {
@@ -495,7 +500,7 @@ __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
             const float g = (g4[j] + a.lam2 * wp[j]) * cs;
             mp[j] = mp[j] + (g - mp[j]) * ob1;
             vp[j] = vp[j] + (g * g - vp[j]) * ob2;
-            wp[j] = wp[j] - lr_t * mp[j] / (sqrtf(vp[j]) + a.eps);
+            wp[j] = (WD ? tnt_decayed(wp[j], dk) : wp[j]) - lr_t * mp[j] / (sqrtf(vp[j]) + a.eps);
           }
           const long o = (long)s * DW_MS * a.E + (long)r * a.E + eoff;
           *reinterpret_cast<float4*>(a.theta + o) = th[r];
@@ -1000,6 +1005,31 @@ extern "C" int32_t tnt_dense_dw_sqnorm_f32(const float* x, const float* dpre, co
   return 0;
 }
 
+// The fused update's four entry points: the clip norm from sq (partial == nullptr) or from the span partials
+// partial[k0:k1] (the _fin forms), plain (lr == nullptr: the instantiation without decay) or decaying by wd at *lr.
+static int32_t dw_adam_launch(const float* x, const float* dpre, float* theta, float* m, float* v, float l2, const float* sq,
+                              const float* partial, int32_t k0, int32_t k1, const float* sq_override, const float* lr_t_dev,
+                              float beta1, float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N, int32_t E,
+                              int32_t Bk, int32_t ldx, const float* lr, float wd, void* stream) {
+  const int nstrip = (N + DW_MS - 1) / DW_MS, grid = nstrip < 256 ? nstrip : 256;
+  DwArgs a{};
+  a.x = x; a.dpre = dpre; a.N = N; a.E = E; a.Bk = Bk; a.ldx = ldx;
+  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = sq; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.guard = guard;
+  a.fin_partial = partial; a.fin_k0 = k0; a.fin_k1 = k1;
+  a.lr_dev = lr; a.wd = wd;
+  const dim3 g(grid, E / 512);
+  const bool nt = tnt_stream_policy_nt();
+  if (lr != nullptr && nt) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true, true>), g, dim3(512), 0, tnt_stream(stream), a);
+  else if (lr != nullptr) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, false, true>), g, dim3(512), 0, tnt_stream(stream), a);
+  else if (nt) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true>), g, dim3(512), 0, tnt_stream(stream), a);
+  else hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2>), g, dim3(512), 0, tnt_stream(stream), a);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+static bool dw_wd_ok(const float* lr, float wd) { return lr != nullptr && wd >= 0.f && wd <= 3.4028234e38f; }   // NaN fails wd >= 0
+
 extern "C" int32_t tnt_dense_dw_adam_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
                                          const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
                                          float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N,
@@ -1007,17 +1037,20 @@ extern "C" int32_t tnt_dense_dw_adam_f32(const float* x, const float* dpre, floa
   if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
   if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || sq == nullptr)
     return TNT_BADARG(3);
-  const int nstrip = (N + DW_MS - 1) / DW_MS, grid = nstrip < 256 ? nstrip : 256;
-  DwArgs a{};
-  a.x = x; a.dpre = dpre; a.N = N; a.E = E; a.Bk = Bk; a.ldx = ldx;
-  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = sq; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
-  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.guard = guard;
-  if (tnt_stream_policy_nt())
-    hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true>), dim3(grid, E / 512), dim3(512), 0, tnt_stream(stream), a);
-  else
-    hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2>), dim3(grid, E / 512), dim3(512), 0, tnt_stream(stream), a);
-  TNT_LAUNCH_CHECK();
-  return 0;
+  return dw_adam_launch(x, dpre, theta, m, v, l2, sq, nullptr, 0, 0, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard, N, E,
+                        Bk, ldx, nullptr, 0.f, stream);
+}
+
+extern "C" int32_t tnt_dense_dw_adamw_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                          const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                                          float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N,
+                                          int32_t E, int32_t Bk, int32_t ldx, const float* lr, float wd, void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || sq == nullptr)
+    return TNT_BADARG(3);
+  if (!dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  return dw_adam_launch(x, dpre, theta, m, v, l2, sq, nullptr, 0, 0, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard, N, E,
+                        Bk, ldx, lr, wd, stream);
 }
 
 extern "C" int32_t tnt_dense_dw_adam_fin_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
@@ -1027,18 +1060,21 @@ extern "C" int32_t tnt_dense_dw_adam_fin_f32(const float* x, const float* dpre, 
   if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
   if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || partial == nullptr || k0 < 0 || k1 <= k0)
     return TNT_BADARG(3);
-  const int nstrip = (N + DW_MS - 1) / DW_MS, grid = nstrip < 256 ? nstrip : 256;
-  DwArgs a{};
-  a.x = x; a.dpre = dpre; a.N = N; a.E = E; a.Bk = Bk; a.ldx = ldx;
-  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = nullptr; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
-  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.guard = guard;
-  a.fin_partial = partial; a.fin_k0 = k0; a.fin_k1 = k1;
-  if (tnt_stream_policy_nt())
-    hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true>), dim3(grid, E / 512), dim3(512), 0, tnt_stream(stream), a);
-  else
-    hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2>), dim3(grid, E / 512), dim3(512), 0, tnt_stream(stream), a);
-  TNT_LAUNCH_CHECK();
-  return 0;
+  return dw_adam_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard,
+                        N, E, Bk, ldx, nullptr, 0.f, stream);
+}
+
+extern "C" int32_t tnt_dense_dw_adamw_fin_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                              const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                              const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                              const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx,
+                                              const float* lr, float wd, void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || partial == nullptr || k0 < 0 || k1 <= k0)
+    return TNT_BADARG(3);
+  if (!dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  return dw_adam_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard,
+                        N, E, Bk, ldx, lr, wd, stream);
 }
 
 extern "C" int32_t tnt_block_dense_dx_f32(const float* dpre, const float* W, float* dx, int32_t B, int32_t R,

@@ -57,10 +57,15 @@ __device__ __forceinline__ float clip_scale(const float* sq, const float* sq_ove
 
 struct MetRing { const float* met; float* ring; uint32_t* ring_t; int nmet, rows; };
 
+// WD (here and in adam_fin_kernel, sgd_kernel, csrc/encoder.hip's EPI 2): decoupled weight decay, the step is taken from
+// theta - (lr * seg_wd[seg]) * theta instead of theta (tnt_decayed); lr is read on the device.  Without WD the two
+// trailing pointers are not read.
+template <bool WD>
 __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
                                                    const float* sq, const float* sq_override, int nspan, float lr_t,
                                                    const float* lr_t_dev, float b1, float b2, float eps,
-                                                   float clipnorm, const uint32_t* guard, MetRing r) {
+                                                   float clipnorm, const uint32_t* guard, MetRing r, const float* lr_dev,
+                                                   const float* seg_wd) {
   const int sp = blockIdx.x;
   if (sp >= nspan) return;
   // Metrics ring (one wave of workgroup 0, off every critical path: the metrics are final before this launch starts): the
@@ -79,6 +84,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float
   const int seg = t.span_seg[sp];
   const float lam2 = 2.f * t.seg_l2[seg];
   const float cs = clip_scale(sq, sq_override, seg, clipnorm);
+  const float dk = WD ? lr_dev[0] * seg_wd[seg] : 0.f;
   const float ob1 = 1.f - b1, ob2 = 1.f - b2;
   const int len4 = len & ~3;
   for (int i = threadIdx.x * 4; i < len4; i += 1024) {
@@ -92,7 +98,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float
       const float g = (gp[j] + lam2 * wp[j]) * cs;
       mp[j] = mp[j] + (g - mp[j]) * ob1;
       vp[j] = vp[j] + (g * g - vp[j]) * ob2;
-      wp[j] = wp[j] - lr_t * mp[j] / (sqrtf(vp[j]) + eps);
+      wp[j] = (WD ? tnt_decayed(wp[j], dk) : wp[j]) - lr_t * mp[j] / (sqrtf(vp[j]) + eps);
     }
     *reinterpret_cast<float4*>(theta + off + i) = w;
     *reinterpret_cast<float4*>(m + off + i) = mm;
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float
     const float mm = m[off + i] + (g - m[off + i]) * ob1;
     const float vv = v[off + i] + (g * g - v[off + i]) * ob2;
     m[off + i] = mm; v[off + i] = vv;
-    theta[off + i] = w - lr_t * mm / (sqrtf(vv) + eps);
+    theta[off + i] = (WD ? tnt_decayed(w, dk) : w) - lr_t * mm / (sqrtf(vv) + eps);
   }
 }
 
@@ -124,7 +130,11 @@ struct FinArgs {
   const float* extra_part; float* extra; int n_extra; int extra_seg;
   const int32_t* ids_src; int32_t* ids_dst; int n_ids;
   const float* x2; float* out2; int n2; float scale2;
-  int64_t* adam_t; uint32_t* drop_step; const float* lr; float* lr_t; float b1, b2; const uint32_t* guard;
+  int64_t* adam_t; uint32_t* drop_step; const float* lr; float* lr_t;
+  const float* seg_wd;     // WD instantiations only (tnt_adamw_fin_f32): beside lr / lr_t, so that its kernel-argument word comes
+                           // with theirs -- as a trailing kernel parameter the pointer was a scalar load of its own, waited for
+                           // at once, between the span workgroup's first loads and its clip norm
+  float b1, b2; const uint32_t* guard;
   uint32_t* arrive;
 };
 
@@ -140,7 +150,7 @@ __device__ __forceinline__ void fin_arrive_and_tick(const FinArgs& f, unsigned t
 
 constexpr int AF_U = 4;          // rounds of 1024 elements in flight per span workgroup (tnt_adam_fin_f32)
 
-template <bool NT>
+template <bool NT, bool WD>
 __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
                                                        const float* sq_override, int nspan, float eps, float clipnorm,
                                                        FinArgs f, MetRing r) {
@@ -174,6 +184,7 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
       load(tid * 4);
       const float lr_t = f.lr_t[0];                        // written by the norm launch in front of this one (its "lr job")
       const float lam2 = 2.f * f.seg_l2[seg];
+      const float dk = WD ? f.lr[0] * f.seg_wd[seg] : 0.f; // one uniform scalar: the AF_U x 4 float4 in flight are untouched
       float cs = 1.f;
       if (clipnorm > 0.f) {
         float q;
@@ -201,7 +212,7 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
               const float g = (gp[j] + lam2 * wp[j]) * cs;
               mp[j] = mp[j] + (g - mp[j]) * ob1;
               vp[j] = vp[j] + (g * g - vp[j]) * ob2;
-              wp[j] = wp[j] - lr_t * mp[j] / (sqrtf(vp[j]) + eps);
+              wp[j] = (WD ? tnt_decayed(wp[j], dk) : wp[j]) - lr_t * mp[j] / (sqrtf(vp[j]) + eps);
             }
             *reinterpret_cast<float4*>(theta + off + i) = wv[u];
             tnt_st4<NT>(m + off + i, mm[u]);
@@ -215,7 +226,7 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
         const float mm = m[off + i] + (g - m[off + i]) * ob1;
         const float vv = v[off + i] + (g * g - v[off + i]) * ob2;
         m[off + i] = mm; v[off + i] = vv;
-        theta[off + i] = wv - lr_t * mm / (sqrtf(vv) + eps);
+        theta[off + i] = (WD ? tnt_decayed(wv, dk) : wv) - lr_t * mm / (sqrtf(vv) + eps);
       }
     }
   } else {
@@ -278,10 +289,11 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
   if (tid == 0) fin_arrive_and_tick(f, (unsigned)nspan + 1u);
 }
 
+template <bool WD>
 __global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, const float* grad, SpanTab t,
                                                   const float* sq, const float* sq_override, int nspan, float lr,
                                                   const float* lr_dev, float momentum, float clipnorm,
-                                                  const uint32_t* guard) {
+                                                  const uint32_t* guard, const float* seg_wd) {
   const int sp = blockIdx.x;
   if (sp >= nspan) return;
   if (guard && guard[0] != 0u) return;
@@ -291,12 +303,13 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, cons
   const int seg = t.span_seg[sp];
   const float lam2 = 2.f * t.seg_l2[seg];
   const float cs = clip_scale(sq, sq_override, seg, clipnorm);
+  const float dk = WD ? lr * seg_wd[seg] : 0.f;
   for (int i = threadIdx.x; i < len; i += 256) {
     const float w = theta[off + i];
     const float g = (grad[off + i] + lam2 * w) * cs;
     const float mv = momentum * mom[off + i] - lr * g;
     mom[off + i] = mv;
-    theta[off + i] = w + mv;
+    theta[off + i] = (WD ? tnt_decayed(w, dk) : w) + mv;
   }
 }
 
@@ -571,18 +584,46 @@ extern "C" int32_t tnt_l2_total_f32(const float* wsq, const float* seg_l2, int32
   return 0;
 }
 
+namespace {
+// tnt_adam_ring_f32 (seg_wd == nullptr: the plain instantiation) and tnt_adamw_ring_f32
+int32_t adam_ring_launch(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg, const int64_t* span_off,
+                         const int32_t* span_len, const float* seg_l2, const float* sq, const float* sq_override, int32_t nspan,
+                         float lr_t, const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                         const uint32_t* guard, const float* met, int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t,
+                         const float* lr, const float* seg_wd, void* stream) {
+  if (nspan <= 0) return ring ? TNT_BADARG(11) : 0;
+  if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(20);
+  SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
+  const MetRing r{met, ring, ring_t, nmet, ring_rows};
+  if (seg_wd != nullptr)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override,
+                       nspan, lr_t, lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, lr, seg_wd);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override,
+                       nspan, lr_t, lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, nullptr, nullptr);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace
+
 extern "C" int32_t tnt_adam_ring_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
                                      const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
                                      const float* sq_override, int32_t nspan, float lr_t, const float* lr_t_dev, float beta1,
                                      float beta2, float eps, float clipnorm, const uint32_t* guard, const float* met,
                                      int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, void* stream) {
-  if (nspan <= 0) return ring ? TNT_BADARG(11) : 0;
-  if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(20);
-  SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
-  hipLaunchKernelGGL(adam_kernel, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override,
-                     nspan, lr_t, lr_t_dev, beta1, beta2, eps, clipnorm, guard, MetRing{met, ring, ring_t, nmet, ring_rows});
-  TNT_LAUNCH_CHECK();
-  return 0;
+  return adam_ring_launch(theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev, beta1,
+                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, nullptr, nullptr, stream);
+}
+
+extern "C" int32_t tnt_adamw_ring_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                      const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                      const float* sq_override, int32_t nspan, float lr_t, const float* lr_t_dev, float beta1,
+                                      float beta2, float eps, float clipnorm, const uint32_t* guard, const float* met,
+                                      int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, const float* lr,
+                                      const float* seg_wd, void* stream) {
+  if (lr == nullptr || seg_wd == nullptr) return TNT_BADARG(21);
+  return adam_ring_launch(theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev, beta1,
+                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, lr, seg_wd, stream);
 }
 
 extern "C" int32_t tnt_adam_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
@@ -599,8 +640,21 @@ extern "C" int32_t tnt_sgd_f32(float* theta, float* mom, const float* grad, cons
                                float clipnorm, const uint32_t* guard, void* stream) {
   if (nspan <= 0) return 0;
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
-  hipLaunchKernelGGL(sgd_kernel, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override,
-                     nspan, lr, lr_dev, momentum, clipnorm, guard);
+  hipLaunchKernelGGL(sgd_kernel<false>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override,
+                     nspan, lr, lr_dev, momentum, clipnorm, guard, nullptr);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t tnt_sgdw_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                                const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                const float* sq_override, int32_t nspan, const float* lr, float momentum, float clipnorm,
+                                const uint32_t* guard, const float* seg_wd, void* stream) {
+  if (lr == nullptr || seg_wd == nullptr) return TNT_BADARG(14);
+  if (nspan <= 0) return 0;
+  SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
+  hipLaunchKernelGGL(sgd_kernel<true>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override,
+                     nspan, 0.f, lr, momentum, clipnorm, guard, seg_wd);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -708,21 +762,45 @@ int32_t fin_fill(FinArgs& f, const tnt_finalize_desc* d) {
 }
 }  // namespace
 
-extern "C" int32_t tnt_adam_fin_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
-                                    const int64_t* span_off, const int32_t* span_len, const float* sq_override,
-                                    int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met,
-                                    int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, void* stream) {
+namespace {
+// tnt_adam_fin_f32 (seg_wd == nullptr: the plain instantiations) and tnt_adamw_fin_f32
+template <bool WD>
+int32_t adam_fin_launch(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg, const int64_t* span_off,
+                        const int32_t* span_len, const float* sq_override, int32_t nspan, float eps, float clipnorm,
+                        const tnt_finalize_desc* fin, const float* met, int32_t nmet, float* ring, int32_t ring_rows,
+                        uint32_t* ring_t, const float* seg_wd, void* stream) {
   if (nspan < 0) return TNT_BADARG(9);
   if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(13);
   FinArgs f;
   if (int32_t rc = fin_fill(f, fin)) return rc;
+  f.seg_wd = seg_wd;
   SpanTab t{span_seg, span_off, span_len, nullptr, nullptr};
   if (tnt_stream_policy_nt())
-    hipLaunchKernelGGL(adam_fin_kernel<true>, dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq_override,
-                       nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
+    hipLaunchKernelGGL((adam_fin_kernel<true, WD>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
+                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
   else
-    hipLaunchKernelGGL(adam_fin_kernel<false>, dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq_override,
-                       nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
+    hipLaunchKernelGGL((adam_fin_kernel<false, WD>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
+                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
   TNT_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+extern "C" int32_t tnt_adam_fin_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                    const int64_t* span_off, const int32_t* span_len, const float* sq_override,
+                                    int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met,
+                                    int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, void* stream) {
+  return adam_fin_launch<false>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met, nmet,
+                                ring, ring_rows, ring_t, nullptr, stream);
+}
+
+// the decaying launch reads the learning rate through the descriptor's own `lr` (fin_fill refuses a null one)
+extern "C" int32_t tnt_adamw_fin_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                     const int64_t* span_off, const int32_t* span_len, const float* sq_override,
+                                     int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met,
+                                     int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, const float* seg_wd,
+                                     void* stream) {
+  if (seg_wd == nullptr) return TNT_BADARG(14);
+  return adam_fin_launch<true>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met, nmet,
+                               ring, ring_rows, ring_t, seg_wd, stream);
 }

@@ -95,6 +95,11 @@ __device__ __forceinline__ void tnt_span_norm(const float* theta, const float* g
   }
 }
 
+// Decoupled weight decay (AdamW / keras weight_decay=; the WD instantiations of the update kernels): the theta the step
+// is subtracted from, theta - dk * theta with dk = lr * wd formed once per workgroup.  dk == 0 hands theta back bit for
+// bit (-0.0 included), so a variable without decay is updated exactly as the plain instantiation updates it.
+__device__ __forceinline__ float tnt_decayed(float w, float dk) { return dk != 0.f ? w - dk * w : w; }
+
 // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) for the step being applied, t = *adam_t + 1 (the counter is advanced at the END of the
 // update launch, by its last workgroup, when nobody reads it any more)
 __device__ __forceinline__ float tnt_adam_lr_t(const int64_t* adam_t, const float* lr, float b1, float b2) {

@@ -434,6 +434,10 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.__dict__.get("average") is not None:
         # compile(optimizers.MovingAverage / SWA): the averaging launch has no place in the data-parallel schedules
         raise NotImplementedError(model.AVERAGE_DP_REFUSAL)
+    if model.__dict__.get("seg_wd") is not None or getattr(model.optimizer, "weight_decay", None):
+        # compile(AdamW / weight_decay=): the data-parallel update launches (slices, the row-sharded encoder) do not decay
+        raise NotImplementedError(model.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
+                                                                    "row-sharded encoder update included)"))
     if model.__dict__.get("loss_normalise", "count") == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)

@@ -16,7 +16,8 @@ import torch
 
 from . import ops
 from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_focal_gamma, loss_label_smoothing, loss_normalise,
-                         loss_unlikelihood, optimizer_average, optimizer_schedule)
+                         loss_unlikelihood, optimizer_average, optimizer_schedule, check_weight_decay,
+                         weight_decay_table)
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -884,6 +885,8 @@ class ModelBase:
         self.class_weight = None            # host copy of the token weights (compile loss / set_class_weight / fit), or None
         self.cw_dev = None                  # the same V floats on the device: an argument of the weighted head launch
         self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
+        self.seg_wd = None                  # decoupled weight decay (compile optimizer's weight_decay): one float per variable on the device, or None
+        self.seg_wd_host = None             # the same table on the host (the encoder's fused update takes its entry as a scalar)
         self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
         self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
         self.built = False
@@ -917,6 +920,7 @@ class ModelBase:
         avg = optimizer_average(optimizer)
         if avg is not None and self.grad_sync is not None:
             raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
+        self._check_weight_decay(bool(check_weight_decay(getattr(optimizer, "weight_decay", None))))
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
         # fixed here, not read per step: the head launch sits inside captured graphs
@@ -1037,7 +1041,71 @@ class ModelBase:
         # max(start_step, 1); until then it holds the initial ones
         self.opt_avg = a.theta.clone() if self.__dict__.get("average") is not None else None
         self._swapped = False
+        # decoupled weight decay: the per-variable table from the descriptor and its exclusions, which are final from here
+        # on (keras: exclude_from_weight_decay raises once the optimizer is built)
+        tab = weight_decay_table(self.optimizer, list(a.entries))
+        self._check_weight_decay(tab is not None)
+        self.seg_wd = self.seg_wd_host = None
+        self._store_seg_wd(tab)
+        getattr(self.optimizer, "_optimizer", self.optimizer)._wd_built = True
         self._graphs = {}
+
+    # ------------------------------------------------------------------ decoupled weight decay (Adam / SGD weight_decay=, AdamW)
+    WEIGHT_DECAY_REFUSAL = ("decoupled weight decay (weight_decay= / AdamW) is built for the single-device update launches only: "
+                            "{what} does not apply it.  Train with weight_decay=None there, or on one device without it")
+
+    def _check_weight_decay(self, on):
+        """the refusals of a decaying optimizer (compile, the optimizer-state build, set_weight_decay): data parallel and
+        adaptive gradient clipping; train_step_sam and dp.attach refuse on their side"""
+        if not on:
+            return
+        if self.grad_sync is not None or int(self.__dict__.get("dp_world", 1) or 1) > 1:
+            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, "
+                                                                      "the row-sharded encoder update included)"))
+        if self.__dict__.get("agc"):
+            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
+
+    def _weight_decay_refuse(self, what):
+        if self.__dict__.get("seg_wd") is not None:
+            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what=what))
+
+    def _store_seg_wd(self, tab):
+        """tab: None (nothing decays: the plain update launches) or one decay per variable.  The device table is written in
+        place where it exists, so a recorded plan or a captured graph that holds its address decays by the new values; a
+        change between no decay and decay changes the launches and drops the recordings, and so does a new value for a
+        variable whose update takes its decay as a scalar argument (the encoder's fused update)."""
+        if tab is not None and not any(tab):
+            tab = None
+        old = self.__dict__.get("seg_wd_host")
+        if (tab is None) != (old is None):
+            self._graphs = {}
+        if tab is None:
+            self.seg_wd = self.seg_wd_host = None
+            return
+        host = np.asarray(tab, dtype=np.float32)
+        if old is not None and any(host[s] != old[s] for s in self.__dict__.get("_wd_scalar_segs", ())):
+            self._graphs = {}
+        if self.__dict__.get("seg_wd") is None:
+            self.seg_wd = torch.from_numpy(host.copy()).to(self.device)
+        else:
+            self.seg_wd.copy_(torch.from_numpy(host))
+        self.seg_wd_host = host
+
+    def set_weight_decay(self, value):
+        """Replace the decay of a compiled and built model: every variable that exclude_from_weight_decay does not name
+        decays by ``value`` (a finite float >= 0, or None) from the next step on, a replay of a recorded plan or graph
+        included -- the table is a device buffer written in place.  The optimizer descriptor takes the value too."""
+        if self.optimizer is None or self.__dict__.get("adam_t") is None:
+            raise RuntimeError("set_weight_decay: compile and build the model first")
+        wd = check_weight_decay(value)
+        self._check_weight_decay(bool(wd))
+        self.optimizer.weight_decay = wd
+        self._store_seg_wd(weight_decay_table(self.optimizer, list(self.arena.entries)))
+
+    def _wd_scalar(self, seg):
+        """the decay of one variable as the scalar argument of the encoder's fused update"""
+        self.__dict__.setdefault("_wd_scalar_segs", set()).add(seg)
+        return float(self.seg_wd_host[seg])
 
     AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
                           "schedules update the arena in slices and the row-sharded encoder finishes its update behind "
@@ -1106,17 +1174,33 @@ class ModelBase:
         be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
         clip = opt.clipnorm if opt.clipnorm is not None else 0.0
         gd = self._guard_word()
+        wd = self.__dict__.get("seg_wd")         # decoupled weight decay: the decaying entry point in the plain one's place
         self._lr_schedule_launch()
         if opt.kind == "adam":
             be.step_tick(self.adam_t, self.drop_step, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2, guard=gd)
-            be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
-                    a.sq_override, sp.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, guard=gd)
+            if wd is None:
+                be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
+                        a.sq_override, sp.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, guard=gd)
+            else:
+                be.adamw(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
+                         a.sq_override, sp.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, self.lr_dev, wd,
+                         guard=gd)
         else:
             be.step_tick(self.adam_t, self.drop_step, self.lr_dev, None, 0.0, 0.0, guard=gd)
-            be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
-                   sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+            self._sgd_update(clip, gd)
         # the tick precedes the update here: adam_t is the number of applied updates when the averaging launch starts
         self._average_update()
+
+    def _sgd_update(self, clip, gd):
+        """clip + SGD over the whole arena: tnt_sgd_f32, or tnt_sgdw_f32 under decoupled weight decay"""
+        be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
+        wd = self.__dict__.get("seg_wd")
+        if wd is None:
+            be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
+                   sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+        else:
+            be.sgdw(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
+                    sp.nspan, self.lr_dev, opt.momentum, clip, wd, guard=gd)
 
     def _average_update(self):
         """The averaging launch of a step (tnt_weight_average_f32 over the whole arena): the step's last launch, behind its
@@ -1152,6 +1236,7 @@ class ModelBase:
         clip = opt.clipnorm if opt.clipnorm is not None else 0.0
         gd = self._guard_word()
         adam = opt.kind == "adam"
+        wd = self.__dict__.get("seg_wd")         # decoupled weight decay: every update launch below in its decaying form
         enc = self.__dict__.pop("_enc_fused", None)
         # lr_dev is first read by the norm launch that carries the lr job, else by the finalize launch: the schedule goes here
         self._lr_schedule_launch()
@@ -1205,9 +1290,15 @@ class ModelBase:
         if fin:
             if enc is not None:        # the encoder kernel first: it reads the step counter's lr_t like the Adam launch, which ticks
                 sl = slice(e.off, e.off + e.size)
-                be.dense_dw_adam_fin(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.partial, sp.first_host[e.seg],
-                                     sp.first_host[e.seg + 1], a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1,
-                                     opt.beta_2, opt.epsilon, clip, N, E, rows, ldx, guard=gd)
+                if wd is None:
+                    be.dense_dw_adam_fin(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.partial, sp.first_host[e.seg],
+                                         sp.first_host[e.seg + 1], a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1,
+                                         opt.beta_2, opt.epsilon, clip, N, E, rows, ldx, guard=gd)
+                else:
+                    be.dense_dw_adamw_fin(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.partial,
+                                          sp.first_host[e.seg], sp.first_host[e.seg + 1], a.sq_override[e.seg:e.seg + 1],
+                                          self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, N, E, rows, ldx, self.lr_dev,
+                                          self._wd_scalar(e.seg), guard=gd)
             if "extra_part" in kw:
                 kw["extra_seg"] = self.emb_seg
             arrive = self.__dict__.get("_fin_arrive")
@@ -1220,8 +1311,12 @@ class ModelBase:
                 descs[ck] = be.finalize_desc(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, arrive,
                                              adam_t=self.adam_t, drop_step=self.drop_step, lr=self.lr_dev, lr_t=self.lr_t_dev,
                                              beta1=opt.beta_1, beta2=opt.beta_2, guard=gd, **kw)
-            be.adam_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
-                        a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], **self._ring_args())
+            if wd is None:
+                be.adam_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
+                            a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], **self._ring_args())
+            else:                      # the descriptor's lr is lr_dev: the decay reads the step's rate through it
+                be.adamw_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
+                             a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], wd, **self._ring_args())
             # the counters tick when the last workgroup of the Adam launch arrives, behind the encoder's update: adam_t is
             # the number of applied updates when the averaging launch starts
             self._average_update()
@@ -1230,17 +1325,27 @@ class ModelBase:
                          drop_step=self.drop_step, lr=self.lr_dev, lr_t=self.lr_t_dev if adam else None,
                          beta1=opt.beta_1 if adam else 0.0, beta2=opt.beta_2 if adam else 0.0, guard=gd, **kw)
         if adam:
-            be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
-                    a.sq, a.sq_override, sp.nspan - s1, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                    guard=gd, **(self._ring_args() if sp.nspan - s1 > 0 else {}))
+            ring = self._ring_args() if sp.nspan - s1 > 0 else {}
+            if wd is None:
+                be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
+                        a.sq, a.sq_override, sp.nspan - s1, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
+                        guard=gd, **ring)
+            else:
+                be.adamw(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
+                         a.sq, a.sq_override, sp.nspan - s1, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
+                         self.lr_dev, wd, guard=gd, **ring)
             if enc is not None:
                 sl = slice(e.off, e.off + e.size)
-                be.dense_dw_adam(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.sq[e.seg:e.seg + 1],
-                                 a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                                 N, E, rows, ldx, guard=gd)
+                if wd is None:
+                    be.dense_dw_adam(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.sq[e.seg:e.seg + 1],
+                                     a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
+                                     N, E, rows, ldx, guard=gd)
+                else:
+                    be.dense_dw_adamw(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.sq[e.seg:e.seg + 1],
+                                      a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
+                                      N, E, rows, ldx, self.lr_dev, self._wd_scalar(e.seg), guard=gd)
         else:
-            be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
-                   sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+            self._sgd_update(clip, gd)
         # the finalize launch ticked in front of the update launches: adam_t is the number of applied updates here too
         self._average_update()
 
@@ -1558,6 +1663,9 @@ class ModelBase:
         optimizer.apply_gradients -- the (commented-out) call of lc_NIC.py:388.  clip_factor=None switches it off."""
         if clip_factor is not None and int(self.__dict__.get("dp_world", 1) or 1) > 1:
             raise NotImplementedError("adaptive gradient clipping is not supported under data parallel (dp.attach)")
+        if clip_factor is not None and (self.__dict__.get("seg_wd") is not None or
+                                        check_weight_decay(getattr(self.optimizer, "weight_decay", None))):
+            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
         self._graphs = {}
 

@@ -462,6 +462,12 @@ class HipBackend:
         self._call(self.lib.tnt_dense_dw_adam_f32, "tnt_dense_dw_adam_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
                    _p(sq), _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, self._s())
 
+    def dense_dw_adamw(self, x, dpre, theta, m, v, l2, sq, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, N, E, Bk, ldx, lr,
+                       wd, guard=None):
+        """dense_dw_adam with decoupled weight decay ``wd`` at the device learning rate ``lr`` (tnt_dense_dw_adamw_f32)"""
+        self._call(self.lib.tnt_dense_dw_adamw_f32, "tnt_dense_dw_adamw_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
+                   _p(sq), _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, _p(lr), wd, self._s())
+
     def dense_dw_skinny(self, x, dpre, dw, N, E, Bk, ldx):
         self._call(self.lib.tnt_dense_dw_skinny_f32, "tnt_dense_dw_skinny_f32", _p(x), _p(dpre), _p(dw), N, E, Bk, ldx, self._s())
 
@@ -628,6 +634,21 @@ class HipBackend:
                                         _p(seg_l2), _p(sq), _p(sq_override), nspan, lr, _p(lr_dev), momentum,
                                         clipnorm, _p(guard), self._s())
 
+    def adamw(self, theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev,
+              beta1, beta2, eps, clipnorm, lr, seg_wd, guard=None, met=None, ring=None, ring_t=None):
+        """adam with decoupled weight decay (tnt_adamw_ring_f32; definition in include/tnt_hip.h): ``lr`` the device learning
+        rate, ``seg_wd`` one float per variable"""
+        self._call(self.lib.tnt_adamw_ring_f32, "tnt_adamw_ring_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(seg_l2), _p(sq), _p(sq_override), nspan, lr_t, _p(lr_t_dev), beta1, beta2, eps, clipnorm,
+                   _p(guard), _p(met), met.numel() if met is not None else 0, _p(ring), ring.shape[0] if ring is not None else 0,
+                   _p(ring_t), _p(lr), _p(seg_wd), self._s())
+
+    def sgdw(self, theta, mom, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_dev, momentum, clipnorm,
+             seg_wd, guard=None):
+        """sgd with decoupled weight decay (tnt_sgdw_f32): the learning rate comes from the device only"""
+        self._call(self.lib.tnt_sgdw_f32, "tnt_sgdw_f32", _p(theta), _p(mom), _p(grad), _p(span_seg), _p(span_off), _p(span_len),
+                   _p(seg_l2), _p(sq), _p(sq_override), nspan, _p(lr_dev), momentum, clipnorm, _p(guard), _p(seg_wd), self._s())
+
     def sam(self, theta, grad, ew, span_seg, span_off, span_len, seg_l2, sq, nseg, nspan, rho, mode, sq_override=None):
         self._call(self.lib.tnt_sam_f32, "tnt_sam_f32", _p(theta), _p(grad), _p(ew), _p(span_seg), _p(span_off), _p(span_len),
                                         _p(seg_l2), _p(sq), _p(sq_override), nseg, nspan, rho, mode, self._s())
@@ -659,6 +680,14 @@ class HipBackend:
                    _p(span_len), _p(sq_override), nspan, eps, clipnorm, _ct.addressof(fin), _p(met), met.numel() if met is not None else 0,
                    _p(ring), ring.shape[0] if ring is not None else 0, _p(ring_t), self._s())
 
+    def adamw_fin(self, theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, seg_wd, met=None,
+                  ring=None, ring_t=None):
+        """adam_fin with decoupled weight decay (tnt_adamw_fin_f32): ``seg_wd`` one float per variable, the learning rate is
+        the descriptor's ``lr``"""
+        self._call(self.lib.tnt_adamw_fin_f32, "tnt_adamw_fin_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(sq_override), nspan, eps, clipnorm, _ct.addressof(fin), _p(met), met.numel() if met is not None else 0,
+                   _p(ring), ring.shape[0] if ring is not None else 0, _p(ring_t), _p(seg_wd), self._s())
+
     def span_sqnorm_lr(self, theta, grad, span_seg, span_off, span_len, seg_l2, partial, nspan, adam_t, lr, lr_t, beta1, beta2,
                        skip=None):
         """``skip`` = the sq_override table (or None): see tnt_span_sqnorm_lr_f32"""
@@ -669,6 +698,13 @@ class HipBackend:
                           Bk, ldx, guard=None):
         self._call(self.lib.tnt_dense_dw_adam_fin_f32, "tnt_dense_dw_adam_fin_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
                    _p(partial), k0, k1, _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, self._s())
+
+    def dense_dw_adamw_fin(self, x, dpre, theta, m, v, l2, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, N, E,
+                           Bk, ldx, lr, wd, guard=None):
+        """dense_dw_adam_fin with decoupled weight decay ``wd`` at the device learning rate ``lr`` (tnt_dense_dw_adamw_fin_f32)"""
+        self._call(self.lib.tnt_dense_dw_adamw_fin_f32, "tnt_dense_dw_adamw_fin_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
+                   _p(partial), k0, k1, _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, _p(lr), wd,
+                   self._s())
 
     def step_finalize(self, partial, seg_first, seg_l2, sq, wsq, l2_out, nseg, x0=None, out0=None, x1=None, out1=None, n=0,
                       scale=1.0, extra_part=None, extra=None, n_extra=0, ids_src=None, ids_dst=None, n_ids=0, adam_t=None,

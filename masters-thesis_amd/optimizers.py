@@ -29,33 +29,108 @@ def optimizer_schedule(optimizer):
     return lr if isinstance(lr, LearningRateSchedule) else None
 
 
-class Adam(_LearningRate):
-    """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm) -- main.py:97.
+def check_weight_decay(wd):
+    """None, or the value as a float; ValueError unless it is a finite number >= 0 (bool, str and NaN refused)"""
+    import numbers
+    if wd is None:
+        return None
+    if isinstance(wd, bool) or not isinstance(wd, numbers.Real):
+        raise ValueError(f"weight_decay must be None or a finite number >= 0, got {wd!r}")
+    v = float(wd)
+    if not 0.0 <= v < float("inf"):
+        raise ValueError(f"weight_decay must be finite and >= 0, got {wd!r}")
+    return v
+
+
+class _WeightDecay:
+    """``weight_decay`` of a descriptor (keras >= 2.11: the argument of every optimizer, and AdamW): decoupled weight decay,
+    every update also shrinks a decayed variable by lr * weight_decay * theta outside the gradient path (definition:
+    tnt_adamw_ring_f32 in include/tnt_hip.h), with lr the step's learning rate, a schedule's value included.  None or 0:
+    no decay, and the update launches are the plain ones.
+
+    Keras's rule: EVERY variable the optimizer updates is decayed unless it is excluded.  To leave the biases and the
+    normalisation parameters alone, as is usual, call
+    ``optimizer.exclude_from_weight_decay(var_names=["bias", "gamma", "beta"])`` before the model builds its optimizer
+    state (compile of a built model, or the first step).  The model's variable names: ``model.trainable_names()``.
+
+    Single device only, like weight averaging: dp.attach / a model with a grad_sync, train_step_sam and enable_agc()
+    refuse a decaying optimizer with NotImplementedError."""
+
+    @property
+    def weight_decay(self):
+        return self._weight_decay
+
+    @weight_decay.setter
+    def weight_decay(self, v):
+        self._weight_decay = check_weight_decay(v)
+
+    def exclude_from_weight_decay(self, var_list=None, var_names=None):
+        """keras's Optimizer.exclude_from_weight_decay: ``var_list`` holds exact variable names, ``var_names`` substrings
+        matched against the variable names; each call replaces the earlier exclusions.  Raises once a model has built its
+        optimizer state from this descriptor, as keras does once the optimizer is built."""
+        if getattr(self, "_wd_built", False):
+            raise ValueError("exclude_from_weight_decay() must be called before the model builds its optimizer state")
+        for what, v in (("var_list", var_list), ("var_names", var_names)):
+            if v is not None and (isinstance(v, str) or not all(isinstance(n, str) for n in v)):
+                raise ValueError(f"{what} must be a list of variable names, got {v!r}")
+        self._wd_exclude_exact = frozenset(var_list or ())
+        self._wd_exclude_sub = tuple(var_names or ())
+
+
+def weight_decay_table(optimizer, names):
+    """one decay per variable name, in order: the descriptor's ``weight_decay`` (a wrapper's: the wrapped descriptor's), 0
+    for a variable that exclude_from_weight_decay names; None when nothing decays"""
+    inner = getattr(optimizer, "_optimizer", optimizer)
+    wd = check_weight_decay(getattr(inner, "weight_decay", None))
+    if not wd:
+        return None
+    exact, sub = getattr(inner, "_wd_exclude_exact", frozenset()), getattr(inner, "_wd_exclude_sub", ())
+    tab = [0.0 if (n in exact or any(s in n for s in sub)) else wd for n in names]
+    return tab if any(tab) else None
+
+
+class Adam(_LearningRate, _WeightDecay):
+    """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay) -- main.py:97.
     ``learning_rate``: a float or an ``optimizers.schedules`` object.
     ``clipnorm`` is per variable; None disables it (the TF<=2.3 behaviour of a
-    custom tape.gradient -> apply_gradients step)."""
+    custom tape.gradient -> apply_gradients step).
+    ``weight_decay``: decoupled weight decay, see ``_WeightDecay``; None or 0 is plain Adam."""
 
     kind = "adam"
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, **kw):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, weight_decay=None, **kw):
         self.lr = kw.pop("lr", learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self.weight_decay = weight_decay
         self.iterations = 0
 
 
-class SGD(_LearningRate):
-    """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False) -- main.py:100-102.  ``learning_rate``: a float
-    or an ``optimizers.schedules`` object."""
+class AdamW(Adam):
+    """tf.keras.optimizers.AdamW(learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+    clipnorm): Adam with decoupled weight decay (Loshchilov & Hutter 2019), the rule of torch.optim.AdamW.  Every
+    variable is decayed unless ``exclude_from_weight_decay`` names it (see ``_WeightDecay``)."""
+
+    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, **kw):
+        if weight_decay is None:
+            raise ValueError("AdamW needs a weight_decay; Adam is the optimizer without one")
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay, **kw)
+
+
+class SGD(_LearningRate, _WeightDecay):
+    """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False, weight_decay) -- main.py:100-102.
+    ``learning_rate``: a float or an ``optimizers.schedules`` object.  ``weight_decay``: decoupled weight decay, see
+    ``_WeightDecay``; None or 0 is plain SGD."""
 
     kind = "sgd"
 
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, **kw):
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, weight_decay=None, **kw):
         if nesterov:
             raise NotImplementedError("nesterov momentum is not used by the reference path")
         self.lr = kw.pop("lr", learning_rate)
         self.momentum = float(momentum)
         self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self.weight_decay = weight_decay
         self.iterations = 0
 
 
@@ -117,6 +192,10 @@ class _AveragedOptimizer:
     clipnorm = _delegate("clipnorm")
     momentum = _delegate("momentum")
     iterations = _delegate("iterations")
+    weight_decay = _delegate("weight_decay")
+
+    def exclude_from_weight_decay(self, var_list=None, var_names=None):
+        self._optimizer.exclude_from_weight_decay(var_list=var_list, var_names=var_names)
 
     def __init__(self, optimizer, average):
         if getattr(optimizer, "average", None) is not None:
