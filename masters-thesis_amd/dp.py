@@ -289,7 +289,7 @@ class PipelinedDenseSync:
         """the row-sharded encoder update applies: opted in, equal 16-byte-aligned shards, Adam, no adaptive clipping"""
         opt = m.optimizer
         return bool(self.shard_encoder and not self.split_update and m.N % self.world == 0 and (m.N // self.world) % 4 == 0
-                    and opt is not None and opt.kind == "adam" and not m.__dict__.get("agc")
+                    and opt is not None and opt.kind == "adam" and not m.agc
                     and m.arena.entries["dense_img/kernel"].seg == 0 and hasattr(m.be, "step_finalize"))
 
     def __call__(self, model):          # generic fallback (models without a pipelined schedule)
@@ -391,11 +391,8 @@ def _segment_a(m, B, T, defer_totals):
     the step's loss / accuracy (/ attention-metric) totals are not summed by a launch of their own behind the loss kernel but
     by the finalize work of the update launch at the end of the step (ModelBase._update_fused), as in the single-process step.
     Only this segment defers: the Embedding backward and the encoder update keep their data-parallel forms."""
-    m._defer_sum2 = bool(defer_totals)
-    try:
+    with m._deferring(defer_totals):
         m._forward(B, T, True); m._loss_metrics(B, T, True); m._bwd_head(B, T)
-    finally:
-        m._defer_sum2 = False
 
 
 def _sparse_norm_slot(model):
@@ -431,14 +428,14 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if getattr(model, "self_critical", None) is not None:
         # nic.NIC(self_critical=...): the step's host round trip has no data-parallel schedule
         raise NotImplementedError("data parallel self-critical training is not supported: train it on one device")
-    if model.__dict__.get("average") is not None:
+    if model.average is not None:
         # compile(optimizers.MovingAverage / SWA): the averaging launch has no place in the data-parallel schedules
         raise NotImplementedError(model.AVERAGE_DP_REFUSAL)
-    if model.__dict__.get("seg_wd") is not None or getattr(model.optimizer, "weight_decay", None):
+    if model.seg_wd is not None or getattr(model.optimizer, "weight_decay", None):
         # compile(AdamW / weight_decay=): the data-parallel update launches (slices, the row-sharded encoder) do not decay
         raise NotImplementedError(model.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
                                                                     "row-sharded encoder update included)"))
-    if model.__dict__.get("loss_normalise", "count") == "weights":
+    if model.loss_normalise == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)
     if model.__dict__.get("attention_coverage") is not None:
@@ -446,7 +443,7 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
         raise NotImplementedError(model.COVERAGE_DP_REFUSAL)
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
-    if model.__dict__.get("agc") and world > 1:
+    if model.agc and world > 1:
         # agc.py:25-30 clips the Embedding by the column norms of its UN-merged IndexedSlices rows; across replicas those
         # are per-rank partial sums that would have to be all-reduced before every rank scales the summed gradient, and
         # the pipelined schedules update slice by slice without an AGC pass.  Not built: refuse instead of training wrong.

@@ -580,15 +580,15 @@ class NIC(ModelBase):
         self._hs_used = hs
         self._head_inter(hs, self.inter, n, self.ipre)
         inter = self.inter
-        self._metric_parts_ready = False
+        self._tail.metric_parts_ready = False
         if training and self.r_out > 0:
             npart = be.attention_metric_parts(T, self.R) if hasattr(be, "dropout_metric") else 0
-            if (self.S == 1 and self.__dict__.get("_defer_sum2") and getattr(self, "fuse_metric_rider", True) and H % 4 == 0
+            if (self.S == 1 and self._tail.deferring and getattr(self, "fuse_metric_rider", True) and H % 4 == 0
                     and 0 < npart <= self.metric_part.numel()):
                 # the attention metric's partials (:365-367) ride in this launch: alpha is complete behind the chain
                 be.dropout_metric(self.inter, self.inter_d, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds, self.alpha,
                                   self.metric_part, T, B, self.R)
-                self._metric_parts_ready = True
+                self._tail.metric_parts_ready = True
             else:
                 be.dropout(self.inter, self.inter_d, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds)
             inter = self.inter_d
@@ -692,7 +692,7 @@ class NIC(ModelBase):
         self._hs_used = self.Hd if self.r_lstm > 0 else self.Hs[1:].view(T * B, U)
         self._inter_used = self.inter_d if self.r_out > 0 else self.inter
         self._out_dropped = False
-        self._metric_parts_ready = False           # the attention metric: _loss_metrics, behind the loop
+        self._tail.metric_parts_ready = False      # the attention metric: _loss_metrics, behind the loop
 
     def _forward_naive(self, B, T, training):
         """lc_NIC.call_naive_attention (lc_NIC.py:175-221): the decoder fed its own greedy predictions.  Per step: attention
@@ -731,34 +731,21 @@ class NIC(ModelBase):
         self._hs_used = self.Hd if (r_lo > 0 or r_o > 0) else self.Hs[1:].view(T * B, U)
         self._inter_used = self.inter
         self._out_dropped = False
-        self._metric_parts_ready = False
+        self._tail.metric_parts_ready = False
 
     def _loss_metrics(self, B, T, want_grad):
         be = self.be
         n = T * B
-        eps = self.label_smoothing
-        if eps > 0:         # keras smooths the evaluation loss too
-            be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
-                                  self.logits if want_grad else None, n, self.V, self.ldV,
-                                  1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
-        elif self.unlikelihood > 0:
-            self._loss_unlikely(B, T, want_grad)
-        elif self._token_weights_on():
-            self._loss_weighted(B, T, want_grad)
-        elif want_grad:
-            be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V, self.ldV,
-                           1.0 / (n * self.dp_world))
-        else:
-            be.softmax_cce(self.logits, self.tgt, self.logits, self.loss_row, self.corr_row, None, n, self.V, self.ldV,
-                           0.0)
+        self._head_loss(B, T, want_grad)
         self._sum2(self.loss_row, self.met[0:1], self.corr_row, self.met[1:2], n, 1.0 / n)
         if self.S == 1:
             npart = be.attention_metric_parts(T, self.R) if hasattr(be, "attention_metric_parts") else 0
-            if self.__dict__.get("_defer_sum2") and want_grad and 0 < npart <= self.metric_part.numel():
+            t = self._tail
+            if t.deferring and want_grad and 0 < npart <= self.metric_part.numel():
                 # fused single-process step: partials only, their total rides in the step-finalize launch
-                if not self.__dict__.get("_metric_parts_ready"):
+                if not t.metric_parts_ready:
                     be.attention_metric(self.alpha, None, self.metric_part, T, B, self.R)
-                self._metric_deferred = (self.metric_part, self.met[3:4], npart, 1.0 / (T * self.R))
+                t.x2, t.out2, t.n2, t.scale2 = self.metric_part, self.met[3:4], npart, 1.0 / (T * self.R)
             else:
                 be.attention_metric(self.alpha, self.met[3:4], self.metric_part, T, B, self.R)              # :365-367
         else:       # per-subject loss / accuracy / attention metric (ms2_NIC.py:324-372)
@@ -1118,7 +1105,7 @@ class NIC(ModelBase):
                 tag, k = chr(ord("A") + q), 8 + 4 * q
                 out[f"loss{tag}"], out[f"accuracy{tag}"], out[f"attention{tag}"] = m[k], m[k + 1], m[k + 2]
         if with_lr:
-            if self.__dict__.get("lr_schedule") is not None:
+            if self.lr_schedule is not None:
                 self._lr_metric(out)                                          # computed on the device: read from there
             else:
                 out["lr"] = torch.tensor(self._lr_host, dtype=torch.float32)  # host-set (ModelBase._sync_lr): no device copy

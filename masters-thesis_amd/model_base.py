@@ -10,6 +10,7 @@ launches and owns buffers; it contains no arithmetic of the hot path.
 import time
 from collections import OrderedDict
 from contextlib import contextmanager, nullcontext
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -860,6 +861,51 @@ class Metrics(dict):
         return out
 
 
+class EncGram(NamedTuple):
+    """By-products of nic.NIC's training forward (tnt_dense_fwd_stream_gram_f32) from which the encoder kernel's clip norm
+    follows without a pass over its gradient: the arguments of dense_gram_norm under their names there."""
+    pre: torch.Tensor
+    bias: torch.Tensor
+    gx: torch.Tensor
+    nsplit: int
+    w2: torch.Tensor
+    nw2: int
+
+
+class EncUpdate(NamedTuple):
+    """nic.NIC._bwd_enc's hand-off to the fused update: the encoder kernel ``name`` never has its gradient X^T dpre
+    written, the update launches form it from ``x`` [rows][ldx] and ``dpre`` [rows][E] themselves."""
+    name: str
+    x: torch.Tensor
+    dpre: torch.Tensor
+    rows: int
+    N: int
+    E: int
+    ldx: int
+    gram: Optional[EncGram] = None
+
+
+class StepTail:
+    """What the launches of a fused step leave to its update (ModelBase._update_fused) instead of issuing a launch of their
+    own.  ``deferring`` is on inside ModelBase._deferring(); the producers read it and set the fields, which are named
+    after the finalize_desc / step_finalize keywords they become (None: not handed over)."""
+    FINALIZE = ("x0", "out0", "x1", "out1", "n", "scale",           # the loss / accuracy totals (ModelBase._sum2)
+                "x2", "out2", "n2", "scale2",                       # the attention metric's total (lc_nic.NIC._loss_metrics)
+                "extra_part", "extra", "n_extra",                   # the sparse Embedding backward's norm partials ...
+                "ids_src", "ids_dst", "n_ids")                      # ... and this step's ids, handed on as prev_ids
+
+    def __init__(self, deferring=False):
+        self.deferring = deferring
+        self.metric_parts_ready = False     # lc_nic.NIC: the forward's Dropout launch left the attention metric's partials
+        self.enc = None                     # an EncUpdate (nic.NIC._bwd_enc)
+        for k in self.FINALIZE:
+            setattr(self, k, None)
+
+    def finalize_kw(self):
+        """the keywords of the step's finalize work, whichever launch carries it"""
+        return {k: getattr(self, k) for k in self.FINALIZE if getattr(self, k) is not None}
+
+
 class ModelBase:
     GUARD = 7       # slot of ``met`` that carries the device guard word of the step (see Metrics)
     METRIC_RING = 1024      # rows of the metrics ring: a step's Metrics stay readable for this many further training steps
@@ -889,6 +935,13 @@ class ModelBase:
         self.seg_wd_host = None             # the same table on the host (the encoder's fused update takes its entry as a scalar)
         self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
         self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
+        self.agc = None                     # adaptive gradient clipping (enable_agc): (clip_factor, eps), or None
+        self.adam_t = None                  # the device counter of applied updates; exists once the optimizer state does
+        self._swapped = False               # the weight average sits in the weights (swap_weights)
+        self._wd_scalar_segs = set()        # variables whose update takes its decay as a scalar argument (_wd_scalar)
+        self._fin_arrive = None             # arrival counters of the update launch that carries the finalize work
+        self._fin_descs = {}                # its descriptors (finalize_desc), one per distinct argument set
+        self._tail = StepTail()             # what a fused step's launches leave to its update (_deferring, _update_fused)
         self.built = False
         self.stop_training = False
         self._graphs = {}
@@ -923,25 +976,18 @@ class ModelBase:
         self._check_weight_decay(bool(check_weight_decay(getattr(optimizer, "weight_decay", None))))
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
-        # fixed here, not read per step: the head launch sits inside captured graphs
-        if eps != self.label_smoothing or alpha != self.__dict__.get("unlikelihood", 0.0):
+        # Fixed here, not read per step: the head launch sits inside captured graphs, with its smoothing, alpha, gamma and
+        # mode as arguments.  The averaging launch sits inside the same plans / graphs, and its settings are launch
+        # arguments; so does the schedule's launch (tnt_lr_schedule_f32), whose parameters live in a device buffer of the
+        # model's.  A change of any of them drops the recordings
+        recorded = (eps, alpha, gamma, mode, avg, optimizer_schedule(self.optimizer))
+        if recorded != (self.label_smoothing, self.unlikelihood, self.focal_gamma, self.loss_normalise, self.average,
+                        self.lr_schedule):
             self._graphs = {}
-        self.label_smoothing = eps
-        self.unlikelihood = alpha
-        # so are gamma, the mode and whether there are weights; the weights themselves are the contents of a device buffer
-        if gamma != self.__dict__.get("focal_gamma", 0.0) or mode != self.__dict__.get("loss_normalise", "count"):
-            self._graphs = {}
-        self.focal_gamma, self.loss_normalise = gamma, mode
+        (self.label_smoothing, self.unlikelihood, self.focal_gamma, self.loss_normalise, self.average,
+         self.lr_schedule) = recorded
+        # ... and so does whether there are token weights; the weights themselves are the contents of a device buffer
         self._store_class_weight(cw)
-        # the averaging launch sits inside the same plans / graphs, and its settings are launch arguments
-        if avg != self.__dict__.get("average"):
-            self._graphs = {}
-        self.average = avg
-        # so does the schedule's launch (tnt_lr_schedule_f32); its parameters live in a device buffer of the model's
-        sched = optimizer_schedule(self.optimizer)
-        if sched != self.__dict__.get("lr_schedule"):
-            self._graphs = {}
-        self.lr_schedule = sched
         if self.built:
             self._init_optimizer_state()
 
@@ -960,7 +1006,7 @@ class ModelBase:
         if getattr(self, "self_critical", None) is not None:
             raise ValueError(f"{what} does not apply to a self_critical model: its loss is the advantage-weighted "
                              "tnt_scst_cce_f32, not the compile loss")
-        if mode == "weights" and (self.grad_sync is not None or int(self.__dict__.get("dp_world", 1) or 1) > 1):
+        if mode == "weights" and (self.grad_sync is not None or self.dp_world > 1):
             raise NotImplementedError(self.WEIGHTS_DP_REFUSAL)
         if mode == "weights" and int(getattr(self, "S", 1)) > 1:
             raise NotImplementedError("normalise=\"weights\" with n_subjects > 1 is not implemented: the per-subject metrics "
@@ -979,13 +1025,13 @@ class ModelBase:
         """cw: None or a float32 array of V weights.  The device buffer is written in place where it exists, so a recorded
         plan or a captured graph that holds its address reads the new weights; only a change between no weights and
         weights changes the launch and drops the recordings."""
-        if (cw is None) != (self.__dict__.get("class_weight") is None):
+        if (cw is None) != (self.class_weight is None):
             self._graphs = {}
         if cw is None:
             self.class_weight, self.cw_dev = None, None
             return
         host = torch.from_numpy(np.ascontiguousarray(cw, dtype=np.float32))
-        if self.__dict__.get("cw_dev") is None:
+        if self.cw_dev is None:
             self.cw_dev = host.to(self.device)
         else:
             self.cw_dev.copy_(host)
@@ -998,25 +1044,27 @@ class ModelBase:
                                   self.unlikelihood)
         self._store_class_weight(None if class_weight is None else check_class_weight(class_weight, self.V))
 
-    def _loss_weighted(self, B, T, want_grad):
-        """the head launch of _loss_metrics under token weights / the focal factor / normalise="weights", training form
-        (dlogits in place) or evaluation form (probabilities in place, gscale 0): the same objective in both, as under
-        label smoothing"""
-        n = T * B
-        self.be.softmax_cce_weighted(self.logits, self.tgt, self.cw_dev, None if want_grad else self.logits, self.loss_row,
-                                     self.corr_row, self.logits if want_grad else None, n, self.V, self.ldV,
-                                     1.0 / (n * self.dp_world) if want_grad else 0.0, self.focal_gamma,
-                                     self.loss_normalise == "weights")
-
-    def _loss_unlikely(self, B, T, want_grad):
-        """the head launch of _loss_metrics under unlikelihood > 0, training form (dlogits in place) or evaluation form
-        (probabilities in place, gscale 0): the same objective in both, as under label smoothing.  _stage_batch has refused
-        a caption that is too long before any launch of the step."""
-        assert T <= self.UNLIKELIHOOD_MAX_T
-        n = T * B
-        self.be.softmax_cce_unlikely(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
-                                     self.logits if want_grad else None, B, T, self.V, self.ldV,
-                                     1.0 / (n * self.dp_world) if want_grad else 0.0, self.unlikelihood)
+    def _head_loss(self, B, T, want_grad):
+        """The head launch of _loss_metrics over the T * B position-ordered rows, chosen by the compile loss: label
+        smoothing, unlikelihood, token weights / the focal factor / normalise="weights", or the plain softmax-CCE.  Each in
+        its training form (dlogits in place, scaled for the mean over the global batch) or its evaluation form
+        (probabilities in place, gscale 0): the same objective in both -- keras smooths the evaluation loss too."""
+        be, n = self.be, T * B
+        probs, dlogits = (None, self.logits) if want_grad else (self.logits, None)
+        gscale = 1.0 / (n * self.dp_world) if want_grad else 0.0
+        if self.label_smoothing > 0:
+            be.softmax_cce_smooth(self.logits, self.tgt, probs, self.loss_row, self.corr_row, dlogits, n, self.V, self.ldV,
+                                  gscale, self.label_smoothing)
+        elif self.unlikelihood > 0:
+            # _stage_batch has refused a caption that is too long before any launch of the step
+            assert T <= self.UNLIKELIHOOD_MAX_T
+            be.softmax_cce_unlikely(self.logits, self.tgt, probs, self.loss_row, self.corr_row, dlogits, B, T, self.V,
+                                    self.ldV, gscale, self.unlikelihood)
+        elif self._token_weights_on():
+            be.softmax_cce_weighted(self.logits, self.tgt, self.cw_dev, probs, self.loss_row, self.corr_row, dlogits, n,
+                                    self.V, self.ldV, gscale, self.focal_gamma, self.loss_normalise == "weights")
+        else:
+            be.softmax_cce(self.logits, self.tgt, probs, self.loss_row, self.corr_row, dlogits, n, self.V, self.ldV, gscale)
 
     @property
     def be(self):
@@ -1030,7 +1078,7 @@ class ModelBase:
         self.opt_m = torch.zeros_like(a.theta)
         self.opt_v = torch.zeros_like(a.theta) if self.optimizer.kind == "adam" else None
         self.adam_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        sched = self.__dict__.get("lr_schedule")
+        sched = self.lr_schedule
         # with a schedule the host never writes lr_dev again: every step's tnt_lr_schedule_f32 launch does, from adam_t
         self.lr_dev = torch.tensor([self.optimizer.lr if sched is None else sched(0)], dtype=torch.float32, device=self.device)
         self.lr_t_dev = self._f(1)
@@ -1039,7 +1087,7 @@ class ModelBase:
         # the weight average (optimizers.MovingAverage / SWA): one more slot over the whole arena, padding included (zero in
         # both buffers, and it stays zero).  The first averaging launch overwrites it with the parameters after update
         # max(start_step, 1); until then it holds the initial ones
-        self.opt_avg = a.theta.clone() if self.__dict__.get("average") is not None else None
+        self.opt_avg = a.theta.clone() if self.average is not None else None
         self._swapped = False
         # decoupled weight decay: the per-variable table from the descriptor and its exclusions, which are final from here
         # on (keras: exclude_from_weight_decay raises once the optimizer is built)
@@ -1059,14 +1107,14 @@ class ModelBase:
         adaptive gradient clipping; train_step_sam and dp.attach refuse on their side"""
         if not on:
             return
-        if self.grad_sync is not None or int(self.__dict__.get("dp_world", 1) or 1) > 1:
+        if self.grad_sync is not None or self.dp_world > 1:
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, "
                                                                       "the row-sharded encoder update included)"))
-        if self.__dict__.get("agc"):
+        if self.agc:
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
 
     def _weight_decay_refuse(self, what):
-        if self.__dict__.get("seg_wd") is not None:
+        if self.seg_wd is not None:
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what=what))
 
     def _store_seg_wd(self, tab):
@@ -1076,16 +1124,16 @@ class ModelBase:
         variable whose update takes its decay as a scalar argument (the encoder's fused update)."""
         if tab is not None and not any(tab):
             tab = None
-        old = self.__dict__.get("seg_wd_host")
+        old = self.seg_wd_host
         if (tab is None) != (old is None):
             self._graphs = {}
         if tab is None:
             self.seg_wd = self.seg_wd_host = None
             return
         host = np.asarray(tab, dtype=np.float32)
-        if old is not None and any(host[s] != old[s] for s in self.__dict__.get("_wd_scalar_segs", ())):
+        if old is not None and any(host[s] != old[s] for s in self._wd_scalar_segs):
             self._graphs = {}
-        if self.__dict__.get("seg_wd") is None:
+        if self.seg_wd is None:
             self.seg_wd = torch.from_numpy(host.copy()).to(self.device)
         else:
             self.seg_wd.copy_(torch.from_numpy(host))
@@ -1095,7 +1143,7 @@ class ModelBase:
         """Replace the decay of a compiled and built model: every variable that exclude_from_weight_decay does not name
         decays by ``value`` (a finite float >= 0, or None) from the next step on, a replay of a recorded plan or graph
         included -- the table is a device buffer written in place.  The optimizer descriptor takes the value too."""
-        if self.optimizer is None or self.__dict__.get("adam_t") is None:
+        if self.optimizer is None or self.adam_t is None:
             raise RuntimeError("set_weight_decay: compile and build the model first")
         wd = check_weight_decay(value)
         self._check_weight_decay(bool(wd))
@@ -1104,7 +1152,7 @@ class ModelBase:
 
     def _wd_scalar(self, seg):
         """the decay of one variable as the scalar argument of the encoder's fused update"""
-        self.__dict__.setdefault("_wd_scalar_segs", set()).add(seg)
+        self._wd_scalar_segs.add(seg)
         return float(self.seg_wd_host[seg])
 
     AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
@@ -1115,11 +1163,11 @@ class ModelBase:
     def _sync_lr(self):
         """in front of the update of every training step: the host-set learning rate to the device -- and the refusal of a
         step while the average sits in the weights (swap_weights / averaged_weights)"""
-        if self.__dict__.get("_swapped"):
+        if self._swapped:
             raise RuntimeError("the averaged weights are swapped in (swap_weights / averaged_weights): a training step would "
                                "train the average and average the raw weights.  Swap back first")
         sched = optimizer_schedule(self.optimizer)
-        if sched != self.__dict__.get("lr_schedule"):
+        if sched != self.lr_schedule:
             # optimizer.learning_rate was assigned since compile (a float in place of the schedule, or another schedule):
             # the step's launch sequence changes, so it is recorded again
             self._set_lr_schedule(sched)
@@ -1142,13 +1190,13 @@ class ModelBase:
         far), inside the same recorded plan / graph and in front of the step's first launch that reads lr_dev.  No guard: a
         step whose guard word tripped leaves adam_t, so the next step computes the same value.  Nothing with a float
         learning rate."""
-        if self.__dict__.get("lr_schedule") is not None:
+        if self.lr_schedule is not None:
             self.be.lr_schedule(self.adam_t, self.lr_params, self.lr_dev)
 
     def _lr_metric(self, out):
         """with a schedule: the ``lr`` entry of a training step's metrics is the float32 its update used, read from the
         device with the other metrics (a copy of lr_dev behind the step)"""
-        if self.__dict__.get("lr_schedule") is not None:
+        if self.lr_schedule is not None:
             out["lr"] = self.lr_dev.clone()[0]
         return out
 
@@ -1156,8 +1204,7 @@ class ModelBase:
     def iterations(self):
         """keras's optimizer.iterations: the updates applied so far, read from the device counter (a guarded step does not
         count); what the learning-rate schedule, scheduled sampling and the weight average see"""
-        t = self.__dict__.get("adam_t")
-        return 0 if t is None else int(t[0])
+        return 0 if self.adam_t is None else int(self.adam_t[0])
 
     def set_iterations(self, n):
         """Writes the update counter, and nothing else (the dropout stream's counter stays): a run continued from
@@ -1165,49 +1212,89 @@ class ModelBase:
         reads the same counter."""
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
             raise ValueError(f"iterations must be an int >= 0, got {n!r}")
-        if self.__dict__.get("adam_t") is None:
+        if self.adam_t is None:
             raise RuntimeError("set_iterations: the counter exists once the optimizer state does (compile and build the model)")
         self.adam_t.fill_(int(n))
 
     def _apply_optimizer(self):
         """per-variable clipnorm + Adam/SGD (optimizer.apply_gradients, lc_NIC.py:389)."""
-        be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
-        clip = opt.clipnorm if opt.clipnorm is not None else 0.0
-        gd = self._guard_word()
-        wd = self.__dict__.get("seg_wd")         # decoupled weight decay: the decaying entry point in the plain one's place
-        self._lr_schedule_launch()
-        if opt.kind == "adam":
-            be.step_tick(self.adam_t, self.drop_step, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2, guard=gd)
-            if wd is None:
-                be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
-                        a.sq_override, sp.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, guard=gd)
-            else:
-                be.adamw(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq,
-                         a.sq_override, sp.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, self.lr_dev, wd,
-                         guard=gd)
+        self._tick()
+        if self.optimizer.kind == "adam":
+            self._adam_update(self._spans())
         else:
-            be.step_tick(self.adam_t, self.drop_step, self.lr_dev, None, 0.0, 0.0, guard=gd)
-            self._sgd_update(clip, gd)
+            self._sgd_update(self._spans())
         # the tick precedes the update here: adam_t is the number of applied updates when the averaging launch starts
         self._average_update()
 
-    def _sgd_update(self, clip, gd):
-        """clip + SGD over the whole arena: tnt_sgd_f32, or tnt_sgdw_f32 under decoupled weight decay"""
-        be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
-        wd = self.__dict__.get("seg_wd")
-        if wd is None:
-            be.sgd(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
-                   sp.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+    # ---- the update launches, one helper each.  Under decoupled weight decay (``seg_wd`` set) a helper issues the decaying
+    # entry point in the plain one's place; its callers pass what differs between them -- the spans, the metrics ring, the
+    # finalize descriptor -- and do not know that the decay exists.
+    def _clip(self):
+        """the optimizer's clipnorm as the launches take it: 0 = no clipping"""
+        clip = self.optimizer.clipnorm
+        return clip if clip is not None else 0.0
+
+    def _spans(self, s1=0):
+        """(span_seg, span_off, span_len, nspan) of the arena's spans from span ``s1`` on, as the norm and update launches
+        take them"""
+        sp = self.arena.spans
+        return sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], sp.nspan - s1
+
+    def _adam_update(self, spans, ring=None):
+        """clip + Adam over ``spans`` (_spans, or an arena.seg_slice's): tnt_adam_f32 / tnt_adamw_f32.  ``ring``: _ring_args()"""
+        be, a, opt = self.be, self.arena, self.optimizer
+        seg, off, length, nspan = spans
+        args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan, 0.0,
+                self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, self._clip())
+        if self.seg_wd is None:
+            be.adam(*args, guard=self._guard_word(), **(ring or {}))
         else:
-            be.sgdw(a.theta, self.opt_m, a.grad, sp.span_seg, sp.span_off, sp.span_len, a.seg_l2, a.sq, a.sq_override,
-                    sp.nspan, self.lr_dev, opt.momentum, clip, wd, guard=gd)
+            be.adamw(*args, self.lr_dev, self.seg_wd, guard=self._guard_word(), **(ring or {}))
+
+    def _adam_fin_update(self, spans, desc, ring):
+        """clip + Adam over ``spans`` with the step's finalize work ``desc`` (finalize_desc) inside the launch:
+        tnt_adam_fin_f32 / tnt_adamw_fin_f32.  The descriptor's lr is lr_dev: the decay reads the step's rate through it"""
+        be, a, opt = self.be, self.arena, self.optimizer
+        seg, off, length, nspan = spans
+        args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.sq_override, nspan, opt.epsilon, self._clip(), desc)
+        if self.seg_wd is None:
+            be.adam_fin(*args, **ring)
+        else:
+            be.adamw_fin(*args, self.seg_wd, **ring)
+
+    def _enc_adam_update(self, enc, fin):
+        """The encoder kernel's fused update (``enc``: an EncUpdate): clip + Adam on the strips of X^T dpre as they leave
+        the MFMAs.  ``fin``: the form that sums the variable's clip norm from its span partials itself
+        (tnt_dense_dw_adam_fin_f32 / tnt_dense_dw_adamw_fin_f32), else the one that reads it from ``sq``
+        (tnt_dense_dw_adam_f32 / tnt_dense_dw_adamw_f32).  The decaying forms take the variable's decay as a scalar."""
+        be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
+        e = a.entries[enc.name]
+        sl, one = slice(e.off, e.off + e.size), slice(e.seg, e.seg + 1)
+        norm = (a.partial, sp.first_host[e.seg], sp.first_host[e.seg + 1]) if fin else (a.sq[one],)
+        args = (enc.x, enc.dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, *norm, a.sq_override[one], self.lr_t_dev,
+                opt.beta_1, opt.beta_2, opt.epsilon, self._clip(), enc.N, enc.E, enc.rows, enc.ldx)
+        if self.seg_wd is None:
+            (be.dense_dw_adam_fin if fin else be.dense_dw_adam)(*args, guard=self._guard_word())
+        else:
+            (be.dense_dw_adamw_fin if fin else be.dense_dw_adamw)(*args, self.lr_dev, self._wd_scalar(e.seg),
+                                                                  guard=self._guard_word())
+
+    def _sgd_update(self, spans):
+        """clip + SGD over ``spans``: tnt_sgd_f32 / tnt_sgdw_f32 (its learning rate comes from the device only)"""
+        be, a, opt = self.be, self.arena, self.optimizer
+        seg, off, length, nspan = spans
+        args = (a.theta, self.opt_m, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan)
+        if self.seg_wd is None:
+            be.sgd(*args, 0.0, self.lr_dev, opt.momentum, self._clip(), guard=self._guard_word())
+        else:
+            be.sgdw(*args, self.lr_dev, opt.momentum, self._clip(), self.seg_wd, guard=self._guard_word())
 
     def _average_update(self):
         """The averaging launch of a step (tnt_weight_average_f32 over the whole arena): the step's last launch, behind its
         last update launch and inside the same recorded plan / graph.  Copy, skip or blend is decided on the device from
         adam_t, which must equal the number of applied updates by then, and from the guard word.  Nothing without an
         averaging optimizer."""
-        av = self.__dict__.get("average")
+        av = self.average
         if av is None:
             return
         a = self.arena
@@ -1220,132 +1307,95 @@ class ModelBase:
         launches seg_finalize, l2_total, sum2, step_tick of the unfused sequence (each ~4.6 us inside the graph).
         ``skip_first`` (dp.PipelinedDenseSync with a row-sharded encoder kernel): variable 0 is updated by the caller, its
         (sum g^2, sum theta^2) pair sits in partial[0:2] with the variable's other slots zero -- the finalize work files it
-        like any other, the norm / update launches here start behind it."""
-        be, a, sp, opt = self.be, self.arena, self.arena.spans, self.optimizer
+        like any other, the norm / update launches here start behind it.
+        Three phases: the norm launch(es) (_fused_norms), the finalize arguments (_finalize_args), the update launches
+        (_fused_updates).  The step's tail (StepTail) is taken here and left empty."""
+        sp, adam = self.arena.spans, self.optimizer.kind == "adam"
         self._apply_agc()
-        d = self.__dict__.pop("_sum2_deferred", None)
-        if not hasattr(be, "step_finalize"):
-            if d is not None:
-                be.sum2(*d)
-            md = self.__dict__.pop("_metric_deferred", None)
-            if md is not None:
-                be.sum(md[0], md[1], md[2], md[3])
-            self._norms_and_l2(l2_out)
-            self._apply_optimizer()
-            return
-        clip = opt.clipnorm if opt.clipnorm is not None else 0.0
-        gd = self._guard_word()
-        adam = opt.kind == "adam"
-        wd = self.__dict__.get("seg_wd")         # decoupled weight decay: every update launch below in its decaying form
-        enc = self.__dict__.pop("_enc_fused", None)
+        tail, self._tail = self._tail, StepTail()
+        enc = tail.enc
         # lr_dev is first read by the norm launch that carries the lr job, else by the finalize launch: the schedule goes here
         self._lr_schedule_launch()
-        # no finalize launch (tnt_adam_fin_f32): the norm launch leaves lr_t, the update launches sum the clip norms they need
-        # from the span partials themselves, one extra workgroup of the Adam launch files the scalars, the counters tick at its end
-        fin = adam and hasattr(be, "adam_fin") and getattr(self, "fused_finalize", True)
-        lr_job = (self.adam_t, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2) if fin else None
-        # the norm launch reads only what the update will consume (tnt_span_norm, csrc/tnt_fin.h): no gradient pass for a
-        # variable whose clip norm is supplied through sq_override, no theta pass where there is no regulariser
-        skip = a.sq_override if (fin and not self.__dict__.get("agc") and getattr(self, "norm_skip", True)) else None
-        s1, rest_done = 0, False
+        s1 = 0          # the first span the norm / update launches here walk
         if skip_first:
             if enc is not None or not adam:
                 raise RuntimeError("skip_first needs Adam and an encoder gradient that the caller handles")
             s1 = sp.first_host[1]
         if enc is not None:
+            s1 = sp.first_host[self.arena.entries[enc.name].seg + 1]
+        # no finalize launch (tnt_adam_fin_f32): the norm launch leaves lr_t, the update launches sum the clip norms they need
+        # from the span partials themselves, one extra workgroup of the Adam launch files the scalars, the counters tick at its end
+        fin = adam and hasattr(self.be, "adam_fin") and getattr(self, "fused_finalize", True)
+        fin = self._fused_norms(enc, s1, fin)
+        self._fused_updates(l2_out, enc, s1, fin, self._finalize_args(tail))
+
+    def _fused_norms(self, enc, s1, fin):
+        """_update_fused, phase 1: the norm partials of every variable's spans from span ``s1`` on, and of the encoder
+        kernel handed over in ``enc``.  ``fin``: the launch also carries Adam's lr job (lr_t from the step counter) for an
+        update without a finalize launch.  Returns whether it did: False where a plain span_sqnorm ran."""
+        be, a, opt = self.be, self.arena, self.optimizer
+        seg, off, length, nspan = self._spans(s1)
+        lr_job = (self.adam_t, self.lr_dev, self.lr_t_dev, opt.beta_1, opt.beta_2) if fin else None
+        # the norm launch reads only what the update will consume (tnt_span_norm, csrc/tnt_fin.h): no gradient pass for a
+        # variable whose clip norm is supplied through sq_override, no theta pass where there is no regulariser
+        skip = a.sq_override if (fin and not self.agc) else None
+        if enc is not None:
             # The dense encoder kernel (segment 0, 59 % of config 2's parameters) never has its gradient written: one
             # pass of the skinny product leaves its norm partials in the variable's span slots, a second one applies
             # clip + Adam to the strips as they leave the MFMAs (24 bytes per parameter instead of 40).
-            name, x, dpre, rows, N, E, ldx, gram = enc
-            e = a.entries[name]
-            s1 = sp.first_host[e.seg + 1]
-            if gram is not None and 4 * rows + gram[5] <= s1:
+            e, g = a.entries[enc.name], enc.gram
+            if g is not None and 4 * enc.rows + g.nw2 <= s1:
                 # norm from the forward's by-products: ||X^T D||^2 = sum (X X^T) o (D D^T), no pass over the gradient
-                pre, bias, gx, nsplit, w2, nw2 = gram
                 # ... with the span norms of every other variable riding in the same launch
-                be.dense_gram_norm(dpre, pre, bias, gx, nsplit, w2, nw2, e.l2, a.partial, s1, rows, E,
-                                   spans=(a.theta, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
-                                          a.partial[2 * s1:], sp.nspan - s1), lr_job=lr_job, **({"skip": skip} if skip is not None else {}))
-                rest_done = True
-            else:
-                be.dense_dw_sqnorm(x, dpre, a.p(name), e.l2, a.partial, s1, N, E, rows, ldx)
-        if not rest_done:
-            if fin and sp.nspan - s1 > 0:
-                be.span_sqnorm_lr(a.theta, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2, a.partial[2 * s1:],
-                                  sp.nspan - s1, *lr_job, **({"skip": skip} if skip is not None else {}))
-            else:
-                fin = False
-                be.span_sqnorm(a.theta, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2, a.partial[2 * s1:],
-                               sp.nspan - s1)
-        kw = dict(x0=d[0], out0=d[1], x1=d[2], out1=d[3], n=d[4], scale=d[5]) if d is not None else {}
-        md = self.__dict__.pop("_metric_deferred", None)
-        if md is not None:
-            kw.update(x2=md[0], out2=md[1], n2=md[2], scale2=md[3])
-        ef = self.__dict__.pop("_emb_finalize", None)
-        if ef is not None:       # sparse embedding backward: sum its norm partials, hand this step's ids on as prev_ids
-            parts, sqo, nparts, ids, prev, nids = ef
-            kw.update(ids_src=ids, ids_dst=prev, n_ids=nids)
-            if sqo is not None:
-                kw.update(extra_part=parts, extra=sqo, n_extra=nparts)
+                be.dense_gram_norm(enc.dpre, g.pre, g.bias, g.gx, g.nsplit, g.w2, g.nw2, e.l2, a.partial, s1, enc.rows, enc.E,
+                                   spans=(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan),
+                                   lr_job=lr_job, skip=skip)
+                return fin
+            be.dense_dw_sqnorm(enc.x, enc.dpre, a.p(enc.name), e.l2, a.partial, s1, enc.N, enc.E, enc.rows, enc.ldx)
+        if fin and nspan > 0:
+            be.span_sqnorm_lr(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan, *lr_job, skip=skip)
+            return True
+        be.span_sqnorm(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan)
+        return False
+
+    def _finalize_args(self, tail):
+        """_update_fused, phase 2: the keywords of the step's finalize work -- what the step handed over in ``tail`` and the
+        step state that ticks -- for whichever launch carries it (finalize_desc of the Adam launch, or step_finalize)"""
+        opt, adam = self.optimizer, self.optimizer.kind == "adam"
+        return dict(tail.finalize_kw(), adam_t=self.adam_t, drop_step=self.drop_step, lr=self.lr_dev,
+                    lr_t=self.lr_t_dev if adam else None, beta1=opt.beta_1 if adam else 0.0,
+                    beta2=opt.beta_2 if adam else 0.0, guard=self._guard_word())
+
+    def _fused_updates(self, l2_out, enc, s1, fin, kw):
+        """_update_fused, phase 3: the finalize work ``kw`` (_finalize_args) and clip + Adam / SGD from span ``s1`` on, the
+        encoder kernel's fused update (``enc``) included.  ``fin``: inside the Adam launch (its descriptor), else as the
+        step_finalize launch in front of the update launches."""
+        be, a, sp = self.be, self.arena, self.arena.spans
+        spans = self._spans(s1)
         if fin:
             if enc is not None:        # the encoder kernel first: it reads the step counter's lr_t like the Adam launch, which ticks
-                sl = slice(e.off, e.off + e.size)
-                if wd is None:
-                    be.dense_dw_adam_fin(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.partial, sp.first_host[e.seg],
-                                         sp.first_host[e.seg + 1], a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1,
-                                         opt.beta_2, opt.epsilon, clip, N, E, rows, ldx, guard=gd)
-                else:
-                    be.dense_dw_adamw_fin(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.partial,
-                                          sp.first_host[e.seg], sp.first_host[e.seg + 1], a.sq_override[e.seg:e.seg + 1],
-                                          self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, N, E, rows, ldx, self.lr_dev,
-                                          self._wd_scalar(e.seg), guard=gd)
+                self._enc_adam_update(enc, fin=True)
             if "extra_part" in kw:
                 kw["extra_seg"] = self.emb_seg
-            arrive = self.__dict__.get("_fin_arrive")
-            if arrive is None:
-                arrive = self._fin_arrive = torch.zeros(16, dtype=torch.int32, device=self.device)
+            if self._fin_arrive is None:
+                self._fin_arrive = torch.zeros(16, dtype=torch.int32, device=self.device)
             # one descriptor per distinct argument set, alive as long as the model (recorded launch plans re-issue the call)
-            ck = tuple((k, v.data_ptr() if torch.is_tensor(v) else v) for k, v in sorted(kw.items())) + (l2_out.data_ptr(), gd is not None)
-            descs = self.__dict__.setdefault("_fin_descs", {})
-            if ck not in descs:
-                descs[ck] = be.finalize_desc(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, arrive,
-                                             adam_t=self.adam_t, drop_step=self.drop_step, lr=self.lr_dev, lr_t=self.lr_t_dev,
-                                             beta1=opt.beta_1, beta2=opt.beta_2, guard=gd, **kw)
-            if wd is None:
-                be.adam_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
-                            a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], **self._ring_args())
-            else:                      # the descriptor's lr is lr_dev: the decay reads the step's rate through it
-                be.adamw_fin(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:],
-                             a.sq_override, sp.nspan - s1, opt.epsilon, clip, descs[ck], wd, **self._ring_args())
+            ck = tuple((k, v.data_ptr() if torch.is_tensor(v) else v) for k, v in sorted(kw.items())) + (l2_out.data_ptr(),)
+            if ck not in self._fin_descs:
+                self._fin_descs[ck] = be.finalize_desc(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg,
+                                                       self._fin_arrive, **kw)
+            self._adam_fin_update(spans, self._fin_descs[ck], self._ring_args())
             # the counters tick when the last workgroup of the Adam launch arrives, behind the encoder's update: adam_t is
             # the number of applied updates when the averaging launch starts
             self._average_update()
             return
-        be.step_finalize(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, adam_t=self.adam_t,
-                         drop_step=self.drop_step, lr=self.lr_dev, lr_t=self.lr_t_dev if adam else None,
-                         beta1=opt.beta_1 if adam else 0.0, beta2=opt.beta_2 if adam else 0.0, guard=gd, **kw)
-        if adam:
-            ring = self._ring_args() if sp.nspan - s1 > 0 else {}
-            if wd is None:
-                be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
-                        a.sq, a.sq_override, sp.nspan - s1, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                        guard=gd, **ring)
-            else:
-                be.adamw(a.theta, self.opt_m, self.opt_v, a.grad, sp.span_seg[s1:], sp.span_off[s1:], sp.span_len[s1:], a.seg_l2,
-                         a.sq, a.sq_override, sp.nspan - s1, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                         self.lr_dev, wd, guard=gd, **ring)
+        be.step_finalize(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, **kw)
+        if self.optimizer.kind == "adam":
+            self._adam_update(spans, self._ring_args() if spans[3] > 0 else None)
             if enc is not None:
-                sl = slice(e.off, e.off + e.size)
-                if wd is None:
-                    be.dense_dw_adam(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.sq[e.seg:e.seg + 1],
-                                     a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                                     N, E, rows, ldx, guard=gd)
-                else:
-                    be.dense_dw_adamw(x, dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, a.sq[e.seg:e.seg + 1],
-                                      a.sq_override[e.seg:e.seg + 1], self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip,
-                                      N, E, rows, ldx, self.lr_dev, self._wd_scalar(e.seg), guard=gd)
+                self._enc_adam_update(enc, fin=False)
         else:
-            self._sgd_update(clip, gd)
+            self._sgd_update(spans)
         # the finalize launch ticked in front of the update launches: adam_t is the number of applied updates here too
         self._average_update()
 
@@ -1404,11 +1454,11 @@ class ModelBase:
 
     def _emb_sparse_ok(self, E, ldd):
         """the sparse Embedding backward runs (single-process fused step)"""
-        return bool(self.__dict__.get("_defer_sum2") and self.dp_world == 1 and getattr(self, "sparse_emb_bwd", True)
+        return bool(self._tail.deferring and self.dp_world == 1 and getattr(self, "sparse_emb_bwd", True)
                     and hasattr(self.be, "embedding_bwd_sparse") and E % 4 == 0 and ldd % 4 == 0)
 
     def _embedding_bwd(self, drows, ids, name, B, T, E, ldd, V, drop=None, zero_id=-1):
-        """Embedding scatter + IndexedSlices norm.  Inside the fused single-process step (``_defer_sum2``) the sparse
+        """Embedding scatter + IndexedSlices norm.  Inside the fused single-process step (_deferring) the sparse
         form runs: no table-wide zero fill (rows touched by the previous step only are cleaned through ``prev_ids``),
         the norm as per-block partials that the step-finalize launch sums.  Anywhere else (data parallel: the all-reduce
         writes rows of other ranks' tokens; SAM; eager paths) the dense form runs and hands its ids on as prev_ids, so
@@ -1432,20 +1482,28 @@ class ModelBase:
             if zero_id >= 0 and getattr(self, "emb_skip_masked", True):
                 kw["zero_id"] = zero_id       # rows of the mask id carry no gradient (the caller's guarantee): not read
             be.embedding_bwd_sparse(drows, ids, prev, a.g(name), parts, B, T, E, ldd, V, **kw)
-            self._emb_finalize = (parts, None if self.__dict__.get("agc") else sqo, nparts, ids, prev, B * T)
+            # the finalize work hands this step's ids on as prev_ids and sums the norm partials (not under AGC: its launch
+            # writes the clipped rows' norm into the variable's sq_override slot itself)
+            t = self._tail
+            t.ids_src, t.ids_dst, t.n_ids = ids, prev, B * T
+            if not self.agc:
+                t.extra_part, t.extra, t.n_extra = parts, sqo, nparts
         else:
             be.embedding_bwd(drows, ids, a.g(name), sqo, self.rowsq, B, T, E, ldd, V)
             prev.copy_(ids.reshape(-1))
 
     def _sum2(self, x0, out0, x1, out1, n, scale):
         """loss / accuracy totals: deferred into the step-finalize launch when a fused update follows in the same
-        launch sequence (``_defer_sum2`` set by train_step), else their own launch"""
-        if self.__dict__.get("_defer_sum2"):
-            self._sum2_deferred = (x0, out0, x1, out1, n, scale)
+        launch sequence (inside _deferring), else their own launch"""
+        if self._tail.deferring:
+            t = self._tail
+            t.x0, t.out0, t.x1, t.out1, t.n, t.scale = x0, out0, x1, out1, n, scale
         else:
             self.be.sum2(x0, out0, x1, out1, n, scale)
 
     def _tick(self):
+        """the schedule's launch and the step tick of an update without a finalize launch (_apply_optimizer, and once per
+        step in front of the first _update_slice)"""
         opt, gd = self.optimizer, self._guard_word()
         self._lr_schedule_launch()
         if opt.kind == "adam":
@@ -1456,17 +1514,12 @@ class ModelBase:
     def _update_slice(self, sl):
         """norms + clip + optimizer on one contiguous range of variables (arena.seg_slice); the caller
         runs _tick() once before the first slice and l2_total after the last."""
-        be, a, opt = self.be, self.arena, self.optimizer
-        clip = opt.clipnorm if opt.clipnorm is not None else 0.0
-        be.seg_sqnorm(a.theta, a.grad, sl.span_seg, sl.span_off, sl.span_len, sl.seg_first, a.seg_l2, sl.partial,
-                      sl.sq, sl.wsq, None, sl.nspan, sl.nseg)
-        gd = self._guard_word()
-        if opt.kind == "adam":
-            be.adam(a.theta, self.opt_m, self.opt_v, a.grad, sl.span_seg, sl.span_off, sl.span_len, a.seg_l2, a.sq,
-                    a.sq_override, sl.nspan, 0.0, self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, clip, guard=gd)
+        a, spans = self.arena, (sl.span_seg, sl.span_off, sl.span_len, sl.nspan)
+        self.be.seg_sqnorm(a.theta, a.grad, *spans[:3], sl.seg_first, a.seg_l2, sl.partial, sl.sq, sl.wsq, None, sl.nspan, sl.nseg)
+        if self.optimizer.kind == "adam":
+            self._adam_update(spans)
         else:
-            be.sgd(a.theta, self.opt_m, a.grad, sl.span_seg, sl.span_off, sl.span_len, a.seg_l2, a.sq, a.sq_override,
-                   sl.nspan, 0.0, self.lr_dev, opt.momentum, clip, guard=gd)
+            self._sgd_update(spans)
 
     @staticmethod
     def pick_splitk(M, N, K):
@@ -1661,9 +1714,9 @@ class ModelBase:
     def enable_agc(self, clip_factor=0.01, eps=1e-3):
         """gradients = agc.adaptive_clip_grad(trainable_variables, gradients, clip_factor, eps) before
         optimizer.apply_gradients -- the (commented-out) call of lc_NIC.py:388.  clip_factor=None switches it off."""
-        if clip_factor is not None and int(self.__dict__.get("dp_world", 1) or 1) > 1:
+        if clip_factor is not None and self.dp_world > 1:
             raise NotImplementedError("adaptive gradient clipping is not supported under data parallel (dp.attach)")
-        if clip_factor is not None and (self.__dict__.get("seg_wd") is not None or
+        if clip_factor is not None and (self.seg_wd is not None or
                                         check_weight_decay(getattr(self.optimizer, "weight_decay", None))):
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
@@ -1675,7 +1728,7 @@ class ModelBase:
         return self.__dict__.get("_emb_rows")
 
     def _apply_agc(self):
-        if not self.__dict__.get("agc"):
+        if not self.agc:
             return
         from .arena import AgcTable
         a, er = self.arena, self._emb_row_grads()
@@ -1764,7 +1817,7 @@ class ModelBase:
     # ------------------------------------------------------------------ weight average (optimizers.MovingAverage / SWA)
     def _average_buf(self, what):
         """opt_avg; ValueError on a model compiled without averaging"""
-        if self.__dict__.get("average") is None:
+        if self.average is None:
             raise ValueError(f"{what} needs a model compiled with an averaging optimizer (optimizers.MovingAverage / SWA)")
         if self.__dict__.get("opt_avg") is None:
             raise RuntimeError(f"{what}: the average exists once the optimizer state does, from the first training step on")
@@ -2280,12 +2333,21 @@ class ModelBase:
             self._train_graph(B, T)
             self._update_graph()
             return
-        self._defer_sum2 = True
-        try:
+        with self._deferring():
             self._train_graph(B, T)
-        finally:
-            self._defer_sum2 = False
         self._update_fused(self.met[2:3])
+
+    @contextmanager
+    def _deferring(self, on=True):
+        """The scope of a step's launches that may leave work to the fused update behind them (StepTail): _sum2,
+        _embedding_bwd and the models' _loss_metrics / _bwd_enc read ``_tail.deferring``.  It opens on an empty tail, so
+        nothing is inherited from an earlier step that failed between its loss and its update; what the scope collects
+        stays for the _update_fused that follows.  ``on=False``: the same launches with nothing deferred."""
+        self._tail = StepTail(deferring=bool(on))
+        try:
+            yield
+        finally:
+            self._tail.deferring = False
 
     def _train_step_dp(self, B, T, fb, up):
         """the generic data-parallel schedule: forward+backward | all-reduce of the flat gradient | update"""
@@ -2466,7 +2528,7 @@ class ModelBase:
         the first step; None leaves the model's weights as they are."""
         if class_weight is not None:
             self.set_class_weight(class_weight)
-        if validation_averaged and self.__dict__.get("average") is None:
+        if validation_averaged and self.average is None:
             raise ValueError("fit(validation_averaged=True) needs a model compiled with an averaging optimizer "
                              "(optimizers.MovingAverage / SWA)")
         callbacks = list(callbacks or [])

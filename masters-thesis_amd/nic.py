@@ -20,7 +20,7 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
-                         _TokenChoice, _BeamDecode)
+                         _TokenChoice, _BeamDecode, EncGram, EncUpdate)
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
@@ -138,9 +138,9 @@ class NIC(ModelBase):
         out (tnt_dense_dw_sqnorm_f32 / tnt_dense_dw_adam_f32): the single-process fused step with Adam, no AGC.
         ``defer``: asked ahead of the step (_stage_fwd_args) -- whether that step will be the fused one."""
         opt = self.optimizer
-        defer = self.__dict__.get("_defer_sum2") if defer is None else defer
+        defer = self._tail.deferring if defer is None else defer
         return bool(defer and self.dp_world == 1 and getattr(self, "fuse_enc_update", True)
-                    and opt is not None and opt.kind == "adam" and not self.__dict__.get("agc") and rows <= 64
+                    and opt is not None and opt.kind == "adam" and not self.agc and rows <= 64
                     and self.E % 512 == 0 and hasattr(self.be, "dense_dw_adam") and hasattr(self.be, "step_finalize")
                     and self.arena.entries["dense_img/kernel"].seg == 0
                     # one norm-partial slot per workgroup inside the variable's own span slots
@@ -227,8 +227,8 @@ class NIC(ModelBase):
         ok = (getattr(self, "compact_head", True) and self.__dict__.get("_seq_lstm") and self.__dict__.get("seq_xch") is not None
               and hasattr(be, "stage_batch_map") and hasattr(be, "softmax_cce_live") and hasattr(be, "gemm3")
               and getattr(self, "use_gemm3", True) and getattr(self, "g3_riders", True)
-              and self.grad_sync is None and int(self.__dict__.get("dp_world", 1) or 1) == 1
-              and self.scheduled_sampling is None and self.self_critical is None and not self.__dict__.get("agc")
+              and self.grad_sync is None and self.dp_world == 1
+              and self.scheduled_sampling is None and self.self_critical is None and not self.agc
               and not self.label_smoothing and not self.unlikelihood and not self._token_weights_on() and self.U % 4 == 0)
         if not ok:
             return None
@@ -289,8 +289,8 @@ class NIC(ModelBase):
                 if not staged:
                     be.dense_fwd_stream_gram(x, a.p("dense_img/kernel"), self.enc_part, self.enc_gx, self.enc_w2, B, E, N,
                                              self.ldx, E, ENC_SPLITS)
-                self._enc_gram = (self.enc_pre, a.p("dense_img/bias"), self.enc_gx, ENC_SPLITS, self.enc_w2,
-                                  ENC_SPLITS * (E // 32))
+                self._enc_gram = EncGram(pre=self.enc_pre, bias=a.p("dense_img/bias"), gx=self.enc_gx, nsplit=ENC_SPLITS,
+                                         w2=self.enc_w2, nw2=ENC_SPLITS * (E // 32))
             elif staged:
                 raise RuntimeError("the staging launch ran the Gram form of the encoder forward, which this step does not take")
             else:
@@ -398,27 +398,13 @@ class NIC(ModelBase):
     def _loss_metrics(self, B, T, want_grad):
         """softmax + per-timestep mean CE / accuracy summed over T and divided by T
         (NIC.py:233-240) == sum over all (b,t) / (B*T)."""
-        be = self.be
         n = T * B
-        eps = self.label_smoothing
         if want_grad and self.__dict__.get("_compact"):
             # the distinct rows, each weighted by its multiplicity; rows past the live count hold zeros (staging launch)
-            be.softmax_cce_live(self.logits, self.head_tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
-                                self.ldV, 1.0 / (n * self.dp_world), self.head_live, self.head_w)
-        elif eps > 0:         # keras smooths the evaluation loss too
-            be.softmax_cce_smooth(self.logits, self.tgt, None if want_grad else self.logits, self.loss_row, self.corr_row,
-                                  self.logits if want_grad else None, n, self.V, self.ldV,
-                                  1.0 / (n * self.dp_world) if want_grad else 0.0, eps)
-        elif self.unlikelihood > 0:
-            self._loss_unlikely(B, T, want_grad)
-        elif self._token_weights_on():
-            self._loss_weighted(B, T, want_grad)
-        elif want_grad:
-            be.softmax_cce(self.logits, self.tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
-                           self.ldV, 1.0 / (n * self.dp_world))
+            self.be.softmax_cce_live(self.logits, self.head_tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
+                                     self.ldV, 1.0 / (n * self.dp_world), self.head_live, self.head_w)
         else:
-            be.softmax_cce(self.logits, self.tgt, self.logits, self.loss_row, self.corr_row, None, n, self.V,
-                           self.ldV, 0.0)
+            self._head_loss(B, T, want_grad)
         self._sum2(self.loss_row, self.met[0:1], self.corr_row, self.met[1:2], n, 1.0 / n)
 
     # ------------------------------------------------------------------ backward
@@ -467,7 +453,7 @@ class NIC(ModelBase):
             with self.side(0 if getattr(self, "side_head", True) else -1):
                 self.gemm_sk(self.Out, dlog, a.g("time_distributed_softmax/kernel"), U, V, T * B, U, ldV, ldV, transA=True,
                              ws=1)
-                if self.__dict__.get("_defer_sum2") and hasattr(be, "colsum2") and T * B <= 2048:
+                if self._tail.deferring and hasattr(be, "colsum2") and T * B <= 2048:
                     # single-process step: the head-bias column sums share a launch with the LSTM-bias ones behind the
                     # BPTT chain (dlogits stays in place until the next forward)
                     self._colsum_deferred = (dlog, a.g("time_distributed_softmax/bias"), T * B, V, ldV)
@@ -554,7 +540,7 @@ class NIC(ModelBase):
         # read; not when AGC needs the dropped-out rows themselves).  Off by default: measured 0.5761 -> 0.5845 ms/step --
         # the Philox calls land on the few workgroups that own heavily duplicated ids, on the step's critical path, and cost
         # more there than the 4 us launch they save.
-        fold = self.r_lstm > 0 and self._emb_sparse_ok(E, E) and not self.__dict__.get("agc") and getattr(self, "fold_emb_drop", False)
+        fold = self.r_lstm > 0 and self._emb_sparse_ok(E, E) and not self.agc and getattr(self, "fold_emb_drop", False)
         # ... else it shares a launch with the encoder tail backward (both read the dXin the GEMM above just wrote, different
         # rows), which then runs in front of the Embedding backward
         ride = (self.r_lstm > 0 and not fold and fused and E % 4 == 0 and hasattr(be, "enc_tail_bwd_drop")
@@ -602,8 +588,8 @@ class NIC(ModelBase):
             dpre = self.dpre
         self._enc_last_fused = None
         if x_all is None and self._enc_update_fused(rows):
-            self._enc_fused = ("dense_img/kernel", x, dpre, rows, self.N, self.E, self.ldx,
-                               self.__dict__.get("_enc_gram"))                                    # -> _update_fused
+            self._tail.enc = EncUpdate("dense_img/kernel", x, dpre, rows, self.N, self.E, self.ldx,
+                                       gram=self.__dict__.get("_enc_gram"))                       # -> _update_fused
             self._enc_last_fused = (x, dpre, rows)       # train_step marks the gradient buffer stale after every (re)play
             return
         if rows <= 64 and self.E % 16 == 0 and getattr(self, "skinny_dw", True):
@@ -765,14 +751,11 @@ class NIC(ModelBase):
         """tnt_scst_cce_f32 (loss rows, dlogits in place of the logits), the teacher-forced backward over the sampled ids,
         and the fused update: the L2 terms, the clip and Adam of train_step"""
         st = self._scst
-        self._defer_sum2 = True
-        try:
+        with self._deferring():
             self.be.scst_cce(self.logits, self.ldV, self.V, self.cap, T, st["last"], st["adv"], self.self_critical.end_id,
                              self.loss_row, None, self.logits, R, 1.0 / R)
             self._sum2(self.loss_row, self.met[0:1], self.loss_row, self.met[1:2], T * R, 1.0 / R)
             self._backward(R, T)
-        finally:
-            self._defer_sum2 = False
         self._update_fused(self.met[2:3])
 
     def _scst_round_trip(self, B, T):

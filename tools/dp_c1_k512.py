@@ -37,5 +37,3 @@ for G in (1, 2, 4, 8):
     t_dw = timeit(f)
     t_up = timeit(lambda: m._update_slice(sl))
     print(f"{G:2d} {K:4d} {t_dw:8.1f} {t_up:18.1f} {t_dw + t_up:12.1f}   {prod}")
-m._enc_fused = None
-t_f = timeit(lambda: m._bwd_enc(64, 15)) if False else None
