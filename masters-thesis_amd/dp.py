@@ -155,6 +155,7 @@ class PipelinedDenseSync:
         self.split_update = os.environ.get("TNT_DP_SPLIT_UPDATE", "0") == "1"
         self.one_graph = os.environ.get("TNT_DP_ONE_GRAPH", "0") == "1"
         self.capture_error = None
+        self._ib = None         # the _IssueBehind of the first pipelined step
 
     def _gather(self, out, t):
         if dist.get_backend() == "gloo":
@@ -219,7 +220,7 @@ class PipelinedDenseSync:
             return
 
         cap = lambda key, fn: (m._run_planned if key[0][2:] in self.eager else m._run_captured)(key, fn)
-        ib = self.__dict__.get("_ib") or self.__dict__.setdefault("_ib", _IssueBehind(m))
+        ib = self._ib = self._ib or _IssueBehind(m)
         cap(("dpA", B, T), lambda: _segment_a(m, B, T, defer_totals=not self.split_update))
         eA = ib.mark(0)
         cap(("dpB1", B, T), lambda: (m._bwd_seq_lstm(B, T), m.join()))          # enqueued before the host turns to the collectives
@@ -290,7 +291,7 @@ class PipelinedDenseSync:
         opt = m.optimizer
         return bool(self.shard_encoder and not self.split_update and m.N % self.world == 0 and (m.N // self.world) % 4 == 0
                     and opt is not None and opt.kind == "adam" and not m.agc
-                    and m.arena.entries["dense_img/kernel"].seg == 0 and hasattr(m.be, "step_finalize"))
+                    and m.arena.entries["dense_img/kernel"].seg == 0)
 
     def __call__(self, model):          # generic fallback (models without a pipelined schedule)
         make_grad_sync(self.world)(model)
@@ -327,6 +328,7 @@ class PipelinedAttentionSync:
         self.split_update = os.environ.get("TNT_DP_SPLIT_UPDATE", "0") == "1"
         self.one_graph = os.environ.get("TNT_DP_ONE_GRAPH", "0") == "1"
         self.capture_error = None
+        self._ib = None         # the _IssueBehind of the first pipelined step
 
     def step(self, m, B, T):
         a = m.arena
@@ -356,7 +358,7 @@ class PipelinedAttentionSync:
             return
         cap = lambda key, fn: (m._run_planned if key[0][2:] in self.eager else m._run_captured)(key, fn)
 
-        ib = self.__dict__.get("_ib") or self.__dict__.setdefault("_ib", _IssueBehind(m))
+        ib = self._ib = self._ib or _IssueBehind(m)
         cap(("dpA", B, T), lambda: _segment_a(m, B, T, defer_totals=not self.split_update))
         eA = ib.mark(0)
         cap(("dpB1", B, T), lambda: m._bwd_chain(B, T))               # every compute segment is enqueued before the host turns to
@@ -417,15 +419,15 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     shard_encoder=True (dense-encoder NIC; default: TNT_DP_SHARD_ENC): the encoder kernel's update is row-sharded over the
     ranks (PipelinedDenseSync.step).  Every rank keeps the complete, identical kernel; only the optimizer moments of a shard
     live on its owner alone."""
-    if not getattr(model, "teacher_forcing", True):
+    if not model.teacher_forcing:
         # the free-running training step (lc_nic.NIC(teacher_forcing=False)) has no data-parallel schedule: refuse instead
         # of running the teacher-forced one
         raise NotImplementedError("data parallel training of the free-running decoder (teacher_forcing=False) is not "
                                   "supported: train it on one device")
-    if getattr(model, "scheduled_sampling", None) is not None:
+    if model.scheduled_sampling is not None:
         # nic.NIC / lc_nic.NIC(scheduled_sampling=...) have no data-parallel schedule either
         raise NotImplementedError("data parallel training with scheduled sampling is not supported: train it on one device")
-    if getattr(model, "self_critical", None) is not None:
+    if model.self_critical is not None:
         # nic.NIC(self_critical=...): the step's host round trip has no data-parallel schedule
         raise NotImplementedError("data parallel self-critical training is not supported: train it on one device")
     if model.average is not None:
@@ -438,7 +440,7 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.loss_normalise == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)
-    if model.__dict__.get("attention_coverage") is not None:
+    if model.attention_coverage is not None:
         # lc_nic.NIC(attention_coverage=...): the sum over the batch axis is not a per-rank quantity
         raise NotImplementedError(model.COVERAGE_DP_REFUSAL)
     world = dist.get_world_size() if world is None else world

@@ -79,6 +79,7 @@ class NICfc(_DenseNIC):
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
+        self._init_step_state()
 
     # ------------------------------------------------------------------ weights
     def _init_weights(self, rng):
@@ -134,7 +135,7 @@ class NICfc(_DenseNIC):
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
-        if self.optimizer is not None and getattr(self, "opt_m", None) is None:
+        if self.optimizer is not None and self.opt_m is None:
             self._init_optimizer_state()
         self.built = True
 

@@ -24,7 +24,7 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN, S_LSTM_IN, S_LSTM_OUT, S_SS_COIN,
                          S_SS_DRAW, BN_EPS, BN_MOMENTUM, ScheduledSampling, check_sampling, check_length_penalty,
-                         _TokenChoice, _BeamDecode, AttentionCoverage)
+                         _TokenChoice, _BeamDecode, AttentionCoverage, StepRoute)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -67,12 +67,23 @@ def compact_groups(groups):
 class NIC(ModelBase):
     H = 256     # dense_inter width, hard-coded at lc_NIC.py:141
     PIECE = 64  # voxels per encoder workgroup (split mode)
+    # ---- A/B switches of this model (ModelBase declares the shared ones; same rules)
+    use_lc_seq = True           # False: the per-step attention / LSTM launches instead of the forward chain; INTEGRATION.md 4, tests/test_gpu_fullsize.py
+    use_lc_seq_bwd = True       # False: the same for the backward chain; INTEGRATION.md 4
+    branch_streams = False      # True (with use_side_streams): text and front branch of the backward in parallel; tools/probe/branch_ab.py
+    split_encoder = True        # False: one workgroup per region instead of 64-voxel pieces; tools/probe/ld_split_ab.py
+    voxel_major = True          # False: the split encoder reads the batch-major betas; a tool sets it by name (tools/ab_bench_att.py voxel_major=0)
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
                  teacher_forcing=True, scheduled_sampling=None, attention_coverage=None, **kw):
         super().__init__(**kw)
+        # ---- what exists only once a step or a decode has asked for it
+        self.lc_xch = None              # exchange space of the persistent backward chain (_build)
+        self.ew = None                  # train_step_sam's weight offset e(w)
+        self._att_fb = None             # (scratch, shape) of the fused attention front backward (_bwd_front)
+        self._dec_s = {}                # the decodes' attention-score buffers per (B, max_len)
         # attention_coverage (model_base.AttentionCoverage): train_step differentiates CE + L2 + weight * coverage and the
         # steps report ``coverage`` (_coverage_launch); None or weight 0 builds nothing and issues no launch
         if attention_coverage is not None and not isinstance(attention_coverage, AttentionCoverage):
@@ -325,9 +336,9 @@ class NIC(ModelBase):
         self.met = f(8 + 4 * self.S)
         self._init_seq_lstm(B, U)        # device census + sync state of the persistent chain kernels (tnt_lc_seq_{fwd,bwd}_f32)
         self.lc_xch = None                # exchange space of the persistent backward chain
-        if self.__dict__.get("_seq_lstm") and hasattr(self.be, "lc_seq_bwd") and B <= 128:
+        if self._seq_lstm and hasattr(self.be, "lc_seq_bwd") and B <= 128:
             self.lc_xch = f(self.be.lc_seq_bwd_work_floats(B, U))
-        if self.__dict__.get("_seq_lstm") and hasattr(self.be, "lc_seq_fwd") and B <= 128:
+        if self._seq_lstm and hasattr(self.be, "lc_seq_fwd") and B <= 128:
             self.lc_fwd_work = f(self.be.lc_seq_fwd_work_floats(B))
         self.colB = f(2 * B)
         # backward
@@ -360,11 +371,12 @@ class NIC(ModelBase):
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
-        if self.optimizer is not None and getattr(self, "opt_m", None) is None:
+        if self.optimizer is not None and self.opt_m is None:
             self._init_optimizer_state()
         self.built = True
 
     def _stage_inputs(self, data):
+        self._route = StepRoute()
         x, cap, a0, c0 = data[:4]
         cap_t = self._to_dev(cap, torch.int32)
         if cap_t.dim() == 1:
@@ -396,8 +408,8 @@ class NIC(ModelBase):
             if training and self.r_in > 0:
                 be.dropout(x, self.xd[r0:r1], Bs, self.n_in, self.ldx, 0, self.n_in, 0, self.r_in, sd, S_IN + off, 0, ds)
                 x = self.xd[r0:r1]
-            if self.NV > R and hasattr(be, "locally_dense_fwd_split") and getattr(self, "split_encoder", True):
-                vm = self.xT is not None and getattr(self, "voxel_major", True)
+            if self.NV > R and hasattr(be, "locally_dense_fwd_split") and self.split_encoder:
+                vm = self.xT is not None and self.voxel_major
                 be.locally_dense_fwd_split(self.xT[:, r0:r1] if vm else x, self.xT.shape[1] if vm else self.ldx, self.idx,
                                            self.vgoff, self.vreg, self.rfirst, self.NV, self.encW[q], self.encB[q],
                                            self.enc_pre[r0:r1], self.enc_y[r0:r1], self.enc_part, Bs, R, D, 0.2,
@@ -449,7 +461,7 @@ class NIC(ModelBase):
         # (tools/ab_attr.py attention use_lc_seq=False).  An earlier form that ran both phases on the same workgroups one
         # after the other was slower than the per-step launches (16.3 vs 15.6 us per step): attention and LSTM register sets
         # together spilled 58 VGPRs and half of each group idled through the attention phase.
-        return bool(self.__dict__.get("_seq_lstm") and getattr(self, "use_lc_seq", True) and not self.use_layer_norm
+        return bool(self._seq_lstm and self.use_lc_seq and not self.use_layer_norm
                     and hasattr(self.be, "lc_seq_fwd") and self.R <= (512 if max(self.A, self.D) <= 32 else 384)
                     and self.A % 4 == 0 and self.D % 4 == 0 and self.A <= 64 and self.D <= 64)
 
@@ -502,8 +514,8 @@ class NIC(ModelBase):
         input projection into XZ (one epilogue-free GEMM; the bias is added in the step kernel), the stored attention
         keep-masks.  ``fed``: None = teacher-forced, "ss" = scheduled sampling (always training), "naive" = free-running.
         Embedding + text Dropout are one launch when training with r_text > 0 and Et % 4 == 0 (_ss_check / _naive_check
-        guarantee the layout); the LSTM input mask rides in it when the fed modes have r_lstm > 0, and teacher-forced
-        only with `fused_text_masks` (D % 4 == 0 holds by construction), which the fed modes do not consult.  Otherwise
+        guarantee the layout); the LSTM input mask rides in it when r_lstm > 0 -- teacher-forced only where D % 4 == 0,
+        which the fed modes do not consult.  Otherwise
         the text Dropout covers all n = T*B rows, geometry (B, Et, 0), and the LSTM input mask all n rows with
         rows_per_site=B -- free-running: step 0's B rows only, without rows_per_site.  XZ is projected for all n rows
         teacher-forced, for step 0's B rows in the fed modes: their feedback launches write the later rows of ``text``
@@ -516,7 +528,7 @@ class NIC(ModelBase):
         emb = a.p("emb_text/embeddings")
         lstm_in_mask = training and self.r_lstm > 0 and not self.use_layer_norm
         if training and self.r_text > 0 and Et % 4 == 0:
-            ride = lstm_in_mask and (fed is not None or (D % 4 == 0 and getattr(self, "fused_text_masks", True)))
+            ride = lstm_in_mask and (fed is not None or D % 4 == 0)
             be.embedding_fwd_drop(emb, self.cap, None, self.text, B, T, Et, Et, V, self.r_text, sd, S_TEXT, 0, ds,
                                   mask2=(self.r_lstm, S_LSTM_IN, D + Et, D) if ride else None)
             lstm_in_mask = lstm_in_mask and not ride
@@ -530,7 +542,7 @@ class NIC(ModelBase):
             be.dropout(self.text, self.text, n, Et, Et, 0, D + Et, D, self.r_lstm, sd, S_LSTM_IN, 0, ds, rows_per_site=B)
         m = n if fed is None else B
         self.gemm_sk(self.text[:m], a.p("lstm/kernel")[D:], self.XZ[:m], m, 4 * U, Et, Et, 4 * U, 4 * U)
-        if training and self._keep_stored and not self.__dict__.get("_masks_staged"):
+        if training and self._keep_stored and not self._route.masks_staged:
             be.dropout_mask4(self.att_keep, B * self.R * self.A, T, self.r_attn, sd, S_ATTN, 0, ds)
 
     def _head_inter(self, h, inter, n, ipre=None):
@@ -559,31 +571,31 @@ class NIC(ModelBase):
             r_in = self.r_lstm if training else 0.0
             keep = self.att_keep if (training and self._keep_stored) else None
             # (with the Dropout behind the LSTM, :256, as a rider of the same launch: Hd leaves the chain with hs)
-            self._out_dropped = bool(training and self.r_lstm > 0 and (int(getattr(self, "fuse_out_drop", 3)) & 1))
+            out_dropped = bool(training and self.r_lstm > 0)
             be.lc_seq_fwd(self.F, self.P, a.p("attention/W2/kernel"), a.p("attention/W2/bias"), a.p("attention/V/kernel"),
                           a.p("attention/V/bias"), self.qpre, self.alpha, self.ctx, self.ctx_d, keep,
                           B * R * A // 4 if keep is not None else 0, self.XZ, Wl[:D], a.p("lstm/recurrent_kernel"),
                           a.p("lstm/bias"), self.Hs, self.Cs, self.gates, T, B, R, D, A, U, 0.2,
                           self.r_attn if training else 0.0, r_in, D + Et, self.seed, S_ATTN, S_LSTM_IN, self.drop_step,
                           self.lc_fwd_work, self.seq_sync, self._guard_out(),
-                          out_drop=(self.Hd, self.r_lstm, S_LSTM_OUT) if self._out_dropped else None)
+                          out_drop=(self.Hd, self.r_lstm, S_LSTM_OUT) if out_dropped else None)
         else:
-            self._out_dropped = False
+            out_dropped = False
             for i in range(T):                                                                  # :244-256
                 self._decode_step(i, B, training, xz_bias=a.p("lstm/bias"))
         hs = self.Hs[1:].view(n, U)
-        if self._out_dropped:
+        if out_dropped:
             hs = self.Hd
         elif training and self.r_lstm > 0:                                                      # :256
             be.dropout(hs, self.Hd, n, U, U, 0, U, 0, self.r_lstm, sd, S_LSTM_OUT, 0, ds, rows_per_site=B)
             hs = self.Hd
-        self._hs_used = hs
+        self._route.hs_used = hs
         self._head_inter(hs, self.inter, n, self.ipre)
         inter = self.inter
         self._tail.metric_parts_ready = False
         if training and self.r_out > 0:
             npart = be.attention_metric_parts(T, self.R) if hasattr(be, "dropout_metric") else 0
-            if (self.S == 1 and self._tail.deferring and getattr(self, "fuse_metric_rider", True) and H % 4 == 0
+            if (self.S == 1 and self._tail.deferring and H % 4 == 0
                     and 0 < npart <= self.metric_part.numel()):
                 # the attention metric's partials (:365-367) ride in this launch: alpha is complete behind the chain
                 be.dropout_metric(self.inter, self.inter_d, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds, self.alpha,
@@ -592,7 +604,7 @@ class NIC(ModelBase):
             else:
                 be.dropout(self.inter, self.inter_d, n, H, H, B, H, 0, self.r_out, sd, S_OUT, 0, ds)
             inter = self.inter_d
-        self._inter_used = inter
+        self._route.inter_used = inter
         self._head_out(inter, self.logits, n)
 
     COVERAGE_DP_REFUSAL = ("attention_coverage has no data-parallel schedule: the sum over the batch axis is not a per-rank "
@@ -689,9 +701,8 @@ class NIC(ModelBase):
                                        self.text[nxt], Et, self.XZ[nxt], 4 * U, B, self.r_lstm, sd, S_LSTM_IN + col, 0, ds,
                                        D + Et, D, ss.kind_id, ss.mode_id, self.ss_sched, self.adam_t, S_SS_COIN + t,
                                        S_SS_DRAW + t, self.r_text, S_TEXT, T * Et, col * Et)
-        self._hs_used = self.Hd if self.r_lstm > 0 else self.Hs[1:].view(T * B, U)
-        self._inter_used = self.inter_d if self.r_out > 0 else self.inter
-        self._out_dropped = False
+        self._route.hs_used = self.Hd if self.r_lstm > 0 else self.Hs[1:].view(T * B, U)
+        self._route.inter_used = self.inter_d if self.r_out > 0 else self.inter
         self._tail.metric_parts_ready = False      # the attention metric: _loss_metrics, behind the loop
 
     def _forward_naive(self, B, T, training):
@@ -728,9 +739,8 @@ class NIC(ModelBase):
                 be.greedy_feedback(self.logits[rows], ldV, V, emb, Et, Wl[D:], 4 * U, 4 * U, self.cap, T, i + 1, self.text[nxt],
                                    Et, self.XZ[nxt], 4 * U, B, self.r_lstm if lstm_in else 0.0, sd, S_LSTM_IN + i + 1, 0, ds,
                                    lwidth=D + Et, lcol0=D)
-        self._hs_used = self.Hd if (r_lo > 0 or r_o > 0) else self.Hs[1:].view(T * B, U)
-        self._inter_used = self.inter
-        self._out_dropped = False
+        self._route.hs_used = self.Hd if (r_lo > 0 or r_o > 0) else self.Hs[1:].view(T * B, U)
+        self._route.inter_used = self.inter
         self._tail.metric_parts_ready = False
 
     def _loss_metrics(self, B, T, want_grad):
@@ -739,7 +749,7 @@ class NIC(ModelBase):
         self._head_loss(B, T, want_grad)
         self._sum2(self.loss_row, self.met[0:1], self.corr_row, self.met[1:2], n, 1.0 / n)
         if self.S == 1:
-            npart = be.attention_metric_parts(T, self.R) if hasattr(be, "attention_metric_parts") else 0
+            npart = be.attention_metric_parts(T, self.R)
             t = self._tail
             if t.deferring and want_grad and 0 < npart <= self.metric_part.numel():
                 # fused single-process step: partials only, their total rides in the step-finalize launch
@@ -767,39 +777,38 @@ class NIC(ModelBase):
         self._bwd_chain(B, T)
         # the text branch (input Dropout', sparse Embedding scatter) and the front branch (attention parameters, BatchNorm,
         # region-wise encoder) only share the chain's outputs: with `branch_streams` they are two parallel branches of the step
-        with self.side(0 if getattr(self, "branch_streams", False) else -1):
+        with self.side(0 if self.branch_streams else -1):
             self._bwd_emb(B, T)
         self._bwd_front(B, T)
         self.join()
 
     def _bwd_head(self, B, T):
         """vocabulary head: gradients of time_distributed_softmax / time_distributed_nonlinear, dHs.  The free-running
-        step (teacher_forcing=False) has no Dropout between dense_inter and dense_out: its fused tail runs at rate 0 and
-        whatever `fused_head_tail` says, and the LSTM-output and the output Dropout' both act on dHs (lc_NIC.py:205-211)."""
+        step (teacher_forcing=False) has no Dropout between dense_inter and dense_out: its fused tail runs at rate 0, and the LSTM-output and the output Dropout' both act on dHs (lc_NIC.py:205-211)."""
         be, a = self.be, self.arena
         U, V, H, ldV = self.U, self.V, self.H, self.ldV
         n = T * B
         sd, ds = self.seed, self.drop_step
         naive = not self.teacher_forcing
-        dlog, inter, hs = self.logits, self._inter_used, self._hs_used         # (free-running: _inter_used is self.inter)
+        route = self._route
+        dlog, inter, hs = self.logits, route.inter_used, route.hs_used         # (free-running: inter_used is self.inter)
         tB, r_tail = (0, 0.0) if naive else (B, self.r_out)
         dhs_done = False
         # kernel gradient and input gradient of the softmax layer, the two independent readers of dlogits: ONE launch
-        if not (getattr(self, "g3_riders", True) and self.gemm3_pair(
+        if not (self.g3_riders and self.gemm3_pair(
                 dict(A=inter, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=H, N=V, K=n, lda=H, ldb=ldV, ldc=ldV, transA=True),
                 dict(A=dlog, B=a.p("time_distributed_softmax/kernel"), C=self.dinter, M=n, N=H, K=V, lda=ldV, ldb=ldV, ldc=H,
                      transB=True))):
             self.gemm_sk(inter, dlog, a.g("time_distributed_softmax/kernel"), H, V, n, H, ldV, ldV, transA=True)
             self.gemm_sk(dlog, a.p("time_distributed_softmax/kernel"), self.dinter, n, H, V, ldV, ldV, H, transB=True)
-        if ((naive or getattr(self, "fused_head_tail", True)) and hasattr(be, "bias_act_drop_bwd") and n <= 2048
-                and H % 4 == 0):
+        if n <= 2048 and H % 4 == 0:
             # dropout' + LeakyReLU' + the nonlinear layer's bias gradient in one pass over dinter, with the softmax layer's
             # bias gradient (column sums of dlogits) riding in the same launch: 1 launch instead of 4
             be.bias_act_drop_bwd(self.dinter, self.ipre, self.dinter, a.g("time_distributed_nonlinear/bias"), n, H, H,
                                  ACT_LEAKY, 0.2, tB, H, 0, r_tail, sd, S_OUT, ds,
                                  extra=(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV))
             # kernel gradient and input gradient of the nonlinear layer, the two readers of dinter: ONE launch
-            if getattr(self, "g3_riders", True) and self.gemm3_pair(
+            if self.g3_riders and self.gemm3_pair(
                     dict(A=hs, B=self.dinter, C=a.g("time_distributed_nonlinear/kernel"), M=U, N=H, K=n, lda=U, ldb=H, ldc=H,
                          transA=True, small=True),
                     dict(A=self.dinter, B=a.p("time_distributed_nonlinear/kernel"), C=self.dHs, M=n, N=U, K=H, lda=H, ldb=H, ldc=U,
@@ -818,11 +827,11 @@ class NIC(ModelBase):
             self.gemm_sk(self.dinter, a.p("time_distributed_nonlinear/kernel"), self.dHs, n, U, H, H, H, U, transB=True)
         r_lo, r_o = self.r_lstm, self.r_out
         if not naive:
-            self._dout_masked = not (r_lo > 0 and self._lc_seq_bwd_ok() and (int(getattr(self, "fuse_out_drop", 3)) & 2))
-            if r_lo > 0 and self._dout_masked:              # (else Dropout' rides in the backward chain: tnt_lc_seq_bwd_drop_f32)
+            route.dout_masked = not (r_lo > 0 and self._lc_seq_bwd_ok())
+            if r_lo > 0 and route.dout_masked:              # (else Dropout' rides in the backward chain: tnt_lc_seq_bwd_drop_f32)
                 be.dropout(self.dHs, self.dHs, n, U, U, 0, U, 0, r_lo, sd, S_LSTM_OUT, 0, ds, rows_per_site=B)
             return
-        self._dout_masked = True            # both masks are applied here, none rides in the backward chain
+        route.dout_masked = True            # both masks are applied here, none rides in the backward chain
         if r_lo > 0 and r_o > 0:
             be.dropout2(self.dHs, self.dHs, n, U, U, (0, U, 0, B, r_lo, S_LSTM_OUT), (0, U, 0, B, r_o, S_NOUT), sd, 0, ds)
         elif r_lo > 0 or r_o > 0:
@@ -831,8 +840,7 @@ class NIC(ModelBase):
 
     def _lc_seq_bwd_ok(self):
         """the persistent backward-chain kernel applies (tnt_lc_seq_bwd_f32: the forward chain's shape limits)."""
-        return bool(not self.use_layer_norm and self._lc_seq_ok() and self.__dict__.get("lc_xch") is not None
-                    and getattr(self, "use_lc_seq_bwd", True))
+        return bool(not self.use_layer_norm and self._lc_seq_ok() and self.lc_xch is not None and self.use_lc_seq_bwd)
 
     def _bwd_chain(self, B, T):
         """the T-step chain (LSTM step backward -> attention step backward) and the LSTM parameter gradients."""
@@ -843,6 +851,8 @@ class NIC(ModelBase):
         # no zero fill of dP / dF / dvb: the first executed step (i = T-1) overwrites them (fresh)
         Wl, Ur = a.p("lstm/kernel"), a.p("lstm/recurrent_kernel")
         W2, v = a.p("attention/W2/kernel"), a.p("attention/V/kernel")
+        route = self._route
+        route.dtext_done = route.dw2_done = False
         if self.use_layer_norm:
             return self._bwd_chain_ln(B, T)
         if self._lc_seq_bwd_ok():
@@ -853,31 +863,30 @@ class NIC(ModelBase):
                           self.dP, self.dF, self.dvb, self.dqpre, Ur, Wl[:D], self.dHs, self.gates, self.Cs, self.dZ,
                           self.lc_xch, T, B, R, D, A, U, 0.2, self.r_attn, self.r_lstm, D + Et, sd, S_ATTN, S_LSTM_IN, ds,
                           self._alpha_mse, self.seq_sync, self._guard_out(),
-                          out_drop=None if self.__dict__.get("_dout_masked", True) else (self.r_lstm, S_LSTM_OUT),
+                          out_drop=None if route.dout_masked else (self.r_lstm, S_LSTM_OUT),
                           **({} if self.attention_coverage is None
                              else dict(ext=(self.cov_ext,) + self.attention_coverage.strides(R))))
         else:
             self._bwd_chain_steps(B, T, Wl, Ur, W2, v)
         hprev = self.Hs[:T].view(n, U)
         gWl = a.g("lstm/kernel")
-        self._dtext_done = False
-        if getattr(self, "g3_riders", True) and Et == U and self.gemm3_pair(
+        if self.g3_riders and Et == U and self.gemm3_pair(
                 dict(A=hprev, B=self.dZ, C=a.g("lstm/recurrent_kernel"), M=U, N=4 * U, K=n, lda=U, ldb=4 * U, ldc=4 * U, transA=True,
                      colsum=a.g("lstm/bias"), A2=self.text, C2=gWl[D:]),
                 dict(A=self.dZ, B=Wl[D:], C=self.dtext, M=n, N=Et, K=4 * U, lda=4 * U, ldb=4 * U, ldc=Et, transB=True)):
             # the four readers of dZ that fill the chip -- recurrent-kernel gradient, the text rows of the kernel gradient (+ the
             # bias gradient as a rider) and the text-input gradient (_bwd_emb finds it done) -- in ONE launch
-            self._dtext_done = True
+            route.dtext_done = True
             # ... and the two small kernel gradients that only need the chain's outputs -- the context rows of the LSTM kernel
             # and the attention's W2 -- in one launch behind it
-            self._dw2_done = bool(self.gemm3_pair(
+            route.dw2_done = bool(self.gemm3_pair(
                 dict(A=self.ctx_d, B=self.dZ, C=gWl[:D], M=D, N=4 * U, K=n, lda=D, ldb=4 * U, ldc=4 * U, transA=True, small=True),
                 dict(A=hprev, B=self.dqpre, C=a.g("attention/W2/kernel"), M=U, N=A, K=n, lda=U, ldb=A, ldc=A, transA=True,
                      small=True)))
-            if not self._dw2_done:
+            if not route.dw2_done:
                 self.gemm_sk(self.ctx_d, self.dZ, gWl[:D], D, 4 * U, n, D, 4 * U, 4 * U, transA=True)
             return
-        if getattr(self, "g3_riders", True) and Et == U and self.gemm3(
+        if self.g3_riders and Et == U and self.gemm3(
                 hprev, self.dZ, a.g("lstm/recurrent_kernel"), U, 4 * U, n, U, 4 * U, 4 * U, transA=True,
                 colsum=a.g("lstm/bias"), A2=self.text, C2=gWl[D:]):
             # recurrent-kernel gradient, the text rows of the kernel gradient and the bias gradient in ONE launch: the two
@@ -902,7 +911,7 @@ class NIC(ModelBase):
             ext = {} if cov is None else dict(ext=self.cov_ext[i * ext_ts:], ext_bs=ext_bs)
             # dctx_i = dZ_i @ Wc^T: every LSTM-backward workgroup leaves the partial of its 16 units, the attention
             # backward sums the U/16 parts (instead of running the whole product per sample on its own critical path)
-            parts = (U // 16) * D <= 1024 and getattr(self, "ctx_parts", True)
+            parts = (U // 16) * D <= 1024
             be.lstm_step_bwd(None if last else self.dZ[(i + 1) * B:(i + 2) * B], Ur, None,
                              None if last else self.dh_att, None if last else self.dc, None,
                              self.dHs[i * B:(i + 1) * B], None, 0, 0, self.gates[i], self.Cs[i + 1], self.Cs[i],
@@ -971,11 +980,10 @@ class NIC(ModelBase):
         sd, ds = self.seed, self.drop_step
         naive = not self.teacher_forcing
         Wl = a.p("lstm/kernel")
-        if not self.__dict__.pop("_dtext_done", False):
+        if not self._route.dtext_done:
             self.gemm_sk(self.dZK if self.use_layer_norm else self.dZ, Wl[D:], self.dtext, n, Et, 4 * U, 4 * U, 4 * U, Et, transB=True)
         lstm_in = self.r_lstm > 0 and not self.use_layer_norm
-        if (not naive and lstm_in and self.r_text > 0 and Et % 4 == 0 and D % 4 == 0 and hasattr(be, "dropout2")
-                and getattr(self, "fused_text_masks", True)):
+        if not naive and lstm_in and self.r_text > 0 and Et % 4 == 0 and D % 4 == 0:
             # the LSTM input mask and the Embedding Dropout of the text rows in one pass
             be.dropout2(self.dtext, self.dtext, n, Et, Et, (0, D + Et, D, B, self.r_lstm, S_LSTM_IN),
                         (B, Et, 0, 0, self.r_text, S_TEXT), sd, 0, ds)
@@ -987,7 +995,7 @@ class NIC(ModelBase):
                 be.dropout(self.dtext[:B], self.dtext[:B], B, Et, Et, 0, T * Et, 0, self.r_text, sd, S_TEXT, 0, ds)
             elif self.r_text > 0:
                 be.dropout(self.dtext, self.dtext, n, Et, Et, B, Et, 0, self.r_text, sd, S_TEXT, 0, ds)
-        self._emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
+        self._route.emb_rows = (self.dtext, n, Et, Et, "emb_text/embeddings")
         self._embedding_bwd(self.dtext, self.cap, "emb_text/embeddings", B, T, Et, Et, V)
 
     def _bwd_front(self, B, T):
@@ -998,26 +1006,26 @@ class NIC(ModelBase):
         sd, ds = self.seed, self.drop_step
         hprev = self.Hs[:T].view(n, U)
         # attention parameters
-        if not self.__dict__.pop("_dw2_done", False):
+        if not self._route.dw2_done:
             self.gemm_sk(hprev, self.dqpre, a.g("attention/W2/kernel"), U, A, n, U, A, A, transA=True)
         jobs = [(self.dqpre, a.g("attention/W2/bias"), n, A, A), (self.dvb, a.g("attention/V/kernel"), B, A, A + 1),
                 (self.dvb.view(-1)[A:], a.g("attention/V/bias"), B, 1, A + 1)]
-        if hasattr(be, "colsum_multi") and n <= 2048 and B <= 2048:
+        if n <= 2048 and B <= 2048:
             be.colsum_multi(jobs)                     # the three small bias-type gradients of the attention layer: one launch
         else:
             for x, out, rows, C, ld in jobs:
                 be.colsum(x, out, rows, C, ld, self.work)
         fdrop = None                                   # (rate, seed, site, step_dev) of the Dropout' folded into the dF pass
-        if getattr(self, "fused_att_front", True) and hasattr(be, "attention_front_bwd") and D == 32 and A == 32:
+        if D == 32 and A == 32:
             # LeakyReLU' + bias gradient + W1 gradient + the dF contribution of the hoisted Dense in two launches instead of five
-            fb = self.__dict__.get("_att_fb")
+            fb = self._att_fb
             if fb is None or fb[1] != (B * R, D, A):
                 if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("attention front-backward scratch must be built outside a graph capture")
                 fb = self._att_fb = (self._f(be.attention_front_bwd_parts(B * R, D, A)), (B * R, D, A))
             # dF is finished by this launch: the backward of the LAST feature Dropout (one site over all B*R rows: the
             # deepest stage's, or the single-subject encoder's) rides in its dF pass
-            if self.r_feat > 0 and getattr(self, "fused_bn_drop", True) and (self.depth > 0 or self.S == 1):
+            if self.r_feat > 0 and self.fused_bn_drop and (self.depth > 0 or self.S == 1):
                 fdrop = (self.r_feat, sd, S_DEEP + self.depth - 1 if self.depth > 0 else S_FEAT, ds)
             be.attention_front_bwd(self.Ppre, self.dP, self.F, a.p("attention/W1/kernel"), self.dF,
                                    a.g("attention/W1/kernel"), a.g("attention/W1/bias"), fb[0], B * R, D, A, 0.2, drop=fdrop)
@@ -1069,8 +1077,8 @@ class NIC(ModelBase):
             if not acted:
                 be.act_bwd(self.enc_pre[r0:r1], dbn, dbn, Bs * R * D, ACT_LEAKY, 0.2)
             x = (self.xd if self.r_in > 0 else self.x)[r0:r1]
-            if self.NV > R and hasattr(be, "locally_dense_bwd_split") and getattr(self, "split_encoder", True):
-                vm = self.xT is not None and getattr(self, "voxel_major", True)
+            if self.NV > R and hasattr(be, "locally_dense_bwd_split") and self.split_encoder:
+                vm = self.xT is not None and self.voxel_major
                 be.locally_dense_bwd_split(self.xT[:, r0:r1] if vm else x, self.xT.shape[1] if vm else self.ldx, self.idx,
                                            self.vgoff, self.vreg, self.vfirst, self.NV, dbn, self.encWg[q], self.encBg[q],
                                            Bs, R, D, voxel_major=vm)
@@ -1088,7 +1096,7 @@ class NIC(ModelBase):
         self._backward(B, T)
 
     def _stage_mask_job(self):
-        if not (self._keep_stored and getattr(self, "stage_masks", True)):
+        if not self._keep_stored:
             return None
         B, T = self._shape
         return (self.att_keep, B * self.R * self.A, T, self.r_attn, self.seed, S_ATTN, self.drop_step)
@@ -1109,8 +1117,8 @@ class NIC(ModelBase):
                 self._lr_metric(out)                                          # computed on the device: read from there
             else:
                 out["lr"] = torch.tensor(self._lr_host, dtype=torch.float32)  # host-set (ModelBase._sync_lr): no device copy
-        out._ring = self.__dict__.get("_last_ring")
-        return out.guarded(self, m[self.GUARD]) if self.__dict__.get("_seq_lstm") else out
+        out._ring = self._last_ring
+        return out.guarded(self, m[self.GUARD]) if self._seq_lstm else out
 
     def train_step(self, data):
         """lc_NIC.train_step (lc_NIC.py:328-408): returns {loss, L2, accuracy, attention, lr}."""
@@ -1122,7 +1130,6 @@ class NIC(ModelBase):
         self._coverage_check()                      # (grad_sync may have been attached since the constructor)
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
         self._ss_refuse(T)
-        self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
         ring = False
         if self.grad_sync is None:
@@ -1158,10 +1165,9 @@ class NIC(ModelBase):
             raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
                                       "gradient of its first pass): not built for attention_coverage")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
-        self._masks_staged = self._stage_mask_job() is not None
         self._sync_lr()
         be, a = self.be, self.arena
-        if self.__dict__.get("ew") is None:
+        if self.ew is None:
             self.ew = torch.zeros_like(a.theta)
         n_alpha = T * B * self.R
 
@@ -1191,7 +1197,6 @@ class NIC(ModelBase):
     def test_step(self, data):
         """lc_NIC.test_step (lc_NIC.py:410-459)."""
         B, T = self._stage_batch(data[0], data[1], self.n_in)
-        self._masks_staged = False
 
         # ms2_NIC.test_step calls its sub-models with training=True (ms2_NIC.py:419,426) -- quirk kept
         train_flag = self.S > 1
@@ -1218,7 +1223,6 @@ class NIC(ModelBase):
     def call_attention(self, data, training=False):
         """lc_NIC.call_attention (lc_NIC.py:223-263): returns (probabilities (B,T,V), attention scores (T,B,R,1))."""
         B, T = self._stage_inputs(data)
-        self._masks_staged = False
 
         def run():
             self._forward(B, T, training)
@@ -1232,7 +1236,6 @@ class NIC(ModelBase):
         over the logits (include/tnt_hip.h: tnt_greedy_feedback_f32)."""
         self._naive_check()
         B, T = self._stage_inputs(data)
-        self._masks_staged = False
 
         def run():
             self._forward_naive(B, T, training)
@@ -1289,7 +1292,7 @@ class NIC(ModelBase):
         choice.start.copy_(start.view(B, 1))
         s_all = None
         if return_s:
-            sbufs = self.__dict__.setdefault("_dec_s", {})
+            sbufs = self._dec_s
             if (B, max_len) not in sbufs:
                 sbufs[B, max_len] = self._f(max_len, B, self.R, self.A)
             s_all = sbufs[B, max_len]

@@ -10,7 +10,8 @@ launches and owns buffers; it contains no arithmetic of the hot path.
 import time
 from collections import OrderedDict
 from contextlib import contextmanager, nullcontext
-from typing import NamedTuple, Optional
+from dataclasses import dataclass
+from typing import Any, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -319,7 +320,7 @@ class _ConstrainedDecode:
     the bad_ids buffer on the device, the per-step launch, and the suffix of the capture key."""
 
     def __init__(self, model, c, rows, max_len, end_id):
-        bufs = model.__dict__.setdefault("_con_bufs", {})
+        bufs = model._decode_bufs("_con_bufs")
         if (rows, max_len) not in bufs:
             bufs[rows, max_len] = torch.zeros(2, rows, max_len, dtype=torch.int32, device=model.device)
         if "bad" not in bufs:
@@ -408,7 +409,7 @@ class _ConsensusDecode:
     def _setup(self, model, G, M, k):
         self.be, self.V, self.ldV, self.G, self.M, self.k = model.be, model.V, model.ldV, G, M, k
         self.Rm, self.rows = M * k, G * M * k
-        self._bufs = model.__dict__.setdefault("_cons_bufs", {})
+        self._bufs = model._decode_bufs("_cons_bufs")
         self._model = model
 
     def bufs(self, max_len, steps):
@@ -642,7 +643,7 @@ class _TokenChoice:
             self.start, self.probs, self.ids = cb["start"], cb["mix"], cb["ids"]
             self.pick, self.member_logits = cb["pick"], cb["logits"]
         else:
-            bufs = model.__dict__.setdefault("_dec_bufs", {})
+            bufs = model._dec_bufs
             if (rows, max_len) not in bufs:
                 f, i32 = model._f, torch.int32
                 bufs[rows, max_len] = (f(rows, 1, dtype=i32), f(max_len, rows, ldV), f(max_len, rows, dtype=i32))
@@ -906,7 +907,58 @@ class StepTail:
         return {k: getattr(self, k) for k in self.FINALIZE if getattr(self, k) is not None}
 
 
+@dataclass
+class StepRoute:
+    """What one method of a forward / backward pass tells a later method of the same pass: which route it took, and which
+    of its buffers the later one reads.  StepTail is what the pass leaves to the update; this is what the pass tells
+    itself.  Lifetime: ``model._route`` is replaced by an empty record where a batch is staged (_stage_batch, the models'
+    _stage_inputs, nic.NIC._stage_scst), so nothing is inherited from a step that failed midway, and nowhere else: not
+    between the forward and the backward of a step, nor between the separately recorded segments of a data-parallel step.
+    Every field holds its "nothing handed over" value until its producer sets it."""
+    # ---- the staging launch -> the step
+    head_map_fresh: bool = False    # _stage_batch built the head's row map (compact_head) -> nic.NIC.train_step, _forward,
+    #                                 _loss_metrics, _bwd_head, _bwd_seq_lstm: Out, logits and dlogits hold the distinct rows
+    stage_fwd_done: bool = False    # _stage_batch ran the encoder forward too (stage_fwd) -> nic.NIC.train_step, _forward
+    masks_staged: bool = False      # _stage_batch generated the stored attention keep-masks -> lc_nic.NIC._text_front
+    # ---- forward -> backward
+    xin_used: Any = None            # nic.NIC._forward: the LSTM input it fed (Xin or Xin_d) -> _bwd_seq_lstm
+    hs_used: Any = None             # lc_nic.NIC._forward*: the LSTM output the head read (Hs or Hd) -> _bwd_head
+    inter_used: Any = None          # lc_nic.NIC._forward*: what dense_out read (inter or inter_d) -> _bwd_head
+    # ---- backward -> backward
+    colsum_deferred: Any = None     # nic.NIC._bwd_head: the head-bias column sums' arguments, not issued -> _bwd_seq_lstm
+    dxin_done: bool = False         # nic.NIC._bwd_seq_lstm: its pair launch formed dXin -> _bwd_seq_front
+    dout_masked: bool = True        # lc_nic.NIC._bwd_head applied the LSTM-output Dropout' to dHs (False: it rides in the
+    #                                 backward chain) -> _bwd_chain
+    dtext_done: bool = False        # lc_nic.NIC._bwd_chain: its pair launch formed dtext -> _bwd_emb
+    dw2_done: bool = False          # lc_nic.NIC._bwd_chain: its second pair launch formed the W2 gradient -> _bwd_front
+    emb_rows: Any = None            # the models' Embedding backward: (row gradients [n][E], n, E, ld, arena name) -> _apply_agc
+
+
 class ModelBase:
+    # ---- A/B switches: class attributes, set on a model (``model.name = value``) before its first step.  Each is declared
+    # here once with its default; the comment names the other arm and who sets it.  Tools that take switch names from their
+    # command line refuse a name no model class declares (tools/switches.py).
+    use_gemm3 = True            # False: vendor-library routing (hipBLASLt head, rocBLAS LSTM products); INTEGRATION.md 4, tools/probe/dp_w1_diff.py
+    g3_riders = True            # False: bias sums and paired products as launches of their own; tools/probe/dp_w1_diff.py
+    g3_force = None             # {(M, N, K, tA, tB, batch): (tile, splitk)}: a gemm3 plan forced per shape; tools/pair_scan.py, tests
+    g3_min_flops = 3e7          # products below it keep the tiled split-K kernel; tests/test_gpu_compact_head.py
+    use_blas = True             # False (with use_gemm3 = False): the round-1 hand-written kernels; INTEGRATION.md 4
+    lt_min_flops = 1e9          # hipBLASLt takes the vocabulary-sized products above it (use_gemm3 = False); tools/lt_tune.py
+    use_side_streams = False    # True: independent gradient GEMMs on side streams (measured slower); tools/side_bench.py
+    fused_update = True         # False: the unfused step tail (sum2, seg_sqnorm, step_tick, adam); INTEGRATION.md 4, tools/ab_attr.py
+    fused_finalize = True       # False: the scalar tail as its own launch (step_finalize); INTEGRATION.md 4, tools/step_breakdown.py
+    fused_bn_drop = True        # False: the Dropout / LeakyReLU' beside a BatchNorm as launches of their own; tests/dev_grad_margin.py
+    sparse_emb_bwd = True       # False: the dense Embedding backward (and a hipGraph, not a launch plan); INTEGRATION.md 4
+    plan_step = True            # False: the single-process step replays as a hipGraph; tools/probe/plan_bench.py
+    metric_ring = True          # False: a clone of the metrics buffer behind every step; INTEGRATION.md 4, bench.py
+    sync_bn = False             # True: BatchNorm statistics over the global batch; dp.attach(sync_bn=True)
+    use_seq_lstm = True         # False: the per-step LSTM kernels; INTEGRATION.md 4, disable_seq_lstm()
+
+    # the static buffers of _ConstrainedDecode and of _ConsensusDecode / _GuidanceDecode: a dict on the instance from the first
+    # such decode on (_decode_bufs).  Not made in the constructor: the tests tell "this model never ran one" by the instance
+    # not having the attribute
+    _con_bufs = _cons_bufs = None
+
     GUARD = 7       # slot of ``met`` that carries the device guard word of the step (see Metrics)
     METRIC_RING = 1024      # rows of the metrics ring: a step's Metrics stay readable for this many further training steps
     SUPPORTS_LABEL_SMOOTHING = True     # False where the step does not go through the compile loss (ThinkAndTell generators)
@@ -942,10 +994,39 @@ class ModelBase:
         self._fin_arrive = None             # arrival counters of the update launch that carries the finalize work
         self._fin_descs = {}                # its descriptors (finalize_desc), one per distinct argument set
         self._tail = StepTail()             # what a fused step's launches leave to its update (_deferring, _update_fused)
+        self._route = StepRoute()           # what a pass tells itself; replaced where a batch is staged
         self.built = False
         self.stop_training = False
         self._graphs = {}
         self._lr_host = None
+        # ---- what the model's constructor or its first build replaces
+        self.V = None                       # vocabulary size
+        self.S = 1                          # subjects (lc_nic.NIC(n_subjects=...))
+        self.xT = None                      # lc_nic.NIC: the voxel-major copy of the staged betas, where its encoder reads one
+        self.teacher_forcing = True         # lc_nic.NIC(teacher_forcing=False): the free-running decoder
+        self.scheduled_sampling = None      # nic.NIC / lc_nic.NIC(scheduled_sampling=...)
+        self.self_critical = None           # nic.NIC(self_critical=...)
+        self.attention_coverage = None      # lc_nic.NIC(attention_coverage=...)
+        self.met = None                     # the metrics buffer (_build)
+        # ---- state that exists only once something has asked for it
+        self.opt_m = self.opt_avg = None    # the optimizer's first slot and the weight average (_init_optimizer_state)
+        self._seq_lstm = False              # the persistent LSTM chain is in use (_init_seq_lstm)
+        self.seq_sync = self.seq_xch = None  # its sync state / error word and the BPTT chain's exchange buffer
+        self.met_ring = None                # the metrics ring (_ring_args), with ring_t and _ring_host
+        self._last_ring = None              # (row, tag) of the ring row the last step's metrics are views of
+        self._ring_keys = set()             # the step keys whose update launch files the metrics in the ring (_run_step)
+        self._g3_work = self._g3_sync = None    # gemm3's split-K exchange space and error word (_g3_space)
+        self._g3_plans = {}                 # (M, N, K, tA, tB, batch, colsum) -> (tile, splitk)
+        self._g3_descs = {}                 # gemm3_pair descriptors, one pair per distinct argument set
+        self._skw = {}                      # split-K workspaces of the side branches (gemm_sk(ws=...))
+        self._side_streams = {}             # side(i)'s streams
+        self._side_used = set()             # ... and the ones join() has to wait for
+        self._bn_buf = None                 # synchronised BatchNorm's gather scratch (_bn_scratch)
+        self._emb_state = None              # ((B, T, name), prev_ids, norm partials, nparts) of the Embedding backward
+        self._agc_tab = None                # arena.AgcTable (_apply_agc)
+        self._step_word = None              # the device word a captured sampled decode reads its stream step from
+        self._score = None                  # score_captions' buffers (_score_state)
+        self._dec_bufs = {}                 # _TokenChoice's static buffers per (rows, max_len)
 
     # ------------------------------------------------------------------ keras surface
     def compile(self, optimizer=None, loss=None, *metrics, run_eagerly=True, **kw):
@@ -954,7 +1035,7 @@ class ModelBase:
         if eps > 0 and not self.SUPPORTS_LABEL_SMOOTHING:
             raise NotImplementedError(f"{type(self).__name__} computes its own masked sparse loss and does not read the "
                                       "compile loss: label_smoothing > 0 is not implemented for it")
-        if eps > 0 and getattr(self, "self_critical", None) is not None:
+        if eps > 0 and self.self_critical is not None:
             raise ValueError("label_smoothing > 0 does not apply to a self_critical model: its loss is the "
                              "advantage-weighted tnt_scst_cce_f32, not the compile loss")
         alpha = loss_unlikelihood(loss)
@@ -964,11 +1045,11 @@ class ModelBase:
         if alpha > 0 and eps > 0:
             raise ValueError("unlikelihood > 0 together with label_smoothing > 0 is not implemented: one head kernel "
                              "computes one of the two")
-        if alpha > 0 and getattr(self, "self_critical", None) is not None:
+        if alpha > 0 and self.self_critical is not None:
             raise ValueError("unlikelihood > 0 does not apply to a self_critical model: its loss is the "
                              "advantage-weighted tnt_scst_cce_f32, not the compile loss")
         gamma, mode = loss_focal_gamma(loss), loss_normalise(loss)
-        cw = loss_class_weight(loss, getattr(self, "V", None))
+        cw = loss_class_weight(loss, self.V)
         self._check_token_weights(cw is not None, gamma, mode, eps, alpha)
         avg = optimizer_average(optimizer)
         if avg is not None and self.grad_sync is not None:
@@ -1003,12 +1084,12 @@ class ModelBase:
         if eps > 0 or alpha > 0:
             raise ValueError(f"{what} together with label_smoothing > 0 or unlikelihood > 0 is not implemented: one head "
                              "kernel computes one of them")
-        if getattr(self, "self_critical", None) is not None:
+        if self.self_critical is not None:
             raise ValueError(f"{what} does not apply to a self_critical model: its loss is the advantage-weighted "
                              "tnt_scst_cce_f32, not the compile loss")
         if mode == "weights" and (self.grad_sync is not None or self.dp_world > 1):
             raise NotImplementedError(self.WEIGHTS_DP_REFUSAL)
-        if mode == "weights" and int(getattr(self, "S", 1)) > 1:
+        if mode == "weights" and int(self.S) > 1:
             raise NotImplementedError("normalise=\"weights\" with n_subjects > 1 is not implemented: the per-subject metrics "
                                       "divide each subject's sums by its position count Bs * T, not by its weight sum.  "
                                       "normalise=\"count\" works")
@@ -1325,7 +1406,7 @@ class ModelBase:
             s1 = sp.first_host[self.arena.entries[enc.name].seg + 1]
         # no finalize launch (tnt_adam_fin_f32): the norm launch leaves lr_t, the update launches sum the clip norms they need
         # from the span partials themselves, one extra workgroup of the Adam launch files the scalars, the counters tick at its end
-        fin = adam and hasattr(self.be, "adam_fin") and getattr(self, "fused_finalize", True)
+        fin = adam and hasattr(self.be, "adam_fin") and self.fused_finalize
         fin = self._fused_norms(enc, s1, fin)
         self._fused_updates(l2_out, enc, s1, fin, self._finalize_args(tail))
 
@@ -1405,14 +1486,14 @@ class ModelBase:
         G replicas x local batch train exactly like one process on the concatenated batch.  The reference has no
         counterpart (it trains on one device); per-replica statistics remain the default.  The collectives sit inside
         the forward / backward pass, so dp.attach puts such a model on the generic (non-pipelined, eager) schedule."""
-        return bool(getattr(self, "sync_bn", False) and self.dp_world > 1)
+        return bool(self.sync_bn and self.dp_world > 1)
 
     def _bn_fwd(self, x, gamma, beta, mov_mean, mov_var, y, xhat, inv_std, rows, C, ldy, training, work, drop=None):
         """drop = (rate, seed, site, step_dev), training only: the Dropout over y that follows the normalisation, fused into
         the apply pass where the backend offers it (returns True when it was applied)"""
         be = self.be
         if not (training and self._sync_bn_on()):
-            if drop is not None and drop[0] > 0 and getattr(self, "fused_bn_drop", True):
+            if drop is not None and drop[0] > 0 and self.fused_bn_drop:
                 be.batchnorm_fwd(x, gamma, beta, mov_mean, mov_var, y, xhat, inv_std, rows, C, ldy, training, BN_EPS,
                                  BN_MOMENTUM, work, drop=drop)
                 return True
@@ -1432,7 +1513,7 @@ class ModelBase:
         it was applied)"""
         be = self.be
         if not self._sync_bn_on():
-            if act_pre is not None and getattr(self, "fused_bn_drop", True):
+            if act_pre is not None and self.fused_bn_drop:
                 be.batchnorm_bwd(dy, xhat, gamma, inv_std, dx, dgamma, dbeta, rows, C, lddy, True, work, act_pre=act_pre,
                                  slope=slope)
                 return True
@@ -1447,17 +1528,16 @@ class ModelBase:
         be.batchnorm_dx(dy, lddy, xhat, gamma, inv_std, sums[:C], sums[C:2 * C], dx, rows, C, rows * self.dp_world)
 
     def _bn_scratch(self, n):
-        buf = self.__dict__.get("_bn_buf")
+        buf = self._bn_buf
         if buf is None or buf.numel() < n:
             buf = self._bn_buf = self._f(n)
         return buf[:n]
 
     def _emb_sparse_ok(self, E, ldd):
         """the sparse Embedding backward runs (single-process fused step)"""
-        return bool(self._tail.deferring and self.dp_world == 1 and getattr(self, "sparse_emb_bwd", True)
-                    and hasattr(self.be, "embedding_bwd_sparse") and E % 4 == 0 and ldd % 4 == 0)
+        return bool(self._tail.deferring and self.dp_world == 1 and self.sparse_emb_bwd and E % 4 == 0 and ldd % 4 == 0)
 
-    def _embedding_bwd(self, drows, ids, name, B, T, E, ldd, V, drop=None, zero_id=-1):
+    def _embedding_bwd(self, drows, ids, name, B, T, E, ldd, V, zero_id=-1):
         """Embedding scatter + IndexedSlices norm.  Inside the fused single-process step (_deferring) the sparse
         form runs: no table-wide zero fill (rows touched by the previous step only are cleaned through ``prev_ids``),
         the norm as per-block partials that the step-finalize launch sums.  Anywhere else (data parallel: the all-reduce
@@ -1466,21 +1546,19 @@ class ModelBase:
         be, a = self.be, self.arena
         seg = a.entries[name].seg
         sqo = a.sq_override[seg:seg + 1]
-        st = self.__dict__.get("_emb_state")
+        st = self._emb_state
         if st is None or st[0] != (B, T, name):
             if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("embedding backward state must be built outside a graph capture (run one eager step)")
-            nparts = be.embedding_bwd_parts(B, T, E) if hasattr(be, "embedding_bwd_parts") else 1
+            nparts = be.embedding_bwd_parts(B, T, E)
             st = self._emb_state = ((B, T, name), torch.full((B * T,), -1, dtype=torch.int32, device=self.device),
                                     self._f(nparts), nparts)
             a.g(name).zero_()
         _, prev, parts, nparts = st
         sparse = self._emb_sparse_ok(E, ldd)
-        assert drop is None or sparse, "the input-dropout mask can only ride on the sparse form"
         if sparse:
-            kw = dict(drop_rate=drop[0], drop_seed=drop[1], drop_site=drop[2], drop_step_dev=drop[3]) if drop else {}
-            if zero_id >= 0 and getattr(self, "emb_skip_masked", True):
-                kw["zero_id"] = zero_id       # rows of the mask id carry no gradient (the caller's guarantee): not read
+            # rows of the mask id carry no gradient (the caller's guarantee): not read
+            kw = dict(zero_id=zero_id) if zero_id >= 0 else {}
             be.embedding_bwd_sparse(drows, ids, prev, a.g(name), parts, B, T, E, ldd, V, **kw)
             # the finalize work hands this step's ids on as prev_ids and sums the norm partials (not under AGC: its launch
             # writes the clipped rows' norm into the variable's sq_override slot itself)
@@ -1543,24 +1621,23 @@ class ModelBase:
         """Split-K exchange space of tnt_gemm3_f32: ONE armed work buffer and ONE error word per model, shared by every
         launch (launches of a model run one after the other on its stream, and every launch leaves the buffer armed).
         Grown during eager passes only; growing invalidates captured graphs."""
-        d = self.__dict__
-        w, sy = d.get("_g3_work"), d.get("_g3_sync")
+        w, sy = self._g3_work, self._g3_sync
         if w is None or w.numel() < floats or sy is None:
             if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("gemm3 split-K workspace too small inside a graph capture (run one eager step first)")
             if w is None or w.numel() < floats:
-                w = d["_g3_work"] = self._f((max(floats, 4) + 3) // 4 * 4)
+                w = self._g3_work = self._f((max(floats, 4) + 3) // 4 * 4)
                 self.be.gemm3_work_arm(w)
             if sy is None:
-                sy = d["_g3_sync"] = torch.zeros(64, dtype=torch.int32, device=self.device)
+                sy = self._g3_sync = torch.zeros(64, dtype=torch.int32, device=self.device)
             self._graphs = {}
         return w, sy
 
     def _g3_plan(self, M, N, K, transA, transB, batch, colsum):
         key = (M, N, K, bool(transA), bool(transB), batch, bool(colsum))
-        plans = self.__dict__.setdefault("_g3_plans", {})
+        plans = self._g3_plans
         if key not in plans:
-            force = getattr(self, "g3_force", {}).get(key[:6])          # tools / tests: {(M, N, K, tA, tB, batch): (tile, splitk)}
+            force = (self.g3_force or {}).get(key[:6])          # tools / tests: {(M, N, K, tA, tB, batch): (tile, splitk)}
             plans[key] = force or self.be.gemm3_plan(M, N, K, transA, transB, batch, allow_split=not colsum)
         return plans[key]
 
@@ -1572,7 +1649,7 @@ class ModelBase:
         ``plan_M``: the extent to EXPECT in that word -- the tile is planned for it (unsplit: the grid still covers M, and
         the splits of a tile would have to be resident together), the result never depends on it."""
         be = self.be
-        if not getattr(self, "use_gemm3", True) or not hasattr(be, "gemm3") or (transA and transB):
+        if not self.use_gemm3 or not hasattr(be, "gemm3") or (transA and transB):
             return False
         if lda % 4 or ldb % 4 or ldc % 4:
             return False
@@ -1591,7 +1668,7 @@ class ModelBase:
         """Two INDEPENDENT products in one launch (tnt_gemm3_pair_f32): p, q = dicts of gemm3's arguments.  True = issued;
         False = this pair has no co-launch form (the caller issues the two products itself)."""
         be = self.be
-        if (not getattr(self, "use_gemm3", True) or not getattr(self, "g3_pairs", True) or not hasattr(be, "gemm3_pair")):
+        if not self.use_gemm3 or not hasattr(be, "gemm3_pair"):
             return False
         descs, need = [], 0
         for d in (p, q):
@@ -1614,7 +1691,7 @@ class ModelBase:
         # distinct argument set, kept for the life of the model (same operands -> same objects)
         ck = tuple((tuple((k, v.data_ptr() if torch.is_tensor(v) else v) for k, v in sorted(d.items()) if k != "small"), tile, sk, off)
                    for d, tile, sk, off, _ in descs) + (work.data_ptr() if need else 0,)
-        keep = self.__dict__.setdefault("_g3_descs", {})
+        keep = self._g3_descs
         if ck in keep:
             be.gemm3_pair(*keep[ck])
             return True
@@ -1633,8 +1710,8 @@ class ModelBase:
         """A/B tool since round 3 (``use_gemm3 = False``): hipBLASLt (tnt_gemm_lt_f32) for the vocabulary-sized GEMMs, i.e. the
         head forward and its two gradients; rocBLAS for the LSTM-sized ones (gemm_sk below).  True = call issued."""
         be = self.be
-        if (not getattr(self, "use_lt", True) or not hasattr(be, "gemm_lt") or kw.get("pre") is not None or kw.get("act", 0)
-                or kw.get("accumulate") or max(N, K) < 4096 or 2.0 * M * N * K < getattr(self, "lt_min_flops", 1e9)):
+        if (not hasattr(be, "gemm_lt") or kw.get("pre") is not None or kw.get("act", 0)
+                or kw.get("accumulate") or max(N, K) < 4096 or 2.0 * M * N * K < self.lt_min_flops):
             return False
         tA, tB = bool(kw.get("transA", False)), bool(kw.get("transB", False))
         if tA and tB:
@@ -1648,18 +1725,18 @@ class ModelBase:
         growing one invalidates captured graphs, which are then re-captured."""
         # default since round 3: every product without an activation epilogue that is large enough to fill the chip runs on
         # the hand-written family (csrc/gemm3.hip); the vendor libraries remain as A/B tools (use_gemm3 = False)
-        if (kw.get("pre") is None and kw.get("act", 0) == 0 and not kw.get("accumulate") and 2.0 * M * N * K >= getattr(self, "g3_min_flops", 3e7)
+        if (kw.get("pre") is None and kw.get("act", 0) == 0 and not kw.get("accumulate") and 2.0 * M * N * K >= self.g3_min_flops
                 and self.gemm3(A, B, C, M, N, K, lda, ldb, ldc, transA=kw.get("transA", False), transB=kw.get("transB", False),
                                bias=kw.get("bias"))):
             return
-        if not getattr(self, "use_gemm3", True) and self._route_lt(A, B, C, M, N, K, lda, ldb, ldc, ws, kw):
+        if not self.use_gemm3 and self._route_lt(A, B, C, M, N, K, lda, ldb, ldc, ws, kw):
             return
         plain = kw.get("bias") is None and kw.get("pre") is None and kw.get("act", 0) == 0
         # One shape family where the vendor's pick is poor: NT with a narrow output and a very long K (config 3's
         # head dX = dlogits[960x5001] @ Wo^T[5001x256]: 59 us = 42 TF, against 38 us for the tiled kernel with
         # split-K 16; tools/c3_head_grad_probe.py).  At N = 512 the two are level and the library stays.
         blas_poor = kw.get("transB", False) and not kw.get("transA", False) and N <= 256 and K >= 16 * N
-        if (plain and not blas_poor and getattr(self, "use_blas", True) and not getattr(self, "use_gemm3", True)
+        if (plain and not blas_poor and self.use_blas and not self.use_gemm3
                 and hasattr(self.be, "gemm_blas")):
             # no fused epilogue (weight / input gradients): the vendor's stream-K sgemm (tnt_gemm_blas_f32) needs no
             # split-K pass + reduce launch on these skinny-output / long-K shapes
@@ -1668,7 +1745,7 @@ class ModelBase:
             return
         sk = self.pick_splitk(M, N, K)
         if sk > 1:
-            pool = self.__dict__.setdefault("_skw", {})
+            pool = self._skw
             buf = self.skwork if ws == 0 else pool.get(ws)
             if buf is None or sk * M * N > buf.numel():
                 if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
@@ -1689,20 +1766,20 @@ class ModelBase:
     def side(self, i):
         # Measured on MI355X (tools/side_bench.py): 0.868 ms/step without, 0.94-1.07 ms with side branches --
         # the concurrent GEMM workgroups crowd out the LDS-heavy BPTT step kernels.  Off by default.
-        if i < 0 or self.device.type != "cuda" or not getattr(self, "use_side_streams", False):
+        if i < 0 or self.device.type != "cuda" or not self.use_side_streams:
             yield
             return
-        streams = self.__dict__.setdefault("_side_streams", {})
+        streams = self._side_streams
         if i not in streams:
             streams[i] = torch.cuda.Stream(device=self.device)
         s = streams[i]
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             yield
-        self.__dict__.setdefault("_side_used", set()).add(i)
+        self._side_used.add(i)
 
     def join(self):
-        used = self.__dict__.get("_side_used")
+        used = self._side_used
         if not used:
             return
         main = torch.cuda.current_stream()
@@ -1725,14 +1802,14 @@ class ModelBase:
     def _emb_row_grads(self):
         """(row-gradient matrix of the Embedding [n][E], n, E, ld, arena name) or None: the IndexedSlices values whose
         un-deduplicated column norms agc.py:25-30 uses.  Set by the models that have an Embedding."""
-        return self.__dict__.get("_emb_rows")
+        return self._route.emb_rows
 
     def _apply_agc(self):
         if not self.agc:
             return
         from .arena import AgcTable
         a, er = self.arena, self._emb_row_grads()
-        tab = self.__dict__.get("_agc_tab")
+        tab = self._agc_tab
         if tab is None:
             shapes = {n: self.keras_shapes[n] for n in a.entries}
             tab = self._agc_tab = AgcTable(a, shapes, er[4] if er else None)
@@ -1819,7 +1896,7 @@ class ModelBase:
         """opt_avg; ValueError on a model compiled without averaging"""
         if self.average is None:
             raise ValueError(f"{what} needs a model compiled with an averaging optimizer (optimizers.MovingAverage / SWA)")
-        if self.__dict__.get("opt_avg") is None:
+        if self.opt_avg is None:
             raise RuntimeError(f"{what}: the average exists once the optimizer state does, from the first training step on")
         return self.opt_avg
 
@@ -1957,24 +2034,26 @@ class ModelBase:
         ok = ok and cap.dtype == torch.int32
         ok = ok and x.dim() == 2 and cap.dim() == 2 and x.shape == (cap.shape[0], n_cols)
         ok = ok and (target is None or (target.dtype == torch.int32 and target.shape == cap.shape))
-        self._head_map_fresh = False
-        self._stage_fwd_done = False
+        route = self._route = StepRoute()        # a new batch: nothing is handed over from the step before
         if not ok:
             B, T = self._stage_inputs(inputs)
+            route = self._route                 # (_stage_inputs stages a batch too)
             if target is not None:
                 self._stage_target(target, B, T)
             mk = self._stage_mask_job() if masks else None
             if mk is not None:
                 self.be.dropout_mask4(mk[0], mk[1], mk[2], mk[3], mk[4], mk[5], 0, mk[6])
+            route.masks_staged = mk is not None
             return B, T
         B, T = cap.shape
         self._build(B, T)
         assert a0.shape == c0.shape == (B, self.U), f"state shape {tuple(a0.shape)} != {(B, self.U)}"
-        xT = getattr(self, "xT", None)       # voxel-major copy for the region-wise encoder, written in the same launch
+        xT = self.xT                        # voxel-major copy for the region-wise encoder, written in the same launch
         kw = {}
         mk = self._stage_mask_job() if masks else None
         if mk is not None:                   # the step's dropout masks ride in the staging launch
             kw["masks"] = mk
+        route.masks_staged = mk is not None
         hm = self._head_map_bufs(B, T) if (head_map and target is not None and mk is None and xT is None
                                            and x.dtype == torch.float32) else None
         sf = self._stage_fwd_args(B) if (fwd and hm is not None and n_cols == self.ldx) else None
@@ -1983,13 +2062,13 @@ class ModelBase:
                                                                   self.Cs[0], T, self.U, *hm):
             # ... and both ride behind the encoder forward, which reads the caller's x in place: the step's first launch is
             # the forward, and _forward leaves its own out (False: the entry refused these arguments, e.g. their alignment)
-            self._head_map_fresh = self._stage_fwd_done = True
+            route.head_map_fresh = route.stage_fwd_done = True
         elif hm is not None:
             # the head's row map (which caption positions repeat an earlier row) rides in the staging launch: the step that
             # follows runs its vocabulary head over the distinct rows only
             self.be.stage_batch_map(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,
                                     self.ldx, self.U, *hm)
-            self._head_map_fresh = True
+            route.head_map_fresh = True
         elif xT is not None:
             self.be.stage_batch(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,
                                 self.ldx, self.U, xT, xT.shape[1], **kw)
@@ -2013,8 +2092,8 @@ class ModelBase:
     def _guard_word(self):
         """The error word of the persistent kernel's sync state (uint32, device) while that kernel is in use, else None.
         The optimizer kernels take it as ``guard`` and leave the model untouched when it is set."""
-        sync = self.__dict__.get("seq_sync")
-        return sync[1024:1025] if (sync is not None and self.__dict__.get("_seq_lstm")) else None
+        sync = self.seq_sync
+        return sync[1024:1025] if (sync is not None and self._seq_lstm) else None
 
     def _guard_out(self):
         """Where the persistent kernel reports its error code for the host: slot GUARD of the metrics buffer."""
@@ -2036,7 +2115,7 @@ class ModelBase:
         executed = (not graphs) or st is None or (isinstance(st, str) and st == "warm")
         self._ring_hit = False
         run(key, fn)
-        keys = self.__dict__.setdefault("_ring_keys", set())
+        keys = self._ring_keys
         if executed or self._ring_hit:
             (keys.add if self._ring_hit else keys.discard)(key)
         return key in keys
@@ -2055,9 +2134,9 @@ class ModelBase:
 
     def _ring_args(self):
         """keyword arguments that make the Adam launch of the fused step file the metrics vector in the ring"""
-        if not getattr(self, "metric_ring", True) or self.__dict__.get("met") is None or self.met.numel() > 62:
+        if not self.metric_ring or self.met is None or self.met.numel() > 62:
             return {}
-        if self.__dict__.get("met_ring") is None or self.met_ring.shape[1] != self.met.numel() + 1:
+        if self.met_ring is None or self.met_ring.shape[1] != self.met.numel() + 1:
             if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
                 return {}
             self.met_ring = self._f(self.METRIC_RING, self.met.numel() + 1)
@@ -2070,8 +2149,8 @@ class ModelBase:
     def _metrics_from(self, m, **slots):
         """Metrics from a snapshot ``m`` of the metrics buffer (_met_snapshot); the guard word of the same snapshot rides along."""
         out = Metrics((k, m[i] if isinstance(i, int) else i) for k, i in slots.items())
-        out._ring = self.__dict__.get("_last_ring")
-        return out.guarded(self, m[self.GUARD]) if self.__dict__.get("_seq_lstm") else out
+        out._ring = self._last_ring
+        return out.guarded(self, m[self.GUARD]) if self._seq_lstm else out
 
     def _on_guard_trip(self, code):
         self.disable_seq_lstm()
@@ -2097,22 +2176,20 @@ class ModelBase:
         """Raises DeviceGuardError if the persistent LSTM kernel's error word is set (synchronises).  train_step /
         test_step results carry the same check with them (Metrics.as_floats), the inference paths check after their
         own host read; this is the explicit form for loops that never read a metric."""
-        sync = self.__dict__.get("seq_sync")
+        sync = self.seq_sync
         if sync is not None and int(sync[1024].item()) != 0:
             self._on_guard_trip(int(sync[1024].item()))
 
     def _init_seq_lstm(self, B, U):
         """Opt in to the persistent sequence-forward kernel for this (B, U) on this device.  Probes once per process
         (tnt_lstm_seq_supported synchronises), so it is called from _build, outside any capture."""
-        self._seq_lstm = bool(getattr(self, "use_seq_lstm", True) and hasattr(self.be, "lstm_seq_supported")
+        self._seq_lstm = bool(self.use_seq_lstm and hasattr(self.be, "lstm_seq_supported")
                               and self.be.lstm_seq_supported(B, U))
-        if self._seq_lstm and self.__dict__.get("seq_sync") is None:
+        if self._seq_lstm and self.seq_sync is None:
             self.seq_sync = torch.zeros(1025, dtype=torch.int32, device=self.device)     # re-armed by the kernel itself
-        elif not self._seq_lstm and "seq_sync" not in self.__dict__:
-            self.seq_sync = None
-        if self._seq_lstm and hasattr(self.be, "lstm_seq_bwd") and getattr(self, "use_seq_lstm_bwd", True):
+        if self._seq_lstm and hasattr(self.be, "lstm_seq_bwd"):
             n = self.be.lstm_seq_bwd_work_floats(B, U)       # exchange buffer of the persistent BPTT chain
-            if self.__dict__.get("seq_xch") is None or self.seq_xch.numel() < n:
+            if self.seq_xch is None or self.seq_xch.numel() < n:
                 self.seq_xch = self._f(n)
         else:
             self.seq_xch = None
@@ -2121,10 +2198,10 @@ class ModelBase:
         """Back to the per-step LSTM kernels (after a guard trip of the persistent one, or by choice): zeroes the sync
         state and the guard slot, drops captured graphs / launch plans; the step buffers are reused as they are."""
         self.use_seq_lstm = False
-        sync = self.__dict__.get("seq_sync")
+        sync = self.seq_sync
         if sync is not None:
             sync.zero_()
-        if self.__dict__.get("met") is not None:
+        if self.met is not None:
             self.met[self.GUARD] = 0
         self._seq_lstm = False
         self._graphs = {}
@@ -2133,11 +2210,17 @@ class ModelBase:
     def _sample_step_word(self, step):
         """the static device word a captured sampled decode reads its Philox stream step from (step_dev), set to
         ``step`` (mod 2^32) on the stream before the launch or replay"""
-        w = self.__dict__.get("_step_word")
+        w = self._step_word
         if w is None:
             w = self._step_word = torch.zeros(1, dtype=torch.int32, device=self.device)
         w.fill_(int(np.uint32(int(step) & 0xFFFFFFFF).view(np.int32)))
         return w
+
+    def _decode_bufs(self, name):
+        """the buffer dict ``name`` (_con_bufs / _cons_bufs), made on first use"""
+        if getattr(self, name) is None:
+            setattr(self, name, {})
+        return getattr(self, name)
 
     def _constrain(self, constraints, rows, max_len, beam_width=1, end_id=-1):
         """The constrained-decode helper of a decode over ``rows`` rows (``end_id``: beam search's), or None when
@@ -2183,7 +2266,7 @@ class ModelBase:
             raise ValueError("consensus decoding is an inference mode: training=True is refused")
         if self.grad_sync is not None:
             raise NotImplementedError("consensus decoding has no data-parallel schedule: decode on one device")
-        G, S = c.members, int(getattr(self, "S", 1))
+        G, S = c.members, int(self.S)
         n_rows = int(img_input.shape[0]) if hasattr(img_input, "shape") else len(img_input)
         if S > 1 and G != S:
             raise ValueError(f"a model of n_subjects = {S} decodes the consensus of its subject slices: members must be {S}, "
@@ -2216,7 +2299,7 @@ class ModelBase:
             raise ValueError("guided decoding is an inference mode: training=True is refused")
         if self.grad_sync is not None:
             raise NotImplementedError("guided decoding has no data-parallel schedule: decode on one device")
-        S = int(getattr(self, "S", 1))
+        S = int(self.S)
         if S > 1:
             raise ValueError(f"guided decoding is built for one subject: n_subjects = {S} is not supported")
         if not hasattr(img_input, "shape"):
@@ -2329,7 +2412,7 @@ class ModelBase:
 
     def _train_and_update_graph(self, B, T):
         """the single-process step as one launch sequence: the loss / accuracy totals ride in the step-finalize launch"""
-        if not getattr(self, "fused_update", True):          # A/B switch (tools/ab_attr.py): the unfused launch sequence
+        if not self.fused_update:          # A/B switch (tools/ab_attr.py): the unfused launch sequence
             self._train_graph(B, T)
             self._update_graph()
             return
@@ -2364,8 +2447,7 @@ class ModelBase:
     def _step_runner(self, E=None):
         """_run_planned where the training step is backend launches only, else _run_captured.  ``E``: the text-embedding
         width (default self.E)"""
-        plan = (getattr(self, "plan_step", True) and (self.E if E is None else E) % 4 == 0
-                and getattr(self, "sparse_emb_bwd", True) and hasattr(self.be, "embedding_bwd_sparse"))
+        plan = self.plan_step and (self.E if E is None else E) % 4 == 0 and self.sparse_emb_bwd
         return self._run_planned if plan else self._run_captured
 
     def _ss_refuse(self, T=None):
@@ -2475,8 +2557,8 @@ class ModelBase:
         """per (B, chunk, C, T): the captions (B, C, T) on the device, the packed results [logprob B*C | length B*C (int32
         bits) | guard word | tok_lp B*C*(T-1)], and the model's decoder buffers for one chunk of B*Cc rows (_score_bufs),
         allocated once and viewed per pass (_score_views)"""
-        st = self.__dict__.get("_score")
-        key = (B, Cc, C, T, bool(self.__dict__.get("_seq_lstm")))
+        st = self._score
+        key = (B, Cc, C, T, bool(self._seq_lstm))
         if st is None or st["key"] != key:
             n = B * C
             st = self._score = dict(key=key, caps=torch.zeros(B, C, T, dtype=torch.int32, device=self.device),

@@ -20,7 +20,7 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
-                         _TokenChoice, _BeamDecode, EncGram, EncUpdate)
+                         _TokenChoice, _BeamDecode, EncGram, EncUpdate, StepRoute)
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
@@ -29,6 +29,15 @@ ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column grou
 
 class NIC(ModelBase):
     BN = "batch_norm"       # the BatchNormalization layer that owns the moving statistics (fc_nic: its own)
+    # ---- A/B switches of this model (ModelBase declares the shared ones; same rules)
+    compact_head = True         # False: the vocabulary head over all T * B position-ordered rows; tests/test_gpu_compact_head.py
+    stage_fwd = True            # False: batch staging and encoder forward as two launches; INTEGRATION.md 4, tests/test_gpu_stage_forward.py
+    fuse_enc_update = True      # False: the encoder kernel's gradient is written and updated like any other; tests/test_host_nic.py
+    fuse_tail = True            # False: the encoder tail (BatchNorm, Dropouts, LeakyReLU') as separate launches; tools/ab_bench.py
+    fused_xproj = False         # True: the LSTM input projection on the one-round GEMM family (gemm_fused); tools/ab_fused.py
+    fused_head_grads = False    # True: the head's dW + bias gradient on gemm_fused (with g3_riders = False); tools/ab_fused.py
+    fused_lstm_grads = False    # True: the LSTM's parameter gradients on gemm_fused (with g3_riders = False); tools/ab_fused.py
+    side_head = True            # False: the head's dW stays on the main stream under use_side_streams; tools/side_bench.py
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
@@ -100,6 +109,18 @@ class NIC(ModelBase):
                                          device=self.device)
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
+        self._init_step_state()
+
+    def _init_step_state(self):
+        """what exists only once a step or a decode has asked for it (fc_nic.NICfc, which has its own constructor, too)"""
+        self._enc_gram = None           # EncGram of the last training forward that left the Gram by-products (_forward)
+        self._enc_last_fused = None     # (x, dpre, rows) of the last _bwd_enc that handed the encoder gradient to the update
+        self._enc_grad_stale = None     # ... while the gradient buffer lags behind them (train_step; get_gradient forms it)
+        self._enc_shard = None          # the row-sharded encoder update's spans and buffers (_enc_shard_state)
+        self._head_live_est = None      # the head's live row count at the warm-up step (_head_plan_rows)
+        self._plan_staged = {}          # step key -> whether its recording left the encoder forward to the staging launch
+        self._scst = None               # the self-critical step's buffers (_scst_bufs)
+        self._beam_bufs = {}            # beam_search's static buffers per (B, k, max_len, end_id[, G])
 
     # ------------------------------------------------------------------ weights
     def _init_weights(self, rng):
@@ -124,7 +145,7 @@ class NIC(ModelBase):
     def get_gradient(self, name):
         """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
         optimizer kernels add on the fly)."""
-        st = self.__dict__.get("_enc_grad_stale")
+        st = self._enc_grad_stale
         if name == "dense_img/kernel" and st is not None:
             # the fused step consumed X^T dpre inside the optimizer launches without writing it: its operands are still
             # in place, materialise it on request
@@ -139,9 +160,9 @@ class NIC(ModelBase):
         ``defer``: asked ahead of the step (_stage_fwd_args) -- whether that step will be the fused one."""
         opt = self.optimizer
         defer = self._tail.deferring if defer is None else defer
-        return bool(defer and self.dp_world == 1 and getattr(self, "fuse_enc_update", True)
+        return bool(defer and self.dp_world == 1 and self.fuse_enc_update
                     and opt is not None and opt.kind == "adam" and not self.agc and rows <= 64
-                    and self.E % 512 == 0 and hasattr(self.be, "dense_dw_adam") and hasattr(self.be, "step_finalize")
+                    and self.E % 512 == 0
                     and self.arena.entries["dense_img/kernel"].seg == 0
                     # one norm-partial slot per workgroup inside the variable's own span slots
                     and min((self.N + 15) // 16, 256) * (self.E // 512) <= self.arena.spans.first_host[1])
@@ -159,8 +180,8 @@ class NIC(ModelBase):
         self.tgt = torch.zeros(T * B, dtype=torch.int32, device=self.device)
         self.enc_pre, self.enc_y = f(B, E), f(B, E)
         # K-split partials of the streaming encoder forward (tnt_dense_fwd_stream_f32); None -> generic split-K GEMM
-        ok = self.norm == "batch" and B <= 256 and E % 32 == 0 and N % 4 == 0 and hasattr(self.be, "dense_fwd_stream")
-        self.enc_part = f(ENC_SPLITS * B * E) if ok and getattr(self, "stream_encoder", True) else None
+        ok = self.norm == "batch" and B <= 256 and E % 32 == 0 and N % 4 == 0
+        self.enc_part = f(ENC_SPLITS * B * E) if ok else None
         self.enc_gx = self.enc_w2 = None        # Gram by-products of the forward (allocated on first use, outside captures)
         self.enc_yd = f(B, E) if self.r_feat > 0 else self.enc_y
         self.xhat = f(B, E)
@@ -196,11 +217,12 @@ class NIC(ModelBase):
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
-        if self.optimizer is not None and getattr(self, "opt_m", None) is None:
+        if self.optimizer is not None and self.opt_m is None:
             self._init_optimizer_state()
         self.built = True
 
     def _stage_inputs(self, data):
+        self._route = StepRoute()
         x, cap, a0, c0 = data
         cap_t = self._to_dev(cap, torch.int32)
         B, T = cap_t.shape
@@ -224,9 +246,9 @@ class NIC(ModelBase):
         Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the position-ordered
         buffers."""
         be = self.be
-        ok = (getattr(self, "compact_head", True) and self.__dict__.get("_seq_lstm") and self.__dict__.get("seq_xch") is not None
+        ok = (self.compact_head and self._seq_lstm and self.seq_xch is not None
               and hasattr(be, "stage_batch_map") and hasattr(be, "softmax_cce_live") and hasattr(be, "gemm3")
-              and getattr(self, "use_gemm3", True) and getattr(self, "g3_riders", True)
+              and self.use_gemm3 and self.g3_riders
               and self.grad_sync is None and self.dp_world == 1
               and self.scheduled_sampling is None and self.self_critical is None and not self.agc
               and not self.label_smoothing and not self.unlikelihood and not self._token_weights_on() and self.U % 4 == 0)
@@ -238,8 +260,7 @@ class NIC(ModelBase):
         """the training forward leaves X X^T and sum W^2 behind (tnt_dense_fwd_stream_gram_f32): the optimizer step takes the
         encoder kernel's gradient X^T dpre without writing it, and its clip-by-norm factor follows from these"""
         return (self._fused_tail(B) and self.enc_part is not None and self._enc_update_fused(B, defer)
-                and getattr(self, "gram_norm", True) and self.N % 16 == 0 and self.E >= 512
-                and hasattr(self.be, "dense_gram_norm"))
+                and self.N % 16 == 0 and self.E >= 512)
 
     def _gram_bufs(self):
         if self.enc_gx is None:
@@ -250,8 +271,8 @@ class NIC(ModelBase):
         (tnt_dense_fwd_stream_gram_stage_f32) where the step's first kernel is the Gram form of the streaming forward on
         the staged betas themselves (no input Dropout), and the step is the single-process fused one.  Everything else
         keeps the two launches."""
-        ok = (getattr(self, "stage_fwd", True) and self.r_in == 0 and hasattr(self.be, "dense_fwd_stream_gram_stage")
-              and self._gram_fwd(B, defer=bool(getattr(self, "fused_update", True))))
+        ok = (self.stage_fwd and self.r_in == 0 and hasattr(self.be, "dense_fwd_stream_gram_stage")
+              and self._gram_fwd(B, defer=bool(self.fused_update)))
         if not ok:
             return None
         self._gram_bufs()
@@ -259,7 +280,7 @@ class NIC(ModelBase):
 
     def _fused_tail(self, B):
         """one-launch encoder tail (tnt_enc_tail_*): BatchNorm encoder, batch <= 256 rows, E % 4 == 0"""
-        return (self.norm == "batch" and B <= 256 and self.E % 4 == 0 and getattr(self, "fuse_tail", True)
+        return (self.norm == "batch" and B <= 256 and self.E % 4 == 0 and self.fuse_tail
                 and not self._sync_bn_on())        # synchronised BatchNorm: the statistics leave the kernel for a collective
 
     # ------------------------------------------------------------------ forward
@@ -281,7 +302,7 @@ class NIC(ModelBase):
         if stream:      # :125-128 + the feature step's LSTM input dropout: the streaming product's K-split partials are
             #             summed (+ bias, LeakyReLU) by the tail kernel, which holds whole columns for the batch statistics
             self._enc_gram = None
-            staged = bool(training and self.__dict__.get("_stage_fwd"))      # train_step: the staging launch ran this product
+            staged = bool(training and self._route.stage_fwd_done)      # train_step: the staging launch ran this product
             if training and self._gram_fwd(B):
                 # the optimizer step will take this kernel's gradient X^T dpre without writing it: leave X X^T and
                 # sum W^2 behind, from which (with dpre) its clip-by-norm factor follows (tnt_dense_gram_norm_f32)
@@ -295,7 +316,7 @@ class NIC(ModelBase):
                 raise RuntimeError("the staging launch ran the Gram form of the encoder forward, which this step does not take")
             else:
                 be.dense_fwd_stream(x, a.p("dense_img/kernel"), self.enc_part, B, E, N, self.ldx, E, ENC_SPLITS)
-            emb_ride = E % 4 == 0 and hasattr(be, "enc_tail_fwd_sk_emb") and getattr(self, "emb_ride", True)
+            emb_ride = E % 4 == 0
             targs = (self.enc_part, ENC_SPLITS, a.p("dense_img/bias"), self.enc_pre, 0.2, a.p("batch_norm/gamma"),
                      a.p("batch_norm/beta"), self.mov_mean, self.mov_var, xin, self.xhat, self.inv_std, B, E, E, training,
                      BN_EPS, BN_MOMENTUM, self.r_feat if training else 0.0, self.r_lstm if training else 0.0, sd, S_FEAT,
@@ -337,17 +358,17 @@ class NIC(ModelBase):
             be.embedding_fwd(a.p("emb_text/embeddings"), self.cap, self.Xin[B:], B, T, E, E, V)   # :131
             if drop_l:       # LSTM(dropout=...) masks the layer input, one mask per call
                 be.dropout(self.Xin[B:], self.Xin_d[B:], T * B, E, E, B, E, 0, self.r_lstm, sd, S_LSTM_IN + 1, 0, ds)
-        self._xin_used = xin
+        self._route.xin_used = xin
         if ss:
             self._forward_ss(B, T, xin, drop_l)
             return
         # input projection of all T+1 steps as ONE epilogue-free GEMM; the LSTM bias is added inside the step kernel
-        if getattr(self, "fused_xproj", False) and hasattr(be, "gemm_fused") and be.gemm_fused_cfg(R1, 4 * U, E) > 0:
+        if self.fused_xproj and hasattr(be, "gemm_fused") and be.gemm_fused_cfg(R1, 4 * U, E) > 0:
             be.gemm_fused(xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U)
         else:
             self.gemm_sk(xin, a.p("lstm/kernel"), self.XZ, R1, 4 * U, E, E, 4 * U, 4 * U)
         Ur, bl = a.p("lstm/recurrent_kernel"), a.p("lstm/bias")
-        compact = bool(training and self.__dict__.get("_compact"))       # _head_map_bufs: Out and logits hold the distinct rows
+        compact = bool(training and self._route.head_map_fresh)       # _head_map_bufs: Out and logits hold the distinct rows
         # both LSTM calls: the feature, one unmasked step (NIC.py:138), and the text, masked by the Embedding mask (:140)
         lstm_layer_fwd(be, self.XZ, self.Hs, self.Cs, Ur, bl, self.cap, T, 1, self.Out, self.gates, T + 1, B, U,
                        chain=self._seq_chain(), out_pos=self.head_pos if compact else None)
@@ -364,7 +385,7 @@ class NIC(ModelBase):
         """the row count the head forward's tile is planned for: the live count of the warm-up batch plus 3 % (batches of the
         same data differ a little), or n when none was read"""
         est = self._head_live_est
-        if not getattr(self, "compact_head_replan", True) or est is None or est <= 0:
+        if est is None or est <= 0:
             return n
         return min(n, est + max(est // 32, 1))
 
@@ -399,7 +420,7 @@ class NIC(ModelBase):
         """softmax + per-timestep mean CE / accuracy summed over T and divided by T
         (NIC.py:233-240) == sum over all (b,t) / (B*T)."""
         n = T * B
-        if want_grad and self.__dict__.get("_compact"):
+        if want_grad and self._route.head_map_fresh:
             # the distinct rows, each weighted by its multiplicity; rows past the live count hold zeros (staging launch)
             self.be.softmax_cce_live(self.logits, self.head_tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
                                      self.ldV, 1.0 / (n * self.dp_world), self.head_live, self.head_w)
@@ -423,7 +444,9 @@ class NIC(ModelBase):
         dw = dict(A=self.Out, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=U, N=V, K=T * B, lda=U, ldb=ldV, ldc=ldV,
                   transA=True, colsum=a.g("time_distributed_softmax/bias"))
         dx = dict(A=dlog, B=Wo, C=self.dOut, M=T * B, N=U, K=V, lda=ldV, ldb=ldV, ldc=U, transB=True)
-        if self.__dict__.get("_compact"):
+        route = self._route
+        route.colsum_deferred = None
+        if route.head_map_fresh:
             # dlogits and Out hold `live` rows: dW and db sum over those (each already carries its multiplicity), dOut is
             # formed for those; one device word bounds both products
             dw.update(live=self.head_live, live_mode=LIVE_ROWS_K)
@@ -436,27 +459,27 @@ class NIC(ModelBase):
             if join:
                 self.join()
             return
-        if getattr(self, "g3_riders", True) and self.gemm3_pair(dw, dx):
+        if self.g3_riders and self.gemm3_pair(dw, dx):
             # kernel gradient (with the bias gradient as a rider on the dlogits tiles it streams anyway) and input gradient,
             # the two independent readers of dlogits, in ONE launch
             if join:
                 self.join()
             return
-        if getattr(self, "g3_riders", True) and self.gemm3(self.Out, dlog, a.g("time_distributed_softmax/kernel"), U, V, T * B,
-                                                        U, ldV, ldV, transA=True, colsum=a.g("time_distributed_softmax/bias")):
+        if self.g3_riders and self.gemm3(self.Out, dlog, a.g("time_distributed_softmax/kernel"), U, V, T * B, U, ldV, ldV,
+                                         transA=True, colsum=a.g("time_distributed_softmax/bias")):
             pass        # dW and the bias gradient: one launch
-        elif getattr(self, "fused_head_grads", False) and hasattr(be, "gemm_fused") and \
+        elif self.fused_head_grads and hasattr(be, "gemm_fused") and \
                 be.gemm_fused_cfg(U, V, T * B, True, False, 1) > 0:
             be.gemm_fused(self.Out, dlog, a.g("time_distributed_softmax/kernel"), U, V, T * B, U, ldV, ldV, transA=True,
                           colsum=a.g("time_distributed_softmax/bias"))
         else:
-            with self.side(0 if getattr(self, "side_head", True) else -1):
+            with self.side(0 if self.side_head else -1):
                 self.gemm_sk(self.Out, dlog, a.g("time_distributed_softmax/kernel"), U, V, T * B, U, ldV, ldV, transA=True,
                              ws=1)
-                if self._tail.deferring and hasattr(be, "colsum2") and T * B <= 2048:
+                if self._tail.deferring and T * B <= 2048:
                     # single-process step: the head-bias column sums share a launch with the LSTM-bias ones behind the
                     # BPTT chain (dlogits stays in place until the next forward)
-                    self._colsum_deferred = (dlog, a.g("time_distributed_softmax/bias"), T * B, V, ldV)
+                    route.colsum_deferred = (dlog, a.g("time_distributed_softmax/bias"), T * B, V, ldV)
                 else:
                     be.colsum(dlog, a.g("time_distributed_softmax/bias"), T * B, V, ldV, self.work2)
         self.gemm_sk(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True)
@@ -476,39 +499,33 @@ class NIC(ModelBase):
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
         R1 = (T + 1) * B
         sd, ds = self.seed, self.drop_step
+        route = self._route
         lstm_layer_bwd(be, a.p("lstm/recurrent_kernel"), self.dOut, self.cap, T, 1, self.gates, self.Cs, self.dZ,
                        (self.da_pass, self.dc, self.dout), T + 1, B, U, chain=self._seq_chain(bwd=True),
-                       dout_pos=self.head_pos if self.__dict__.get("_compact") else None, pass_out_last=False)
-        xin = self._xin_used
-        self._dxin_done = False
-        if getattr(self, "g3_riders", True) and E == U:
+                       dout_pos=self.head_pos if route.head_map_fresh else None, pass_out_last=False)
+        xin, d = route.xin_used, route.colsum_deferred      # d: the head-bias column sums _bwd_head left to this method
+        route.dxin_done = False
+        riders = self.g3_riders and E == U
+        one = False         # kernel, recurrent-kernel and bias gradients went out as ONE launch
+        if riders:
             dw = dict(A=xin, B=self.dZ, C=a.g("lstm/kernel"), M=E, N=4 * U, K=R1, lda=E, ldb=4 * U, ldc=4 * U, transA=True,
                       colsum=a.g("lstm/bias"), A2=self.Hs, C2=a.g("lstm/recurrent_kernel"))
             dx = dict(A=self.dZ, B=a.p("lstm/kernel"), C=self.dXin, M=R1, N=E, K=4 * U, lda=4 * U, ldb=4 * U, ldc=E, transB=True)
-            if self.gemm3_pair(dw, dx):
-                # the LSTM's three parameter gradients AND its input gradient (the four readers of dZ) in ONE launch;
-                # _bwd_seq_front finds dXin done
-                self._dxin_done = True
-                d = self.__dict__.pop("_colsum_deferred", None)
-                if d is not None:
-                    be.colsum(*d, self.work2)
-                return
-        if getattr(self, "g3_riders", True) and E == U and self.gemm3(
-                xin, self.dZ, a.g("lstm/kernel"), E, 4 * U, R1, E, 4 * U, 4 * U, transA=True, colsum=a.g("lstm/bias"),
-                A2=self.Hs, C2=a.g("lstm/recurrent_kernel")):
-            # kernel, recurrent-kernel and bias gradients in ONE launch: the two products share dZ, the column sums of dZ
-            # ride on the fragments the first tile row holds anyway
-            d = self.__dict__.pop("_colsum_deferred", None)
-            if d is not None:
-                be.colsum(*d, self.work2)
-            return
-        if getattr(self, "fused_lstm_grads", False) and E == U and hasattr(be, "gemm_fused") and \
+            # the LSTM's three parameter gradients AND its input gradient (the four readers of dZ) in ONE launch;
+            # _bwd_seq_front finds dXin done
+            one = route.dxin_done = bool(self.gemm3_pair(dw, dx))
+        if riders and not one:
+            # the two products share dZ, the column sums of dZ ride on the fragments the first tile row holds anyway
+            one = bool(self.gemm3(xin, self.dZ, a.g("lstm/kernel"), E, 4 * U, R1, E, 4 * U, 4 * U, transA=True,
+                                  colsum=a.g("lstm/bias"), A2=self.Hs, C2=a.g("lstm/recurrent_kernel")))
+        if not one and self.fused_lstm_grads and E == U and hasattr(be, "gemm_fused") and \
                 be.gemm_fused_cfg(U, 4 * U, R1, True, False, 2) > 0:
-            # kernel, recurrent-kernel and bias gradients in ONE launch of the one-round GEMM family: the two products
-            # share dZ, the bias gradient (column sums of dZ) rides on the tiles the first row of workgroups loads anyway
+            # ... or in ONE launch of the one-round GEMM family: the bias gradient (column sums of dZ) rides on the tiles the
+            # first row of workgroups loads anyway
             be.gemm_fused(xin, self.dZ, a.g("lstm/kernel"), E, 4 * U, R1, E, 4 * U, 4 * U, transA=True,
                           colsum=a.g("lstm/bias"), A2=self.Hs, C2=a.g("lstm/recurrent_kernel"))
-            d = self.__dict__.pop("_colsum_deferred", None)
+            one = True
+        if one:
             if d is not None:
                 be.colsum(*d, self.work2)
             return
@@ -516,7 +533,6 @@ class NIC(ModelBase):
             self.gemm_sk(self.Hs, self.dZ, a.g("lstm/recurrent_kernel"), U, 4 * U, R1, U, 4 * U, 4 * U, transA=True, ws=2)
         with self.side(0):
             self.gemm_sk(xin, self.dZ, a.g("lstm/kernel"), E, 4 * U, R1, E, 4 * U, 4 * U, transA=True, ws=1)
-            d = self.__dict__.pop("_colsum_deferred", None)
             if d is not None and R1 <= 2048:
                 be.colsum2(*d, self.dZ, a.g("lstm/bias"), R1, 4 * U, 4 * U)
             else:
@@ -530,33 +546,28 @@ class NIC(ModelBase):
         N, U, E, V, ldV = self.N, self.U, self.E, self.V, self.ldV
         R1 = (T + 1) * B
         sd, ds = self.seed, self.drop_step
-        if not self.__dict__.pop("_dxin_done", False):
+        if not self._route.dxin_done:
             self.gemm_sk(self.dZ, a.p("lstm/kernel"), self.dXin, R1, E, 4 * U, 4 * U, 4 * U, E, transB=True)
         fused = self._fused_tail(B)
         if self.r_lstm > 0:
             if not fused:
                 be.dropout(self.dXin, self.dXin, B, E, E, 0, E, 0, self.r_lstm, sd, S_LSTM_IN + 0, 0, ds)
-        # The text call's LSTM-input dropout' can ride on the sparse Embedding backward (mask applied to the rows as they are
-        # read; not when AGC needs the dropped-out rows themselves).  Off by default: measured 0.5761 -> 0.5845 ms/step --
-        # the Philox calls land on the few workgroups that own heavily duplicated ids, on the step's critical path, and cost
-        # more there than the 4 us launch they save.
-        fold = self.r_lstm > 0 and self._emb_sparse_ok(E, E) and not self.agc and getattr(self, "fold_emb_drop", False)
-        # ... else it shares a launch with the encoder tail backward (both read the dXin the GEMM above just wrote, different
-        # rows), which then runs in front of the Embedding backward
-        ride = (self.r_lstm > 0 and not fold and fused and E % 4 == 0 and hasattr(be, "enc_tail_bwd_drop")
-                and getattr(self, "tail_drop_ride", True))
+        # The text call's LSTM-input dropout' shares a launch with the encoder tail backward (both read the dXin the GEMM above
+        # just wrote, different rows), which then runs in front of the Embedding backward.  (Riding on the sparse Embedding
+        # backward instead was measured slower, 0.5761 -> 0.5845 ms/step: the Philox calls landed on the few workgroups that
+        # own heavily duplicated ids, on the step's critical path.)
+        ride = self.r_lstm > 0 and fused and E % 4 == 0
         if ride:
             be.enc_tail_bwd_drop(self.dXin, self.xhat, a.p("batch_norm/gamma"), self.inv_std, self.enc_pre, self.dpre,
                                  a.g("batch_norm/gamma"), a.g("batch_norm/beta"), a.g("dense_img/bias"), B, E, E,
                                  self.r_feat, self.r_lstm, 0.2, sd, S_FEAT, S_LSTM_IN + 0, ds,
                                  self.dXin[B:], T * B, E, E, B, E, 0, self.r_lstm, S_LSTM_IN + 1)
-        elif self.r_lstm > 0 and not fold:
+        elif self.r_lstm > 0:
             be.dropout(self.dXin[B:], self.dXin[B:], T * B, E, E, B, E, 0, self.r_lstm, sd, S_LSTM_IN + 1, 0, ds)
-        self._emb_rows = (self.dXin[B:], T * B, E, E, "emb_text/embeddings")
+        self._route.emb_rows = (self.dXin[B:], T * B, E, E, "emb_text/embeddings")
         # id 0 is the Embedding's mask (mask_zero, NIC.py:77) and the text LSTM honours it: a masked step hands no gradient to
         # its input row, so the rows of id 0 are zero (BPTT leaves dz = 0 there and dXin = dz W^T)
-        self._embedding_bwd(self.dXin[B:], self.cap, "emb_text/embeddings", B, T, E, E, V,
-                            drop=(self.r_lstm, sd, S_LSTM_IN + 1, ds) if fold else None, zero_id=0)
+        self._embedding_bwd(self.dXin[B:], self.cap, "emb_text/embeddings", B, T, E, E, V, zero_id=0)
         if ride:
             return
         if fused:       # dropout' -> BatchNorm' -> dropout' -> LeakyReLU' -> dpre, encoder bias gradient: one launch
@@ -589,10 +600,10 @@ class NIC(ModelBase):
         self._enc_last_fused = None
         if x_all is None and self._enc_update_fused(rows):
             self._tail.enc = EncUpdate("dense_img/kernel", x, dpre, rows, self.N, self.E, self.ldx,
-                                       gram=self.__dict__.get("_enc_gram"))                       # -> _update_fused
+                                       gram=self._enc_gram)                       # -> _update_fused
             self._enc_last_fused = (x, dpre, rows)       # train_step marks the gradient buffer stale after every (re)play
             return
-        if rows <= 64 and self.E % 16 == 0 and getattr(self, "skinny_dw", True):
+        if rows <= 64 and self.E % 16 == 0:
             be.dense_dw_skinny(x, dpre, a.g("dense_img/kernel"), self.N, self.E, rows, self.ldx)
         else:
             self.gemm_sk(x, dpre, a.g("dense_img/kernel"), self.N, self.E, rows, self.ldx, self.E, self.E, transA=True)
@@ -602,7 +613,7 @@ class NIC(ModelBase):
     # instead of G times it), the variable's clip norm is one 8-byte all-reduce of the shards' (sum g^2, sum theta^2), Adam runs
     # on the shard (1 / G of the 246 MB the update of this variable moves) and the updated rows are all-gathered.
     def _enc_shard_state(self, r0, nr):
-        st = self.__dict__.get("_enc_shard")
+        st = self._enc_shard
         if st is None or st["key"] != (r0, nr):
             from .arena import build_spans
             a, e = self.arena, self.arena.entries["dense_img/kernel"]
@@ -653,22 +664,18 @@ class NIC(ModelBase):
         self._enc_grad_stale = None
         ring = False
         if self.grad_sync is None:      # replayed as a launch plan or a hipGraph: ModelBase._step_runner
-            compact = bool(self.__dict__.get("_head_map_fresh"))      # the staging launch built the head's row map
-            staged = bool(self.__dict__.get("_stage_fwd_done"))     # ... and ran the encoder forward: the step leaves it out
+            compact = self._route.head_map_fresh        # the staging launch built the head's row map
+            staged = self._route.stage_fwd_done         # ... and ran the encoder forward: the step leaves it out
             key = ("train", B, T, "compact") if compact else ("train", B, T)
-            seen = self.__dict__.setdefault("_plan_staged", {})
+            seen = self._plan_staged
             if self._graphs.get(key) is not None and seen.get(key) != staged:
                 del self._graphs[key]       # recorded with / without the forward (the entry refuses by alignment): start over
             seen[key] = staged
             if compact and self._head_live_est is None and self._graphs.get(key) is None:
                 # the eager warm-up step synchronises anyway: read the live count once, for the head forward's tile only
                 self._head_live_est = int(self.head_live.item())
-            self._compact, self._stage_fwd = compact, staged
-            try:
-                ring = self._run_step(self._step_runner(), key, lambda: self._train_and_update_graph(B, T))
-            finally:
-                self._compact = self._stage_fwd = False
-            self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
+            ring = self._run_step(self._step_runner(), key, lambda: self._train_and_update_graph(B, T))
+            self._enc_grad_stale = self._enc_last_fused
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
         else:
@@ -682,7 +689,7 @@ class NIC(ModelBase):
         """per (B, T): the B staged rows (betas, state, caption, start token), the greedy ids (T, B), the last sampled
         token and the advantage (R), and the host side of the step's one round trip"""
         R = B * self.self_critical.n_samples
-        st = self.__dict__.get("_scst")
+        st = self._scst
         if st is not None and st["key"] == (B, T):
             return st
         f, dev, i32 = self._f, self.device, torch.int32
@@ -700,6 +707,7 @@ class NIC(ModelBase):
         b*K + k: copy k of scan b), on the device (a torch copy, at staging: a recorded launch plan re-issues backend
         launches only).  Over K identical copies BatchNorm's batch statistics are those of the B rows; every copy draws its
         own Dropout masks (so with input Dropout the copies, and the statistics, differ)."""
+        self._route = StepRoute()
         x, cap, a0, c0 = inputs[:4]
         cap_t = self._to_dev(cap, torch.int32)
         B, T = cap_t.shape
@@ -807,7 +815,7 @@ class NIC(ModelBase):
         st["h_adv"].copy_(torch.from_numpy(adv.astype(np.float32)))
         st["adv"].copy_(st["h_adv"], non_blocking=True)
         ring = self._run_step(run, ("scst_update", R, T), lambda: self._scst_update(R, T))
-        self._enc_grad_stale = self.__dict__.get("_enc_last_fused")
+        self._enc_grad_stale = self._enc_last_fused
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         return self._lr_metric(self._metrics_from(m, loss=0, L2=2, reward=float(reward.mean()), baseline=float(base.mean()),
@@ -946,7 +954,7 @@ class NIC(ModelBase):
         """decoder buffers of one scoring pass of up to Rmax rows: T-1 LSTM steps, their logits, the kernel's outputs"""
         f, U, E, steps = self._f, self.U, self.E, T - 1
         # the persistent chain (passes of <= 128 rows) keeps the gates of every step, the per-step kernels reuse one slab
-        seq_rows = min(Rmax, 128) if self.__dict__.get("_seq_lstm") else 0
+        seq_rows = min(Rmax, 128) if self._seq_lstm else 0
         return dict(cap=torch.zeros(Rmax * T, dtype=torch.int32, device=self.device), xin=f(T * Rmax * E),
                     xz=f(steps * Rmax * 4 * U), hs=f((steps + 1) * Rmax * U), cs=f((steps + 1) * Rmax * U),
                     out=f(steps * Rmax * U), gates=f(max(Rmax, steps * seq_rows) * 4 * U), logits=f(steps * Rmax * self.ldV),
@@ -955,7 +963,7 @@ class NIC(ModelBase):
     def _score_shape(self, st, R, T):
         U, E, steps = self.U, self.E, T - 1
         pre = lambda k, *shape: st[k][:int(np.prod(shape))].view(*shape)
-        seq = bool(self.__dict__.get("_seq_lstm")) and R <= 128 and self.be.lstm_seq_supported(R, U)
+        seq = bool(self._seq_lstm) and R <= 128 and self.be.lstm_seq_supported(R, U)
         return dict(cap=pre("cap", R, T), xin=pre("xin", T * R, E), xz=pre("xz", steps * R, U, 4),
                     hs=pre("hs", steps + 1, R, U), cs=pre("cs", steps + 1, R, U), out=pre("out", steps, R, U),
                     gates=pre("gates", steps, R, U, 4) if seq else pre("gates", R, U, 4),
@@ -1016,7 +1024,7 @@ class NIC(ModelBase):
         U, E, V, ldV = self.U, self.E, self.V, self.ldV
         Bk = B * k
         key = (B, k, max_len, end_id) if cons is None else (B, k, max_len, end_id, G)
-        bufs = self.__dict__.setdefault("_beam_bufs", {})
+        bufs = self._beam_bufs
         if key not in bufs:
             dev, i32, f = self.device, torch.int32, self._f
             bufs[key] = dict(

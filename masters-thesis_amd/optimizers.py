@@ -55,6 +55,7 @@ class _WeightDecay:
 
     Single device only, like weight averaging: dp.attach / a model with a grad_sync, train_step_sam and enable_agc()
     refuse a decaying optimizer with NotImplementedError."""
+    _wd_built = False       # a model has built its optimizer state from this descriptor (ModelBase._init_optimizer_state)
 
     @property
     def weight_decay(self):
@@ -68,7 +69,7 @@ class _WeightDecay:
         """keras's Optimizer.exclude_from_weight_decay: ``var_list`` holds exact variable names, ``var_names`` substrings
         matched against the variable names; each call replaces the earlier exclusions.  Raises once a model has built its
         optimizer state from this descriptor, as keras does once the optimizer is built."""
-        if getattr(self, "_wd_built", False):
+        if self._wd_built:
             raise ValueError("exclude_from_weight_decay() must be called before the model builds its optimizer state")
         for what, v in (("var_list", var_list), ("var_names", var_names)):
             if v is not None and (isinstance(v, str) or not all(isinstance(n, str) for n in v)):

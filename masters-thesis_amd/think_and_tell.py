@@ -136,7 +136,7 @@ class CaptionGenerator(ModelBase):
         self.emb_seg = self.arena.entries["embedding/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
-        if self.optimizer is not None and getattr(self, "opt_m", None) is None:
+        if self.optimizer is not None and self.opt_m is None:
             self._init_optimizer_state()
         self.built = True
 

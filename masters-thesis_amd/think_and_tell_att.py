@@ -110,7 +110,7 @@ class CaptionGenerator(_CaptionGeneratorLSTM):
         self._alloc_splitk([(B, E, N), (R1, U, V), (R1, E, 4 * U), (R1, U, U), (U, 4 * U, R1)])
         self._shape = (B, T)
         self._graphs = {}
-        if self.optimizer is not None and getattr(self, "opt_m", None) is None:
+        if self.optimizer is not None and self.opt_m is None:
             self._init_optimizer_state()
         self.built = True
 

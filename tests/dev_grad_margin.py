@@ -7,7 +7,9 @@ import numpy as np
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import test_gpu_fullsize as F
+from switches import set_switches
 from oracle import models as M
 
 kind = sys.argv[1] if len(sys.argv) > 1 else "attention"
@@ -15,8 +17,7 @@ attrs = dict(a.split("=") for a in sys.argv[2:])
 rng = np.random.default_rng(21)
 rates = tuple(0.0 for _ in F.RATES[kind])
 model = F.make(kind, rates=rates)
-for k, v in attrs.items():
-    setattr(model, k, bool(int(v)))
+set_switches(model, {k: bool(int(v)) for k, v in attrs.items()})      # refuses an undeclared name
 orc = F.make_oracle(kind, rates)
 orc.p = {k: v.astype(np.float64) for k, v in model.get_weights_dict().items()}
 names = [k for k in orc.p if "moving_" not in k]

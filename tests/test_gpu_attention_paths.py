@@ -484,6 +484,6 @@ def test_chain_contract(be):
     assert be.lc_seq_bwd_work_floats(0, 512) == 0 and be.lc_seq_bwd_work_floats(129, 512) == 0
     assert be.lc_seq_bwd_work_floats(128, 512) > 0 and be.lc_seq_bwd_work_floats(64, 256) == 0
     for R, D, A in ((512, 32, 32), (513, 32, 32), (384, 32, 40), (385, 32, 40), (384, 40, 32), (385, 40, 32)):
-        model = types.SimpleNamespace(_seq_lstm=True, use_layer_norm=False, be=be, R=R, D=D, A=A)
+        model = types.SimpleNamespace(_seq_lstm=True, use_lc_seq=True, use_layer_norm=False, be=be, R=R, D=D, A=A)
         admitted = _chain_call(be, 1, 2, R, D, A, 512, poff=1) == [-1001, -1001]
         assert NIC._lc_seq_ok(model) == admitted == (R in (512, 384)), (R, D, A)

@@ -59,13 +59,13 @@ def mock_backend():
     ops.set_backend(old)
 
 
-def make(kind):
+def make(kind, attn_units=5, dropout_attn=0):
     rng = np.random.default_rng(1)
     if kind == "dense":
         model = NIC(N, U, E, V, T, 0, 0, 0, 0.01, 3e-5, 1e-5, device="cpu", seed=11)
     else:
         g = (tiny_groups(N, 4, rng), [16] * 4)
-        model = LcNIC(g, U, 512, 12, 5, V, T, 0, 0, 0, 0, 0, 0.1, 0.01, 0.001, 3e-5, 1e-5, device="cpu", seed=11)
+        model = LcNIC(g, U, 512, 12, attn_units, V, T, 0, 0, 0, dropout_attn, 0, 0.1, 0.01, 0.001, 3e-5, 1e-5, device="cpu", seed=11)
     for name in model.trainable_names():
         model.set_weight(name, 0.3 * rng.standard_normal(model.keras_shapes[name]))
     model.compile(Adam(1e-2, clipnorm=0.1))

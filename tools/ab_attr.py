@@ -5,6 +5,7 @@ import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import bench
+from switches import set_switches
 wl = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("dense", "attention") else "dense"
 arms = []
 for a in sys.argv[1:]:
@@ -16,7 +17,7 @@ batch, _ = bench.synth(0, dev)
 models = []
 for name, flags in arms:
     m = bench.make_model(wl, dev)
-    for k, v in flags.items(): setattr(m, k, v)
+    set_switches(m, flags)             # refuses a name the model's class does not declare
     for _ in range(20): m.train_step(batch)
     models.append((name, m))
 torch.cuda.synchronize()

@@ -3,12 +3,12 @@ import sys, time
 import torch
 sys.path.insert(0, ".")
 import bench
+from switches import set_switches
 
 def run(**attrs):
     dev = torch.device("cuda", 0)
     model = bench.make_model("dense", dev, None)
-    for k, v in attrs.items():
-        setattr(model, k, v)
+    set_switches(model, attrs)         # refuses a name the model's class does not declare
     batch, _ = bench.synth(0, dev)
     for _ in range(30):
         model.train_step(batch)
