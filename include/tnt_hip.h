@@ -443,9 +443,17 @@ int32_t tnt_colsum2_f32(const float* x0, float* out0, int32_t rows0, int32_t C0,
  * bwd: dtable[v][:] = sum over (b,t) with ids[b*T+t]==v of drows[(t*B+b)][:] (every row
  *      of dtable is written: unreferenced rows are zeroed by the call itself);
  *      sq_norm[0] = sum of squares of the un-merged rows (IndexedSlices clipnorm
- *      quirk), overwritten; rowsq_work: B*T floats.
- *      Deterministic (no atomics): one wave per vocabulary row sums its matches in
- *      (b,t) order and writes every row of dtable (no pre-zeroing needed). */
+ *      quirk), overwritten (nullable: no norm, rowsq_work unused); rowsq_work: B*T floats.
+ * Ids outside [0, V): every embedding entry point (fwd, fwd_drop, fwd_drop2, bwd, bwd_sparse) treats an id as
+ *      clip(id, 0, V-1).  The backward scatters a row to the table row the forward gathered it from and counts it in the
+ *      norm; in prev_ids of tnt_embedding_bwd_sparse_f32 an entry >= V stands for row V-1 and every negative entry -- the
+ *      "none" sentinel -1 cannot be told from a stray id -- for row 0.
+ * Deterministic (no atomics): a launch zero-fills dtable, then one workgroup per (b,t) position k = b*T+t and column
+ *      chunk (64 columns; 256 when E % 4 == 0, ldd % 4 == 0 and drows, dtable are 16-byte aligned) looks for an earlier
+ *      occurrence of its id.  The FIRST occurrence owns the vocabulary row: its 4 waves scan the later positions 64 at a
+ *      time (wave w the windows k+1+64w, +256, ...), sum the duplicates' rows in position order, 16 (8 in the 256-column
+ *      form) row loads in flight, and the 4 partial sums are added in wave order.  Fixed partition, fixed order: the same
+ *      bits on every run. */
 int32_t tnt_embedding_fwd_f32(const float* table, const int32_t* ids, float* out, int32_t B,
                               int32_t T, int32_t E, int32_t ldo, int32_t V, void* stream);
 /* fwd + keras Dropout over the logical (B,T,E) tensor in the same pass (NIC.py:131,140): out_drop gets the

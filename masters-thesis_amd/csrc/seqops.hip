@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void emb_bwd_kernel(const float* drows, const 
   for (int base = k + 1 + 64 * w; base < n; base += 256) {
     const int i = base + lane;
     int other = i < n ? ids[i] : -1;
-    other = other >= V ? V - 1 : other;
+    other = other < 0 ? 0 : (other >= V ? V - 1 : other);
     unsigned long long hit = __ballot(i < n && other == id);
     while (hit) {
       int kk[NF];
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void emb_bwd4_kernel(const float* drows, const
   for (int base = k + 1 + 64 * w; base < n; base += 256) {
     const int i = base + lane;
     int other = i < n ? ids[i] : -1;
-    other = other >= V ? V - 1 : other;
+    other = other < 0 ? 0 : (other >= V ? V - 1 : other);
     unsigned long long hit = __ballot(i < n && other == id);
     while (hit) {
       int kk[NF];
@@ -184,6 +184,8 @@ __global__ __launch_bounds__(256) void emb_bwd4_kernel(const float* drows, const
 //                      of the un-deduplicated rows; non-owners write 0);
 //   blocks [n, 2n)     cleanup: entry k of prev_ids (the ids of the PREVIOUS step, -1 = none) whose id does not occur
 //                      in this step's ids gets its gradient row zeroed (first occurrence in prev_ids only).
+// Every id, of this step and of the previous one, counts as clip(id, 0, V-1) -- the row the forward gathered from -- in
+// both halves and in every scan; a negative prev_ids entry (the sentinel included) stands for row 0.
 // Rows touched by neither step are zero already (the table gradient starts zeroed and nothing else writes it), rows of
 // this step are fully overwritten by their owner: no race between the two halves.  The caller copies ids -> prev_ids
 // after this launch (tnt_step_finalize_f32 does).
@@ -227,9 +229,15 @@ __global__ __launch_bounds__(64 * EBS_W) void emb_bwd_sparse_kernel(const float*
   if ((int)blockIdx.x >= n) {
     // ---- cleanup of a row that only the previous step touched
     const int k = blockIdx.x - n;
-    const int id = prev_ids[k];
-    if (id < 0 || id >= V) return;
-    for (int i = threadIdx.x; i < k; i += NT) if (prev_ids[i] == id) s_flag = 1;           // an earlier entry handles it
+    // the previous step wrote the CLAMPED row of this entry.  A negative entry is the "none" sentinel or a stray id, which
+    // cannot be told apart: either way row 0 is cleaned unless this step writes it (a no-op on a row that is zero already)
+    int id = prev_ids[k];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    for (int i = threadIdx.x; i < k; i += NT) {                                             // an earlier entry handles it
+      int other = prev_ids[i];
+      other = other < 0 ? 0 : (other >= V ? V - 1 : other);
+      if (other == id) s_flag = 1;
+    }
     for (int i = threadIdx.x; i < n; i += NT) {
       int cur = ids[i];
       cur = cur < 0 ? 0 : (cur >= V ? V - 1 : cur);
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(64 * EBS_W) void emb_bwd_sparse_kernel(const float*
   for (int base = k + 1 + 64 * w; base < n; base += NT) {
     const int i = base + lane;
     int other = i < n ? ids[i] : -1;
-    other = other >= V ? V - 1 : other;
+    other = other < 0 ? 0 : (other >= V ? V - 1 : other);
     unsigned long long hit = __ballot(i < n && other == id);
     while (hit) {
       int kk[NF];

@@ -395,7 +395,7 @@ class MockBackend:
             self.dropout(out_drop, out_drop, T * B, E, ldo, 0, lw2, lc2, rate2, seed, site2, step, step_dev, rows_per_site=B)
 
     def embedding_bwd(self, drows, ids, dtable, sq_norm, rowsq_work, B, T, E, ldd, V):
-        idv = flat(ids)[:B * T].reshape(B, T)
+        idv = np.clip(flat(ids)[:B * T].reshape(B, T), 0, V - 1)      # include/tnt_hip.h: an id counts as clip(id, 0, V-1)
         rows = mat(drows, T * B, E, ldd).astype(np.float64)
         g = np.zeros((V, E))
         np.add.at(g, idv.T.reshape(-1), rows)
@@ -678,7 +678,7 @@ class MockBackend:
             drows, ldd = tmp, E
         rows = mat(drows, T * B, E, ldd).reshape(T, B, E).astype(np.float64)
         tab = flat(dtable)[:V * E].reshape(V, E)
-        for p in set(int(x) for x in flat(prev_ids)[:B * T] if 0 <= x < V):
+        for p in set(int(x) for x in np.clip(flat(prev_ids)[:B * T], 0, V - 1)):      # -1 (none) and stray negatives: row 0
             tab[p] = 0
         acc = {}
         for b in range(B):
