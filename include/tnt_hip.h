@@ -201,7 +201,9 @@ int32_t tnt_gemm_f32_tile(const float* A, const float* B, float* C, const float*
  * (rows_per_site x cols) tensors, block k using site + k and local rows -- one launch for
  * the T per-timestep masks of lc_NIC.py:255-256.
  * The stream step is step + *step_dev (step_dev nullable): a device-resident counter
- * lets a captured hipGraph replay with a fresh mask each time (see tnt_step_tick). */
+ * lets a captured hipGraph replay with a fresh mask each time (see tnt_step_tick).
+ * rows <= 0 or cols <= 0 is a no-op.  TNT_BADARG, and no launch, for ld < cols and for a rate outside [0, 1) (in
+ * tnt_dropout_f32, tnt_dropout_metric_f32, tnt_dropout2_f32 -- whose rates lie in (0, 1) -- and tnt_dropout_mask4_u8). */
 /* Keep-masks only (no data pass): out[nsites][n/4] bytes, bit j of byte g of block k = element 4g+j of site site0+k is
  * kept -- the same Philox stream (seed, site, step + *step_dev, element) as tnt_dropout_f32, n % 4 == 0.  One launch
  * produces the attention-dropout masks of all T timesteps (attention.py:36, sites S_ATTN + t) off the serial chain;
@@ -234,7 +236,7 @@ int32_t tnt_act_bwd_f32(const float* pre, const float* dy, float* dx, int64_t n,
 /* Backward of y = Dropout(act(pre)) of a layer applied to rows <= 2048 rows, up to its bias gradient, in one launch:
  * dx = dropout'(dy) * act'(pre) (dx may alias dy), dbias[c] = sum_r dx[r][c].  The dropout stream / logical layout
  * arguments are those of tnt_dropout_f32 for the forward's mask (rate 0: no dropout).  cols, ld, lwidth, lcol0 % 4 == 0,
- * 16-byte aligned.  Optional second job in the same launch: out1 = column sums of x1 [rows1 <= 2048][C1] (x1 NULL: none).
+ * 16-byte aligned, ld >= cols, rate in [0, 1): anything else is TNT_BADARG and no launch.  Optional second job in the same launch: out1 = column sums of x1 [rows1 <= 2048][C1] (x1 NULL: none).
  * (TimeDistributed(Dense) + Dropout of the caption head, lc_NIC.py:271-275, and its bias gradients.) */
 int32_t tnt_bias_act_drop_bwd_f32(const float* dy, const float* pre, float* dx, float* dbias, int32_t rows, int32_t cols,
                                   int32_t ld, int32_t act, float slope, int32_t tmajor_B, int32_t lwidth, int32_t lcol0,
@@ -246,7 +248,10 @@ int32_t tnt_bias_act_drop_bwd_f32(const float* dy, const float* pre, float* dx, 
  * x is [rows][C] (ld = C).  training=1: biased batch statistics over rows;
  * moving <- moving*momentum + batch*(1-momentum) (updated in place).
  * Outputs: y, xhat (saved for backward), inv_std[C].  work: C*(2*nchunk+1) floats
- * (nchunk = tnt_bn_nchunk(rows)), same size for the backward and for LayerNorm bwd. */
+ * (nchunk = tnt_bn_nchunk(rows)), same size for the backward and for LayerNorm bwd.
+ * xhat and dx are dense ([rows][C]); only y (ldy) and dy (lddy) carry a row stride.
+ * Every BatchNorm / LayerNorm entry point below returns TNT_BADARG, before any launch, for rows <= 0, C <= 0 and a row
+ * stride (ldy, lddy) smaller than C. */
 int32_t tnt_bn_nchunk(int32_t rows);
 int32_t tnt_batchnorm_fwd_f32(const float* x, const float* gamma, const float* beta,
                               float* mov_mean, float* mov_var, float* y, float* xhat,
@@ -261,7 +266,10 @@ int32_t tnt_batchnorm_fwd_drop_f32(const float* x, const float* gamma, const flo
                                    int32_t training, float eps, float momentum, float* work,
                                    float rate, uint64_t seed, uint32_t site, const uint32_t* step_dev,
                                    void* stream);
-/* dx (nullable), dgamma[C], dbeta[C] from dy (row stride lddy), xhat, inv_std. */
+/* dx (nullable), dgamma[C], dbeta[C] from dy (row stride lddy), xhat, inv_std.  dgamma and dbeta come as a pair (with
+ * work) or are both NULL.  Both NULL is valid only for training = 0, where dx = gamma * inv_std * dy needs no sums; with
+ * training != 0 the input gradient reads both sums, so dx != NULL without them is TNT_BADARG (nothing is launched).
+ * dx == NULL with the sums given (the local sums of synchronised BatchNorm) is valid in either mode. */
 int32_t tnt_batchnorm_bwd_f32(const float* dy, const float* xhat, const float* gamma,
                               const float* inv_std, float* dx, float* dgamma, float* dbeta,
                               int32_t rows, int32_t C, int32_t lddy, int32_t training,
@@ -379,7 +387,9 @@ int32_t tnt_dense_dw_adam_f32(const float* x, const float* dpre, float* theta, f
  *      Dropout element index = r*C + c in streams (seed, site_feat | site_lstm, *step_dev).
  * bwd: dout (gradient w.r.t. out, row stride ldo) -> lstm-in dropout' -> BatchNorm' (dgamma, dbeta) ->
  *      feature dropout' -> LeakyReLU'(pre, slope) -> dpre [rows][C]; dbias[c] = sum_r dpre.
- * One launch each, replacing 5 / 7 dependent launches of the generic entry points above (same arithmetic). */
+ * One launch each, replacing 5 / 7 dependent launches of the generic entry points above (same arithmetic).
+ * TNT_BADARG, and no launch, for rows outside 1 .. 256, C <= 0 or C % 4 != 0, ldo < C or ldo % 4 != 0, r_feat or r_lstm
+ * outside [0, 1) and an operand off 16-byte alignment (forward and backward entry points alike). */
 int32_t tnt_enc_tail_fwd_f32(const float* y, const float* gamma, const float* beta, float* mov_mean,
                              float* mov_var, float* out, float* xhat, float* inv_std, int32_t rows,
                              int32_t C, int32_t ldo, int32_t training, float eps, float momentum,
@@ -409,7 +419,8 @@ int32_t tnt_enc_tail_bwd_f32(const float* dout, const float* xhat, const float* 
                              const uint32_t* step_dev, void* stream);
 /* bwd with an independent in-place dropout' job in the same launch: drop_x [drop_rows][drop_cols] (row stride drop_ld) gets
  * the keep mask of stream (seed, drop_site, *step_dev) in the logical layout arguments of tnt_dropout_f32 -- the text
- * call's LSTM-input dropout over the other rows of the same gradient buffer (NIC.py:131,140).  All % 4 == 0. */
+ * call's LSTM-input dropout over the other rows of the same gradient buffer (NIC.py:131,140).  All % 4 == 0,
+ * drop_ld >= drop_cols, drop_rate in [0, 1). */
 int32_t tnt_enc_tail_bwd_drop_f32(const float* dout, const float* xhat, const float* gamma, const float* inv_std,
                                   const float* pre, float* dpre, float* dgamma, float* dbeta, float* dbias, int32_t rows,
                                   int32_t C, int32_t ldo, float r_feat, float r_lstm, float slope, uint64_t seed,

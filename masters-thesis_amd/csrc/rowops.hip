@@ -447,6 +447,8 @@ extern "C" int32_t tnt_dropout_f32(const float* x, float* y, int32_t rows, int32
                                    int32_t lwidth, int32_t lcol0, int32_t rows_per_site, float rate, uint64_t seed,
                                    uint32_t site, uint32_t step, const uint32_t* step_dev, void* stream) {
   if (rows <= 0 || cols <= 0) return 0;
+  if (ld < cols) return TNT_BADARG(5);
+  if (!(rate >= 0.f && rate < 1.f)) return TNT_BADARG(10);
   const int rsite = rows_per_site > 0 ? rows_per_site : rows;
   if (tmajor_B > 0 && rsite % tmajor_B != 0) return TNT_BADARG(6);
   if (rows_per_site > 0 && tmajor_B > 0) return TNT_BADARG(9);     // per-site blocks are (rows_per_site, cols) row-major
@@ -514,6 +516,7 @@ extern "C" int32_t tnt_dropout_metric_f32(const float* x, float* y, int32_t rows
                                           uint32_t site, uint32_t step, const uint32_t* step_dev, const float* alpha,
                                           float* partial, int32_t T, int32_t B, int32_t R, void* stream) {
   if (rows <= 0 || cols <= 0 || T <= 0 || B <= 0 || R <= 0 || alpha == nullptr || partial == nullptr) return TNT_BADARG(3);
+  if (ld < cols) return TNT_BADARG(5);
   const int rsite = rows_per_site > 0 ? rows_per_site : rows;
   if (tmajor_B > 0 && rsite % tmajor_B != 0) return TNT_BADARG(6);
   if (rows_per_site > 0 && tmajor_B > 0) return TNT_BADARG(9);
@@ -539,6 +542,7 @@ extern "C" int32_t tnt_dropout2_f32(const float* x, float* y, int32_t rows, int3
                                     float rate_b, uint32_t site_b, uint64_t seed, uint32_t step, const uint32_t* step_dev,
                                     void* stream) {
   if (rows <= 0 || cols <= 0) return 0;
+  if (ld < cols) return TNT_BADARG(5);
   if (!(rate_a > 0.f && rate_a < 1.f && rate_b > 0.f && rate_b < 1.f)) return TNT_BADARG(10);
   const int tb[2] = {tmajor_B_a, tmajor_B_b}, rps[2] = {rows_per_site_a, rows_per_site_b};
   for (int k = 0; k < 2; ++k) {
@@ -564,6 +568,7 @@ extern "C" int32_t tnt_dropout_mask4_u8(uint8_t* out, int64_t n, int32_t nsites,
                                        uint32_t site0, uint32_t step, const uint32_t* step_dev, void* stream) {
   if (n <= 0 || nsites <= 0) return 0;
   if (n % 4 != 0) return TNT_BADARG(2);
+  if (!(rate >= 0.f && rate < 1.f)) return TNT_BADARG(4);
   const long n4 = n / 4, total = n4 * nsites;
   long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -820,6 +825,7 @@ extern "C" int32_t tnt_enc_tail_fwd_f32(const float* y, const float* gamma, cons
                                         uint32_t site_lstm, const uint32_t* step_dev, void* stream) {
   if (rows <= 0 || rows > ET_RG * ET_MAXR) return TNT_BADARG(9);
   if (C <= 0 || C % 4 != 0 || ldo < C || ldo % 4 != 0) return TNT_BADARG(10);
+  if (!(r_feat >= 0.f && r_feat < 1.f) || !(r_lstm >= 0.f && r_lstm < 1.f)) return TNT_BADARG(15);
   if (!tnt_aligned16(y) || !tnt_aligned16(out) || !tnt_aligned16(xhat) || !tnt_aligned16(gamma) || !tnt_aligned16(beta) ||
       !tnt_aligned16(mov_mean) || !tnt_aligned16(mov_var) || !tnt_aligned16(inv_std)) return TNT_BADARG(1);
   EncTailArgs a{};
@@ -842,6 +848,7 @@ extern "C" int32_t tnt_enc_tail_fwd_sk_emb_f32(const float* part, int32_t nsplit
                                                uint32_t emb_site, void* stream) {
   if (rows <= 0 || rows > ET_RG * ET_MAXR || nsplit <= 0) return TNT_BADARG(13);
   if (C <= 0 || C % 4 != 0 || ldo < C || ldo % 4 != 0) return TNT_BADARG(14);
+  if (!(r_feat >= 0.f && r_feat < 1.f) || !(r_lstm >= 0.f && r_lstm < 1.f)) return TNT_BADARG(19);
   if (!tnt_aligned16(part) || !tnt_aligned16(bias) || !tnt_aligned16(pre) || !tnt_aligned16(out) || !tnt_aligned16(xhat) ||
       !tnt_aligned16(gamma) || !tnt_aligned16(beta) || !tnt_aligned16(mov_mean) || !tnt_aligned16(mov_var) ||
       !tnt_aligned16(inv_std)) return TNT_BADARG(1);
@@ -854,7 +861,7 @@ extern "C" int32_t tnt_enc_tail_fwd_sk_emb_f32(const float* part, int32_t nsplit
   a.nb_tail = (C + ET_CW - 1) / ET_CW;
   int nbe = 0;
   if (emb_table != nullptr) {       // Embedding width = C (both feed the same LSTM input), rows behind the feature rows
-    if (emb_ids == nullptr || emb_out == nullptr || emb_B <= 0 || emb_T <= 0 || emb_V <= 0 || emb_rate < 0.f || emb_rate >= 1.f ||
+    if (emb_ids == nullptr || emb_out == nullptr || emb_B <= 0 || emb_T <= 0 || emb_V <= 0 || !(emb_rate >= 0.f && emb_rate < 1.f) ||
         !tnt_aligned16(emb_table) || !tnt_aligned16(emb_out)) return TNT_BADARG(25);
     a.emb_table = emb_table; a.emb_ids = emb_ids; a.emb_out = emb_out; a.emb_B = emb_B; a.emb_T = emb_T; a.emb_V = emb_V;
     a.emb_rate = emb_rate; a.emb_site = emb_site;
@@ -883,6 +890,7 @@ extern "C" int32_t tnt_enc_tail_bwd_f32(const float* dout, const float* xhat, co
                                         void* stream) {
   if (rows <= 0 || rows > ET_RG * ET_MAXR) return TNT_BADARG(10);
   if (C <= 0 || C % 4 != 0 || ldo < C || ldo % 4 != 0) return TNT_BADARG(11);
+  if (!(r_feat >= 0.f && r_feat < 1.f) || !(r_lstm >= 0.f && r_lstm < 1.f)) return TNT_BADARG(13);
   if (!tnt_aligned16(dout) || !tnt_aligned16(xhat) || !tnt_aligned16(gamma) || !tnt_aligned16(inv_std) || !tnt_aligned16(pre) ||
       !tnt_aligned16(dpre) || !tnt_aligned16(dgamma) || !tnt_aligned16(dbeta) || !tnt_aligned16(dbias)) return TNT_BADARG(1);
   EncTailArgs a{};
@@ -904,9 +912,10 @@ extern "C" int32_t tnt_enc_tail_bwd_drop_f32(const float* dout, const float* xha
                                              uint32_t drop_site, void* stream) {
   if (rows <= 0 || rows > ET_RG * ET_MAXR) return TNT_BADARG(10);
   if (C <= 0 || C % 4 != 0 || ldo < C || ldo % 4 != 0) return TNT_BADARG(11);
+  if (!(r_feat >= 0.f && r_feat < 1.f) || !(r_lstm >= 0.f && r_lstm < 1.f)) return TNT_BADARG(13);
   if (!tnt_aligned16(dout) || !tnt_aligned16(xhat) || !tnt_aligned16(gamma) || !tnt_aligned16(inv_std) || !tnt_aligned16(pre) ||
       !tnt_aligned16(dpre) || !tnt_aligned16(dgamma) || !tnt_aligned16(dbeta) || !tnt_aligned16(dbias)) return TNT_BADARG(1);
-  if (drop_rate < 0.f || drop_rate >= 1.f || drop_rows <= 0 || ((drop_cols | drop_ld | drop_lwidth | drop_lcol0) & 3) != 0 ||
+  if (!(drop_rate >= 0.f && drop_rate < 1.f) || drop_rows <= 0 || drop_ld < drop_cols || ((drop_cols | drop_ld | drop_lwidth | drop_lcol0) & 3) != 0 ||
       !tnt_aligned16(drop_x) || (drop_tmajor_B > 0 && drop_rows % drop_tmajor_B != 0)) return TNT_BADARG(20);
   EncTailArgs a{};
   a.dout = dout; a.xhat = const_cast<float*>(xhat); a.gamma = gamma; a.inv_std = const_cast<float*>(inv_std); a.pre = pre; a.dpre = dpre; a.dgamma = dgamma;
@@ -944,7 +953,8 @@ extern "C" int32_t tnt_batchnorm_fwd_drop_f32(const float* x, const float* gamma
                                               int32_t C, int32_t ldy, int32_t training, float eps, float momentum,
                                               float* work, float rate, uint64_t seed, uint32_t site,
                                               const uint32_t* step_dev, void* stream) {
-  if (rate < 0.f || rate >= 1.f) return TNT_BADARG(16);
+  if (rows <= 0 || C <= 0 || ldy < C) return TNT_BADARG(9);
+  if (!(rate >= 0.f && rate < 1.f)) return TNT_BADARG(16);
   hipStream_t s = tnt_stream(stream);
   const int nchunk = chunk_count(rows);
   float* mean = work;
@@ -977,8 +987,11 @@ extern "C" int32_t tnt_batchnorm_bwd_act_f32(const float* dy, const float* xhat,
                                              float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t C, int32_t lddy,
                                              int32_t training, float* work, const float* act_pre, float slope,
                                              void* stream) {
+  if (rows <= 0 || C <= 0 || lddy < C) return TNT_BADARG(8);
+  // the training-mode input gradient reads the sums: without them only the inference form (dx = gamma * inv_std * dy) exists
+  if (training != 0 && dx != nullptr && dgamma == nullptr) return TNT_BADARG(5);
   hipStream_t s = tnt_stream(stream);
-  if (dgamma != nullptr || dbeta != nullptr) {        // both null: input gradient only (per-step use inside a T-step chain)
+  if (dgamma != nullptr || dbeta != nullptr) {        // both null: the inference input gradient only
     if (dgamma == nullptr || dbeta == nullptr || work == nullptr) return TNT_BADARG(6);
     const int nchunk = chunk_count(rows);
     float* part = work + C;
@@ -1017,7 +1030,7 @@ extern "C" int32_t tnt_batchnorm_apply_stats_f32(const float* part_all, int32_t 
                                                  const float* beta, float* mov_mean, float* mov_var, float* y, float* xhat,
                                                  float* inv_std, int32_t rows, int32_t C, int32_t ldy, float eps,
                                                  float momentum, float* mean_work, void* stream) {
-  if (rows <= 0 || C <= 0 || nrep <= 0) return TNT_BADARG(10);
+  if (rows <= 0 || C <= 0 || nrep <= 0 || ldy < C) return TNT_BADARG(10);
   hipStream_t s = tnt_stream(stream);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, s, part_all, rows, C, chunk_count(rows), chunk_rows(rows), eps,
                      momentum, mov_mean, mov_var, mean_work, inv_std, nrep);
@@ -1030,7 +1043,7 @@ extern "C" int32_t tnt_batchnorm_apply_stats_f32(const float* part_all, int32_t 
 extern "C" int32_t tnt_batchnorm_dx_f32(const float* dy, int32_t lddy, const float* xhat, const float* gamma,
                                         const float* inv_std, const float* dgamma_sum, const float* dbeta_sum, float* dx,
                                         int32_t rows, int32_t C, int32_t n_total, void* stream) {
-  if (rows <= 0 || C <= 0 || n_total < rows) return TNT_BADARG(8);
+  if (rows <= 0 || C <= 0 || n_total < rows || lddy < C) return TNT_BADARG(8);
   hipLaunchKernelGGL(bn_dx_kernel, dim3(ew_blocks((long)rows * C)), dim3(256), 0, tnt_stream(stream), dy, lddy, xhat, gamma,
                      inv_std, dgamma_sum, dbeta_sum, dx, rows, C, 1, n_total, nullptr, 0.f);
   TNT_LAUNCH_CHECK();
@@ -1039,6 +1052,7 @@ extern "C" int32_t tnt_batchnorm_dx_f32(const float* dy, int32_t lddy, const flo
 
 extern "C" int32_t tnt_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* xhat,
                                          float* inv_std, int32_t rows, int32_t C, int32_t ldy, float eps, void* stream) {
+  if (rows <= 0 || C <= 0 || ldy < C) return TNT_BADARG(6);
   hipLaunchKernelGGL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, tnt_stream(stream), x, gamma, beta, y, xhat,
                      inv_std, rows, C, ldy, eps);
   TNT_LAUNCH_CHECK();
@@ -1048,6 +1062,7 @@ extern "C" int32_t tnt_layernorm_fwd_f32(const float* x, const float* gamma, con
 extern "C" int32_t tnt_layernorm_bwd_f32(const float* dy, const float* xhat, const float* gamma, const float* inv_std,
                                          float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t C, int32_t lddy,
                                          float* work, void* stream) {
+  if (rows <= 0 || C <= 0 || lddy < C) return TNT_BADARG(7);
   hipStream_t s = tnt_stream(stream);
   if (dgamma != nullptr || dbeta != nullptr) {        // both null: input gradient only (per-step use inside a T-step chain)
     if (dgamma == nullptr || dbeta == nullptr || work == nullptr) return TNT_BADARG(6);
@@ -1243,10 +1258,10 @@ extern "C" int32_t tnt_bias_act_drop_bwd_f32(const float* dy, const float* pre, 
                                              int32_t lwidth, int32_t lcol0, float rate, uint64_t seed, uint32_t site,
                                              const uint32_t* step_dev, const float* x1, float* out1, int32_t rows1,
                                              int32_t C1, int32_t ld1, void* stream) {
-  if (rows <= 0 || cols <= 0 || rows > 2048 || ((cols | ld | lwidth | lcol0) & 3) != 0) return TNT_BADARG(4);
+  if (rows <= 0 || cols <= 0 || rows > 2048 || ld < cols || ((cols | ld | lwidth | lcol0) & 3) != 0) return TNT_BADARG(4);
   if (!tnt_aligned16(dy) || !tnt_aligned16(pre) || !tnt_aligned16(dx) || !tnt_aligned16(dbias)) return TNT_BADARG(1);
   if (tmajor_B > 0 && rows % tmajor_B != 0) return TNT_BADARG(9);
-  if (rate < 0.f || rate >= 1.f) return TNT_BADARG(12);
+  if (!(rate >= 0.f && rate < 1.f)) return TNT_BADARG(12);
   if (x1 != nullptr && (rows1 <= 0 || C1 <= 0 || rows1 > 2048 || out1 == nullptr)) return TNT_BADARG(18);
   BadArgs a{};
   a.d.x = dy; a.d.y = dx; a.d.rows = rows; a.d.cols = cols; a.d.ld = ld; a.d.tB = tmajor_B; a.d.lwidth = lwidth;
