@@ -88,7 +88,13 @@ int32_t tnt_gemm_fused_cfg(int32_t M, int32_t N, int32_t K, int32_t transA, int3
  * its kernel / input gradients, the LSTM input projection (NIC.py:138-140) and the LSTM kernel / recurrent-kernel / input
  * gradients.  C = op(A) op(B) (+ bias[N]); operand conventions of tnt_gemm_f32; A, B, C 16-byte aligned, lda / ldb / ldc
  * multiples of 4; a K-contiguous operand (A with transA = 0, B with transB = 1) whose K is not a multiple of 4 must have
- * zeros in the pad columns [K, roundup4(K)) (the layout contract of every buffer of this library).  Exact f32
+ * zeros in the pad columns [K, roundup4(K)) (the layout contract of every buffer of this library), and the floats that follow
+ * them up to the next multiple of the tile's stage depth (32 or 64 floats of k) -- the rest of a row stride above roundup4(K)
+ * and the beginning of the following rows included -- must be FINITE: a row's last stage is fetched whole and what lies past
+ * K is multiplied by zeros, so a NaN or an Inf there (in a view into an uninitialised buffer, say) lands in C.  Floats behind
+ * the last row of the operand are not read.  Around an M/N-contiguous operand anything may stand: what is read there only
+ * reaches rows / columns of C past M / N, which are not stored (with splitk > 1 it must not be the bit pattern 0x7FC5EED5, the
+ * exchange buffer's "not written yet" word, for which an owner would wait until it gives up and sets `sync`).  Exact f32
  * (v_mfma_f32_16x16x4_f32), fixed summation order: bitwise reproducible.  cfg selects the workgroup tile (table in
  * csrc/gemm3.hip; tools/gemm3_scan.py). */
 int32_t tnt_gemm3_f32(const float* A, const float* B, float* C, const float* bias, float* colsum, const float* A2,

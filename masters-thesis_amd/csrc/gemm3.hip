@@ -203,7 +203,9 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
   // Piece p (0 .. NPW-1) of this wave for the NEXT stage not yet issued -> the LDS buffer at byte offset boff; the
   // per-lane offsets then advance by one stage.  Stages past the workgroup's last one are issued too (every stage has the
   // same piece count): an MC operand's rows past K are out of range (zeros, no traffic); a KC operand's columns past K
-  // read on into the following rows -- harmless, never multiplied (NT: masked; NN: B's rows there are zero).
+  // read on into the rest of the row stride and the following rows.  NT: A's are masked, so B's meet zeros; NN: A's meet B's
+  // rows past K, which read as zeros.  They ARE multiplied, by zeros -- which is why include/tnt_hip.h requires those floats
+  // to be finite (masking them as well was measured: +0.45 % on the training step, profiles/gemm_paths_bench.txt).
   auto issue_piece = [&](int boff, int p) __attribute__((always_inline)) {
     if (p < OA::NIW) {
       const int i = p, j = wave + i * NW;
