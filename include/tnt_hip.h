@@ -1141,6 +1141,64 @@ int32_t tnt_dense_dw_adamw_fin_f32(const float* x, const float* dpre, float* the
                                    const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
                                    const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx, const float* lr,
                                    float wd, void* stream);
+/* ---- global-norm gradient clipping (tf.clip_by_global_norm; keras `global_clipnorm=`) inside the update launches.
+ * Per variable s, q_s is the squared clip-norm input that the per-variable clip of the same route uses:
+ *     fin form   (partial != NULL, in front of tnt_adam_fin_gclip_f32; the rule of tnt_adam_fin_f32's span workgroups)
+ *         s == extra_seg and n_extra > 0:  sum of extra_part[0..n_extra), lanes of a wave striding by 64, then the
+ *                                          wave tree -- the Embedding's un-deduplicated IndexedSlices norm, which is
+ *                                          also what tf.linalg.global_norm takes
+ *         else sq_override[s] >= 0:        sq_override[s]
+ *         else                             the sum over the variable's spans of partial[2 k] = sum (g + 2 lambda theta)^2,
+ *                                          in the order of tnt_step_finalize_f32 (<= 8 spans serially, more lane-strided)
+ *     table form (sq != NULL, behind tnt_step_finalize_f32 or tnt_seg_sqnorm_f32, which filed sq)
+ *         sq_override[s] >= 0 ? sq_override[s] : sq[s]
+ * G = sum_s q_s in float32, in ONE fixed order for both forms: 256 accumulators A_t = ((q_t + q_{t+256}) + q_{t+512}) + ...,
+ * each 64 of them summed by the library's wave tree (offsets 32, 16, 8, 4, 2, 1) into W_0..W_3, and
+ * G = (W_0 + W_1) + (W_2 + W_3).  No atomics: two launches on the same inputs write the same bits, and so do the two
+ * forms where sq[s] is the span sum.  tnt_global_sqnorm_f32 is one launch of one workgroup that writes gsq[0] = G; it
+ * takes no guard word (G is a pure function of the step's gradients) and must run behind the norm launch(es) and in
+ * front of the first update launch of the step.
+ * With a threshold c > 0 every gradient element of every variable is scaled by
+ *     cs = c / fmaxf(sqrtf(G), c)                         G <= c^2 gives cs == 1.0f exactly
+ * which is tf.clip_by_global_norm up to rounding.  L2, the Adam / SGD arithmetic, decoupled decay, the guard rule, the
+ * metrics ring and the side workgroup's filings are those of the plain entries.  Each *_gclip_f32 entry is its plain
+ * counterpart's kernel with the switch on at compile time and takes the counterpart's arguments, in which `clipnorm`
+ * is c and sq / sq_override / partial[k0:k1] are not read for clipping, plus `gsq` (read on the device when the launch
+ * runs: a replayed plan or hipGraph clips by the live word) and an optional decay:
+ *     tnt_adam_gclip_f32               (tnt_adam_ring_f32)   gsq, lr, seg_wd   seg_wd NULL: no decay; with it lr must be given
+ *     tnt_adam_fin_gclip_f32           (tnt_adam_fin_f32)    gsq, seg_wd       lr is fin->lr
+ *     tnt_sgd_gclip_f32                (tnt_sgd_f32)         gsq, seg_wd       with seg_wd, lr_dev must be given
+ *     tnt_dense_dw_adam_gclip_f32, tnt_dense_dw_adam_fin_gclip_f32             gsq, lr, wd   lr NULL: no decay
+ * TNT_BADARG, and no launch, for a null gsq and for a threshold that is not a finite number > 0. */
+int32_t tnt_global_sqnorm_f32(const float* partial, const int32_t* seg_first, const float* sq, const float* sq_override,
+                              const float* extra_part, int32_t n_extra, int32_t extra_seg, int32_t nseg, float* gsq,
+                              void* stream);
+int32_t tnt_adam_gclip_f32(float* theta, float* m, float* v, const float* grad,
+                           const int32_t* span_seg, const int64_t* span_off, const int32_t* span_len,
+                           const float* seg_l2, const float* sq, const float* sq_override,
+                           int32_t nspan, float lr_t, const float* lr_t_dev, float beta1, float beta2,
+                           float eps, float clipnorm, const uint32_t* guard, const float* met, int32_t nmet, float* ring,
+                           int32_t ring_rows, uint32_t* ring_t, const float* gsq, const float* lr, const float* seg_wd,
+                           void* stream);
+int32_t tnt_adam_fin_gclip_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                               const int64_t* span_off, const int32_t* span_len, const float* sq_override, int32_t nspan,
+                               float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met, int32_t nmet,
+                               float* ring, int32_t ring_rows, uint32_t* ring_t, const float* gsq, const float* seg_wd,
+                               void* stream);
+int32_t tnt_sgd_gclip_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                          const int64_t* span_off, const int32_t* span_len, const float* seg_l2,
+                          const float* sq, const float* sq_override, int32_t nspan, float lr, const float* lr_dev,
+                          float momentum, float clipnorm, const uint32_t* guard, const float* gsq, const float* seg_wd,
+                          void* stream);
+int32_t tnt_dense_dw_adam_gclip_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                    const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                                    float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N, int32_t E,
+                                    int32_t Bk, int32_t ldx, const float* gsq, const float* lr, float wd, void* stream);
+int32_t tnt_dense_dw_adam_fin_gclip_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                        const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                        const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                        const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx,
+                                        const float* gsq, const float* lr, float wd, void* stream);
 /* ---- adaptive gradient clipping, unit-wise (AttemptFour/Model/agc.py:20-38; call site lc_NIC.py:388) ----
  * Applied in place to the flat gradient arena before the norms / clip-by-norm / Adam: per variable v (table entry:
  * arena offset var_off, row stride var_ld, L2 lambda var_lam) and per unit = output column of a keras (in, out) kernel

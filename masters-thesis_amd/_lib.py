@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 124
+TNT_VERSION = 125
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -151,6 +151,12 @@ SIGNATURES = {
     "tnt_sgdw_f32": [P, P, P, P, P, P, P, P, P, I32, P, F32, F32, P, P, P],
     "tnt_dense_dw_adamw_f32": [P, P, P, P, P, F32, P, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, F32, P],
     "tnt_dense_dw_adamw_fin_f32": [P, P, P, P, P, F32, P, I32, I32, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, F32, P],
+    "tnt_global_sqnorm_f32": [P, P, P, P, P, I32, I32, I32, P, P],
+    "tnt_adam_gclip_f32": [P, P, P, P, P, P, P, P, P, P, I32, F32, P, F32, F32, F32, F32, P, P, I32, P, I32, P, P, P, P, P],
+    "tnt_adam_fin_gclip_f32": [P, P, P, P, P, P, P, P, I32, F32, F32, P, P, I32, P, I32, P, P, P, P],
+    "tnt_sgd_gclip_f32": [P, P, P, P, P, P, P, P, P, I32, F32, P, F32, F32, P, P, P, P],
+    "tnt_dense_dw_adam_gclip_f32": [P, P, P, P, P, F32, P, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, P, F32, P],
+    "tnt_dense_dw_adam_fin_gclip_f32": [P, P, P, P, P, F32, P, I32, I32, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, P, F32, P],
     "tnt_agc_f32": [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, F32, F32, P],
     "tnt_colsq_f32": [P, P, I32, I32, I32, P],
     "tnt_step_tick": [P, P, P, P, F32, F32, P, P],

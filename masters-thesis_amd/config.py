@@ -23,15 +23,21 @@ def build_optimizer(config):
     wd, excl = config.get("weight_decay"), config.get("weight_decay_exclude")
     if excl is not None and (isinstance(excl, str) or not isinstance(excl, (list, tuple))):
         raise ValueError(f"weight_decay_exclude must be a list of name substrings, got {excl!r}")
+    # global_clipnorm: an optional key of this library's, one norm over all gradients (optimizers._GlobalClipnorm).  With it
+    # set, ``clipnorm`` may be absent or null; the two together are refused, as in keras
+    gclip = config.get("global_clipnorm")
+    if gclip is not None and config.get("clipnorm") is not None:
+        raise ValueError("clipnorm and global_clipnorm cannot both be set: at most one of them, as in keras")
     if config["optimizer"] in ("Adam", "AdamW"):
         kw = dict(learning_rate=0.0001 if sched is None else sched, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9,
-                  clipnorm=config["clipnorm"])
+                  clipnorm=config["clipnorm"] if gclip is None else None, global_clipnorm=gclip)
         if config["optimizer"] == "AdamW":
             opt = AdamW(weight_decay=0.004 if wd is None else wd, **kw)
         else:
             opt = Adam(weight_decay=wd, **kw)
     elif config["optimizer"] == "SGD":
-        opt = SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False, weight_decay=wd)
+        opt = SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False, weight_decay=wd,
+                  global_clipnorm=gclip)
     else:
         raise ValueError("No optimizer specified")
     if excl:

@@ -314,6 +314,9 @@ struct DwArgs {
   const float* fin_partial; int fin_k0, fin_k1;
   // EPI 2 with WD (tnt_dense_dw_adamw_f32 / _fin_f32): decoupled weight decay of the one variable, lr read on the device
   const float* lr_dev; float wd;
+  // EPI 2 with GC (tnt_dense_dw_adam_gclip_f32 / _fin_gclip_f32): global-norm clipping.  `sq` is then the one word that
+  // tnt_global_sqnorm_f32 wrote and clipnorm the global threshold; sq_override / fin_partial are not read.  (No field of
+  // its own: the struct is the kernel's argument block, and growing it moves the words behind it in every instantiation.)
 };
 
 // PERM (every wave has all its TPW tiles, TPW = 2 or 4): MFMA column n of tile j is output column TPW n + j of the
@@ -328,10 +331,12 @@ struct DwArgs {
 //      loads are issued before the previous strip's stores, so waiting for them never drains the stores), g is never
 //      stored -- 24 bytes per parameter instead of 4 (dW write) + 8 (norm pass) + 28 (Adam).
 //      WD: the step is taken from theta - (lr * wd) * theta (decoupled weight decay, tnt_decayed in tnt_fin.h).
-template <int TPW, bool PERM, int EPI = 0, bool NTM = false, bool WD = false>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
+//      GC: the clip scale is c / max(sqrt(gsq[0]), c), one norm over all variables (global-norm clipping, optim.hip).
+template <int TPW, bool PERM, int EPI = 0, bool NTM = false, bool WD = false, bool GC = false>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
 __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
   static_assert(EPI == 0 || (PERM && TPW == 4), "fused epilogues use the vector row layout");
   static_assert(!WD || EPI == 2, "the decay belongs to the fused update");
+  static_assert(!GC || EPI == 2, "the global clip belongs to the fused update");
   constexpr int DW_MAXT = TPW;
   if (EPI == 2 && a.guard && a.guard[0] != 0u) return;       // the step's forward pass was invalid: leave the model untouched
   __shared__ float As[2][DW_KS * 4 * DW_LDA];
@@ -440,7 +445,9 @@ __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
   // (behind the first strip's loads: the clip norm may come from a chain of dependent loads, tnt_dense_dw_adam_fin_f32)
   if (EPI == 2) {
     cs = 1.f;
-    if (a.clipnorm > 0.f) {
+    if (GC) {
+      cs = a.clipnorm / fmaxf(sqrtf(a.sq[0]), a.clipnorm);           // one word in the place of every wave's tnt_seg_sums
+    } else if (a.clipnorm > 0.f) {
       float sqv = a.fin_partial ? tnt_seg_sums(a.fin_partial, a.fin_k0, a.fin_k1, lane).x : a.sq[0];
       if (a.sq_override && a.sq_override[0] >= 0.f) sqv = a.sq_override[0];
       cs = a.clipnorm / fmaxf(sqrtf(sqv), a.clipnorm);
@@ -1010,17 +1017,22 @@ extern "C" int32_t tnt_dense_dw_sqnorm_f32(const float* x, const float* dpre, co
 static int32_t dw_adam_launch(const float* x, const float* dpre, float* theta, float* m, float* v, float l2, const float* sq,
                               const float* partial, int32_t k0, int32_t k1, const float* sq_override, const float* lr_t_dev,
                               float beta1, float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N, int32_t E,
-                              int32_t Bk, int32_t ldx, const float* lr, float wd, void* stream) {
+                              int32_t Bk, int32_t ldx, const float* lr, float wd, void* stream, const float* gsq = nullptr) {
   const int nstrip = (N + DW_MS - 1) / DW_MS, grid = nstrip < 256 ? nstrip : 256;
   DwArgs a{};
   a.x = x; a.dpre = dpre; a.N = N; a.E = E; a.Bk = Bk; a.ldx = ldx;
-  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = sq; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
+  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = gsq ? gsq : sq; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
   a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.guard = guard;
   a.fin_partial = partial; a.fin_k0 = k0; a.fin_k1 = k1;
   a.lr_dev = lr; a.wd = wd;
   const dim3 g(grid, E / 512);
   const bool nt = tnt_stream_policy_nt();
-  if (lr != nullptr && nt) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true, true>), g, dim3(512), 0, tnt_stream(stream), a);
+  if (gsq != nullptr) {      // the global-clip forms: the same four instantiations with GC
+    using Kern = void (*)(DwArgs);
+    static const Kern gc[2][2] = {{dense_dw_skinny_kernel<4, true, 2, false, false, true>, dense_dw_skinny_kernel<4, true, 2, true, false, true>},
+                                  {dense_dw_skinny_kernel<4, true, 2, false, true, true>, dense_dw_skinny_kernel<4, true, 2, true, true, true>}};
+    hipLaunchKernelGGL(gc[lr != nullptr][nt], g, dim3(512), 0, tnt_stream(stream), a);
+  } else if (lr != nullptr && nt) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true, true>), g, dim3(512), 0, tnt_stream(stream), a);
   else if (lr != nullptr) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, false, true>), g, dim3(512), 0, tnt_stream(stream), a);
   else if (nt) hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2, true>), g, dim3(512), 0, tnt_stream(stream), a);
   else hipLaunchKernelGGL((dense_dw_skinny_kernel<4, true, 2>), g, dim3(512), 0, tnt_stream(stream), a);
@@ -1075,6 +1087,37 @@ extern "C" int32_t tnt_dense_dw_adamw_fin_f32(const float* x, const float* dpre,
   if (!dw_wd_ok(lr, wd)) return TNT_BADARG(4);
   return dw_adam_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard,
                         N, E, Bk, ldx, lr, wd, stream);
+}
+
+// The global-clip forms (definition: tnt_global_sqnorm_f32 in include/tnt_hip.h): their plain counterpart's arguments, so
+// that a caller issues one in the other's place, plus the word `gsq` and a decay that may be absent (lr == nullptr: none).
+// clipnorm is the global threshold; sq / partial[k0:k1] / sq_override are checked as the counterpart checks them, not read.
+extern "C" int32_t tnt_dense_dw_adam_gclip_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                               const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                                               float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N,
+                                               int32_t E, int32_t Bk, int32_t ldx, const float* gsq, const float* lr, float wd,
+                                               void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || sq == nullptr)
+    return TNT_BADARG(3);
+  if (lr != nullptr && !dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  return dw_adam_launch(x, dpre, theta, m, v, l2, sq, nullptr, 0, 0, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard, N, E,
+                        Bk, ldx, lr, lr ? wd : 0.f, stream, gsq);
+}
+
+extern "C" int32_t tnt_dense_dw_adam_fin_gclip_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                                   const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                                   const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                                   const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx,
+                                                   const float* gsq, const float* lr, float wd, void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || partial == nullptr || k0 < 0 || k1 <= k0)
+    return TNT_BADARG(3);
+  if (lr != nullptr && !dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  return dw_adam_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard,
+                        N, E, Bk, ldx, lr, lr ? wd : 0.f, stream, gsq);
 }
 
 extern "C" int32_t tnt_block_dense_dx_f32(const float* dpre, const float* W, float* dx, int32_t B, int32_t R,

@@ -55,17 +55,80 @@ __device__ __forceinline__ float clip_scale(const float* sq, const float* sq_ove
   return clipnorm / fmaxf(sqrtf(q), clipnorm);
 }
 
+// ---- global-norm clipping (tnt_global_sqnorm_f32; definition in include/tnt_hip.h): gsq[0] = G = sum_s q_s, q_s the squared
+// clip-norm input of variable s, for the GC instantiations of the update kernels (cs = c / max(sqrt(G), c), tnt_gclip_scale).
+// One workgroup, no atomics.  Thread t owns the variables t, t + 256, t + 512, ... and adds their q_s in that order; the 256
+// thread sums meet in tnt_wave_sum's tree and the four wave sums as (W0 + W1) + (W2 + W3).  Both input forms add in this
+// order, so they write the same bits wherever sq[s] holds the sum of the variable's span partials in tnt_seg_sums order.
+//   fin form (partial != nullptr; in front of tnt_adam_fin_gclip_f32): adam_fin_kernel's rule per variable -- the
+//     Embedding's extra_part total, else a supplied norm, else the span partials: up to 8 spans serially by the owning
+//     thread, more by the owning thread's whole wave (tnt_seg_sums), as the side workgroup walks them;
+//   table form (behind tnt_step_finalize_f32 / tnt_seg_sqnorm_f32): clip_scale's rule, sq_override[s] >= 0 else sq[s].
+struct GsqArgs {
+  const float* partial; const int32_t* seg_first; const float* sq; const float* sq_override; const float* extra_part;
+  int n_extra, extra_seg, nseg; float* gsq;
+};
+
+__global__ __launch_bounds__(256) void global_sqnorm_kernel(GsqArgs a) {
+  __shared__ float sw[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const bool fin = a.partial != nullptr;
+  float e = 0.f;
+  if (fin && a.n_extra > 0) {                                // every wave, in the order adam_fin_kernel's workgroups use
+    for (int i = lane; i < a.n_extra; i += 64) e += a.extra_part[i];
+    e = tnt_wave_sum(e);
+  }
+  float acc = 0.f;
+  for (int s0 = 0; s0 < a.nseg; s0 += 256) {                 // the trip count is uniform: the waves vote inside
+    const int s = s0 + tid;
+    const bool live = s < a.nseg;
+    const float ov = live && a.sq_override ? a.sq_override[s] : -1.f;
+    float q = 0.f;
+    if (fin) {
+      const bool is_extra = live && s == a.extra_seg && a.n_extra > 0;
+      const bool walk = live && !is_extra && !(ov >= 0.f);   // a norm that comes from elsewhere: its partials are not read
+      int k0 = 0, k1 = 0;
+      if (walk) { k0 = a.seg_first[s]; k1 = a.seg_first[s + 1]; }
+      if (k1 - k0 <= 8)
+        for (int k = k0; k < k1; ++k) q += a.partial[2 * k];
+      unsigned long long big = __ballot(k1 - k0 > 8);
+      while (big) {
+        const int j = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const float2 qs = tnt_seg_sums(a.partial, __shfl(k0, j, 64), __shfl(k1, j, 64), lane);
+        if (lane == j) q = qs.x;
+      }
+      if (is_extra) q = e;
+      else if (ov >= 0.f) q = ov;
+    } else if (live) {
+      q = ov >= 0.f ? ov : a.sq[s];
+    }
+    acc += q;                                                // + 0 behind the last variable changes nothing
+  }
+  acc = tnt_wave_sum(acc);
+  if (lane == 0) sw[w] = acc;
+  __syncthreads();
+  if (tid == 0) a.gsq[0] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+
+// the GC instantiations' clip scale from the one word: the form of clip_scale, G <= c^2 gives 1.0f exactly
+__device__ __forceinline__ float tnt_gclip_scale(const float* gsq, float clipnorm) {
+  return clipnorm / fmaxf(sqrtf(gsq[0]), clipnorm);
+}
+
 struct MetRing { const float* met; float* ring; uint32_t* ring_t; int nmet, rows; };
 
 // WD (here and in adam_fin_kernel, sgd_kernel, csrc/encoder.hip's EPI 2): decoupled weight decay, the step is taken from
 // theta - (lr * seg_wd[seg]) * theta instead of theta (tnt_decayed); lr is read on the device.  Without WD the two
 // trailing pointers are not read.
-template <bool WD>
+// GC (the same four kernels): global-norm clipping, clipnorm is the threshold of the one norm over all variables and the
+// scale comes from gsq[0] (tnt_gclip_scale); sq / sq_override are not read.  Without GC the trailing gsq is not read.
+template <bool WD, bool GC = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
                                                    const float* sq, const float* sq_override, int nspan, float lr_t,
                                                    const float* lr_t_dev, float b1, float b2, float eps,
                                                    float clipnorm, const uint32_t* guard, MetRing r, const float* lr_dev,
-                                                   const float* seg_wd) {
+                                                   const float* seg_wd, const float* gsq) {
   const int sp = blockIdx.x;
   if (sp >= nspan) return;
   // Metrics ring (one wave of workgroup 0, off every critical path: the metrics are final before this launch starts): the
@@ -83,7 +146,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float
   const int len = t.span_len[sp];
   const int seg = t.span_seg[sp];
   const float lam2 = 2.f * t.seg_l2[seg];
-  const float cs = clip_scale(sq, sq_override, seg, clipnorm);
+  const float cs = GC ? tnt_gclip_scale(gsq, clipnorm) : clip_scale(sq, sq_override, seg, clipnorm);
   const float dk = WD ? lr_dev[0] * seg_wd[seg] : 0.f;
   const float ob1 = 1.f - b1, ob2 = 1.f - b2;
   const int len4 = len & ~3;
@@ -150,10 +213,10 @@ __device__ __forceinline__ void fin_arrive_and_tick(const FinArgs& f, unsigned t
 
 constexpr int AF_U = 4;          // rounds of 1024 elements in flight per span workgroup (tnt_adam_fin_f32)
 
-template <bool NT, bool WD>
+template <bool NT, bool WD, bool GC = false>
 __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
                                                        const float* sq_override, int nspan, float eps, float clipnorm,
-                                                       FinArgs f, MetRing r) {
+                                                       FinArgs f, MetRing r, const float* gsq) {
   // workgroup 0 is the side workgroup: its work is a chain of dependent loads (~8 us end to end), so it is dispatched FIRST
   // and runs beside the whole update instead of hanging off its last round
   const int sp = (int)blockIdx.x - 1, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -186,7 +249,9 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
       const float lam2 = 2.f * f.seg_l2[seg];
       const float dk = WD ? f.lr[0] * f.seg_wd[seg] : 0.f; // one uniform scalar: the AF_U x 4 float4 in flight are untouched
       float cs = 1.f;
-      if (clipnorm > 0.f) {
+      if (GC) {
+        cs = tnt_gclip_scale(gsq, clipnorm);               // one word in the chain's place: nothing depends on the variable
+      } else if (clipnorm > 0.f) {
         float q;
         if (seg == f.extra_seg && f.n_extra > 0) {         // the Embedding: norm of the un-merged IndexedSlices rows
           q = 0.f;
@@ -289,11 +354,11 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
   if (tid == 0) fin_arrive_and_tick(f, (unsigned)nspan + 1u);
 }
 
-template <bool WD>
+template <bool WD, bool GC = false>
 __global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, const float* grad, SpanTab t,
                                                   const float* sq, const float* sq_override, int nspan, float lr,
                                                   const float* lr_dev, float momentum, float clipnorm,
-                                                  const uint32_t* guard, const float* seg_wd) {
+                                                  const uint32_t* guard, const float* seg_wd, const float* gsq) {
   const int sp = blockIdx.x;
   if (sp >= nspan) return;
   if (guard && guard[0] != 0u) return;
@@ -302,7 +367,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, cons
   const int len = t.span_len[sp];
   const int seg = t.span_seg[sp];
   const float lam2 = 2.f * t.seg_l2[seg];
-  const float cs = clip_scale(sq, sq_override, seg, clipnorm);
+  const float cs = GC ? tnt_gclip_scale(gsq, clipnorm) : clip_scale(sq, sq_override, seg, clipnorm);
   const float dk = WD ? lr * seg_wd[seg] : 0.f;
   for (int i = threadIdx.x; i < len; i += 256) {
     const float w = theta[off + i];
@@ -590,21 +655,46 @@ int32_t adam_ring_launch(float* theta, float* m, float* v, const float* grad, co
                          const int32_t* span_len, const float* seg_l2, const float* sq, const float* sq_override, int32_t nspan,
                          float lr_t, const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
                          const uint32_t* guard, const float* met, int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t,
-                         const float* lr, const float* seg_wd, void* stream) {
+                         const float* lr, const float* seg_wd, const float* gsq, void* stream) {
   if (nspan <= 0) return ring ? TNT_BADARG(11) : 0;
   if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(20);
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
   const MetRing r{met, ring, ring_t, nmet, ring_rows};
-  if (seg_wd != nullptr)
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override,
-                       nspan, lr_t, lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, lr, seg_wd);
-  else
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override,
-                       nspan, lr_t, lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, nullptr, nullptr);
+  const bool wd = seg_wd != nullptr;
+  // ... and tnt_adam_gclip_f32 (gsq != nullptr: the GC instantiations, with or without decay)
+  const auto k = gsq != nullptr ? (wd ? adam_kernel<true, true> : adam_kernel<false, true>)
+                                : (wd ? adam_kernel<true, false> : adam_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override, nspan, lr_t,
+                     lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, wd ? lr : nullptr, seg_wd, gsq);
   TNT_LAUNCH_CHECK();
   return 0;
 }
 }  // namespace
+
+extern "C" int32_t tnt_global_sqnorm_f32(const float* partial, const int32_t* seg_first, const float* sq,
+                                         const float* sq_override, const float* extra_part, int32_t n_extra,
+                                         int32_t extra_seg, int32_t nseg, float* gsq, void* stream) {
+  if (gsq == nullptr || nseg <= 0 || n_extra < 0) return TNT_BADARG(1);
+  if ((partial == nullptr) == (sq == nullptr)) return TNT_BADARG(2);          // one form or the other
+  if (partial != nullptr && seg_first == nullptr) return TNT_BADARG(3);
+  if (partial == nullptr && (extra_part != nullptr && n_extra > 0)) return TNT_BADARG(4);   // the table form has no extra job
+  GsqArgs a{partial, seg_first, sq, sq_override, extra_part, extra_part ? n_extra : 0, extra_seg, nseg, gsq};
+  hipLaunchKernelGGL(global_sqnorm_kernel, dim3(1), dim3(256), 0, tnt_stream(stream), a);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t tnt_adam_gclip_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                      const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                      const float* sq_override, int32_t nspan, float lr_t, const float* lr_t_dev, float beta1,
+                                      float beta2, float eps, float clipnorm, const uint32_t* guard, const float* met,
+                                      int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, const float* gsq,
+                                      const float* lr, const float* seg_wd, void* stream) {
+  if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (seg_wd != nullptr && lr == nullptr) return TNT_BADARG(21);
+  return adam_ring_launch(theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev, beta1,
+                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, lr, seg_wd, gsq, stream);
+}
 
 extern "C" int32_t tnt_adam_ring_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
                                      const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
@@ -612,7 +702,7 @@ extern "C" int32_t tnt_adam_ring_f32(float* theta, float* m, float* v, const flo
                                      float beta2, float eps, float clipnorm, const uint32_t* guard, const float* met,
                                      int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, void* stream) {
   return adam_ring_launch(theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev, beta1,
-                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, nullptr, nullptr, stream);
+                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t tnt_adamw_ring_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
@@ -623,7 +713,7 @@ extern "C" int32_t tnt_adamw_ring_f32(float* theta, float* m, float* v, const fl
                                       const float* seg_wd, void* stream) {
   if (lr == nullptr || seg_wd == nullptr) return TNT_BADARG(21);
   return adam_ring_launch(theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev, beta1,
-                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, lr, seg_wd, stream);
+                          beta2, eps, clipnorm, guard, met, nmet, ring, ring_rows, ring_t, lr, seg_wd, nullptr, stream);
 }
 
 extern "C" int32_t tnt_adam_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
@@ -641,7 +731,24 @@ extern "C" int32_t tnt_sgd_f32(float* theta, float* mom, const float* grad, cons
   if (nspan <= 0) return 0;
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
   hipLaunchKernelGGL(sgd_kernel<false>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override,
-                     nspan, lr, lr_dev, momentum, clipnorm, guard, nullptr);
+                     nspan, lr, lr_dev, momentum, clipnorm, guard, nullptr, nullptr);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+// seg_wd (nullable) decays as tnt_sgdw_f32 does, at the device learning rate: lr_dev must be given with it
+extern "C" int32_t tnt_sgd_gclip_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                                     const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                     const float* sq_override, int32_t nspan, float lr, const float* lr_dev, float momentum,
+                                     float clipnorm, const uint32_t* guard, const float* gsq, const float* seg_wd,
+                                     void* stream) {
+  if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (seg_wd != nullptr && lr_dev == nullptr) return TNT_BADARG(14);
+  if (nspan <= 0) return 0;
+  SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
+  const auto k = seg_wd != nullptr ? sgd_kernel<true, true> : sgd_kernel<false, true>;
+  hipLaunchKernelGGL(k, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override, nspan, lr, lr_dev,
+                     momentum, clipnorm, guard, seg_wd, gsq);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -654,7 +761,7 @@ extern "C" int32_t tnt_sgdw_f32(float* theta, float* mom, const float* grad, con
   if (nspan <= 0) return 0;
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
   hipLaunchKernelGGL(sgd_kernel<true>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override,
-                     nspan, 0.f, lr, momentum, clipnorm, guard, seg_wd);
+                     nspan, 0.f, lr, momentum, clipnorm, guard, seg_wd, nullptr);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -763,12 +870,12 @@ int32_t fin_fill(FinArgs& f, const tnt_finalize_desc* d) {
 }  // namespace
 
 namespace {
-// tnt_adam_fin_f32 (seg_wd == nullptr: the plain instantiations) and tnt_adamw_fin_f32
-template <bool WD>
+// tnt_adam_fin_f32 (seg_wd == nullptr: the plain instantiations), tnt_adamw_fin_f32 and, with GC, tnt_adam_fin_gclip_f32
+template <bool WD, bool GC = false>
 int32_t adam_fin_launch(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg, const int64_t* span_off,
                         const int32_t* span_len, const float* sq_override, int32_t nspan, float eps, float clipnorm,
                         const tnt_finalize_desc* fin, const float* met, int32_t nmet, float* ring, int32_t ring_rows,
-                        uint32_t* ring_t, const float* seg_wd, void* stream) {
+                        uint32_t* ring_t, const float* seg_wd, const float* gsq, void* stream) {
   if (nspan < 0) return TNT_BADARG(9);
   if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(13);
   FinArgs f;
@@ -776,11 +883,11 @@ int32_t adam_fin_launch(float* theta, float* m, float* v, const float* grad, con
   f.seg_wd = seg_wd;
   SpanTab t{span_seg, span_off, span_len, nullptr, nullptr};
   if (tnt_stream_policy_nt())
-    hipLaunchKernelGGL((adam_fin_kernel<true, WD>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
-                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
+    hipLaunchKernelGGL((adam_fin_kernel<true, WD, GC>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
+                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows}, gsq);
   else
-    hipLaunchKernelGGL((adam_fin_kernel<false, WD>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
-                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows});
+    hipLaunchKernelGGL((adam_fin_kernel<false, WD, GC>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t,
+                       sq_override, nspan, eps, clipnorm, f, MetRing{met, ring, ring_t, nmet, ring_rows}, gsq);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -791,7 +898,7 @@ extern "C" int32_t tnt_adam_fin_f32(float* theta, float* m, float* v, const floa
                                     int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met,
                                     int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, void* stream) {
   return adam_fin_launch<false>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met, nmet,
-                                ring, ring_rows, ring_t, nullptr, stream);
+                                ring, ring_rows, ring_t, nullptr, nullptr, stream);
 }
 
 // the decaying launch reads the learning rate through the descriptor's own `lr` (fin_fill refuses a null one)
@@ -802,5 +909,20 @@ extern "C" int32_t tnt_adamw_fin_f32(float* theta, float* m, float* v, const flo
                                      void* stream) {
   if (seg_wd == nullptr) return TNT_BADARG(14);
   return adam_fin_launch<true>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met, nmet,
-                               ring, ring_rows, ring_t, seg_wd, stream);
+                               ring, ring_rows, ring_t, seg_wd, nullptr, stream);
+}
+
+// clipnorm is the global threshold and gsq the word tnt_global_sqnorm_f32 (fin form) left; the side workgroup files the
+// per-variable norms as ever.  seg_wd (nullable) decays as tnt_adamw_fin_f32 does, at the descriptor's lr
+extern "C" int32_t tnt_adam_fin_gclip_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                          const int64_t* span_off, const int32_t* span_len, const float* sq_override,
+                                          int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin,
+                                          const float* met, int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t,
+                                          const float* gsq, const float* seg_wd, void* stream) {
+  if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (seg_wd != nullptr)
+    return adam_fin_launch<true, true>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met,
+                                       nmet, ring, ring_rows, ring_t, seg_wd, gsq, stream);
+  return adam_fin_launch<false, true>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met,
+                                      nmet, ring, ring_rows, ring_t, nullptr, gsq, stream);
 }

@@ -100,6 +100,10 @@ __device__ __forceinline__ void tnt_span_norm(const float* theta, const float* g
 // bit (-0.0 included), so a variable without decay is updated exactly as the plain instantiation updates it.
 __device__ __forceinline__ float tnt_decayed(float w, float dk) { return dk != 0.f ? w - dk * w : w; }
 
+// Global-norm clipping (the GC instantiations of the update kernels): what every *_gclip_f32 entry asks before it launches --
+// the word tnt_global_sqnorm_f32 wrote and a threshold that is a finite number > 0 (NaN fails c > 0).
+static inline bool tnt_gclip_ok(const float* gsq, float c) { return gsq != nullptr && c > 0.f && c <= 3.4028234e38f; }
+
 // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) for the step being applied, t = *adam_t + 1 (the counter is advanced at the END of the
 // update launch, by its last workgroup, when nobody reads it any more)
 __device__ __forceinline__ float tnt_adam_lr_t(const int64_t* adam_t, const float* lr, float b1, float b2) {

@@ -437,6 +437,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
         # compile(AdamW / weight_decay=): the data-parallel update launches (slices, the row-sharded encoder) do not decay
         raise NotImplementedError(model.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
                                                                     "row-sharded encoder update included)"))
+    if getattr(model.optimizer, "global_clipnorm", None) is not None:
+        # compile(global_clipnorm=): the pipelined schedules update in slices before all norms exist
+        raise NotImplementedError(model.GLOBAL_CLIP_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync)"))
     if model.loss_normalise == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)

@@ -1154,6 +1154,7 @@ class NIC(ModelBase):
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step_sam")
         self._weight_decay_refuse("train_step_sam")
+        self._global_clip_refuse("train_step_sam")
         if not self.teacher_forcing:
             raise NotImplementedError("train_step_sam is a teacher-forced step (lc_NIC.py:713-838): not built for "
                                       "teacher_forcing=False")

@@ -18,8 +18,8 @@ import torch
 
 from . import ops
 from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_focal_gamma, loss_label_smoothing, loss_normalise,
-                         loss_unlikelihood, optimizer_average, optimizer_schedule, check_weight_decay,
-                         weight_decay_table)
+                         loss_unlikelihood, optimizer_average, optimizer_schedule, check_global_clipnorm,
+                         check_weight_decay, weight_decay_table)
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -985,6 +985,9 @@ class ModelBase:
         self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
         self.seg_wd = None                  # decoupled weight decay (compile optimizer's weight_decay): one float per variable on the device, or None
         self.seg_wd_host = None             # the same table on the host (the encoder's fused update takes its entry as a scalar)
+        self.gsq = None                     # global-norm clipping: the one float the update launches read (squared norm of the last step)
+        self._gclip_host = None             # the optimizer's global_clipnorm as the recorded launches hold it (_sync_lr)
+        self._gsq_filed = False             # a step has written gsq (global_grad_norm)
         self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
         self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
         self.agc = None                     # adaptive gradient clipping (enable_agc): (clip_factor, eps), or None
@@ -1055,6 +1058,7 @@ class ModelBase:
         if avg is not None and self.grad_sync is not None:
             raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
         self._check_weight_decay(bool(check_weight_decay(getattr(optimizer, "weight_decay", None))))
+        self._check_global_clip(check_global_clipnorm(getattr(optimizer, "global_clipnorm", None)) is not None)
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
         # Fixed here, not read per step: the head launch sits inside captured graphs, with its smoothing, alpha, gamma and
@@ -1177,6 +1181,11 @@ class ModelBase:
         self.seg_wd = self.seg_wd_host = None
         self._store_seg_wd(tab)
         getattr(self.optimizer, "_optimizer", self.optimizer)._wd_built = True
+        # global-norm clipping: the word tnt_global_sqnorm_f32 writes and every update launch of the step reads
+        self.gsq = self._f(1)
+        self._gsq_filed = False
+        self._gclip_host = self._gclip()
+        self._check_global_clip(self._gclip_host is not None)
         self._graphs = {}
 
     # ------------------------------------------------------------------ decoupled weight decay (Adam / SGD weight_decay=, AdamW)
@@ -1236,6 +1245,53 @@ class ModelBase:
         self._wd_scalar_segs.add(seg)
         return float(self.seg_wd_host[seg])
 
+    # ------------------------------------------------------------------ global-norm clipping (Adam / SGD global_clipnorm=)
+    GLOBAL_CLIP_REFUSAL = ("global-norm clipping (global_clipnorm=) is built for the single-device update launches only: "
+                           "{what} does not apply it.  Train with clipnorm there, or on one device without it")
+
+    def _gclip(self):
+        """the optimizer's global_clipnorm: a float > 0, or None (off)"""
+        return None if self.optimizer is None else check_global_clipnorm(getattr(self.optimizer, "global_clipnorm", None))
+
+    def _check_global_clip(self, on):
+        """the refusals of a globally clipping optimizer (compile, the optimizer-state build, an assignment found by
+        _sync_lr): data parallel -- its pipelined schedules update in slices before all norms exist -- and adaptive
+        gradient clipping; train_step_sam and dp.attach refuse on their side"""
+        if not on:
+            return
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync)"))
+        if self.agc:
+            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
+
+    def _global_clip_refuse(self, what):
+        if self._gclip() is not None:
+            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what=what))
+
+    def _global_sqnorm(self, fin_kw=None):
+        """The reduction launch of a globally clipped step (tnt_global_sqnorm_f32): behind the step's norm launch(es), in
+        front of its first update launch and inside the same recorded plan / graph.  ``fin_kw``: the finalize keywords of an
+        update that carries the finalize work itself (the fin form, from the span partials); None behind a launch that
+        has filed ``sq`` (the table form).  Nothing without global_clipnorm."""
+        if self._gclip() is None:
+            return
+        a = self.arena
+        if fin_kw is None:
+            self.be.global_sqnorm(self.gsq, a.nseg, sq_override=a.sq_override, sq=a.sq)
+        else:
+            extra = {k: fin_kw[k] for k in ("extra_part", "n_extra", "extra_seg") if k in fin_kw}
+            self.be.global_sqnorm(self.gsq, a.nseg, sq_override=a.sq_override, partial=a.partial,
+                                  seg_first=a.spans.seg_first, **extra)
+        self._gsq_filed = True
+
+    def global_grad_norm(self):
+        """The global gradient norm of the last training step as a float: sqrt of the word its update launches clipped by
+        (every variable's gradient with its L2 term, the Embedding by its un-deduplicated rows -- tf.linalg.global_norm).
+        A host read.  The number to plot when choosing global_clipnorm; it exists for a model compiled with one."""
+        if self.gsq is None or not self._gsq_filed:
+            raise RuntimeError("global_grad_norm: no training step with global_clipnorm has run yet")
+        return float(self.gsq[0]) ** 0.5
+
     AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
                           "schedules update the arena in slices and the row-sharded encoder finishes its update behind "
                           "_update_fused, so one averaging launch behind the update has no single place there.  Train it on "
@@ -1247,6 +1303,13 @@ class ModelBase:
         if self._swapped:
             raise RuntimeError("the averaged weights are swapped in (swap_weights / averaged_weights): a training step would "
                                "train the average and average the raw weights.  Swap back first")
+        gclip = self._gclip()
+        if gclip != self._gclip_host:
+            # optimizer.global_clipnorm was assigned since the state was built: the threshold is an argument of the update
+            # launches, and switching it on or off changes which launches run -- the step is recorded again
+            self._check_global_clip(gclip is not None)
+            self._gclip_host = gclip
+            self._graphs = {}
         sched = optimizer_schedule(self.optimizer)
         if sched != self.lr_schedule:
             # optimizer.learning_rate was assigned since compile (a float in place of the schedule, or another schedule):
@@ -1298,7 +1361,9 @@ class ModelBase:
         self.adam_t.fill_(int(n))
 
     def _apply_optimizer(self):
-        """per-variable clipnorm + Adam/SGD (optimizer.apply_gradients, lc_NIC.py:389)."""
+        """per-variable clipnorm + Adam/SGD (optimizer.apply_gradients, lc_NIC.py:389).  Its callers have run _norms_and_l2:
+        under global_clipnorm the reduction launch reads the table that left."""
+        self._global_sqnorm()
         self._tick()
         if self.optimizer.kind == "adam":
             self._adam_update(self._spans())
@@ -1310,10 +1375,19 @@ class ModelBase:
     # ---- the update launches, one helper each.  Under decoupled weight decay (``seg_wd`` set) a helper issues the decaying
     # entry point in the plain one's place; its callers pass what differs between them -- the spans, the metrics ring, the
     # finalize descriptor -- and do not know that the decay exists.
+    # Under global-norm clipping (``_gclip()`` set) a helper issues the *_gclip entry instead, with the global threshold as its
+    # clipnorm, the model's ``gsq`` word and the decay, if any, as its trailing arguments (_gclip_kw).
     def _clip(self):
-        """the optimizer's clipnorm as the launches take it: 0 = no clipping"""
+        """the clip threshold as the launches take it: the optimizer's clipnorm (0 = no clipping), or its global_clipnorm"""
+        g = self._gclip()
+        if g is not None:
+            return g
         clip = self.optimizer.clipnorm
         return clip if clip is not None else 0.0
+
+    def _gclip_kw(self, **decay):
+        """the trailing arguments of a *_gclip launch: the global word, and ``decay`` where the model decays"""
+        return dict(gsq=self.gsq, **(decay if self.seg_wd is not None else {}))
 
     def _spans(self, s1=0):
         """(span_seg, span_off, span_len, nspan) of the arena's spans from span ``s1`` on, as the norm and update launches
@@ -1327,7 +1401,9 @@ class ModelBase:
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan, 0.0,
                 self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, self._clip())
-        if self.seg_wd is None:
+        if self._gclip() is not None:
+            be.adam_gclip(*args, **self._gclip_kw(lr=self.lr_dev, seg_wd=self.seg_wd), guard=self._guard_word(), **(ring or {}))
+        elif self.seg_wd is None:
             be.adam(*args, guard=self._guard_word(), **(ring or {}))
         else:
             be.adamw(*args, self.lr_dev, self.seg_wd, guard=self._guard_word(), **(ring or {}))
@@ -1338,7 +1414,9 @@ class ModelBase:
         be, a, opt = self.be, self.arena, self.optimizer
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.sq_override, nspan, opt.epsilon, self._clip(), desc)
-        if self.seg_wd is None:
+        if self._gclip() is not None:
+            be.adam_fin_gclip(*args, **self._gclip_kw(seg_wd=self.seg_wd), **ring)
+        elif self.seg_wd is None:
             be.adam_fin(*args, **ring)
         else:
             be.adamw_fin(*args, self.seg_wd, **ring)
@@ -1354,7 +1432,10 @@ class ModelBase:
         norm = (a.partial, sp.first_host[e.seg], sp.first_host[e.seg + 1]) if fin else (a.sq[one],)
         args = (enc.x, enc.dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, *norm, a.sq_override[one], self.lr_t_dev,
                 opt.beta_1, opt.beta_2, opt.epsilon, self._clip(), enc.N, enc.E, enc.rows, enc.ldx)
-        if self.seg_wd is None:
+        if self._gclip() is not None:
+            kw = self._gclip_kw(lr=self.lr_dev, wd=self._wd_scalar(e.seg) if self.seg_wd is not None else 0.0)
+            (be.dense_dw_adam_fin_gclip if fin else be.dense_dw_adam_gclip)(*args, **kw, guard=self._guard_word())
+        elif self.seg_wd is None:
             (be.dense_dw_adam_fin if fin else be.dense_dw_adam)(*args, guard=self._guard_word())
         else:
             (be.dense_dw_adamw_fin if fin else be.dense_dw_adamw)(*args, self.lr_dev, self._wd_scalar(e.seg),
@@ -1365,7 +1446,10 @@ class ModelBase:
         be, a, opt = self.be, self.arena, self.optimizer
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan)
-        if self.seg_wd is None:
+        if self._gclip() is not None:
+            be.sgd_gclip(*args, 0.0, self.lr_dev, opt.momentum, self._clip(), **self._gclip_kw(seg_wd=self.seg_wd),
+                         guard=self._guard_word())
+        elif self.seg_wd is None:
             be.sgd(*args, 0.0, self.lr_dev, opt.momentum, self._clip(), guard=self._guard_word())
         else:
             be.sgdw(*args, self.lr_dev, opt.momentum, self._clip(), self.seg_wd, guard=self._guard_word())
@@ -1454,10 +1538,11 @@ class ModelBase:
         be, a, sp = self.be, self.arena, self.arena.spans
         spans = self._spans(s1)
         if fin:
-            if enc is not None:        # the encoder kernel first: it reads the step counter's lr_t like the Adam launch, which ticks
-                self._enc_adam_update(enc, fin=True)
             if "extra_part" in kw:
                 kw["extra_seg"] = self.emb_seg
+            self._global_sqnorm(kw)    # global_clipnorm: the one word both update launches clip by, from the span partials
+            if enc is not None:        # the encoder kernel first: it reads the step counter's lr_t like the Adam launch, which ticks
+                self._enc_adam_update(enc, fin=True)
             if self._fin_arrive is None:
                 self._fin_arrive = torch.zeros(16, dtype=torch.int32, device=self.device)
             # one descriptor per distinct argument set, alive as long as the model (recorded launch plans re-issue the call)
@@ -1471,6 +1556,7 @@ class ModelBase:
             self._average_update()
             return
         be.step_finalize(a.partial, sp.seg_first, a.seg_l2, a.sq, a.wsq, l2_out, a.nseg, **kw)
+        self._global_sqnorm()
         if self.optimizer.kind == "adam":
             self._adam_update(spans, self._ring_args() if spans[3] > 0 else None)
             if enc is not None:
@@ -1796,6 +1882,8 @@ class ModelBase:
         if clip_factor is not None and (self.seg_wd is not None or
                                         check_weight_decay(getattr(self.optimizer, "weight_decay", None))):
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
+        if clip_factor is not None:
+            self._global_clip_refuse("a step with adaptive gradient clipping (enable_agc)")
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
         self._graphs = {}
 

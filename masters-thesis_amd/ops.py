@@ -649,6 +649,47 @@ class HipBackend:
         self._call(self.lib.tnt_sgdw_f32, "tnt_sgdw_f32", _p(theta), _p(mom), _p(grad), _p(span_seg), _p(span_off), _p(span_len),
                    _p(seg_l2), _p(sq), _p(sq_override), nspan, _p(lr_dev), momentum, clipnorm, _p(guard), _p(seg_wd), self._s())
 
+    # ---- global-norm clipping (definition: tnt_global_sqnorm_f32 in include/tnt_hip.h).  Each *_gclip method takes its plain
+    # sibling's arguments with ``clipnorm`` the global threshold, then ``gsq`` and the optional decay
+    def global_sqnorm(self, gsq, nseg, sq_override=None, partial=None, seg_first=None, extra_part=None, n_extra=0, extra_seg=-1,
+                      sq=None):
+        """gsq[0] = the squared global gradient norm: the fin form from the span partials (``partial``, ``seg_first`` and the
+        Embedding's ``extra_part``), or the table form from ``sq``"""
+        self._call(self.lib.tnt_global_sqnorm_f32, "tnt_global_sqnorm_f32", _p(partial), _p(seg_first), _p(sq), _p(sq_override),
+                   _p(extra_part), n_extra, extra_seg, nseg, _p(gsq), self._s())
+
+    def adam_gclip(self, theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev,
+                   beta1, beta2, eps, clipnorm, gsq, lr=None, seg_wd=None, guard=None, met=None, ring=None, ring_t=None):
+        self._call(self.lib.tnt_adam_gclip_f32, "tnt_adam_gclip_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(seg_l2), _p(sq), _p(sq_override), nspan, lr_t, _p(lr_t_dev), beta1, beta2, eps, clipnorm,
+                   _p(guard), _p(met), met.numel() if met is not None else 0, _p(ring), ring.shape[0] if ring is not None else 0,
+                   _p(ring_t), _p(gsq), _p(lr), _p(seg_wd), self._s())
+
+    def adam_fin_gclip(self, theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, gsq,
+                       seg_wd=None, met=None, ring=None, ring_t=None):
+        self._call(self.lib.tnt_adam_fin_gclip_f32, "tnt_adam_fin_gclip_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg),
+                   _p(span_off), _p(span_len), _p(sq_override), nspan, eps, clipnorm, _ct.addressof(fin), _p(met),
+                   met.numel() if met is not None else 0, _p(ring), ring.shape[0] if ring is not None else 0, _p(ring_t), _p(gsq),
+                   _p(seg_wd), self._s())
+
+    def sgd_gclip(self, theta, mom, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr, lr_dev, momentum,
+                  clipnorm, gsq, seg_wd=None, guard=None):
+        self._call(self.lib.tnt_sgd_gclip_f32, "tnt_sgd_gclip_f32", _p(theta), _p(mom), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(seg_l2), _p(sq), _p(sq_override), nspan, lr, _p(lr_dev), momentum, clipnorm, _p(guard), _p(gsq),
+                   _p(seg_wd), self._s())
+
+    def dense_dw_adam_gclip(self, x, dpre, theta, m, v, l2, sq, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, N, E, Bk, ldx,
+                            gsq, lr=None, wd=0.0, guard=None):
+        self._call(self.lib.tnt_dense_dw_adam_gclip_f32, "tnt_dense_dw_adam_gclip_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
+                   _p(sq), _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, _p(gsq), _p(lr), wd,
+                   self._s())
+
+    def dense_dw_adam_fin_gclip(self, x, dpre, theta, m, v, l2, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps,
+                                clipnorm, N, E, Bk, ldx, gsq, lr=None, wd=0.0, guard=None):
+        self._call(self.lib.tnt_dense_dw_adam_fin_gclip_f32, "tnt_dense_dw_adam_fin_gclip_f32", _p(x), _p(dpre), _p(theta), _p(m),
+                   _p(v), l2, _p(partial), k0, k1, _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk,
+                   ldx, _p(gsq), _p(lr), wd, self._s())
+
     def sam(self, theta, grad, ew, span_seg, span_off, span_len, seg_l2, sq, nseg, nspan, rho, mode, sq_override=None):
         self._call(self.lib.tnt_sam_f32, "tnt_sam_f32", _p(theta), _p(grad), _p(ew), _p(span_seg), _p(span_off), _p(span_len),
                                         _p(seg_l2), _p(sq), _p(sq_override), nseg, nspan, rho, mode, self._s())

@@ -90,19 +90,66 @@ def weight_decay_table(optimizer, names):
     return tab if any(tab) else None
 
 
-class Adam(_LearningRate, _WeightDecay):
+def check_global_clipnorm(c):
+    """None, or the value as a float; ValueError unless it is a finite number > 0 (bool, str and NaN refused)"""
+    import numbers
+    if c is None:
+        return None
+    if isinstance(c, bool) or not isinstance(c, numbers.Real):
+        raise ValueError(f"global_clipnorm must be None or a finite number > 0, got {c!r}")
+    v = float(c)
+    if not 0.0 < v < float("inf"):
+        raise ValueError(f"global_clipnorm must be finite and > 0, got {c!r}")
+    return v
+
+
+CLIPVALUE_REFUSAL = ("clipvalue is not implemented: keras clips an IndexedSlices gradient row by row before the rows are summed, "
+                     "which the Embedding scatter here does not do.  Use clipnorm or global_clipnorm")
+
+
+class _GlobalClipnorm:
+    """``global_clipnorm`` of a descriptor (keras: the argument of every optimizer; tf.clip_by_global_norm): ONE norm over
+    the gradients of all variables, every gradient scaled by c / max(norm, c), which keeps the direction of the whole
+    update (definition: tnt_global_sqnorm_f32 in include/tnt_hip.h).  None: off.  Not together with ``clipnorm`` (keras's
+    rule); ``clipvalue`` is refused.  ``model.global_grad_norm()`` reads the last step's norm.
+
+    Single device only: dp.attach / a model with a grad_sync, train_step_sam and enable_agc() refuse it with
+    NotImplementedError."""
+
+    @property
+    def global_clipnorm(self):
+        return self._global_clipnorm
+
+    @global_clipnorm.setter
+    def global_clipnorm(self, v):
+        v = check_global_clipnorm(v)
+        if v is not None and getattr(self, "clipnorm", None) is not None:
+            raise ValueError("clipnorm and global_clipnorm cannot both be set: at most one of them, as in keras")
+        self._global_clipnorm = v
+
+    def _init_clipping(self, clipnorm, global_clipnorm, kw):
+        if kw.pop("clipvalue", None) is not None:
+            raise NotImplementedError(CLIPVALUE_REFUSAL)
+        self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self.global_clipnorm = global_clipnorm
+
+
+class Adam(_LearningRate, _WeightDecay, _GlobalClipnorm):
     """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay) -- main.py:97.
     ``learning_rate``: a float or an ``optimizers.schedules`` object.
     ``clipnorm`` is per variable; None disables it (the TF<=2.3 behaviour of a
     custom tape.gradient -> apply_gradients step).
-    ``weight_decay``: decoupled weight decay, see ``_WeightDecay``; None or 0 is plain Adam."""
+    ``weight_decay``: decoupled weight decay, see ``_WeightDecay``; None or 0 is plain Adam.
+    ``global_clipnorm``: one norm over all gradients in ``clipnorm``'s place, see ``_GlobalClipnorm``; ``clipvalue`` is
+    refused."""
 
     kind = "adam"
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, weight_decay=None, **kw):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, weight_decay=None,
+                 global_clipnorm=None, **kw):
         self.lr = kw.pop("lr", learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
-        self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self._init_clipping(clipnorm, global_clipnorm, kw)
         self.weight_decay = weight_decay
         self.iterations = 0
 
@@ -112,25 +159,27 @@ class AdamW(Adam):
     clipnorm): Adam with decoupled weight decay (Loshchilov & Hutter 2019), the rule of torch.optim.AdamW.  Every
     variable is decayed unless ``exclude_from_weight_decay`` names it (see ``_WeightDecay``)."""
 
-    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, **kw):
+    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None,
+                 global_clipnorm=None, **kw):
         if weight_decay is None:
             raise ValueError("AdamW needs a weight_decay; Adam is the optimizer without one")
-        super().__init__(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay, **kw)
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay, global_clipnorm, **kw)
 
 
-class SGD(_LearningRate, _WeightDecay):
+class SGD(_LearningRate, _WeightDecay, _GlobalClipnorm):
     """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False, weight_decay) -- main.py:100-102.
     ``learning_rate``: a float or an ``optimizers.schedules`` object.  ``weight_decay``: decoupled weight decay, see
-    ``_WeightDecay``; None or 0 is plain SGD."""
+    ``_WeightDecay``; None or 0 is plain SGD.  ``global_clipnorm``: see ``_GlobalClipnorm``."""
 
     kind = "sgd"
 
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, weight_decay=None, **kw):
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, weight_decay=None,
+                 global_clipnorm=None, **kw):
         if nesterov:
             raise NotImplementedError("nesterov momentum is not used by the reference path")
         self.lr = kw.pop("lr", learning_rate)
         self.momentum = float(momentum)
-        self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self._init_clipping(clipnorm, global_clipnorm, kw)
         self.weight_decay = weight_decay
         self.iterations = 0
 
@@ -194,6 +243,7 @@ class _AveragedOptimizer:
     momentum = _delegate("momentum")
     iterations = _delegate("iterations")
     weight_decay = _delegate("weight_decay")
+    global_clipnorm = _delegate("global_clipnorm")
 
     def exclude_from_weight_decay(self, var_list=None, var_names=None):
         self._optimizer.exclude_from_weight_decay(var_list=var_list, var_names=var_names)
