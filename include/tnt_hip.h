@@ -1043,6 +1043,29 @@ int32_t tnt_stage_batch_h16(const uint16_t* x_half, float* x_dst, const int32_t*
                             const int32_t* tgt, int32_t* tgt_tmajor, const float* a0, float* h0,
                             const float* c0, float* c0_dst, int32_t B, int32_t T, int32_t N, int32_t ldx,
                             int32_t U, float* xT_dst, int32_t ldt, void* stream);
+/* Training-time corruption of a staged batch, in place and in one launch of its own behind whichever staging entry ran:
+ * scan dropout (the condition dropout of classifier-free guidance) and word dropout (Bowman et al. 2016).
+ * step = *step_dev, read on the device when the launch runs.  u(e, site) is the 24-bit uniform of logical element e of the
+ * Philox stream (seed, site, step) -- csrc/tnt_rng.h, oracle.philox.uniform24 --, and an element FIRES when u < rate, the
+ * negation of the Dropout kernels' keep decision.
+ *   scan part (scan_rate > 0): row b fires on element e = b of site_scan.  A fired row gets
+ *     x[b * ldx + c] = null_scan ? null_scan[c] : 0.0f for c < N, and, when xT is given (the voxel-major copy [N][ldt]),
+ *     xT[c * ldt + b] the same value.  Nothing else is written: not the rows that did not fire, not the columns [N, ldx)
+ *     of x, not the columns >= B of xT.
+ *   word part (word_rate > 0): position (b, t) with 1 <= t < T and cap[b * T + t] != 0 fires on element e = b * T + t of
+ *     site_word; a fired position gets cap[b * T + t] = unk_id.  Column 0 (the start token) and id 0 (padding, the mask
+ *     id) are never changed; nothing else is written.
+ * rate == 1 fires wherever it may; rate == 0 switches the part off, and its pointers (x, xT, null_scan / cap) may then be
+ * null.  Both rates 0: success without a launch.  TNT_BADARG, with nothing launched: a rate outside [0, 1] or NaN;
+ * word_rate > 0 with unk_id outside [1, V); B, T or N < 0; ldx < N; xT with ldt < B; a null step_dev; a null x or cap
+ * for a part that is switched on.
+ * A row is cut into pieces of 1024 columns, one workgroup each; a workgroup makes one Philox call for its row (none per
+ * element) and returns at once when the row did not fire: the traffic is that of the fired rows.  float4 stores where N % 4 == ldx % 4 == 0 and x and null_scan are 16-byte aligned, scalar stores
+ * otherwise (no refusal).  Deterministic: every address is stored by one thread; no atomics, LDS or scratch. */
+int32_t tnt_input_corrupt_f32(float* x, int32_t ldx, float* xT, int32_t ldt, int32_t* cap, int32_t B, int32_t T,
+                              int32_t N, int32_t V, float scan_rate, const float* null_scan, float word_rate,
+                              int32_t unk_id, uint64_t seed, uint32_t site_scan, uint32_t site_word,
+                              const uint32_t* step_dev, void* stream);
 
 /* ---- optimizer: per-variable clipnorm + Adam / SGD over a flat parameter arena --
  * (main.py:97,100-102; lc_NIC.py:389).  The arena is cut by the host into

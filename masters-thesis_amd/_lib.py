@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 125
+TNT_VERSION = 126
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -132,6 +132,7 @@ SIGNATURES = {
     "tnt_stage_batch_map_f32": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P, P, P, P, P, P, P],
     "tnt_stage_batch_h16": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P],
     "tnt_stage_batch_masks_f32": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, P, I64, I32, F32, U64, U32, P, P],
+    "tnt_input_corrupt_f32": [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, F32, I32, U64, U32, U32, P, P],
     "tnt_scst_cce_f32": [P, I32, I32, P, I32, P, P, I32, P, P, P, I32, F32, P],
     "tnt_caption_score_f32": [P, I32, I32, P, I32, I32, I32, I32, P, P, P, P],
     "tnt_sample_rows_f32": [P, P, I32, I32, I32, F32, I32, U64, U32, U32, P, P],

@@ -4,7 +4,7 @@ the way main.py:113-134 does."""
 import yaml
 
 from . import schedules
-from .model_base import AttentionCoverage
+from .model_base import AttentionCoverage, ScanDropout, WordDropout
 from .optimizers import Adam, AdamW, SGD, CategoricalCrossentropy
 
 
@@ -45,6 +45,22 @@ def build_optimizer(config):
     return opt
 
 
+def _corruption_keys(config, kw):
+    """scan_dropout: a rate or {rate: } and word_dropout: {rate: , unk_id: }: optional keys of this library's
+    (model_base.ScanDropout / WordDropout) -> the constructor keywords, unless the caller passed them"""
+    sd, wd = config.get("scan_dropout"), config.get("word_dropout")
+    if sd is not None and "scan_dropout" not in kw:
+        if isinstance(sd, dict):
+            if set(sd) != {"rate"}:
+                raise ValueError(f"scan_dropout must be a rate or a mapping with rate, got {sd!r}")
+            sd = sd["rate"]
+        kw["scan_dropout"] = ScanDropout(sd)
+    if wd is not None and "word_dropout" not in kw:
+        if not isinstance(wd, dict) or set(wd) != {"rate", "unk_id"}:
+            raise ValueError(f"word_dropout must be a mapping with rate and unk_id, got {wd!r}")
+        kw["word_dropout"] = WordDropout(wd["rate"], wd["unk_id"])
+
+
 def build_model(config, groups, mode="attention", input_size=None, **kw):
     """lc_NIC.NIC(...) exactly as main.py:113-132 builds it, compiled as at main.py:134.
     mode="fc" builds the fully-connected variant instead (the call_fc / greedy_predict_fc dispatch the
@@ -58,6 +74,7 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
                       config["output_reg"], seed=config.get("seed", 42), **kw)
     elif mode == "attention":
         from .lc_nic import NIC
+        _corruption_keys(config, kw)
         # attention_coverage: {weight: , axis: }: an optional key of this library's (model_base.AttentionCoverage)
         cov = config.get("attention_coverage")
         if cov is not None and "attention_coverage" not in kw:

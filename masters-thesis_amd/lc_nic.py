@@ -73,11 +73,13 @@ class NIC(ModelBase):
     branch_streams = False      # True (with use_side_streams): text and front branch of the backward in parallel; tools/probe/branch_ab.py
     split_encoder = True        # False: one workgroup per region instead of 64-voxel pieces; tools/probe/ld_split_ab.py
     voxel_major = True          # False: the split encoder reads the batch-major betas; a tool sets it by name (tools/ab_bench_att.py voxel_major=0)
+    SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
-                 teacher_forcing=True, scheduled_sampling=None, attention_coverage=None, **kw):
+                 teacher_forcing=True, scheduled_sampling=None, attention_coverage=None, scan_dropout=None,
+                 word_dropout=None, **kw):
         super().__init__(**kw)
         # ---- what exists only once a step or a decode has asked for it
         self.lc_xch = None              # exchange space of the persistent backward chain (_build)
@@ -244,6 +246,12 @@ class NIC(ModelBase):
         if not self.teacher_forcing:
             self._naive_check()
         self._coverage_check()
+        # scan_dropout (model_base.ScanDropout) / word_dropout (model_base.WordDropout): train_step and train_step_sam corrupt
+        # the staged batch (tnt_input_corrupt_f32, one launch behind the staging); None or rate 0 issues nothing
+        self.scan_dropout, self.word_dropout = scan_dropout, word_dropout
+
+    def _input_width(self):
+        return self.n_in
 
     # ------------------------------------------------------------------ weights
     def _init_weights(self, rng):
@@ -1128,7 +1136,8 @@ class NIC(ModelBase):
             raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
         self._ss_refuse()
         self._coverage_check()                      # (grad_sync may have been attached since the constructor)
-        B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
+        self._corrupt_check()
+        B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)
         self._ss_refuse(T)
         self._sync_lr()
         ring = False
@@ -1165,7 +1174,8 @@ class NIC(ModelBase):
         if self.attention_coverage is not None:
             raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
                                       "gradient of its first pass): not built for attention_coverage")
-        B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True)
+        self._corrupt_check()
+        B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)      # both passes read this batch
         self._sync_lr()
         be, a = self.be, self.arena
         if self.ew is None:

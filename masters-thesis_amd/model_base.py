@@ -30,6 +30,9 @@ S_SAMPLE = 112          # + decode position: categorical-sampling stream of samp
 S_SS_COIN, S_SS_DRAW = 176, 208
 SS_MAX_POSITIONS = 32
 S_SCST_LAST = 240       # self-critical rollouts: the draw of the last token position (nic.NIC(self_critical=...))
+# the training-time input corruption of nic.NIC / lc_nic.NIC (tnt_input_corrupt_f32): element b decides scan row b,
+# element b * T + t the fed caption token (b, t)
+S_SCAN_DROP, S_WORD_DROP = 241, 242
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
@@ -442,7 +445,8 @@ class Guidance:
     log p = lc + scale * (lc - ln) renormalised, so that words the scan makes more likely than the language prior does
     are promoted; the common word is fed back to the scan's row and to the null row.
       scale         finite, >= 0; 0 leaves the conditional distribution
-      null          the null scan: None, the all-zero scan (the mean of z-scored betas); an array (N,), one null scan
+      null          the null scan: None, the model's null_scan (the null of its ScanDropout, which it was trained on) or,
+                    without one, the all-zero scan (the mean of z-scored betas); an array (N,), one null scan
                     shared by every image; an array (M, N), one per image of the decoded batch
       plausibility  in [0, 1) (0: off): tokens whose conditional probability is below plausibility times the conditional
                     maximum are banned (Li et al. 2022), which keeps a large scale from promoting implausible words
@@ -484,6 +488,76 @@ class Guidance:
     def __repr__(self):
         null = "None" if self.null is None else f"<array {self.null.shape}>"
         return f"Guidance(scale={self.scale}, null={null}, plausibility={self.plausibility})"
+
+
+def _check_rate(what, rate):
+    """a dropout probability of the input corruption: a finite number in [0, 1] (bool and str refused) -> float"""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not np.isfinite(rate):
+        raise ValueError(f"{what} rate must be a finite number in [0, 1], got {rate!r}")
+    if not 0 <= rate <= 1:
+        raise ValueError(f"{what} rate must be in [0, 1] (0: off), got {rate!r}")
+    return float(rate)
+
+
+class ScanDropout:
+    """Scan dropout, the condition dropout of classifier-free guidance (Ho & Salimans 2022), for the ``scan_dropout=``
+    keyword of nic.NIC and lc_nic.NIC: in train_step, with probability ``rate`` per sample, the whole scan row of the staged
+    batch is replaced by the null scan (tnt_input_corrupt_f32, include/tnt_hip.h), so the model learns p(caption | null)
+    beside p(caption | scan) and ``guidance=Guidance(scale, null=None)`` contrasts against a distribution it was trained on.
+      rate   a finite number in [0, 1]; 0 is the model without the option
+      null   the null scan: None, the all-zero scan; an array (N,) of finite numbers, checked against the model's input
+             width by the model.  ``model.null_scan`` returns it, and a guided decode with null=None takes it from there
+    Row b of step s fires when the 24-bit uniform of element b of the Philox stream (seed, S_SCAN_DROP, s) is below the
+    rate.  Bad values raise ValueError here, before any launch.  test_step, __call__, the decodes and score_captions never
+    corrupt their input."""
+
+    def __init__(self, rate, null=None):
+        self.rate = _check_rate("scan dropout", rate)
+        if null is not None:
+            try:
+                v = null.detach().cpu().numpy() if isinstance(null, torch.Tensor) else np.asarray(null)
+                v = np.array(v, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"null must be None or an array (N,) of numbers, got {null!r}") from None
+            if v.ndim != 1 or v.size == 0 or not np.all(np.isfinite(v)):
+                raise ValueError(f"null must be None or a finite, non-empty array (N,), got shape {v.shape}")
+            null = v
+        self.null = null
+
+    @property
+    def neutral(self):
+        """the rate is 0 in float32: the step runs as without the option"""
+        return np.float32(self.rate) == 0
+
+    def __repr__(self):
+        null = "None" if self.null is None else f"<array {self.null.shape}>"
+        return f"ScanDropout(rate={self.rate!r}, null={null})"
+
+
+class WordDropout:
+    """Word dropout (Bowman et al. 2016, "Generating sentences from a continuous space"), for the ``word_dropout=`` keyword
+    of nic.NIC and lc_nic.NIC: in train_step, with probability ``rate`` per fed caption token, the token is replaced by the
+    unknown-word id ``unk_id`` (tnt_input_corrupt_f32, include/tnt_hip.h); the targets stay, so the decoder cannot lean on
+    the previous words alone and has to read the scan.  Column 0 (the start token) and id 0 (padding, the mask id) are never
+    replaced.
+      rate    a finite number in [0, 1]; 0 is the model without the option
+      unk_id  an int >= 1; the model checks it against its vocabulary size
+    Position (b, t) of step s fires when the 24-bit uniform of element b * T + t of the Philox stream (seed, S_WORD_DROP, s)
+    is below the rate.  Bad values raise ValueError here, before any launch."""
+
+    def __init__(self, rate, unk_id):
+        self.rate = _check_rate("word dropout", rate)
+        if isinstance(unk_id, bool) or not isinstance(unk_id, (int, np.integer)) or unk_id < 1:
+            raise ValueError(f"unk_id must be an int >= 1 (0 is the padding id), got {unk_id!r}")
+        self.unk_id = int(unk_id)
+
+    @property
+    def neutral(self):
+        """the rate is 0 in float32: the step runs as without the option"""
+        return np.float32(self.rate) == 0
+
+    def __repr__(self):
+        return f"WordDropout(rate={self.rate!r}, unk_id={self.unk_id})"
 
 
 class _GuidanceDecode(_ConsensusDecode):
@@ -1010,6 +1084,8 @@ class ModelBase:
         self.scheduled_sampling = None      # nic.NIC / lc_nic.NIC(scheduled_sampling=...)
         self.self_critical = None           # nic.NIC(self_critical=...)
         self.attention_coverage = None      # lc_nic.NIC(attention_coverage=...)
+        self._scan_dropout = self._word_dropout = None      # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...)
+        self._null_dev = None               # the ScanDropout's null scan on the device (None: the all-zero scan)
         self.met = None                     # the metrics buffer (_build)
         # ---- state that exists only once something has asked for it
         self.opt_m = self.opt_avg = None    # the optimizer's first slot and the weight average (_init_optimizer_state)
@@ -2083,6 +2159,95 @@ class ModelBase:
             print_fn(f"  {layer:36s} {n:>12,d}")
         print_fn(f"Total params: {self.count_params():,d}")
 
+    # ------------------------------------------------------------------ input corruption (scan_dropout=, word_dropout=)
+    SUPPORTS_INPUT_CORRUPTION = False   # True on nic.NIC and lc_nic.NIC, whose train_step stages with corrupt=True
+    CORRUPT_DP_REFUSAL = ("scan_dropout / word_dropout are built for the single-device step only: the ranks of a data-parallel "
+                          "step (dp.attach / grad_sync) would draw the same coins for their slices.  Train them on one device")
+
+    def _input_width(self):
+        """the voxel columns of a staged scan row (lc_nic.NIC: n_in)"""
+        return self.N
+
+    @property
+    def scan_dropout(self):
+        """the model's model_base.ScanDropout, or None; assignable (validated), and a new rate needs no re-recording: the
+        launch sits with the staging, outside the recorded step"""
+        return self._scan_dropout
+
+    @scan_dropout.setter
+    def scan_dropout(self, sd):
+        if sd is not None and not isinstance(sd, ScanDropout):
+            raise ValueError(f"scan_dropout must be None or a model_base.ScanDropout, got {sd!r}")
+        if sd is not None and not self.SUPPORTS_INPUT_CORRUPTION:
+            raise NotImplementedError(f"{type(self).__name__} has no scan_dropout: it is built for nic.NIC and lc_nic.NIC")
+        if sd is not None and sd.null is not None and sd.null.shape[0] != self._input_width():
+            raise ValueError(f"the null scan of scan_dropout must have the model's input width {self._input_width()}, "
+                             f"got {sd.null.shape[0]}")
+        self._corrupt_check(sd, self._word_dropout)
+        self._scan_dropout = sd
+        self._null_dev = None if sd is None or sd.null is None else torch.from_numpy(sd.null.copy()).to(self.device)
+
+    @property
+    def word_dropout(self):
+        """the model's model_base.WordDropout, or None; assignable (validated), without re-recording"""
+        return self._word_dropout
+
+    @word_dropout.setter
+    def word_dropout(self, wd):
+        if wd is not None and not isinstance(wd, WordDropout):
+            raise ValueError(f"word_dropout must be None or a model_base.WordDropout, got {wd!r}")
+        if wd is not None and not self.SUPPORTS_INPUT_CORRUPTION:
+            raise NotImplementedError(f"{type(self).__name__} has no word_dropout: it is built for nic.NIC and lc_nic.NIC")
+        if wd is not None and wd.unk_id >= self.V:
+            raise ValueError(f"word dropout unk_id {wd.unk_id} is not below vocab_size {self.V}")
+        self._corrupt_check(self._scan_dropout, wd)
+        self._word_dropout = wd
+
+    @property
+    def null_scan(self):
+        """the (N,) float32 null scan of the model's ScanDropout (whatever its rate: no decode corrupts its input), or None;
+        ``guidance=Guidance(scale, null=None)`` decodes against it"""
+        sd = self._scan_dropout
+        return None if sd is None or sd.null is None else sd.null
+
+    def _corruption(self, sd=False, wd=False):
+        """(ScanDropout or None, WordDropout or None) with a neutral one as None, or None when neither is active: then the
+        step issues the launches it issues without the keywords"""
+        sd = self._scan_dropout if sd is False else sd
+        wd = self._word_dropout if wd is False else wd
+        sd = None if sd is None or sd.neutral else sd
+        wd = None if wd is None or wd.neutral else wd
+        return (sd, wd) if (sd is not None or wd is not None) else None
+
+    def _corrupt_check(self, sd=False, wd=False):
+        """the combinations the input corruption is built for (the constructor, an assignment, train_step -- grad_sync may
+        have been attached since); anything else refuses instead of training another mode.  Neutral settings pass"""
+        if self._corruption(sd, wd) is None:
+            return
+        what = "scan_dropout / word_dropout"
+        if self.scheduled_sampling is not None:
+            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for scheduled_sampling")
+        if self.self_critical is not None:
+            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for self_critical")
+        if not self.teacher_forcing:
+            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for teacher_forcing=False "
+                                      "(the free-running decoder)")
+        if int(self.S) != 1:
+            raise NotImplementedError(f"{what} are single-subject options: n_subjects > 1 is not supported")
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise NotImplementedError(self.CORRUPT_DP_REFUSAL)
+
+    def _input_corrupt(self, cor, B, T, n_cols):
+        """tnt_input_corrupt_f32 on the staged x (and its voxel-major copy) and cap, at this step's drop_step: one launch
+        directly behind the staging, outside the recorded step"""
+        sd, wd = cor
+        xT = self.xT if sd is not None else None
+        self.be.input_corrupt(self.x if sd is not None else None, self.ldx, xT, xT.shape[1] if xT is not None else 0,
+                              self.cap if wd is not None else None, B, T, n_cols, self.V,
+                              sd.rate if sd is not None else 0.0, self._null_dev if sd is not None else None,
+                              wd.rate if wd is not None else 0.0, wd.unk_id if wd is not None else 0,
+                              self.seed, S_SCAN_DROP, S_WORD_DROP, self.drop_step)
+
     # ------------------------------------------------------------------ input staging
     def _to_dev(self, a, dtype):
         if isinstance(a, torch.Tensor):
@@ -2104,11 +2269,14 @@ class ModelBase:
         product of the staged batch and wants it in the staging launch (nic.NIC: stage_fwd), else None"""
         return None
 
-    def _stage_batch(self, inputs, target, n_cols, masks=False, head_map=False, fwd=False):
+    def _stage_batch(self, inputs, target, n_cols, masks=False, head_map=False, fwd=False, corrupt=False):
         """(inputs, target) -> static buffers.  A batch that already sits on the model's device in the staged
         dtypes (float32 -- or float16 "on-wire" -- betas, float32 states, int32 ids, contiguous) goes through ONE launch
         (tnt_stage_batch_f32 / _h16);
-        anything else (numpy, one-hot targets, other dtypes) takes the general per-tensor path."""
+        anything else (numpy, one-hot targets, other dtypes) takes the general per-tensor path.
+        ``corrupt`` (the training steps): behind whichever route ran, the model's scan / word dropout as one launch on the
+        staged buffers (_input_corrupt); a model without them, or with neutral ones, issues nothing."""
+        cor = self._corruption() if corrupt else None
         x, cap, a0, c0 = inputs[:4]
         if target is not None and self.unlikelihood > 0 and np.shape(cap)[-1] > self.UNLIKELIHOOD_MAX_T:
             # a step with a loss: refused here, in front of every launch (and so outside any capture)
@@ -2132,6 +2300,8 @@ class ModelBase:
             if mk is not None:
                 self.be.dropout_mask4(mk[0], mk[1], mk[2], mk[3], mk[4], mk[5], 0, mk[6])
             route.masks_staged = mk is not None
+            if cor is not None:
+                self._input_corrupt(cor, B, T, n_cols)
             return B, T
         B, T = cap.shape
         self._build(B, T)
@@ -2144,7 +2314,10 @@ class ModelBase:
         route.masks_staged = mk is not None
         hm = self._head_map_bufs(B, T) if (head_map and target is not None and mk is None and xT is None
                                            and x.dtype == torch.float32) else None
-        sf = self._stage_fwd_args(B) if (fwd and hm is not None and n_cols == self.ldx) else None
+        # scan dropout declines the stage_fwd ride: the encoder forward inside that launch reads the caller's x in place,
+        # not the staged rows the corruption writes (word dropout keeps it: the row map merges on id 0 only)
+        sf = self._stage_fwd_args(B) if (fwd and hm is not None and n_cols == self.ldx
+                                         and (cor is None or cor[0] is None)) else None
         if sf is not None and self.be.dense_fwd_stream_gram_stage(x, *sf[:4], B, sf[4], n_cols, sf[5], sf[6], self.x, self.ldx,
                                                                   cap, self.cap, target, self.tgt, a0, self.Hs[0], c0,
                                                                   self.Cs[0], T, self.U, *hm):
@@ -2163,6 +2336,8 @@ class ModelBase:
         else:
             self.be.stage_batch(x, self.x, cap, self.cap, target, self.tgt, a0, self.Hs[0], c0, self.Cs[0], B, T, n_cols,
                                 self.ldx, self.U, **kw)
+        if cor is not None:
+            self._input_corrupt(cor, B, T, n_cols)
         return B, T
 
     def _stage_target(self, target, B, T):
@@ -2396,7 +2571,9 @@ class ModelBase:
         if len(shape) != 2 or shape[0] != n_start:
             raise ValueError(f"guided decoding takes one scan per caption: img_input must be ({n_start}, N) for the "
                              f"{n_start} entries of start_seq, got {shape}")
-        null = np.zeros(shape[1], np.float32) if g.null is None else g.null
+        null = g.null if g.null is not None else self.null_scan        # (a ScanDropout model: the null it was trained on)
+        if null is None:
+            null = np.zeros(shape[1], np.float32)
         if null.shape != shape[1:] and null.shape != shape:
             raise ValueError(f"the null scan must have shape {shape[1:]} or {shape} for this batch, got {null.shape}")
         null = np.ascontiguousarray(np.broadcast_to(null, shape))

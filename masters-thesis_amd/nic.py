@@ -38,10 +38,11 @@ class NIC(ModelBase):
     fused_head_grads = False    # True: the head's dW + bias gradient on gemm_fused (with g3_riders = False); tools/ab_fused.py
     fused_lstm_grads = False    # True: the LSTM's parameter gradients on gemm_fused (with g3_riders = False); tools/ab_fused.py
     side_head = True            # False: the head's dW stays on the main stream under use_side_streams; tools/side_bench.py
+    SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
-                 **kw):
+                 scan_dropout=None, word_dropout=None, **kw):
         super().__init__(**kw)
         self.N, self.U, self.E, self.V, self.max_length = int(input_size), int(units), int(embedding_dim), int(vocab_size), int(max_length)
         self.r_in, self.r_feat, self.r_lstm = float(dropout_input), float(dropout), float(dropout_lstm)
@@ -110,6 +111,9 @@ class NIC(ModelBase):
         self._init_weights(np.random.default_rng(self.seed))
         self._shape = None
         self._init_step_state()
+        # scan_dropout (model_base.ScanDropout) / word_dropout (model_base.WordDropout): train_step corrupts the staged batch
+        # (tnt_input_corrupt_f32, one launch behind the staging); None or rate 0 issues nothing.  The setters validate
+        self.scan_dropout, self.word_dropout = scan_dropout, word_dropout
 
     def _init_step_state(self):
         """what exists only once a step or a decode has asked for it (fc_nic.NICfc, which has its own constructor, too)"""
@@ -656,9 +660,11 @@ class NIC(ModelBase):
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
         self._ss_refuse()
+        self._corrupt_check()                       # (grad_sync may have been attached since the constructor)
         if self.self_critical is not None:
             return self.train_step_scst(data)
-        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None, fwd=self.grad_sync is None)
+        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None, fwd=self.grad_sync is None,
+                                 corrupt=True)
         self._ss_refuse(T)
         self._sync_lr()
         self._enc_grad_stale = None

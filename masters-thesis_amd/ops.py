@@ -584,6 +584,15 @@ class HipBackend:
                    _p(tgt_tmajor), _p(a0), _p(h0), _p(c0), _p(c0_dst), B, T, N, ldx, U, _p(xT_dst), ldt, _p(pos), _p(row_weight),
                    _p(tgt_compact), _p(live), _p(loss_row), _p(corr_row), self._s())
 
+    def input_corrupt(self, x, ldx, xT, ldt, cap, B, T, N, V, scan_rate, null_scan, word_rate, unk_id, seed, site_scan, site_word,
+                      step_dev):
+        """scan dropout and word dropout of a staged training batch, in place (tnt_input_corrupt_f32; definition in
+        include/tnt_hip.h): a fired row of x [B][ldx] (and column of xT [N][ldt], nullable) becomes null_scan (nullable:
+        zeros), a fired fed token of cap [B][T] becomes unk_id; the coins are read at the device step word ``step_dev``"""
+        self._call(self.lib.tnt_input_corrupt_f32, "tnt_input_corrupt_f32", _p(x), int(ldx), _p(xT), int(ldt), _p(cap), B, T, N,
+                   int(V), float(scan_rate), _p(null_scan), float(word_rate), int(unk_id), int(seed), int(site_scan),
+                   int(site_word), _p(step_dev), self._s())
+
     def scst_cce(self, logits, ld, V, fed, T, last, adv, end_id, loss_row, lp_row, dlogits, R, gscale):
         """the SCST policy-gradient loss of R sampled captions and its logits gradient (tnt_scst_cce_f32; definition in
         include/tnt_hip.h): row (t-1)*R + r, token fed[r*T + t] (t < T) or last[r], masked after the first terminator"""
