@@ -1280,6 +1280,28 @@ int32_t tnt_weight_average_f32(const float* theta, float* avg, int64_t n, const 
  * buffers' addresses, so the contents move).  TNT_BADARG, and no launch, for n < 0, a null or not 16-byte aligned
  * pointer, overlapping buffers.  n == 0 is a no-op. */
 int32_t tnt_swap_f32(float* a, float* b, int64_t n, void* stream);
+/* Gradient accumulation over the flat gradient arena (accumulate.hip): the device-side sum over the k micro-steps of an
+ * accumulation window (gradient_accumulation_steps=k), in the place data parallel's all-reduce over ranks has; restated by
+ * tests/accum_oracle.py.  This library's definition.  acc: the accumulator, n floats; grad: the gradient arena the
+ * micro-step's backward has just written; sq_acc / sq_slot: one float each, the accumulated and the micro-step's
+ * un-deduplicated Embedding squared norm (the model's sq_override slot); drop_step: the dropout stream's step counter.
+ * The launch is the last one of a micro-step (phases 0, 1) or sits between the backward and the norm launch (phase 2):
+ *   phase 0 OPEN   acc[i] = grad[i] (acc is not read);   sq_acc[0] = sq_slot[0];              drop_step[0] += 1
+ *   phase 1 ADD    acc[i] = acc[i] + grad[i];            sq_acc[0] = sq_acc[0] + sq_slot[0];  drop_step[0] += 1
+ *   phase 2 CLOSE  grad[i] = acc[i] + grad[i] (acc is not written);  sq_slot[0] = sq_acc[0] + sq_slot[0];  drop_step is
+ *                  left alone: the tick of the update behind it advances it
+ * for i in [0, n); the scalars are the work of one thread.  Plain float32 adds in exactly that operand order, every address
+ * written by one thread, no atomic and no cross-thread reduction: the result is bit-identical to numpy float32 doing the
+ * same adds, and a replay is bit-reproducible.  In OPEN / ADD grad is never written.
+ *  - guard (nullable) non-zero: nothing is read, written or advanced (the rule of tnt_step_tick and the update kernels: a
+ *    micro-step whose forward pass was invalid leaves the window as it was).
+ *  - sq_acc / sq_slot are null together (no scalar sum); drop_step is nullable.  With n == 0 the scalar work still happens.
+ * TNT_BADARG, and no launch, for n < 0, null acc / grad, acc or grad not 16-byte aligned, acc and grad sharing an element,
+ * phase outside 0..2, exactly one of sq_acc / sq_slot null, sq_acc == sq_slot.  Float4 main path over a grid-stride range,
+ * n % 4 tail; acc moves non-temporally under the TNT_STREAM_NT policy of the optimizer kernels, grad with plain accesses
+ * (the backward has just written it, and in CLOSE the norm launch reads it next); no LDS or scratch. */
+int32_t tnt_grad_accumulate_f32(float* acc, float* grad, int64_t n, int32_t phase, float* sq_acc, float* sq_slot,
+                                uint32_t* drop_step, const uint32_t* guard, void* stream);
 /* Learning-rate schedule evaluated on the device (schedule.hip): lr[0] = (float) schedule(*step), one thread, in front of
  * the first launch of a training step that reads lr; restated by tests/lr_schedule_oracle.py.  *step (int64: the updates
  * applied so far, the model's adam_t; the first update sees 0, a negative value counts as 0) and params[0..16) (float64)

@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 126
+TNT_VERSION = 127
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -163,6 +163,7 @@ SIGNATURES = {
     "tnt_step_tick": [P, P, P, P, F32, F32, P, P],
     "tnt_weight_average_f32": [P, P, I64, P, I32, P, I32, I64, I32, P, P],
     "tnt_swap_f32": [P, P, I64, P],
+    "tnt_grad_accumulate_f32": [P, P, I64, I32, P, P, P, P, P],
     "tnt_lr_schedule_f32": [P, P, P, P],
     "tnt_sam_f32": [P, P, P, P, P, P, P, P, P, I32, I32, F32, I32, P],
     "tnt_gemm_f32_tile": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, I32, I32, P],

@@ -28,16 +28,20 @@ def build_optimizer(config):
     gclip = config.get("global_clipnorm")
     if gclip is not None and config.get("clipnorm") is not None:
         raise ValueError("clipnorm and global_clipnorm cannot both be set: at most one of them, as in keras")
+    # gradient_accumulation_steps: an optional key of this library's, one update per k training steps
+    # (optimizers._GradientAccumulation); absent, null or 1: off
+    accum = config.get("gradient_accumulation_steps")
     if config["optimizer"] in ("Adam", "AdamW"):
         kw = dict(learning_rate=0.0001 if sched is None else sched, beta_1=0.9, beta_2=0.98, epsilon=10.0e-9,
-                  clipnorm=config["clipnorm"] if gclip is None else None, global_clipnorm=gclip)
+                  clipnorm=config["clipnorm"] if gclip is None else None, global_clipnorm=gclip,
+                  gradient_accumulation_steps=accum)
         if config["optimizer"] == "AdamW":
             opt = AdamW(weight_decay=0.004 if wd is None else wd, **kw)
         else:
             opt = Adam(weight_decay=wd, **kw)
     elif config["optimizer"] == "SGD":
         opt = SGD(learning_rate=config["alpha"] if sched is None else sched, momentum=0.9, nesterov=False, weight_decay=wd,
-                  global_clipnorm=gclip)
+                  global_clipnorm=gclip, gradient_accumulation_steps=accum)
     else:
         raise ValueError("No optimizer specified")
     if excl:

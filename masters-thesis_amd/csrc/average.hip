@@ -126,22 +126,12 @@ int av_grid(int64_t n) {
   return (int)(chunks < 1 ? 1 : (chunks > AV_MAX_GRID ? AV_MAX_GRID : chunks));
 }
 
-// two buffers of n floats, each 16-byte aligned, that share no element
-int32_t av_check_pair(const float* a, const float* b, int64_t n) {
-  if (n < 0) return TNT_BADARG(1);
-  if (a == nullptr || b == nullptr) return TNT_BADARG(2);
-  if (!tnt_aligned16(a) || !tnt_aligned16(b)) return TNT_BADARG(3);
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4u;
-  if (pa == pb || (pa < pb ? pb - pa < bytes : pa - pb < bytes)) return TNT_BADARG(4);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int32_t tnt_weight_average_f32(const float* theta, float* avg, int64_t n, const int64_t* step, int32_t kind,
                                           const double* momentum, int32_t dynamic, int64_t start_step, int32_t every,
                                           const uint32_t* guard, void* stream) {
-  if (int32_t rc = av_check_pair(theta, avg, n)) return rc;
+  if (int32_t rc = tnt_check_stream_pair(theta, avg, n)) return rc;
   if (step == nullptr || momentum == nullptr) return TNT_BADARG(5);
   if (kind != 0 && kind != 1) return TNT_BADARG(6);
   const double mom = *momentum;
@@ -159,7 +149,7 @@ extern "C" int32_t tnt_weight_average_f32(const float* theta, float* avg, int64_
 }
 
 extern "C" int32_t tnt_swap_f32(float* a, float* b, int64_t n, void* stream) {
-  if (int32_t rc = av_check_pair(a, b, n)) return rc;
+  if (int32_t rc = tnt_check_stream_pair(a, b, n)) return rc;
   if (n == 0) return 0;
   hipLaunchKernelGGL(swap_kernel, dim3(av_grid(n)), dim3(AV_THREADS), 0, tnt_stream(stream), a, b, n);
   TNT_LAUNCH_CHECK();

@@ -21,6 +21,17 @@ static inline hipStream_t tnt_stream(void* s) { return reinterpret_cast<hipStrea
 
 static inline bool tnt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// two buffers of n floats, each 16-byte aligned, that share no element (the arena-wide streams of average.hip and
+// accumulate.hip): 0, or the TNT_BADARG code 1 (n < 0), 2 (a null pointer), 3 (alignment), 4 (overlap)
+static inline int32_t tnt_check_stream_pair(const float* a, const float* b, int64_t n) {
+  if (n < 0) return TNT_BADARG(1);
+  if (a == nullptr || b == nullptr) return TNT_BADARG(2);
+  if (!tnt_aligned16(a) || !tnt_aligned16(b)) return TNT_BADARG(3);
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4u;
+  if (pa == pb || (pa < pb ? pb - pa < bytes : pa - pb < bytes)) return TNT_BADARG(4);
+  return 0;
+}
+
 __device__ __forceinline__ float tnt_act(float x, int act, float slope) {
   switch (act) {
     case TNT_ACT_LEAKY: return x > 0.f ? x : x * slope;

@@ -440,6 +440,10 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if getattr(model.optimizer, "global_clipnorm", None) is not None:
         # compile(global_clipnorm=): the pipelined schedules update in slices before all norms exist
         raise NotImplementedError(model.GLOBAL_CLIP_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync)"))
+    if getattr(model.optimizer, "gradient_accumulation_steps", None) is not None:
+        # compile(gradient_accumulation_steps=): the sum over micro-steps takes the all-reduce's place; the two are not combined
+        raise NotImplementedError(model.GRAD_ACCUM_REFUSAL.format(what="accumulation under data parallel (dp.attach / grad_sync) "
+                                                                  "is not implemented"))
     if model.loss_normalise == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)

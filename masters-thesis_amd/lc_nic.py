@@ -74,6 +74,7 @@ class NIC(ModelBase):
     split_encoder = True        # False: one workgroup per region instead of 64-voxel pieces; tools/probe/ld_split_ab.py
     voxel_major = True          # False: the split encoder reads the batch-major betas; a tool sets it by name (tools/ab_bench_att.py voxel_major=0)
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
+    SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
@@ -1137,10 +1138,15 @@ class NIC(ModelBase):
         self._ss_refuse()
         self._coverage_check()                      # (grad_sync may have been attached since the constructor)
         self._corrupt_check()
+        self._sync_accum()
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)
         self._ss_refuse(T)
         self._sync_lr()
         ring = False
+        if self._accum_host is not None:    # gradient_accumulation_steps=k: ModelBase._train_step_accum
+            if self._train_step_accum(B, T):
+                self.optimizer.iterations += 1
+            return self._metrics(True)
         if self.grad_sync is None:
             ring = self._run_step(self._step_runner(self.Et), ("train", B, T) + self._coverage_key(),
                                   lambda: self._train_and_update_graph(B, T))
@@ -1164,6 +1170,7 @@ class NIC(ModelBase):
             raise RuntimeError("compile() the model before train_step_sam")
         self._weight_decay_refuse("train_step_sam")
         self._global_clip_refuse("train_step_sam")
+        self._grad_accum_refuse("train_step_sam applies an update of its own every step")
         if not self.teacher_forcing:
             raise NotImplementedError("train_step_sam is a teacher-forced step (lc_NIC.py:713-838): not built for "
                                       "teacher_forcing=False")

@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_focal_gamma, loss_label_smoothing, loss_normalise,
                          loss_unlikelihood, optimizer_average, optimizer_schedule, check_global_clipnorm,
-                         check_weight_decay, weight_decay_table)
+                         check_gradient_accumulation_steps, check_weight_decay, weight_decay_table)
 
 # dropout site ids of the Philox stream (shared with oracle/models.py)
 S_IN, S_FEAT, S_TEXT, S_OUT = 1, 2, 3, 5
@@ -1039,6 +1039,7 @@ class ModelBase:
     SUPPORTS_UNLIKELIHOOD = True        # False where the loss is not the (t, b)-ordered caption head (those, and NICfc)
     UNLIKELIHOOD_MAX_T = 64             # loss positions per caption: one wave holds a caption's prefix
     SUPPORTS_TOKEN_WEIGHTS = True       # class_weight / focal_gamma / normalise: as SUPPORTS_UNLIKELIHOOD
+    SUPPORTS_GRAD_ACCUMULATION = False  # gradient_accumulation_steps=: True where train_step runs _train_step_accum (nic.NIC, lc_nic.NIC)
     # subclasses fill: self.layers_spec = OrderedDict(layer -> [weight names]),
     # self.keras_shapes = {full name: keras shape}
     def __init__(self, device=None, seed=42, use_graph=True, grad_sync=None):
@@ -1062,6 +1063,9 @@ class ModelBase:
         self.gsq = None                     # global-norm clipping: the one float the update launches read (squared norm of the last step)
         self._gclip_host = None             # the optimizer's global_clipnorm as the recorded launches hold it (_sync_lr)
         self._gsq_filed = False             # a step has written gsq (global_grad_norm)
+        self.acc_grad = self.acc_sq = None  # gradient accumulation: the arena-sized accumulator and the Embedding norm's float
+        self._accum_host = None             # the optimizer's gradient_accumulation_steps as the recorded launches hold it (_sync_lr)
+        self._accum_j = 0                   # micro-steps of the open window that are in the accumulator
         self.lr_schedule = None             # of the compile optimizer (learning_rate=<optimizers.schedules object>)
         self.lr_params = None               # its 16 float64 parameters on the device (tnt_lr_schedule_f32)
         self.agc = None                     # adaptive gradient clipping (enable_agc): (clip_factor, eps), or None
@@ -1135,6 +1139,8 @@ class ModelBase:
             raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
         self._check_weight_decay(bool(check_weight_decay(getattr(optimizer, "weight_decay", None))))
         self._check_global_clip(check_global_clipnorm(getattr(optimizer, "global_clipnorm", None)) is not None)
+        self._check_grad_accum(check_gradient_accumulation_steps(getattr(optimizer, "gradient_accumulation_steps", None))
+                               is not None, normalise=mode)
         self.optimizer = optimizer if optimizer is not None else Adam()
         self.loss = loss
         # Fixed here, not read per step: the head launch sits inside captured graphs, with its smoothing, alpha, gamma and
@@ -1169,6 +1175,8 @@ class ModelBase:
                              "tnt_scst_cce_f32, not the compile loss")
         if mode == "weights" and (self.grad_sync is not None or self.dp_world > 1):
             raise NotImplementedError(self.WEIGHTS_DP_REFUSAL)
+        if mode == "weights" and self._accum_k() is not None:
+            raise NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=self.GRAD_ACCUM_WEIGHTS))
         if mode == "weights" and int(self.S) > 1:
             raise NotImplementedError("normalise=\"weights\" with n_subjects > 1 is not implemented: the per-subject metrics "
                                       "divide each subject's sums by its position count Bs * T, not by its weight sum.  "
@@ -1205,6 +1213,12 @@ class ModelBase:
                                   self.unlikelihood)
         self._store_class_weight(None if class_weight is None else check_class_weight(class_weight, self.V))
 
+    def _head_gscale(self, n):
+        """The gradient scale of a training head launch over ``n`` loss positions: 1 / n for the mean over the batch,
+        divided by the data-parallel world size (the all-reduce is a SUM) and, inside an accumulation window, by its k
+        micro-steps (tnt_grad_accumulate_f32 sums them): either sum is then the mean over the global batch."""
+        return 1.0 / (n * self.dp_world * (self._accum_host or 1))
+
     def _head_loss(self, B, T, want_grad):
         """The head launch of _loss_metrics over the T * B position-ordered rows, chosen by the compile loss: label
         smoothing, unlikelihood, token weights / the focal factor / normalise="weights", or the plain softmax-CCE.  Each in
@@ -1212,7 +1226,7 @@ class ModelBase:
         (probabilities in place, gscale 0): the same objective in both -- keras smooths the evaluation loss too."""
         be, n = self.be, T * B
         probs, dlogits = (None, self.logits) if want_grad else (self.logits, None)
-        gscale = 1.0 / (n * self.dp_world) if want_grad else 0.0
+        gscale = self._head_gscale(n) if want_grad else 0.0
         if self.label_smoothing > 0:
             be.softmax_cce_smooth(self.logits, self.tgt, probs, self.loss_row, self.corr_row, dlogits, n, self.V, self.ldV,
                                   gscale, self.label_smoothing)
@@ -1262,6 +1276,12 @@ class ModelBase:
         self._gsq_filed = False
         self._gclip_host = self._gclip()
         self._check_global_clip(self._gclip_host is not None)
+        # gradient accumulation: one more arena-sized buffer and the float beside it, only for a model that accumulates
+        self._accum_host = self._accum_k()
+        self._check_grad_accum(self._accum_host is not None)
+        self._accum_j = 0
+        self.acc_grad = torch.zeros_like(a.grad) if self._accum_host is not None else None
+        self.acc_sq = self._f(1) if self._accum_host is not None else None
         self._graphs = {}
 
     # ------------------------------------------------------------------ decoupled weight decay (Adam / SGD weight_decay=, AdamW)
@@ -1368,6 +1388,125 @@ class ModelBase:
             raise RuntimeError("global_grad_norm: no training step with global_clipnorm has run yet")
         return float(self.gsq[0]) ** 0.5
 
+    # ------------------------------------------------------------------ gradient accumulation (Adam / SGD gradient_accumulation_steps=)
+    GRAD_ACCUM_REFUSAL = ("gradient accumulation (gradient_accumulation_steps=) is built for the teacher-forced single-device "
+                          "train_step of nic.NIC and lc_nic.NIC only: {what}.  Train with gradient_accumulation_steps=None there")
+    GRAD_ACCUM_WEIGHTS = ("normalise=\"weights\" divides each head launch's gradient by the weight sum of its own micro-batch, so "
+                          "the micro-steps would carry different denominators (the reason of WEIGHTS_DP_REFUSAL); "
+                          "normalise=\"count\" works")
+
+    def _accum_k(self):
+        """the optimizer's gradient_accumulation_steps: an int >= 2, or None (off)"""
+        return None if self.optimizer is None else check_gradient_accumulation_steps(
+            getattr(self.optimizer, "gradient_accumulation_steps", None))
+
+    def _check_grad_accum(self, on, normalise=None):
+        """the refusals of an accumulating optimizer (compile, the optimizer-state build, an assignment found by
+        _sync_accum, every micro-step); dp.attach, enable_agc, train_step_sam and the token-weight check refuse on their
+        side.  ``normalise``: the compile loss's mode where compile has not stored it yet."""
+        if not on:
+            return
+        no = lambda what: NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=what))
+        if not self.SUPPORTS_GRAD_ACCUMULATION:
+            raise no(f"{type(self).__name__} has no accumulating step")
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise no("accumulation under data parallel (dp.attach / grad_sync) is not implemented")
+        if self.agc:
+            raise no("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the window's")
+        if self.scheduled_sampling is not None:
+            raise no("scheduled_sampling has no accumulating step")
+        if self.self_critical is not None:
+            raise no("self_critical has no accumulating step")
+        if not self.teacher_forcing:
+            raise no("the free-running decoder (teacher_forcing=False) has no accumulating step")
+        if self.attention_coverage is not None:
+            raise no("attention_coverage's gradient scale is not threaded through the micro-steps")
+        if (self.loss_normalise if normalise is None else normalise) == "weights":
+            raise no(self.GRAD_ACCUM_WEIGHTS)
+        if int(self.S) > 1:
+            raise no("n_subjects > 1 has no accumulating step")
+
+    def _grad_accum_refuse(self, what):
+        if self._accum_k() is not None:
+            raise NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=what))
+
+    def _sync_accum(self):
+        """In front of every training step (train_step of the accumulating models, in front of the staging; _sync_lr): an
+        assignment to optimizer.gradient_accumulation_steps since the state was built.  Allowed between two windows only.
+        k scales the head launch's gradient and decides which launches a step is, so the recordings are dropped; so is the
+        Embedding backward's state: the dense form and CLOSE leave rows in the gradient table that the sparse form's
+        invariant (zero outside the rows of prev_ids) does not allow, and a fresh state starts from a zeroed table."""
+        k = self._accum_k()
+        if k == self._accum_host or self.adam_t is None:        # (no optimizer state yet: its build reads k)
+            return
+        if self._accum_j:
+            raise RuntimeError(f"gradient_accumulation_steps changed from {self._accum_host} to {k} inside an open window "
+                               f"({self._accum_j} micro-steps accumulated): finish the window or call reset_accumulation() "
+                               "first")
+        self._check_grad_accum(k is not None)
+        self._accum_host = k
+        self.acc_grad = torch.zeros_like(self.arena.grad) if k is not None else None
+        self.acc_sq = self._f(1) if k is not None else None
+        self._graphs = {}
+        self._emb_state = None
+
+    @property
+    def accumulation_position(self):
+        """(j, k): j micro-steps of the current window are in the accumulator, the k-th closes it and applies the update.
+        Without accumulation (0, 1): every step is a window of its own.  A host value, no device read."""
+        return self._accum_j, self._accum_k() or 1
+
+    def reset_accumulation(self):
+        """Drops the open window: the next train_step opens a new one, and what the accumulator holds is never read (OPEN
+        overwrites it).  Weights, moments and every counter of applied updates are untouched; the dropout stream has
+        advanced by the dropped micro-steps."""
+        self._accum_j = 0
+
+    def _train_step_accum(self, B, T, extra=()):
+        """One micro-step of an accumulation window (optimizer gradient_accumulation_steps=k), behind the staging; returns
+        whether it closed the window, i.e. applied an update.  Accumulation is data parallel in time: the contract of dp.py,
+        "G ranks x local batch == one rank on the concatenated batch", with the all-reduce over ranks replaced by a sum
+        over micro-steps on the device (tnt_grad_accumulate_f32).  Micro-step j of a window:
+          forward + backward, nothing deferred (_train_graph as the generic data-parallel schedule runs it): every gradient
+          is written to the arena, the head launch scales dlogits by 1 / (n k) (_head_gscale), the dense Embedding backward
+          files its un-deduplicated squared norm, scaled by 1 / k^2, in its sq_override slot;
+          j == 0: OPEN (acc = grad);  0 < j < k - 1: ADD (acc += grad);  j == k - 1: CLOSE (grad += acc), then
+          _update_graph() unchanged -- norms, L2, global norm, tick, schedule, Adam / SGD with or without decay, averaging.
+        With no BatchNorm and no dropout, k micro-steps on consecutive slices of a batch equal one plain step on the whole
+        batch up to float32 summation order: the loss mean, every gradient, the per-variable clip norms (sum_j sq_j is the
+        Embedding's un-deduplicated norm of the concatenated batch), the global norm, the updated weights.
+        Counting -- this library's rule (keras is not at hand to compare its own):
+          applied updates: adam_t, model.iterations, the learning-rate schedule, Adam's bias correction, the weight average
+          and optimizer.iterations advance on the closing micro-step only;
+          micro-steps: drop_step advances on every one (OPEN / ADD tick it, the update's tick does in CLOSE), so every
+          micro-batch draws its own masks; BatchNorm's batch statistics are per micro-batch and its moving statistics
+          advance per micro-step, as per-replica statistics do under data parallel.
+        Micro-batches of different sizes in one window are allowed: the update is the mean of the k micro-batch means, not
+        the mean over their samples.  Every micro-step's metrics are its own micro-batch's; L2 is the term of the weights
+        its forward used: computed in the opening micro-step (_norms_and_l2, as test_step does), kept in slot 2 of the
+        metrics buffer over the window -- the weights do not change inside it -- and recomputed by the closing update.
+        A guarded micro-step (the persistent LSTM kernel's error word) leaves accumulator, norm and drop_step alone; the trip
+        raises where the metrics are read, and _on_guard_trip reopens the window.
+        Each phase is a recording of its own, replayed as a hipGraph: the dense Embedding backward hands its ids on with a
+        tensor copy, which a launch plan would drop (see _step_runner)."""
+        self._check_grad_accum(True)
+        k, j, a = self._accum_host, self._accum_j, self.arena
+        phase = 0 if j == 0 else (2 if j == k - 1 else 1)
+        seg = self.emb_seg
+
+        def run():
+            with self._deferring(False):
+                self._train_graph(B, T)
+            if phase == 0:
+                self._norms_and_l2(self.met[2:3])
+            self.be.grad_accumulate(self.acc_grad, a.grad, a.total, phase, self.acc_sq, a.sq_override[seg:seg + 1],
+                                    self.drop_step, guard=self._guard_word())
+            if phase == 2:
+                self._update_graph()
+        self._run_captured(("train_acc", B, T, phase) + tuple(extra), run)
+        self._accum_j = 0 if phase == 2 else j + 1
+        return phase == 2
+
     AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
                           "schedules update the arena in slices and the row-sharded encoder finishes its update behind "
                           "_update_fused, so one averaging launch behind the update has no single place there.  Train it on "
@@ -1386,6 +1525,7 @@ class ModelBase:
             self._check_global_clip(gclip is not None)
             self._gclip_host = gclip
             self._graphs = {}
+        self._sync_accum()      # ... and optimizer.gradient_accumulation_steps, between two windows only
         sched = optimizer_schedule(self.optimizer)
         if sched != self.lr_schedule:
             # optimizer.learning_rate was assigned since compile (a float in place of the schedule, or another schedule):
@@ -1960,6 +2100,8 @@ class ModelBase:
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
         if clip_factor is not None:
             self._global_clip_refuse("a step with adaptive gradient clipping (enable_agc)")
+            self._grad_accum_refuse("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the "
+                                    "window's")
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
         self._graphs = {}
 
@@ -2018,7 +2160,8 @@ class ModelBase:
 
     def get_gradient(self, name):
         """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
-        optimizer kernels add on the fly)."""
+        optimizer kernels add on the fly).  Under gradient accumulation: behind a closing micro-step what the update
+        consumed, the window's mean gradient; behind any other that micro-batch's share of it (its gradient / k)."""
         return self._unpack(name, self.arena.g(name))
 
     @property
@@ -2418,13 +2561,19 @@ class ModelBase:
     def _on_guard_trip(self, code):
         self.disable_seq_lstm()
         what = {1: "a barrier timed out", 2: "a launch did not place 32 workgroups on every XCD"}.get(code, "unknown")
+        accum = ""
+        if self._accum_host is not None:
+            # the faulted micro-step left the accumulator alone, but its place in the window is lost: start the window again
+            self._accum_j = 0
+            accum = ("  Gradient accumulation: the open window was dropped -- its earlier micro-batches were discarded, the "
+                     "next train_step opens a new window.")
         raise DeviceGuardError(
             f"persistent LSTM kernel: device guard tripped (code {code}: {what}).  The results of that step are invalid; "
             "its optimizer update was skipped, so weights, moments and step counters are unchanged.  NOT unchanged: the "
             "BatchNorm moving mean / variance, which the forward pass of the faulted step already advanced (a retried step "
             "applies that 1 % moving-average update a second time), and under data parallel the trip is per rank -- the other "
             "replicas have applied their update, so re-broadcast the parameters (dp.broadcast_parameters) before going on.  "
-            "The model now uses the per-step LSTM kernels: run the step again.")
+            "The model now uses the per-step LSTM kernels: run the step again." + accum)
 
     def _guarded(self, fn):
         """Inference paths: run ``fn`` (which ends in a host read anyway), check the guard word, and on a trip fall back
@@ -2872,7 +3021,9 @@ class ModelBase:
         ``validation_averaged=True`` (optimizers.MovingAverage / SWA): the validation pass of every epoch runs inside
         ``averaged_weights()``, so the ``val_*`` logs are the averaged model's.
         ``class_weight`` (keras: an ``{id: weight}`` dict; an array of V weights is accepted too): ``set_class_weight`` before
-        the first step; None leaves the model's weights as they are."""
+        the first step; None leaves the model's weights as they are.
+        Gradient accumulation (optimizer gradient_accumulation_steps=k): ``steps_per_epoch`` counts micro-steps, an update
+        is applied every k-th, and a window left open at the end of an epoch carries over into the next."""
         if class_weight is not None:
             self.set_class_weight(class_weight)
         if validation_averaged and self.average is None:

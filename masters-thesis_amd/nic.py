@@ -39,6 +39,7 @@ class NIC(ModelBase):
     fused_lstm_grads = False    # True: the LSTM's parameter gradients on gemm_fused (with g3_riders = False); tools/ab_fused.py
     side_head = True            # False: the head's dW stays on the main stream under use_side_streams; tools/side_bench.py
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
+    SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
@@ -427,7 +428,7 @@ class NIC(ModelBase):
         if want_grad and self._route.head_map_fresh:
             # the distinct rows, each weighted by its multiplicity; rows past the live count hold zeros (staging launch)
             self.be.softmax_cce_live(self.logits, self.head_tgt, None, self.loss_row, self.corr_row, self.logits, n, self.V,
-                                     self.ldV, 1.0 / (n * self.dp_world), self.head_live, self.head_w)
+                                     self.ldV, self._head_gscale(n), self.head_live, self.head_w)
         else:
             self._head_loss(B, T, want_grad)
         self._sum2(self.loss_row, self.met[0:1], self.corr_row, self.met[1:2], n, 1.0 / n)
@@ -663,12 +664,19 @@ class NIC(ModelBase):
         self._corrupt_check()                       # (grad_sync may have been attached since the constructor)
         if self.self_critical is not None:
             return self.train_step_scst(data)
-        B, T = self._stage_batch(data[0], data[1], self.N, head_map=self.grad_sync is None, fwd=self.grad_sync is None,
-                                 corrupt=True)
+        self._sync_accum()
+        # a micro-step of an accumulation window stages as the generic data-parallel step does: the forward does not ride in
+        # the staging launch and the head keeps its position-ordered rows
+        plain = self.grad_sync is None and self._accum_k() is None
+        B, T = self._stage_batch(data[0], data[1], self.N, head_map=plain, fwd=plain, corrupt=True)
         self._ss_refuse(T)
         self._sync_lr()
         self._enc_grad_stale = None
         ring = False
+        if self._accum_host is not None:    # gradient_accumulation_steps=k: ModelBase._train_step_accum
+            if self._train_step_accum(B, T):
+                self.optimizer.iterations += 1
+            return self._lr_metric(self._metrics_from(self._met_snapshot(), loss=0, L2=2, accuracy=1))
         if self.grad_sync is None:      # replayed as a launch plan or a hipGraph: ModelBase._step_runner
             compact = self._route.head_map_fresh        # the staging launch built the head's row map
             staged = self._route.stage_fwd_done         # ... and ran the encoder forward: the step leaves it out

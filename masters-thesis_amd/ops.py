@@ -857,6 +857,13 @@ class HipBackend:
         """a <-> b over n floats, in place (tnt_swap_f32)"""
         self._call(self.lib.tnt_swap_f32, "tnt_swap_f32", _p(a), _p(b), int(n), self._s())
 
+    def grad_accumulate(self, acc, grad, n, phase, sq_acc=None, sq_slot=None, drop_step=None, guard=None):
+        """one accumulation launch over the n floats of the gradient arena (tnt_grad_accumulate_f32; definition in
+        include/tnt_hip.h): phase 0 opens the window (acc = grad), 1 adds (acc += grad), 2 closes it (grad += acc); the
+        Embedding's squared norm is summed beside it, and phases 0 / 1 advance ``drop_step``"""
+        self._call(self.lib.tnt_grad_accumulate_f32, "tnt_grad_accumulate_f32", _p(acc), _p(grad), int(n), int(phase),
+                   _p(sq_acc), _p(sq_slot), _p(drop_step), _p(guard), self._s())
+
     def block_dense_dx(self, dpre, W, dx, B, R, Din, Dout):
         self._call(self.lib.tnt_block_dense_dx_f32, "tnt_block_dense_dx_f32", _p(dpre), _p(W), _p(dx), B, R, Din, Dout, self._s())
 

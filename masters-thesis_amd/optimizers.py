@@ -134,23 +134,56 @@ class _GlobalClipnorm:
         self.global_clipnorm = global_clipnorm
 
 
-class Adam(_LearningRate, _WeightDecay, _GlobalClipnorm):
+def check_gradient_accumulation_steps(k):
+    """None, or the value as an int >= 2; 1 is None (no accumulation).  ValueError unless it is None or an integer >= 1
+    (bool, float and str refused)"""
+    import numbers
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 1 or k >= 2 ** 31:
+        raise ValueError(f"gradient_accumulation_steps must be None or an int >= 1, got {k!r}")
+    return int(k) if k > 1 else None
+
+
+class _GradientAccumulation:
+    """``gradient_accumulation_steps`` of a descriptor (keras 3: the argument of every optimizer): with k >= 2 a
+    ``train_step`` is a micro-step, the gradients of k consecutive micro-steps are summed on the device
+    (tnt_grad_accumulate_f32, definition in include/tnt_hip.h), each scaled by 1 / k, and the k-th applies ONE update from
+    their mean -- an effective batch of k micro-batches at the memory and kernel shapes of one.  None or 1: off.
+    ``ModelBase._train_step_accum`` holds the counting rules (what advances per update and what per micro-step).
+
+    nic.NIC and lc_nic.NIC only, on one device; data parallel, enable_agc, train_step_sam, scheduled sampling,
+    self-critical training, teacher_forcing=False, attention_coverage, normalise="weights" and n_subjects > 1 refuse it
+    with NotImplementedError."""
+
+    @property
+    def gradient_accumulation_steps(self):
+        return self._gradient_accumulation_steps
+
+    @gradient_accumulation_steps.setter
+    def gradient_accumulation_steps(self, v):
+        self._gradient_accumulation_steps = check_gradient_accumulation_steps(v)
+
+
+class Adam(_LearningRate, _WeightDecay, _GlobalClipnorm, _GradientAccumulation):
     """tf.keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay) -- main.py:97.
     ``learning_rate``: a float or an ``optimizers.schedules`` object.
     ``clipnorm`` is per variable; None disables it (the TF<=2.3 behaviour of a
     custom tape.gradient -> apply_gradients step).
     ``weight_decay``: decoupled weight decay, see ``_WeightDecay``; None or 0 is plain Adam.
     ``global_clipnorm``: one norm over all gradients in ``clipnorm``'s place, see ``_GlobalClipnorm``; ``clipvalue`` is
-    refused."""
+    refused.
+    ``gradient_accumulation_steps``: one update per k micro-steps, see ``_GradientAccumulation``; None or 1 is off."""
 
     kind = "adam"
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, weight_decay=None,
-                 global_clipnorm=None, **kw):
+                 global_clipnorm=None, gradient_accumulation_steps=None, **kw):
         self.lr = kw.pop("lr", learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self._init_clipping(clipnorm, global_clipnorm, kw)
         self.weight_decay = weight_decay
+        self.gradient_accumulation_steps = gradient_accumulation_steps
         self.iterations = 0
 
 
@@ -160,27 +193,30 @@ class AdamW(Adam):
     variable is decayed unless ``exclude_from_weight_decay`` names it (see ``_WeightDecay``)."""
 
     def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None,
-                 global_clipnorm=None, **kw):
+                 global_clipnorm=None, gradient_accumulation_steps=None, **kw):
         if weight_decay is None:
             raise ValueError("AdamW needs a weight_decay; Adam is the optimizer without one")
-        super().__init__(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay, global_clipnorm, **kw)
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, clipnorm, weight_decay, global_clipnorm,
+                         gradient_accumulation_steps, **kw)
 
 
-class SGD(_LearningRate, _WeightDecay, _GlobalClipnorm):
+class SGD(_LearningRate, _WeightDecay, _GlobalClipnorm, _GradientAccumulation):
     """tf.keras.optimizers.SGD(learning_rate, momentum, nesterov=False, weight_decay) -- main.py:100-102.
     ``learning_rate``: a float or an ``optimizers.schedules`` object.  ``weight_decay``: decoupled weight decay, see
-    ``_WeightDecay``; None or 0 is plain SGD.  ``global_clipnorm``: see ``_GlobalClipnorm``."""
+    ``_WeightDecay``; None or 0 is plain SGD.  ``global_clipnorm``: see ``_GlobalClipnorm``.
+    ``gradient_accumulation_steps``: see ``_GradientAccumulation``."""
 
     kind = "sgd"
 
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None, weight_decay=None,
-                 global_clipnorm=None, **kw):
+                 global_clipnorm=None, gradient_accumulation_steps=None, **kw):
         if nesterov:
             raise NotImplementedError("nesterov momentum is not used by the reference path")
         self.lr = kw.pop("lr", learning_rate)
         self.momentum = float(momentum)
         self._init_clipping(clipnorm, global_clipnorm, kw)
         self.weight_decay = weight_decay
+        self.gradient_accumulation_steps = gradient_accumulation_steps
         self.iterations = 0
 
 
@@ -244,6 +280,7 @@ class _AveragedOptimizer:
     iterations = _delegate("iterations")
     weight_decay = _delegate("weight_decay")
     global_clipnorm = _delegate("global_clipnorm")
+    gradient_accumulation_steps = _delegate("gradient_accumulation_steps")
 
     def exclude_from_weight_decay(self, var_list=None, var_names=None):
         self._optimizer.exclude_from_weight_decay(var_list=var_list, var_names=var_names)
