@@ -708,6 +708,31 @@ int32_t tnt_softmax_cce_weighted_f32(const float* logits, const int32_t* target,
                                      float* probs, float* loss_row, float* correct_row, float* dlogits,
                                      int32_t rows, int32_t V, int32_t ld, float gscale,
                                      float gamma, int32_t normalise, void* stream);
+/* ---- the same head mixed with knowledge distillation (Hinton et al. 2015, "Distilling the Knowledge in a Neural
+ * Network"), one launch (distill.hip): a frozen teacher's temperature-softened distribution is a second target of every
+ * row.  logits [rows][ld] (student x), teacher [rows][ld_teacher] (teacher logits u), V valid columns in both,
+ * y = target[r], a = alpha in [0, 1], t = temperature > 0.  Per row:
+ *   ce, m_y, p = softmax(x)   as tnt_softmax_cce_f32(from_logits=0, mask_zero=0): ce = -log(clip(p_y, 1e-7, 1 - 1e-7)),
+ *                             m_y = 1 where that clip is inactive, else 0; a target id outside [0, V) matches no class
+ *                             (p_y = 0: ce = -log(1e-7), m_y = 0)
+ *   pt = softmax(x / t),  qt = softmax(u / t)   over the V valid columns
+ *   kl        = sum_v qt_v (log qt_v - log pt_v), the logs taken from the logits ((u_v - max u) / t - log Zu, likewise
+ *               for x), not from clipped probabilities: no clip in this term; a class with qt_v == 0 contributes exactly 0
+ *   loss_row  = (1 - a) ce + a t^2 kl
+ *   kl_row    = kl                                                   (unscaled)
+ *   correct_row = (first argmax of x == y)
+ *   dlogits_v = gscale ((1 - a) m_y (p_v - [v == y]) + a t (pt_v - qt_v))
+ * alpha = 0 gives tnt_softmax_cce_f32's outputs up to rounding.  The teacher must be finite in the valid columns.
+ * dlogits may alias logits.  teacher may not alias any output: TNT_BADARG when the pointers are equal.  Pad columns
+ * [V, ld) of logits are ignored; pad columns [V, ld_teacher) of teacher are never read, not even as part of a float4; pad
+ * columns of dlogits are left as they were or written as zero (inside the register kernel's window, which needs both
+ * rows float4-addressable: ld % 4 == 0, ld_teacher % 4 == 0, 16-byte aligned pointers).  Every output is nullable.
+ * rows == 0 is a no-op.  TNT_BADARG for rows < 0, V <= 0, ld < V, ld_teacher < V, null logits / teacher / target, alpha
+ * outside [0, 1] or NaN, temperature not finite or <= 0: a rejected call launches nothing. */
+int32_t tnt_softmax_cce_distill_f32(const float* logits, const float* teacher, const int32_t* target,
+                                    float* loss_row, float* kl_row, float* correct_row, float* dlogits,
+                                    int32_t rows, int32_t V, int32_t ld, int32_t ld_teacher,
+                                    float gscale, float alpha, float temperature, void* stream);
 /* target ids from a dense one-hot (B,T,V) float array: ids[t*B+b] = argmax_v (first max wins).
  * B == 0 or T == 0 is a no-op; TNT_BADARG for B < 0, T < 0, V <= 0, null pointers. */
 int32_t tnt_onehot_argmax_f32(const float* onehot, int32_t* ids_tmajor, int32_t B, int32_t T,

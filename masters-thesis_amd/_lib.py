@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 127
+TNT_VERSION = 128
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -75,6 +75,7 @@ SIGNATURES = {
     "tnt_softmax_cce_smooth_f32": [P, P, P, P, P, P, I32, I32, I32, F32, F32, P],
     "tnt_softmax_cce_unlikely_f32": [P, P, P, P, P, P, I32, I32, I32, I32, F32, F32, P],
     "tnt_softmax_cce_weighted_f32": [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, I32, P],
+    "tnt_softmax_cce_distill_f32": [P, P, P, P, P, P, P, I32, I32, I32, I32, F32, F32, F32, P],
     "tnt_onehot_argmax_f32": [P, P, I32, I32, I32, P],
     "tnt_beam_topk_f32": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P],
     "tnt_beam_step_f32": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, P, P],

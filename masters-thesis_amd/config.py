@@ -93,10 +93,12 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
     else:
         raise ValueError(f"unknown mode {mode!r}")
     # label_smoothing, unlikelihood: optional keys of this library's (the reference's config has none), default 0; so are
-    # class_weight (an {id: weight} mapping), focal_gamma and loss_normalise ("count" / "weights"), default neutral
+    # class_weight (an {id: weight} mapping), focal_gamma and loss_normalise ("count" / "weights"), default neutral; and
+    # distillation ({alpha: , temperature: }; the caller gives the model its teacher with set_teacher), default none
     loss = CategoricalCrossentropy(from_logits=False, reduction="none", label_smoothing=config.get("label_smoothing", 0.0),
                                    unlikelihood=config.get("unlikelihood", 0.0), class_weight=config.get("class_weight"),
                                    focal_gamma=config.get("focal_gamma", 0.0),
-                                   normalise=config.get("loss_normalise", "count"))
+                                   normalise=config.get("loss_normalise", "count"),
+                                   distillation=config.get("distillation"))
     model.compile(build_optimizer(config), loss, run_eagerly=True)
     return model

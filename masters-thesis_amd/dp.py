@@ -453,6 +453,10 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model._corruption() is not None:
         # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...): single device only
         raise NotImplementedError(model.CORRUPT_DP_REFUSAL)
+    if model._distill_on():
+        # compile(CategoricalCrossentropy(distillation=...)): no data-parallel schedule runs the teacher
+        raise NotImplementedError(model.DISTILL_REFUSAL.format(what="there is no data-parallel schedule (dp.attach / grad_sync) "
+                                                                   "that runs the teacher"))
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
     if model.agc and world > 1:

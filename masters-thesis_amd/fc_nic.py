@@ -34,6 +34,7 @@ class NICfc(_DenseNIC):
     SUPPORTS_TOKEN_WEIGHTS = False      # so is the weighted head
     SUPPORTS_INPUT_CORRUPTION = False   # and so are scan_dropout / word_dropout
     SUPPORTS_GRAD_ACCUMULATION = False  # and gradient_accumulation_steps
+    SUPPORTS_DISTILLATION = False       # and distillation= / set_teacher
 
     def __init__(self, input_size, units, embedding_features, embedding_text, vocab_size, max_length, dropout_input,
                  dropout_features, dropout_text, dropout_lstm, dropout_out, input_reg, lstm_reg, output_reg, **kw):

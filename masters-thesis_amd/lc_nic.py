@@ -75,6 +75,7 @@ class NIC(ModelBase):
     voxel_major = True          # False: the split encoder reads the batch-major betas; a tool sets it by name (tools/ab_bench_att.py voxel_major=0)
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
     SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
+    SUPPORTS_DISTILLATION = True        # CategoricalCrossentropy(distillation=) / set_teacher (ModelBase._teach)
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
@@ -777,6 +778,8 @@ class NIC(ModelBase):
                 be.sum(self.colB[B + q * Bs:], self.met[k + 1:k + 2], Bs, 1.0 / (Bs * T))
                 be.attention_metric(self.alpha.view(-1)[q * Bs * self.R:], self.met[k + 2:k + 3], self.metric_part, T, Bs,
                                     self.R, B * self.R)
+        if want_grad and self._distill_on():
+            self._distill_metric(n)     # the finalize launch's third slot is the attention metric's: a launch of its own then
 
     # ------------------------------------------------------------------ backward
     def _backward(self, B, T):
@@ -1110,12 +1113,14 @@ class NIC(ModelBase):
         B, T = self._shape
         return (self.att_keep, B * self.R * self.A, T, self.r_attn, self.seed, S_ATTN, self.drop_step)
 
-    def _metrics(self, with_lr, ring=False):
+    def _metrics(self, with_lr, ring=False, distill=False):
         m = self._met_snapshot(ring)
         if self.S == 1:
             out = Metrics(loss=m[0], L2=m[2], accuracy=m[1], attention=m[3])
             if self.attention_coverage is not None:
                 out["coverage"] = m[4]              # unweighted; ``loss`` stays the cross-entropy
+            if distill:
+                out["distill_kl"] = m[self.DISTILL_KL]
         else:       # keys of ms2_NIC.train_step's return dict (ms2_NIC.py:366-374), A, B, C ... per subject
             out = Metrics(loss=m[0], L2=m[2])
             for q in range(self.S):
@@ -1139,8 +1144,12 @@ class NIC(ModelBase):
         self._coverage_check()                      # (grad_sync may have been attached since the constructor)
         self._corrupt_check()
         self._sync_accum()
+        distill = self._distill_begin()
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)
         self._ss_refuse(T)
+        if distill:
+            self._teach(data, B, T)
+            self._distill_bufs(B, T)        # behind it: the teacher may just have rebuilt its buffers
         self._sync_lr()
         ring = False
         if self._accum_host is not None:    # gradient_accumulation_steps=k: ModelBase._train_step_accum
@@ -1148,14 +1157,14 @@ class NIC(ModelBase):
                 self.optimizer.iterations += 1
             return self._metrics(True)
         if self.grad_sync is None:
-            ring = self._run_step(self._step_runner(self.Et), ("train", B, T) + self._coverage_key(),
+            ring = self._run_step(self._step_runner(self.Et), ("train", B, T) + self._coverage_key() + (("distill",) if distill else ()),
                                   lambda: self._train_and_update_graph(B, T))
         elif getattr(self.grad_sync, "pipelined", False):
             self.grad_sync.step(self, B, T)
         else:
             self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
-        return self._metrics(True, ring)
+        return self._metrics(True, ring, distill)
 
     _alpha_mse = 0.0        # coefficient of the attention-MSE gradient in the backward chain (train_step_sam's first pass)
 
@@ -1181,6 +1190,8 @@ class NIC(ModelBase):
         if self.attention_coverage is not None:
             raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
                                       "gradient of its first pass): not built for attention_coverage")
+        if self._distill_on():
+            raise NotImplementedError(self.DISTILL_REFUSAL.format(what="train_step_sam's two passes do not run the teacher"))
         self._corrupt_check()
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)      # both passes read this batch
         self._sync_lr()

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_focal_gamma, loss_label_smoothing, loss_normalise,
+from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_distillation, loss_focal_gamma, loss_label_smoothing,
+                         loss_normalise,
                          loss_unlikelihood, optimizer_average, optimizer_schedule, check_global_clipnorm,
                          check_gradient_accumulation_steps, check_weight_decay, weight_decay_table)
 
@@ -1040,6 +1041,8 @@ class ModelBase:
     UNLIKELIHOOD_MAX_T = 64             # loss positions per caption: one wave holds a caption's prefix
     SUPPORTS_TOKEN_WEIGHTS = True       # class_weight / focal_gamma / normalise: as SUPPORTS_UNLIKELIHOOD
     SUPPORTS_GRAD_ACCUMULATION = False  # gradient_accumulation_steps=: True where train_step runs _train_step_accum (nic.NIC, lc_nic.NIC)
+    SUPPORTS_DISTILLATION = False       # CategoricalCrossentropy(distillation=) / set_teacher: True on nic.NIC and lc_nic.NIC
+    DISTILL_KL = 5                      # slot of ``met`` that carries the mean of kl_row (``distill_kl``)
     # subclasses fill: self.layers_spec = OrderedDict(layer -> [weight names]),
     # self.keras_shapes = {full name: keras shape}
     def __init__(self, device=None, seed=42, use_graph=True, grad_sync=None):
@@ -1057,6 +1060,11 @@ class ModelBase:
         self.loss_normalise = "count"       # of the compile loss (CategoricalCrossentropy(normalise=...))
         self.class_weight = None            # host copy of the token weights (compile loss / set_class_weight / fit), or None
         self.cw_dev = None                  # the same V floats on the device: an argument of the weighted head launch
+        self.distillation = None            # of the compile loss (CategoricalCrossentropy(distillation=...)); None where neutral
+        self.teacher = None                 # the frozen model whose logits a distilled step reads (set_teacher)
+        self._teacher_adapt = None          # set_teacher(adapt=): maps the student's batch to the teacher's
+        self.kl_row = None                  # the distilled head's kl per loss position (_distill_bufs)
+        self._teacher_held = None           # (address, row stride, shape) of teacher.logits in the recorded steps (_distill_bufs)
         self.average = None                 # of the compile optimizer (optimizers.MovingAverage / SWA): an optimizers.Average
         self.seg_wd = None                  # decoupled weight decay (compile optimizer's weight_decay): one float per variable on the device, or None
         self.seg_wd_host = None             # the same table on the host (the encoder's fused update takes its entry as a scalar)
@@ -1134,6 +1142,15 @@ class ModelBase:
         gamma, mode = loss_focal_gamma(loss), loss_normalise(loss)
         cw = loss_class_weight(loss, self.V)
         self._check_token_weights(cw is not None, gamma, mode, eps, alpha)
+        distill = loss_distillation(loss)
+        if distill is not None:
+            if eps > 0 or alpha > 0 or cw is not None or gamma > 0 or mode == "weights":
+                raise ValueError("distillation together with label_smoothing > 0, unlikelihood > 0 or class_weight / focal_gamma "
+                                 "/ normalise=\"weights\" is not implemented: one head kernel computes one of them")
+            if self.SUPPORTS_DISTILLATION and self.self_critical is not None:
+                raise ValueError("distillation does not apply to a self_critical model: its loss is the advantage-weighted "
+                                 "tnt_scst_cce_f32, not the compile loss")
+            self._distill_refuse(self.teacher, optimizer)
         avg = optimizer_average(optimizer)
         if avg is not None and self.grad_sync is not None:
             raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
@@ -1147,12 +1164,12 @@ class ModelBase:
         # mode as arguments.  The averaging launch sits inside the same plans / graphs, and its settings are launch
         # arguments; so does the schedule's launch (tnt_lr_schedule_f32), whose parameters live in a device buffer of the
         # model's.  A change of any of them drops the recordings
-        recorded = (eps, alpha, gamma, mode, avg, optimizer_schedule(self.optimizer))
+        recorded = (eps, alpha, gamma, mode, avg, optimizer_schedule(self.optimizer), distill)
         if recorded != (self.label_smoothing, self.unlikelihood, self.focal_gamma, self.loss_normalise, self.average,
-                        self.lr_schedule):
+                        self.lr_schedule, self.distillation):
             self._graphs = {}
         (self.label_smoothing, self.unlikelihood, self.focal_gamma, self.loss_normalise, self.average,
-         self.lr_schedule) = recorded
+         self.lr_schedule, self.distillation) = recorded
         # ... and so does whether there are token weights; the weights themselves are the contents of a device buffer
         self._store_class_weight(cw)
         if self.built:
@@ -1209,9 +1226,137 @@ class ModelBase:
     def set_class_weight(self, class_weight):
         """Replace the token weights of a compiled model: an array-like of V weights, an ``{id: weight}`` dict (missing ids
         weigh 1) or None.  The next step, a replay of a recorded plan or graph included, uses them."""
+        if class_weight is not None and self._distill_on():
+            # compile's exclusion, for the weights that arrive behind it (fit(class_weight=) comes through here)
+            raise ValueError("class_weight together with distillation is not implemented: one head kernel computes one of "
+                             "them")
         self._check_token_weights(class_weight is not None, self.focal_gamma, self.loss_normalise, self.label_smoothing,
                                   self.unlikelihood)
         self._store_class_weight(None if class_weight is None else check_class_weight(class_weight, self.V))
+
+    # ------------------------------------------------------------------ knowledge distillation (distillation= / set_teacher)
+    DISTILL_REFUSAL = ("knowledge distillation (CategoricalCrossentropy(distillation=...) / set_teacher) is built for the plain "
+                       "single-device teacher-forced step of nic.NIC and lc_nic.NIC only: {what}")
+
+    def _distill_on(self):
+        """whether the training head launch is tnt_softmax_cce_distill_f32 (a non-neutral descriptor)"""
+        return self.distillation is not None
+
+    def _distill_refuse(self, teacher=None, optimizer=None):
+        """what a distilled step refuses, of the student and (where given) of its teacher: compile, set_teacher, dp.attach and
+        every distilled train_step call it.  ``optimizer``: the one compile is about to store."""
+        no = lambda what: NotImplementedError(self.DISTILL_REFUSAL.format(what=what))
+        if not self.SUPPORTS_DISTILLATION:
+            raise no(f"{type(self).__name__} does not support it")
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise no("there is no data-parallel schedule (dp.attach / grad_sync) that runs the teacher")
+        opt = self.optimizer if optimizer is None else optimizer
+        if check_gradient_accumulation_steps(getattr(opt, "gradient_accumulation_steps", None)) is not None:
+            raise no("gradient_accumulation_steps has no distilled micro-step")
+        if self.scheduled_sampling is not None:
+            raise no("scheduled_sampling feeds the student its own words, the teacher the caption's")
+        if self.self_critical is not None:
+            raise no("a self_critical model's loss is the advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        if not self.teacher_forcing:
+            raise no("the free-running decoder (teacher_forcing=False) feeds the student its own words")
+        if int(self.S) > 1:
+            raise no("n_subjects > 1 is not supported on the student")
+        if teacher is None:
+            return
+        if teacher is self:
+            raise no("a model cannot be its own teacher (its logits buffer is the one the student's gradient is written to)")
+        if not isinstance(teacher, ModelBase) or not teacher.SUPPORTS_DISTILLATION:
+            raise no(f"a {type(teacher).__name__} cannot be a teacher")
+        if int(teacher.S) > 1:
+            raise no("n_subjects > 1 is not supported on the teacher")
+        if getattr(teacher, "use_layer_norm", False):
+            raise no("an attention-model teacher with use_layer_norm=True is not supported")
+        if not teacher.teacher_forcing:
+            raise no("a teacher built with teacher_forcing=False is not supported: the teacher's pass is the teacher-forced one")
+
+    def set_teacher(self, teacher, adapt=None):
+        """The frozen model a distilled training step (CategoricalCrossentropy(distillation=...)) takes its second target
+        from: a nic.NIC or lc_nic.NIC of either family on the same device, with the same vocabulary size and maximum caption
+        length.  In front of every distilled train_step it stages the batch and runs its inference forward (no dropout,
+        moving BatchNorm statistics, no loss) as a captured sequence of its own; its weights, optimizer state, moving
+        statistics and dropout counters are not touched, and a later change of its weights is seen by the next step.
+        That forward is always the teacher-forced one over the caption's own words, also for a teacher that was itself
+        trained with scheduled_sampling or self_critical (either is a way to train it, not a part of its inference
+        forward); a teacher built with teacher_forcing=False is refused.
+        ``adapt(data) -> data`` maps the student's ``((scan, cap, a0, c0), target)`` batch to the teacher's (another scan
+        width or state size); without it the batch is passed through, and refused where the teacher cannot stage it.
+        ``set_teacher(None)`` detaches.  Either drops the recorded plans and graphs."""
+        if teacher is None:
+            if adapt is not None:
+                raise ValueError("adapt= needs a teacher")
+        else:
+            self._distill_refuse(teacher)
+            same = teacher.device.type == self.device.type and (teacher.device.index or 0) == (self.device.index or 0)
+            if not same:
+                raise ValueError(f"the teacher sits on {teacher.device}, the student on {self.device}: both must share a device")
+            if int(teacher.V) != int(self.V):
+                raise ValueError(f"the teacher's vocabulary has {teacher.V} words, the student's {self.V}")
+            if int(teacher.max_length) != int(self.max_length):
+                raise ValueError(f"the teacher's maximum caption length is {teacher.max_length}, the student's {self.max_length}")
+            if adapt is not None and not callable(adapt):
+                raise ValueError(f"adapt must be a callable data -> data, got {adapt!r}")
+        self.teacher, self._teacher_adapt = teacher, adapt
+        self._teacher_held = None
+        self._graphs = {}
+
+    def _distill_bufs(self, B, T):
+        """Behind _teach and outside any capture: kl_row of the staged shape, and the address and row stride of the
+        teacher's logits as the student's recordings hold them.  The teacher rebuilds its buffers whenever it is staged at
+        another shape (its own test_step or decode at another batch size, a second student) and drops only its own
+        recordings; a new kl_row or a moved teacher row drops the student's."""
+        if self.kl_row is None or self.kl_row.numel() != T * B:
+            self.kl_row = self._f(T * B)
+            self._graphs = {}
+        t = self.teacher
+        held = (t.logits.data_ptr(), int(t.ldV), tuple(t.logits.shape))
+        if held != self._teacher_held:
+            self._teacher_held = held
+            self._graphs = {}
+
+    def _distill_begin(self):
+        """In front of a train_step's staging: whether the step is a distilled one, behind its refusals"""
+        if not self._distill_on():
+            return False
+        self._distill_refuse(self.teacher)
+        if self.teacher is None:
+            raise RuntimeError("the compile loss asks for distillation but the model has no teacher: call set_teacher(model) "
+                               "before train_step")
+        return True
+
+    def _teach(self, data, B, T):
+        """The teacher's part of a distilled step, behind the student's staging and in front of its recorded step: stage
+        the (adapted) batch on the teacher and run its teacher-forced inference forward, which leaves teacher.logits
+        (T * B rows, t-major: the student's row order) where they are.  The teacher's persistent-chain guard word is
+        honoured as _guarded does (one host read): fall back to the per-step kernels and run again."""
+        t = self.teacher
+        batch = data if self._teacher_adapt is None else self._teacher_adapt(data)
+        x, cap, a0, c0 = batch[0][:4]
+        if np.shape(x)[-1] != t._input_width() or np.shape(a0)[-1] != t.U or np.shape(c0)[-1] != t.U:
+            raise ValueError(f"the teacher stages scans of {t._input_width()} columns and states of {t.U} units, the batch holds "
+                             f"{np.shape(x)[-1]} and {np.shape(a0)[-1]}: give set_teacher an adapt= that maps the batch")
+        if tuple(np.shape(cap)) != (B, T):
+            raise ValueError(f"the teacher's captions have shape {tuple(np.shape(cap))}, the student's {(B, T)}")
+        t._stage_batch((x, cap, a0, c0), None, t._input_width())
+        run = lambda: t._run_captured(("teach", B, T), lambda: t._forward(B, T, False))
+        run()
+        if t._guard_word() is not None and float(t.met[t.GUARD]) != 0.0:
+            t.disable_seq_lstm()
+            run()
+
+    def _distill_metric(self, n):
+        """the total of kl_row behind a distilled head launch: in the step-finalize launch's free third slot where the step
+        defers its totals and the model has not taken the slot, else a launch of its own"""
+        out = self.met[self.DISTILL_KL:self.DISTILL_KL + 1]
+        t = self._tail
+        if t.deferring and t.x2 is None:
+            t.x2, t.out2, t.n2, t.scale2 = self.kl_row, out, n, 1.0 / n
+        else:
+            self.be.sum(self.kl_row, out, n, 1.0 / n)
 
     def _head_gscale(self, n):
         """The gradient scale of a training head launch over ``n`` loss positions: 1 / n for the mean over the batch,
@@ -1223,7 +1368,9 @@ class ModelBase:
         """The head launch of _loss_metrics over the T * B position-ordered rows, chosen by the compile loss: label
         smoothing, unlikelihood, token weights / the focal factor / normalise="weights", or the plain softmax-CCE.  Each in
         its training form (dlogits in place, scaled for the mean over the global batch) or its evaluation form
-        (probabilities in place, gscale 0): the same objective in both -- keras smooths the evaluation loss too."""
+        (probabilities in place, gscale 0): the same objective in both -- keras smooths the evaluation loss too.
+        Distillation is a training objective only: its launch exists in the training form, and the evaluation form of a
+        distilling model is the plain one."""
         be, n = self.be, T * B
         probs, dlogits = (None, self.logits) if want_grad else (self.logits, None)
         gscale = self._head_gscale(n) if want_grad else 0.0
@@ -1238,6 +1385,11 @@ class ModelBase:
         elif self._token_weights_on():
             be.softmax_cce_weighted(self.logits, self.tgt, self.cw_dev, probs, self.loss_row, self.corr_row, dlogits, n,
                                     self.V, self.ldV, gscale, self.focal_gamma, self.loss_normalise == "weights")
+        elif want_grad and self._distill_on():
+            # the training form only: test_step reports the plain cross-entropy.  train_step ran the teacher (_teach)
+            d, t = self.distillation, self.teacher
+            be.softmax_cce_distill(self.logits, t.logits, self.tgt, self.loss_row, self.kl_row, self.corr_row, dlogits, n,
+                                   self.V, self.ldV, t.ldV, gscale, d.alpha, d.temperature)
         else:
             be.softmax_cce(self.logits, self.tgt, probs, self.loss_row, self.corr_row, dlogits, n, self.V, self.ldV, gscale)
 

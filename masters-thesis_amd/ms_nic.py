@@ -13,6 +13,8 @@ from . import lc_nic
 
 
 class NIC(lc_nic.NIC):
+    SUPPORTS_DISTILLATION = False       # distillation= / set_teacher are wired for nic.NIC and lc_nic.NIC
+
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, n_subjects=2, **kw):

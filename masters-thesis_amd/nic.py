@@ -40,6 +40,7 @@ class NIC(ModelBase):
     side_head = True            # False: the head's dW stays on the main stream under use_side_streams; tools/side_bench.py
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
     SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
+    SUPPORTS_DISTILLATION = True        # CategoricalCrossentropy(distillation=) / set_teacher (ModelBase._teach)
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
@@ -247,7 +248,8 @@ class NIC(ModelBase):
         Taken by train_step where the step is the persistent chains + the gemm3 products of one process and nothing else
         writes or reads the head's buffers by position: no scheduled sampling, self-critical step, AGC, label smoothing,
         unlikelihood (its candidates are a row's earlier positions, which the compacted rows have lost), token weights /
-        focal loss / normalise="weights" (the weighted head has no row-multiplicity form), data parallel.
+        focal loss / normalise="weights" (the weighted head has no row-multiplicity form), data parallel; a distilled step
+        (train_step stages it with head_map=False: a distinct row has no teacher row to pair with).
         Everything else (test_step, decode, the per-step LSTM kernels, other backends) keeps the position-ordered
         buffers."""
         be = self.be
@@ -432,6 +434,8 @@ class NIC(ModelBase):
         else:
             self._head_loss(B, T, want_grad)
         self._sum2(self.loss_row, self.met[0:1], self.corr_row, self.met[1:2], n, 1.0 / n)
+        if want_grad and self._distill_on():
+            self._distill_metric(n)
 
     # ------------------------------------------------------------------ backward
     def _backward(self, B, T):
@@ -665,11 +669,16 @@ class NIC(ModelBase):
         if self.self_critical is not None:
             return self.train_step_scst(data)
         self._sync_accum()
+        distill = self._distill_begin()
         # a micro-step of an accumulation window stages as the generic data-parallel step does: the forward does not ride in
-        # the staging launch and the head keeps its position-ordered rows
-        plain = self.grad_sync is None and self._accum_k() is None
+        # the staging launch and the head keeps its position-ordered rows; so does a distilled step (the staging launch's
+        # encoder forward needs the row map beside it)
+        plain = self.grad_sync is None and self._accum_k() is None and not distill
         B, T = self._stage_batch(data[0], data[1], self.N, head_map=plain, fwd=plain, corrupt=True)
         self._ss_refuse(T)
+        if distill:
+            self._teach(data, B, T)
+            self._distill_bufs(B, T)        # behind it: the teacher may just have rebuilt its buffers
         self._sync_lr()
         self._enc_grad_stale = None
         ring = False
@@ -680,7 +689,7 @@ class NIC(ModelBase):
         if self.grad_sync is None:      # replayed as a launch plan or a hipGraph: ModelBase._step_runner
             compact = self._route.head_map_fresh        # the staging launch built the head's row map
             staged = self._route.stage_fwd_done         # ... and ran the encoder forward: the step leaves it out
-            key = ("train", B, T, "compact") if compact else ("train", B, T)
+            key = ("train", B, T, "compact") if compact else ("train", B, T, "distill") if distill else ("train", B, T)
             seen = self._plan_staged
             if self._graphs.get(key) is not None and seen.get(key) != staged:
                 del self._graphs[key]       # recorded with / without the forward (the entry refuses by alignment): start over
@@ -696,7 +705,8 @@ class NIC(ModelBase):
             self._train_step_dp(B, T, lambda: self._train_graph(B, T), self._update_graph)
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
-        return self._lr_metric(self._metrics_from(m, loss=0, L2=2, accuracy=1))
+        kl = dict(distill_kl=self.DISTILL_KL) if distill else {}
+        return self._lr_metric(self._metrics_from(m, loss=0, L2=2, accuracy=1, **kl))
 
     # ------------------------------------------------------------------ self-critical sequence training
     def _scst_bufs(self, B, T):

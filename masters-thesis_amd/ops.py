@@ -337,6 +337,15 @@ class HipBackend:
                    _p(probs), _p(loss_row), _p(correct_row), _p(dlogits), rows, V, ld, gscale, float(gamma), int(normalise),
                    self._s())
 
+    def softmax_cce_distill(self, logits, teacher, target, loss_row, kl_row, correct_row, dlogits, rows, V, ld, ld_teacher,
+                            gscale, alpha, temperature):
+        """the head mixed with knowledge distillation in the same single launch: (1 - alpha) ce + alpha t^2 kl(softmax(teacher
+        / t) || softmax(logits / t)) per row, kl_row the unscaled kl (tnt_softmax_cce_distill_f32; definition in
+        include/tnt_hip.h)"""
+        self._call(self.lib.tnt_softmax_cce_distill_f32, "tnt_softmax_cce_distill_f32", _p(logits), _p(teacher), _p(target),
+                   _p(loss_row), _p(kl_row), _p(correct_row), _p(dlogits), rows, V, ld, ld_teacher, gscale, float(alpha),
+                   float(temperature), self._s())
+
     def softmax_cce_unlikely(self, logits, target, probs, loss_row, correct_row, dlogits, B, T, V, ld, gscale, alpha):
         """the head with token-level unlikelihood over each caption's own prefix in the same single launch: rows = T * B,
         t-major (tnt_softmax_cce_unlikely_f32; definition in include/tnt_hip.h)"""

@@ -364,10 +364,16 @@ class CategoricalCrossentropy:
     ``class_weight={0: 0}`` the mean over the non-padding tokens, and ``accuracy`` the accuracy over them).  One
     tnt_softmax_cce_weighted_f32 launch in place of tnt_softmax_cce_f32 (definition in include/tnt_hip.h), in training
     and evaluation.  Not together with ``label_smoothing`` or ``unlikelihood``; ``model.set_class_weight`` replaces the
-    weights of a compiled model."""
+    weights of a compiled model.
+
+    ``distillation`` (an ``optimizers.Distillation``; Hinton et al. 2015): the training loss of every position becomes
+    (1 - alpha) ce + alpha t^2 KL(softmax(teacher / t) || softmax(student / t)) against the logits of the frozen model
+    given to ``model.set_teacher``, from one tnt_softmax_cce_distill_f32 launch in place of tnt_softmax_cce_f32
+    (definition in include/tnt_hip.h); train_step also reports ``distill_kl``, the mean unscaled KL.  test_step stays
+    the plain cross-entropy.  Not together with any of the settings above."""
 
     def __init__(self, from_logits=False, reduction="none", label_smoothing=0.0, unlikelihood=0.0, class_weight=None,
-                 focal_gamma=0.0, normalise="count"):
+                 focal_gamma=0.0, normalise="count", distillation=None):
         if from_logits:
             raise NotImplementedError("the reference path uses from_logits=False")
         self.label_smoothing = check_label_smoothing(label_smoothing)
@@ -375,6 +381,7 @@ class CategoricalCrossentropy:
         self.class_weight = class_weight if class_weight is None else check_class_weight(class_weight)
         self.focal_gamma = check_focal_gamma(focal_gamma)
         self.normalise = check_normalise(normalise)
+        self.distillation = check_distillation(distillation)
         self.from_logits, self.reduction = from_logits, reduction
 
 
@@ -406,6 +413,62 @@ class UniformClassWeight:
 
     def __hash__(self):
         return hash(("UniformClassWeight", self.value))
+
+
+class Distillation:
+    """Knowledge distillation (Hinton et al. 2015) as a setting of the compile loss:
+    ``CategoricalCrossentropy(distillation=Distillation(alpha, temperature))``.  ``alpha`` in [0, 1] weighs the teacher's
+    term against the ground truth's, ``temperature`` > 0 softens both distributions; alpha = 0 is the plain loss."""
+
+    def __init__(self, alpha=0.5, temperature=2.0):
+        self.alpha = _check_distill_number("alpha", alpha, lambda v: 0.0 <= v <= 1.0, "in [0, 1]")
+        self.temperature = _check_distill_number("temperature", temperature, lambda v: 0.0 < v < float("inf"),
+                                                 "finite and > 0")
+
+    @property
+    def neutral(self):
+        return self.alpha == 0.0
+
+    def __eq__(self, other):
+        return isinstance(other, Distillation) and (other.alpha, other.temperature) == (self.alpha, self.temperature)
+
+    def __hash__(self):
+        return hash(("Distillation", self.alpha, self.temperature))
+
+    def __repr__(self):
+        return f"Distillation(alpha={self.alpha!r}, temperature={self.temperature!r})"
+
+
+def _check_distill_number(name, v, ok, rule):
+    """the value as a float; ValueError for a bool, a str, anything float() refuses, NaN, or a value outside the rule"""
+    if isinstance(v, (bool, str)):
+        raise ValueError(f"distillation {name} must be a number {rule}, got {v!r}")
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"distillation {name} must be a number {rule}, got {v!r}") from None
+    if not ok(f):                                  # NaN fails every compare
+        raise ValueError(f"distillation {name} must be {rule}, got {v!r}")
+    return f
+
+
+def check_distillation(d):
+    """None, a Distillation, or an ``{alpha: , temperature: }`` mapping (the config key) -> None or a Distillation"""
+    if d is None or isinstance(d, Distillation):
+        return d
+    if isinstance(d, dict):
+        extra = set(d) - {"alpha", "temperature"}
+        if extra:
+            raise ValueError(f"distillation takes the keys alpha and temperature, got {sorted(map(str, extra))}")
+        return Distillation(**d)
+    raise ValueError(f"distillation must be an optimizers.Distillation or None, got {d!r}")
+
+
+def loss_distillation(loss):
+    """distillation of a compile() loss argument: None, an object without the attribute, or a neutral descriptor
+    (alpha == 0) means None"""
+    d = check_distillation(getattr(loss, "distillation", None) if loss is not None else None)
+    return None if d is None or d.neutral else d
 
 
 def check_label_smoothing(eps):
