@@ -1247,6 +1247,72 @@ int32_t tnt_dense_dw_adam_fin_gclip_f32(const float* x, const float* dpre, float
                                         const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
                                         const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx,
                                         const float* gsq, const float* lr, float wd, void* stream);
+/* ---- per-variable learning-rate multipliers and frozen variables (fine-tuning: keras `layer.trainable = False`, and
+ * discriminative learning rates) inside the update launches.  seg_lrm holds one float per variable, indexed like seg_l2:
+ * mul_s >= 0, finite.  With the current rates lr and lr_t of the plain entries one update of variable s does
+ *     g, the clip scale, m, v as in the plain entry                (mul_s enters neither a norm nor the moments)
+ *     theta' = (theta - ((mul_s * lr) * wd_s) * theta) - (mul_s * lr_t) * m / (sqrt(v) + eps)           Adam
+ *     theta' = (theta - ((mul_s * lr) * wd_s) * theta) + (mu * mom - (mul_s * lr) * g)                  SGD
+ * mul_s * lr and mul_s * lr_t are float32 products formed once per workgroup, so mul_s == 1 leaves the update bit for bit
+ * what the entry without the table computes.  mul_s == 0 is a FROZEN variable: the workgroups of its spans issue no load
+ * and no store of theta, m, v (mom) or grad -- the three stay bit-unchanged, and grad may hold anything, non-finite values
+ * included.  The branch is uniform per workgroup.  Frozen variables are excluded by selection, never by a product with 0:
+ *     tnt_span_sqnorm_lrmul_f32 / tnt_seg_sqnorm_lrmul_f32   (tnt_span_sqnorm_lr_f32 / tnt_span_sqnorm_f32, tnt_seg_sqnorm_f32)
+ *         do not read a frozen variable's gradient: its slot partial[2 k] (and sq[s]) is 0; sum theta^2 and with it the L2
+ *         metric are formed as for any variable.  adam_t / lr / lr_t all NULL: no lr job (tnt_span_sqnorm_f32's launch)
+ *     tnt_global_sqnorm_lrmul_f32   (tnt_global_sqnorm_f32)
+ *         G is the sum over the variables with mul_s != 0 in the same fixed order (a frozen variable's term is the + 0 of a
+ *         slot behind the last variable; nothing of it is loaded).  A multiplier other than 0 does not change G
+ *     tnt_adam_fin_lrmul_f32   (tnt_adam_fin_f32)      seg_lrm, gsq, seg_wd       a frozen span's workgroup still arrives: the
+ *         finalize work, the counters' tick and the metrics ring are those of the plain entry, once per launch
+ *     tnt_adam_lrmul_f32       (tnt_adam_ring_f32)     seg_lrm, gsq, lr, seg_wd
+ *     tnt_sgd_lrmul_f32        (tnt_sgd_f32)           seg_lrm, gsq, seg_wd       with seg_wd, lr_dev must be given
+ *     tnt_dense_dw_adam_lrmul_f32, tnt_dense_dw_adam_fin_lrmul_f32   (tnt_dense_dw_adam_f32 / _fin_f32)   lrm, gsq, lr, wd
+ *         the encoder's fused update takes its one variable's multiplier as the scalar lrm, as it takes wd; lr NULL: no
+ *         decay.  A negative or non-finite lrm is TNT_BADARG; lrm == 0 checks the arguments and launches nothing
+ * gsq (nullable) switches global-norm clipping on as in the *_gclip_f32 entries, seg_wd (nullable) the decoupled decay as
+ * in the adamw / sgdw entries.  adam_t and the bias correction stay global: a variable unfrozen later resumes with its
+ * old moments at the global step count.  The table is read on the device when the launch runs, so a replayed launch plan
+ * or hipGraph follows an in-place rewrite.  The guard rule is the plain entries'.  TNT_BADARG, and no launch, for a null
+ * seg_lrm; the entries do not read the table on the host: a negative or non-finite entry is the caller's to refuse. */
+int32_t tnt_span_sqnorm_lrmul_f32(const float* theta, const float* grad, const int32_t* span_seg, const int64_t* span_off,
+                                  const int32_t* span_len, const float* seg_l2, float* partial, int32_t nspan,
+                                  const int64_t* adam_t, const float* lr, float* lr_t, float beta1, float beta2,
+                                  const float* sq_override, const float* seg_lrm, void* stream);
+int32_t tnt_seg_sqnorm_lrmul_f32(const float* theta, const float* grad, const int32_t* span_seg, const int64_t* span_off,
+                                 const int32_t* span_len, const int32_t* seg_first, const float* seg_l2, float* partial,
+                                 float* sq, float* wsq, float* l2_out, int32_t nspan, int32_t nseg, const float* seg_lrm,
+                                 void* stream);
+int32_t tnt_global_sqnorm_lrmul_f32(const float* partial, const int32_t* seg_first, const float* sq, const float* sq_override,
+                                    const float* extra_part, int32_t n_extra, int32_t extra_seg, int32_t nseg, float* gsq,
+                                    const float* seg_lrm, void* stream);
+int32_t tnt_adam_lrmul_f32(float* theta, float* m, float* v, const float* grad,
+                           const int32_t* span_seg, const int64_t* span_off, const int32_t* span_len,
+                           const float* seg_l2, const float* sq, const float* sq_override,
+                           int32_t nspan, float lr_t, const float* lr_t_dev, float beta1, float beta2,
+                           float eps, float clipnorm, const uint32_t* guard, const float* met, int32_t nmet, float* ring,
+                           int32_t ring_rows, uint32_t* ring_t, const float* seg_lrm, const float* gsq, const float* lr,
+                           const float* seg_wd, void* stream);
+int32_t tnt_adam_fin_lrmul_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                               const int64_t* span_off, const int32_t* span_len, const float* sq_override, int32_t nspan,
+                               float eps, float clipnorm, const tnt_finalize_desc* fin, const float* met, int32_t nmet,
+                               float* ring, int32_t ring_rows, uint32_t* ring_t, const float* seg_lrm, const float* gsq,
+                               const float* seg_wd, void* stream);
+int32_t tnt_sgd_lrmul_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                          const int64_t* span_off, const int32_t* span_len, const float* seg_l2,
+                          const float* sq, const float* sq_override, int32_t nspan, float lr, const float* lr_dev,
+                          float momentum, float clipnorm, const uint32_t* guard, const float* seg_lrm, const float* gsq,
+                          const float* seg_wd, void* stream);
+int32_t tnt_dense_dw_adam_lrmul_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                    const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                                    float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N, int32_t E,
+                                    int32_t Bk, int32_t ldx, float lrm, const float* gsq, const float* lr, float wd,
+                                    void* stream);
+int32_t tnt_dense_dw_adam_fin_lrmul_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                        const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                        const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                        const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx, float lrm,
+                                        const float* gsq, const float* lr, float wd, void* stream);
 /* ---- adaptive gradient clipping, unit-wise (AttemptFour/Model/agc.py:20-38; call site lc_NIC.py:388) ----
  * Applied in place to the flat gradient arena before the norms / clip-by-norm / Adam: per variable v (table entry:
  * arena offset var_off, row stride var_ld, L2 lambda var_lam) and per unit = output column of a keras (in, out) kernel

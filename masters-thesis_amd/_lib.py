@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 128
+TNT_VERSION = 130
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -159,6 +159,14 @@ SIGNATURES = {
     "tnt_sgd_gclip_f32": [P, P, P, P, P, P, P, P, P, I32, F32, P, F32, F32, P, P, P, P],
     "tnt_dense_dw_adam_gclip_f32": [P, P, P, P, P, F32, P, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, P, F32, P],
     "tnt_dense_dw_adam_fin_gclip_f32": [P, P, P, P, P, F32, P, I32, I32, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P, P, F32, P],
+    "tnt_span_sqnorm_lrmul_f32": [P, P, P, P, P, P, P, I32, P, P, P, F32, F32, P, P, P],
+    "tnt_seg_sqnorm_lrmul_f32": [P, P, P, P, P, P, P, P, P, P, P, I32, I32, P, P],
+    "tnt_global_sqnorm_lrmul_f32": [P, P, P, P, P, I32, I32, I32, P, P, P],
+    "tnt_adam_lrmul_f32": [P, P, P, P, P, P, P, P, P, P, I32, F32, P, F32, F32, F32, F32, P, P, I32, P, I32, P, P, P, P, P, P],
+    "tnt_adam_fin_lrmul_f32": [P, P, P, P, P, P, P, P, I32, F32, F32, P, P, I32, P, I32, P, P, P, P, P],
+    "tnt_sgd_lrmul_f32": [P, P, P, P, P, P, P, P, P, I32, F32, P, F32, F32, P, P, P, P, P],
+    "tnt_dense_dw_adam_lrmul_f32": [P, P, P, P, P, F32, P, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, F32, P, P, F32, P],
+    "tnt_dense_dw_adam_fin_lrmul_f32": [P, P, P, P, P, F32, P, I32, I32, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, F32, P, P, F32, P],
     "tnt_agc_f32": [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, F32, F32, P],
     "tnt_colsq_f32": [P, P, I32, I32, I32, P],
     "tnt_step_tick": [P, P, P, P, F32, F32, P, P],

@@ -100,5 +100,8 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
                                    focal_gamma=config.get("focal_gamma", 0.0),
                                    normalise=config.get("loss_normalise", "count"),
                                    distillation=config.get("distillation"))
-    model.compile(build_optimizer(config), loss, run_eagerly=True)
+    # freeze (a list of layer / variable names) and lr_multipliers ({name: multiplier}): optional keys of this library's,
+    # the fine-tuning recipe (ModelBase.freeze / set_lr_multipliers); compile validates the names
+    model.compile(build_optimizer(config), loss, run_eagerly=True, freeze=config.get("freeze"),
+                  lr_multipliers=config.get("lr_multipliers"))
     return model

@@ -318,6 +318,12 @@ struct DwArgs {
   // tnt_global_sqnorm_f32 wrote and clipnorm the global threshold; sq_override / fin_partial are not read.  (No field of
   // its own: the struct is the kernel's argument block, and growing it moves the words behind it in every instantiation.)
 };
+// EPI 2 with LM (tnt_dense_dw_adam_lrmul_f32 / _fin_lrmul_f32): the one variable's learning-rate multiplier as a scalar
+// behind the block -- the step is lrm * lr_t, the decay (lrm * lr * wd) * theta.  A kernel templated on its argument type:
+// with a plain DwArgs the multiplier folds away and the instantiation is the one it was.  lrm == 0 (frozen) is no launch.
+struct DwArgsLM : DwArgs { float lrm; };
+__device__ __forceinline__ float dw_lrm(const DwArgs&) { return 1.f; }
+__device__ __forceinline__ float dw_lrm(const DwArgsLM& a) { return a.lrm; }
 
 // PERM (every wave has all its TPW tiles, TPW = 2 or 4): MFMA column n of tile j is output column TPW n + j of the
 // wave's 16 TPW columns, so a lane's TPW results of one row are adjacent and leave as ONE dwordx2/x4 store covering
@@ -332,8 +338,10 @@ struct DwArgs {
 //      stored -- 24 bytes per parameter instead of 4 (dW write) + 8 (norm pass) + 28 (Adam).
 //      WD: the step is taken from theta - (lr * wd) * theta (decoupled weight decay, tnt_decayed in tnt_fin.h).
 //      GC: the clip scale is c / max(sqrt(gsq[0]), c), one norm over all variables (global-norm clipping, optim.hip).
-template <int TPW, bool PERM, int EPI = 0, bool NTM = false, bool WD = false, bool GC = false>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
-__global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
+template <int TPW, bool PERM, int EPI = 0, bool NTM = false, bool WD = false, bool GC = false, class ARGS = DwArgs>   // 16-column tiles per wave; a workgroup covers 8 * TPW * 16 columns (blockIdx.y picks the group); NTM: non-temporal moments
+__global__ __launch_bounds__(512) void dense_dw_skinny_kernel(ARGS a) {
+  constexpr bool LM = std::is_same<ARGS, DwArgsLM>::value;
+  static_assert(!LM || EPI == 2, "the multiplier belongs to the fused update");
   static_assert(EPI == 0 || (PERM && TPW == 4), "fused epilogues use the vector row layout");
   static_assert(!WD || EPI == 2, "the decay belongs to the fused update");
   static_assert(!GC || EPI == 2, "the global clip belongs to the fused update");
@@ -452,8 +460,8 @@ __global__ __launch_bounds__(512) void dense_dw_skinny_kernel(DwArgs a) {
       if (a.sq_override && a.sq_override[0] >= 0.f) sqv = a.sq_override[0];
       cs = a.clipnorm / fmaxf(sqrtf(sqv), a.clipnorm);
     }
-    lr_t = a.lr_t_dev[0];
-    if (WD) dk = a.lr_dev[0] * a.wd;
+    lr_t = LM ? dw_lrm(a) * a.lr_t_dev[0] : a.lr_t_dev[0];
+    if (WD) dk = (LM ? dw_lrm(a) * a.lr_dev[0] : a.lr_dev[0]) * a.wd;
   }
   __syncthreads();
   for (; s < nstrip; s += gridDim.x, cur ^= 1) {
@@ -1040,6 +1048,31 @@ static int32_t dw_adam_launch(const float* x, const float* dpre, float* theta, f
   return 0;
 }
 
+// the LM forms: the same eight instantiations of EPI 2 on DwArgsLM
+static int32_t dw_adam_lrmul_launch(const float* x, const float* dpre, float* theta, float* m, float* v, float l2, const float* sq,
+                                    const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                    const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                    const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx, float lrm,
+                                    const float* gsq, const float* lr, float wd, void* stream) {
+  const int nstrip = (N + DW_MS - 1) / DW_MS, grid = nstrip < 256 ? nstrip : 256;
+  DwArgsLM a{};
+  a.x = x; a.dpre = dpre; a.N = N; a.E = E; a.Bk = Bk; a.ldx = ldx;
+  a.theta = theta; a.m = m; a.v = v; a.lam2 = 2.f * l2; a.sq = gsq ? gsq : sq; a.sq_override = sq_override; a.lr_t_dev = lr_t_dev;
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.guard = guard;
+  a.fin_partial = partial; a.fin_k0 = k0; a.fin_k1 = k1;
+  a.lr_dev = lr; a.wd = wd; a.lrm = lrm;
+  using Kern = void (*)(DwArgsLM);
+  static const Kern k[2][2][2] = {
+      {{dense_dw_skinny_kernel<4, true, 2, false, false, false, DwArgsLM>, dense_dw_skinny_kernel<4, true, 2, true, false, false, DwArgsLM>},
+       {dense_dw_skinny_kernel<4, true, 2, false, true, false, DwArgsLM>, dense_dw_skinny_kernel<4, true, 2, true, true, false, DwArgsLM>}},
+      {{dense_dw_skinny_kernel<4, true, 2, false, false, true, DwArgsLM>, dense_dw_skinny_kernel<4, true, 2, true, false, true, DwArgsLM>},
+       {dense_dw_skinny_kernel<4, true, 2, false, true, true, DwArgsLM>, dense_dw_skinny_kernel<4, true, 2, true, true, true, DwArgsLM>}}};
+  hipLaunchKernelGGL(k[gsq != nullptr][lr != nullptr][tnt_stream_policy_nt()], dim3(grid, E / 512), dim3(512), 0,
+                     tnt_stream(stream), a);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
 static bool dw_wd_ok(const float* lr, float wd) { return lr != nullptr && wd >= 0.f && wd <= 3.4028234e38f; }   // NaN fails wd >= 0
 
 extern "C" int32_t tnt_dense_dw_adam_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
@@ -1118,6 +1151,43 @@ extern "C" int32_t tnt_dense_dw_adam_fin_gclip_f32(const float* x, const float* 
   if (!tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
   return dw_adam_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, guard,
                         N, E, Bk, ldx, lr, lr ? wd : 0.f, stream, gsq);
+}
+
+// The multiplier forms (definition: tnt_adam_fin_lrmul_f32 in include/tnt_hip.h): the global-clip forms' arguments with the
+// one variable's multiplier `lrm` in front of gsq, and gsq nullable (NULL: per-variable clipping as the plain entries do it).
+// lrm must be a finite float >= 0; lrm == 0 (a frozen variable) checks the arguments and launches nothing.
+static bool dw_lrm_ok(float lrm) { return lrm >= 0.f && lrm <= 3.4028234e38f; }     // NaN fails lrm >= 0
+
+extern "C" int32_t tnt_dense_dw_adam_lrmul_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                               const float* sq, const float* sq_override, const float* lr_t_dev, float beta1,
+                                               float beta2, float eps, float clipnorm, const uint32_t* guard, int32_t N,
+                                               int32_t E, int32_t Bk, int32_t ldx, float lrm, const float* gsq, const float* lr,
+                                               float wd, void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || sq == nullptr)
+    return TNT_BADARG(3);
+  if (lr != nullptr && !dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  if (gsq != nullptr && !tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (!dw_lrm_ok(lrm)) return TNT_BADARG(23);
+  if (lrm == 0.f) return 0;
+  return dw_adam_lrmul_launch(x, dpre, theta, m, v, l2, sq, nullptr, 0, 0, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm,
+                              guard, N, E, Bk, ldx, lrm, gsq, lr, lr ? wd : 0.f, stream);
+}
+
+extern "C" int32_t tnt_dense_dw_adam_fin_lrmul_f32(const float* x, const float* dpre, float* theta, float* m, float* v, float l2,
+                                                   const float* partial, int32_t k0, int32_t k1, const float* sq_override,
+                                                   const float* lr_t_dev, float beta1, float beta2, float eps, float clipnorm,
+                                                   const uint32_t* guard, int32_t N, int32_t E, int32_t Bk, int32_t ldx,
+                                                   float lrm, const float* gsq, const float* lr, float wd, void* stream) {
+  if (int32_t rc = dw_fused_check(x, dpre, N, E, Bk, ldx)) return rc;
+  if (!tnt_aligned16(theta) || !tnt_aligned16(m) || !tnt_aligned16(v) || lr_t_dev == nullptr || partial == nullptr || k0 < 0 || k1 <= k0)
+    return TNT_BADARG(3);
+  if (lr != nullptr && !dw_wd_ok(lr, wd)) return TNT_BADARG(4);
+  if (gsq != nullptr && !tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (!dw_lrm_ok(lrm)) return TNT_BADARG(23);
+  if (lrm == 0.f) return 0;
+  return dw_adam_lrmul_launch(x, dpre, theta, m, v, l2, nullptr, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps,
+                              clipnorm, guard, N, E, Bk, ldx, lrm, gsq, lr, lr ? wd : 0.f, stream);
 }
 
 extern "C" int32_t tnt_block_dense_dx_f32(const float* dpre, const float* W, float* dx, int32_t B, int32_t R,

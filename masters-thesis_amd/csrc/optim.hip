@@ -10,12 +10,15 @@
 // the host builds the span table once.  Norms are reduced span -> segment in fixed order.
 #include "tnt_common.h"
 #include "tnt_fin.h"
+#include <type_traits>
 
 namespace {
 
 struct LrJob { const int64_t* adam_t; const float* lr; float* lr_t; float b1, b2; const float* ovr; };
 
-__global__ __launch_bounds__(256) void span_sqnorm_kernel(const float* theta, const float* grad, SpanTab t,
+// TAB = SpanTabLM (tnt_span_sqnorm_lrmul_f32 / tnt_seg_sqnorm_lrmul_f32): a frozen variable's gradient is not read
+template <class TAB = SpanTab>
+__global__ __launch_bounds__(256) void span_sqnorm_kernel(const float* theta, const float* grad, TAB t,
                                                           float* partial, int nspan, LrJob lj) {
   __shared__ float s0[4], s1[4];
   const int sp = blockIdx.x;
@@ -23,7 +26,7 @@ __global__ __launch_bounds__(256) void span_sqnorm_kernel(const float* theta, co
   // update: tnt_adam_fin_f32), one thread of the launch, beside the norms
   if (lj.lr_t != nullptr && sp == 0 && threadIdx.x == 255) lj.lr_t[0] = tnt_adam_lr_t(lj.adam_t, lj.lr, lj.b1, lj.b2);
   if (sp >= nspan) return;
-  tnt_span_norm(theta, grad, t, sp, partial, lj.ovr, s0, s1);
+  tnt_span_norm(theta, grad, t, sp, partial, lj.ovr, s0, s1, tnt_lrm(t));
 }
 
 // one wave per segment: lanes stride over the segment's spans, then a fixed shuffle tree
@@ -68,20 +71,28 @@ struct GsqArgs {
   const float* partial; const int32_t* seg_first; const float* sq; const float* sq_override; const float* extra_part;
   int n_extra, extra_seg, nseg; float* gsq;
 };
+// tnt_global_sqnorm_lrmul_f32: the frozen variables (seg_lrm[s] == 0) are left out by selection -- nothing of theirs is
+// loaded, their term is the + 0 of a slot behind the last variable -- in the same order; a multiplier other than 0 does
+// not enter the norm
+struct GsqArgsLM : GsqArgs { const float* seg_lrm; };
+__device__ __forceinline__ const float* gsq_lrm(const GsqArgs&) { return nullptr; }
+__device__ __forceinline__ const float* gsq_lrm(const GsqArgsLM& a) { return a.seg_lrm; }
 
-__global__ __launch_bounds__(256) void global_sqnorm_kernel(GsqArgs a) {
+template <class ARGS = GsqArgs>
+__global__ __launch_bounds__(256) void global_sqnorm_kernel(ARGS a) {
   __shared__ float sw[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool fin = a.partial != nullptr;
+  const float* lrm = gsq_lrm(a);
   float e = 0.f;
-  if (fin && a.n_extra > 0) {                                // every wave, in the order adam_fin_kernel's workgroups use
+  if (fin && a.n_extra > 0 && (lrm == nullptr || (a.extra_seg >= 0 && a.extra_seg < a.nseg && lrm[a.extra_seg] != 0.f))) {                               // every wave, in the order adam_fin_kernel's workgroups use
     for (int i = lane; i < a.n_extra; i += 64) e += a.extra_part[i];
     e = tnt_wave_sum(e);
   }
   float acc = 0.f;
   for (int s0 = 0; s0 < a.nseg; s0 += 256) {                 // the trip count is uniform: the waves vote inside
     const int s = s0 + tid;
-    const bool live = s < a.nseg;
+    const bool live = s < a.nseg && (lrm == nullptr || lrm[s] != 0.f);
     const float ov = live && a.sq_override ? a.sq_override[s] : -1.f;
     float q = 0.f;
     if (fin) {
@@ -123,8 +134,12 @@ struct MetRing { const float* met; float* ring; uint32_t* ring_t; int nmet, rows
 // trailing pointers are not read.
 // GC (the same four kernels): global-norm clipping, clipnorm is the threshold of the one norm over all variables and the
 // scale comes from gsq[0] (tnt_gclip_scale); sq / sq_override are not read.  Without GC the trailing gsq is not read.
-template <bool WD, bool GC = false>
-__global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
+// LM (TAB = SpanTabLM; the same three kernels, the *_lrmul_f32 entries): per-variable learning-rate multipliers, mul =
+// seg_lrm[seg].  The step is mul * lr_t (SGD: mul * lr) and the decay (mul * lr * wd) * theta; mul == 1 gives the plain
+// instantiation's bits.  A workgroup whose span belongs to a frozen variable (mul == 0) loads and stores nothing of theta,
+// m, v and grad: the branch is uniform per workgroup (span -> segment -> multiplier are scalar loads).
+template <bool WD, bool GC = false, class TAB = SpanTab>
+__global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float* v, const float* grad, TAB t,
                                                    const float* sq, const float* sq_override, int nspan, float lr_t,
                                                    const float* lr_t_dev, float b1, float b2, float eps,
                                                    float clipnorm, const uint32_t* guard, MetRing r, const float* lr_dev,
@@ -141,13 +156,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* theta, float* m, float
     else { row[r.nmet] = (float)(rt & 0xFFFFFFu); r.ring_t[0] = rt + 1u; }
   }
   if (guard && guard[0] != 0u) return;       // the step's forward pass was invalid: leave the model untouched
+  constexpr bool LM = std::is_same<TAB, SpanTabLM>::value;
+  if (LM && tnt_lrm(t)[t.span_seg[sp]] == 0.f) return;     // frozen: behind the ring job, in front of every load of the variable
   if (lr_t_dev) lr_t = lr_t_dev[0];
   const long off = t.span_off[sp];
   const int len = t.span_len[sp];
   const int seg = t.span_seg[sp];
+  const float mul = LM ? tnt_lrm(t)[seg] : 1.f;
+  if (LM) lr_t *= mul;
   const float lam2 = 2.f * t.seg_l2[seg];
   const float cs = GC ? tnt_gclip_scale(gsq, clipnorm) : clip_scale(sq, sq_override, seg, clipnorm);
-  const float dk = WD ? lr_dev[0] * seg_wd[seg] : 0.f;
+  const float dk = WD ? (LM ? mul * lr_dev[0] : lr_dev[0]) * seg_wd[seg] : 0.f;
   const float ob1 = 1.f - b1, ob2 = 1.f - b2;
   const int len4 = len & ~3;
   for (int i = threadIdx.x * 4; i < len4; i += 1024) {
@@ -213,19 +232,24 @@ __device__ __forceinline__ void fin_arrive_and_tick(const FinArgs& f, unsigned t
 
 constexpr int AF_U = 4;          // rounds of 1024 elements in flight per span workgroup (tnt_adam_fin_f32)
 
-template <bool NT, bool WD, bool GC = false>
-__global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, float* v, const float* grad, SpanTab t,
+// LM: a frozen span's workgroup skips the update and still arrives below -- the finalize work, the counters' tick and the
+// metrics ring wait for every workgroup of the launch.  The side workgroup files every variable's norms and the L2 metric as
+// ever (a frozen variable's sq slot is the 0 its norm launch left, its L2 term stays).
+template <bool NT, bool WD, bool GC = false, class TAB = SpanTab>
+__global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, float* v, const float* grad, TAB t,
                                                        const float* sq_override, int nspan, float eps, float clipnorm,
                                                        FinArgs f, MetRing r, const float* gsq) {
   // workgroup 0 is the side workgroup: its work is a chain of dependent loads (~8 us end to end), so it is dispatched FIRST
   // and runs beside the whole update instead of hanging off its last round
   const int sp = (int)blockIdx.x - 1, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool bad = f.guard && f.guard[0] != 0u;            // the step's forward pass was invalid: leave the model untouched
+  constexpr bool LM = std::is_same<TAB, SpanTabLM>::value;
   if (sp >= 0) {
-    if (!bad) {
+    if (!bad && !(LM && tnt_lrm(t)[t.span_seg[sp]] == 0.f)) {    // uniform: the workgroup's one span, scalar loads
       const long off = t.span_off[sp];
       const int len = t.span_len[sp];
       const int seg = t.span_seg[sp];
+      const float mul = LM ? tnt_lrm(t)[seg] : 1.f;
       const int len4 = len & ~3;
       // The span's operands are read AF_U rounds at a time (AF_U x 4 x 16 bytes per lane in flight): with one round per
       // trip the launch is bound by concurrency x latency, not by HBM (3.4 workgroups per CU x 4 KB per wave in flight
@@ -245,9 +269,9 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
         }
       };
       load(tid * 4);
-      const float lr_t = f.lr_t[0];                        // written by the norm launch in front of this one (its "lr job")
+      const float lr_t = LM ? mul * f.lr_t[0] : f.lr_t[0]; // written by the norm launch in front of this one (its "lr job")
       const float lam2 = 2.f * f.seg_l2[seg];
-      const float dk = WD ? f.lr[0] * f.seg_wd[seg] : 0.f; // one uniform scalar: the AF_U x 4 float4 in flight are untouched
+      const float dk = WD ? (LM ? mul * f.lr[0] : f.lr[0]) * f.seg_wd[seg] : 0.f; // one uniform scalar: the AF_U x 4 float4 in flight are untouched
       float cs = 1.f;
       if (GC) {
         cs = tnt_gclip_scale(gsq, clipnorm);               // one word in the chain's place: nothing depends on the variable
@@ -354,18 +378,21 @@ __global__ __launch_bounds__(256) void adam_fin_kernel(float* theta, float* m, f
   if (tid == 0) fin_arrive_and_tick(f, (unsigned)nspan + 1u);
 }
 
-template <bool WD, bool GC = false>
-__global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, const float* grad, SpanTab t,
+template <bool WD, bool GC = false, class TAB = SpanTab>
+__global__ __launch_bounds__(256) void sgd_kernel(float* theta, float* mom, const float* grad, TAB t,
                                                   const float* sq, const float* sq_override, int nspan, float lr,
                                                   const float* lr_dev, float momentum, float clipnorm,
                                                   const uint32_t* guard, const float* seg_wd, const float* gsq) {
   const int sp = blockIdx.x;
   if (sp >= nspan) return;
   if (guard && guard[0] != 0u) return;
+  constexpr bool LM = std::is_same<TAB, SpanTabLM>::value;
+  if (LM && tnt_lrm(t)[t.span_seg[sp]] == 0.f) return;     // frozen: nothing of the variable is loaded or stored
   if (lr_dev) lr = lr_dev[0];
   const long off = t.span_off[sp];
   const int len = t.span_len[sp];
   const int seg = t.span_seg[sp];
+  if (LM) lr *= tnt_lrm(t)[seg];
   const float lam2 = 2.f * t.seg_l2[seg];
   const float cs = GC ? tnt_gclip_scale(gsq, clipnorm) : clip_scale(sq, sq_override, seg, clipnorm);
   const float dk = WD ? lr * seg_wd[seg] : 0.f;
@@ -631,7 +658,7 @@ extern "C" int32_t tnt_seg_sqnorm_f32(const float* theta, const float* grad, con
   if (nspan <= 0 || nseg <= 0) return 0;
   SpanTab t{span_seg, span_off, span_len, seg_first, seg_l2};
   hipStream_t s = tnt_stream(stream);
-  hipLaunchKernelGGL(span_sqnorm_kernel, dim3(nspan), dim3(256), 0, s, theta, grad, t, partial, nspan, LrJob{});
+  hipLaunchKernelGGL(span_sqnorm_kernel<>, dim3(nspan), dim3(256), 0, s, theta, grad, t, partial, nspan, LrJob{});
   TNT_LAUNCH_CHECK();
   hipLaunchKernelGGL(seg_finalize_kernel, dim3(nseg), dim3(64), 0, s, partial, t, sq, wsq, nseg);
   TNT_LAUNCH_CHECK();
@@ -679,7 +706,7 @@ extern "C" int32_t tnt_global_sqnorm_f32(const float* partial, const int32_t* se
   if (partial != nullptr && seg_first == nullptr) return TNT_BADARG(3);
   if (partial == nullptr && (extra_part != nullptr && n_extra > 0)) return TNT_BADARG(4);   // the table form has no extra job
   GsqArgs a{partial, seg_first, sq, sq_override, extra_part, extra_part ? n_extra : 0, extra_seg, nseg, gsq};
-  hipLaunchKernelGGL(global_sqnorm_kernel, dim3(1), dim3(256), 0, tnt_stream(stream), a);
+  hipLaunchKernelGGL(global_sqnorm_kernel<>, dim3(1), dim3(256), 0, tnt_stream(stream), a);
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -810,7 +837,7 @@ extern "C" int32_t tnt_span_sqnorm_f32(const float* theta, const float* grad, co
                                        float* partial, int32_t nspan, void* stream) {
   if (nspan <= 0) return 0;
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
-  hipLaunchKernelGGL(span_sqnorm_kernel, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, grad, t, partial, nspan, LrJob{});
+  hipLaunchKernelGGL(span_sqnorm_kernel<>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, grad, t, partial, nspan, LrJob{});
   TNT_LAUNCH_CHECK();
   return 0;
 }
@@ -822,7 +849,7 @@ extern "C" int32_t tnt_span_sqnorm_lr_f32(const float* theta, const float* grad,
   if (nspan <= 0) return TNT_BADARG(8);
   if (adam_t == nullptr || lr == nullptr || lr_t == nullptr) return TNT_BADARG(9);
   SpanTab t{span_seg, span_off, span_len, nullptr, seg_l2};
-  hipLaunchKernelGGL(span_sqnorm_kernel, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, grad, t, partial, nspan,
+  hipLaunchKernelGGL(span_sqnorm_kernel<>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, grad, t, partial, nspan,
                      LrJob{adam_t, lr, lr_t, beta1, beta2, sq_override});
   TNT_LAUNCH_CHECK();
   return 0;
@@ -925,4 +952,143 @@ extern "C" int32_t tnt_adam_fin_gclip_f32(float* theta, float* m, float* v, cons
                                        nmet, ring, ring_rows, ring_t, seg_wd, gsq, stream);
   return adam_fin_launch<false, true>(theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, met,
                                       nmet, ring, ring_rows, ring_t, nullptr, gsq, stream);
+}
+
+// ---- per-variable learning-rate multipliers and frozen variables (the LM instantiations; definition in include/tnt_hip.h).
+// Each entry takes its plain counterpart's arguments, then the table and what the counterpart's other forms take: the
+// global-clip word and the decay table, both nullable.
+namespace {
+SpanTabLM span_tab_lm(const int32_t* span_seg, const int64_t* span_off, const int32_t* span_len, const int32_t* seg_first,
+                      const float* seg_l2, const float* seg_lrm) {
+  SpanTabLM t;
+  t.span_seg = span_seg; t.span_off = span_off; t.span_len = span_len; t.seg_first = seg_first; t.seg_l2 = seg_l2;
+  t.seg_lrm = seg_lrm;
+  return t;
+}
+
+template <bool WD, bool GC>
+int32_t adam_fin_lrmul_launch(float* theta, float* m, float* v, const float* grad, const SpanTabLM& t, const float* sq_override,
+                              int32_t nspan, float eps, float clipnorm, const FinArgs& f, const MetRing& r, const float* gsq,
+                              void* stream) {
+  if (tnt_stream_policy_nt())
+    hipLaunchKernelGGL((adam_fin_kernel<true, WD, GC, SpanTabLM>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v,
+                       grad, t, sq_override, nspan, eps, clipnorm, f, r, gsq);
+  else
+    hipLaunchKernelGGL((adam_fin_kernel<false, WD, GC, SpanTabLM>), dim3(nspan + 1), dim3(256), 0, tnt_stream(stream), theta, m, v,
+                       grad, t, sq_override, nspan, eps, clipnorm, f, r, gsq);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace
+
+extern "C" int32_t tnt_span_sqnorm_lrmul_f32(const float* theta, const float* grad, const int32_t* span_seg,
+                                             const int64_t* span_off, const int32_t* span_len, const float* seg_l2,
+                                             float* partial, int32_t nspan, const int64_t* adam_t, const float* lr, float* lr_t,
+                                             float beta1, float beta2, const float* sq_override, const float* seg_lrm,
+                                             void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (nspan <= 0) return lr_t != nullptr ? TNT_BADARG(8) : 0;
+  if (lr_t != nullptr && (adam_t == nullptr || lr == nullptr)) return TNT_BADARG(9);
+  hipLaunchKernelGGL(span_sqnorm_kernel<SpanTabLM>, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, grad,
+                     span_tab_lm(span_seg, span_off, span_len, nullptr, seg_l2, seg_lrm), partial, nspan,
+                     LrJob{adam_t, lr, lr_t, beta1, beta2, sq_override});
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t tnt_seg_sqnorm_lrmul_f32(const float* theta, const float* grad, const int32_t* span_seg,
+                                            const int64_t* span_off, const int32_t* span_len, const int32_t* seg_first,
+                                            const float* seg_l2, float* partial, float* sq, float* wsq, float* l2_out,
+                                            int32_t nspan, int32_t nseg, const float* seg_lrm, void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (nspan <= 0 || nseg <= 0) return 0;
+  const SpanTabLM t = span_tab_lm(span_seg, span_off, span_len, seg_first, seg_l2, seg_lrm);
+  hipStream_t s = tnt_stream(stream);
+  hipLaunchKernelGGL(span_sqnorm_kernel<SpanTabLM>, dim3(nspan), dim3(256), 0, s, theta, grad, t, partial, nspan, LrJob{});
+  TNT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(seg_finalize_kernel, dim3(nseg), dim3(64), 0, s, partial, static_cast<const SpanTab&>(t), sq, wsq, nseg);
+  TNT_LAUNCH_CHECK();
+  if (l2_out) {
+    hipLaunchKernelGGL(l2_total_kernel, dim3(1), dim3(256), 0, s, wsq, seg_l2, nseg, l2_out);
+    TNT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int32_t tnt_global_sqnorm_lrmul_f32(const float* partial, const int32_t* seg_first, const float* sq,
+                                               const float* sq_override, const float* extra_part, int32_t n_extra,
+                                               int32_t extra_seg, int32_t nseg, float* gsq, const float* seg_lrm, void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (gsq == nullptr || nseg <= 0 || n_extra < 0) return TNT_BADARG(1);
+  if ((partial == nullptr) == (sq == nullptr)) return TNT_BADARG(2);
+  if (partial != nullptr && seg_first == nullptr) return TNT_BADARG(3);
+  if (partial == nullptr && (extra_part != nullptr && n_extra > 0)) return TNT_BADARG(4);
+  GsqArgsLM a;
+  a.partial = partial; a.seg_first = seg_first; a.sq = sq; a.sq_override = sq_override; a.extra_part = extra_part;
+  a.n_extra = extra_part ? n_extra : 0; a.extra_seg = extra_seg; a.nseg = nseg; a.gsq = gsq; a.seg_lrm = seg_lrm;
+  hipLaunchKernelGGL(global_sqnorm_kernel<GsqArgsLM>, dim3(1), dim3(256), 0, tnt_stream(stream), a);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t tnt_adam_lrmul_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                      const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                      const float* sq_override, int32_t nspan, float lr_t, const float* lr_t_dev, float beta1,
+                                      float beta2, float eps, float clipnorm, const uint32_t* guard, const float* met,
+                                      int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t, const float* seg_lrm,
+                                      const float* gsq, const float* lr, const float* seg_wd, void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (gsq != nullptr && !tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (seg_wd != nullptr && lr == nullptr) return TNT_BADARG(21);
+  if (nspan <= 0) return ring ? TNT_BADARG(11) : 0;
+  if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(20);
+  const SpanTabLM t = span_tab_lm(span_seg, span_off, span_len, nullptr, seg_l2, seg_lrm);
+  const MetRing r{met, ring, ring_t, nmet, ring_rows};
+  const bool wd = seg_wd != nullptr;
+  const auto k = gsq != nullptr ? (wd ? adam_kernel<true, true, SpanTabLM> : adam_kernel<false, true, SpanTabLM>)
+                                : (wd ? adam_kernel<true, false, SpanTabLM> : adam_kernel<false, false, SpanTabLM>);
+  hipLaunchKernelGGL(k, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, m, v, grad, t, sq, sq_override, nspan, lr_t,
+                     lr_t_dev, beta1, beta2, eps, clipnorm, guard, r, wd ? lr : nullptr, seg_wd, gsq);
+  TNT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int32_t tnt_adam_fin_lrmul_f32(float* theta, float* m, float* v, const float* grad, const int32_t* span_seg,
+                                          const int64_t* span_off, const int32_t* span_len, const float* sq_override,
+                                          int32_t nspan, float eps, float clipnorm, const tnt_finalize_desc* fin,
+                                          const float* met, int32_t nmet, float* ring, int32_t ring_rows, uint32_t* ring_t,
+                                          const float* seg_lrm, const float* gsq, const float* seg_wd, void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (gsq != nullptr && !tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (nspan < 0) return TNT_BADARG(9);
+  if (ring != nullptr && (met == nullptr || ring_t == nullptr || nmet <= 0 || nmet > 62 || ring_rows <= 0)) return TNT_BADARG(13);
+  FinArgs f;
+  if (int32_t rc = fin_fill(f, fin)) return rc;
+  f.seg_wd = seg_wd;
+  const SpanTabLM t = span_tab_lm(span_seg, span_off, span_len, nullptr, nullptr, seg_lrm);
+  const MetRing r{met, ring, ring_t, nmet, ring_rows};
+  if (gsq != nullptr)
+    return seg_wd ? adam_fin_lrmul_launch<true, true>(theta, m, v, grad, t, sq_override, nspan, eps, clipnorm, f, r, gsq, stream)
+                  : adam_fin_lrmul_launch<false, true>(theta, m, v, grad, t, sq_override, nspan, eps, clipnorm, f, r, gsq, stream);
+  return seg_wd ? adam_fin_lrmul_launch<true, false>(theta, m, v, grad, t, sq_override, nspan, eps, clipnorm, f, r, nullptr, stream)
+                : adam_fin_lrmul_launch<false, false>(theta, m, v, grad, t, sq_override, nspan, eps, clipnorm, f, r, nullptr, stream);
+}
+
+extern "C" int32_t tnt_sgd_lrmul_f32(float* theta, float* mom, const float* grad, const int32_t* span_seg,
+                                     const int64_t* span_off, const int32_t* span_len, const float* seg_l2, const float* sq,
+                                     const float* sq_override, int32_t nspan, float lr, const float* lr_dev, float momentum,
+                                     float clipnorm, const uint32_t* guard, const float* seg_lrm, const float* gsq,
+                                     const float* seg_wd, void* stream) {
+  if (seg_lrm == nullptr) return TNT_BADARG(23);
+  if (gsq != nullptr && !tnt_gclip_ok(gsq, clipnorm)) return TNT_BADARG(22);
+  if (seg_wd != nullptr && lr_dev == nullptr) return TNT_BADARG(14);
+  if (nspan <= 0) return 0;
+  const SpanTabLM t = span_tab_lm(span_seg, span_off, span_len, nullptr, seg_l2, seg_lrm);
+  const bool wd = seg_wd != nullptr;
+  const auto k = gsq != nullptr ? (wd ? sgd_kernel<true, true, SpanTabLM> : sgd_kernel<false, true, SpanTabLM>)
+                                : (wd ? sgd_kernel<true, false, SpanTabLM> : sgd_kernel<false, false, SpanTabLM>);
+  hipLaunchKernelGGL(k, dim3(nspan), dim3(256), 0, tnt_stream(stream), theta, mom, grad, t, sq, sq_override, nspan, lr, lr_dev,
+                     momentum, clipnorm, guard, seg_wd, gsq);
+  TNT_LAUNCH_CHECK();
+  return 0;
 }

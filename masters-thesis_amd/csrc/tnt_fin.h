@@ -14,6 +14,15 @@ struct SpanTab {
   const float* seg_l2;         // L2 lambda per segment
 };
 
+// The span table of the LM instantiations (the *_lrmul_f32 entries): one learning-rate multiplier per segment beside it, so
+// that its kernel-argument word comes with the table's own.  A kernel templated on its table type reads it through
+// tnt_lrm(); with a plain SpanTab that is a constant null and the kernel is the one it was.
+struct SpanTabLM : SpanTab {
+  const float* seg_lrm;        // [nseg] multiplier >= 0 of each segment's learning rate; 0 = frozen
+};
+__device__ __forceinline__ const float* tnt_lrm(const SpanTab&) { return nullptr; }
+__device__ __forceinline__ const float* tnt_lrm(const SpanTabLM& t) { return t.seg_lrm; }
+
 // (sum of partial[2 k], sum of partial[2 k + 1]) over the spans k0 <= k < k1 of one variable, computed by a whole wave,
 // every lane returning the same value: up to 8 spans serially in span order, more lane-strided + the fixed shuffle tree
 // (the orders tnt_step_finalize_f32 has always used).
@@ -47,15 +56,18 @@ __device__ __forceinline__ float2 tnt_seg_sums(const float* partial, int k0, int
 //     by the previous update and re-filed by this one) needs no pass over its gradient;
 //   * sum theta^2 only feeds the L2 metric lambda * sum theta^2: without a regulariser theta is not read and the slot is 0.
 // For BASELINE config 2 that is 33 MB instead of 58 MB per step behind the norm launch (HBM-bound).
+// `lrm` (optional, the *_lrmul_f32 norm launches): the gradient of a frozen variable (lrm[seg] == 0) is not read, whatever
+// it holds -- slot 0 gets 0; sum theta^2 is formed as for any other variable (its L2 term stays in the metric).
 __device__ __forceinline__ void tnt_span_norm(const float* theta, const float* grad, const SpanTab& t, int sp, float* partial,
-                                              const float* ovr, float* s0, float* s1) {
+                                              const float* ovr, float* s0, float* s1, const float* lrm = nullptr) {
   const int tid = threadIdx.x;
   const long off = t.span_off[sp];
   const int len = t.span_len[sp];
   const int seg = t.span_seg[sp];
   const float lam2 = 2.f * t.seg_l2[seg];
   const bool need_w = ovr == nullptr || lam2 != 0.f;
-  const bool need_g = ovr == nullptr || !(ovr[seg] >= 0.f);
+  bool need_g = ovr == nullptr || !(ovr[seg] >= 0.f);
+  if (lrm != nullptr && lrm[seg] == 0.f) need_g = false;
   float q = 0.f, wq = 0.f;
   const int len4 = len & ~3;
   if (need_g && need_w) {

@@ -444,6 +444,10 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
         # compile(gradient_accumulation_steps=): the sum over micro-steps takes the all-reduce's place; the two are not combined
         raise NotImplementedError(model.GRAD_ACCUM_REFUSAL.format(what="accumulation under data parallel (dp.attach / grad_sync) "
                                                                   "is not implemented"))
+    if model._lr_mul:
+        # freeze / set_lr_multipliers: the data-parallel update launches (slices, the row-sharded encoder) take no table
+        raise NotImplementedError(model.FINETUNE_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
+                                                                "row-sharded encoder update included)"))
     if model.loss_normalise == "weights":
         # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
         raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)

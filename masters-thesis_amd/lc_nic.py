@@ -806,8 +806,13 @@ class NIC(ModelBase):
         dlog, inter, hs = self.logits, route.inter_used, route.hs_used         # (free-running: inter_used is self.inter)
         tB, r_tail = (0, 0.0) if naive else (B, self.r_out)
         dhs_done = False
+        head_frozen = self._skip_grad("time_distributed_softmax/kernel", "time_distributed_softmax/bias")
+        if head_frozen:
+            # a frozen softmax layer: its input gradient alone.  (Its bias gradient's column sums share the launch below
+            # with the nonlinear layer's Dropout' / LeakyReLU' / bias gradient, which is still needed: that launch stays)
+            self.gemm_sk(dlog, a.p("time_distributed_softmax/kernel"), self.dinter, n, H, V, ldV, ldV, H, transB=True)
         # kernel gradient and input gradient of the softmax layer, the two independent readers of dlogits: ONE launch
-        if not (self.g3_riders and self.gemm3_pair(
+        elif not (self.g3_riders and self.gemm3_pair(
                 dict(A=inter, B=dlog, C=a.g("time_distributed_softmax/kernel"), M=H, N=V, K=n, lda=H, ldb=ldV, ldc=ldV, transA=True),
                 dict(A=dlog, B=a.p("time_distributed_softmax/kernel"), C=self.dinter, M=n, N=H, K=V, lda=ldV, ldb=ldV, ldc=H,
                      transB=True))):
@@ -829,7 +834,8 @@ class NIC(ModelBase):
             else:
                 self.gemm_sk(hs, self.dinter, a.g("time_distributed_nonlinear/kernel"), U, H, n, U, H, H, transA=True)
         else:
-            be.colsum(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV, self.work)
+            if not head_frozen:         # (a launch of its own here: a frozen softmax layer has none)
+                be.colsum(dlog, a.g("time_distributed_softmax/bias"), n, V, ldV, self.work)
             if r_tail > 0:
                 be.dropout(self.dinter, self.dinter, n, H, H, B, H, 0, r_tail, sd, S_OUT, 0, ds)
             be.act_bwd(self.ipre, self.dinter, self.dinter, n * H, ACT_LEAKY, 0.2)
@@ -882,6 +888,9 @@ class NIC(ModelBase):
             self._bwd_chain_steps(B, T, Wl, Ur, W2, v)
         hprev = self.Hs[:T].view(n, U)
         gWl = a.g("lstm/kernel")
+        if self._skip_grad("lstm/kernel", "lstm/recurrent_kernel", "lstm/bias"):
+            # a frozen LSTM: none of its parameter gradients; _bwd_emb forms dtext and _bwd_front the W2 gradient alone
+            return
         if self.g3_riders and Et == U and self.gemm3_pair(
                 dict(A=hprev, B=self.dZ, C=a.g("lstm/recurrent_kernel"), M=U, N=4 * U, K=n, lda=U, ldb=4 * U, ldc=4 * U, transA=True,
                      colsum=a.g("lstm/bias"), A2=self.text, C2=gWl[D:]),
@@ -987,6 +996,10 @@ class NIC(ModelBase):
         (teacher_forcing=False): the LSTM input mask' on every step's text rows, the text Dropout' on step 0's only (the
         fed tokens have none, lc_NIC.py:217), the scatter to the fed ids."""
         be, a = self.be, self.arena
+        if self._skip_grad("emb_text/embeddings"):
+            # a frozen Embedding: dtext feeds nothing else, so neither its product nor its Dropout' nor the scatter run (where
+            # the chain's pair launch formed dtext beside the LSTM gradients, that launch stays)
+            return
         D, U, Et, V = self.D, self.U, self.Et, self.V
         n = T * B
         sd, ds = self.seed, self.drop_step
@@ -1179,6 +1192,7 @@ class NIC(ModelBase):
             raise RuntimeError("compile() the model before train_step_sam")
         self._weight_decay_refuse("train_step_sam")
         self._global_clip_refuse("train_step_sam")
+        self._finetune_refuse("train_step_sam")
         self._grad_accum_refuse("train_step_sam applies an update of its own every step")
         if not self.teacher_forcing:
             raise NotImplementedError("train_step_sam is a teacher-forced step (lc_NIC.py:713-838): not built for "

@@ -908,6 +908,25 @@ class _LayerView:
         for w, arr in zip(self.weight_names, weights):
             self.model.set_weight(f"{self.name}/{w}", arr)
 
+    @property
+    def trainable(self):
+        """keras's layer.trainable: False when every variable of the layer is frozen.  Assignable: False freezes the
+        layer (model.freeze), True puts its frozen variables back at multiplier 1."""
+        names = [n for n in self.model._finetune_vars() if n.rsplit("/", 1)[0] == self.name]
+        return not self.model._frozen(*names)
+
+    @trainable.setter
+    def trainable(self, value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"trainable must be True or False, got {value!r}")
+        names = [n for n in self.model._finetune_vars() if n.rsplit("/", 1)[0] == self.name]
+        if not names:
+            raise ValueError(f"layer {self.name} has no trainable variable")
+        if not value:
+            self.model.freeze(*names)
+        else:
+            self.model.set_lr_multipliers({n: 1.0 for n in names if self.model._lr_mul.get(n) == 0.0})
+
 
 class DeviceGuardError(RuntimeError):
     """A device-side guard tripped (today: the barrier / census guard of the persistent LSTM kernel).  The step that
@@ -1028,6 +1047,7 @@ class ModelBase:
     metric_ring = True          # False: a clone of the metrics buffer behind every step; INTEGRATION.md 4, bench.py
     sync_bn = False             # True: BatchNorm statistics over the global batch; dp.attach(sync_bn=True)
     use_seq_lstm = True         # False: the per-step LSTM kernels; INTEGRATION.md 4, disable_seq_lstm()
+    skip_frozen_work = True     # False: the gradient launches of frozen variables run as ever (the table alone freezes); tests/test_host_finetune.py
 
     # the static buffers of _ConstrainedDecode and of _ConsensusDecode / _GuidanceDecode: a dict on the instance from the first
     # such decode on (_decode_bufs).  Not made in the constructor: the tests tell "this model never ran one" by the instance
@@ -1071,6 +1091,10 @@ class ModelBase:
         self.gsq = None                     # global-norm clipping: the one float the update launches read (squared norm of the last step)
         self._gclip_host = None             # the optimizer's global_clipnorm as the recorded launches hold it (_sync_lr)
         self._gsq_filed = False             # a step has written gsq (global_grad_norm)
+        self.seg_lrm = None                 # learning-rate multipliers / frozen variables: one float per variable on the device, or None
+        self.seg_lrm_host = None            # the same table on the host
+        self._lr_mul = {}                   # variable name -> multiplier, the entries that are not 1 (set_lr_multipliers, freeze)
+        self._skip_key = None               # the frozen variables whose gradient launches the recorded steps leave out
         self.acc_grad = self.acc_sq = None  # gradient accumulation: the arena-sized accumulator and the Embedding norm's float
         self._accum_host = None             # the optimizer's gradient_accumulation_steps as the recorded launches hold it (_sync_lr)
         self._accum_j = 0                   # micro-steps of the open window that are in the accumulator
@@ -1080,6 +1104,7 @@ class ModelBase:
         self.adam_t = None                  # the device counter of applied updates; exists once the optimizer state does
         self._swapped = False               # the weight average sits in the weights (swap_weights)
         self._wd_scalar_segs = set()        # variables whose update takes its decay as a scalar argument (_wd_scalar)
+        self._lrm_scalar_segs = set()       # ... and its learning-rate multiplier (_lrm_scalar)
         self._fin_arrive = None             # arrival counters of the update launch that carries the finalize work
         self._fin_descs = {}                # its descriptors (finalize_desc), one per distinct argument set
         self._tail = StepTail()             # what a fused step's launches leave to its update (_deferring, _update_fused)
@@ -1120,8 +1145,15 @@ class ModelBase:
         self._dec_bufs = {}                 # _TokenChoice's static buffers per (rows, max_len)
 
     # ------------------------------------------------------------------ keras surface
-    def compile(self, optimizer=None, loss=None, *metrics, run_eagerly=True, **kw):
-        """model.compile(optimizer, loss_object, run_eagerly=True) -- main.py:134."""
+    def compile(self, optimizer=None, loss=None, *metrics, run_eagerly=True, freeze=None, lr_multipliers=None, **kw):
+        """model.compile(optimizer, loss_object, run_eagerly=True) -- main.py:134.  ``freeze`` (a list of layer / variable
+        names) and ``lr_multipliers`` ({name: multiplier}): the config keys of the same names, applied as model.freeze /
+        model.set_lr_multipliers apply them."""
+        if freeze is not None and (isinstance(freeze, str) or not isinstance(freeze, (list, tuple))):
+            raise ValueError(f"freeze must be a list of layer or variable names, got {freeze!r}")
+        if lr_multipliers is not None and not isinstance(lr_multipliers, dict):
+            raise ValueError(f"lr_multipliers must be a mapping name -> multiplier, got {lr_multipliers!r}")
+        mul = self._resolve_lr_multipliers(dict(lr_multipliers or {}, **{n: 0.0 for n in (freeze or ())}))
         eps = loss_label_smoothing(loss)
         if eps > 0 and not self.SUPPORTS_LABEL_SMOOTHING:
             raise NotImplementedError(f"{type(self).__name__} computes its own masked sparse loss and does not read the "
@@ -1158,7 +1190,9 @@ class ModelBase:
         self._check_global_clip(check_global_clipnorm(getattr(optimizer, "global_clipnorm", None)) is not None)
         self._check_grad_accum(check_gradient_accumulation_steps(getattr(optimizer, "gradient_accumulation_steps", None))
                                is not None, normalise=mode)
+        self._check_finetune(bool(self._merged_lr_mul(mul)), optimizer=optimizer)
         self.optimizer = optimizer if optimizer is not None else Adam()
+        self._lr_mul = self._merged_lr_mul(mul)
         self.loss = loss
         # Fixed here, not read per step: the head launch sits inside captured graphs, with its smoothing, alpha, gamma and
         # mode as arguments.  The averaging launch sits inside the same plans / graphs, and its settings are launch
@@ -1425,6 +1459,10 @@ class ModelBase:
         getattr(self.optimizer, "_optimizer", self.optimizer)._wd_built = True
         # global-norm clipping: the word tnt_global_sqnorm_f32 writes and every update launch of the step reads
         self.gsq = self._f(1)
+        # learning-rate multipliers and frozen variables: the table of what set_lr_multipliers / freeze have asked for so far
+        self._check_finetune(bool(self._lr_mul))
+        self.seg_lrm = self.seg_lrm_host = None
+        self._store_seg_lrm()
         self._gsq_filed = False
         self._gclip_host = self._gclip()
         self._check_global_clip(self._gclip_host is not None)
@@ -1524,12 +1562,14 @@ class ModelBase:
         if self._gclip() is None:
             return
         a = self.arena
+        # with a multiplier table: the form that leaves the frozen variables out
+        launch = self.be.global_sqnorm if self.seg_lrm is None else \
+            (lambda gsq, nseg, **kw: self.be.global_sqnorm_lrmul(gsq, nseg, self.seg_lrm, **kw))
         if fin_kw is None:
-            self.be.global_sqnorm(self.gsq, a.nseg, sq_override=a.sq_override, sq=a.sq)
+            launch(self.gsq, a.nseg, sq_override=a.sq_override, sq=a.sq)
         else:
             extra = {k: fin_kw[k] for k in ("extra_part", "n_extra", "extra_seg") if k in fin_kw}
-            self.be.global_sqnorm(self.gsq, a.nseg, sq_override=a.sq_override, partial=a.partial,
-                                  seg_first=a.spans.seg_first, **extra)
+            launch(self.gsq, a.nseg, sq_override=a.sq_override, partial=a.partial, seg_first=a.spans.seg_first, **extra)
         self._gsq_filed = True
 
     def global_grad_norm(self):
@@ -1539,6 +1579,156 @@ class ModelBase:
         if self.gsq is None or not self._gsq_filed:
             raise RuntimeError("global_grad_norm: no training step with global_clipnorm has run yet")
         return float(self.gsq[0]) ** 0.5
+
+    # ------------------------------------------------------------------ layer freezing and per-variable learning rates (fine-tuning)
+    FINETUNE_REFUSAL = ("layer freezing and learning-rate multipliers (freeze / set_lr_multipliers / layer.trainable) are built "
+                        "for the single-device update launches only: {what} does not apply them.  Unfreeze everything and "
+                        "clear the multipliers there, or train on one device without it")
+    FINETUNE_BATCHNORM = ("freezing a BatchNorm layer ({name}) is not implemented: keras runs a frozen BatchNorm in inference "
+                          "mode, on its moving statistics, and the training step here has no such mode.  Freeze the layers "
+                          "around it, or give it a small multiplier; LayerNorm gains and biases freeze like any variable")
+
+    def _finetune_vars(self):
+        """the names a multiplier can be given to: the variables of the arena, in its order"""
+        return list(self.arena.entries)
+
+    def _match_variables(self, name):
+        """the variables ``name`` stands for: a layer's (exact layer name), one variable (exact name), else every variable
+        whose name contains it -- exclude_from_weight_decay's var_list / var_names rule.  A name that matches nothing raises."""
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"a layer or variable name must be a non-empty string, got {name!r}")
+        names = self._finetune_vars()
+        if name in self.layers_spec:
+            hit = [n for n in names if n.rsplit("/", 1)[0] == name]
+        elif name in names:
+            hit = [name]
+        else:
+            hit = [n for n in names if name in n]
+        if not hit:
+            raise ValueError(f"{name!r} matches no layer and no trainable variable of {type(self).__name__}; the variables "
+                             f"are {names}")
+        return hit
+
+    def _resolve_lr_multipliers(self, mapping):
+        """{layer / variable name or substring: multiplier} -> {variable name: float}, validated: a finite multiplier
+        >= 0, names that match, no frozen BatchNorm.  Later keys override earlier ones where they overlap."""
+        out = {}
+        for key, mul in mapping.items():
+            if isinstance(mul, bool) or not isinstance(mul, (int, float, np.integer, np.floating)) or \
+                    not np.isfinite(mul) or mul < 0:
+                raise ValueError(f"a learning-rate multiplier must be a finite number >= 0, got {mul!r} for {key!r}")
+            for n in self._match_variables(key):
+                out[n] = float(np.float32(mul))
+        for n, mul in out.items():
+            layer = n.rsplit("/", 1)[0]
+            # a layer with moving statistics (nic.NIC(norm="layer") keeps the names and normalises per row: no BatchNorm)
+            if mul == 0.0 and getattr(self, "norm", "batch") == "batch" and \
+                    any(k.startswith(layer + "/moving_") for k in self.keras_shapes):
+                raise NotImplementedError(self.FINETUNE_BATCHNORM.format(name=layer))
+        return out
+
+    def _merged_lr_mul(self, new):
+        return {n: m for n, m in dict(self._lr_mul, **new).items() if m != 1.0}
+
+    def _check_finetune(self, on, optimizer=None):
+        """the refusals of a model with a multiplier table (compile, the optimizer-state build, set_lr_multipliers): data
+        parallel, adaptive gradient clipping and gradient accumulation; train_step_sam, dp.attach, enable_agc and the
+        accumulation check refuse on their side"""
+        if not on:
+            return
+        no = lambda what: NotImplementedError(self.FINETUNE_REFUSAL.format(what=what))
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise no("the data-parallel update (dp.attach / grad_sync, the row-sharded encoder update included)")
+        if self.agc:
+            raise no("a step with adaptive gradient clipping (enable_agc)")
+        opt = self.optimizer if optimizer is None else optimizer
+        if check_gradient_accumulation_steps(getattr(opt, "gradient_accumulation_steps", None)) is not None:
+            raise no("a step with gradient_accumulation_steps")
+
+    def _finetune_refuse(self, what):
+        if self._lr_mul:
+            raise NotImplementedError(self.FINETUNE_REFUSAL.format(what=what))
+
+    def set_lr_multipliers(self, mapping):
+        """Per-variable learning-rate multipliers: {layer name, variable name or substring: mul}, mul a finite float >= 0.
+        Adam steps the variable by mul * lr_t, SGD by mul * lr, decoupled decay by (mul * lr * wd) * theta, a schedule's rate
+        likewise; 1 is the default and restores it, 0 freezes the variable (model.freeze).  Variables not named keep what
+        they have.  On a built model the device table is written in place: the next step, a replay of a recorded plan or
+        graph included, follows it; only the first multiplier, the last one's removal and a change of which gradient
+        launches are left out record the step again."""
+        if not isinstance(mapping, dict):
+            raise ValueError(f"set_lr_multipliers takes a mapping name -> multiplier, got {mapping!r}")
+        new = self._merged_lr_mul(self._resolve_lr_multipliers(mapping))
+        self._check_finetune(bool(new))
+        self._lr_mul = new
+        if self.adam_t is not None:
+            self._store_seg_lrm()
+
+    def freeze(self, *names):
+        """Freeze layers or variables (names as set_lr_multipliers takes them): weights and optimizer slots stay
+        bit-unchanged by a training step, no decay, no L2 gradient, no share in global_clipnorm's norm; the L2 term stays
+        in the reported loss.  adam_t stays global: unfreeze resumes with the old moments at the current step count."""
+        self.set_lr_multipliers({n: 0.0 for n in names})
+
+    def unfreeze(self, *names, multiplier=1.0):
+        """Back to training, at ``multiplier`` times the learning rate.  A name that matches no frozen variable raises."""
+        for n in names:
+            if not any(self._lr_mul.get(v) == 0.0 for v in self._match_variables(n)):
+                raise ValueError(f"unfreeze: {n!r} matches no frozen variable")
+        self.set_lr_multipliers({v: multiplier for n in names for v in self._match_variables(n) if self._lr_mul.get(v) == 0.0})
+
+    def lr_multipliers(self):
+        """{variable name: multiplier} of every variable, 1.0 where none was set"""
+        return OrderedDict((n, self._lr_mul.get(n, 1.0)) for n in self._finetune_vars())
+
+    def _frozen(self, *names):
+        """every one of the variables ``names`` is frozen"""
+        return bool(names) and all(self._lr_mul.get(n) == 0.0 for n in names)
+
+    def _skip_grad(self, *names):
+        """whether the step leaves out a launch whose only outputs are the gradients of ``names``: all of them frozen
+        (skip_frozen_work = False: never -- the table alone freezes them)"""
+        return self.skip_frozen_work and self._frozen(*names)
+
+    def _store_seg_lrm(self):
+        """The device table from ``_lr_mul``: None while every multiplier is 1 (the plain launches), else one float per
+        variable, written in place where the table exists -- a recorded plan or a captured graph that holds its address
+        follows.  A change between no table and a table changes the launches and drops the recordings; so does a change of
+        the frozen set, which decides the gradient launches a step leaves out (_skip_grad)."""
+        entries = self.arena.entries
+        tab = None
+        if self._lr_mul:
+            tab = np.ones(self.arena.nseg, dtype=np.float32)
+            for n, mul in self._lr_mul.items():
+                tab[entries[n].seg] = mul
+        skip = frozenset(n for n, m in self._lr_mul.items() if m == 0.0) if self.skip_frozen_work else frozenset()
+        old = self.seg_lrm_host
+        if (tab is None) != (old is None) or skip != (self._skip_key or frozenset()):
+            self._graphs = {}
+        elif tab is not None and any(tab[s] != old[s] for s in self._lrm_scalar_segs):
+            self._graphs = {}               # a new scalar argument of the encoder's fused update
+        self._skip_key = skip
+        if tab is None:
+            self.seg_lrm = self.seg_lrm_host = None
+            return
+        if self.seg_lrm is None:
+            self.seg_lrm = torch.from_numpy(tab.copy()).to(self.device)
+        else:
+            self.seg_lrm.copy_(torch.from_numpy(tab))
+        self.seg_lrm_host = tab
+
+    def _lrm_scalar(self, seg):
+        """the multiplier of one variable as the scalar argument of the encoder's fused update"""
+        self._lrm_scalar_segs.add(seg)
+        return float(self.seg_lrm_host[seg])
+
+    def _lrm_kw(self, **decay):
+        """the optional trailing arguments of a *_lrmul launch: the global word under global_clipnorm, and ``decay`` where
+        the model decays"""
+        kw = dict(gsq=self.gsq) if self._gclip() is not None else {}
+        if self.seg_wd is not None:
+            kw.update(decay)
+        return kw
 
     # ------------------------------------------------------------------ gradient accumulation (Adam / SGD gradient_accumulation_steps=)
     GRAD_ACCUM_REFUSAL = ("gradient accumulation (gradient_accumulation_steps=) is built for the teacher-forced single-device "
@@ -1565,6 +1755,8 @@ class ModelBase:
             raise no("accumulation under data parallel (dp.attach / grad_sync) is not implemented")
         if self.agc:
             raise no("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the window's")
+        if self._lr_mul:
+            raise NotImplementedError(self.FINETUNE_REFUSAL.format(what="a step with gradient_accumulation_steps"))
         if self.scheduled_sampling is not None:
             raise no("scheduled_sampling has no accumulating step")
         if self.self_critical is not None:
@@ -1769,7 +1961,10 @@ class ModelBase:
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan, 0.0,
                 self.lr_t_dev, opt.beta_1, opt.beta_2, opt.epsilon, self._clip())
-        if self._gclip() is not None:
+        if self.seg_lrm is not None:
+            be.adam_lrmul(*args, self.seg_lrm, **self._lrm_kw(lr=self.lr_dev, seg_wd=self.seg_wd), guard=self._guard_word(),
+                          **(ring or {}))
+        elif self._gclip() is not None:
             be.adam_gclip(*args, **self._gclip_kw(lr=self.lr_dev, seg_wd=self.seg_wd), guard=self._guard_word(), **(ring or {}))
         elif self.seg_wd is None:
             be.adam(*args, guard=self._guard_word(), **(ring or {}))
@@ -1782,7 +1977,9 @@ class ModelBase:
         be, a, opt = self.be, self.arena, self.optimizer
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, self.opt_v, a.grad, seg, off, length, a.sq_override, nspan, opt.epsilon, self._clip(), desc)
-        if self._gclip() is not None:
+        if self.seg_lrm is not None:
+            be.adam_fin_lrmul(*args, self.seg_lrm, **self._lrm_kw(seg_wd=self.seg_wd), **ring)
+        elif self._gclip() is not None:
             be.adam_fin_gclip(*args, **self._gclip_kw(seg_wd=self.seg_wd), **ring)
         elif self.seg_wd is None:
             be.adam_fin(*args, **ring)
@@ -1800,7 +1997,12 @@ class ModelBase:
         norm = (a.partial, sp.first_host[e.seg], sp.first_host[e.seg + 1]) if fin else (a.sq[one],)
         args = (enc.x, enc.dpre, a.theta[sl], self.opt_m[sl], self.opt_v[sl], e.l2, *norm, a.sq_override[one], self.lr_t_dev,
                 opt.beta_1, opt.beta_2, opt.epsilon, self._clip(), enc.N, enc.E, enc.rows, enc.ldx)
-        if self._gclip() is not None:
+        if self.seg_lrm is not None:
+            # the multiplier forms take the variable's multiplier as a scalar, as the decaying forms take its decay
+            kw = self._lrm_kw(lr=self.lr_dev, wd=self._wd_scalar(e.seg) if self.seg_wd is not None else 0.0)
+            (be.dense_dw_adam_fin_lrmul if fin else be.dense_dw_adam_lrmul)(*args, self._lrm_scalar(e.seg), **kw,
+                                                                            guard=self._guard_word())
+        elif self._gclip() is not None:
             kw = self._gclip_kw(lr=self.lr_dev, wd=self._wd_scalar(e.seg) if self.seg_wd is not None else 0.0)
             (be.dense_dw_adam_fin_gclip if fin else be.dense_dw_adam_gclip)(*args, **kw, guard=self._guard_word())
         elif self.seg_wd is None:
@@ -1814,7 +2016,10 @@ class ModelBase:
         be, a, opt = self.be, self.arena, self.optimizer
         seg, off, length, nspan = spans
         args = (a.theta, self.opt_m, a.grad, seg, off, length, a.seg_l2, a.sq, a.sq_override, nspan)
-        if self._gclip() is not None:
+        if self.seg_lrm is not None:
+            be.sgd_lrmul(*args, 0.0, self.lr_dev, opt.momentum, self._clip(), self.seg_lrm, **self._lrm_kw(seg_wd=self.seg_wd),
+                         guard=self._guard_word())
+        elif self._gclip() is not None:
             be.sgd_gclip(*args, 0.0, self.lr_dev, opt.momentum, self._clip(), **self._gclip_kw(seg_wd=self.seg_wd),
                          guard=self._guard_word())
         elif self.seg_wd is None:
@@ -1877,14 +2082,25 @@ class ModelBase:
             # pass of the skinny product leaves its norm partials in the variable's span slots, a second one applies
             # clip + Adam to the strips as they leave the MFMAs (24 bytes per parameter instead of 40).
             e, g = a.entries[enc.name], enc.gram
-            if g is not None and 4 * enc.rows + g.nw2 <= s1:
+            if g is not None and 4 * enc.rows + g.nw2 <= s1 and self.seg_lrm is not None:
+                # with a multiplier table the Gram-norm launch runs alone: the span norms that ride in it would read a frozen
+                # variable's gradient, so they run in the table form of the norm launch below
+                be.dense_gram_norm(enc.dpre, g.pre, g.bias, g.gx, g.nsplit, g.w2, g.nw2, e.l2, a.partial, s1, enc.rows, enc.E)
+            elif g is not None and 4 * enc.rows + g.nw2 <= s1:
                 # norm from the forward's by-products: ||X^T D||^2 = sum (X X^T) o (D D^T), no pass over the gradient
                 # ... with the span norms of every other variable riding in the same launch
                 be.dense_gram_norm(enc.dpre, g.pre, g.bias, g.gx, g.nsplit, g.w2, g.nw2, e.l2, a.partial, s1, enc.rows, enc.E,
                                    spans=(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan),
                                    lr_job=lr_job, skip=skip)
                 return fin
-            be.dense_dw_sqnorm(enc.x, enc.dpre, a.p(enc.name), e.l2, a.partial, s1, enc.N, enc.E, enc.rows, enc.ldx)
+            else:
+                be.dense_dw_sqnorm(enc.x, enc.dpre, a.p(enc.name), e.l2, a.partial, s1, enc.N, enc.E, enc.rows, enc.ldx)
+        if self.seg_lrm is not None:
+            # the forms that do not read a frozen variable's gradient, with or without the lr job
+            fin = bool(fin and nspan > 0)
+            be.span_sqnorm_lrmul(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan, self.seg_lrm,
+                                 lr_job=lr_job if fin else None, skip=skip if fin else None)
+            return fin
         if fin and nspan > 0:
             be.span_sqnorm_lr(a.theta, a.grad, seg, off, length, a.seg_l2, a.partial[2 * s1:], nspan, *lr_job, skip=skip)
             return True
@@ -1998,6 +2214,8 @@ class ModelBase:
         writes rows of other ranks' tokens; SAM; eager paths) the dense form runs and hands its ids on as prev_ids, so
         the invariant "dtable is zero outside the rows of prev_ids" holds whichever form runs next."""
         be, a = self.be, self.arena
+        if self._skip_grad(name):       # a frozen Embedding: neither the scatter nor its un-deduplicated norm
+            return
         seg = a.entries[name].seg
         sqo = a.sq_override[seg:seg + 1]
         st = self._emb_state
@@ -2254,6 +2472,7 @@ class ModelBase:
             self._global_clip_refuse("a step with adaptive gradient clipping (enable_agc)")
             self._grad_accum_refuse("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the "
                                     "window's")
+            self._finetune_refuse("a step with adaptive gradient clipping (enable_agc)")
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
         self._graphs = {}
 
@@ -2282,8 +2501,12 @@ class ModelBase:
 
     def _norms_and_l2(self, l2_out):
         a, sp = self.arena, self.arena.spans
-        self.be.seg_sqnorm(a.theta, a.grad, sp.span_seg, sp.span_off, sp.span_len, sp.seg_first, a.seg_l2, a.partial,
-                           a.sq, a.wsq, l2_out, sp.nspan, a.nseg)
+        args = (a.theta, a.grad, sp.span_seg, sp.span_off, sp.span_len, sp.seg_first, a.seg_l2, a.partial, a.sq, a.wsq, l2_out,
+                sp.nspan, a.nseg)
+        if self.seg_lrm is not None:       # a frozen variable's gradient is not read
+            self.be.seg_sqnorm_lrmul(*args, self.seg_lrm)
+        else:
+            self.be.seg_sqnorm(*args)
 
     # ------------------------------------------------------------------ weights
     def _state_map(self):
@@ -2313,8 +2536,15 @@ class ModelBase:
     def get_gradient(self, name):
         """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
         optimizer kernels add on the fly).  Under gradient accumulation: behind a closing micro-step what the update
-        consumed, the window's mean gradient; behind any other that micro-batch's share of it (its gradient / k)."""
+        consumed, the window's mean gradient; behind any other that micro-batch's share of it (its gradient / k).
+        A frozen variable has no gradient: ValueError."""
+        self._frozen_gradient_refuse(name)
         return self._unpack(name, self.arena.g(name))
+
+    def _frozen_gradient_refuse(self, name):
+        if self._frozen(name):
+            raise ValueError(f"{name} is frozen: a frozen variable's gradient is undefined (its buffer holds whatever an "
+                             "earlier step left)")
 
     @property
     def losses(self):
@@ -2328,7 +2558,12 @@ class ModelBase:
         return [(n, self.get_weight(n)) for n in self.trainable_names()]
 
     def trainable_names(self):
-        return [n for n in self.keras_shapes if "moving_" not in n]
+        """the variables a training step updates: not the BatchNorm moving statistics, not the frozen ones"""
+        return [n for n in self.keras_shapes if "moving_" not in n and not self._frozen(n)]
+
+    def non_trainable_names(self):
+        """the rest: the frozen variables and the BatchNorm moving statistics"""
+        return [n for n in self.keras_shapes if "moving_" in n or self._frozen(n)]
 
     def get_weights_dict(self):
         return OrderedDict((n, self.get_weight(n)) for n in self.keras_shapes)
@@ -2453,6 +2688,9 @@ class ModelBase:
             n = sum(int(np.prod(self.keras_shapes[f"{layer}/{w}"])) for w in ws)
             print_fn(f"  {layer:36s} {n:>12,d}")
         print_fn(f"Total params: {self.count_params():,d}")
+        size = lambda names: int(sum(np.prod(self.keras_shapes[n]) for n in names))
+        print_fn(f"Trainable params: {size(self.trainable_names()):,d}")
+        print_fn(f"Non-trainable params: {size(self.non_trainable_names()):,d}")
 
     # ------------------------------------------------------------------ input corruption (scan_dropout=, word_dropout=)
     SUPPORTS_INPUT_CORRUPTION = False   # True on nic.NIC and lc_nic.NIC, whose train_step stages with corrupt=True

@@ -151,6 +151,7 @@ class NIC(ModelBase):
     def get_gradient(self, name):
         """Last computed gradient of a trainable (keras layout, *without* the L2 term, which the
         optimizer kernels add on the fly)."""
+        self._frozen_gradient_refuse(name)
         st = self._enc_grad_stale
         if name == "dense_img/kernel" and st is not None:
             # the fused step consumed X^T dpre inside the optimizer launches without writing it: its operands are still
@@ -166,7 +167,8 @@ class NIC(ModelBase):
         ``defer``: asked ahead of the step (_stage_fwd_args) -- whether that step will be the fused one."""
         opt = self.optimizer
         defer = self._tail.deferring if defer is None else defer
-        return bool(defer and self.dp_world == 1 and self.fuse_enc_update
+        # (a frozen encoder kernel has no update at all: with skip_frozen_work off its gradient is written like any other)
+        return bool(defer and self.dp_world == 1 and self.fuse_enc_update and not self._frozen("dense_img/kernel")
                     and opt is not None and opt.kind == "adam" and not self.agc and rows <= 64
                     and self.E % 512 == 0
                     and self.arena.entries["dense_img/kernel"].seg == 0
@@ -455,6 +457,16 @@ class NIC(ModelBase):
         dx = dict(A=dlog, B=Wo, C=self.dOut, M=T * B, N=U, K=V, lda=ldV, ldb=ldV, ldc=U, transB=True)
         route = self._route
         route.colsum_deferred = None
+        if self._skip_grad("time_distributed_softmax/kernel", "time_distributed_softmax/bias"):
+            # a frozen head: the input gradient alone -- no dW / dx pair, no column sums, now or deferred
+            if route.head_map_fresh:        # dlogits holds the `live` rows: the compacted head's own dx launch
+                self.gemm3(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True, live=self.head_live,
+                           live_mode=LIVE_ROWS_M)
+            elif not (self.g3_riders and self.gemm3(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True)):
+                self.gemm_sk(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True)
+            if join:
+                self.join()
+            return
         if route.head_map_fresh:
             # dlogits and Out hold `live` rows: dW and db sum over those (each already carries its multiplicity), dOut is
             # formed for those; one device word bounds both products
@@ -514,6 +526,11 @@ class NIC(ModelBase):
                        dout_pos=self.head_pos if route.head_map_fresh else None, pass_out_last=False)
         xin, d = route.xin_used, route.colsum_deferred      # d: the head-bias column sums _bwd_head left to this method
         route.dxin_done = False
+        if self._skip_grad("lstm/kernel", "lstm/recurrent_kernel", "lstm/bias"):
+            # a frozen LSTM: none of its three parameter gradients; _bwd_seq_front forms dXin alone
+            if d is not None:
+                be.colsum(*d, self.work2)
+            return
         riders = self.g3_riders and E == U
         one = False         # kernel, recurrent-kernel and bias gradients went out as ONE launch
         if riders:
@@ -600,6 +617,9 @@ class NIC(ModelBase):
         (all-gathered: 5 MB of betas + 128 KB per rank) and every rank computes the full global-batch
         gradient itself, instead of all-reducing the 41 MB result."""
         be, a = self.be, self.arena
+        if x_all is None and self._skip_grad("dense_img/kernel"):     # a frozen encoder kernel: no product, no fused update, no Gram norm
+            self._enc_last_fused = None
+            return
         x = self.xd if self.r_in > 0 else self.x
         rows = B
         if x_all is not None:

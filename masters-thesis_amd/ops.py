@@ -708,6 +708,64 @@ class HipBackend:
                    _p(v), l2, _p(partial), k0, k1, _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk,
                    ldx, _p(gsq), _p(lr), wd, self._s())
 
+    # ---- per-variable learning-rate multipliers and frozen variables (definition: tnt_adam_fin_lrmul_f32 in
+    # include/tnt_hip.h).  Each *_lrmul method takes its plain sibling's arguments, then the table ``seg_lrm`` (one float per
+    # variable, 0 = frozen) and, optional, the global-clip word and the decay table of the sibling's other forms
+    def span_sqnorm_lrmul(self, theta, grad, span_seg, span_off, span_len, seg_l2, partial, nspan, seg_lrm, lr_job=None,
+                          skip=None):
+        """span_sqnorm (``lr_job`` None) / span_sqnorm_lr (``lr_job`` = (adam_t, lr, lr_t, beta1, beta2)) that does not read
+        a frozen variable's gradient"""
+        adam_t, lr, lr_t, beta1, beta2 = lr_job if lr_job is not None else (None, None, None, 0.0, 0.0)
+        self._call(self.lib.tnt_span_sqnorm_lrmul_f32, "tnt_span_sqnorm_lrmul_f32", _p(theta), _p(grad), _p(span_seg),
+                   _p(span_off), _p(span_len), _p(seg_l2), _p(partial), nspan, _p(adam_t), _p(lr), _p(lr_t), beta1, beta2,
+                   _p(skip), _p(seg_lrm), self._s())
+
+    def seg_sqnorm_lrmul(self, theta, grad, span_seg, span_off, span_len, seg_first, seg_l2, partial, sq, wsq, l2_out, nspan,
+                         nseg, seg_lrm):
+        self._call(self.lib.tnt_seg_sqnorm_lrmul_f32, "tnt_seg_sqnorm_lrmul_f32", _p(theta), _p(grad), _p(span_seg),
+                   _p(span_off), _p(span_len), _p(seg_first), _p(seg_l2), _p(partial), _p(sq), _p(wsq), _p(l2_out), nspan, nseg,
+                   _p(seg_lrm), self._s())
+
+    def global_sqnorm_lrmul(self, gsq, nseg, seg_lrm, sq_override=None, partial=None, seg_first=None, extra_part=None,
+                            n_extra=0, extra_seg=-1, sq=None):
+        """global_sqnorm over the variables that are not frozen"""
+        self._call(self.lib.tnt_global_sqnorm_lrmul_f32, "tnt_global_sqnorm_lrmul_f32", _p(partial), _p(seg_first), _p(sq),
+                   _p(sq_override), _p(extra_part), n_extra, extra_seg, nseg, _p(gsq), _p(seg_lrm), self._s())
+
+    def adam_lrmul(self, theta, m, v, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr_t, lr_t_dev,
+                   beta1, beta2, eps, clipnorm, seg_lrm, gsq=None, lr=None, seg_wd=None, guard=None, met=None, ring=None,
+                   ring_t=None):
+        self._call(self.lib.tnt_adam_lrmul_f32, "tnt_adam_lrmul_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(seg_l2), _p(sq), _p(sq_override), nspan, lr_t, _p(lr_t_dev), beta1, beta2, eps, clipnorm,
+                   _p(guard), _p(met), met.numel() if met is not None else 0, _p(ring), ring.shape[0] if ring is not None else 0,
+                   _p(ring_t), _p(seg_lrm), _p(gsq), _p(lr), _p(seg_wd), self._s())
+
+    def adam_fin_lrmul(self, theta, m, v, grad, span_seg, span_off, span_len, sq_override, nspan, eps, clipnorm, fin, seg_lrm,
+                       gsq=None, seg_wd=None, met=None, ring=None, ring_t=None):
+        self._call(self.lib.tnt_adam_fin_lrmul_f32, "tnt_adam_fin_lrmul_f32", _p(theta), _p(m), _p(v), _p(grad), _p(span_seg),
+                   _p(span_off), _p(span_len), _p(sq_override), nspan, eps, clipnorm, _ct.addressof(fin), _p(met),
+                   met.numel() if met is not None else 0, _p(ring), ring.shape[0] if ring is not None else 0, _p(ring_t),
+                   _p(seg_lrm), _p(gsq), _p(seg_wd), self._s())
+
+    def sgd_lrmul(self, theta, mom, grad, span_seg, span_off, span_len, seg_l2, sq, sq_override, nspan, lr, lr_dev, momentum,
+                  clipnorm, seg_lrm, gsq=None, seg_wd=None, guard=None):
+        self._call(self.lib.tnt_sgd_lrmul_f32, "tnt_sgd_lrmul_f32", _p(theta), _p(mom), _p(grad), _p(span_seg), _p(span_off),
+                   _p(span_len), _p(seg_l2), _p(sq), _p(sq_override), nspan, lr, _p(lr_dev), momentum, clipnorm, _p(guard),
+                   _p(seg_lrm), _p(gsq), _p(seg_wd), self._s())
+
+    def dense_dw_adam_lrmul(self, x, dpre, theta, m, v, l2, sq, sq_override, lr_t_dev, beta1, beta2, eps, clipnorm, N, E, Bk, ldx,
+                            lrm, gsq=None, lr=None, wd=0.0, guard=None):
+        """dense_dw_adam at ``lrm`` times the learning rate (a scalar: the one variable's multiplier); 0 launches nothing"""
+        self._call(self.lib.tnt_dense_dw_adam_lrmul_f32, "tnt_dense_dw_adam_lrmul_f32", _p(x), _p(dpre), _p(theta), _p(m), _p(v), l2,
+                   _p(sq), _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk, ldx, float(lrm), _p(gsq),
+                   _p(lr), wd, self._s())
+
+    def dense_dw_adam_fin_lrmul(self, x, dpre, theta, m, v, l2, partial, k0, k1, sq_override, lr_t_dev, beta1, beta2, eps,
+                                clipnorm, N, E, Bk, ldx, lrm, gsq=None, lr=None, wd=0.0, guard=None):
+        self._call(self.lib.tnt_dense_dw_adam_fin_lrmul_f32, "tnt_dense_dw_adam_fin_lrmul_f32", _p(x), _p(dpre), _p(theta), _p(m),
+                   _p(v), l2, _p(partial), k0, k1, _p(sq_override), _p(lr_t_dev), beta1, beta2, eps, clipnorm, _p(guard), N, E, Bk,
+                   ldx, float(lrm), _p(gsq), _p(lr), wd, self._s())
+
     def sam(self, theta, grad, ew, span_seg, span_off, span_len, seg_l2, sq, nseg, nspan, rho, mode, sq_override=None):
         self._call(self.lib.tnt_sam_f32, "tnt_sam_f32", _p(theta), _p(grad), _p(ew), _p(span_seg), _p(span_off), _p(span_len),
                                         _p(seg_l2), _p(sq), _p(sq_override), nseg, nspan, rho, mode, self._s())

@@ -286,6 +286,7 @@ class CaptionGenerator(ModelBase):
             raise RuntimeError("compile() the model before train_step_SAM")
         self._weight_decay_refuse("train_step_SAM")
         self._global_clip_refuse("train_step_SAM")
+        self._finetune_refuse("train_step_SAM")
         img, target = self._unpack_batch(data)
         B, T = self._stage(img, target)
         self._sync_lr()
