@@ -119,6 +119,11 @@ int32_t tnt_gemm3_f32(const float* A, const float* B, float* C, const float* bia
  *     at or past *live returns at once, rows of A past it read as zero, rows of C at or past it are NOT written.
  *   live_mode = 2 (transA = 1, transB = 0, splitk = 1): only rows [0, *live) of the contraction (of A and B as stored) exist:
  *     C = sum over k < *live, colsum likewise; *live = 0 gives C = bias or 0 and colsum = 0.
+ *   live_mode = 3 (transA = 0): live_mode 1, and with splitk > 1 and fewer live row tiles than M has, the launch deals the
+ *     SAME grid over the live row tiles only, with the largest split S' that fits it (S' <= the grid's units / live tiles,
+ *     S' <= the stage count, never below splitk): equal, smaller shares of K instead of idle workgroups.  The summation
+ *     order of C then depends on the word (a deterministic function of operands and word; the same launch twice gives the
+ *     same bits); for *live >= M, or a word that leaves the row-tile count at M's, the launch is that of live_mode 1.
  *   Any other combination: TNT_BADARG.  To get a tile that suits the live extent, ask tnt_gemm3_plan for the shape with the
  *   EXPECTED extent in place of M (the result stays correct for any value of the word: the grid always covers M). */
 /* The (tile, splitk) the library's cost model picks for a shape (batch = 2 for a dual launch; allow_split = 0 restricts
@@ -144,6 +149,16 @@ typedef struct tnt_gemm3_desc {
 int32_t tnt_gemm3_pair_supported(int32_t tile1, int32_t transA1, int32_t transB1, int32_t tile2, int32_t transA2,
                                  int32_t transB2);
 int32_t tnt_gemm3_pair_f32(const tnt_gemm3_desc* p, const tnt_gemm3_desc* q, void* stream);
+/* The joint plan of a pair launch.  p1, p2: eight int32 each = {M, N, K, transA, transB, batch, live, flags}: the shape as the
+ * descriptor will carry it, the extent to EXPECT in the product's live word (rows of A / C, or of the contraction for
+ * transA = 1; 0: no live word) and flags (1: no split -- the colsum rider; 2: the launch will use live_mode 3; 4: a 64-deep
+ * pick is launched as its 32-deep twin, as the step does for a small product that rides along).  The model deals the
+ * workgroups of both products over 256 CUs in launch order, at the workgroups per CU the pair kernel's registers and LDS
+ * allow, prices each by the K stages it will really run and minimises the busiest CU.  A launch with a split product keeps
+ * all its workgroups resident together.  out: eight int32 = {tile1, splitk1, units1, tile2, splitk2, units2, workgroups
+ * per CU, 0}; span (nullable; two doubles): {modelled us of this plan, of the two independent tnt_gemm3_plan picks}, span[0] <= span[1]
+ * by construction (the independent picks are the incumbent).  TNT_BADARG where the independent picks have no pair form. */
+int32_t tnt_gemm3_plan_pair(const int32_t* p1, const int32_t* p2, int32_t* out, void* span);
 
 /* ---- the optimizer step without a finalize launch (single-process step; optimizer.apply_gradients with clipnorm + Adam,
  * main.py:97, lc_NIC.py:389).  tnt_step_finalize_f32 -- per-variable norms from the span partials, the step's scalar totals,

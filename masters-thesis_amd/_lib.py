@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 130
+TNT_VERSION = 131
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -33,6 +33,7 @@ SIGNATURES = {
     "tnt_gemm3_work_arm": [P, I64, P],
     "tnt_gemm3_pair_supported": [I32, I32, I32, I32, I32, I32],
     "tnt_gemm3_pair_f32": [P, P, P],
+    "tnt_gemm3_plan_pair": [P, P, P, P],
     "tnt_span_sqnorm_lr_f32": [P, P, P, P, P, P, P, I32, P, P, P, F32, F32, P, P],
     "tnt_dense_gram_norm_spans_lr_f32": [P, P, P, P, I32, P, I32, F32, P, I32, I32, I32, P, P, P, P, P, P, P, I32, P, P, P, F32, F32, P, P],
     "tnt_dense_dw_adam_fin_f32": [P, P, P, P, P, F32, P, I32, I32, P, P, F32, F32, F32, F32, P, I32, I32, I32, I32, P],

@@ -32,7 +32,9 @@
 //    owns, in split order (bitwise reproducible), before the ordinary epilogue.  Each workgroup moves (S-1)/S of a tile
 //    out and in; no reduce launch, no second pass over C.
 #include "tnt_common.h"
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -50,7 +52,8 @@ struct G3Args {
   //   live_mode 1: only rows [0, *live) of A / C exist (A K-contiguous) -- the tile map stays that of M, a workgroup whose
   //                tile starts at or past *live leaves at once, rows past it read as zero and are not stored;
   //   live_mode 2: only rows [0, *live) of the contraction exist (TN, no split) -- K, the stage count and the column sums
-  //                follow *live; 0 gives the empty sum.
+  //                follow *live; 0 gives the empty sum;
+  //   live_mode 3: live_mode 1, and a split product deals its grid over the live row tiles only (the unit map in body).
   const int* live; int live_mode;
 };
 
@@ -154,25 +157,42 @@ __device__ __forceinline__ void G3Cfg<A_KC, B_KC, TM, TN, WGM, WGN, BK, NS>::bod
   const int wm = wave / WGN, wn = wave % WGN;
   const int r = lane & 15, q = lane >> 4;
   const int MT = (g.M + BM - 1) / BM, NTl = (g.N + BN - 1) / BN;
-  const int S = g.splitk;
   int Mv = g.M, Kv = g.K, nst = g.nst;                         // the extents this launch really has (G3Args::live)
   if (LIVE && g.live != nullptr) {
     const int lv = max(*g.live, 0);
-    if (g.live_mode == 1) Mv = min(lv, g.M);
+    if (g.live_mode != 2) Mv = min(lv, g.M);
     else { Kv = min(lv, g.K); nst = (Kv + BK - 1) / BK; }
   }
-  const int nwg = MT * NTl * S, bid = bx;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;       // XCD-contiguous unit order (bijective for any nwg)
+  const int nwg = MT * NTl * g.splitk, bid = bx;               // the grid of this product: what the host planned for M
+  // The unit map: S splits of nsp stages over MTu x NTl tiles = nun units.  Without a live extent it is the host's.
+  // live_mode 3, split product, fewer live row tiles than planned: the SAME grid is dealt over the live tiles only, with
+  // the largest split that fits it -- equal, smaller shares of K for the rows that exist instead of idle workgroups for the
+  // rows that do not.  Every word is wave-uniform (kernel arguments, the live word, the workgroup id).
+  int S = g.splitk, nsp = g.nst_split, MTu = MT, nun = nwg;
+  if (LIVE && g.live_mode == 3 && S > 1) {
+    const int MTv = (Mv + BM - 1) / BM;
+    if (MTv < MT) {
+      if (MTv == 0) return;
+      const int tl = MTv * NTl;
+      nsp = (nst + min(nwg / tl, nst) - 1) / min(nwg / tl, nst);
+      S = (nst + nsp - 1) / nsp;                               // no empty split; never below the host's (tl <= MT * NTl)
+      MTu = MTv; nun = tl * S;
+      // the workgroups of an XCD past its share of the live units leave here: before the first barrier, LDS-DMA piece
+      // or exchange access (the share is at most what the grid put on the XCD, since nun <= nwg)
+      if ((bid >> 3) >= (nun >> 3) + ((bid & 7) < (nun & 7) ? 1 : 0)) return;
+    }
+  }
+  const int q8 = nun >> 3, r8 = nun & 7, xcd = bid & 7;       // XCD-contiguous unit order (bijective for any unit count)
   const int u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int t = u / S, z = u - t * S;                          // output tile, K split
-  const int m0 = (t % MT) * BM, n0 = (t / MT) * BN;
+  const int m0 = (t % MTu) * BM, n0 = (t / MTu) * BN;
   if (LIVE && m0 >= Mv) return;   // a tile of rows that do not exist: every K split of it takes this exit (same word), before
                                // the first barrier, LDS-DMA piece or exchange access
   const bool second = by != 0;                                 // the second product of a dual launch
   const float* Ag = second ? g.A2 : g.A;
   float* Cg = second ? g.C2 : g.C;
-  const int s_begin = z * g.nst_split;
-  const int s_end = min(nst, s_begin + g.nst_split);           // this workgroup's stages [s_begin, s_end)
+  const int s_begin = z * nsp;
+  const int s_end = min(nst, s_begin + nsp);                   // this workgroup's stages [s_begin, s_end)
   const int nloc = max(s_end - s_begin, 0);
 
   // ---- LDS-DMA sources (the extern array is the kernel's only LDS object: byte offsets inside it are LDS addresses)
@@ -723,13 +743,154 @@ extern "C" int32_t tnt_gemm3_plan(int32_t M, int32_t N, int32_t K, int32_t trans
   return *tile ? 0 : TNT_BADARG(2);
 }
 
+// ---- the joint plan of a pair launch.  tnt_gemm3_plan prices a product as if it had the device to itself; in a pair
+// launch the two products share every CU, and a product under a live extent does less than its shape says.  The model
+// below deals the launch's workgroups the way the hardware does -- in order, one per CU until every CU has one, then the
+// next resident slot -- gives each the MFMA time of the stages it will really run, and takes the busiest CU.
+namespace {
+struct G3Prod { int M, N, K, tA, tB, batch, live, flags; };   // flags: 1 no split (colsum rider), 2 device-side unit map,
+                                                               // 4 "small" (a 64-deep pick is launched as its 32-deep twin)
+constexpr int G3_PAIR_CUS = 256;
+
+// wave tile (TM, TN) of a configuration: the register side of the residency estimate
+void g3_wave_tile(int tile, int& tm, int& tn) {
+  static const int t[G3_NTILES + 1][2] = {{0, 0}, {5, 4}, {4, 5}, {4, 4}, {2, 5}, {2, 4}, {4, 2}, {2, 2}, {4, 5}, {2, 2}, {2, 4}, {4, 2}};
+  tm = t[tile][0]; tn = t[tile][1];
+}
+// Workgroups of a pair instantiation a CU holds: LDS of the larger ring, and registers -- accumulators + two fragment
+// buffers + addressing; the constant is set by the one measured pair (128 x 80 TN with 64 x 128 NT: 172 VGPR + 40 AGPR,
+// profiles/compact_head_resource_usage.txt).  Four waves per workgroup, one per SIMD, 512 registers per SIMD lane.
+int g3_pair_resident(int tile1, int tile2) {
+  G3Tile a, b;
+  g3_tile(tile1, a); g3_tile(tile2, b);
+  int regs = 0;
+  for (int tile : {tile1, tile2}) {
+    int tm, tn;
+    g3_wave_tile(tile, tm, tn);
+    regs = std::max(regs, 4 * tm * tn + 8 * (tm + tn) + 116);
+  }
+  const int r = std::min(163840 / std::max(a.lds, b.lds), 512 / regs);
+  return r < 1 ? 1 : r;
+}
+
+struct G3Units { int n = 0, splitk = 1; double xch = 0.0, stores = 0.0, eff = 1.0; std::vector<float> t; };
+// the units of product p on (tile, splitk) in launch order, each with its MFMA time in us at the full rate (0: the unit
+// leaves at once); false: this product cannot run on (tile, splitk)
+bool g3_pair_units(const G3Prod& p, int tile, int splitk, G3Units& o) {
+  G3Tile tl;
+  if (!g3_tile(tile, tl)) return false;
+  const int bk = tile >= 9 ? 64 : 32, nst = (p.K + bk - 1) / bk;
+  const int per = (nst + splitk - 1) / splitk;
+  if (splitk > 1 && ((p.flags & 1) || per < 4 || (nst + per - 1) / per != splitk)) return false;
+  const bool tn = p.tA && !p.tB;
+  if (tn && p.live > 0 && splitk > 1) return false;             // a live contraction needs the whole K in one workgroup
+  const int MT = (p.M + tl.bm - 1) / tl.bm, NTl = (p.N + tl.bn - 1) / tl.bn, nwg = MT * NTl * splitk;
+  if (nwg * p.batch > 1024) return false;
+  int S = splitk, nsp = per, MTu = MT, nun = nwg, Mv = p.M, stages = nst;
+  if (p.live > 0 && tn) stages = (std::min(p.live, p.K) + bk - 1) / bk;
+  if (p.live > 0 && !p.tA) Mv = std::min(p.live, p.M);
+  const int MTv = (Mv + tl.bm - 1) / tl.bm;
+  bool mapped = false;
+  if ((p.flags & 2) && !p.tA && p.live > 0 && splitk > 1 && MTv < MT) {       // body<true>'s unit map, word for word
+    const int tiles = MTv * NTl, s0 = std::min(nwg / tiles, nst);
+    nsp = (nst + s0 - 1) / s0;
+    S = (nst + nsp - 1) / nsp;
+    MTu = MTv; nun = tiles * S; mapped = true;
+  }
+  o.n = nwg * p.batch; o.splitk = splitk; o.eff = tl.eff;
+  o.t.assign(o.n, 0.f);
+  const int q8 = nun >> 3, r8 = nun & 7;
+  for (int b = 0; b < o.n; ++b) {
+    const int bid = b % nwg, xcd = bid & 7;
+    if (mapped && (bid >> 3) >= q8 + (xcd < r8 ? 1 : 0)) continue;
+    const int u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int t = u / S, z = u - t * S;
+    if ((t % MTu) * tl.bm >= Mv) continue;
+    const int s_begin = z * nsp, s_end = std::min(S > 1 ? nst : stages, s_begin + nsp);
+    const int nloc = S > 1 ? std::max(s_end - s_begin, 0) : stages;
+    o.t[b] = (float)((double)tl.bm * tl.bn * nloc * bk * 2.0 / 256.0 / 2400.0);
+  }
+  o.xch = S > 1 ? 4.0 + 0.4 * S + tl.bm * tl.bn * 4.0e-3 * (S - 1) / S / 20.0 : 0.0;     // as g3_cost
+  o.stores = (double)Mv * p.N * p.batch * 4.0 / 4.0e6 + (bk == 64 ? 0.8 : 0.0);
+  return true;
+}
+
+// modelled time in us of the pair launch a + b with `resident` workgroups per CU; 1e30: the launch is not allowed
+double g3_pair_span(const G3Units& a, const G3Units& b, int resident) {
+  const int n = a.n + b.n, round1 = G3_PAIR_CUS * resident;
+  if ((a.splitk > 1 || b.splitk > 1) && n > std::min(1024, round1)) return 1e30;   // the splits of a tile are resident together
+  double load[G3_PAIR_CUS] = {0.0};
+  int held[G3_PAIR_CUS] = {0};
+  for (int i = 0; i < n; ++i) {
+    const bool first = i < a.n;
+    const double t = first ? a.t[i] : b.t[i - a.n];
+    int cu = i % G3_PAIR_CUS;
+    if (i >= round1) cu = (int)(std::min_element(load, load + G3_PAIR_CUS) - load);   // the CU whose slot frees first
+    if (t > 0.0) { load[cu] += t / (first ? a.eff : b.eff); ++held[cu]; }
+  }
+  double worst = 0.0;
+  for (int c = 0; c < G3_PAIR_CUS; ++c) {
+    const double shared = held[c] > 1 && resident > 1 ? 1.04 : 1.0;    // co-resident workgroups hide each other's stalls (g3_cost)
+    worst = std::max(worst, load[c] / shared);
+  }
+  return 4.0 + a.stores + b.stores + worst + std::max(a.xch, b.xch);
+}
+}  // namespace
+
+extern "C" int32_t tnt_gemm3_plan_pair(const int32_t* p1, const int32_t* p2, int32_t* out, void* span_us) {
+  double* span = static_cast<double*>(span_us);
+  if (p1 == nullptr || p2 == nullptr || out == nullptr) return TNT_BADARG(1);
+  G3Prod p[2];
+  int pick[2][2];
+  for (int i = 0; i < 2; ++i) {
+    const int32_t* s = i ? p2 : p1;
+    p[i] = G3Prod{s[0], s[1], s[2], s[3] != 0, s[4] != 0, s[5] > 1 ? 2 : 1, s[6], s[7]};
+    if (p[i].M <= 0 || p[i].N <= 0 || p[i].K <= 0) return TNT_BADARG(1);
+    // the independent pick: what two tnt_gemm3_plan calls give today
+    int32_t t, sk;
+    if (int32_t rc = tnt_gemm3_plan(p[i].M, p[i].N, p[i].K, p[i].tA, p[i].tB, p[i].batch, !(p[i].flags & 1), &t, &sk)) return rc;
+    if (p[i].flags & 4) t = t == 9 ? 7 : (t == 10 ? 5 : t);
+    pick[i][0] = t; pick[i][1] = sk;
+  }
+  if (!tnt_gemm3_pair_supported(pick[0][0], p[0].tA, p[0].tB, pick[1][0], p[1].tA, p[1].tB)) return TNT_BADARG(13);
+  G3Units a, b;
+  if (!g3_pair_units(p[0], pick[0][0], pick[0][1], a) || !g3_pair_units(p[1], pick[1][0], pick[1][1], b)) return TNT_BADARG(13);
+  const double indep = g3_pair_span(a, b, g3_pair_resident(pick[0][0], pick[1][0]));
+  if (indep >= 1e30) return TNT_BADARG(16);
+  // every supported (tile, split) pair; the independent pick stays unless another one is modelled clearly shorter, so the
+  // result is never above it
+  double best = indep;
+  int bt[2][2] = {{pick[0][0], pick[0][1]}, {pick[1][0], pick[1][1]}}, bn[2] = {a.n, b.n};
+  const int ss[] = {1, 2, 3, 4, 5, 6, 8};
+  for (int t1 = 1; t1 <= G3_NTILES; ++t1)
+    for (int t2 = 1; t2 <= G3_NTILES; ++t2) {
+      if (!tnt_gemm3_pair_supported(t1, p[0].tA, p[0].tB, t2, p[1].tA, p[1].tB)) continue;
+      const int res = g3_pair_resident(t1, t2);
+      for (int s1 : ss) {
+        G3Units ua;
+        if (!g3_pair_units(p[0], t1, s1, ua)) continue;
+        for (int s2 : ss) {
+          G3Units ub;
+          if (!g3_pair_units(p[1], t2, s2, ub)) continue;
+          const double c = g3_pair_span(ua, ub, res);
+          if (c < best - 0.25) { best = c; bt[0][0] = t1; bt[0][1] = s1; bt[1][0] = t2; bt[1][1] = s2; bn[0] = ua.n; bn[1] = ub.n; }
+        }
+      }
+    }
+  out[0] = bt[0][0]; out[1] = bt[0][1]; out[2] = bn[0];
+  out[3] = bt[1][0]; out[4] = bt[1][1]; out[5] = bn[1];
+  out[6] = g3_pair_resident(bt[0][0], bt[1][0]); out[7] = 0;
+  if (span != nullptr) { span[0] = best; span[1] = indep; }
+  return 0;
+}
+
 namespace {
 int32_t g3_fill(G3Args& g, const float* A, const float* B, float* C, const float* bias, float* colsum, const float* A2, float* C2,
                 int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t transA, int32_t transB,
                 int32_t splitk, float* work, uint32_t* sync, const int32_t* live, int32_t live_mode) {
   if (M <= 0 || N <= 0 || K <= 0) return TNT_BADARG(8);
   if (live != nullptr) {
-    if (live_mode == 1) { if (transA) return TNT_BADARG(21); }                      // rows of a K-contiguous A
+    if (live_mode == 1 || live_mode == 3) { if (transA) return TNT_BADARG(21); }   // rows of a K-contiguous A
     else if (live_mode == 2) { if (!transA || transB || splitk > 1) return TNT_BADARG(21); }   // TN, whole K per workgroup
     else return TNT_BADARG(21);
   }

@@ -1035,6 +1035,7 @@ class ModelBase:
     use_gemm3 = True            # False: vendor-library routing (hipBLASLt head, rocBLAS LSTM products); INTEGRATION.md 4, tools/probe/dp_w1_diff.py
     g3_riders = True            # False: bias sums and paired products as launches of their own; tools/probe/dp_w1_diff.py
     g3_force = None             # {(M, N, K, tA, tB, batch): (tile, splitk)}: a gemm3 plan forced per shape; tools/pair_scan.py, tests
+    g3_live_map = True          # False: a split product under a live row count keeps the grid map of its full shape, and its pair the two independent plans; tools/ab_attr.py
     g3_min_flops = 3e7          # products below it keep the tiled split-K kernel; tests/test_gpu_compact_head.py
     use_blas = True             # False (with use_gemm3 = False): the round-1 hand-written kernels; INTEGRATION.md 4
     lt_min_flops = 1e9          # hipBLASLt takes the vocabulary-sized products above it (use_gemm3 = False); tools/lt_tune.py
@@ -2336,21 +2337,62 @@ class ModelBase:
                  tile=tile, splitk=sk, work=work, sync=sync, **kw)
         return True
 
+    def _g3_pair_live(self, p, q):
+        """a pair launch planned for the rows expected to exist: the switch is on, the backend has the joint plan and a
+        product carries a live word with its expected extent (``plan_M``)"""
+        return (self.g3_live_map and hasattr(self.be, "gemm3_plan_pair")
+                and any(d.get("plan_M") is not None and d.get("live") is not None for d in (p, q)))
+
+    def _g3_plan_pair(self, p, q):
+        """the joint plan of a pair launch whose products carry ``plan_M`` (tnt_gemm3_plan_pair; cached per argument set):
+        ((tile, splitk), (tile, splitk)), or None -- not such a launch (_g3_pair_live), a forced plan, or independent picks
+        without a pair form -- for the two independent plans"""
+        from .ops import G3_PLAN_MAP, G3_PLAN_NOSPLIT, G3_PLAN_SMALL, LIVE_ROWS_M
+        be = self.be
+        if not self._g3_pair_live(p, q):
+            return None
+        args = []
+        for d in (p, q):
+            live = d.get("plan_M") if d.get("live") is not None else None
+            flags = (G3_PLAN_NOSPLIT if d.get("colsum") is not None else 0) | (G3_PLAN_SMALL if d.get("small") else 0) \
+                | (G3_PLAN_MAP if d.get("live_mode") == LIVE_ROWS_M else 0)
+            args.append((d["M"], d["N"], d["K"], int(d.get("transA", False)), int(d.get("transB", False)),
+                         2 if d.get("A2") is not None else 1, int(live or 0), flags))
+        forced = self.g3_force or {}
+        if any((a[0], a[1], a[2], bool(a[3]), bool(a[4]), a[5]) in forced for a in args):
+            return None                 # a forced plan (tools, tests) stands
+        key = ("pair",) + tuple(args)
+        plans = self._g3_plans
+        if key not in plans:
+            r = be.gemm3_plan_pair(*args)
+            plans[key] = None if r is None else (r[0][:2], r[1][:2])
+        return plans[key]
+
     def gemm3_pair(self, p, q):
         """Two INDEPENDENT products in one launch (tnt_gemm3_pair_f32): p, q = dicts of gemm3's arguments.  True = issued;
-        False = this pair has no co-launch form (the caller issues the two products itself)."""
+        False = this pair has no co-launch form (the caller issues the two products itself).
+        ``plan_M`` in a dict: the extent to EXPECT in that product's live word (rows for LIVE_ROWS_M, the contraction for
+        LIVE_ROWS_K).  With it (``g3_live_map``) the two products are planned together for the work they will really do
+        (_g3_plan_pair) and a split LIVE_ROWS_M product deals its grid over the live rows only (LIVE_ROWS_M_MAP); the
+        result never depends on the value."""
+        from .ops import LIVE_ROWS_M, LIVE_ROWS_M_MAP
         be = self.be
         if not self.use_gemm3 or not hasattr(be, "gemm3_pair"):
             return False
+        live_map = self._g3_pair_live(p, q)
+        joint = self._g3_plan_pair(p, q)
         descs, need = [], 0
-        for d in (p, q):
+        for i, d in enumerate((p, q)):
             if d["lda"] % 4 or d["ldb"] % 4 or d["ldc"] % 4:
                 return False
             batch = 2 if d.get("A2") is not None else 1
-            tile, sk = self._g3_plan(d["M"], d["N"], d["K"], d.get("transA", False), d.get("transB", False), batch,
-                                     d.get("colsum") is not None)
-            if d.get("small"):            # a small product rides along: the 32-deep tile of the SAME shape has a pair form
-                tile = {9: 7, 10: 5}.get(tile, tile)      # (same tile count, so the planned split stays valid)
+            if joint is not None:
+                tile, sk = joint[i]
+            else:
+                tile, sk = self._g3_plan(d["M"], d["N"], d["K"], d.get("transA", False), d.get("transB", False), batch,
+                                         d.get("colsum") is not None)
+                if d.get("small"):            # a small product rides along: the 32-deep tile of the SAME shape has a pair form
+                    tile = {9: 7, 10: 5}.get(tile, tile)      # (same tile count, so the planned split stays valid)
             wf = (be.gemm3_work_floats(d["M"], d["N"], tile, sk, batch) + 3) // 4 * 4 if sk > 1 else 0
             descs.append((d, tile, sk, need, wf))
             need += wf
@@ -2361,7 +2403,8 @@ class ModelBase:
         work, sync = self._g3_space(need) if need else (None, None)
         # the descriptors are passed by address and recorded launch plans re-issue the call later: one descriptor pair per
         # distinct argument set, kept for the life of the model (same operands -> same objects)
-        ck = tuple((tuple((k, v.data_ptr() if torch.is_tensor(v) else v) for k, v in sorted(d.items()) if k != "small"), tile, sk, off)
+        ck = tuple((tuple((k, v.data_ptr() if torch.is_tensor(v) else v) for k, v in sorted(d.items()) if k not in ("small", "plan_M")), tile, sk, off,
+                    live_map)
                    for d, tile, sk, off, _ in descs) + (work.data_ptr() if need else 0,)
         keep = self._g3_descs
         if ck in keep:
@@ -2370,6 +2413,8 @@ class ModelBase:
         out = []
         for d, tile, sk, off, wf in descs:
             lv = dict(live=d["live"], live_mode=d["live_mode"]) if d.get("live") is not None else {}
+            if live_map and sk > 1 and lv.get("live_mode") == LIVE_ROWS_M:
+                lv["live_mode"] = LIVE_ROWS_M_MAP
             out.append(be.gemm3_desc(d["A"], d["B"], d["C"], d["M"], d["N"], d["K"], d["lda"], d["ldb"], d["ldc"],
                                      transA=d.get("transA", False), transB=d.get("transB", False), bias=d.get("bias"),
                                      colsum=d.get("colsum"), A2=d.get("A2"), C2=d.get("C2"), tile=tile, splitk=sk,

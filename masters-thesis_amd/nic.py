@@ -472,7 +472,8 @@ class NIC(ModelBase):
             # formed for those; one device word bounds both products
             dw.update(live=self.head_live, live_mode=LIVE_ROWS_K)
             dx.update(live=self.head_live, live_mode=LIVE_ROWS_M)
-            if not self.gemm3_pair(dw, dx):
+            rows = self._head_plan_rows(T * B)       # both products are planned, together, for the rows expected to exist
+            if not self.gemm3_pair(dict(dw, plan_M=rows), dict(dx, plan_M=rows)):
                 self.gemm3(dw["A"], dw["B"], dw["C"], U, V, T * B, U, ldV, ldV, transA=True, colsum=dw["colsum"],
                            live=self.head_live, live_mode=LIVE_ROWS_K)
                 self.gemm3(dlog, Wo, self.dOut, T * B, U, V, ldV, ldV, U, transB=True, live=self.head_live,

@@ -23,6 +23,21 @@ def _p(t):
 import ctypes as _ct
 
 
+def gemm3_plan_pair(lib, p1, p2):
+    """The joint plan of a pair launch (tnt_gemm3_plan_pair; host code, launches nothing).  p = (M, N, K, transA, transB,
+    batch, live, flags): the shape, the extent to EXPECT in the product's live word (0: none) and G3_PLAN_* flags.
+    Returns ((tile, splitk, units) of each product, workgroups per CU, (modelled us of the joint plan, of the two
+    independent picks)), or None where the independent picks have no pair form.  A function of the module, bound by
+    HipBackend.__init__ as ``be.gemm3_plan_pair(p1, p2)`` (HipBackend's methods are its launches and the query helpers
+    tests/test_host_backend_coverage.py lists by name); a backend without it keeps the two independent plans
+    (ModelBase._g3_pair_live)."""
+    a, b = ((_ct.c_int32 * 8)(*[int(v) for v in p]) for p in (p1, p2))
+    out, span = (_ct.c_int32 * 8)(), (_ct.c_double * 2)()
+    if lib.tnt_gemm3_plan_pair(a, b, out, span) != 0:
+        return None
+    return tuple(out[0:3]), tuple(out[3:6]), int(out[6]), (float(span[0]), float(span[1]))
+
+
 class _G3Desc(_ct.Structure):
     _fields_ = ([(n, _ct.c_void_p) for n in ("A", "B", "C", "bias", "colsum", "A2", "C2")]
                 + [(n, _ct.c_int32) for n in ("M", "N", "K", "lda", "ldb", "ldc", "transA", "transB", "tile", "splitk")]
@@ -43,6 +58,8 @@ class _FinDesc(_ct.Structure):
 
 
 LIVE_ROWS_M, LIVE_ROWS_K = 1, 2      # live_mode of gemm3 / gemm3_desc: the device word bounds the rows of A and C / of the contraction
+LIVE_ROWS_M_MAP = 3                  # LIVE_ROWS_M, and a split product deals its grid over the live row tiles only
+G3_PLAN_NOSPLIT, G3_PLAN_MAP, G3_PLAN_SMALL = 1, 2, 4      # flags of gemm3_plan_pair's products
 
 
 class HipBackend:
@@ -52,6 +69,7 @@ class HipBackend:
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.KernelLibraryError("no GPU visible: the HIP backend needs an MI355X (there is no CPU fallback)")
+        self.gemm3_plan_pair = lambda p1, p2: gemm3_plan_pair(self.lib, p1, p2)       # host-side query, not a launch
 
     _rec = None     # while a launch plan is being recorded: list of (c function, name, argument tuple)
 
@@ -103,7 +121,7 @@ class HipBackend:
               tile=1, splitk=1, work=None, sync=None, live=None, live_mode=0):
         """the round-3 FP32-MFMA family (LDS-DMA staged, b128 fragments): C = op(A) op(B) (+ bias); riders: column sums of B,
         a second product sharing B; splitk > 1 reduces the K splits inside the launch (work / sync: gemm3_work_floats /
-        gemm3_sync_words); live / live_mode: a device-side extent (LIVE_ROWS_M / LIVE_ROWS_K, include/tnt_hip.h)"""
+        gemm3_sync_words); live / live_mode: a device-side extent (LIVE_ROWS_M / LIVE_ROWS_K / LIVE_ROWS_M_MAP, include/tnt_hip.h)"""
         self._call(self.lib.tnt_gemm3_f32, "tnt_gemm3_f32", _p(A), _p(B), _p(C), _p(bias), _p(colsum), _p(A2), _p(C2),
                    M, N, K, lda, ldb, ldc, int(transA), int(transB), tile, splitk, _p(work), _p(sync), _p(live), int(live_mode),
                    self._s())
