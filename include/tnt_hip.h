@@ -890,6 +890,36 @@ int32_t tnt_consensus_spread_i32(const int32_t* token, const int32_t* parent, co
  * logits or mix, mix overlapping logits anywhere in their extents; nothing is launched then. */
 int32_t tnt_guidance_mix_f32(const float* logits, int32_t ld, int32_t V, int32_t Rm, float scale, float plaus,
                              float* mix, int32_t ldm, int32_t* token, void* stream);
+/* Minimum Bayes risk caption selection (Eikema & Aziz 2020, sampling-based MBR): of the Nc candidate captions of a scan
+ * the one with the highest expected n-gram utility against the first Nr of them, the pseudo-references (restated by
+ * tests/mbr_oracle.py).  Library-defined:
+ *  - Layout.  ids [Nc][L][ld] int32: candidate c of scan b at position t is ids[(c*L + t)*ld + b], the (max_len, rows)
+ *    layout of a decode's ids stacked Nc times; B scans, ld >= B, columns [B, ld) are never read (the member rows of a
+ *    consensus or guided decode).  ids is read only.  Tokens are only compared: any int32 value is safe.
+ *  - Caption.  A candidate's caption is its tokens before the first end_id or 0 (SelfCritical.truncate's rule); end_id < 0:
+ *    only 0 terminates.  What follows the terminator is ignored.  Its length is len, 0 <= len <= L.
+ *  - Match counts, exact integers.  For k = 1..order: c_k(h, r) = sum over the distinct k-grams g of h of
+ *    min(count_h(g), count_r(g)), and tot_k(x) = max(len_x - k + 1, 0).
+ *  - kind 0 ("ngram-f"):  F_k = 2*c_k / (tot_k(h) + tot_k(r)), one float32 division of the two integers, 0 when the
+ *    denominator is 0; u(h, r) = (F_1 + ... + F_order) / order, summed in ascending k in float32.  Symmetric bit for bit.
+ *  - kind 1 ("bleu"):  u(h, r) = evaluate.sentence_bleu([r], h, weights=(1/order,)*order), method-1 smoothing with epsilon
+ *    0.1, in float32: 0 for an empty h or c_1 = 0; else s = sum_k (1/order) * log(n_k / max(1, tot_k(h))) in ascending k,
+ *    n_k = c_k or 0.1 where c_k = 0, and u = bp * exp(s), bp = exp(1 - len_r/len_h) when len_h <= len_r, else 1.
+ *  - Expected utility.  All Nc candidates are hypotheses, 1 <= Nr <= Nc: E[b][i] = (sum_{j < Nr} u(i, j)) / Nr, the float32
+ *    utilities accumulated in ascending j in float64 and rounded to float32 once, behind the division.  The self term is
+ *    included when i < Nr, so that two identical hypotheses get bit-identical E.
+ *  - best [B]: the first maximum of E[b][:] (the smallest index wins).
+ *  - Outputs: expected [B][Nc] float32; best [B] int32; out_ids (nullable) [L][ldo] int32, ldo >= B: column b receives the
+ *    chosen candidate's L tokens verbatim, columns [B, ldo) are untouched; match (nullable) [B][Nc][Nr][order] int32, the
+ *    c_k; util (nullable) [B][Nc][Nr] float32.
+ *  - One workgroup per scan, the scan's tokens staged once in LDS, the pairs dealt over the threads; integer compares
+ *    only in the inner loop; no atomics, no scratch memory, fixed summation orders: deterministic.
+ * TNT_BADARG for B <= 0, ld < B, Nc outside [1, 64], Nr outside [1, Nc], L outside [1, 64], order outside [1, 4], kind other
+ * than 0 or 1, null ids / expected / best, ldo < B with out_ids, any output overlapping ids anywhere in their extents;
+ * nothing is launched then. */
+int32_t tnt_mbr_select_f32(const int32_t* ids, int32_t ld, int32_t B, int32_t Nc, int32_t Nr, int32_t L, int32_t end_id,
+                           int32_t order, int32_t kind, float* expected, int32_t* best, int32_t* out_ids, int32_t ldo,
+                           int32_t* match, float* util, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

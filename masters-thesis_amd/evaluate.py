@@ -132,6 +132,24 @@ def beam_captions(model, features, a0, c0, tokenizer, max_len, beam_width=5, len
     return ids, ids_to_captions(ids, tokenizer, end_token=end_token)
 
 
+def mbr_captions(model, features, a0, c0, tokenizer, max_len, mbr, sample_step=0, end_token="<end>", constraints=None,
+                 consensus=None, guidance=None):
+    """Minimum Bayes risk captions of either model (nic.NIC or lc_nic.NIC ``mbr_decode``; ``mbr``: a model_base.MBR, whose
+    end_id must be ``end_token``'s index): every caption starts at the tokenizer's "<start>" index.  Returns (ids (B,
+    max_len) int64 of each scan's chosen candidate, captions: token lists cut at ``end_token`` as ids_to_captions cuts,
+    info: mbr_decode's, the expected utilities (B, Nc) and the chosen index (B,)).  ``constraints``, ``consensus`` and
+    ``guidance`` go to mbr_decode, and through it to every candidate decode; with consensus ``features`` holds members * M
+    scans, member-major, and one caption per image comes back."""
+    end_id = int(tokenizer.word_index[end_token])
+    if int(mbr.end_id) != end_id:
+        raise ValueError(f"mbr.end_id = {mbr.end_id} is not the index of {end_token!r} ({end_id})")
+    start = np.full(_n_start(features, consensus), int(tokenizer.word_index["<start>"]), np.int64)
+    words, info = model.mbr_decode(features, a0, c0, start, max_len, mbr, sample_step=sample_step,
+                                   **_con_kw(constraints, consensus, guidance))
+    ids = np.ascontiguousarray(words[:, :, 0]).astype(np.int64)
+    return ids, ids_to_captions(ids, tokenizer, end_token=end_token), info
+
+
 def distinct_n(captions, n):
     """distinct-n (Li et al. 2016) of a list of token sequences (lists of words or ids): the number of distinct n-grams
     over all the sequences divided by the total number of n-grams; 0.0 when no sequence holds an n-gram.  1.0: no n-gram

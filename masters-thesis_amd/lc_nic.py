@@ -1326,6 +1326,21 @@ class NIC(ModelBase):
         the S subject slices and G must be S) words (M, max_len, 1) and probs (M, max_len, V), the mixtures, are per
         image; with guidance words and probs, the guided distributions, are per scan.  alpha and s stay per member row,
         (max_len, G*M, R, ...), under guidance (max_len, 2*B, R, ...) with the scans' rows first."""
+        choice, s_all, M = self._decode(img_input, a0, c0, start_seq, max_len, _sample, _filter, return_s, constraints,
+                                        consensus, guidance, training)
+        ids = choice.ids[:, :M]                        # member 0's rows: every member holds the common word
+        out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
+        out_probs = choice.probs[:, :, :self.V].permute(1, 0, 2).contiguous().cpu().numpy()
+        # s (the dropout-free tanh activations, 44 MB at the BASELINE shape) is part of the reference's return tuple but
+        # only analysis code reads it: return_s=False skips its device-to-host copy (eval_model does)
+        return out_words, out_probs, self.alpha[:max_len].cpu().numpy()[..., None], (s_all.cpu().numpy() if return_s else None)
+
+    greedy_predict_attention = greedy_predict
+
+    def _decode(self, img_input, a0, c0, start_seq, max_len, _sample=None, _filter=None, return_s=True, constraints=None,
+                consensus=None, guidance=None, training=False):
+        """the decode loop of greedy_predict and sample_predict on the device: returns (the step's choice
+        (model_base._TokenChoice: probs, ids), s (max_len, B, R, A) or None, M captions)"""
         cons, (img_input, a0, c0), start, M, G, B, con, _, ckey = self._decode_setup(
             guidance, consensus, constraints, None, img_input, a0, c0, start_seq, max_len, training=training)
         self._stage_inputs((img_input, torch.zeros(B, max_len, dtype=torch.int32), a0, c0))
@@ -1354,14 +1369,15 @@ class NIC(ModelBase):
             self._run_captured(("greedy",) + key + ckey, run)
         else:                      # the sampling stream step is a launch argument: not captured
             run()
-        ids = choice.ids[:, :M]                        # member 0's rows: every member holds the common word
-        out_words = ids.t().contiguous().cpu().numpy().astype(np.int64)[:, :, None]
-        out_probs = choice.probs[:, :, :self.V].permute(1, 0, 2).contiguous().cpu().numpy()
-        # s (the dropout-free tanh activations, 44 MB at the BASELINE shape) is part of the reference's return tuple but
-        # only analysis code reads it: return_s=False skips its device-to-host copy (eval_model does)
-        return out_words, out_probs, self.alpha[:max_len].cpu().numpy()[..., None], (s_all.cpu().numpy() if return_s else None)
+        return choice, s_all, M
 
-    greedy_predict_attention = greedy_predict
+    def _mbr_candidate(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
+        """ModelBase.mbr_decode's candidate decode: sample_predict's (with both filters off the unfiltered draw, as there) or
+        (``filt`` None) greedy_predict's, ids left on the device"""
+        sample = None
+        if filt is not None and filt[1] == 0 and filt[2] == 1.0:
+            sample, filt = (filt[0], filt[3]), None
+        return self._decode(img_input, a0, c0, start_seq, max_len, sample, filt, False, constraints, consensus, guidance)[0].ids
 
     # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
     def _score_refuse(self):

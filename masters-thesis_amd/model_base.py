@@ -262,6 +262,57 @@ class SelfCritical:
                 f"reward={self.reward!r}, corpus={'None' if self.corpus is None else f'<{len(self.corpus)} documents>'})")
 
 
+class MBR:
+    """Minimum Bayes risk decoding (Eikema & Aziz 2020, sampling-based), for ``mbr_decode`` of nic.NIC and lc_nic.NIC: per
+    scan ``n_samples`` captions are drawn from the model, and the candidate with the highest expected utility against
+    those samples is returned -- the caption the model's distribution agrees on, where beam search and the greedy decode
+    return its mode and a sampled decode one noisy draw.  The definition on the device is tnt_mbr_select_f32's
+    (include/tnt_hip.h).
+      end_id          the tokenizer's <end> index; a caption ends at its first end_id or 0
+      n_samples       N sampled captions per scan: the pseudo-references, and hypotheses too
+      utility         "ngram-f": the mean over k = 1..order of the F1 of the clipped k-gram matches (symmetric); "bleu":
+                      evaluate.sentence_bleu([reference], hypothesis, weights=(1/order,)*order), method-1 smoothing
+      order           the longest n-gram, 1..4
+      include_greedy  the greedy caption is one more hypothesis (never a reference): n_samples + include_greedy <= 64
+      temperature, top_k, top_p   the filters of every draw, as sample_predict takes them
+    Bad arguments raise ValueError here, before any launch."""
+
+    UTILITIES = ("ngram-f", "bleu")
+    MAX_CANDIDATES = 64
+    MAX_LEN = 64
+    MAX_ORDER = 4
+
+    def __init__(self, end_id, n_samples=16, utility="ngram-f", order=4, include_greedy=True, temperature=1.0, top_k=0,
+                 top_p=1.0):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not is_int(end_id) or end_id < 1:
+            raise ValueError(f"MBR end_id must be an int >= 1 (the <end> index), got {end_id!r}")
+        if not isinstance(include_greedy, (bool, np.bool_)):
+            raise ValueError(f"MBR include_greedy must be a bool, got {include_greedy!r}")
+        if not is_int(n_samples) or n_samples < 1 or n_samples + int(include_greedy) > self.MAX_CANDIDATES:
+            raise ValueError(f"MBR n_samples must be an int >= 1 with n_samples + include_greedy <= {self.MAX_CANDIDATES}, got "
+                             f"{n_samples!r} (include_greedy = {include_greedy})")
+        if not (isinstance(utility, str) and utility in self.UTILITIES):
+            raise ValueError(f"MBR utility must be one of {self.UTILITIES}, got {utility!r}")
+        if not is_int(order) or not 1 <= order <= self.MAX_ORDER:
+            raise ValueError(f"MBR order must be an int in [1, {self.MAX_ORDER}], got {order!r}")
+        self.top_k, self.top_p, self.temperature = check_sampling(top_k, top_p, temperature)
+        self.end_id, self.n_samples, self.utility, self.order = int(end_id), int(n_samples), utility, int(order)
+        self.include_greedy = bool(include_greedy)
+
+    @property
+    def kind(self):
+        return self.UTILITIES.index(self.utility)
+
+    @property
+    def n_candidates(self):
+        return self.n_samples + int(self.include_greedy)
+
+    def __repr__(self):
+        return (f"MBR(end_id={self.end_id}, n_samples={self.n_samples}, utility={self.utility!r}, order={self.order}, "
+                f"include_greedy={self.include_greedy}, temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p})")
+
+
 class DecodeConstraints:
     """Constraints on caption decoding, for the ``constraints=`` keyword of greedy_predict, sample_predict and beam_search
     of nic.NIC and lc_nic.NIC; applied to each step's logits on the device, in front of the softmax, from the tokens the
@@ -1050,10 +1101,10 @@ class ModelBase:
     use_seq_lstm = True         # False: the per-step LSTM kernels; INTEGRATION.md 4, disable_seq_lstm()
     skip_frozen_work = True     # False: the gradient launches of frozen variables run as ever (the table alone freezes); tests/test_host_finetune.py
 
-    # the static buffers of _ConstrainedDecode and of _ConsensusDecode / _GuidanceDecode: a dict on the instance from the first
-    # such decode on (_decode_bufs).  Not made in the constructor: the tests tell "this model never ran one" by the instance
-    # not having the attribute
-    _con_bufs = _cons_bufs = None
+    # the static buffers of _ConstrainedDecode, of _ConsensusDecode / _GuidanceDecode and of mbr_decode: a dict on the instance
+    # from the first such decode on (_decode_bufs).  Not made in the constructor: the tests tell "this model never ran one"
+    # by the instance not having the attribute
+    _con_bufs = _cons_bufs = _mbr_bufs = None
 
     GUARD = 7       # slot of ``met`` that carries the device guard word of the step (see Metrics)
     METRIC_RING = 1024      # rows of the metrics ring: a step's Metrics stay readable for this many further training steps
@@ -3064,7 +3115,7 @@ class ModelBase:
         return w
 
     def _decode_bufs(self, name):
-        """the buffer dict ``name`` (_con_bufs / _cons_bufs), made on first use"""
+        """the buffer dict ``name`` (_con_bufs / _cons_bufs / _mbr_bufs), made on first use"""
         if getattr(self, name) is None:
             setattr(self, name, {})
         return getattr(self, name)
@@ -3426,6 +3477,63 @@ class ModelBase:
             v = st["views"][Cr] = self._score_shape(st, R, T)
             v["rep"] = torch.arange(B, dtype=torch.int32, device=self.device).repeat_interleave(Cr).view(R, 1)
         return v
+
+    # ------------------------------------------------------------------ minimum Bayes risk decoding
+    def mbr_decode(self, img_input, a0, c0, start_seq, max_len, mbr, sample_step=0, constraints=None, consensus=None,
+                   guidance=None, return_candidates=False):
+        """Minimum Bayes risk decoding (``mbr``: a model_base.MBR, whose docstring defines it): per scan N = mbr.n_samples
+        captions are sampled, and of them -- and the greedy caption, with mbr.include_greedy -- the one with the highest
+        expected utility against the N samples is returned (definition: tnt_mbr_select_f32 in include/tnt_hip.h).
+        Candidate c < N is exactly what sample_predict(..., temperature, top_k, top_p of ``mbr``, sample_step=sample_step
+        + c) draws: the same captured decode replayed with another stream step; candidate N is greedy_predict's caption,
+        a hypothesis only.  Each decode's ids are copied on the device into slot c of one (Nc, max_len, rows) buffer, and one
+        tnt_mbr_select_f32 launch chooses: no token id visits the host before it.  ``constraints``, ``consensus``,
+        ``guidance`` go to every candidate decode unchanged; with consensus or guidance the launch reads the M mixed rows of
+        the G * M member rows.  Refused: max_len > 64 (ValueError), a data-parallel model (NotImplementedError).
+        Returns (ids (M, max_len, 1) int64, info): info["expected"] (M, Nc) float32, info["best"] (M,) int32, and with
+        ``return_candidates`` info["candidates"] (M, Nc, max_len) int64."""
+        if not isinstance(mbr, MBR):
+            raise ValueError(f"mbr must be a model_base.MBR, got {mbr!r}")
+        if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)) or not 1 <= max_len <= mbr.MAX_LEN:
+            raise ValueError(f"mbr_decode holds at most {mbr.MAX_LEN} tokens per caption: max_len must be an int in "
+                             f"[1, {mbr.MAX_LEN}], got {max_len!r}")
+        if isinstance(sample_step, bool) or not isinstance(sample_step, (int, np.integer)):
+            raise ValueError(f"sample_step must be an int, got {sample_step!r}")
+        if self.grad_sync is not None:
+            raise NotImplementedError("mbr_decode has no data-parallel schedule: decode on one device")
+        max_len, N, Nc = int(max_len), mbr.n_samples, mbr.n_candidates
+        M = int(np.asarray(start_seq).reshape(-1).shape[0])
+        kw = dict(constraints=constraints, consensus=consensus, guidance=guidance)
+        st = None
+        for c in range(Nc):
+            filt = (mbr.temperature, mbr.top_k, mbr.top_p, int(sample_step) + c) if c < N else None
+            ids = self._mbr_candidate(img_input, a0, c0, start_seq, max_len, filt, **kw)      # (max_len, rows) int32, static
+            if st is None:
+                st = self._mbr_state(M, Nc, max_len, int(ids.shape[1]))
+            st["cand"][c].copy_(ids)
+        rows = st["cand"].shape[2]
+        self.be.mbr_select(st["cand"], rows, M, Nc, N, max_len, mbr.end_id, mbr.order, mbr.kind, st["expected"], st["best"],
+                           st["out"], M)
+        info = dict(expected=st["expected"].cpu().numpy(), best=st["best"].cpu().numpy())
+        if return_candidates:
+            info["candidates"] = st["cand"][:, :, :M].permute(2, 0, 1).contiguous().cpu().numpy().astype(np.int64)
+        return st["out"].t().contiguous().cpu().numpy().astype(np.int64)[:, :, None], info
+
+    def _mbr_candidate(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
+        """one candidate decode of mbr_decode: sample_predict's decode with ``filt`` = (temperature, top_k, top_p,
+        sample_step), greedy_predict's with None.  Returns the decode's static device ids (max_len, rows) int32"""
+        raise NotImplementedError(f"{type(self).__name__} has no minimum Bayes risk decoding")
+
+    def _mbr_state(self, M, Nc, max_len, rows):
+        """static buffers per (M, Nc, max_len, rows): cand (Nc, max_len, rows) int32, the candidates' ids; expected (M, Nc);
+        best (M,) int32; out (max_len, M) int32, the chosen captions"""
+        bufs = self._decode_bufs("_mbr_bufs")
+        key = (M, Nc, max_len, rows)
+        if key not in bufs:
+            f, i32 = self._f, torch.int32
+            bufs[key] = dict(cand=f(Nc, max_len, rows, dtype=i32), expected=f(M, Nc), best=f(M, dtype=i32),
+                             out=f(max_len, M, dtype=i32))
+        return bufs[key]
 
     def _dp_mean_logs(self, logs):
         """epoch logs averaged over the data-parallel ranks (same keys on every rank, sorted)"""

@@ -990,6 +990,10 @@ class NIC(ModelBase):
             self._run_captured(("sample", B, max_len) + tuple(filt[:3]) + ckey, run)
         return choice.probs, choice.ids
 
+    def _mbr_candidate(self, img_input, a0, c0, start_seq, max_len, filt, constraints=None, consensus=None, guidance=None):
+        """ModelBase.mbr_decode's candidate decode: sample_predict's or (``filt`` None) greedy_predict's, ids left on the device"""
+        return self._decode(img_input, a0, c0, start_seq, max_len, filt, constraints, consensus, guidance)[1]
+
     # ------------------------------------------------------------------ caption scoring (ModelBase.score_captions)
     def _score_refuse(self):
         if self.grad_sync is not None:

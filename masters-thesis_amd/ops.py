@@ -918,6 +918,14 @@ class HipBackend:
         self._call(self.lib.tnt_guidance_mix_f32, "tnt_guidance_mix_f32", _p(logits), ld, V, Rm, float(scale), float(plaus),
                    _p(mix), ldm, _p(token), self._s())
 
+    def mbr_select(self, ids, ld, B, Nc, Nr, L, end_id, order, kind, expected, best, out_ids=None, ldo=0, match=None,
+                   util=None):
+        """minimum Bayes risk selection: of the Nc candidate captions ids [Nc][L][ld] of each of the B scans the one with the
+        highest expected n-gram utility (kind 0 ngram-f, 1 bleu) against the first Nr (tnt_mbr_select_f32; definition in
+        include/tnt_hip.h); out_ids, match and util are nullable"""
+        self._call(self.lib.tnt_mbr_select_f32, "tnt_mbr_select_f32", _p(ids), ld, B, Nc, Nr, L, int(end_id), int(order),
+                   int(kind), _p(expected), _p(best), _p(out_ids), int(ldo), _p(match), _p(util), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
