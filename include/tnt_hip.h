@@ -920,6 +920,47 @@ int32_t tnt_guidance_mix_f32(const float* logits, int32_t ld, int32_t V, int32_t
 int32_t tnt_mbr_select_f32(const int32_t* ids, int32_t ld, int32_t B, int32_t Nc, int32_t Nr, int32_t L, int32_t end_id,
                            int32_t order, int32_t kind, float* expected, int32_t* best, int32_t* out_ids, int32_t ldo,
                            int32_t* match, float* util, void* stream);
+/* Caption rewards of the self-critical step, scored on the device (nic.NIC(self_critical=SelfCritical(score_on="device")));
+ * restated by tests/reward_oracle.py): the CIDEr-D or BLEU-4 score of the K sampled captions of each of B scans (and of its
+ * greedy caption) against the scan's references, and the advantages tnt_scst_cce_f32 reads.  Library-defined:
+ *  - Candidates.  R = B*K samples, row b*K + k = sample k of scan b: its T tokens are fed[r*T + 1 .. r*T + T-1] and then
+ *    last[r] (the layout tnt_scst_cce_f32 reads; fed[r*T] is never read).  baseline 0 ("greedy") adds candidate K of scan
+ *    b, greedy[t*ldg + b], t < T, ldg >= B; greedy is not read with baseline 1.
+ *  - References.  refs [B][M][Lr] int32, zero padded: reference j < n_refs[b] of scan b at position t is
+ *    refs[(b*M + j)*Lr + t]; n_refs[b] is clamped to [0, M]; the rows j >= n_refs[b] are never read.
+ *  - Caption.  A candidate's or a reference's caption is its tokens before the first end_id or 0 (SelfCritical.truncate's
+ *    rule); end_id < 0: only 0 terminates.  Its length is len.  counted[r] = min(len_r + 1, T): the positions up to and
+ *    including the first terminator (SelfCritical.counted).
+ *  - Tokens are only compared, or packed into a key: any int32 value is safe.  tf_x(g): the number of times the k-gram g
+ *    (k = 1..4) occurs in caption x, an exact integer, full int32 words compared.
+ *  - Table (kind 0).  The k-gram w0..w(k-1) of words in [1, 65535] has the key w0 | w1<<16 | w2<<32 | w3<<48 (missing high
+ *    words zero).  keys [n_keys] uint64, strictly ascending; idf [n_keys] float64; params = {log(ndoc), sigma} float64.
+ *    idf(g) = idf[i] where keys[i] is g's key, and log(ndoc) for a gram that is not in the table or holds a word outside
+ *    [1, 65535].  n_keys = 0 is legal (keys and idf are not read then).  evaluate.RewardTable builds it.
+ *  - kind 0 (CIDEr-D, evaluate.CiderD._score with the table's frequencies), all float64.  For candidate c, reference j,
+ *    order k: num = sum over the distinct k-grams g of c, in the order of their first positions, of
+ *    min(tf_c(g)*idf(g), tf_j(g)*idf(g)) * tf_j(g)*idf(g); nrm_x = sum over the distinct k-grams of x of (tf_x(g)*idf(g))^2;
+ *    sim(c, j) = (sum_k (nrm_c*nrm_j != 0 ? num / sqrt(nrm_c*nrm_j) : 0) * exp(-(len_c - len_j)^2 / (2 sigma^2))) / 4;
+ *    score(c) = 10 * (sum_j sim(c, j)) / n_refs in ascending j; 0 with no references.
+ *  - kind 1 (BLEU-4, evaluate.sentence_bleu(refs, c, weights=(0.25,)*4, smoothing="method1", epsilon=0.1)), float64:
+ *    n_k = sum over the distinct k-grams g of c of min(tf_c(g), max_j tf_j(g)); 0 for an empty c, n_1 = 0 or no references;
+ *    else bp * exp(sum_k 0.25 * log((n_k or 0.1 where n_k = 0) / max(1, len_c - k + 1))), bp = 1 when len_c > rl, else
+ *    exp(1 - rl/len_c), rl the reference length closest to len_c, the shorter on a tie.
+ *  - adv [R] float32: adv[b*K + k] = float32(score(k) - base): base = score(greedy) with baseline 0; with baseline 1
+ *    ("mean") ((sum of the scan's K sample scores in ascending k) - score(k)) / (K - 1), K >= 2.
+ *  - score (nullable) [B][K+1] float64: the K sample scores, then the greedy caption's (0 with baseline 1).
+ *  - One workgroup per scan, its rows staged once in LDS; counting, first-occurrence detection and the binary search of
+ *    keys are integer work, everything floating-point is float64 and only adv is rounded; no atomics, no scratch memory,
+ *    fixed summation orders: deterministic.
+ * TNT_BADARG for B <= 0, T or Lr outside [1, 64], K outside [1, 16] (or K < 2 with baseline 1), M outside [1, 8], kind or
+ * baseline other than 0 or 1, n_keys < 0, null fed / last / refs / n_refs / adv / counted, null greedy or ldg < B with
+ * baseline 0, null params with kind 0, null keys / idf with kind 0 and n_keys > 0, any output overlapping an input or
+ * another output anywhere in their extents; nothing is launched then. */
+int32_t tnt_caption_reward_f32(const int32_t* fed, int32_t T, const int32_t* last, const int32_t* greedy, int32_t ldg,
+                               const int32_t* refs, const int32_t* n_refs, int32_t M, int32_t Lr, const uint64_t* keys,
+                               const double* idf, int32_t n_keys, const double* params, int32_t B, int32_t K,
+                               int32_t end_id, int32_t kind, int32_t baseline, float* adv, double* score,
+                               int32_t* counted, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

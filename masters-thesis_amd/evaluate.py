@@ -15,7 +15,10 @@
   nltk is not installable here, so the published algorithm (Papineni et al. 2002; Chen & Cherry 2014 method 1:
   a zero n-gram match count becomes epsilon = 0.1) is restated.  PARITY UNPINNED against nltk itself; pinned by
   the worked example of the nltk documentation (tests/test_data_fit.py).
-Host-side Python throughout: nothing here is on the per-step hot path.
+* ``RewardTable`` / ``device_scores``   -- CiderD's document frequencies as the sorted key / idf table that
+  tnt_caption_reward_f32 reads (``SelfCritical(score_on="device")``), and that kernel's scores of lists of token ids.
+Host-side Python throughout: nothing here is on the per-step hot path (``pack_references`` fills a pinned array per
+device-scored self-critical step).
 """
 import math
 import os
@@ -353,6 +356,134 @@ class CiderD:
         """the score of one candidate against its references (one document: the scorer's corpus frequencies, or,
         without a corpus, these references alone)"""
         return float(self.batch_scores([[candidate]], [references])[0][0])
+
+
+# ---------------------------------------------------------------------------------------------------- rewards on the device
+REWARD_KINDS = {"cider-d": 0, "bleu4": 1}
+REWARD_MAX_SAMPLES, REWARD_MAX_REFS, REWARD_MAX_LEN = 16, 8, 64        # tnt_caption_reward_f32's limits: K, M, T and Lr
+
+
+def gram_key(gram):
+    """the 64-bit table key of a k-gram (k <= 4) of token ids in [1, 65535]: w0 | w1<<16 | w2<<32 | w3<<48, missing high
+    words zero.  Id 0 never occurs inside a gram, so the orders share one key space."""
+    key = 0
+    for i, w in enumerate(gram):
+        key |= int(w) << (16 * i)
+    return key
+
+
+class RewardTable:
+    """The document frequencies of ``CiderD(corpus)`` as tnt_caption_reward_f32 reads them (definition: include/tnt_hip.h):
+    ``keys`` uint64, strictly ascending (gram_key of every n-gram of the corpus, n = 1..4), ``idf`` float64 with
+    idf = log(ndoc) - log(max(1, df)) computed exactly as CiderD._vec does, ``params`` = {log(ndoc), sigma} float64.
+    A gram that is not in the table has df = 0: its idf is log(ndoc).  Token ids outside [1, 65535] (a vocabulary above
+    65536; ``vocab_size`` states it without a corpus that uses it) are refused: a key holds 16 bits per word.
+    ``device(dev)`` uploads the three arrays once and caches them."""
+
+    def __init__(self, corpus, n=4, sigma=6.0, vocab_size=None):
+        if int(n) != 4:
+            raise ValueError(f"the device scorer's n-gram order is 4, got n = {n!r}")
+        if vocab_size is not None and int(vocab_size) > 65536:
+            raise ValueError(f"a reward table packs 16 bits per token id: vocab_size {vocab_size} is above 65536")
+        cd = CiderD(corpus, n=4, sigma=sigma)
+        if cd._df is None:
+            raise ValueError("a reward table needs a corpus (a list of documents, each a list of tokenised references)")
+        entries = []
+        for gram, df in cd._df.items():
+            for w in gram:
+                if not isinstance(w, (int, np.integer)) or not 1 <= w <= 65535:
+                    raise ValueError(f"a reward table packs 16 bits per token id, each in [1, 65535]: the corpus holds {w!r}")
+            entries.append((gram_key(gram), cd._log_docs - math.log(max(1.0, float(df)))))
+        entries.sort()
+        self.keys = np.array([k for k, _ in entries], np.uint64)
+        self.idf = np.array([v for _, v in entries], np.float64)
+        self.params = np.array([cd._log_docs, cd.sigma], np.float64)
+        self._dev = {}
+
+    def __len__(self):
+        return int(self.keys.size)
+
+    def device(self, dev):
+        """(keys, idf, params) on ``dev``, uploaded once; keys travel as the int64 tensor with the same bits"""
+        import torch
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = (torch.from_numpy(self.keys.view(np.int64).copy()).to(dev),
+                                  torch.from_numpy(self.idf.copy()).to(dev), torch.from_numpy(self.params.copy()).to(dev))
+        return t
+
+
+def pack_references(references, refs_out, n_out):
+    """B lists of tokenised references into the zero-padded refs_out (B, M, Lr) int32 and n_out (B,) int32 (numpy arrays
+    or CPU tensors' numpy views), tnt_caption_reward_f32's layout.  More than M references or a reference longer than Lr
+    raises ValueError, before anything is written."""
+    B, M, Lr = refs_out.shape
+    if len(references) != B:
+        raise ValueError(f"{len(references)} reference lists for {B} scans")
+    docs = [[[int(w) for w in r] for r in doc] for doc in references]
+    for doc in docs:
+        if len(doc) > M:
+            raise ValueError(f"the device scorer holds at most {M} references per scan, got {len(doc)}")
+        for r in doc:
+            if len(r) > Lr:
+                raise ValueError(f"the device scorer holds at most {Lr} tokens per reference, got {len(r)}")
+    refs_out[...] = 0
+    for b, doc in enumerate(docs):
+        n_out[b] = len(doc)
+        for j, r in enumerate(doc):
+            refs_out[b, j, :len(r)] = r
+
+
+def device_scores(candidates, references, kind="cider-d", table=None, end_id=-1, device="cuda"):
+    """The scores tnt_caption_reward_f32 gives lists of token ids: ``candidates`` one list of at most 16 candidate
+    token sequences per document, ``references`` one list of at most 8 reference sequences per document, as
+    CiderD.batch_scores takes them; sequences hold at most 64 tokens and are cut at their first ``end_id`` or 0
+    (end_id < 0: only 0).  kind "cider-d" needs ``table`` (a RewardTable); "bleu4" takes none.  One launch with
+    K = the largest candidate count; returns one float64 array of scores per document."""
+    import torch
+    from . import ops
+    if kind not in REWARD_KINDS:
+        raise ValueError(f"kind must be one of {tuple(REWARD_KINDS)}, got {kind!r}")
+    if kind == "cider-d" and not isinstance(table, RewardTable):
+        raise ValueError("kind 'cider-d' needs table=RewardTable(corpus)")
+    if len(candidates) != len(references):
+        raise ValueError(f"{len(candidates)} candidate lists for {len(references)} documents")
+    B = len(candidates)
+    if B == 0:
+        return []
+    cands = [[[int(w) for w in c] for c in doc] for doc in candidates]
+    K = max(1, max(len(doc) for doc in cands))
+    T = max(1, max((len(c) for doc in cands for c in doc), default=1))
+    if K > REWARD_MAX_SAMPLES or T > REWARD_MAX_LEN:
+        raise ValueError(f"the device scorer holds at most {REWARD_MAX_SAMPLES} candidates per document of at most "
+                         f"{REWARD_MAX_LEN} tokens, got {K} of {T}")
+    M = max(1, max(len(doc) for doc in references))
+    Lr = max(1, max((len(r) for doc in references for r in doc), default=1))
+    if M > REWARD_MAX_REFS or Lr > REWARD_MAX_LEN:
+        raise ValueError(f"the device scorer holds at most {REWARD_MAX_REFS} references per document of at most "
+                         f"{REWARD_MAX_LEN} tokens, got {M} of {Lr}")
+    refs, n_refs = np.zeros((B, M, Lr), np.int32), np.zeros(B, np.int32)
+    pack_references(references, refs, n_refs)
+    w = np.zeros((B * K, T + 1), np.int32)                 # column 0: the start token's place, never read
+    for b, doc in enumerate(cands):
+        for k, c in enumerate(doc):
+            w[b * K + k, 1:1 + len(c)] = c
+    dev = torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    fed, last = up(w[:, :T]), up(w[:, T])
+    greedy = torch.zeros(T, B, dtype=torch.int32, device=dev)
+    adv = torch.zeros(B * K, dtype=torch.float32, device=dev)
+    score = torch.zeros(B, K + 1, dtype=torch.float64, device=dev)
+    counted = torch.zeros(B * K, dtype=torch.int32, device=dev)
+    keys, idf, params = table.device(dev) if kind == "cider-d" else (None, None, None)
+    n_keys = len(table) if kind == "cider-d" else 0
+    if n_keys == 0:
+        keys = idf = None
+    ops.backend().caption_reward(fed, T, last, greedy, B, up(refs), up(n_refs), M, Lr, keys, idf, n_keys, params, B, K,
+                                 int(end_id), REWARD_KINDS[kind], 0, adv, score, counted)
+    s = score.cpu().numpy()
+    return [s[b, :len(doc)].copy() for b, doc in enumerate(cands)]
 
 
 # ---------------------------------------------------------------------------------------------------- likelihood metrics

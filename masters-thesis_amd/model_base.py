@@ -174,12 +174,19 @@ class SelfCritical:
                  (candidate_ids, reference_id_lists) -> float
       corpus     tokenised reference captions, one list of references per scan: CIDEr-D's document frequencies; None takes
                  them from each batch's references
+      score_on   "host": the sampled ids visit the host in the middle of the step and ``reward`` is scored in Python;
+                 "device": one tnt_caption_reward_f32 launch between the rollout and the update scores them (definition:
+                 include/tnt_hip.h), no id and no reward crosses the bus and the host does not wait.  On the device
+                 ``reward`` is "cider-d" or "bleu4", "cider-d" needs ``corpus`` (evaluate.RewardTable holds its document
+                 frequencies), a step takes at most 8 references per scan of at most 64 tokens, and a reference is cut at
+                 its first end_id or 0 like a candidate
     Bad arguments raise ValueError here, before any launch."""
 
     BASELINES = ("greedy", "mean")
     REWARDS = ("cider-d", "bleu4")
+    SCORE_ON = ("host", "device")
 
-    def __init__(self, end_id, n_samples=1, baseline="greedy", reward="cider-d", corpus=None):
+    def __init__(self, end_id, n_samples=1, baseline="greedy", reward="cider-d", corpus=None, score_on="host"):
         is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
         if not is_int(end_id) or end_id < 1:
             raise ValueError(f"self-critical end_id must be an int >= 1 (the <end> index), got {end_id!r}")
@@ -191,6 +198,14 @@ class SelfCritical:
             raise ValueError("self-critical baseline 'mean' needs n_samples >= 2 (the other samples of the scan)")
         if not (callable(reward) or (isinstance(reward, str) and reward in self.REWARDS)):
             raise ValueError(f"self-critical reward must be one of {self.REWARDS} or a callable, got {reward!r}")
+        if not (isinstance(score_on, str) and score_on in self.SCORE_ON):
+            raise ValueError(f"self-critical score_on must be one of {self.SCORE_ON}, got {score_on!r}")
+        if score_on == "device":
+            if not isinstance(reward, str):
+                raise ValueError(f"score_on='device' scores {self.REWARDS} only: a callable reward runs on the host")
+            if reward == "cider-d" and corpus is None:
+                raise ValueError("score_on='device' with reward 'cider-d' needs corpus=: the batch-local document "
+                                 "frequencies of corpus=None would have to be rebuilt on the host every step")
         if corpus is not None:
             try:
                 corpus = [[list(r) for r in doc] for doc in corpus]
@@ -198,10 +213,14 @@ class SelfCritical:
                 raise ValueError("self-critical corpus must be None or a list of documents, each a list of tokenised "
                                  "references") from None
         self.end_id, self.n_samples, self.baseline, self.reward, self.corpus = int(end_id), int(n_samples), baseline, reward, corpus
-        self._cider = None
+        self.score_on = score_on
+        self._cider = self.table = None
         if reward == "cider-d":
             from .evaluate import CiderD
             self._cider = CiderD(corpus)
+        if score_on == "device" and reward == "cider-d":
+            from .evaluate import RewardTable
+            self.table = RewardTable(self.corpus)      # the kernel's view of _cider's frequencies, uploaded on first use
 
     def truncate(self, ids):
         """the tokens of a caption before its first terminator (end_id or 0)"""
@@ -259,7 +278,8 @@ class SelfCritical:
 
     def __repr__(self):
         return (f"SelfCritical(end_id={self.end_id}, n_samples={self.n_samples}, baseline={self.baseline!r}, "
-                f"reward={self.reward!r}, corpus={'None' if self.corpus is None else f'<{len(self.corpus)} documents>'})")
+                f"reward={self.reward!r}, corpus={'None' if self.corpus is None else f'<{len(self.corpus)} documents>'}"
+                + (f", score_on={self.score_on!r})" if self.score_on != "host" else ")"))
 
 
 class MBR:

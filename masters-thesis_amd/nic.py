@@ -21,6 +21,7 @@ from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
                          _TokenChoice, _BeamDecode, EncGram, EncUpdate, StepRoute)
+from .evaluate import REWARD_KINDS, REWARD_MAX_LEN, REWARD_MAX_REFS, pack_references
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
 
@@ -77,6 +78,9 @@ class NIC(ModelBase):
                                  f"(tnt_scheduled_feedback_f32), got {E}")
             if self_critical.end_id >= V:
                 raise ValueError(f"self-critical end_id {self_critical.end_id} is not below vocab_size {V}")
+            if self_critical.score_on == "device" and V > 65536:
+                raise ValueError(f"self-critical score_on='device' packs 16 bits per token id (evaluate.RewardTable): "
+                                 f"vocab_size {V} is above 65536")
         self.self_critical = self_critical
         self._rollout_ss = ScheduledSampling.linear(1.0, 0.0, 1.0, mode="sample") if self_critical is not None else None
         self.ldx, self.ldV = _r4(N), _r4(V)
@@ -745,6 +749,14 @@ class NIC(ModelBase):
                                greedy=torch.zeros(T, B, dtype=i32, device=dev), last=torch.zeros(R, dtype=i32, device=dev),
                                adv=f(R), h_cap=h(R, T), h_last=h(R), h_greedy=h(T, B), h_ref=h(B, T),
                                h_adv=h(R, dtype=torch.float32))
+        if self.self_critical.score_on == "device":
+            # tnt_caption_reward_f32's side: the references at the kernel's largest extents, so that the launch is the same
+            # whatever a step's references are, the float64 scores and the counted positions
+            M, Lr = REWARD_MAX_REFS, REWARD_MAX_LEN
+            st.update(refs=torch.zeros(B, M, Lr, dtype=i32, device=dev), n_refs=torch.zeros(B, dtype=i32, device=dev),
+                      h_refs=h(B, M, Lr), h_nrefs=h(B), refs_own=False, refs_sent=None,
+                      score=torch.zeros(B, self.self_critical.n_samples + 1, dtype=torch.float64, device=dev),
+                      counted=torch.zeros(R, dtype=i32, device=dev))
         return st
 
     def _stage_scst(self, inputs):
@@ -804,12 +816,54 @@ class NIC(ModelBase):
         """tnt_scst_cce_f32 (loss rows, dlogits in place of the logits), the teacher-forced backward over the sampled ids,
         and the fused update: the L2 terms, the clip and Adam of train_step"""
         st = self._scst
+        if self.self_critical.score_on == "device":
+            self._scst_reward(R, T)
         with self._deferring():
             self.be.scst_cce(self.logits, self.ldV, self.V, self.cap, T, st["last"], st["adv"], self.self_critical.end_id,
                              self.loss_row, None, self.logits, R, 1.0 / R)
             self._sum2(self.loss_row, self.met[0:1], self.loss_row, self.met[1:2], T * R, 1.0 / R)
             self._backward(R, T)
         self._update_fused(self.met[2:3])
+
+    def _scst_reward(self, R, T):
+        """score_on="device": the rewards of the R sampled captions (and the greedy captions) against the staged references
+        and the advantages into st["adv"], one tnt_caption_reward_f32 launch on buffers that are static per (B, T)"""
+        sc, st = self.self_critical, self._scst
+        B = R // sc.n_samples
+        keys = idf = params = None
+        n_keys = 0
+        if sc.table is not None:
+            keys, idf, params = sc.table.device(self.device)
+            n_keys = len(sc.table)
+            if n_keys == 0:
+                keys = idf = None
+        greedy = sc.baseline == "greedy"
+        self.be.caption_reward(self.cap, T, st["last"], st["greedy"] if greedy else None, B, st["refs"], st["n_refs"],
+                               REWARD_MAX_REFS, REWARD_MAX_LEN, keys, idf, n_keys, params, B, sc.n_samples, sc.end_id,
+                               REWARD_KINDS[sc.reward], 0 if greedy else 1, st["adv"], st["score"], st["counted"])
+
+    def _scst_stage_refs(self, references, B, T):
+        """score_on="device": the step's references into st["refs"] (B, 8, 64) / st["n_refs"].  ``references`` None: each
+        row's own staged caption, columns 1.., copied on the device (the kernel cuts it at its first end_id or 0);
+        else B lists of references, packed into pinned host arrays and copied over without waiting.  More than 8
+        references or one longer than 64 tokens raises ValueError, before any launch."""
+        st = self._scst
+        if references is None:
+            if not st["refs_own"]:
+                st["refs"].zero_()
+                st["n_refs"].fill_(1)
+                st["refs_own"] = True
+            st["refs"][:, 0, :T - 1].copy_(st["cap"][:, 1:])
+            return
+        if st["refs_sent"] is not None:
+            st["refs_sent"].synchronize()          # the last step's copy has read the pinned arrays (long done)
+        pack_references(references, st["h_refs"].numpy(), st["h_nrefs"].numpy())
+        st["refs_own"] = False
+        st["refs"].copy_(st["h_refs"], non_blocking=True)
+        st["n_refs"].copy_(st["h_nrefs"], non_blocking=True)
+        if self.device.type == "cuda":
+            st["refs_sent"] = torch.cuda.Event()
+            st["refs_sent"].record()
 
     def _scst_round_trip(self, B, T):
         """the step's one synchronisation: sampled (R, T), greedy (T, B) and staged caption (B, T) ids to the host"""
@@ -832,8 +886,10 @@ class NIC(ModelBase):
         decode of the B rows, ids kept on the device]; the rollout: the training forward over the R rows with every token
         sampled (Philox sites S_SS_DRAW + j and S_SCST_LAST, stream step drop_step); one device-to-host copy of the ids,
         the rewards and advantages on the host, the advantages back to the device; then tnt_scst_cce_f32, the backward
-        and the update as one recorded segment.  Each device segment is replayed as a launch plan or a hipGraph like
-        train_step.  Metrics: loss (the policy-gradient loss), L2, reward (mean sampled reward), baseline (mean baseline
+        and the update as one recorded segment.  With SelfCritical(score_on="device") the middle stays on the device
+        instead: the references are staged beside the batch (_scst_stage_refs) and the update segment opens with one
+        tnt_caption_reward_f32 launch that writes the advantages (_scst_device_tail); nothing waits for the stream.
+        Each device segment is replayed as a launch plan or a hipGraph like train_step.  Metrics: loss (the policy-gradient loss), L2, reward (mean sampled reward), baseline (mean baseline
         reward), sample_len (mean number of tokens the loss counts)."""
         sc = self.self_critical
         if sc is None:
@@ -846,12 +902,16 @@ class NIC(ModelBase):
         if references is not None and len(references) != B:
             raise ValueError(f"references: {len(references)} reference lists for a batch of {B}")
         R = B * sc.n_samples
+        if sc.score_on == "device":
+            self._scst_stage_refs(references, B, T)
         self._sync_lr()
         self._enc_grad_stale = None
         run = self._step_runner()
         if sc.baseline == "greedy":
             run(("scst_greedy", B, T), lambda: self._scst_greedy(B, T))
         run(("scst_rollout", R, T), lambda: self._scst_rollout(R, T))
+        if sc.score_on == "device":
+            return self._scst_device_tail(run, B, R, T)
         samples, greedy, cap0 = self._scst_round_trip(B, T)
         if references is None:
             references = [[sc.truncate(row[1:])] for row in cap0]
@@ -865,6 +925,25 @@ class NIC(ModelBase):
         m = self._met_snapshot(ring)
         return self._lr_metric(self._metrics_from(m, loss=0, L2=2, reward=float(reward.mean()), baseline=float(base.mean()),
                                                   sample_len=float(counted.mean())))
+
+    def _scst_device_tail(self, run, B, R, T):
+        """score_on="device": behind the rollout the update segment, whose first launch is tnt_caption_reward_f32 (recorded
+        into the segment's plan or hipGraph with it): no id and no reward visits the host and nothing waits for the
+        stream.  The reward, baseline and sample_len metrics are means of the kernel's float64 scores and counted
+        positions, taken on the device behind the update and read with the step's metrics."""
+        sc, st = self.self_critical, self._scst
+        K = sc.n_samples
+        ring = self._run_step(run, ("scst_update", R, T), lambda: self._scst_update(R, T))
+        self._enc_grad_stale = self._enc_last_fused
+        self.optimizer.iterations += 1
+        m = self._met_snapshot(ring)
+        reward = st["score"][:, :K]
+        if sc.baseline == "greedy":
+            base = st["score"][:, K].mean()
+        else:
+            base = ((reward.sum(1, keepdim=True) - reward) / (K - 1)).mean()
+        return self._lr_metric(self._metrics_from(m, loss=0, L2=2, reward=reward.mean(), baseline=base,
+                                                  sample_len=st["counted"].to(torch.float64).mean()))
 
     def test_step(self, data):
         """NIC.test_step (NIC.py:254-299)."""

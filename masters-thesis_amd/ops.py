@@ -926,6 +926,17 @@ class HipBackend:
         self._call(self.lib.tnt_mbr_select_f32, "tnt_mbr_select_f32", _p(ids), ld, B, Nc, Nr, L, int(end_id), int(order),
                    int(kind), _p(expected), _p(best), _p(out_ids), int(ldo), _p(match), _p(util), self._s())
 
+    def caption_reward(self, fed, T, last, greedy, ldg, refs, n_refs, M, Lr, keys, idf, n_keys, params, B, K, end_id, kind,
+                       baseline, adv, score=None, counted=None):
+        """the self-critical step's rewards on the device: the CIDEr-D (kind 0, against the table keys / idf / params of
+        evaluate.RewardTable) or BLEU-4 (kind 1) score of the K sampled captions of each of the B scans and of its greedy
+        caption (baseline 0; 1: the mean of the scan's other samples) against refs [B][M][Lr], the advantages adv [B*K],
+        the scores [B][K+1] float64 and the counted positions [B*K] (tnt_caption_reward_f32; definition in
+        include/tnt_hip.h); greedy, keys, idf, params and score are nullable"""
+        self._call(self.lib.tnt_caption_reward_f32, "tnt_caption_reward_f32", _p(fed), int(T), _p(last), _p(greedy), int(ldg),
+                   _p(refs), _p(n_refs), int(M), int(Lr), _p(keys), _p(idf), int(n_keys), _p(params), int(B), int(K),
+                   int(end_id), int(kind), int(baseline), _p(adv), _p(score), _p(counted), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
