@@ -1651,6 +1651,21 @@ int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const float* W2, 
                                uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
                                uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, uint32_t* sync,
                                float* guard_out, void* stream);
+/* the _ext launch with the gradient of the initial cell state as one more output: dc0 [B][U] (nullable) is WRITTEN behind
+ * the step loop with what the cell backward of step 0 leaves for the state in front of it,
+ *   dc0[b][u] = dc_0[b][u] * f_0[b][u]     (dc_0 the cell-state gradient of step 0, f_0 its forget gate),
+ * by the thread that owns the element, rows b < B only.  The gradient of the initial hidden state is not formed here: it is
+ * dz[0] Ur^T + dqpre[0] W2^T, two products over outputs of this launch.  dc0 == NULL: the three entries above, bit for bit
+ * (they forward here). */
+int32_t tnt_lc_seq_bwd_init_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+                                const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
+                                float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
+                                const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
+                                int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
+                                float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
+                                uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
+                                uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, float* dc0,
+                                uint32_t* sync, float* guard_out, void* stream);
 
 /* ---- the attention layer's hoisted first Dense (P = LeakyReLU(F W1 + b1), attention.py:32) backward, behind the chain:
  * with dP [rows][A] the score gradient accumulated over the T steps and Ppre its pre-activation:
@@ -1694,6 +1709,33 @@ int32_t tnt_attention_metric_f32(const float* alpha, float* out, float* work,
  * atomics, the same bits every time.  work: rows * ceil(R / 256) floats with rows = B for axis 0 and T for axis 1. */
 int32_t tnt_attention_coverage_f32(const float* alpha, int64_t tstride, int32_t T, int32_t B, int32_t R, int32_t axis,
                                    float coef, float* ext, float* out, float* work, void* stream);
+
+/* ---- learned initial LSTM state of the attention model (Xu et al. 2015, section 3.1.2: "the initial memory state and
+ * hidden state of the LSTM are predicted by an average of the annotation vectors fed through two separate MLPs"; the
+ * reference's learn_init_state, lc_NIC.py:169-173, whose two layers it never builds).  F [B][R][D] are the region features
+ * the attention reads, Wh / Wc [D][U] and bh / bc [U] the two layers:
+ *   m[b][d] = (1/R) sum_r F[b][r][d]
+ *   h0[b][u] = tanh(bh[u] + sum_d m[b][d] Wh[d][u])
+ *   c0[b][u] = tanh(bc[u] + sum_d m[b][d] Wc[d][u])
+ * One launch, one workgroup per sample.  fmean [B][D] (nullable: inference) receives m for the backward; h0 and c0 [B][U]
+ * are written (the callers pass slab 0 of the chains' hs / cs).  Any B, R, U >= 1 and 1 <= D <= 64, no alignment
+ * requirement; anything else: TNT_BADARG.  Row b's bits depend on F[b] and the weights alone -- not on B, not on the row's
+ * position -- and every sum runs in a fixed order (regions in 256 / D interleaved groups, each ascending, the groups in
+ * order; d ascending from the bias): no atomics, the same bits every time. */
+int32_t tnt_init_state_fwd_f32(const float* F, const float* Wh, const float* bh, const float* Wc, const float* bc,
+                               float* fmean, float* h0, float* c0, int32_t B, int32_t R, int32_t D, int32_t U,
+                               void* stream);
+/* its backward.  dh0 / dc0 [B][U] are the gradients of the two outputs, h0 / c0 the outputs themselves, fmean the forward's:
+ *   gh = dh0 (1 - h0^2),  gc = dc0 (1 - c0^2)
+ *   dWh [D][U] = fmean^T gh,  dbh [U] = column sums of gh,  dWc, dbc likewise from gc      -- WRITTEN, not accumulated
+ *   dF[b][r][:] += (1/R) (gh Wh^T + gc Wc^T)[b][:]  for every region r                    -- ADDED to what dF holds
+ * dF [B][R][D] is nullable (the parameter gradients alone: one launch instead of two); so are the four parameter gradients,
+ * all of them or none (NULL: both layers frozen, the dF launch alone).  fmean is required.  Same sizes as the forward.  No
+ * scratch, no atomics; the sums over b (ascending) and over u (per lane ascending, then the 64-lane butterfly) run in a
+ * fixed order: the same bits every time. */
+int32_t tnt_init_state_bwd_f32(const float* dh0, const float* dc0, const float* h0, const float* c0, const float* fmean,
+                               const float* Wh, const float* Wc, float* dWh, float* dbh, float* dWc, float* dbc, float* dF,
+                               int32_t B, int32_t R, int32_t D, int32_t U, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 133
+TNT_VERSION = 134
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -192,6 +192,10 @@ SIGNATURES = {
     "tnt_lc_seq_bwd_ext_f32": [P, P, P, P, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, F32,
                                F32, I32, U64, U32, U32, P, F32, F32, U32, P, I32, I32, P, P, P],
     "tnt_attention_coverage_f32": [P, I64, I32, I32, I32, I32, F32, P, P, P, P],
+    "tnt_lc_seq_bwd_init_f32": [P, P, P, P, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, F32,
+                                F32, I32, U64, U32, U32, P, F32, F32, U32, P, I32, I32, P, P, P, P],
+    "tnt_init_state_fwd_f32": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
+    "tnt_init_state_bwd_f32": [P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
 }
 
 _lib = None

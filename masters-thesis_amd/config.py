@@ -4,7 +4,7 @@ the way main.py:113-134 does."""
 import yaml
 
 from . import schedules
-from .model_base import AttentionCoverage, ScanDropout, WordDropout
+from .model_base import AttentionCoverage, LearnedInitState, ScanDropout, WordDropout
 from .optimizers import Adam, AdamW, SGD, CategoricalCrossentropy
 
 
@@ -85,6 +85,11 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
             if not isinstance(cov, dict) or not set(cov) <= {"weight", "axis"} or "weight" not in cov:
                 raise ValueError(f"attention_coverage must be a mapping with weight and optionally axis, got {cov!r}")
             kw["attention_coverage"] = AttentionCoverage(cov["weight"], cov.get("axis", "time"))
+        # learn_init_state: true or {reg: }: an optional key of this library's (model_base.LearnedInitState)
+        if "init_state" not in kw:
+            init = LearnedInitState.from_config(config.get("learn_init_state"))
+            if init is not None:
+                kw["init_state"] = init
         model = NIC(groups, config["units"], config["embedding_features"], config["embedding_text"],
                     config["attn_units"], vocab_size, config["max_length"], config["dropout_input"],
                     config["dropout_features"], config["dropout_text"], config["dropout_attn"], config["dropout_lstm"],

@@ -1837,6 +1837,7 @@ struct LcSeqBwdArgs {
   float rate_out; uint32_t site_out0;   // Dropout' of the LSTM outputs applied to dout as it is read (one site per step)
   int T;
   unsigned* sync; float* guard_out;
+  float* dc0;              // nullable [B][U]: the gradient of the initial cell state, stored behind the step loop
 };
 constexpr int LB_DZLD = 68;
 constexpr int LB_RED_FLOATS = 16 * 4 * 16 * 17;                  // gather sums [2][16][256] / context-part tiles [16 waves][4][16][17]
@@ -1846,7 +1847,9 @@ constexpr int LB_LSTM_FLOATS = LB_LDS_FLOATS + 32 * LB_W2LD + 16 * 64 + 16 * 2 *
 constexpr int LB_PF_FLOATS = 35 * 1024;                          // floor of the dynamic LDS block: the RB == 8 LSTM role parks its [512][65] Ur slab here before the loop (the attention role holds P, F, dP and dF in registers and uses none of it)
 constexpr int LB_LDS_BYTES = (LB_LSTM_FLOATS > LB_PF_FLOATS ? LB_LSTM_FLOATS : LB_PF_FLOATS) * 4 + 16;
 
-template <int G4, int NP, int RB>
+// DC0: the form that stores the gradient of the initial cell state behind the step loop (tnt_lc_seq_bwd_init_f32 with dc0);
+// false compiles the statement away, so the forms every other entry launches are the code they were without it
+template <int G4, int NP, int RB, bool DC0 = false>
 __global__ __launch_bounds__(1024) void lc_seq_bwd_kernel(LcSeqBwdArgs a) {
   constexpr int RPP = WT / G4, NTW = 2, NWB = 16;
   extern __shared__ __attribute__((aligned(16))) float lb_lds[];
@@ -2570,6 +2573,14 @@ __global__ __launch_bounds__(1024) void lc_seq_bwd_kernel(LcSeqBwdArgs a) {
     }
     LCT(25);
   }
+  // ---- the gradient of the initial cell state: what the cell backward of step 0 left in dc_c, one plain store per owner
+  // (a global store: a buffer resource here cost <8, 6, 16> 16 bytes of scratch per lane, this form none anywhere)
+  if (DC0 && a.dc0 != nullptr) {
+    LC_TID(t9);
+    const int erow9 = (t9 & 255) >> 4, eb9 = rb * RB + erow9;
+    if (t9 < 512 && erow9 < RB && eb9 < B)
+      a.dc0[eb9 * U + (2 * j + (t9 >> 8)) * 16 + (t9 & 15)] = dc_c;
+  }
 #undef LC_TID
   if (ub == 16) LCT_DUMP(16, 32);
   LCS(38); LCS(39);
@@ -2584,15 +2595,15 @@ extern "C" int32_t tnt_lc_seq_bwd_work_floats(int32_t B, int32_t U) {
   return 3 * nrb * 32 * 32 * 256 + 3 * B * U + 3 * nrb * 16 * 16 * 64;
 }
 
-extern "C" int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+extern "C" int32_t tnt_lc_seq_bwd_init_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
                                       const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
                                       float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
                                       const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
                                       int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
                                       float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
                                       uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
-                                      uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, uint32_t* sync,
-                                      float* guard_out, void* stream) {
+                                      uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, float* dc0,
+                                      uint32_t* sync, float* guard_out, void* stream) {
   if (T <= 0 || sync == nullptr || work == nullptr || U != 512 || B <= 0 || B > 128) return TNT_BADARG(24);
   if (!(rate_out >= 0.f && rate_out < 1.f)) return TNT_BADARG(36);
   if (!wide_ok(R, D, A) || R > 512 || D > 64 || A > 64) return TNT_BADARG(21);
@@ -2616,11 +2627,19 @@ extern "C" int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const 
   a.keep_stride = keep_stride; a.Ur = Ur; a.Wc = Wc; a.dout = dout; a.gates = gates; a.cs = cs; a.dz = dz;
   a.rate_out = rate_out; a.site_out0 = site_out0;
   a.xch = work; a.dhx = work + 3 * nrb * 32 * 32 * 256; a.parts = a.dhx + 3 * (int64_t)B * U;
-  a.T = T; a.sync = sync; a.guard_out = guard_out;
+  a.T = T; a.sync = sync; a.guard_out = guard_out; a.dc0 = dc0;
   const int g4 = (A <= 32 && D <= 32) ? 8 : 16, np = (R + WT / g4 - 1) / (WT / g4);
   if (np > 6) return TNT_BADARG(21);
   void (*kern)(LcSeqBwdArgs) = nullptr;
-  if (rb8) {
+  if (dc0 != nullptr) {
+    if (rb8) {
+      if (g4 == 8) kern = np <= 3 ? lc_seq_bwd_kernel<8, 3, 8, true> : lc_seq_bwd_kernel<8, 6, 8, true>;
+      else kern = np <= 3 ? lc_seq_bwd_kernel<16, 3, 8, true> : lc_seq_bwd_kernel<16, 6, 8, true>;
+    } else {
+      if (g4 == 8) kern = np <= 3 ? lc_seq_bwd_kernel<8, 3, 16, true> : lc_seq_bwd_kernel<8, 6, 16, true>;
+      else kern = np <= 3 ? lc_seq_bwd_kernel<16, 3, 16, true> : lc_seq_bwd_kernel<16, 6, 16, true>;
+    }
+  } else if (rb8) {
     if (g4 == 8) kern = np <= 3 ? lc_seq_bwd_kernel<8, 3, 8> : lc_seq_bwd_kernel<8, 6, 8>;
     else kern = np <= 3 ? lc_seq_bwd_kernel<16, 3, 8> : lc_seq_bwd_kernel<16, 6, 8>;
   } else {
@@ -2632,6 +2651,21 @@ extern "C" int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const 
   hipLaunchKernelGGL(kern, dim3(256), dim3(1024), LB_LDS_BYTES, tnt_stream(stream), a);
   TNT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int32_t tnt_lc_seq_bwd_ext_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,
+                                      const float* alpha, const uint8_t* keep4, int64_t keep_stride, float* dP, float* dF,
+                                      float* dvb, float* dqpre, const float* Ur, const float* Wc, const float* dout,
+                                      const float* gates, const float* cs, float* dz, float* work, int32_t T, int32_t B,
+                                      int32_t R, int32_t D, int32_t A, int32_t U, float slope, float rate_attn,
+                                      float rate_in, int32_t in_lwidth, uint64_t seed, uint32_t site_attn0,
+                                      uint32_t site_in0, const uint32_t* step_dev, float alpha_mse_coef, float rate_out,
+                                      uint32_t site_out0, const float* ext, int32_t ext_ts, int32_t ext_bs, uint32_t* sync,
+                                      float* guard_out, void* stream) {
+  return tnt_lc_seq_bwd_init_f32(F, P, W2, v, qpre, alpha, keep4, keep_stride, dP, dF, dvb, dqpre, Ur, Wc, dout, gates, cs, dz,
+                                 work, T, B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, seed, site_attn0, site_in0,
+                                 step_dev, alpha_mse_coef, rate_out, site_out0, ext, ext_ts, ext_bs, nullptr, sync, guard_out,
+                                 stream);
 }
 
 extern "C" int32_t tnt_lc_seq_bwd_drop_f32(const float* F, const float* P, const float* W2, const float* v, const float* qpre,

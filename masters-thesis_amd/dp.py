@@ -454,6 +454,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.attention_coverage is not None:
         # lc_nic.NIC(attention_coverage=...): the sum over the batch axis is not a per-rank quantity
         raise NotImplementedError(model.COVERAGE_DP_REFUSAL)
+    if model.init_state is not None:
+        # lc_nic.NIC(init_state=...): its gradient launches sit in none of the all-reduce buckets
+        raise NotImplementedError(model.INIT_STATE_DP_REFUSAL)
     if model._corruption() is not None:
         # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...): single device only
         raise NotImplementedError(model.CORRUPT_DP_REFUSAL)

@@ -24,7 +24,7 @@ import torch
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN, S_LSTM_IN, S_LSTM_OUT, S_SS_COIN,
                          S_SS_DRAW, BN_EPS, BN_MOMENTUM, ScheduledSampling, check_sampling, check_length_penalty,
-                         _TokenChoice, _BeamDecode, AttentionCoverage, StepRoute)
+                         _TokenChoice, _BeamDecode, AttentionCoverage, StepRoute, LearnedInitState)
 
 SUBJ_SITE = 1000      # dropout-site offset per subject (multi-subject model)
 S_FEAT2 = 4           # second application of the feature dropout (ms2_NIC.py:214)
@@ -81,8 +81,14 @@ class NIC(ModelBase):
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
                  attn_reg, lstm_reg, output_reg, norm="batch", n_subjects=1, depth=0, use_layer_norm=False,
                  teacher_forcing=True, scheduled_sampling=None, attention_coverage=None, scan_dropout=None,
-                 word_dropout=None, **kw):
+                 word_dropout=None, init_state=None, **kw):
         super().__init__(**kw)
+        # init_state (model_base.LearnedInitState): the decoder starts from h0 = tanh(mean_r(F) Wh + bh), c0 likewise, two
+        # layers of its own (hidden_init, carry_init; tnt_init_state_fwd_f32 at the end of _encode); None builds nothing, and
+        # the arena, the launches and every bit are those of the model without the argument
+        if init_state is not None and not isinstance(init_state, LearnedInitState):
+            raise ValueError(f"init_state must be None or a model_base.LearnedInitState, got {init_state!r}")
+        self.init_state = init_state
         # ---- what exists only once a step or a decode has asked for it
         self.lc_xch = None              # exchange space of the persistent backward chain (_build)
         self.ew = None                  # train_step_sam's weight offset e(w)
@@ -182,6 +188,10 @@ class NIC(ModelBase):
         ks["time_distributed_nonlinear/kernel"], ks["time_distributed_nonlinear/bias"] = (U, H), (H,)
         ls["time_distributed_softmax"] = ["kernel", "bias"]
         ks["time_distributed_softmax/kernel"], ks["time_distributed_softmax/bias"] = (H, V), (V,)
+        if self.init_state is not None:
+            for nm in LearnedInitState.LAYERS:
+                ls[nm] = ["kernel", "bias"]
+                ks[f"{nm}/kernel"], ks[f"{nm}/bias"] = (D, U), (U,)
         self.layers_spec, self.keras_shapes = ls, ks
 
         a = self.arena = ParamArena(self.device)
@@ -221,6 +231,9 @@ class NIC(ModelBase):
         a.add("time_distributed_nonlinear/kernel", (U, H), self.l2_out); a.add("time_distributed_nonlinear/bias", (H,))
         a.add("time_distributed_softmax/kernel", (H, self.ldV), self.l2_out)
         a.add("time_distributed_softmax/bias", (self.ldV,))
+        if self.init_state is not None:         # behind every entry of the model without them
+            for nm in LearnedInitState.LAYERS:
+                a.add(f"{nm}/kernel", (D, U), self.init_state.reg); a.add(f"{nm}/bias", (U,))
         a.finalize()
         nW = int(self.goff_host[-1]) * D
         self.encW = [a.theta[w:w + nW] for w, _ in enc_off]
@@ -248,6 +261,7 @@ class NIC(ModelBase):
         if not self.teacher_forcing:
             self._naive_check()
         self._coverage_check()
+        self._init_state_check()
         # scan_dropout (model_base.ScanDropout) / word_dropout (model_base.WordDropout): train_step and train_step_sam corrupt
         # the staged batch (tnt_input_corrupt_f32, one launch behind the staging); None or rate 0 issues nothing
         self.scan_dropout, self.word_dropout = scan_dropout, word_dropout
@@ -284,6 +298,10 @@ class NIC(ModelBase):
                 self.set_weight(f"lstm/{nm}/gamma", np.ones(n))
         self.set_weight("time_distributed_nonlinear/kernel", tn((U, H), np.sqrt(2.0 / (U + H))))
         self.set_weight("time_distributed_softmax/kernel", tn((H, V), np.sqrt(2.0 / (H + V))))
+        if self.init_state is not None:         # glorot_uniform, drawn behind every other weight: those keep their values
+            lim = np.sqrt(6.0 / (D + U))
+            for nm in LearnedInitState.LAYERS:
+                self.set_weight(f"{nm}/kernel", rng.uniform(-lim, lim, (D, U)))
 
     def _bn_slots(self):
         """(slot of mov_mean / mov_var, keras layer name) of every BatchNormalization of the encoder"""
@@ -373,6 +391,8 @@ class NIC(ModelBase):
         self.work = f(max(D, A, 4 * U, ldV, H) * (2 * nch + 1))
         self.rowsq = f(n)
         self.metric_part = f(T * ((self.R + 63) // 64))      # partial sums of the attention metric (tnt_attention_metric_parts)
+        if self.init_state is not None:     # the region means the init backward reads, and the gradients of the two states
+            self.fmean, self.dh0, self.dc0 = f(B, D), f(B, U), f(B, U)
         cov = self.attention_coverage
         if cov is not None:     # the coverage gradient rider [rows][R] and the partials of the value (tnt_attention_coverage_f32)
             self.cov_ext = f(cov.rows(T, B) * R)
@@ -399,6 +419,7 @@ class NIC(ModelBase):
         if self.xT is not None:
             self.xT[:, :B].copy_(self.x[:, :self.n_in].t())
         self.cap.copy_(cap_t)
+        # (with init_state the two copies are shape checks only: _encode overwrites slab 0 with the learned state)
         self.Hs[0].copy_(self._to_dev(a0, torch.float32))
         self.Cs[0].copy_(self._to_dev(c0, torch.float32))
         return B, T
@@ -461,6 +482,11 @@ class NIC(ModelBase):
             be.dropout(self.F, self.F, B * R, D, D, 0, D, 0, self.r_feat, sd, S_FEAT2, 0, ds)
         self.gemm_sk(self.F, a.p("attention/W1/kernel"), self.P, B * R, self.A, D, D, self.A, self.A,
                 bias=a.p("attention/W1/bias"), pre=self.Ppre, act=ACT_LEAKY, slope=0.2)      # attention.py:32 (hoisted)
+        if self.init_state is not None:
+            # the learned initial state from the features the attention reads, over the staged a0 / c0 (slab 0 of Hs / Cs,
+            # where both chains, the per-step kernels, the decodes and score_captions' gather read it)
+            be.init_state_fwd(self.F, a.p("hidden_init/kernel"), a.p("hidden_init/bias"), a.p("carry_init/kernel"),
+                              a.p("carry_init/bias"), self.fmean, self.Hs[0], self.Cs[0], B, R, D, self.U)
 
     def _lc_seq_ok(self):
         """the persistent forward-chain kernel applies (tnt_lc_seq_fwd_f32's shape limits; the device census was taken by
@@ -636,6 +662,71 @@ class NIC(ModelBase):
         if self.grad_sync is not None:
             raise NotImplementedError(self.COVERAGE_DP_REFUSAL)
 
+    INIT_STATE_DP_REFUSAL = ("init_state (the learned initial LSTM state) has no data-parallel schedule: its gradient launches "
+                             "sit in none of the all-reduce buckets.  Train it on one device")
+
+    def _init_state_check(self):
+        """the combinations the learned initial state is built for; anything else refuses instead of running without it"""
+        if self.init_state is None:
+            return
+        if not self.teacher_forcing:
+            raise NotImplementedError("init_state (the learned initial LSTM state) has not been checked on the free-running "
+                                      "decoder: not with teacher_forcing=False")
+        if self.scheduled_sampling is not None:
+            raise NotImplementedError("init_state (the learned initial LSTM state) has not been checked under "
+                                      "scheduled_sampling")
+        if self.S != 1:
+            raise NotImplementedError("init_state (the learned initial LSTM state) is a single-subject layer: n_subjects > 1 "
+                                      "is not supported")
+        if self.use_layer_norm:
+            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for the LayerNormLSTMCell "
+                                      "(use_layer_norm=True)")
+        if self.agc:
+            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for adaptive gradient "
+                                      "clipping (enable_agc)")
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise NotImplementedError(self.INIT_STATE_DP_REFUSAL)
+
+    def enable_agc(self, clip_factor=0.01, eps=1e-3):
+        if clip_factor is not None and self.init_state is not None:
+            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for adaptive gradient "
+                                      "clipping (enable_agc)")
+        super().enable_agc(clip_factor, eps)
+
+    def learn_init_state(self, img_input):
+        """lc_NIC.learn_init_state (lc_NIC.py:169-173) on the scans ``img_input`` (B, n_voxels): (h0, c0), two (B, units)
+        numpy arrays, in inference mode (moving BatchNorm statistics, no Dropout)"""
+        if self.init_state is None:
+            raise ValueError("learn_init_state needs a model built with init_state=model_base.LearnedInitState(...)")
+        B = int(np.shape(img_input)[0])
+        z = np.zeros((B, self.U), np.float32)
+        self._stage_inputs((img_input, torch.zeros(B, 1, dtype=torch.int32), z, z))
+        self._encode(B, False)
+        return self.Hs[0].cpu().numpy().copy(), self.Cs[0].cpu().numpy().copy()
+
+    def _bwd_init(self, B, T):
+        """the backward of the learned initial state, between the chain and _bwd_front (which finishes dF: the folded
+        feature Dropout' acts on the finished dF).  dh0 = dZ[0] Ur^T + dqpre[0] W2^T: two products of the dtext shape; on
+        the per-step route the second is what step 0's attention backward left in dh_att, and dc what its cell backward
+        left.  Then tnt_init_state_bwd_f32: the four parameter gradients (left out where both layers are frozen) and its
+        share of dF."""
+        if self.init_state is None:
+            return
+        be, a = self.be, self.arena
+        R, D, A, U = self.R, self.D, self.A, self.U
+        Ur = a.p("lstm/recurrent_kernel")
+        if self._lc_seq_bwd_ok():
+            dh0, dc0 = self.dh0, self.dc0
+            self.gemm_sk(self.dZ[:B], Ur, dh0, B, U, 4 * U, 4 * U, 4 * U, U, transB=True)
+            self.gemm_sk(self.dqpre[0], a.p("attention/W2/kernel"), dh0, B, U, A, A, A, U, transB=True, accumulate=True)
+        else:
+            dh0, dc0 = self.dh_att, self.dc
+            self.gemm_sk(self.dZ[:B], Ur, dh0, B, U, 4 * U, 4 * U, 4 * U, U, transB=True, accumulate=True)
+        names = [f"{nm}/{w}" for nm in LearnedInitState.LAYERS for w in ("kernel", "bias")]
+        grads = [None] * 4 if self._skip_grad(*names) else [a.g(n) for n in names]
+        be.init_state_bwd(dh0, dc0, self.Hs[0], self.Cs[0], self.fmean, a.p("hidden_init/kernel"), a.p("carry_init/kernel"),
+                          *grads, self.dF, B, R, D, U)
+
     def _coverage_launch(self, B, T, want_grad):
         """tnt_attention_coverage_f32 on the finished attention weights of the step: ``coverage`` into met[4], and with
         ``want_grad`` the gradient rider of the backward chain into cov_ext; a model without the term launches nothing"""
@@ -787,6 +878,7 @@ class NIC(ModelBase):
         data-parallel schedule (dp.PipelinedAttentionSync) issues one all-reduce bucket after each."""
         self._bwd_head(B, T)
         self._bwd_chain(B, T)
+        self._bwd_init(B, T)
         # the text branch (input Dropout', sparse Embedding scatter) and the front branch (attention parameters, BatchNorm,
         # region-wise encoder) only share the chain's outputs: with `branch_streams` they are two parallel branches of the step
         with self.side(0 if self.branch_streams else -1):
@@ -883,7 +975,8 @@ class NIC(ModelBase):
                           self._alpha_mse, self.seq_sync, self._guard_out(),
                           out_drop=None if route.dout_masked else (self.r_lstm, S_LSTM_OUT),
                           **({} if self.attention_coverage is None
-                             else dict(ext=(self.cov_ext,) + self.attention_coverage.strides(R))))
+                             else dict(ext=(self.cov_ext,) + self.attention_coverage.strides(R))),
+                          **({} if self.init_state is None else dict(dc0=self.dc0)))
         else:
             self._bwd_chain_steps(B, T, Wl, Ur, W2, v)
         hprev = self.Hs[:T].view(n, U)
@@ -1155,6 +1248,7 @@ class NIC(ModelBase):
             raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
         self._ss_refuse()
         self._coverage_check()                      # (grad_sync may have been attached since the constructor)
+        self._init_state_check()
         self._corrupt_check()
         self._sync_accum()
         distill = self._distill_begin()
@@ -1204,6 +1298,8 @@ class NIC(ModelBase):
         if self.attention_coverage is not None:
             raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
                                       "gradient of its first pass): not built for attention_coverage")
+        if self.init_state is not None:
+            raise NotImplementedError("train_step_sam is not built for init_state (the learned initial LSTM state)")
         if self._distill_on():
             raise NotImplementedError(self.DISTILL_REFUSAL.format(what="train_step_sam's two passes do not run the teacher"))
         self._corrupt_check()

@@ -93,6 +93,46 @@ class AttentionCoverage:
         return f"AttentionCoverage(weight={self.weight!r}, axis={self.axis!r})"
 
 
+class LearnedInitState:
+    """The learned initial LSTM state of Show, Attend and Tell (Xu et al. 2015, section 3.1.2) for lc_nic.NIC; the reference
+    names it learn_init_state (lc_NIC.py:169-173: "init the LSTM h,c state as MLP(mean(features))") and never builds the two
+    layers it reads, so the definition is tnt_init_state_fwd_f32's (include/tnt_hip.h).  With F [B][R][D] the region features
+    the attention reads -- behind BatchNorm / LayerNorm and the feature Dropout, in training and inference mode alike --
+      m = mean_r F,   h0 = tanh(m Wh + bh),   c0 = tanh(m Wc + bc)
+    Wh, bh are the layer ``hidden_init`` (kernel (D, U), bias (U,)), Wc, bc the layer ``carry_init``: Glorot-uniform
+    kernels, zero biases.  ``reg`` is the L2 coefficient of both kernels (part of the ``L2`` metric and of the gradient).
+    The ``a0`` / ``c0`` every call still takes are shape-checked and their values are not used."""
+
+    def __init__(self, reg=0.0):
+        if isinstance(reg, bool) or not isinstance(reg, (int, float, np.integer, np.floating)) or not np.isfinite(reg):
+            raise ValueError(f"the L2 coefficient of the learned initial state must be a finite number, got {reg!r}")
+        if reg < 0:
+            raise ValueError(f"the L2 coefficient of the learned initial state must be >= 0, got {reg!r}")
+        self.reg = float(reg)
+
+    LAYERS = ("hidden_init", "carry_init")
+
+    @classmethod
+    def from_config(cls, value):
+        """the config key ``learn_init_state``: true, false / null (off), or {reg: <float>}"""
+        if value is None or value is False:
+            return None
+        if value is True:
+            return cls()
+        if not isinstance(value, dict) or not set(value) <= {"reg"}:
+            raise ValueError(f"learn_init_state must be true, false or a mapping with reg, got {value!r}")
+        return cls(value.get("reg", 0.0))
+
+    def __eq__(self, other):
+        return isinstance(other, LearnedInitState) and self.reg == other.reg
+
+    def __hash__(self):
+        return hash(("init_state", self.reg))
+
+    def __repr__(self):
+        return f"LearnedInitState(reg={self.reg!r})"
+
+
 class ScheduledSampling:
     """Scheduled sampling (Bengio et al. 2015) for the train_step of nic.NIC and lc_nic.NIC; the definitions are
     tnt_scheduled_feedback_f32's and tnt_scheduled_feedback2_f32's (include/tnt_hip.h).  At each step, each caption row is
@@ -1193,6 +1233,7 @@ class ModelBase:
         self.scheduled_sampling = None      # nic.NIC / lc_nic.NIC(scheduled_sampling=...)
         self.self_critical = None           # nic.NIC(self_critical=...)
         self.attention_coverage = None      # lc_nic.NIC(attention_coverage=...)
+        self.init_state = None              # lc_nic.NIC(init_state=...)
         self._scan_dropout = self._word_dropout = None      # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...)
         self._null_dev = None               # the ScanDropout's null scan on the device (None: the all-zero scan)
         self.met = None                     # the metrics buffer (_build)
@@ -1837,6 +1878,8 @@ class ModelBase:
             raise no("the free-running decoder (teacher_forcing=False) has no accumulating step")
         if self.attention_coverage is not None:
             raise no("attention_coverage's gradient scale is not threaded through the micro-steps")
+        if self.init_state is not None:
+            raise no("init_state (the learned initial LSTM state) has no accumulating step")
         if (self.loss_normalise if normalise is None else normalise) == "weights":
             raise no(self.GRAD_ACCUM_WEIGHTS)
         if int(self.S) > 1:

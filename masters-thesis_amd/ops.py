@@ -524,10 +524,20 @@ class HipBackend:
 
     def lc_seq_bwd(self, F, P, W2, v, qpre, alpha, keep4, keep_stride, dP, dF, dvb, dqpre, Ur, Wc, dout, gates, cs, dz, work, T,
                    B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, seed, site_attn0, site_in0, step_dev, alpha_mse, sync,
-                   guard_out=None, out_drop=None, ext=None):
+                   guard_out=None, out_drop=None, ext=None, dc0=None):
         """out_drop = (rate, site0): dout is the gradient of the DROPPED outputs (tnt_lc_seq_bwd_drop_f32).
         ext = (buffer, ext_ts, ext_bs): an external gradient of the attention weights rides along (tnt_lc_seq_bwd_ext_f32,
-        with or without out_drop)."""
+        with or without out_drop).
+        dc0 [B][U]: receives the gradient of the initial cell state (tnt_lc_seq_bwd_init_f32, with or without the others)."""
+        if dc0 is not None:
+            buf, ext_ts, ext_bs = ext if ext is not None else (None, 0, 0)
+            rate_out, site_out0 = out_drop if out_drop is not None else (0.0, 0)
+            self._call(self.lib.tnt_lc_seq_bwd_init_f32, "tnt_lc_seq_bwd_init_f32", _p(F), _p(P), _p(W2), _p(v), _p(qpre),
+                       _p(alpha), _p(keep4), int(keep_stride), _p(dP), _p(dF), _p(dvb), _p(dqpre), _p(Ur), _p(Wc), _p(dout),
+                       _p(gates), _p(cs), _p(dz), _p(work), T, B, R, D, A, U, slope, rate_attn, rate_in, in_lwidth, int(seed),
+                       int(site_attn0), int(site_in0), _p(step_dev), float(alpha_mse), float(rate_out), int(site_out0),
+                       _p(buf), int(ext_ts), int(ext_bs), _p(dc0), _p(sync), _p(guard_out), self._s())
+            return
         if ext is not None:
             buf, ext_ts, ext_bs = ext
             rate_out, site_out0 = out_drop if out_drop is not None else (0.0, 0)
@@ -1013,6 +1023,17 @@ class HipBackend:
         """axis 0 = time, 1 = batch; ext / out nullable; work: attention_coverage_work_floats(T, B, R, axis) floats"""
         self._call(self.lib.tnt_attention_coverage_f32, "tnt_attention_coverage_f32", _p(alpha), int(tstride), T, B, R, int(axis),
                    float(coef), _p(ext), _p(out), _p(work), self._s())
+
+
+    def init_state_fwd(self, F, Wh, bh, Wc, bc, fmean, h0, c0, B, R, D, U):
+        """the learned initial LSTM state (tnt_init_state_fwd_f32): fmean [B][D] nullable, h0 / c0 [B][U] written"""
+        self._call(self.lib.tnt_init_state_fwd_f32, "tnt_init_state_fwd_f32", _p(F), _p(Wh), _p(bh), _p(Wc), _p(bc), _p(fmean),
+                   _p(h0), _p(c0), B, R, D, U, self._s())
+
+    def init_state_bwd(self, dh0, dc0, h0, c0, fmean, Wh, Wc, dWh, dbh, dWc, dbc, dF, B, R, D, U):
+        """its backward (tnt_init_state_bwd_f32): the four parameter gradients written, dF (nullable) added to"""
+        self._call(self.lib.tnt_init_state_bwd_f32, "tnt_init_state_bwd_f32", _p(dh0), _p(dc0), _p(h0), _p(c0), _p(fmean),
+                   _p(Wh), _p(Wc), _p(dWh), _p(dbh), _p(dWc), _p(dbc), _p(dF), B, R, D, U, self._s())
 
 
 def attention_coverage_work_floats(T, B, R, axis):
