@@ -1737,6 +1737,42 @@ int32_t tnt_init_state_bwd_f32(const float* dh0, const float* dc0, const float* 
                                const float* Wh, const float* Wc, float* dWh, float* dbh, float* dWc, float* dbc, float* dF,
                                int32_t B, int32_t R, int32_t D, int32_t U, void* stream);
 
+/* ---- sentence-embedding target: cosine loss, inverse row norms, cosine top-k (csrc/semantic.hip).  The reference hands every
+ * model the caption's sentence embedding ("GUSE") and defines cosine_loss = 1 - cosine_similarity (lc_NIC.py:488-502) with
+ * keras l2_normalize, epsilon 1e-12.  All three entries are float32, take every sum in a fixed order and use no float atomics:
+ * the same bits every time, and row r's outputs depend on row r's inputs alone (not on B / rows, not on the row's place).
+ *
+ * tnt_cosine_loss_f32.  z [B][ldz] the predictions, g [B][ldg] the targets, G <= ldz, ldg columns used, 1 <= G <= 2048:
+ *   nz2 = max(sum_j z_j^2, 1e-12),  ng2 = max(sum_j g_j^2, 1e-12),  nz = sqrt(nz2),  ng = sqrt(ng2)
+ *   zn = z / nz,  gn = g / ng,  cos = sum_j zn_j gn_j  (formed as ((sum_j z_j g_j) * (1 / nz)) * (1 / ng)),  loss = 1 - cos
+ *   cos_row[r] = cos,  loss_row[r] = loss,  out[0] (nullable) = (sum_r loss_row[r]) / B, the rows added in ascending order
+ *   dz (nullable) [B][ldz], the gradient of gscale * sum_r loss_r:
+ *     sum z^2 >  1e-12:  dz_j = -gscale * (gn_j - cos * zn_j) / nz
+ *     sum z^2 <= 1e-12:  dz_j = -gscale * gn_j / nz            (the normaliser is the constant 1e-6 there)
+ *   A training step passes gscale = weight / B.  An all-zero target row has gn = 0: cos = 0, loss = 1, dz = 0, and it counts
+ *   in the mean.  dz may be z itself (each element is read, then written, by the same lane); columns >= G of dz are not
+ *   written.  The three sums of a row: lane l of one wave takes the float4 l, l + 64, ... (the four elements in order) and
+ *   then the G % 4 tail, by fused multiply-add, then the 64-lane butterfly; without 16-byte alignment of z, g, dz or with ldz
+ *   or ldg not a multiple of 4 the lanes take single floats l, l + 64, ... instead.  B <= 256 is one launch; above, a second
+ *   one-thread launch forms out.  Null z, g, loss_row or cos_row, B < 1, G outside [1, 2048], ldz < G, ldg < G: TNT_BADARG,
+ *   nothing launched. */
+int32_t tnt_cosine_loss_f32(const float* z, int32_t ldz, const float* g, int32_t ldg, float* dz /* nullable */,
+                            float* loss_row, float* cos_row, float* out /* nullable */, int32_t B, int32_t G, float gscale,
+                            void* stream);
+/* inv[r] = 1 / sqrt(max(sum_j X[r][j]^2, 1e-12)) for the rows of X [rows][ldx], G <= ldx columns used, any G >= 1; the sum as
+ * in tnt_cosine_loss_f32 (one wave per row).  Null pointers, rows < 1, G < 1, ldx < G: TNT_BADARG. */
+int32_t tnt_row_inv_norm_f32(const float* X, int64_t ldx, float* inv, int64_t rows, int32_t G, void* stream);
+/* The k most similar bank rows of every query.  S [B][lds] holds the raw dot products S[b][m] = <q_b, bank_m>, M <= lds
+ * columns used, qinv [B] and binv [M] the inverse norms (tnt_row_inv_norm_f32).  The similarity is
+ *   c[b][m] = (S[b][m] * qinv[b]) * binv[m]        two float32 multiplications, in exactly this order
+ * idx [B][k] (int32) and sim [B][k] receive the k largest of row b in descending order of this total order: a larger c comes
+ * first; equal c (-0 equals +0) in ascending index order (the first-max rule of every argmax in this library); NaN comes
+ * behind -inf, and NaNs among themselves in ascending index order.  sim holds c's own bits.  1 <= k <= 64, k <= M, any
+ * M >= 1 (a row is read k times and is expected to stay in the L2: 256 KB at M = 65 536).  A null pointer, B < 1, M < 1,
+ * k outside [1, min(64, M)], lds < M: TNT_BADARG, nothing launched. */
+int32_t tnt_cosine_topk_f32(const float* S, int64_t lds, const float* qinv, const float* binv, int32_t* idx, float* sim,
+                            int32_t B, int32_t M, int32_t k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

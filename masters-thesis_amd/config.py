@@ -4,7 +4,7 @@ the way main.py:113-134 does."""
 import yaml
 
 from . import schedules
-from .model_base import AttentionCoverage, LearnedInitState, ScanDropout, WordDropout
+from .model_base import AttentionCoverage, LearnedInitState, ScanDropout, SemanticTarget, WordDropout
 from .optimizers import Adam, AdamW, SGD, CategoricalCrossentropy
 
 
@@ -68,14 +68,30 @@ def _corruption_keys(config, kw):
 def build_model(config, groups, mode="attention", input_size=None, **kw):
     """lc_NIC.NIC(...) exactly as main.py:113-132 builds it, compiled as at main.py:134.
     mode="fc" builds the fully-connected variant instead (the call_fc / greedy_predict_fc dispatch the
-    reference selects by editing lc_NIC.py:163-167,507-509); it needs ``input_size`` (#voxels)."""
+    reference selects by editing lc_NIC.py:163-167,507-509); it needs ``input_size`` (#voxels).
+    mode="dense" builds nic.NIC (Model/NIC.py: the dense encoder in front of the LSTM, embedding_text wide); it needs
+    ``input_size`` too, and ``groups`` is not used."""
     vocab_size = config["top_k"] + 1
+    # semantic: {dim: , weight: , reg: }: an optional key of this library's (model_base.SemanticTarget), the sentence-embedding
+    # target of nic.NIC; the other models do not take it
+    sem = SemanticTarget.from_config(config.get("semantic")) if "semantic" not in kw else None
+    if sem is not None:
+        if mode != "dense":
+            raise NotImplementedError(f"semantic (the sentence-embedding target) is built for nic.NIC (mode=\"dense\") only, "
+                                      f"not for mode={mode!r}")
+        kw["semantic"] = sem
     if mode == "fc":
         from .fc_nic import NICfc
         model = NICfc(input_size, config["units"], config["embedding_features"], config["embedding_text"], vocab_size,
                       config["max_length"], config["dropout_input"], config["dropout_features"], config["dropout_text"],
                       config["dropout_lstm"], config["dropout_out"], config["input_reg"], config["lstm_reg"],
                       config["output_reg"], seed=config.get("seed", 42), **kw)
+    elif mode == "dense":
+        from .nic import NIC as DenseNIC
+        _corruption_keys(config, kw)
+        model = DenseNIC(input_size, config["units"], config["embedding_text"], vocab_size, config["max_length"],
+                         config["dropout_input"], config["dropout_features"], config["dropout_lstm"], config["input_reg"],
+                         config["lstm_reg"], config["output_reg"], seed=config.get("seed", 42), **kw)
     elif mode == "attention":
         from .lc_nic import NIC
         _corruption_keys(config, kw)

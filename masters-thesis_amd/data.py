@@ -113,13 +113,15 @@ def make_target(cap_vector):
 class DataGenerator:
     """keras.utils.Sequence protocol of data_generator_guse.DataGenerator (lines 25-171).
     ``pairs`` rows are (nsd_key, caption, ...); ``load_betas(key, row) -> (N,) float32`` replaces the
-    hard-coded np.load of the lab paths (data_generator_guse.py:147-153)."""
+    hard-coded np.load of the lab paths (data_generator_guse.py:147-153).  ``load_guse(key, row) -> (G,) float32`` (optional)
+    is the caption's sentence embedding, the guse_key column of the reference's batch rows: when given, ``x`` gains it as a
+    fifth element (B, G), the target of nic.NIC(semantic=...)."""
 
     def __init__(self, pairs, batch_size, tokenizer, units, max_len, vocab_size, load_betas, n_voxels, shuffle=True,
-                 training=False, one_hot=True, seed=None):
+                 training=False, one_hot=True, seed=None, load_guse=None):
         self.pairs = np.array(pairs, dtype=object)
         self.batch_size, self.tokenizer, self.units, self.max_len, self.vocab_size = batch_size, tokenizer, units, max_len, vocab_size
-        self.load_betas, self.n_voxels = load_betas, n_voxels
+        self.load_betas, self.n_voxels, self.load_guse = load_betas, n_voxels, load_guse
         self.shuffle, self.training, self.one_hot = shuffle, training, one_hot
         self.rng = np.random.default_rng(seed)
         self.on_epoch_end()
@@ -143,17 +145,25 @@ class DataGenerator:
             target = to_categorical(target, self.vocab_size)
         init = np.zeros((B, self.units), np.float32)
         x = (betas, cap, init, init.copy())
+        if self.load_guse is not None:
+            x += (np.stack([np.asarray(self.load_guse(r[0], r), np.float32) for r in batch]),)
         return (x, target) if self.training else (x, target, np.array([r[0] for r in batch]))
 
 
 class SyntheticGenerator:
     """Synthetic batches with the reference's tuple layout: betas ~ N(0,1) (the reference's
     betas are z-scored per voxel), captions = <start>, 6..13 tokens uniform in [3, V), <end>, zero
-    padding.  ``device`` set: tensors are created once on the device (benchmarks)."""
+    padding.  ``device`` set: tensors are created once on the device (benchmarks).  ``guse_dim`` = G: a fifth input (B, G),
+    unit-norm Gaussian rows from a generator of their own seeded with (seed, index), so that every other array of a batch
+    keeps its bits."""
 
-    def __init__(self, n_batches, batch_size, n_voxels, units, max_len, vocab_size, seed=42, one_hot=False, device=None):
+    def __init__(self, n_batches, batch_size, n_voxels, units, max_len, vocab_size, seed=42, one_hot=False, device=None,
+                 guse_dim=None):
         self.n, self.B, self.N, self.U, self.T, self.V = n_batches, batch_size, n_voxels, units, max_len, vocab_size
         self.seed, self.one_hot, self.device = seed, one_hot, device
+        if guse_dim is not None and (isinstance(guse_dim, bool) or int(guse_dim) != guse_dim or guse_dim < 1):
+            raise ValueError(f"guse_dim must be None or an integer >= 1, got {guse_dim!r}")
+        self.guse_dim = None if guse_dim is None else int(guse_dim)
         self._cache = {}
 
     def __len__(self):
@@ -177,6 +187,10 @@ class SyntheticGenerator:
         tgt = make_target(cap)
         z = np.zeros((self.B, self.U), np.float32)
         item = ((x, cap, z, z.copy()), to_categorical(tgt, self.V) if self.one_hot else tgt)
+        if self.guse_dim is not None:
+            g = np.random.default_rng([self.seed, index]).standard_normal((self.B, self.guse_dim))
+            g = (g / np.sqrt((g * g).sum(axis=1, keepdims=True))).astype(np.float32)
+            item = (item[0] + (g,), item[1])
         if self.device is not None:
             dev = lambda a: torch.as_tensor(a).to(self.device)
             item = (tuple(dev(a) for a in item[0]), dev(item[1]))

@@ -457,6 +457,9 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     if model.init_state is not None:
         # lc_nic.NIC(init_state=...): its gradient launches sit in none of the all-reduce buckets
         raise NotImplementedError(model.INIT_STATE_DP_REFUSAL)
+    if model.semantic is not None:
+        # nic.NIC(semantic=...): the mean over the batch and the layer's gradient launches are per rank
+        raise NotImplementedError(model.SEMANTIC_DP_REFUSAL)
     if model._corruption() is not None:
         # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...): single device only
         raise NotImplementedError(model.CORRUPT_DP_REFUSAL)

@@ -17,6 +17,9 @@
   the worked example of the nltk documentation (tests/test_data_fit.py).
 * ``RewardTable`` / ``device_scores``   -- CiderD's document frequencies as the sorted key / idf table that
   tnt_caption_reward_f32 reads (``SelfCritical(score_on="device")``), and that kernel's scores of lists of token ids.
+* ``SemanticBank`` / ``semantic_retrieve`` / ``semantic_identification`` -- nearest-neighbour retrieval and identification in
+  sentence-embedding space for nic.NIC(semantic=...): Model/guse.py's "KNN is used to find a known GUSE vector", which the
+  reference never finishes; the similarities and the selection run on the device (tnt_cosine_topk_f32).
 Host-side Python throughout: nothing here is on the per-step hot path (``pack_references`` fills a pinned array per
 device-scored self-critical step).
 """
@@ -523,3 +526,104 @@ def identification_ranks(scores, captions):
     scores = np.asarray(scores)
     own = scores[np.arange(len(caps)), np.arange(len(caps))]
     return ((scores > own[:, None]) & keep[None, :]).sum(1).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------- embedding-space retrieval
+class SemanticBank:
+    """A bank of M known sentence embeddings (M, G) held on the device for nearest-neighbour retrieval in embedding space
+    (Model/guse.py: "KNN is used to find a known GUSE vector as the output"): the rows as given and their inverse norms
+    1 / sqrt(max(sum x^2, 1e-12)), computed once by tnt_row_inv_norm_f32."""
+
+    def __init__(self, embeddings, device=None):
+        import torch
+        from . import ops
+        e = embeddings if isinstance(embeddings, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(embeddings, np.float32))
+        if e.dim() != 2 or e.shape[0] < 1 or e.shape[1] < 1:
+            raise ValueError(f"a semantic bank is an (M, G) array of embeddings, got shape {tuple(e.shape)}")
+        dev = torch.device(device) if device is not None else (e.device if e.device.type != "cpu" or not torch.cuda.is_available()
+                                                                else torch.device("cuda"))
+        self.rows = e.to(device=dev, dtype=torch.float32).contiguous()
+        self.M, self.G = int(e.shape[0]), int(e.shape[1])
+        self.inv = torch.zeros(self.M, dtype=torch.float32, device=dev)
+        ops.backend().row_inv_norm(self.rows, self.G, self.inv, self.M, self.G)
+
+    @property
+    def device(self):
+        return self.rows.device
+
+    def __len__(self):
+        return self.M
+
+
+def semantic_retrieve(model_or_queries, betas, bank, k=5, return_sims=False):
+    """The k bank rows nearest in cosine similarity to each query: ``model_or_queries`` a nic.NIC built with semantic= (the
+    queries are then model.predict_embedding(betas)) or a (B, G) array of queries (``betas`` is not used).  On the device:
+    S = Q bank^T on the model's product route (gemm_sk; the tiled tnt_gemm_f32 without a model), the queries' inverse norms
+    (tnt_row_inv_norm_f32) and the selection (tnt_cosine_topk_f32, whose text in include/tnt_hip.h defines the order:
+    descending similarity, ties by ascending index, NaN last).  Returns (idx (B, k) int32, sim (B, k) float32) as numpy arrays,
+    the only data that crosses the bus; ``return_sims``: also the whole (B, M) similarity matrix, (S * qinv) * binv in
+    float32 as the kernel forms it."""
+    import torch
+    from . import ops
+    if not isinstance(bank, SemanticBank):
+        raise ValueError(f"bank must be an evaluate.SemanticBank, got {type(bank).__name__}")
+    M, G, dev = bank.M, bank.G, bank.device
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(64, M):
+        raise ValueError(f"k must be an integer in [1, min(64, M = {M})] (tnt_cosine_topk_f32), got {k!r}")
+    k = int(k)
+    model = model_or_queries if hasattr(model_or_queries, "predict_embedding") else None
+    if model is not None:
+        q = model.predict_embedding(betas)
+    else:
+        q = model_or_queries if isinstance(model_or_queries, torch.Tensor) else torch.as_tensor(
+            np.ascontiguousarray(model_or_queries, np.float32))
+    q = q.to(device=dev, dtype=torch.float32).contiguous()
+    if q.dim() != 2 or q.shape[1] != G or q.shape[0] < 1:
+        raise ValueError(f"queries of shape {tuple(q.shape)} against a bank of {G}-wide embeddings")
+    B = int(q.shape[0])
+    be = ops.backend()
+    lds = (M + 3) // 4 * 4
+    S = torch.zeros(B, lds, dtype=torch.float32, device=dev)
+    if model is not None:
+        model.gemm_sk(q, bank.rows, S, B, M, G, G, G, lds, transB=True)
+    else:
+        be.gemm(q, bank.rows, S, B, M, G, G, G, lds, transB=True)
+    qinv = torch.zeros(B, dtype=torch.float32, device=dev)
+    be.row_inv_norm(q, G, qinv, B, G)
+    idx = torch.zeros(B, k, dtype=torch.int32, device=dev)
+    sim = torch.zeros(B, k, dtype=torch.float32, device=dev)
+    be.cosine_topk(S, lds, qinv, bank.inv, idx, sim, B, M, k)
+    out = (idx.cpu().numpy(), sim.cpu().numpy())
+    if return_sims:
+        out += (((S[:, :M] * qinv[:, None]) * bank.inv[None, :]).cpu().numpy(),)
+    return out
+
+
+def semantic_ranks(sims, own):
+    """rank[b] = the number of bank rows outside own[b] whose similarity is strictly above the best of own[b]; own[b] an
+    index or a collection of indices (an image's five captions).  Returns (rank (B,) int64, best (B,) the best own similarity)."""
+    sims = np.asarray(sims)
+    B, M = sims.shape
+    if len(own) != B:
+        raise ValueError(f"own holds {len(own)} entries for {B} queries")
+    rank, best = np.zeros(B, np.int64), np.zeros(B, sims.dtype)
+    for b in range(B):
+        mine = np.unique(np.atleast_1d(np.asarray(list(own[b]) if isinstance(own[b], (set, frozenset)) else own[b], np.int64)))
+        if mine.size == 0 or mine.min() < 0 or mine.max() >= M:
+            raise ValueError(f"own[{b}] must hold at least one bank index in [0, {M}), got {own[b]!r}")
+        best[b] = sims[b, mine].max()
+        other = np.ones(M, bool)
+        other[mine] = False
+        rank[b] = int(((sims[b] > best[b]) & other).sum())
+    return rank, best
+
+
+def semantic_identification(model, betas, bank, own):
+    """Identification in embedding space, the analysis of the fMRI-decoding literature: the predicted embedding of every scan
+    against the whole bank (one product and one selection launch, where evaluate.identification takes B x B decoder passes).
+    Returns a dict: rank (B,) (semantic_ranks), top1 / top5 (fraction of rank 0 / rank < 5), mrr (mean of 1 / (rank + 1)),
+    mean_cos (mean of each scan's best own similarity) and sims (B, M)."""
+    _, _, sims = semantic_retrieve(model, betas, bank, k=1, return_sims=True)
+    rank, best = semantic_ranks(sims, own)
+    return dict(rank=rank, top1=float((rank == 0).mean()), top5=float((rank < 5).mean()),
+                mrr=float((1.0 / (rank + 1.0)).mean()), mean_cos=float(best.astype(np.float64).mean()), sims=sims)

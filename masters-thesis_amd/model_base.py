@@ -133,6 +133,51 @@ class LearnedInitState:
         return f"LearnedInitState(reg={self.reg!r})"
 
 
+class SemanticTarget:
+    """The sentence-embedding target of nic.NIC: the reference hands every model the caption's Universal Sentence Encoder
+    ("GUSE") vector as a fifth input (data_generator_guse.py's guse_key, lc_NIC.train_step's ``guse = data[0][-1]``) and
+    defines cosine_loss = 1 - cosine_similarity (lc_NIC.py:488-502) without ever applying it; Model/guse.py names the use: "a
+    model that linearly maps the brain betas to an embedding vector.  Then KNN is used to find a known GUSE vector".  The
+    definition is tnt_cosine_loss_f32's (include/tnt_hip.h).  With x_b the feature row exactly as the first LSTM step receives
+    it (behind BatchNorm and, in training, the feature step's LSTM-input Dropout), g_b the target and the layer ``guse_out``
+    (kernel (E, dim) Glorot-uniform, L2 ``reg``; bias (dim,) zeros):
+      z_b = x_b W + bias,   zn = z / sqrt(max(sum z^2, 1e-12)),   gn likewise,   semantic = mean_b (1 - sum zn gn)
+    train_step differentiates CE + L2 + ``weight`` * semantic and reports the unweighted value as the metric ``semantic``;
+    ``loss`` stays the cross-entropy.  A target row of all zeros (the reference's missing embedding) gives loss 1 and no
+    gradient, and counts in the mean.  data[0] is then (betas, cap, a0, c0, guse) with guse (B, dim) float32."""
+
+    def __init__(self, dim=512, weight=1.0, reg=0.0):
+        num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or not 1 <= dim <= 2048:
+            raise ValueError(f"the semantic target's dim must be an integer in [1, 2048] (tnt_cosine_loss_f32), got {dim!r}")
+        if not num(weight) or weight < 0:
+            raise ValueError(f"the semantic target's weight must be a finite number >= 0, got {weight!r}")
+        if not num(reg) or reg < 0:
+            raise ValueError(f"the semantic target's L2 coefficient (reg) must be a finite number >= 0, got {reg!r}")
+        self.dim, self.weight, self.reg = int(dim), float(weight), float(reg)
+
+    LAYER = "guse_out"
+    SLOT = 6                # slot of ``met`` that carries the unweighted mean (free in nic.NIC)
+
+    @classmethod
+    def from_config(cls, value):
+        """the config key ``semantic``: null (off) or {dim: , weight: , reg: }, each optional"""
+        if value is None:
+            return None
+        if not isinstance(value, dict) or not set(value) <= {"dim", "weight", "reg"}:
+            raise ValueError(f"semantic must be a mapping with dim, weight and reg, got {value!r}")
+        return cls(value.get("dim", 512), value.get("weight", 1.0), value.get("reg", 0.0))
+
+    def __eq__(self, other):
+        return isinstance(other, SemanticTarget) and (self.dim, self.weight, self.reg) == (other.dim, other.weight, other.reg)
+
+    def __hash__(self):
+        return hash(("semantic", self.dim, self.weight, self.reg))
+
+    def __repr__(self):
+        return f"SemanticTarget(dim={self.dim!r}, weight={self.weight!r}, reg={self.reg!r})"
+
+
 class ScheduledSampling:
     """Scheduled sampling (Bengio et al. 2015) for the train_step of nic.NIC and lc_nic.NIC; the definitions are
     tnt_scheduled_feedback_f32's and tnt_scheduled_feedback2_f32's (include/tnt_hip.h).  At each step, each caption row is
@@ -1234,6 +1279,7 @@ class ModelBase:
         self.self_critical = None           # nic.NIC(self_critical=...)
         self.attention_coverage = None      # lc_nic.NIC(attention_coverage=...)
         self.init_state = None              # lc_nic.NIC(init_state=...)
+        self.semantic = None                # nic.NIC(semantic=...)
         self._scan_dropout = self._word_dropout = None      # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...)
         self._null_dev = None               # the ScanDropout's null scan on the device (None: the all-zero scan)
         self.met = None                     # the metrics buffer (_build)
@@ -1404,6 +1450,8 @@ class ModelBase:
             raise no("scheduled_sampling feeds the student its own words, the teacher the caption's")
         if self.self_critical is not None:
             raise no("a self_critical model's loss is the advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        if self.semantic is not None:
+            raise no("semantic (the sentence-embedding target) was not checked beside a teacher's pass")
         if not self.teacher_forcing:
             raise no("the free-running decoder (teacher_forcing=False) feeds the student its own words")
         if int(self.S) > 1:
@@ -1750,6 +1798,9 @@ class ModelBase:
         if not on:
             return
         no = lambda what: NotImplementedError(self.FINETUNE_REFUSAL.format(what=what))
+        if self.semantic is not None:
+            raise no("a model with semantic= (the sentence-embedding target: its launches do not leave out a frozen "
+                     "variable's share)")
         if self.grad_sync is not None or self.dp_world > 1:
             raise no("the data-parallel update (dp.attach / grad_sync, the row-sharded encoder update included)")
         if self.agc:
@@ -1880,6 +1931,9 @@ class ModelBase:
             raise no("attention_coverage's gradient scale is not threaded through the micro-steps")
         if self.init_state is not None:
             raise no("init_state (the learned initial LSTM state) has no accumulating step")
+        if self.semantic is not None:
+            raise no("semantic (the sentence-embedding target) has no accumulating step: its gradient scale is not threaded "
+                     "through the micro-steps")
         if (self.loss_normalise if normalise is None else normalise) == "weights":
             raise no(self.GRAD_ACCUM_WEIGHTS)
         if int(self.S) > 1:
@@ -2624,6 +2678,9 @@ class ModelBase:
         optimizer.apply_gradients -- the (commented-out) call of lc_NIC.py:388.  clip_factor=None switches it off."""
         if clip_factor is not None and self.dp_world > 1:
             raise NotImplementedError("adaptive gradient clipping is not supported under data parallel (dp.attach)")
+        if clip_factor is not None and self.semantic is not None:
+            raise NotImplementedError("semantic (the sentence-embedding target) is not built for adaptive gradient clipping "
+                                      "(enable_agc)")
         if clip_factor is not None and (self.seg_wd is not None or
                                         check_weight_decay(getattr(self.optimizer, "weight_decay", None))):
             raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))

@@ -19,7 +19,7 @@ import torch
 
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
-                         SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, check_sampling, check_beam,
+                         SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, SemanticTarget, check_sampling, check_beam,
                          _TokenChoice, _BeamDecode, EncGram, EncUpdate, StepRoute)
 from .evaluate import REWARD_KINDS, REWARD_MAX_LEN, REWARD_MAX_REFS, pack_references
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
@@ -45,7 +45,7 @@ class NIC(ModelBase):
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
-                 scan_dropout=None, word_dropout=None, **kw):
+                 scan_dropout=None, word_dropout=None, semantic=None, **kw):
         super().__init__(**kw)
         self.N, self.U, self.E, self.V, self.max_length = int(input_size), int(units), int(embedding_dim), int(vocab_size), int(max_length)
         self.r_in, self.r_feat, self.r_lstm = float(dropout_input), float(dropout), float(dropout_lstm)
@@ -83,6 +83,13 @@ class NIC(ModelBase):
                                  f"vocab_size {V} is above 65536")
         self.self_critical = self_critical
         self._rollout_ss = ScheduledSampling.linear(1.0, 0.0, 1.0, mode="sample") if self_critical is not None else None
+        # semantic (model_base.SemanticTarget): train_step adds weight * mean_b (1 - cos(x_b W + bias, guse_b)) to its loss, x_b
+        # the feature row the first LSTM step receives and guse the batch's fifth input; one layer of its own (guse_out), whose
+        # arena entries sit behind every other; None builds nothing and keeps launches and bits
+        if semantic is not None and not isinstance(semantic, SemanticTarget):
+            raise ValueError(f"semantic must be None or a model_base.SemanticTarget, got {semantic!r}")
+        self.semantic = semantic
+        self._semantic_check()
         self.ldx, self.ldV = _r4(N), _r4(V)
         self.layers_spec = OrderedDict([
             ("dense_img", ["kernel", "bias"]),
@@ -97,6 +104,10 @@ class NIC(ModelBase):
             ("emb_text/embeddings", (V, E)),
             ("lstm/kernel", (E, 4 * U)), ("lstm/recurrent_kernel", (U, 4 * U)), ("lstm/bias", (4 * U,)),
             ("time_distributed_softmax/kernel", (U, V)), ("time_distributed_softmax/bias", (V,))])
+        if semantic is not None:
+            self.G, self.ldG = semantic.dim, _r4(semantic.dim)
+            self.layers_spec[SemanticTarget.LAYER] = ["kernel", "bias"]
+            self.keras_shapes["guse_out/kernel"], self.keras_shapes["guse_out/bias"] = (E, self.G), (self.G,)
         a = self.arena = ParamArena(self.device)
         a.add("dense_img/kernel", (N, E), self.l2_in)
         a.add("dense_img/bias", (E,))
@@ -108,6 +119,9 @@ class NIC(ModelBase):
         a.add("lstm/bias", (U, 4))
         a.add("time_distributed_softmax/kernel", (U, self.ldV), self.l2_out)
         a.add("time_distributed_softmax/bias", (self.ldV,))
+        if semantic is not None:            # behind every entry of the model without it; rows padded as the head pads V
+            a.add("guse_out/kernel", (E, self.ldG), semantic.reg)
+            a.add("guse_out/bias", (self.ldG,))
         a.finalize()
         self.mov_mean, self.mov_var = self._f(E), torch.ones(E, dtype=torch.float32, device=self.device)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -148,6 +162,9 @@ class NIC(ModelBase):
         self.set_weight("lstm/bias", b)
         self.set_weight("time_distributed_softmax/kernel", tn((U, V), np.sqrt(2.0 / (U + V))))
         self.set_weight("batch_norm/gamma", np.ones(E))
+        if self.semantic is not None:       # glorot_uniform, drawn behind every other weight: those keep their values
+            lim = np.sqrt(6.0 / (E + self.G))
+            self.set_weight("guse_out/kernel", rng.uniform(-lim, lim, (E, self.G)))
 
     def _state_map(self):
         return {f"{self.BN}/moving_mean": self.mov_mean, f"{self.BN}/moving_variance": self.mov_var}
@@ -226,6 +243,9 @@ class NIC(ModelBase):
         self.work = f(max(E, 4 * U, ldV) * (2 * nch + 1))
         self.work2 = f(max(E, 4 * U, ldV) * (2 * nch + 1))
         self.rowsq = f(B * T)
+        if self.semantic is not None:       # the staged target, the prediction (its gradient in place), the rows' loss and cos
+            self.sem_g, self.sem_z = f(B, self.ldG), f(B, self.ldG)
+            self.sem_loss, self.sem_cos = f(B), f(B)
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
@@ -235,7 +255,7 @@ class NIC(ModelBase):
 
     def _stage_inputs(self, data):
         self._route = StepRoute()
-        x, cap, a0, c0 = data
+        x, cap, a0, c0 = data[:4]           # (a fifth input, the sentence embedding, is train_step's / test_step's)
         cap_t = self._to_dev(cap, torch.int32)
         B, T = cap_t.shape
         self._build(B, T)
@@ -295,6 +315,108 @@ class NIC(ModelBase):
         """one-launch encoder tail (tnt_enc_tail_*): BatchNorm encoder, batch <= 256 rows, E % 4 == 0"""
         return (self.norm == "batch" and B <= 256 and self.E % 4 == 0 and self.fuse_tail
                 and not self._sync_bn_on())        # synchronised BatchNorm: the statistics leave the kernel for a collective
+
+    # ------------------------------------------------------------------ sentence-embedding target (model_base.SemanticTarget)
+    SEMANTIC_DP_REFUSAL = ("semantic (the sentence-embedding target) has no data-parallel schedule: its mean runs over one "
+                           "rank's rows and the gradient launches of guse_out sit in none of the all-reduce buckets; train it on "
+                           "one device")
+
+    def _semantic_check(self):
+        """what a model with semantic= refuses, in the constructor and again in front of every step (grad_sync may have been
+        attached since); compile, set_teacher, enable_agc, freeze / set_lr_multipliers and dp.attach refuse on their side"""
+        if self.semantic is None:
+            return
+        if self.scheduled_sampling is not None:
+            raise NotImplementedError("semantic (the sentence-embedding target) has not been checked under scheduled_sampling")
+        if self.self_critical is not None:
+            raise NotImplementedError("semantic (the sentence-embedding target) is not built for the self_critical step, whose "
+                                      "rows are copies of the scans")
+        if self.grad_sync is not None or self.dp_world > 1:
+            raise NotImplementedError(self.SEMANTIC_DP_REFUSAL)
+
+    def _semantic_target(self, inputs):
+        """the batch's fifth input as a (B, G) float32 tensor on the device, checked in front of every launch; None without
+        semantic= (a fifth input is then ignored)"""
+        if self.semantic is None:
+            return None
+        if len(inputs) < 5 or inputs[4] is None:
+            raise ValueError(f"a model with semantic= takes (betas, cap, a0, c0, guse): the batch has {len(inputs)} inputs")
+        B, G = int(np.shape(inputs[1])[0]), self.G
+        if tuple(np.shape(inputs[4])) != (B, G):
+            raise ValueError(f"guse shape {tuple(np.shape(inputs[4]))} != {(B, G)} (batch, SemanticTarget.dim)")
+        return self._to_dev(inputs[4], torch.float32)
+
+    def _semantic_stage(self, guse):
+        """the target into its static buffer (a copy in front of the step: a replayed plan or graph reads each batch's own)"""
+        if guse is not None:
+            self.sem_g[:, :self.G].copy_(guse)
+
+    def _semantic_fwd(self, B, want_grad):
+        """z = x W + bias on the model's product route, then tnt_cosine_loss_f32: the rows' loss and cos, the unweighted mean
+        into met[6] and (``want_grad``) the gradient of weight * mean in place of z.  x = xin[:B], the feature rows the first
+        LSTM step was fed.  Issued behind the encoder tail, whose launch writes those rows."""
+        if self.semantic is None:
+            return
+        a, E, G, ldG = self.arena, self.E, self.G, self.ldG
+        x = self._route.xin_used
+        self.gemm_sk(x, a.p("guse_out/kernel"), self.sem_z, B, G, E, E, ldG, ldG, bias=a.p("guse_out/bias"))
+        k = SemanticTarget.SLOT
+        self.be.cosine_loss(self.sem_z, ldG, self.sem_g, ldG, self.sem_z if want_grad else None, self.sem_loss, self.sem_cos,
+                            self.met[k:k + 1], B, G, self.semantic.weight / B)
+
+    def _semantic_bwd_w(self, B):
+        """the layer's gradients: dW = x^T dz with the bias gradient as the column-sum rider where the route offers it"""
+        if self.semantic is None:
+            return
+        a, E, G, ldG = self.arena, self.E, self.G, self.ldG
+        x, dz = self._route.xin_used, self.sem_z
+        if self.g3_riders and self.gemm3(x, dz, a.g("guse_out/kernel"), E, G, B, E, ldG, ldG, transA=True,
+                                         colsum=a.g("guse_out/bias")):
+            return
+        self.gemm_sk(x, dz, a.g("guse_out/kernel"), E, G, B, E, ldG, ldG, transA=True)
+        self.be.colsum(dz, a.g("guse_out/bias"), B, G, ldG, self.work2)
+
+    def _semantic_bwd_x(self, B):
+        """dXin[:B] += dz W^T, an accumulating product on the stream that wrote dXin (the pair launch of _bwd_seq_lstm or the
+        product at the top of _bwd_seq_front) and in front of the tail backward that reads it"""
+        if self.semantic is None:
+            return
+        a, E, G, ldG = self.arena, self.E, self.G, self.ldG
+        self.gemm_sk(self.sem_z, a.p("guse_out/kernel"), self.dXin, B, E, G, ldG, ldG, E, transB=True, accumulate=True)
+
+    def _infer_encode(self, B, x):
+        """the inference encoder (dense_img, LeakyReLU, BatchNorm / LayerNorm on the moving statistics) of the rows ``x``
+        into Xin[:B]"""
+        be, a = self.be, self.arena
+        N, E = self.N, self.E
+        self.gemm_sk(x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
+                     pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
+        if self.norm == "batch":
+            be.batchnorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.mov_mean, self.mov_var,
+                             self.Xin, self.xhat, self.inv_std, B, E, E, False, BN_EPS, BN_MOMENTUM, self.work)
+        else:
+            be.layernorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.Xin, self.xhat,
+                             self.inv_std, B, E, E, BN_EPS)
+
+    def predict_embedding(self, betas):
+        """The predicted sentence embedding z = x W + bias of the scans ``betas`` (B, n_voxels) -> (B, dim) float32 on the
+        model's device, x the inference encoder's feature row (what a decode feeds its feature step): the encoder and one
+        product, no decoder step and no decode buffer.  Not normalised: evaluate.semantic_retrieve divides by the norms."""
+        if self.semantic is None:
+            raise ValueError("predict_embedding needs a model built with semantic=model_base.SemanticTarget(...)")
+        xs = self._to_dev(betas, torch.float32)
+        if xs.dim() != 2 or xs.shape[1] != self.N:
+            raise ValueError(f"betas shape {tuple(xs.shape)} != (batch, {self.N})")
+        B = int(xs.shape[0])
+        self._build(B, self._shape[1] if self._shape is not None and self._shape[0] == B else 1)
+        self.x[:, :self.N].copy_(xs)
+        a, E, G, ldG = self.arena, self.E, self.G, self.ldG
+
+        def run():
+            self._infer_encode(B, self.x)
+            self.gemm_sk(self.Xin, a.p("guse_out/kernel"), self.sem_z, B, G, E, E, ldG, ldG, bias=a.p("guse_out/bias"))
+        self._run_captured(("embed", B), run)
+        return self.sem_z[:, :G].clone()
 
     # ------------------------------------------------------------------ forward
     def _forward(self, B, T, training, ss=False):
@@ -446,6 +568,7 @@ class NIC(ModelBase):
     # ------------------------------------------------------------------ backward
     def _backward(self, B, T):
         self._bwd_head(B, T, join=False)       # dW of the head keeps running beside the BPTT chain
+        self._semantic_bwd_w(B)
         self._bwd_seq(B, T, join=False)
         self._bwd_enc(B, T)
         self.join()
@@ -579,6 +702,7 @@ class NIC(ModelBase):
         sd, ds = self.seed, self.drop_step
         if not self._route.dxin_done:
             self.gemm_sk(self.dZ, a.p("lstm/kernel"), self.dXin, R1, E, 4 * U, 4 * U, 4 * U, E, transB=True)
+        self._semantic_bwd_x(B)
         fused = self._fused_tail(B)
         if self.r_lstm > 0:
             if not fused:
@@ -682,6 +806,7 @@ class NIC(ModelBase):
     def _train_graph(self, B, T):
         self._forward(B, T, True, ss=self.scheduled_sampling is not None)
         self._loss_metrics(B, T, True)
+        self._semantic_fwd(B, True)
         self._backward(B, T)
 
     def train_step(self, data):
@@ -691,6 +816,7 @@ class NIC(ModelBase):
             raise RuntimeError("compile() the model before train_step")
         self._ss_refuse()
         self._corrupt_check()                       # (grad_sync may have been attached since the constructor)
+        self._semantic_check()
         if self.self_critical is not None:
             return self.train_step_scst(data)
         self._sync_accum()
@@ -699,7 +825,9 @@ class NIC(ModelBase):
         # the staging launch and the head keeps its position-ordered rows; so does a distilled step (the staging launch's
         # encoder forward needs the row map beside it)
         plain = self.grad_sync is None and self._accum_k() is None and not distill
+        guse = self._semantic_target(data[0])
         B, T = self._stage_batch(data[0], data[1], self.N, head_map=plain, fwd=plain, corrupt=True)
+        self._semantic_stage(guse)
         self._ss_refuse(T)
         if distill:
             self._teach(data, B, T)
@@ -715,6 +843,8 @@ class NIC(ModelBase):
             compact = self._route.head_map_fresh        # the staging launch built the head's row map
             staged = self._route.stage_fwd_done         # ... and ran the encoder forward: the step leaves it out
             key = ("train", B, T, "compact") if compact else ("train", B, T, "distill") if distill else ("train", B, T)
+            if self.semantic is not None:       # the step with the term is another launch sequence
+                key += ("semantic",)
             seen = self._plan_staged
             if self._graphs.get(key) is not None and seen.get(key) != staged:
                 del self._graphs[key]       # recorded with / without the forward (the entry refuses by alignment): start over
@@ -731,6 +861,8 @@ class NIC(ModelBase):
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         kl = dict(distill_kl=self.DISTILL_KL) if distill else {}
+        if self.semantic is not None:
+            kl["semantic"] = SemanticTarget.SLOT
         return self._lr_metric(self._metrics_from(m, loss=0, L2=2, accuracy=1, **kl))
 
     # ------------------------------------------------------------------ self-critical sequence training
@@ -947,15 +1079,20 @@ class NIC(ModelBase):
 
     def test_step(self, data):
         """NIC.test_step (NIC.py:254-299)."""
+        self._semantic_check()
+        guse = self._semantic_target(data[0])
         B, T = self._stage_batch(data[0], data[1], self.N)
+        self._semantic_stage(guse)
+        sem = self.semantic is not None
 
         def run():
             self._forward(B, T, False)
             self._loss_metrics(B, T, False)
+            self._semantic_fwd(B, False)
             self._norms_and_l2(self.met[2:3])
-        self._run_captured(("test", B, T), run)
+        self._run_captured(("test", B, T) + (("semantic",) if sem else ()), run)
         m = self._met_snapshot()
-        return self._metrics_from(m, loss=0, L2=2, accuracy=1)
+        return self._metrics_from(m, loss=0, L2=2, accuracy=1, **(dict(semantic=SemanticTarget.SLOT) if sem else {}))
 
     def __call__(self, data, training=False):
         """NIC.call (NIC.py:100-145): returns probabilities (B, T, V)."""
@@ -1002,17 +1139,8 @@ class NIC(ModelBase):
         """the inference encoder (dense_img, BatchNorm / LayerNorm) and the feature LSTM step of a decode over the staged
         B rows: the state after the feature step is Hs[1], Cs[1].  ``src`` = (x, h0, c0, h1, c1): other input rows and
         initial state, and where the state after the feature step goes"""
-        be, a = self.be, self.arena
-        N, E = self.N, self.E
         x, h0, c0, h1, c1 = src if src is not None else (self.x, self.Hs[0], self.Cs[0], self.Hs[1], self.Cs[1])
-        self.gemm_sk(x, a.p("dense_img/kernel"), self.enc_y, B, E, N, self.ldx, E, E, bias=a.p("dense_img/bias"),
-                     pre=self.enc_pre, act=ACT_LEAKY, slope=0.2)
-        if self.norm == "batch":
-            be.batchnorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.mov_mean, self.mov_var,
-                             self.Xin, self.xhat, self.inv_std, B, E, E, False, BN_EPS, BN_MOMENTUM, self.work)
-        else:
-            be.layernorm_fwd(self.enc_y, a.p("batch_norm/gamma"), a.p("batch_norm/beta"), self.Xin, self.xhat,
-                             self.inv_std, B, E, E, BN_EPS)
+        self._infer_encode(B, x)
         self._feature_step(self.Xin, B, self.XZ[:B], h0, c0, h1, c1, self.gates[0])
 
     def _feature_step(self, feat, rows, xz, h_in, c_in, h_out, c_out, gates):

@@ -1035,6 +1035,22 @@ class HipBackend:
         self._call(self.lib.tnt_init_state_bwd_f32, "tnt_init_state_bwd_f32", _p(dh0), _p(dc0), _p(h0), _p(c0), _p(fmean),
                    _p(Wh), _p(Wc), _p(dWh), _p(dbh), _p(dWc), _p(dbc), _p(dF), B, R, D, U, self._s())
 
+    def cosine_loss(self, z, ldz, g, ldg, dz, loss_row, cos_row, out, B, G, gscale):
+        """the cosine loss of B prediction / target rows (tnt_cosine_loss_f32; definition in include/tnt_hip.h): dz (nullable,
+        may be z) the gradient of gscale * sum of the rows' losses, out (nullable) their mean"""
+        self._call(self.lib.tnt_cosine_loss_f32, "tnt_cosine_loss_f32", _p(z), int(ldz), _p(g), int(ldg), _p(dz), _p(loss_row),
+                   _p(cos_row), _p(out), int(B), int(G), float(gscale), self._s())
+
+    def row_inv_norm(self, X, ldx, inv, rows, G):
+        """inv[r] = 1 / sqrt(max(sum X[r]^2, 1e-12)) (tnt_row_inv_norm_f32)"""
+        self._call(self.lib.tnt_row_inv_norm_f32, "tnt_row_inv_norm_f32", _p(X), int(ldx), _p(inv), int(rows), int(G), self._s())
+
+    def cosine_topk(self, S, lds, qinv, binv, idx, sim, B, M, k):
+        """the k largest cosine similarities (S[b][m] * qinv[b]) * binv[m] of every row and their indices, descending, ties by
+        ascending index, NaN last (tnt_cosine_topk_f32)"""
+        self._call(self.lib.tnt_cosine_topk_f32, "tnt_cosine_topk_f32", _p(S), int(lds), _p(qinv), _p(binv), _p(idx), _p(sim),
+                   int(B), int(M), int(k), self._s())
+
 
 def attention_coverage_work_floats(T, B, R, axis):
     """floats of ``work`` of tnt_attention_coverage_f32 (the formula of include/tnt_hip.h): one partial per 256 regions of a
