@@ -19,6 +19,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import compat
+
 warnings.filterwarnings("ignore", message=".*all_reduce_coalesced.*")
 
 
@@ -419,62 +421,10 @@ def attach(model, world=None, bucket_elems=None, pipelined=None, rank=None, sync
     shard_encoder=True (dense-encoder NIC; default: TNT_DP_SHARD_ENC): the encoder kernel's update is row-sharded over the
     ranks (PipelinedDenseSync.step).  Every rank keeps the complete, identical kernel; only the optimizer moments of a shard
     live on its owner alone."""
-    if not model.teacher_forcing:
-        # the free-running training step (lc_nic.NIC(teacher_forcing=False)) has no data-parallel schedule: refuse instead
-        # of running the teacher-forced one
-        raise NotImplementedError("data parallel training of the free-running decoder (teacher_forcing=False) is not "
-                                  "supported: train it on one device")
-    if model.scheduled_sampling is not None:
-        # nic.NIC / lc_nic.NIC(scheduled_sampling=...) have no data-parallel schedule either
-        raise NotImplementedError("data parallel training with scheduled sampling is not supported: train it on one device")
-    if model.self_critical is not None:
-        # nic.NIC(self_critical=...): the step's host round trip has no data-parallel schedule
-        raise NotImplementedError("data parallel self-critical training is not supported: train it on one device")
-    if model.average is not None:
-        # compile(optimizers.MovingAverage / SWA): the averaging launch has no place in the data-parallel schedules
-        raise NotImplementedError(model.AVERAGE_DP_REFUSAL)
-    if model.seg_wd is not None or getattr(model.optimizer, "weight_decay", None):
-        # compile(AdamW / weight_decay=): the data-parallel update launches (slices, the row-sharded encoder) do not decay
-        raise NotImplementedError(model.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
-                                                                    "row-sharded encoder update included)"))
-    if getattr(model.optimizer, "global_clipnorm", None) is not None:
-        # compile(global_clipnorm=): the pipelined schedules update in slices before all norms exist
-        raise NotImplementedError(model.GLOBAL_CLIP_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync)"))
-    if getattr(model.optimizer, "gradient_accumulation_steps", None) is not None:
-        # compile(gradient_accumulation_steps=): the sum over micro-steps takes the all-reduce's place; the two are not combined
-        raise NotImplementedError(model.GRAD_ACCUM_REFUSAL.format(what="accumulation under data parallel (dp.attach / grad_sync) "
-                                                                  "is not implemented"))
-    if model._lr_mul:
-        # freeze / set_lr_multipliers: the data-parallel update launches (slices, the row-sharded encoder) take no table
-        raise NotImplementedError(model.FINETUNE_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, the "
-                                                                "row-sharded encoder update included)"))
-    if model.loss_normalise == "weights":
-        # compile(CategoricalCrossentropy(normalise="weights")): the denominator is formed per rank
-        raise NotImplementedError(model.WEIGHTS_DP_REFUSAL)
-    if model.attention_coverage is not None:
-        # lc_nic.NIC(attention_coverage=...): the sum over the batch axis is not a per-rank quantity
-        raise NotImplementedError(model.COVERAGE_DP_REFUSAL)
-    if model.init_state is not None:
-        # lc_nic.NIC(init_state=...): its gradient launches sit in none of the all-reduce buckets
-        raise NotImplementedError(model.INIT_STATE_DP_REFUSAL)
-    if model.semantic is not None:
-        # nic.NIC(semantic=...): the mean over the batch and the layer's gradient launches are per rank
-        raise NotImplementedError(model.SEMANTIC_DP_REFUSAL)
-    if model._corruption() is not None:
-        # nic.NIC / lc_nic.NIC(scan_dropout=..., word_dropout=...): single device only
-        raise NotImplementedError(model.CORRUPT_DP_REFUSAL)
-    if model._distill_on():
-        # compile(CategoricalCrossentropy(distillation=...)): no data-parallel schedule runs the teacher
-        raise NotImplementedError(model.DISTILL_REFUSAL.format(what="there is no data-parallel schedule (dp.attach / grad_sync) "
-                                                                   "that runs the teacher"))
+    compat.check(model, ("dp",), dp=True)                   # what has no data-parallel schedule, whatever the world
     world = dist.get_world_size() if world is None else world
     rank = dist.get_rank() if rank is None else rank
-    if model.agc and world > 1:
-        # agc.py:25-30 clips the Embedding by the column norms of its UN-merged IndexedSlices rows; across replicas those
-        # are per-rank partial sums that would have to be all-reduced before every rank scales the summed gradient, and
-        # the pipelined schedules update slice by slice without an AGC pass.  Not built: refuse instead of training wrong.
-        raise NotImplementedError("adaptive gradient clipping (enable_agc) is not supported under data parallel: "
-                                  "call enable_agc(None) before dp.attach, or train on one device")
+    compat.check(model, ("dp_multi",), dp_world=world)      # ... and what one rank may keep
     model.dp_world = world
     model.seed = (int(model.seed) + 0x9E3779B1 * int(rank)) & 0x7FFFFFFFFFFFFFFF
     from .nic import NIC as DenseNIC

@@ -21,6 +21,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from . import compat
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_TEXT, S_OUT, S_ATTN, S_LSTM_IN, S_LSTM_OUT, S_SS_COIN,
                          S_SS_DRAW, BN_EPS, BN_MOMENTUM, ScheduledSampling, check_sampling, check_length_penalty,
@@ -76,6 +77,8 @@ class NIC(ModelBase):
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
     SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
     SUPPORTS_DISTILLATION = True        # CategoricalCrossentropy(distillation=) / set_teacher (ModelBase._teach)
+    # what train_step checks (compat)
+    STEP_FEATURES = ("free_running", "scheduled_sampling", "attention_coverage", "init_state", "corruption")
 
     def __init__(self, groups, units, embedding_features, embedding_text, attn_units, vocab_size, max_length,
                  dropout_input, dropout_features, dropout_text, dropout_attn, dropout_lstm, dropout_out, input_reg,
@@ -260,8 +263,7 @@ class NIC(ModelBase):
         self._shape = None
         if not self.teacher_forcing:
             self._naive_check()
-        self._coverage_check()
-        self._init_state_check()
+        compat.check(self, ("scheduled_sampling", "free_running", "attention_coverage", "init_state"))
         # scan_dropout (model_base.ScanDropout) / word_dropout (model_base.WordDropout): train_step and train_step_sam corrupt
         # the staged batch (tnt_input_corrupt_f32, one launch behind the staging); None or rate 0 issues nothing
         self.scan_dropout, self.word_dropout = scan_dropout, word_dropout
@@ -643,56 +645,6 @@ class NIC(ModelBase):
         self._route.inter_used = inter
         self._head_out(inter, self.logits, n)
 
-    COVERAGE_DP_REFUSAL = ("attention_coverage has no data-parallel schedule: the sum over the batch axis is not a per-rank "
-                           "quantity, and the sum over time would need the ranks' gradient scales.  Train it on one device")
-
-    def _coverage_check(self):
-        """the combinations the coverage penalty is built for; anything else refuses instead of training another loss"""
-        if self.attention_coverage is None:
-            return
-        if not self.teacher_forcing:
-            raise NotImplementedError("attention_coverage is built for the teacher-forced step: not for teacher_forcing=False "
-                                      "(the free-running decoder)")
-        if self.scheduled_sampling is not None:
-            raise NotImplementedError("attention_coverage is built for the teacher-forced step: not for scheduled_sampling")
-        if self.S != 1:
-            raise NotImplementedError("attention_coverage is a single-subject term: n_subjects > 1 is not supported")
-        if self.use_layer_norm:
-            raise NotImplementedError("attention_coverage is not built for the LayerNormLSTMCell (use_layer_norm=True)")
-        if self.grad_sync is not None:
-            raise NotImplementedError(self.COVERAGE_DP_REFUSAL)
-
-    INIT_STATE_DP_REFUSAL = ("init_state (the learned initial LSTM state) has no data-parallel schedule: its gradient launches "
-                             "sit in none of the all-reduce buckets.  Train it on one device")
-
-    def _init_state_check(self):
-        """the combinations the learned initial state is built for; anything else refuses instead of running without it"""
-        if self.init_state is None:
-            return
-        if not self.teacher_forcing:
-            raise NotImplementedError("init_state (the learned initial LSTM state) has not been checked on the free-running "
-                                      "decoder: not with teacher_forcing=False")
-        if self.scheduled_sampling is not None:
-            raise NotImplementedError("init_state (the learned initial LSTM state) has not been checked under "
-                                      "scheduled_sampling")
-        if self.S != 1:
-            raise NotImplementedError("init_state (the learned initial LSTM state) is a single-subject layer: n_subjects > 1 "
-                                      "is not supported")
-        if self.use_layer_norm:
-            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for the LayerNormLSTMCell "
-                                      "(use_layer_norm=True)")
-        if self.agc:
-            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for adaptive gradient "
-                                      "clipping (enable_agc)")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise NotImplementedError(self.INIT_STATE_DP_REFUSAL)
-
-    def enable_agc(self, clip_factor=0.01, eps=1e-3):
-        if clip_factor is not None and self.init_state is not None:
-            raise NotImplementedError("init_state (the learned initial LSTM state) is not built for adaptive gradient "
-                                      "clipping (enable_agc)")
-        super().enable_agc(clip_factor, eps)
-
     def learn_init_state(self, img_input):
         """lc_NIC.learn_init_state (lc_NIC.py:169-173) on the scans ``img_input`` (B, n_voxels): (h0, c0), two (B, units)
         numpy arrays, in inference mode (moving BatchNorm statistics, no Dropout)"""
@@ -741,28 +693,15 @@ class NIC(ModelBase):
         return cov.key if cov is not None else ()
 
     def _naive_check(self):
-        """the combinations the free-running decoder is built for; anything else refuses instead of running another mode"""
-        if self.S != 1:
-            raise NotImplementedError("the free-running decoder (call_naive_attention) is a single-subject mode: n_subjects > 1 "
-                                      "is not supported")
-        if self.use_layer_norm:
-            raise NotImplementedError("the free-running decoder (call_naive_attention) is not built for the LayerNormLSTMCell "
-                                      "(use_layer_norm=True)")
+        """the shape the free-running decoder's feedback kernel is built for"""
         if self.Et % 4:
             raise NotImplementedError("the free-running decoder needs embedding_text % 4 == 0 (tnt_greedy_feedback_f32)")
 
     def _ss_check(self):
-        """the combinations scheduled sampling is built for; anything else refuses instead of training another mode"""
+        """the descriptor and the shape scheduled sampling's feedback kernel is built for"""
         ss = self.scheduled_sampling
         if not isinstance(ss, ScheduledSampling):
             raise ValueError(f"scheduled_sampling must be None or a model_base.ScheduledSampling, got {ss!r}")
-        if not self.teacher_forcing:
-            raise ValueError("scheduled_sampling is a teacher-forced curriculum: it cannot be combined with "
-                             "teacher_forcing=False (the free-running decoder)")
-        if self.S != 1:
-            raise NotImplementedError("scheduled sampling is a single-subject mode: n_subjects > 1 is not supported")
-        if self.use_layer_norm:
-            raise NotImplementedError("scheduled sampling is not built for the LayerNormLSTMCell (use_layer_norm=True)")
         if self.Et % 4 or self.Et > 1016:
             raise ValueError(f"scheduled sampling needs embedding_text % 4 == 0 and <= 1016 (tnt_scheduled_feedback2_f32), "
                              f"got {self.Et}")
@@ -1244,12 +1183,7 @@ class NIC(ModelBase):
         """lc_NIC.train_step (lc_NIC.py:328-408): returns {loss, L2, accuracy, attention, lr}."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
-        if not self.teacher_forcing and self.grad_sync is not None:
-            raise NotImplementedError("the free-running step (teacher_forcing=False) has no data-parallel schedule")
-        self._ss_refuse()
-        self._coverage_check()                      # (grad_sync may have been attached since the constructor)
-        self._init_state_check()
-        self._corrupt_check()
+        compat.check(self, self.STEP_FEATURES)       # (grad_sync may have been attached since the constructor)
         self._sync_accum()
         distill = self._distill_begin()
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)
@@ -1284,25 +1218,7 @@ class NIC(ModelBase):
         same dropout masks.  One captured launch sequence: two forward / backward passes and the update."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step_sam")
-        self._weight_decay_refuse("train_step_sam")
-        self._global_clip_refuse("train_step_sam")
-        self._finetune_refuse("train_step_sam")
-        self._grad_accum_refuse("train_step_sam applies an update of its own every step")
-        if not self.teacher_forcing:
-            raise NotImplementedError("train_step_sam is a teacher-forced step (lc_NIC.py:713-838): not built for "
-                                      "teacher_forcing=False")
-        if self.S != 1:
-            raise NotImplementedError("train_step_sam is a single-subject step (lc_NIC.py)")
-        if self.scheduled_sampling is not None:
-            raise NotImplementedError("train_step_sam is a teacher-forced step: not built for scheduled_sampling")
-        if self.attention_coverage is not None:
-            raise NotImplementedError("train_step_sam adds its own attention term (MSE(ones, attention_scores), the alpha_mse "
-                                      "gradient of its first pass): not built for attention_coverage")
-        if self.init_state is not None:
-            raise NotImplementedError("train_step_sam is not built for init_state (the learned initial LSTM state)")
-        if self._distill_on():
-            raise NotImplementedError(self.DISTILL_REFUSAL.format(what="train_step_sam's two passes do not run the teacher"))
-        self._corrupt_check()
+        compat.check(self, ("sam", "corruption"), sam="train_step_sam")
         B, T = self._stage_batch(data[0], data[1], self.n_in, masks=True, corrupt=True)      # both passes read this batch
         self._sync_lr()
         be, a = self.be, self.arena
@@ -1373,6 +1289,8 @@ class NIC(ModelBase):
         later step is fed the argmax of the step before.  Returns (probabilities (B,T,V), attention scores (T,B,R,1)),
         plus the predicted ids (B,T) int32 (the argmax of every step's output) with return_ids=True.  The argmax is taken
         over the logits (include/tnt_hip.h: tnt_greedy_feedback_f32)."""
+        # the decoder of this call is the free-running one, whatever the model trains with
+        compat.check(self, ("multi_subject", "layer_norm_lstm"), teacher_forcing=False)
         self._naive_check()
         B, T = self._stage_inputs(data)
 

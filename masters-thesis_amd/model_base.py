@@ -16,7 +16,7 @@ from typing import Any, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import compat, ops
 from .optimizers import (Adam, check_class_weight, loss_class_weight, loss_distillation, loss_focal_gamma, loss_label_smoothing,
                          loss_normalise,
                          loss_unlikelihood, optimizer_average, optimizer_schedule, check_global_clipnorm,
@@ -1313,45 +1313,20 @@ class ModelBase:
         if lr_multipliers is not None and not isinstance(lr_multipliers, dict):
             raise ValueError(f"lr_multipliers must be a mapping name -> multiplier, got {lr_multipliers!r}")
         mul = self._resolve_lr_multipliers(dict(lr_multipliers or {}, **{n: 0.0 for n in (freeze or ())}))
-        eps = loss_label_smoothing(loss)
-        if eps > 0 and not self.SUPPORTS_LABEL_SMOOTHING:
-            raise NotImplementedError(f"{type(self).__name__} computes its own masked sparse loss and does not read the "
-                                      "compile loss: label_smoothing > 0 is not implemented for it")
-        if eps > 0 and self.self_critical is not None:
-            raise ValueError("label_smoothing > 0 does not apply to a self_critical model: its loss is the "
-                             "advantage-weighted tnt_scst_cce_f32, not the compile loss")
-        alpha = loss_unlikelihood(loss)
-        if alpha > 0 and not self.SUPPORTS_UNLIKELIHOOD:
-            raise NotImplementedError(f"{type(self).__name__} does not compute its loss with the caption head over "
-                                      "(position, caption) rows: unlikelihood > 0 is not implemented for it")
-        if alpha > 0 and eps > 0:
-            raise ValueError("unlikelihood > 0 together with label_smoothing > 0 is not implemented: one head kernel "
-                             "computes one of the two")
-        if alpha > 0 and self.self_critical is not None:
-            raise ValueError("unlikelihood > 0 does not apply to a self_critical model: its loss is the "
-                             "advantage-weighted tnt_scst_cce_f32, not the compile loss")
+        eps, alpha = loss_label_smoothing(loss), loss_unlikelihood(loss)
         gamma, mode = loss_focal_gamma(loss), loss_normalise(loss)
         cw = loss_class_weight(loss, self.V)
-        self._check_token_weights(cw is not None, gamma, mode, eps, alpha)
         distill = loss_distillation(loss)
-        if distill is not None:
-            if eps > 0 or alpha > 0 or cw is not None or gamma > 0 or mode == "weights":
-                raise ValueError("distillation together with label_smoothing > 0, unlikelihood > 0 or class_weight / focal_gamma "
-                                 "/ normalise=\"weights\" is not implemented: one head kernel computes one of them")
-            if self.SUPPORTS_DISTILLATION and self.self_critical is not None:
-                raise ValueError("distillation does not apply to a self_critical model: its loss is the advantage-weighted "
-                                 "tnt_scst_cce_f32, not the compile loss")
-            self._distill_refuse(self.teacher, optimizer)
         avg = optimizer_average(optimizer)
-        if avg is not None and self.grad_sync is not None:
-            raise NotImplementedError(self.AVERAGE_DP_REFUSAL)
-        self._check_weight_decay(bool(check_weight_decay(getattr(optimizer, "weight_decay", None))))
-        self._check_global_clip(check_global_clipnorm(getattr(optimizer, "global_clipnorm", None)) is not None)
-        self._check_grad_accum(check_gradient_accumulation_steps(getattr(optimizer, "gradient_accumulation_steps", None))
-                               is not None, normalise=mode)
-        self._check_finetune(bool(self._merged_lr_mul(mul)), optimizer=optimizer)
+        lr_mul = self._merged_lr_mul(mul)
+        compat.check(self, ("label_smoothing", "unlikelihood", "token_weights", "normalise_weights", "distill_loss",
+                            "distillation", "average", "weight_decay", "global_clip", "grad_accum", "finetune"),
+                     optimizer=optimizer, label_smoothing=eps, unlikelihood=alpha, focal_gamma=gamma,
+                     loss_normalise=mode, class_weight=cw, distillation=distill, average=avg, _lr_mul=lr_mul)
+        if distill is not None:
+            self._check_teacher(self.teacher)
         self.optimizer = optimizer if optimizer is not None else Adam()
-        self._lr_mul = self._merged_lr_mul(mul)
+        self._lr_mul = lr_mul
         self.loss = loss
         # Fixed here, not read per step: the head launch sits inside captured graphs, with its smoothing, alpha, gamma and
         # mode as arguments.  The averaging launch sits inside the same plans / graphs, and its settings are launch
@@ -1368,37 +1343,13 @@ class ModelBase:
         if self.built:
             self._init_optimizer_state()
 
-    def _check_token_weights(self, has_weights, gamma, mode, eps, alpha):
-        """the refusals of class_weight / focal_gamma / normalise="weights" (compile, set_class_weight, dp.attach); neutral
-        settings pass everywhere"""
-        if not (has_weights or gamma > 0 or mode == "weights"):
-            return
-        what = "class_weight / focal_gamma / normalise=\"weights\""
-        if not self.SUPPORTS_TOKEN_WEIGHTS:
-            raise NotImplementedError(f"{type(self).__name__} does not compute its loss with the caption head over "
-                                      f"(position, caption) rows: {what} is not implemented for it")
-        if eps > 0 or alpha > 0:
-            raise ValueError(f"{what} together with label_smoothing > 0 or unlikelihood > 0 is not implemented: one head "
-                             "kernel computes one of them")
-        if self.self_critical is not None:
-            raise ValueError(f"{what} does not apply to a self_critical model: its loss is the advantage-weighted "
-                             "tnt_scst_cce_f32, not the compile loss")
-        if mode == "weights" and (self.grad_sync is not None or self.dp_world > 1):
-            raise NotImplementedError(self.WEIGHTS_DP_REFUSAL)
-        if mode == "weights" and self._accum_k() is not None:
-            raise NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=self.GRAD_ACCUM_WEIGHTS))
-        if mode == "weights" and int(self.S) > 1:
-            raise NotImplementedError("normalise=\"weights\" with n_subjects > 1 is not implemented: the per-subject metrics "
-                                      "divide each subject's sums by its position count Bs * T, not by its weight sum.  "
-                                      "normalise=\"count\" works")
-
-    WEIGHTS_DP_REFUSAL = ("normalise=\"weights\" is not implemented under data parallel: the weight sum the loss is divided by is "
-                          "formed per rank inside the head launch, so the ranks' gradients would carry different "
-                          "denominators.  normalise=\"count\" works")
-
-    def _token_weights_on(self):
-        """whether the head launch is tnt_softmax_cce_weighted_f32 (any non-neutral setting)"""
-        return self.class_weight is not None or self.focal_gamma > 0 or self.loss_normalise == "weights"
+    def _token_weights_on(self, pending=None):
+        """whether the head launch is tnt_softmax_cce_weighted_f32 (any non-neutral setting).  ``pending``: the values a
+        call is about to store, by attribute name (compat.check)"""
+        if not pending:
+            return self.class_weight is not None or self.focal_gamma > 0 or self.loss_normalise == "weights"
+        g = lambda name: pending[name] if name in pending else getattr(self, name)
+        return g("class_weight") is not None or g("focal_gamma") > 0 or g("loss_normalise") == "weights"
 
     def _store_class_weight(self, cw):
         """cw: None or a float32 array of V weights.  The device buffer is written in place where it exists, so a recorded
@@ -1419,45 +1370,19 @@ class ModelBase:
     def set_class_weight(self, class_weight):
         """Replace the token weights of a compiled model: an array-like of V weights, an ``{id: weight}`` dict (missing ids
         weigh 1) or None.  The next step, a replay of a recorded plan or graph included, uses them."""
-        if class_weight is not None and self._distill_on():
-            # compile's exclusion, for the weights that arrive behind it (fit(class_weight=) comes through here)
-            raise ValueError("class_weight together with distillation is not implemented: one head kernel computes one of "
-                             "them")
-        self._check_token_weights(class_weight is not None, self.focal_gamma, self.loss_normalise, self.label_smoothing,
-                                  self.unlikelihood)
+        compat.check(self, ("token_weights", "normalise_weights"), class_weight=class_weight)
         self._store_class_weight(None if class_weight is None else check_class_weight(class_weight, self.V))
 
     # ------------------------------------------------------------------ knowledge distillation (distillation= / set_teacher)
-    DISTILL_REFUSAL = ("knowledge distillation (CategoricalCrossentropy(distillation=...) / set_teacher) is built for the plain "
-                       "single-device teacher-forced step of nic.NIC and lc_nic.NIC only: {what}")
-
-    def _distill_on(self):
+    def _distill_on(self, pending=None):
         """whether the training head launch is tnt_softmax_cce_distill_f32 (a non-neutral descriptor)"""
-        return self.distillation is not None
+        return (pending["distillation"] if pending and "distillation" in pending else self.distillation) is not None
 
-    def _distill_refuse(self, teacher=None, optimizer=None):
-        """what a distilled step refuses, of the student and (where given) of its teacher: compile, set_teacher, dp.attach and
-        every distilled train_step call it.  ``optimizer``: the one compile is about to store."""
-        no = lambda what: NotImplementedError(self.DISTILL_REFUSAL.format(what=what))
-        if not self.SUPPORTS_DISTILLATION:
-            raise no(f"{type(self).__name__} does not support it")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise no("there is no data-parallel schedule (dp.attach / grad_sync) that runs the teacher")
-        opt = self.optimizer if optimizer is None else optimizer
-        if check_gradient_accumulation_steps(getattr(opt, "gradient_accumulation_steps", None)) is not None:
-            raise no("gradient_accumulation_steps has no distilled micro-step")
-        if self.scheduled_sampling is not None:
-            raise no("scheduled_sampling feeds the student its own words, the teacher the caption's")
-        if self.self_critical is not None:
-            raise no("a self_critical model's loss is the advantage-weighted tnt_scst_cce_f32, not the compile loss")
-        if self.semantic is not None:
-            raise no("semantic (the sentence-embedding target) was not checked beside a teacher's pass")
-        if not self.teacher_forcing:
-            raise no("the free-running decoder (teacher_forcing=False) feeds the student its own words")
-        if int(self.S) > 1:
-            raise no("n_subjects > 1 is not supported on the student")
+    def _check_teacher(self, teacher):
+        """what is refused of a teacher: a second model, not a feature of this one (compat holds what the student refuses)"""
         if teacher is None:
             return
+        no = lambda what: NotImplementedError(compat.DISTILL_REFUSAL.format(what=what))
         if teacher is self:
             raise no("a model cannot be its own teacher (its logits buffer is the one the student's gradient is written to)")
         if not isinstance(teacher, ModelBase) or not teacher.SUPPORTS_DISTILLATION:
@@ -1485,7 +1410,8 @@ class ModelBase:
             if adapt is not None:
                 raise ValueError("adapt= needs a teacher")
         else:
-            self._distill_refuse(teacher)
+            compat.check(self, ("distillation",), teacher=teacher)     # what the student refuses, descriptor or not
+            self._check_teacher(teacher)
             same = teacher.device.type == self.device.type and (teacher.device.index or 0) == (self.device.index or 0)
             if not same:
                 raise ValueError(f"the teacher sits on {teacher.device}, the student on {self.device}: both must share a device")
@@ -1517,7 +1443,8 @@ class ModelBase:
         """In front of a train_step's staging: whether the step is a distilled one, behind its refusals"""
         if not self._distill_on():
             return False
-        self._distill_refuse(self.teacher)
+        compat.check(self, ("distillation",))
+        self._check_teacher(self.teacher)
         if self.teacher is None:
             raise RuntimeError("the compile loss asks for distillation but the model has no teacher: call set_teacher(model) "
                                "before train_step")
@@ -1597,6 +1524,10 @@ class ModelBase:
 
     def _init_optimizer_state(self):
         a = self.arena
+        # decoupled weight decay: the per-variable table from the descriptor and its exclusions, which are final from here
+        # on (keras: exclude_from_weight_decay raises once the optimizer is built)
+        tab = weight_decay_table(self.optimizer, list(a.entries))
+        compat.check(self, ("weight_decay", "global_clip", "grad_accum", "finetune"), weight_decay=tab is not None)
         self.opt_m = torch.zeros_like(a.theta)
         self.opt_v = torch.zeros_like(a.theta) if self.optimizer.kind == "adam" else None
         self.adam_t = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -1611,49 +1542,24 @@ class ModelBase:
         # max(start_step, 1); until then it holds the initial ones
         self.opt_avg = a.theta.clone() if self.average is not None else None
         self._swapped = False
-        # decoupled weight decay: the per-variable table from the descriptor and its exclusions, which are final from here
-        # on (keras: exclude_from_weight_decay raises once the optimizer is built)
-        tab = weight_decay_table(self.optimizer, list(a.entries))
-        self._check_weight_decay(tab is not None)
         self.seg_wd = self.seg_wd_host = None
         self._store_seg_wd(tab)
         getattr(self.optimizer, "_optimizer", self.optimizer)._wd_built = True
         # global-norm clipping: the word tnt_global_sqnorm_f32 writes and every update launch of the step reads
         self.gsq = self._f(1)
         # learning-rate multipliers and frozen variables: the table of what set_lr_multipliers / freeze have asked for so far
-        self._check_finetune(bool(self._lr_mul))
         self.seg_lrm = self.seg_lrm_host = None
         self._store_seg_lrm()
         self._gsq_filed = False
         self._gclip_host = self._gclip()
-        self._check_global_clip(self._gclip_host is not None)
         # gradient accumulation: one more arena-sized buffer and the float beside it, only for a model that accumulates
         self._accum_host = self._accum_k()
-        self._check_grad_accum(self._accum_host is not None)
         self._accum_j = 0
         self.acc_grad = torch.zeros_like(a.grad) if self._accum_host is not None else None
         self.acc_sq = self._f(1) if self._accum_host is not None else None
         self._graphs = {}
 
     # ------------------------------------------------------------------ decoupled weight decay (Adam / SGD weight_decay=, AdamW)
-    WEIGHT_DECAY_REFUSAL = ("decoupled weight decay (weight_decay= / AdamW) is built for the single-device update launches only: "
-                            "{what} does not apply it.  Train with weight_decay=None there, or on one device without it")
-
-    def _check_weight_decay(self, on):
-        """the refusals of a decaying optimizer (compile, the optimizer-state build, set_weight_decay): data parallel and
-        adaptive gradient clipping; train_step_sam and dp.attach refuse on their side"""
-        if not on:
-            return
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync, "
-                                                                      "the row-sharded encoder update included)"))
-        if self.agc:
-            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
-
-    def _weight_decay_refuse(self, what):
-        if self.seg_wd is not None:
-            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what=what))
-
     def _store_seg_wd(self, tab):
         """tab: None (nothing decays: the plain update launches) or one decay per variable.  The device table is written in
         place where it exists, so a recorded plan or a captured graph that holds its address decays by the new values; a
@@ -1683,7 +1589,7 @@ class ModelBase:
         if self.optimizer is None or self.adam_t is None:
             raise RuntimeError("set_weight_decay: compile and build the model first")
         wd = check_weight_decay(value)
-        self._check_weight_decay(bool(wd))
+        compat.check(self, ("weight_decay",), weight_decay=wd)
         self.optimizer.weight_decay = wd
         self._store_seg_wd(weight_decay_table(self.optimizer, list(self.arena.entries)))
 
@@ -1693,27 +1599,10 @@ class ModelBase:
         return float(self.seg_wd_host[seg])
 
     # ------------------------------------------------------------------ global-norm clipping (Adam / SGD global_clipnorm=)
-    GLOBAL_CLIP_REFUSAL = ("global-norm clipping (global_clipnorm=) is built for the single-device update launches only: "
-                           "{what} does not apply it.  Train with clipnorm there, or on one device without it")
-
-    def _gclip(self):
-        """the optimizer's global_clipnorm: a float > 0, or None (off)"""
-        return None if self.optimizer is None else check_global_clipnorm(getattr(self.optimizer, "global_clipnorm", None))
-
-    def _check_global_clip(self, on):
-        """the refusals of a globally clipping optimizer (compile, the optimizer-state build, an assignment found by
-        _sync_lr): data parallel -- its pipelined schedules update in slices before all norms exist -- and adaptive
-        gradient clipping; train_step_sam and dp.attach refuse on their side"""
-        if not on:
-            return
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what="the data-parallel update (dp.attach / grad_sync)"))
-        if self.agc:
-            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
-
-    def _global_clip_refuse(self, what):
-        if self._gclip() is not None:
-            raise NotImplementedError(self.GLOBAL_CLIP_REFUSAL.format(what=what))
+    def _gclip(self, pending=None):
+        """the optimizer's global_clipnorm: a float > 0, or None (off).  ``pending``: as _token_weights_on takes it"""
+        opt = pending["optimizer"] if pending and "optimizer" in pending else self.optimizer
+        return None if opt is None else check_global_clipnorm(getattr(opt, "global_clipnorm", None))
 
     def _global_sqnorm(self, fin_kw=None):
         """The reduction launch of a globally clipped step (tnt_global_sqnorm_f32): behind the step's norm launch(es), in
@@ -1742,9 +1631,6 @@ class ModelBase:
         return float(self.gsq[0]) ** 0.5
 
     # ------------------------------------------------------------------ layer freezing and per-variable learning rates (fine-tuning)
-    FINETUNE_REFUSAL = ("layer freezing and learning-rate multipliers (freeze / set_lr_multipliers / layer.trainable) are built "
-                        "for the single-device update launches only: {what} does not apply them.  Unfreeze everything and "
-                        "clear the multipliers there, or train on one device without it")
     FINETUNE_BATCHNORM = ("freezing a BatchNorm layer ({name}) is not implemented: keras runs a frozen BatchNorm in inference "
                           "mode, on its moving statistics, and the training step here has no such mode.  Freeze the layers "
                           "around it, or give it a small multiplier; LayerNorm gains and biases freeze like any variable")
@@ -1791,28 +1677,6 @@ class ModelBase:
     def _merged_lr_mul(self, new):
         return {n: m for n, m in dict(self._lr_mul, **new).items() if m != 1.0}
 
-    def _check_finetune(self, on, optimizer=None):
-        """the refusals of a model with a multiplier table (compile, the optimizer-state build, set_lr_multipliers): data
-        parallel, adaptive gradient clipping and gradient accumulation; train_step_sam, dp.attach, enable_agc and the
-        accumulation check refuse on their side"""
-        if not on:
-            return
-        no = lambda what: NotImplementedError(self.FINETUNE_REFUSAL.format(what=what))
-        if self.semantic is not None:
-            raise no("a model with semantic= (the sentence-embedding target: its launches do not leave out a frozen "
-                     "variable's share)")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise no("the data-parallel update (dp.attach / grad_sync, the row-sharded encoder update included)")
-        if self.agc:
-            raise no("a step with adaptive gradient clipping (enable_agc)")
-        opt = self.optimizer if optimizer is None else optimizer
-        if check_gradient_accumulation_steps(getattr(opt, "gradient_accumulation_steps", None)) is not None:
-            raise no("a step with gradient_accumulation_steps")
-
-    def _finetune_refuse(self, what):
-        if self._lr_mul:
-            raise NotImplementedError(self.FINETUNE_REFUSAL.format(what=what))
-
     def set_lr_multipliers(self, mapping):
         """Per-variable learning-rate multipliers: {layer name, variable name or substring: mul}, mul a finite float >= 0.
         Adam steps the variable by mul * lr_t, SGD by mul * lr, decoupled decay by (mul * lr * wd) * theta, a schedule's rate
@@ -1823,7 +1687,7 @@ class ModelBase:
         if not isinstance(mapping, dict):
             raise ValueError(f"set_lr_multipliers takes a mapping name -> multiplier, got {mapping!r}")
         new = self._merged_lr_mul(self._resolve_lr_multipliers(mapping))
-        self._check_finetune(bool(new))
+        compat.check(self, ("finetune",), _lr_mul=new)
         self._lr_mul = new
         if self.adam_t is not None:
             self._store_seg_lrm()
@@ -1895,53 +1759,11 @@ class ModelBase:
         return kw
 
     # ------------------------------------------------------------------ gradient accumulation (Adam / SGD gradient_accumulation_steps=)
-    GRAD_ACCUM_REFUSAL = ("gradient accumulation (gradient_accumulation_steps=) is built for the teacher-forced single-device "
-                          "train_step of nic.NIC and lc_nic.NIC only: {what}.  Train with gradient_accumulation_steps=None there")
-    GRAD_ACCUM_WEIGHTS = ("normalise=\"weights\" divides each head launch's gradient by the weight sum of its own micro-batch, so "
-                          "the micro-steps would carry different denominators (the reason of WEIGHTS_DP_REFUSAL); "
-                          "normalise=\"count\" works")
-
-    def _accum_k(self):
-        """the optimizer's gradient_accumulation_steps: an int >= 2, or None (off)"""
-        return None if self.optimizer is None else check_gradient_accumulation_steps(
-            getattr(self.optimizer, "gradient_accumulation_steps", None))
-
-    def _check_grad_accum(self, on, normalise=None):
-        """the refusals of an accumulating optimizer (compile, the optimizer-state build, an assignment found by
-        _sync_accum, every micro-step); dp.attach, enable_agc, train_step_sam and the token-weight check refuse on their
-        side.  ``normalise``: the compile loss's mode where compile has not stored it yet."""
-        if not on:
-            return
-        no = lambda what: NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=what))
-        if not self.SUPPORTS_GRAD_ACCUMULATION:
-            raise no(f"{type(self).__name__} has no accumulating step")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise no("accumulation under data parallel (dp.attach / grad_sync) is not implemented")
-        if self.agc:
-            raise no("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the window's")
-        if self._lr_mul:
-            raise NotImplementedError(self.FINETUNE_REFUSAL.format(what="a step with gradient_accumulation_steps"))
-        if self.scheduled_sampling is not None:
-            raise no("scheduled_sampling has no accumulating step")
-        if self.self_critical is not None:
-            raise no("self_critical has no accumulating step")
-        if not self.teacher_forcing:
-            raise no("the free-running decoder (teacher_forcing=False) has no accumulating step")
-        if self.attention_coverage is not None:
-            raise no("attention_coverage's gradient scale is not threaded through the micro-steps")
-        if self.init_state is not None:
-            raise no("init_state (the learned initial LSTM state) has no accumulating step")
-        if self.semantic is not None:
-            raise no("semantic (the sentence-embedding target) has no accumulating step: its gradient scale is not threaded "
-                     "through the micro-steps")
-        if (self.loss_normalise if normalise is None else normalise) == "weights":
-            raise no(self.GRAD_ACCUM_WEIGHTS)
-        if int(self.S) > 1:
-            raise no("n_subjects > 1 has no accumulating step")
-
-    def _grad_accum_refuse(self, what):
-        if self._accum_k() is not None:
-            raise NotImplementedError(self.GRAD_ACCUM_REFUSAL.format(what=what))
+    def _accum_k(self, pending=None):
+        """the optimizer's gradient_accumulation_steps: an int >= 2, or None (off).  ``pending``: as _token_weights_on
+        takes it"""
+        opt = pending["optimizer"] if pending and "optimizer" in pending else self.optimizer
+        return None if opt is None else check_gradient_accumulation_steps(getattr(opt, "gradient_accumulation_steps", None))
 
     def _sync_accum(self):
         """In front of every training step (train_step of the accumulating models, in front of the staging; _sync_lr): an
@@ -1956,7 +1778,7 @@ class ModelBase:
             raise RuntimeError(f"gradient_accumulation_steps changed from {self._accum_host} to {k} inside an open window "
                                f"({self._accum_j} micro-steps accumulated): finish the window or call reset_accumulation() "
                                "first")
-        self._check_grad_accum(k is not None)
+        compat.check(self, ("grad_accum",))
         self._accum_host = k
         self.acc_grad = torch.zeros_like(self.arena.grad) if k is not None else None
         self.acc_sq = self._f(1) if k is not None else None
@@ -2002,7 +1824,7 @@ class ModelBase:
         raises where the metrics are read, and _on_guard_trip reopens the window.
         Each phase is a recording of its own, replayed as a hipGraph: the dense Embedding backward hands its ids on with a
         tensor copy, which a launch plan would drop (see _step_runner)."""
-        self._check_grad_accum(True)
+        compat.check(self, ("grad_accum",))
         k, j, a = self._accum_host, self._accum_j, self.arena
         phase = 0 if j == 0 else (2 if j == k - 1 else 1)
         seg = self.emb_seg
@@ -2020,11 +1842,6 @@ class ModelBase:
         self._accum_j = 0 if phase == 2 else j + 1
         return phase == 2
 
-    AVERAGE_DP_REFUSAL = ("weight averaging (optimizers.MovingAverage / SWA) has no data-parallel schedule: the pipelined "
-                          "schedules update the arena in slices and the row-sharded encoder finishes its update behind "
-                          "_update_fused, so one averaging launch behind the update has no single place there.  Train it on "
-                          "one device")
-
     def _sync_lr(self):
         """in front of the update of every training step: the host-set learning rate to the device -- and the refusal of a
         step while the average sits in the weights (swap_weights / averaged_weights)"""
@@ -2035,7 +1852,7 @@ class ModelBase:
         if gclip != self._gclip_host:
             # optimizer.global_clipnorm was assigned since the state was built: the threshold is an argument of the update
             # launches, and switching it on or off changes which launches run -- the step is recorded again
-            self._check_global_clip(gclip is not None)
+            compat.check(self, ("global_clip",))
             self._gclip_host = gclip
             self._graphs = {}
         self._sync_accum()      # ... and optimizer.gradient_accumulation_steps, between two windows only
@@ -2676,19 +2493,7 @@ class ModelBase:
     def enable_agc(self, clip_factor=0.01, eps=1e-3):
         """gradients = agc.adaptive_clip_grad(trainable_variables, gradients, clip_factor, eps) before
         optimizer.apply_gradients -- the (commented-out) call of lc_NIC.py:388.  clip_factor=None switches it off."""
-        if clip_factor is not None and self.dp_world > 1:
-            raise NotImplementedError("adaptive gradient clipping is not supported under data parallel (dp.attach)")
-        if clip_factor is not None and self.semantic is not None:
-            raise NotImplementedError("semantic (the sentence-embedding target) is not built for adaptive gradient clipping "
-                                      "(enable_agc)")
-        if clip_factor is not None and (self.seg_wd is not None or
-                                        check_weight_decay(getattr(self.optimizer, "weight_decay", None))):
-            raise NotImplementedError(self.WEIGHT_DECAY_REFUSAL.format(what="a step with adaptive gradient clipping (enable_agc)"))
-        if clip_factor is not None:
-            self._global_clip_refuse("a step with adaptive gradient clipping (enable_agc)")
-            self._grad_accum_refuse("adaptive gradient clipping (enable_agc) would clip each micro-batch's gradient, not the "
-                                    "window's")
-            self._finetune_refuse("a step with adaptive gradient clipping (enable_agc)")
+        compat.check(self, ("agc",), agc=clip_factor is not None)
         self.agc = None if clip_factor is None else (float(clip_factor), float(eps))
         self._graphs = {}
 
@@ -2910,9 +2715,6 @@ class ModelBase:
 
     # ------------------------------------------------------------------ input corruption (scan_dropout=, word_dropout=)
     SUPPORTS_INPUT_CORRUPTION = False   # True on nic.NIC and lc_nic.NIC, whose train_step stages with corrupt=True
-    CORRUPT_DP_REFUSAL = ("scan_dropout / word_dropout are built for the single-device step only: the ranks of a data-parallel "
-                          "step (dp.attach / grad_sync) would draw the same coins for their slices.  Train them on one device")
-
     def _input_width(self):
         """the voxel columns of a staged scan row (lc_nic.NIC: n_in)"""
         return self.N
@@ -2932,7 +2734,7 @@ class ModelBase:
         if sd is not None and sd.null is not None and sd.null.shape[0] != self._input_width():
             raise ValueError(f"the null scan of scan_dropout must have the model's input width {self._input_width()}, "
                              f"got {sd.null.shape[0]}")
-        self._corrupt_check(sd, self._word_dropout)
+        compat.check(self, ("corruption",), _scan_dropout=sd)
         self._scan_dropout = sd
         self._null_dev = None if sd is None or sd.null is None else torch.from_numpy(sd.null.copy()).to(self.device)
 
@@ -2949,7 +2751,7 @@ class ModelBase:
             raise NotImplementedError(f"{type(self).__name__} has no word_dropout: it is built for nic.NIC and lc_nic.NIC")
         if wd is not None and wd.unk_id >= self.V:
             raise ValueError(f"word dropout unk_id {wd.unk_id} is not below vocab_size {self.V}")
-        self._corrupt_check(self._scan_dropout, wd)
+        compat.check(self, ("corruption",), _word_dropout=wd)
         self._word_dropout = wd
 
     @property
@@ -2959,32 +2761,19 @@ class ModelBase:
         sd = self._scan_dropout
         return None if sd is None or sd.null is None else sd.null
 
-    def _corruption(self, sd=False, wd=False):
+    def _corruption(self, pending=None):
         """(ScanDropout or None, WordDropout or None) with a neutral one as None, or None when neither is active: then the
-        step issues the launches it issues without the keywords"""
-        sd = self._scan_dropout if sd is False else sd
-        wd = self._word_dropout if wd is False else wd
+        step issues the launches it issues without the keywords.  ``pending``: as _token_weights_on takes it"""
+        sd, wd = self._scan_dropout, self._word_dropout
+        if pending:
+            sd, wd = pending.get("_scan_dropout", sd), pending.get("_word_dropout", wd)
         sd = None if sd is None or sd.neutral else sd
         wd = None if wd is None or wd.neutral else wd
         return (sd, wd) if (sd is not None or wd is not None) else None
 
-    def _corrupt_check(self, sd=False, wd=False):
-        """the combinations the input corruption is built for (the constructor, an assignment, train_step -- grad_sync may
-        have been attached since); anything else refuses instead of training another mode.  Neutral settings pass"""
-        if self._corruption(sd, wd) is None:
-            return
-        what = "scan_dropout / word_dropout"
-        if self.scheduled_sampling is not None:
-            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for scheduled_sampling")
-        if self.self_critical is not None:
-            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for self_critical")
-        if not self.teacher_forcing:
-            raise NotImplementedError(f"{what} are built for the teacher-forced step: not for teacher_forcing=False "
-                                      "(the free-running decoder)")
-        if int(self.S) != 1:
-            raise NotImplementedError(f"{what} are single-subject options: n_subjects > 1 is not supported")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise NotImplementedError(self.CORRUPT_DP_REFUSAL)
+    def _corrupt_check(self):
+        """what a model with active input corruption refuses, as it stands (compat.check on ``corruption``)"""
+        compat.check(self, ("corruption",))
 
     def _input_corrupt(self, cor, B, T, n_cols):
         """tnt_input_corrupt_f32 on the staged x (and its voxel-major copy) and cap, at this step's drop_step: one launch
@@ -3470,15 +3259,10 @@ class ModelBase:
         plan = self.plan_step and (self.E if E is None else E) % 4 == 0 and self.sparse_emb_bwd
         return self._run_planned if plan else self._run_captured
 
-    def _ss_refuse(self, T=None):
-        """what a scheduled-sampling train_step refuses: in front of the staging a data-parallel schedule, behind it
-        (``T``: the staged caption length) a caption with more token positions than the Philox sites hold"""
-        if self.scheduled_sampling is None:
-            return
-        if T is None:
-            if self.grad_sync is not None:
-                raise NotImplementedError("scheduled sampling has no data-parallel schedule: train it on one device")
-        elif T - 1 > SS_MAX_POSITIONS:
+    def _ss_refuse(self, T):
+        """behind the staging of a scheduled-sampling train_step (``T``: the staged caption length): a caption with more
+        token positions than the Philox sites hold"""
+        if self.scheduled_sampling is not None and T - 1 > SS_MAX_POSITIONS:
             raise ValueError(f"scheduled sampling decides at most {SS_MAX_POSITIONS} token positions per caption "
                              f"(Philox sites S_SS_COIN/S_SS_DRAW + j): caption length {T} is too long")
 

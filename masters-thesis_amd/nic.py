@@ -17,6 +17,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from . import compat
 from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, SemanticTarget, check_sampling, check_beam,
@@ -42,6 +43,7 @@ class NIC(ModelBase):
     SUPPORTS_INPUT_CORRUPTION = True    # scan_dropout= / word_dropout= (ModelBase._stage_batch(corrupt=True))
     SUPPORTS_GRAD_ACCUMULATION = True   # gradient_accumulation_steps= (ModelBase._train_step_accum)
     SUPPORTS_DISTILLATION = True        # CategoricalCrossentropy(distillation=) / set_teacher (ModelBase._teach)
+    STEP_FEATURES = ("scheduled_sampling", "self_critical", "corruption", "semantic")   # what train_step checks (compat)
 
     def __init__(self, input_size, units, embedding_dim, vocab_size, max_length, dropout_input, dropout,
                  dropout_lstm, input_reg, lstm_reg, output_reg, norm="batch", scheduled_sampling=None, self_critical=None,
@@ -71,8 +73,6 @@ class NIC(ModelBase):
         if self_critical is not None:
             if not isinstance(self_critical, SelfCritical):
                 raise ValueError(f"self_critical must be None or a model_base.SelfCritical, got {self_critical!r}")
-            if scheduled_sampling is not None:
-                raise ValueError("a model takes scheduled_sampling or self_critical, not both")
             if E % 4 or E > 1016:
                 raise ValueError(f"self-critical training needs embedding_dim % 4 == 0 and <= 1016 "
                                  f"(tnt_scheduled_feedback_f32), got {E}")
@@ -89,7 +89,7 @@ class NIC(ModelBase):
         if semantic is not None and not isinstance(semantic, SemanticTarget):
             raise ValueError(f"semantic must be None or a model_base.SemanticTarget, got {semantic!r}")
         self.semantic = semantic
-        self._semantic_check()
+        compat.check(self, ("scheduled_sampling", "self_critical", "semantic"))
         self.ldx, self.ldV = _r4(N), _r4(V)
         self.layers_spec = OrderedDict([
             ("dense_img", ["kernel", "bias"]),
@@ -282,9 +282,9 @@ class NIC(ModelBase):
         ok = (self.compact_head and self._seq_lstm and self.seq_xch is not None
               and hasattr(be, "stage_batch_map") and hasattr(be, "softmax_cce_live") and hasattr(be, "gemm3")
               and self.use_gemm3 and self.g3_riders
-              and self.grad_sync is None and self.dp_world == 1
-              and self.scheduled_sampling is None and self.self_critical is None and not self.agc
-              and not self.label_smoothing and not self.unlikelihood and not self._token_weights_on() and self.U % 4 == 0)
+              and not compat.any_on(self, ("dp", "scheduled_sampling", "self_critical", "agc", "label_smoothing",
+                                           "unlikelihood", "token_weights"))
+              and self.U % 4 == 0)
         if not ok:
             return None
         return (self.head_pos, self.head_w, self.head_tgt, self.head_live, self.loss_row, self.corr_row)
@@ -317,23 +317,6 @@ class NIC(ModelBase):
                 and not self._sync_bn_on())        # synchronised BatchNorm: the statistics leave the kernel for a collective
 
     # ------------------------------------------------------------------ sentence-embedding target (model_base.SemanticTarget)
-    SEMANTIC_DP_REFUSAL = ("semantic (the sentence-embedding target) has no data-parallel schedule: its mean runs over one "
-                           "rank's rows and the gradient launches of guse_out sit in none of the all-reduce buckets; train it on "
-                           "one device")
-
-    def _semantic_check(self):
-        """what a model with semantic= refuses, in the constructor and again in front of every step (grad_sync may have been
-        attached since); compile, set_teacher, enable_agc, freeze / set_lr_multipliers and dp.attach refuse on their side"""
-        if self.semantic is None:
-            return
-        if self.scheduled_sampling is not None:
-            raise NotImplementedError("semantic (the sentence-embedding target) has not been checked under scheduled_sampling")
-        if self.self_critical is not None:
-            raise NotImplementedError("semantic (the sentence-embedding target) is not built for the self_critical step, whose "
-                                      "rows are copies of the scans")
-        if self.grad_sync is not None or self.dp_world > 1:
-            raise NotImplementedError(self.SEMANTIC_DP_REFUSAL)
-
     def _semantic_target(self, inputs):
         """the batch's fifth input as a (B, G) float32 tensor on the device, checked in front of every launch; None without
         semantic= (a fifth input is then ignored)"""
@@ -814,9 +797,7 @@ class NIC(ModelBase):
         self-critical step (train_step_scst) instead."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
-        self._ss_refuse()
-        self._corrupt_check()                       # (grad_sync may have been attached since the constructor)
-        self._semantic_check()
+        compat.check(self, self.STEP_FEATURES)       # (grad_sync may have been attached since the constructor)
         if self.self_critical is not None:
             return self.train_step_scst(data)
         self._sync_accum()
@@ -1028,8 +1009,7 @@ class NIC(ModelBase):
             raise ValueError("train_step_scst needs a model built with self_critical=model_base.SelfCritical(...)")
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step")
-        if self.grad_sync is not None:
-            raise NotImplementedError("self-critical training has no data-parallel schedule: train it on one device")
+        compat.check(self, ("self_critical",))
         B, T = self._stage_scst(data[0])
         if references is not None and len(references) != B:
             raise ValueError(f"references: {len(references)} reference lists for a batch of {B}")
@@ -1079,7 +1059,7 @@ class NIC(ModelBase):
 
     def test_step(self, data):
         """NIC.test_step (NIC.py:254-299)."""
-        self._semantic_check()
+        compat.check(self, ("semantic",))
         guse = self._semantic_target(data[0])
         B, T = self._stage_batch(data[0], data[1], self.N)
         self._semantic_stage(guse)

@@ -18,6 +18,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from . import compat
 from .arena import ParamArena
 from .model_base import ModelBase, Metrics, _r4, S_FEAT, S_OUT
 from .lstm_layer import lstm_layer_fwd, lstm_layer_bwd
@@ -284,9 +285,7 @@ class CaptionGenerator(ModelBase):
         at the perturbed weights, restore, apply.  Both passes use the same dropout masks."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model before train_step_SAM")
-        self._weight_decay_refuse("train_step_SAM")
-        self._global_clip_refuse("train_step_SAM")
-        self._finetune_refuse("train_step_SAM")
+        compat.check(self, ("grad_accum", "sam"), sam="train_step_SAM")
         img, target = self._unpack_batch(data)
         B, T = self._stage(img, target)
         self._sync_lr()
