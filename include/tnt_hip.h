@@ -1773,6 +1773,45 @@ int32_t tnt_row_inv_norm_f32(const float* X, int64_t ldx, float* inv, int64_t ro
 int32_t tnt_cosine_topk_f32(const float* S, int64_t lds, const float* qinv, const float* binv, int32_t* idx, float* sim,
                             int32_t B, int32_t M, int32_t k, void* stream);
 
+/* ---- contrastive sentence-embedding loss (csrc/contrastive.hip): the CLIP-style form of nic.NIC's semantic target, with in-batch
+ * negatives, a temperature, both directions and optional soft targets.  z [B][ldz] the predictions, g [B][ldg] the targets,
+ * G <= ldz, ldg columns used; 1 <= B <= 1024, 1 <= G <= 2048; eps = 1e-12 as in tnt_cosine_loss_f32.
+ *   iz_i = 1 / sqrt(max(sum z_i^2, eps)),  ig_j likewise,  zn = z iz,  gn = g ig
+ *   valid_j = (sum g_j^2 > eps)                 an all-zero target is the reference's missing embedding
+ *   Bv = number of valid rows
+ *   L_ij = (zn_i . gn_j) inv_temperature         over valid i, j only; formed as (((z_i . g_j) iz_i) ig_j) inv_temperature
+ *   Q_ij = [i == j]                              hard targets (soft_inv_temperature == 0)
+ *   Q_i. = softmax_j(S_ij) over valid j,  S_ij = ((g_i . g_j) (ig_i ig_j)) soft_inv_temperature      soft (S_ij and S_ji: the same bits)
+ *   lr_i = - sum_j Q_ij log softmax_j(L_i.)_j    scan -> caption
+ *   lc_i = - sum_j Q_ij log softmax_j(L_.i)_j    caption -> scan: column i of L, softmax over rows
+ *   loss_row[i] = symmetric ? 0.5 (lr_i + lc_i) : lr_i;  0 for an invalid row
+ *   hit_row[i]  = valid_i and (first argmax over valid j of L_ij) == i
+ *   out[0] (out nullable) = (sum_i loss_row[i]) / max(Bv, 1),  out[1] = (sum_i hit_row[i]) / max(Bv, 1), the rows added in
+ *   ascending order in float32
+ *   dz (nullable) [B][ldz], the gradient of weight * out[0] in z:
+ *     dL_ij = weight / max(Bv, 1) * ((1 - b) (Pr_ij - Q_ij) + b (Pc_ij - Q_ji)),  b = symmetric ? 0.5 : 0,
+ *             Pr the row softmax of L, Pc_ij the softmax over rows of column j
+ *     dzn_i = inv_temperature sum_j dL_ij gn_j     (valid j in ascending order, one accumulator per column)
+ *     dz_i  = iz_i (dzn_i - zn_i (zn_i . dzn_i));  where sum z_i^2 <= eps the normaliser is the constant 1e-6: dz_i = iz_i dzn_i
+ *   There is no gradient to g.  An invalid row gets dz = 0 and takes no part in any softmax, neither as a row nor as a column.
+ *   Bv = 0 and B = 1 give loss 0 and a zero gradient.  Every softmax subtracts its maximum.  dz may be z itself (an element
+ *   of z is read, then that element of dz written, by the same thread, in the last launch that reads z); columns >= G of z, g
+ *   and dz are neither read nor written.  No alignment is asked of any pointer.
+ * work is scratch of TNT_CONTRASTIVE_WORK_FLOATS(B, soft) floats: sum z^2 [B], sum g^2 [B], the row, column and target
+ * log-sum-exp [B] each, L [B][B] and, soft, S [B][B].
+ * Launches, in order on the one stream (a phase that needs another's result is another launch; no workgroup waits for
+ * another): the logits in 16 x 16 tiles with the squared norms beside them; one wave per row for the log-sum-exp, loss and hit;
+ * (dz given) one workgroup per row for the gradient; (out given) one launch for the two means.  float32, no float atomics,
+ * every sum in a fixed order that does not depend on the grid: the same bits every time.
+ * A null z, g, work, loss_row or hit_row: TNT_BADARG(1); ldz < G (2), ldg < G (4), B outside [1, 1024] (10), G outside
+ * [1, 2048] (11), inv_temperature not a finite number > 0 (12), soft_inv_temperature not a finite number >= 0 (13), symmetric
+ * not 0 or 1 (14), weight not a finite number >= 0 (15); nothing launched. */
+#define TNT_CONTRASTIVE_WORK_FLOATS(B, soft) (5 * (B) + ((soft) ? 2 : 1) * (B) * (B))
+int32_t tnt_contrastive_loss_f32(const float* z, int32_t ldz, const float* g, int32_t ldg, float* dz /* nullable, may be z */,
+                                 float* work, float* loss_row, int32_t* hit_row, float* out /* nullable: [0] loss, [1] top1 */,
+                                 int32_t B, int32_t G, float inv_temperature, float soft_inv_temperature /* 0: hard */,
+                                 int32_t symmetric, float weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,7 +72,7 @@ def build_model(config, groups, mode="attention", input_size=None, **kw):
     mode="dense" builds nic.NIC (Model/NIC.py: the dense encoder in front of the LSTM, embedding_text wide); it needs
     ``input_size`` too, and ``groups`` is not used."""
     vocab_size = config["top_k"] + 1
-    # semantic: {dim: , weight: , reg: }: an optional key of this library's (model_base.SemanticTarget), the sentence-embedding
+    # semantic: {dim: , weight: , reg: , loss: , temperature: , symmetric: , soft_temperature: }: an optional key of this library's (model_base.SemanticTarget), the sentence-embedding
     # target of nic.NIC; the other models do not take it
     sem = SemanticTarget.from_config(config.get("semantic")) if "semantic" not in kw else None
     if sem is not None:

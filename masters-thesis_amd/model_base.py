@@ -144,9 +144,33 @@ class SemanticTarget:
       z_b = x_b W + bias,   zn = z / sqrt(max(sum z^2, 1e-12)),   gn likewise,   semantic = mean_b (1 - sum zn gn)
     train_step differentiates CE + L2 + ``weight`` * semantic and reports the unweighted value as the metric ``semantic``;
     ``loss`` stays the cross-entropy.  A target row of all zeros (the reference's missing embedding) gives loss 1 and no
-    gradient, and counts in the mean.  data[0] is then (betas, cap, a0, c0, guse) with guse (B, dim) float32."""
+    gradient, and counts in the mean.  data[0] is then (betas, cap, a0, c0, guse) with guse (B, dim) float32.
 
-    def __init__(self, dim=512, weight=1.0, reg=0.0):
+    ``loss="contrastive"`` trains the same layer with the CLIP-style loss of the fMRI-decoding literature instead: in-batch
+    negatives, a ``temperature``, both directions (``symmetric``) and, with ``soft_temperature``, soft targets, so that two
+    captions of similar images are not hard negatives.  The definition is tnt_contrastive_loss_f32's (include/tnt_hip.h),
+    with eps = 1e-12:
+      iz_i = 1/sqrt(max(sum z_i^2, eps)),  ig_j likewise,  zn = z*iz, gn = g*ig
+      valid_j = (sum g_j^2 > eps)                        an all-zero target is the reference's missing embedding
+      Bv = number of valid rows
+      L_ij = (zn_i . gn_j) / temperature                 over valid i, j only
+      Q_ij = [i == j]                                    (hard: soft_temperature=None)
+      Q_i. = softmax_j( (gn_i . gn_j) / soft_temperature ) over valid j   (soft)
+      lr_i = - sum_j Q_ij log softmax_j(L_i.)_j          scan -> caption
+      lc_i = - sum_j Q_ij log softmax_j(L_.i)_j          caption -> scan: column i of L, softmax over rows
+      row_i = symmetric ? 0.5 (lr_i + lc_i) : lr_i       0 for an invalid row
+      semantic = sum_i row_i / max(Bv, 1)
+      semantic_top1 = sum_i [valid_i and (first argmax over valid j of L_ij) == i] / max(Bv, 1)
+    train_step differentiates CE + L2 + ``weight`` * semantic and reports the unweighted ``semantic`` and ``semantic_top1``;
+    test_step reports them too.  An invalid row has no gradient and takes no part in any softmax; Bv = 0 and a batch of one
+    give 0.  ``semantic_top1`` rides in slot 5 of ``met`` (TOP1_SLOT): ModelBase.DISTILL_KL's, which cannot be live here
+    because distillation is refused beside ``semantic`` (compat).  Under ``loss="cosine"``, the default, ``temperature``,
+    ``symmetric`` and ``soft_temperature`` are ignored and normalised to their defaults: the object equals and hashes as the
+    three-argument one."""
+
+    LOSSES = ("cosine", "contrastive")
+
+    def __init__(self, dim=512, weight=1.0, reg=0.0, loss="cosine", temperature=0.07, symmetric=True, soft_temperature=None):
         num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
         if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or not 1 <= dim <= 2048:
             raise ValueError(f"the semantic target's dim must be an integer in [1, 2048] (tnt_cosine_loss_f32), got {dim!r}")
@@ -154,28 +178,57 @@ class SemanticTarget:
             raise ValueError(f"the semantic target's weight must be a finite number >= 0, got {weight!r}")
         if not num(reg) or reg < 0:
             raise ValueError(f"the semantic target's L2 coefficient (reg) must be a finite number >= 0, got {reg!r}")
-        self.dim, self.weight, self.reg = int(dim), float(weight), float(reg)
+        if not isinstance(loss, str) or loss not in self.LOSSES:
+            raise ValueError(f"the semantic target's loss must be \"cosine\" or \"contrastive\", got {loss!r}")
+        if not num(temperature) or temperature <= 0:
+            raise ValueError(f"the semantic target's temperature must be a finite number > 0, got {temperature!r}")
+        if not isinstance(symmetric, (bool, np.bool_)):
+            raise ValueError(f"the semantic target's symmetric must be a bool, got {symmetric!r}")
+        if soft_temperature is not None and (not num(soft_temperature) or soft_temperature <= 0):
+            raise ValueError(f"the semantic target's soft_temperature must be None or a finite number > 0, got "
+                             f"{soft_temperature!r}")
+        self.dim, self.weight, self.reg, self.loss = int(dim), float(weight), float(reg), loss
+        if loss == "cosine":                # the contrastive fields do not exist for the cosine loss
+            temperature, symmetric, soft_temperature = 0.07, True, None
+        self.temperature, self.symmetric = float(temperature), bool(symmetric)
+        self.soft_temperature = None if soft_temperature is None else float(soft_temperature)
 
     LAYER = "guse_out"
     SLOT = 6                # slot of ``met`` that carries the unweighted mean (free in nic.NIC)
+    TOP1_SLOT = 5           # ... and semantic_top1 (loss="contrastive"): DISTILL_KL's, refused beside semantic
+    KEYS = ("dim", "weight", "reg", "loss", "temperature", "symmetric", "soft_temperature")
+
+    @property
+    def contrastive(self):
+        return self.loss == "contrastive"
 
     @classmethod
     def from_config(cls, value):
-        """the config key ``semantic``: null (off) or {dim: , weight: , reg: }, each optional"""
+        """the config key ``semantic``: null (off) or {dim: , weight: , reg: , loss: , temperature: , symmetric: ,
+        soft_temperature: }, each optional"""
         if value is None:
             return None
-        if not isinstance(value, dict) or not set(value) <= {"dim", "weight", "reg"}:
-            raise ValueError(f"semantic must be a mapping with dim, weight and reg, got {value!r}")
-        return cls(value.get("dim", 512), value.get("weight", 1.0), value.get("reg", 0.0))
+        if not isinstance(value, dict) or not set(value) <= set(cls.KEYS):
+            raise ValueError(f"semantic must be a mapping with dim, weight, reg, loss, temperature, symmetric and "
+                             f"soft_temperature, got {value!r}")
+        return cls(**value)
+
+    def _key(self):
+        base = (self.dim, self.weight, self.reg)
+        return base if self.loss == "cosine" else base + (self.loss, self.temperature, self.symmetric, self.soft_temperature)
 
     def __eq__(self, other):
-        return isinstance(other, SemanticTarget) and (self.dim, self.weight, self.reg) == (other.dim, other.weight, other.reg)
+        return isinstance(other, SemanticTarget) and self._key() == other._key()
 
     def __hash__(self):
-        return hash(("semantic", self.dim, self.weight, self.reg))
+        return hash(("semantic",) + self._key())
 
     def __repr__(self):
-        return f"SemanticTarget(dim={self.dim!r}, weight={self.weight!r}, reg={self.reg!r})"
+        base = f"SemanticTarget(dim={self.dim!r}, weight={self.weight!r}, reg={self.reg!r}"
+        if self.loss == "cosine":
+            return base + ")"
+        return base + (f", loss={self.loss!r}, temperature={self.temperature!r}, symmetric={self.symmetric!r}, "
+                       f"soft_temperature={self.soft_temperature!r})")
 
 
 class ScheduledSampling:

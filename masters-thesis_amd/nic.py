@@ -24,7 +24,7 @@ from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EP
                          _TokenChoice, _BeamDecode, EncGram, EncUpdate, StepRoute)
 from .evaluate import REWARD_KINDS, REWARD_MAX_LEN, REWARD_MAX_REFS, pack_references
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
-from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K
+from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K, contrastive_work_floats
 
 ENC_SPLITS = 16      # K splits of the streaming encoder forward: 16 column groups x 16 splits = one workgroup per CU
 
@@ -246,6 +246,11 @@ class NIC(ModelBase):
         if self.semantic is not None:       # the staged target, the prediction (its gradient in place), the rows' loss and cos
             self.sem_g, self.sem_z = f(B, self.ldG), f(B, self.ldG)
             self.sem_loss, self.sem_cos = f(B), f(B)
+            if self.semantic.contrastive:   # the entry's scratch, the rows' hits and its two means (loss, top1)
+                soft = self.semantic.soft_temperature is not None
+                self.sem_work = f(contrastive_work_floats(B, soft))
+                self.sem_hit = torch.zeros(B, dtype=torch.int32, device=self.device)
+                self.sem_out = f(2)
         self.emb_seg = self.arena.entries["emb_text/embeddings"].seg
         self._shape = (B, T)
         self._graphs = {}
@@ -329,13 +334,26 @@ class NIC(ModelBase):
             raise ValueError(f"guse shape {tuple(np.shape(inputs[4]))} != {(B, G)} (batch, SemanticTarget.dim)")
         return self._to_dev(inputs[4], torch.float32)
 
+    def _semantic_key(self):
+        """what a plan / graph key carries for the term: the cosine loss keeps ("semantic",)"""
+        return ("semantic", "contrastive") if self.semantic.contrastive else ("semantic",)
+
+    def _semantic_slots(self):
+        """the term's metrics and their slots of ``met``"""
+        if self.semantic is None:
+            return {}
+        if self.semantic.contrastive:
+            return dict(semantic=SemanticTarget.SLOT, semantic_top1=SemanticTarget.TOP1_SLOT)
+        return dict(semantic=SemanticTarget.SLOT)
+
     def _semantic_stage(self, guse):
         """the target into its static buffer (a copy in front of the step: a replayed plan or graph reads each batch's own)"""
         if guse is not None:
             self.sem_g[:, :self.G].copy_(guse)
 
     def _semantic_fwd(self, B, want_grad):
-        """z = x W + bias on the model's product route, then tnt_cosine_loss_f32: the rows' loss and cos, the unweighted mean
+        """z = x W + bias on the model's product route, then tnt_cosine_loss_f32 (tnt_contrastive_loss_f32 under
+        loss="contrastive", with semantic_top1 into met[5]): the rows' loss and cos, the unweighted mean
         into met[6] and (``want_grad``) the gradient of weight * mean in place of z.  x = xin[:B], the feature rows the first
         LSTM step was fed.  Issued behind the encoder tail, whose launch writes those rows."""
         if self.semantic is None:
@@ -343,9 +361,19 @@ class NIC(ModelBase):
         a, E, G, ldG = self.arena, self.E, self.G, self.ldG
         x = self._route.xin_used
         self.gemm_sk(x, a.p("guse_out/kernel"), self.sem_z, B, G, E, E, ldG, ldG, bias=a.p("guse_out/bias"))
-        k = SemanticTarget.SLOT
+        k, sem = SemanticTarget.SLOT, self.semantic
+        if sem.contrastive:
+            # tnt_contrastive_loss_f32 in the cosine launch's place: its means (loss, top1) are adjacent, the slots of ``met``
+            # are not (6 and 5), so one two-word launch files them
+            soft = 0.0 if sem.soft_temperature is None else 1.0 / sem.soft_temperature
+            self.be.contrastive_loss(self.sem_z, ldG, self.sem_g, ldG, self.sem_z if want_grad else None, self.sem_work,
+                                     self.sem_loss, self.sem_hit, self.sem_out, B, G, 1.0 / sem.temperature, soft, sem.symmetric,
+                                     sem.weight)
+            k1 = SemanticTarget.TOP1_SLOT
+            self.be.sum2(self.sem_out[0:1], self.met[k:k + 1], self.sem_out[1:2], self.met[k1:k1 + 1], 1, 1.0)
+            return
         self.be.cosine_loss(self.sem_z, ldG, self.sem_g, ldG, self.sem_z if want_grad else None, self.sem_loss, self.sem_cos,
-                            self.met[k:k + 1], B, G, self.semantic.weight / B)
+                            self.met[k:k + 1], B, G, sem.weight / B)
 
     def _semantic_bwd_w(self, B):
         """the layer's gradients: dW = x^T dz with the bias gradient as the column-sum rider where the route offers it"""
@@ -824,8 +852,8 @@ class NIC(ModelBase):
             compact = self._route.head_map_fresh        # the staging launch built the head's row map
             staged = self._route.stage_fwd_done         # ... and ran the encoder forward: the step leaves it out
             key = ("train", B, T, "compact") if compact else ("train", B, T, "distill") if distill else ("train", B, T)
-            if self.semantic is not None:       # the step with the term is another launch sequence
-                key += ("semantic",)
+            if self.semantic is not None:       # the step with the term is another launch sequence, and so is each loss
+                key += self._semantic_key()
             seen = self._plan_staged
             if self._graphs.get(key) is not None and seen.get(key) != staged:
                 del self._graphs[key]       # recorded with / without the forward (the entry refuses by alignment): start over
@@ -842,8 +870,7 @@ class NIC(ModelBase):
         self.optimizer.iterations += 1
         m = self._met_snapshot(ring)
         kl = dict(distill_kl=self.DISTILL_KL) if distill else {}
-        if self.semantic is not None:
-            kl["semantic"] = SemanticTarget.SLOT
+        kl.update(self._semantic_slots())
         return self._lr_metric(self._metrics_from(m, loss=0, L2=2, accuracy=1, **kl))
 
     # ------------------------------------------------------------------ self-critical sequence training
@@ -1070,9 +1097,9 @@ class NIC(ModelBase):
             self._loss_metrics(B, T, False)
             self._semantic_fwd(B, False)
             self._norms_and_l2(self.met[2:3])
-        self._run_captured(("test", B, T) + (("semantic",) if sem else ()), run)
+        self._run_captured(("test", B, T) + (self._semantic_key() if sem else ()), run)
         m = self._met_snapshot()
-        return self._metrics_from(m, loss=0, L2=2, accuracy=1, **(dict(semantic=SemanticTarget.SLOT) if sem else {}))
+        return self._metrics_from(m, loss=0, L2=2, accuracy=1, **self._semantic_slots())
 
     def __call__(self, data, training=False):
         """NIC.call (NIC.py:100-145): returns probabilities (B, T, V)."""

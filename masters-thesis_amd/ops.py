@@ -1051,6 +1051,21 @@ class HipBackend:
         self._call(self.lib.tnt_cosine_topk_f32, "tnt_cosine_topk_f32", _p(S), int(lds), _p(qinv), _p(binv), _p(idx), _p(sim),
                    int(B), int(M), int(k), self._s())
 
+    def contrastive_loss(self, z, ldz, g, ldg, dz, work, loss_row, hit_row, out, B, G, inv_temperature, soft_inv_temperature,
+                         symmetric, weight):
+        """the contrastive loss of B prediction / target rows (tnt_contrastive_loss_f32; definition in include/tnt_hip.h): dz
+        (nullable, may be z) the gradient of weight * mean loss, out (nullable) [0] the mean loss and [1] the top-1 share over
+        the valid rows, hit_row int32, work contrastive_work_floats(B, soft) floats; soft_inv_temperature 0: hard targets"""
+        self._call(self.lib.tnt_contrastive_loss_f32, "tnt_contrastive_loss_f32", _p(z), int(ldz), _p(g), int(ldg), _p(dz),
+                   _p(work), _p(loss_row), _p(hit_row), _p(out), int(B), int(G), float(inv_temperature),
+                   float(soft_inv_temperature), int(bool(symmetric)), float(weight), self._s())
+
+
+def contrastive_work_floats(B, soft):
+    """floats of ``work`` of tnt_contrastive_loss_f32 (TNT_CONTRASTIVE_WORK_FLOATS of include/tnt_hip.h): the squared norms and
+    the three log-sum-exp vectors, the B x B logits and, with soft targets, the B x B target Gram"""
+    return 5 * B + (2 if soft else 1) * B * B
+
 
 def attention_coverage_work_floats(T, B, R, axis):
     """floats of ``work`` of tnt_attention_coverage_f32 (the formula of include/tnt_hip.h): one partial per 256 regions of a
