@@ -961,6 +961,45 @@ int32_t tnt_caption_reward_f32(const int32_t* fed, int32_t T, const int32_t* las
                                const double* idf, int32_t n_keys, const double* params, int32_t B, int32_t K,
                                int32_t end_id, int32_t kind, int32_t baseline, float* adv, double* score,
                                int32_t* counted, void* stream);
+/* ROUGE-L of captions on the device (Lin 2004; the self-critical reward "rouge-l", evaluate.device_scores(kind="rouge-l")
+ * and the validation metric of fit(validation_captions=...); restated by tests/rouge_oracle.py): the longest common
+ * subsequence of the K sampled captions of each of B scans (and of its greedy caption) with the scan's references, the
+ * F-score of pycocoevalcap's Rouge.calc_score, and the advantages tnt_scst_cce_f32 reads.  Library-defined:
+ *  - Candidates, references, captions and counted: word for word as tnt_caption_reward_f32 defines them.  R = B*K samples,
+ *    row b*K + k = sample k of scan b: its T tokens are fed[r*T + 1 .. r*T + T-1] and then last[r] (fed[r*T] is never
+ *    read).  baseline 0 ("greedy") adds candidate K of scan b, greedy[t*ldg + b], t < T, ldg >= B; greedy is not read with
+ *    baseline 1.  refs [B][M][Lr] int32, zero padded: reference j < n_refs[b] of scan b at position t is
+ *    refs[(b*M + j)*Lr + t]; n_refs[b] is clamped to [0, M]; the rows j >= n_refs[b] are never read.  A candidate's or a
+ *    reference's caption is its tokens before the first end_id or 0; end_id < 0: only 0 terminates.  Its length is len.
+ *    counted[r] = min(len_r + 1, T).
+ *  - Tokens are only compared, full int32 words: any int32 value is safe.
+ *  - lcs(c, j): the length of the longest common subsequence of the captions of candidate c and reference j, an exact
+ *    integer in [0, min(len_c, len_j)].  lcs (nullable) [B][K+1][M] int32: lcs[(b*(K+1) + c)*M + j]; the rows
+ *    j >= n_refs[b] get 0, and with baseline 1 the row c = K gets 0.
+ *  - score(c), float64, every operation below rounded on its own (no fused multiply-add), in this order:
+ *      P = R = 0; for j = 0 .. n_refs-1 with len_j > 0, ascending:  P = max(P, lcs(c, j) / len_c), R = max(R, lcs(c, j) / len_j)
+ *      (the two maxima are taken separately: they may come from different references);
+ *      b2 = beta * beta;  num = ((1 + b2) * P) * R;  den = R + b2 * P;  score = num / den.
+ *    The score is 0 for an empty candidate (len_c = 0), with no reference that holds a word, or when P == 0 (then R == 0
+ *    too).  It lies in [0, 1]; beta = 1.2 is pycocoevalcap's.  beta is a HOST pointer to one float64, read during the call
+ *    (a float64 travels by address in this ABI, as tnt_weight_average_f32's momentum does), so that the entry can check it.
+ *  - adv [R] float32, score (nullable) [B][K+1] float64: as tnt_caption_reward_f32 forms them from the scores:
+ *    adv[b*K + k] = float32(score(k) - base), base = score(greedy) with baseline 0; with baseline 1 ("mean") ((sum of the
+ *    scan's K sample scores in ascending k) - score(k)) / (K - 1), K >= 2.  score holds the K sample scores, then the
+ *    greedy caption's (0 with baseline 1).
+ *  - One workgroup per scan, its rows staged once in LDS, one wave per (candidate, reference) pair: lane i holds the
+ *    candidate's token i, the match vector of a reference word is one 64-lane ballot, and the LCS follows from the
+ *    bit-vector recurrence V <- (V + (V & M)) | (V - (V & M)) over the reference's words (Allison & Dix 1986, Hyyro 2004)
+ *    as the number of zero bits of V below len_c.  Integer work only up to the score; no atomics, no scratch memory, fixed
+ *    order: deterministic.
+ * TNT_BADARG for B <= 0, T or Lr outside [1, 64], K outside [1, 16] (or K < 2 with baseline 1), M outside [1, 8], baseline
+ * other than 0 or 1, null beta, *beta (or its square) not finite or *beta <= 0, null fed / last / refs / n_refs / adv / counted, null
+ * greedy or ldg < B with baseline 0, any output (adv, score, counted, lcs) overlapping an input or another output anywhere
+ * in their extents; nothing is launched then. */
+int32_t tnt_caption_rouge_f32(const int32_t* fed, int32_t T, const int32_t* last, const int32_t* greedy, int32_t ldg,
+                              const int32_t* refs, const int32_t* n_refs, int32_t M, int32_t Lr, int32_t B, int32_t K,
+                              int32_t end_id, const double* beta, int32_t baseline, float* adv, double* score,
+                              int32_t* counted, int32_t* lcs, void* stream);
 /* row argmax (first max wins; NaN entries are ignored, a row with no value above -inf gives 0), out int32[rows].
  * rows == 0 is a no-op; TNT_BADARG for rows < 0, V <= 0, ld < V, null pointers. */
 int32_t tnt_argmax_rows_f32(const float* x, int32_t* out, int32_t rows, int32_t V, int32_t ld,

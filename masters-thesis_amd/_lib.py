@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 136
+TNT_VERSION = 137
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -87,6 +87,7 @@ SIGNATURES = {
     "tnt_guidance_mix_f32": [P, I32, I32, I32, F32, F32, P, I32, P, P],
     "tnt_mbr_select_f32": [P, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P, I32, P, P, P],
     "tnt_caption_reward_f32": [P, I32, P, P, I32, P, P, I32, I32, P, P, I32, P, I32, I32, I32, I32, I32, P, P, P, P],
+    "tnt_caption_rouge_f32": [P, I32, P, P, I32, P, P, I32, I32, I32, I32, I32, P, I32, P, P, P, P, P],
     "tnt_argmax_rows_f32": [P, P, I32, I32, I32, P],
     "tnt_greedy_feedback_f32": [P, I32, I32, P, I32, P, I32, I32, P, I32, I32, P, I32, P, I32, I32, F32, U64, U32, U32, P,
                                 I32, I32, P],

@@ -178,17 +178,24 @@ class AverageModelCheckpoint(ModelCheckpoint):
 
 
 class EarlyStopping(Callback):
-    def __init__(self, monitor="val_loss", min_delta=0.0, patience=0):
+    """tf.keras.callbacks.EarlyStopping(monitor, min_delta, patience, mode): training stops once ``monitor`` has not
+    improved by more than ``min_delta`` for more than ``patience`` epochs.  mode "min" (the default: a loss) or "max" (a
+    caption metric such as ``val_rouge_l`` of fit(validation_captions=...)); ``best`` holds sign * value, as
+    ModelCheckpoint's does."""
+
+    def __init__(self, monitor="val_loss", min_delta=0.0, patience=0, mode="min"):
         super().__init__()
-        self.monitor, self.min_delta, self.patience = monitor, min_delta, patience
+        if mode not in ("min", "max"):
+            raise ValueError(f"mode must be 'min' or 'max', got {mode!r}")
+        self.monitor, self.min_delta, self.patience, self.sign = monitor, min_delta, patience, (1 if mode == "min" else -1)
         self.best, self.wait = float("inf"), 0
 
     def on_epoch_end(self, epoch, logs=None):
         cur = (logs or {}).get(self.monitor)
         if cur is None:
             return
-        if cur < self.best - self.min_delta:
-            self.best, self.wait = cur, 0
+        if self.sign * cur < self.best - self.min_delta:
+            self.best, self.wait = self.sign * cur, 0
         else:
             self.wait += 1
             if self.wait > self.patience:

@@ -17,6 +17,12 @@
   the worked example of the nltk documentation (tests/test_data_fit.py).
 * ``RewardTable`` / ``device_scores``   -- CiderD's document frequencies as the sorted key / idf table that
   tnt_caption_reward_f32 reads (``SelfCritical(score_on="device")``), and that kernel's scores of lists of token ids.
+* ``lcs_length`` / ``rouge_l``          -- ROUGE-L (Lin 2004) with the choices of the COCO caption suite's scorer
+  (AttemptFour/metric_suit.py runs pycocoevalcap's Rouge): the F-score at beta = 1.2 of the best LCS precision and the
+  best LCS recall over the references, each maximised on its own.  tnt_caption_rouge_f32 is the same definition on the
+  device (``device_scores(kind="rouge-l")``, ``SelfCritical(reward="rouge-l")``).
+* ``CaptionValidation``                 -- caption metrics of the decoded validation set in ``fit``'s epoch logs
+  (``fit(validation_captions=...)``): val_bleu4, val_rouge_l, val_cider_d, scored on the device.
 * ``SemanticBank`` / ``semantic_retrieve`` / ``semantic_identification`` -- nearest-neighbour retrieval and identification in
   sentence-embedding space for nic.NIC(semantic=...): Model/guse.py's "KNN is used to find a known GUSE vector", which the
   reference never finishes; the similarities and the selection run on the device (tnt_cosine_topk_f32).
@@ -361,8 +367,50 @@ class CiderD:
         return float(self.batch_scores([[candidate]], [references])[0][0])
 
 
+def lcs_length(a, b):
+    """the length of the longest common subsequence of two token sequences (words or ids), the O(len(a) * len(b)) table
+    kept one row at a time"""
+    a, b = list(a), list(b)
+    row = [0] * (len(b) + 1)
+    for x in a:
+        diag = 0
+        for j, y in enumerate(b):
+            diag, row[j + 1] = row[j + 1], (diag + 1 if x == y else max(row[j + 1], row[j]))
+    return row[len(b)]
+
+
+ROUGE_BETA = 1.2        # pycocoevalcap's Rouge().beta
+
+
+def rouge_l(references, hypothesis, beta=ROUGE_BETA):
+    """ROUGE-L of one tokenised hypothesis against tokenised references, pycocoevalcap's Rouge.calc_score: over the
+    references that hold a word, P = max lcs / len(hypothesis) and R = max lcs / len(reference), each maximum on its own (they
+    may come from different references), and ((1 + beta^2) P R) / (R + beta^2 P); 0.0 for an empty hypothesis, no such
+    reference or no common word.  The operation order is tnt_caption_rouge_f32's (include/tnt_hip.h).  PARITY UNPINNED
+    against pycocoevalcap itself, which is not available here; pinned by hand-computed cases (tests/test_host_rouge.py)."""
+    beta = float(beta)
+    if not (beta > 0.0 and math.isfinite(beta * beta)):
+        raise ValueError(f"beta must be a finite float > 0, got {beta!r}")
+    hyp = list(hypothesis)
+    if not hyp:
+        return 0.0
+    P = R = 0.0
+    for ref in references:
+        ref = list(ref)
+        if not ref:
+            continue
+        n = lcs_length(hyp, ref)
+        P, R = max(P, n / len(hyp)), max(R, n / len(ref))
+    if P == 0.0:
+        return 0.0
+    b2 = beta * beta
+    return (((1.0 + b2) * P) * R) / (R + b2 * P)
+
+
 # ---------------------------------------------------------------------------------------------------- rewards on the device
-REWARD_KINDS = {"cider-d": 0, "bleu4": 1}
+REWARD_KINDS = {"cider-d": 0, "bleu4": 1}                              # tnt_caption_reward_f32's kind
+ROUGE_KIND = "rouge-l"                                                 # tnt_caption_rouge_f32: an entry of its own
+DEVICE_KINDS = tuple(REWARD_KINDS) + (ROUGE_KIND,)
 REWARD_MAX_SAMPLES, REWARD_MAX_REFS, REWARD_MAX_LEN = 16, 8, 64        # tnt_caption_reward_f32's limits: K, M, T and Lr
 
 
@@ -438,16 +486,17 @@ def pack_references(references, refs_out, n_out):
             refs_out[b, j, :len(r)] = r
 
 
-def device_scores(candidates, references, kind="cider-d", table=None, end_id=-1, device="cuda"):
+def device_scores(candidates, references, kind="cider-d", table=None, end_id=-1, device="cuda", beta=ROUGE_BETA):
     """The scores tnt_caption_reward_f32 gives lists of token ids: ``candidates`` one list of at most 16 candidate
     token sequences per document, ``references`` one list of at most 8 reference sequences per document, as
     CiderD.batch_scores takes them; sequences hold at most 64 tokens and are cut at their first ``end_id`` or 0
-    (end_id < 0: only 0).  kind "cider-d" needs ``table`` (a RewardTable); "bleu4" takes none.  One launch with
+    (end_id < 0: only 0).  kind "cider-d" needs ``table`` (a RewardTable); "bleu4" takes none.  kind "rouge-l": the
+    scores of tnt_caption_rouge_f32 at ``beta`` on the same buffers (``rouge_l``'s definition).  One launch with
     K = the largest candidate count; returns one float64 array of scores per document."""
     import torch
     from . import ops
-    if kind not in REWARD_KINDS:
-        raise ValueError(f"kind must be one of {tuple(REWARD_KINDS)}, got {kind!r}")
+    if kind not in DEVICE_KINDS:
+        raise ValueError(f"kind must be one of {DEVICE_KINDS}, got {kind!r}")
     if kind == "cider-d" and not isinstance(table, RewardTable):
         raise ValueError("kind 'cider-d' needs table=RewardTable(corpus)")
     if len(candidates) != len(references):
@@ -483,10 +532,162 @@ def device_scores(candidates, references, kind="cider-d", table=None, end_id=-1,
     n_keys = len(table) if kind == "cider-d" else 0
     if n_keys == 0:
         keys = idf = None
-    ops.backend().caption_reward(fed, T, last, greedy, B, up(refs), up(n_refs), M, Lr, keys, idf, n_keys, params, B, K,
-                                 int(end_id), REWARD_KINDS[kind], 0, adv, score, counted)
+    if kind == ROUGE_KIND:
+        ops.backend().caption_rouge(fed, T, last, greedy, B, up(refs), up(n_refs), M, Lr, B, K, int(end_id), float(beta), 0,
+                                    adv, score, counted)
+    else:
+        ops.backend().caption_reward(fed, T, last, greedy, B, up(refs), up(n_refs), M, Lr, keys, idf, n_keys, params, B, K,
+                                     int(end_id), REWARD_KINDS[kind], 0, adv, score, counted)
     s = score.cpu().numpy()
     return [s[b, :len(doc)].copy() for b, doc in enumerate(cands)]
+
+
+# ---------------------------------------------------------------------------------------------------- caption metrics in fit
+class CaptionValidation:
+    """Caption metrics of the decoded validation set in ``fit``'s epoch logs (``fit(validation_captions=...)`` of nic.NIC and
+    lc_nic.NIC): what ModelCheckpoint(save_best_only=True, mode="max") and EarlyStopping(mode="max") select on in place of
+    the teacher-forced ``val_loss``, which a decoder that learns the language prior and ignores the scan keeps lowering.
+    After an epoch's test_step pass every validation batch is decoded in inference mode with the model's device decode,
+    from column 0 of the batch's caption for its remaining positions; the ids stay on the device and are scored there as
+    the "greedy" candidate of a reward launch whose one sample row is empty (tnt_caption_reward_f32 / tnt_caption_rouge_f32,
+    score[:, 1]); one float64 sum per metric and batch is kept on the device and read at the end of the pass.  The decode
+    takes its start tokens from the host: a batch of numpy arrays adds no synchronise, a batch of device tensors one small
+    read per batch.
+      end_id       the tokenizer's <end> index; a caption or a reference ends at its first end_id or 0
+      metrics      of "bleu4" (log ``val_bleu4``), "rouge-l" (``val_rouge_l``), "cider-d" (``val_cider_d``; needs ``table``,
+                   and is added when a table is given)
+      table        a RewardTable: CIDEr-D's document frequencies
+      references   one list of reference lists per validation batch (at most 8 per scan of at most 64 tokens); None: each
+                   row's own caption, columns 1..
+      decode       "greedy", or "beam" with ``beam_width`` (the best beam of beam_search, whose paths are back-tracked on the
+                   host and sent back)
+      constraints, guidance   model_base.DecodeConstraints / Guidance, handed to the decode
+    Each value is the MEAN OF THE PER-CAPTION SCORES over the validation set (evaluate.sentence_bleu, rouge_l, CiderD per
+    caption); val_bleu4 is therefore not corpus-level BLEU, which pools the n-gram counts of all captions first."""
+
+    METRICS = ("bleu4", "rouge-l", "cider-d")
+    DECODES = ("greedy", "beam")
+
+    def __init__(self, end_id, metrics=("bleu4", "rouge-l"), table=None, references=None, decode="greedy", beam_width=None,
+                 constraints=None, guidance=None):
+        if isinstance(end_id, bool) or not isinstance(end_id, (int, np.integer)) or end_id < 1:
+            raise ValueError(f"CaptionValidation end_id must be an int >= 1 (the <end> index), got {end_id!r}")
+        metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+        for m in metrics:
+            if m not in self.METRICS:
+                raise ValueError(f"CaptionValidation metrics are of {self.METRICS}, got {m!r}")
+        if table is not None and not isinstance(table, RewardTable):
+            raise ValueError(f"table must be None or an evaluate.RewardTable, got {type(table).__name__}")
+        if table is not None and "cider-d" not in metrics:
+            metrics += ("cider-d",)
+        if "cider-d" in metrics and table is None:
+            raise ValueError("metric 'cider-d' needs table=RewardTable(corpus)")
+        if not metrics:
+            raise ValueError("CaptionValidation needs at least one metric")
+        if decode not in self.DECODES:
+            raise ValueError(f"decode must be one of {self.DECODES}, got {decode!r}")
+        if decode == "beam":
+            if isinstance(beam_width, bool) or not isinstance(beam_width, (int, np.integer)) or beam_width < 1:
+                raise ValueError(f"decode='beam' needs beam_width, an int >= 1, got {beam_width!r}")
+        elif beam_width is not None:
+            raise ValueError("beam_width goes with decode='beam'")
+        self.end_id, self.metrics, self.table, self.decode = int(end_id), metrics, table, decode
+        self.beam_width = None if beam_width is None else int(beam_width)
+        self.references = None if references is None else [[[[int(w) for w in r] for r in doc] for doc in batch]
+                                                           for batch in references]
+        self.constraints, self.guidance = constraints, guidance
+        self._bufs, self._refs = {}, {}
+
+    @staticmethod
+    def log_name(metric):
+        return "val_" + metric.replace("-", "_")
+
+    def _decode_ids(self, model, x, a0, c0, start, max_len):
+        """the decoded ids (max_len, ld >= B) int32 on the model's device, column b = scan b"""
+        import torch
+        kw = _con_kw(self.constraints, None, self.guidance)
+        if self.decode == "greedy":
+            return model._mbr_candidate(x, a0, c0, start, max_len, None, **kw)
+        seqs, _ = model.beam_search(x, a0, c0, start, max_len, beam_width=self.beam_width, end_id=self.end_id, **kw)
+        best = np.ascontiguousarray(np.asarray(seqs)[:, 0, :].T.astype(np.int32))
+        return torch.from_numpy(best).to(model.device)
+
+    def _batch_refs(self, model, index, cap, B):
+        """(refs (B, M, Lr) int32, n_refs (B,)) on the device: the batch's reference lists, packed and uploaded once, or the
+        rows' own captions"""
+        import torch
+        dev = model.device
+        if self.references is None:
+            own = cap[:, 1:].contiguous()
+            return own.view(B, 1, own.shape[1]), torch.ones(B, dtype=torch.int32, device=dev)
+        if index not in self._refs:
+            docs = self.references[index]
+            if len(docs) != B:
+                raise ValueError(f"validation batch {index}: {len(docs)} reference lists for {B} scans")
+            M = max(1, max(len(d) for d in docs))
+            Lr = max(1, max((len(r) for d in docs for r in d), default=1))
+            if M > REWARD_MAX_REFS or Lr > REWARD_MAX_LEN:
+                raise ValueError(f"the device scorer holds at most {REWARD_MAX_REFS} references per scan of at most "
+                                 f"{REWARD_MAX_LEN} tokens, got {M} of {Lr}")
+            refs, n = np.zeros((B, M, Lr), np.int32), np.zeros(B, np.int32)
+            pack_references(docs, refs, n)
+            self._refs[index] = (torch.from_numpy(refs).to(dev), torch.from_numpy(n).to(dev))
+        return self._refs[index]
+
+    @staticmethod
+    def check_model(model):
+        """refuse, before any training, a model whose decode does not leave its ids on the device (fit calls this)"""
+        from . import lc_nic, nic
+        cls = type(model)
+        # the device decode is nic.NIC's and lc_nic.NIC's; a subclass with a greedy decode of its own (fc_nic.NICfc) has none
+        if not any(isinstance(model, base) and cls.greedy_predict is base.greedy_predict for base in (nic.NIC, lc_nic.NIC)):
+            raise NotImplementedError(f"fit(validation_captions=...) decodes with the device decode of nic.NIC and lc_nic.NIC: "
+                                      f"{type(model).__name__} has none")
+
+    def epoch_logs(self, model, validation_data, steps):
+        """decode and score ``steps`` validation batches; returns {log name: mean per-caption score}"""
+        import torch
+        from . import ops
+        if self.references is not None and len(self.references) < steps:
+            raise ValueError(f"references holds {len(self.references)} batches for {steps} validation batches")
+        be, dev = ops.backend(), model.device
+        sums, count = {m: [] for m in self.metrics}, 0
+        for index in range(steps):
+            x, cap, a0, c0 = validation_data[index][0][:4]
+            # the start tokens go to the decode from the host: a batch that arrives as numpy keeps them there, a batch of
+            # device tensors costs one small read (and so one synchronise) here
+            start = cap[:, 0].cpu().numpy() if isinstance(cap, torch.Tensor) else np.asarray(cap)[:, 0]
+            cap = model._to_dev(cap, torch.int32)
+            B, L = int(cap.shape[0]), int(cap.shape[1]) - 1
+            if not 1 <= L <= REWARD_MAX_LEN:
+                raise ValueError(f"validation captions of {L + 1} columns: the device scorer holds 1 to {REWARD_MAX_LEN} decoded "
+                                 f"positions behind the start token")
+            ids = self._decode_ids(model, x, a0, c0, start, L)
+            refs, n_refs = self._batch_refs(model, index, cap, B)
+            st = self._bufs.get((B, L))
+            if st is None:
+                z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=dev)
+                # the launch's one sample row per scan stays empty (all zeros): its score is 0 and is not read
+                st = self._bufs[(B, L)] = dict(fed=z(B, L), last=z(B), counted=z(B), adv=z(B, dtype=torch.float32),
+                                               score=z(B, 2, dtype=torch.float64))
+            M, Lr = int(refs.shape[1]), int(refs.shape[2])
+            for m in self.metrics:
+                if m == ROUGE_KIND:
+                    be.caption_rouge(st["fed"], L, st["last"], ids, int(ids.shape[1]), refs, n_refs, M, Lr, B, 1, self.end_id,
+                                     ROUGE_BETA, 0, st["adv"], st["score"], st["counted"])
+                else:
+                    keys = idf = params = None
+                    n_keys = 0
+                    if m == "cider-d":
+                        keys, idf, params = self.table.device(dev)
+                        n_keys = len(self.table)
+                        if n_keys == 0:
+                            keys = idf = None
+                    be.caption_reward(st["fed"], L, st["last"], ids, int(ids.shape[1]), refs, n_refs, M, Lr, keys, idf, n_keys,
+                                      params, B, 1, self.end_id, REWARD_KINDS[m], 0, st["adv"], st["score"], st["counted"])
+                sums[m].append(st["score"][:, 1].sum())
+            count += B
+        return {self.log_name(m): float(torch.stack(v).sum().item()) / max(count, 1) if v else 0.0 for m, v in sums.items()}
 
 
 # ---------------------------------------------------------------------------------------------------- likelihood metrics

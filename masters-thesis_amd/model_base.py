@@ -308,20 +308,21 @@ class SelfCritical:
       n_samples  K sampled captions per scan, 1..16
       baseline   "greedy": the reward of the model's inference-mode greedy caption of the scan; "mean": the mean reward of
                  the scan's other K-1 samples (K >= 2, no decode)
-      reward     "cider-d" (evaluate.CiderD), "bleu4" (evaluate.sentence_bleu, weights (0.25,)*4, method 1) or a callable
-                 (candidate_ids, reference_id_lists) -> float
+      reward     "cider-d" (evaluate.CiderD), "bleu4" (evaluate.sentence_bleu, weights (0.25,)*4, method 1), "rouge-l"
+                 (evaluate.rouge_l at beta 1.2: the reward that credits in-order word matches with gaps; needs no corpus)
+                 or a callable (candidate_ids, reference_id_lists) -> float
       corpus     tokenised reference captions, one list of references per scan: CIDEr-D's document frequencies; None takes
                  them from each batch's references
       score_on   "host": the sampled ids visit the host in the middle of the step and ``reward`` is scored in Python;
-                 "device": one tnt_caption_reward_f32 launch between the rollout and the update scores them (definition:
-                 include/tnt_hip.h), no id and no reward crosses the bus and the host does not wait.  On the device
-                 ``reward`` is "cider-d" or "bleu4", "cider-d" needs ``corpus`` (evaluate.RewardTable holds its document
+                 "device": one tnt_caption_reward_f32 launch (tnt_caption_rouge_f32 for "rouge-l") between the rollout and
+                 the update scores them (definition: include/tnt_hip.h), no id and no reward crosses the bus and the host
+                 does not wait.  On the device ``reward`` is one of the names, "cider-d" needs ``corpus`` (evaluate.RewardTable holds its document
                  frequencies), a step takes at most 8 references per scan of at most 64 tokens, and a reference is cut at
                  its first end_id or 0 like a candidate
     Bad arguments raise ValueError here, before any launch."""
 
     BASELINES = ("greedy", "mean")
-    REWARDS = ("cider-d", "bleu4")
+    REWARDS = ("cider-d", "bleu4", "rouge-l")
     SCORE_ON = ("host", "device")
 
     def __init__(self, end_id, n_samples=1, baseline="greedy", reward="cider-d", corpus=None, score_on="host"):
@@ -385,6 +386,9 @@ class SelfCritical:
         if self.reward == "bleu4":
             from .evaluate import sentence_bleu
             fn = lambda c, refs: sentence_bleu(refs, c, weights=(0.25,) * 4) if refs else 0.0
+        elif self.reward == "rouge-l":
+            from .evaluate import rouge_l
+            fn = lambda c, refs: rouge_l(refs, c)
         else:
             fn = self.reward
         return [np.array([float(fn(c, refs)) for c in cands], np.float64) for cands, refs in zip(candidates, references)]
@@ -3506,7 +3510,7 @@ class ModelBase:
     # ------------------------------------------------------------------ fit loop
     def fit(self, x=None, epochs=1, steps_per_epoch=None, batch_size=None, callbacks=None, validation_data=None,
             validation_steps=None, initial_epoch=0, verbose=1, keras_last_batch_logs=False, validation_averaged=False,
-            class_weight=None, **kw):
+            class_weight=None, validation_captions=None, **kw):
         """model.fit(generator, epochs, steps_per_epoch, batch_size, callbacks, validation_data,
         validation_steps, initial_epoch) -- main.py:269-281.  Honours the keras callback protocol
         (on_train_begin, on_epoch_begin, on_train_batch_end, on_test_batch_end, on_epoch_end,
@@ -3523,7 +3527,21 @@ class ModelBase:
         ``class_weight`` (keras: an ``{id: weight}`` dict; an array of V weights is accepted too): ``set_class_weight`` before
         the first step; None leaves the model's weights as they are.
         Gradient accumulation (optimizer gradient_accumulation_steps=k): ``steps_per_epoch`` counts micro-steps, an update
-        is applied every k-th, and a window left open at the end of an epoch carries over into the next."""
+        is applied every k-th, and a window left open at the end of an epoch carries over into the next.
+        ``validation_captions`` (evaluate.CaptionValidation, whose docstring defines it): behind the test_step pass of an
+        epoch, and inside the same ``validation_averaged`` context, every validation batch is decoded and the captions are
+        scored on the device; the epoch logs (``history``, and what the callbacks see) gain ``val_bleu4`` / ``val_rouge_l`` /
+        ``val_cider_d``, each the mean of the per-caption scores.  One device only.  None: the launches and logs as they are."""
+        if validation_captions is not None:
+            from .evaluate import CaptionValidation
+            if not isinstance(validation_captions, CaptionValidation):
+                raise ValueError(f"validation_captions must be None or an evaluate.CaptionValidation, got "
+                                 f"{validation_captions!r}")
+            if self.dp_world > 1:
+                raise NotImplementedError("fit(validation_captions=...) has no data-parallel schedule: validate on one device")
+            if validation_data is None:
+                raise ValueError("fit(validation_captions=...) needs validation_data")
+            validation_captions.check_model(self)
         if class_weight is not None:
             self.set_class_weight(class_weight)
         if validation_averaged and self.average is None:
@@ -3566,8 +3584,10 @@ class ModelBase:
                             vs[k] = vs.get(k, 0.0) + v
                         vlast = logs
                         _call(callbacks, "on_test_batch_end", b, logs)
+                    vcap = validation_captions.epoch_logs(self, validation_data, nv) if validation_captions is not None else {}
                 elogs.update({f"val_{k}": v for k, v in vlast.items()} if keras_last_batch_logs else
                              {f"val_{k}": v / max(nv, 1) for k, v in vs.items()})
+                elogs.update(vcap)
             if self.dp_world > 1:
                 elogs = self._dp_mean_logs(elogs)
             if verbose:

@@ -22,7 +22,7 @@ from .arena import ParamArena
 from .model_base import (ModelBase, Metrics, _r4, S_IN, S_FEAT, S_LSTM_IN, BN_EPS, BN_MOMENTUM, S_SS_COIN, S_SS_DRAW,
                          SS_MAX_POSITIONS, S_SCST_LAST, ScheduledSampling, SelfCritical, SemanticTarget, check_sampling, check_beam,
                          _TokenChoice, _BeamDecode, EncGram, EncUpdate, StepRoute)
-from .evaluate import REWARD_KINDS, REWARD_MAX_LEN, REWARD_MAX_REFS, pack_references
+from .evaluate import REWARD_KINDS, REWARD_MAX_LEN, REWARD_MAX_REFS, ROUGE_BETA, ROUGE_KIND, pack_references
 from .lstm_layer import lstm_layer_step_fwd, lstm_layer_fwd, lstm_layer_bwd
 from .ops import ACT_LEAKY, LIVE_ROWS_M, LIVE_ROWS_K, contrastive_work_floats
 
@@ -78,7 +78,7 @@ class NIC(ModelBase):
                                  f"(tnt_scheduled_feedback_f32), got {E}")
             if self_critical.end_id >= V:
                 raise ValueError(f"self-critical end_id {self_critical.end_id} is not below vocab_size {V}")
-            if self_critical.score_on == "device" and V > 65536:
+            if self_critical.score_on == "device" and self_critical.reward != ROUGE_KIND and V > 65536:
                 raise ValueError(f"self-critical score_on='device' packs 16 bits per token id (evaluate.RewardTable): "
                                  f"vocab_size {V} is above 65536")
         self.self_critical = self_critical
@@ -967,9 +967,16 @@ class NIC(ModelBase):
 
     def _scst_reward(self, R, T):
         """score_on="device": the rewards of the R sampled captions (and the greedy captions) against the staged references
-        and the advantages into st["adv"], one tnt_caption_reward_f32 launch on buffers that are static per (B, T)"""
+        and the advantages into st["adv"], one tnt_caption_reward_f32 launch on buffers that are static per (B, T); reward
+        "rouge-l": one tnt_caption_rouge_f32 launch in its place, on the same buffers"""
         sc, st = self.self_critical, self._scst
         B = R // sc.n_samples
+        if sc.reward == ROUGE_KIND:
+            g = sc.baseline == "greedy"
+            self.be.caption_rouge(self.cap, T, st["last"], st["greedy"] if g else None, B, st["refs"], st["n_refs"],
+                                  REWARD_MAX_REFS, REWARD_MAX_LEN, B, sc.n_samples, sc.end_id, ROUGE_BETA, 0 if g else 1,
+                                  st["adv"], st["score"], st["counted"])
+            return
         keys = idf = params = None
         n_keys = 0
         if sc.table is not None:

@@ -70,6 +70,10 @@ class HipBackend:
         if not torch.cuda.is_available():
             raise _lib.KernelLibraryError("no GPU visible: the HIP backend needs an MI355X (there is no CPU fallback)")
         self.gemm3_plan_pair = lambda p1, p2: gemm3_plan_pair(self.lib, p1, p2)       # host-side query, not a launch
+        # float64 scalars that an entry reads through a host pointer (tnt_weight_average_f32's momentum,
+        # tnt_caption_rouge_f32's beta): one per distinct value, alive as long as the backend, because recorded launch
+        # plans re-issue the call with the address
+        self._f64 = {}
 
     _rec = None     # while a launch plan is being recorded: list of (c function, name, argument tuple)
 
@@ -947,6 +951,24 @@ class HipBackend:
                    _p(refs), _p(n_refs), int(M), int(Lr), _p(keys), _p(idf), int(n_keys), _p(params), int(B), int(K),
                    int(end_id), int(kind), int(baseline), _p(adv), _p(score), _p(counted), self._s())
 
+    def _host_f64(self, value):
+        """the kept c_double that holds ``value`` (self._f64); every NaN shares one entry, since a NaN key never matches"""
+        value = float(value)
+        key = value if value == value else "nan"
+        return self._f64.setdefault(key, _ct.c_double(value))
+
+    def caption_rouge(self, fed, T, last, greedy, ldg, refs, n_refs, M, Lr, B, K, end_id, beta, baseline, adv, score=None,
+                      counted=None, lcs=None):
+        """ROUGE-L on the device, in caption_reward's layout: the F-score (pycocoevalcap's, ``beta`` 1.2 there) of the longest
+        common subsequences of the K sampled captions of each of the B scans and of its greedy caption (baseline 0; 1: the
+        mean of the scan's other samples) with refs [B][M][Lr], the advantages adv [B*K], the scores [B][K+1] float64, the
+        counted positions [B*K] and the LCS lengths [B][K+1][M] (tnt_caption_rouge_f32; definition in include/tnt_hip.h);
+        greedy, score and lcs are nullable"""
+        bt = self._host_f64(beta)
+        self._call(self.lib.tnt_caption_rouge_f32, "tnt_caption_rouge_f32", _p(fed), int(T), _p(last), _p(greedy), int(ldg),
+                   _p(refs), _p(n_refs), int(M), int(Lr), int(B), int(K), int(end_id), _ct.addressof(bt), int(baseline), _p(adv),
+                   _p(score), _p(counted), _p(lcs), self._s())
+
     def step_tick(self, adam_t, drop_step, lr, lr_t, beta1, beta2, guard=None):
         self._call(self.lib.tnt_step_tick, "tnt_step_tick", _p(adam_t), _p(drop_step), _p(lr), _p(lr_t), beta1, beta2, _p(guard),
                    self._s())
@@ -954,10 +976,7 @@ class HipBackend:
     def weight_average(self, theta, avg, n, step, kind, momentum, dynamic, start_step, every, guard=None):
         """one averaging launch over n parameters (tnt_weight_average_f32; definition in include/tnt_hip.h): copy, skip
         or blend decided on the device from ``step`` (the updates applied so far) and ``guard``; kind 0 EMA, 1 SWA"""
-        # the entry reads momentum through a host pointer; one float64 per distinct value, alive as long as the backend
-        # (recorded launch plans re-issue the call)
-        keep = self.__dict__.setdefault("_f64", {})
-        mom = keep.setdefault(float(momentum), _ct.c_double(float(momentum)))
+        mom = self._host_f64(momentum)
         self._call(self.lib.tnt_weight_average_f32, "tnt_weight_average_f32", _p(theta), _p(avg), int(n), _p(step), int(kind),
                    _ct.addressof(mom), int(bool(dynamic)), int(start_step), int(every), _p(guard), self._s())
 
