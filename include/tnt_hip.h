@@ -1851,6 +1851,59 @@ int32_t tnt_contrastive_loss_f32(const float* z, int32_t ldz, const float* g, in
                                  int32_t B, int32_t G, float inv_temperature, float soft_inv_temperature /* 0: hard */,
                                  int32_t symmetric, float weight, void* stream);
 
+/* ---- symmetric positive-definite solves for ridge decoding (csrc/cholesky.hip; masters_thesis_amd/ridge.py).  The baseline of
+ * every fMRI decoding paper -- ridge regression from the voxels to the sentence embedding -- in its dual form needs, for the
+ * n x n Gram matrix K of the scans, (K + alpha I) A = Y per regularisation strength.  Everything is float32 in memory; the
+ * 64 x 64 triangular work is done in float64 in LDS and rounded once.  No workgroup waits for another inside a launch (launch
+ * boundaries are the only synchronisation: no spin, no flag), no float atomics, every sum in a fixed order: the same input
+ * gives the same bits.  The products run on this library's own family, called inside the library: tnt_gemm3_f32 at the tile
+ * tnt_gemm3_plan picks with allow_split = 0 (no exchange buffer, no sync word), or tnt_gemm_f32 (splitk 1) where gemm3's
+ * 32-bit operand offsets do not reach (n * ld >= 2^29 floats); the choice depends on the sizes alone.
+ *
+ * tnt_cholesky_f32: the lower factor of K + shift I,  L L^T = K + shift I.
+ *   K [n][ldk] symmetric; only its lower triangle (diagonal included) is read and it is never written, so one Gram matrix
+ *   serves every shift.  L [n][ldl] is another buffer; only its lower triangle (diagonal included) is written; its strictly
+ *   upper triangle and its pad columns [n, ldl) are neither read nor written by the kernels of this file (a product may fetch
+ *   such floats beside an M-contiguous operand; they only reach rows of its result that are not stored).
+ *   Blocked left-looking at NB = 64.  For block column j (j0 = 64 j, nb = min(64, n - j0)), in stream order:
+ *     (j > 0) one product  P = L[j0:, :j0] L[j0:j0+nb, :j0]^T  into work, [n - j0][64].  Both operands are K-contiguous with
+ *       K = j0, a multiple of 64, so no stage of gemm3 reaches past K: its "finite behind K" contract holds by construction.
+ *     one panel launch of ceil((n - j0) / 64) workgroups.  Each factors D = K[j0:j0+nb, j0:j0+nb] + shift I - P[:nb] itself in
+ *       float64 (right-looking inside the block, a_ij -= a_ik a_jk / a_kk, L_ik = a_ik / sqrt(a_kk)), rounds it to float32
+ *       once, and then workgroup 0 stores L11 while workgroup b >= 1 solves rows [j0 + 64 b, j0 + 64 b + 64) of
+ *       L21 = (K21 - P21) L11^-T against the rounded L11 in float64 and stores them rounded once.
+ *   work: 64 * n floats (n - 64 rows suffice).  status: one int32 in device memory, set to 0 by the call (a memset node on
+ *   the stream).  A pivot a_kk that is not finite, is <= 0, or whose square root is not a positive finite float32 sets
+ *   status = 1 + its row index; all workgroups of a panel find the same pivot, the first in row order, and one of them files
+ *   it.  A panel or triangular launch that finds status != 0 returns before it touches anything else; the products of the
+ *   remaining block columns still run, over whatever L holds, into work alone.  A matrix that is not positive definite, or
+ *   one with a NaN, therefore cannot fault and costs idle launches; L is then unspecified.
+ *   TNT_BADARG, nothing launched: K null or not 16-byte aligned (1), ldk < n or not a multiple of 4 (2), L null, unaligned or
+ *   K itself (3), ldl likewise (4), n outside [1, 32768] (5), work null or unaligned (7), status null (8).
+ *
+ * tnt_cholesky_solve_f32: X <- L^-T L^-1 X in place, the solution of (L L^T) A = X.  X [n][ldx], G >= 1 columns used.
+ *   Forward sweep, block rows ascending:  (j > 0) P = L[j0:j0+nb, :j0] X[:j0] into work [64][ldx], then one launch of
+ *   ceil(G / 64) workgroups: X_j <- L_jj^-1 (X_j - P).  Backward sweep, descending: (rows below) P = L[j0+64:, j0:j0+64]^T
+ *   X[j0+64:], then X_j <- L_jj^-T (X_j - P).  The triangular launches hold 64 columns of X_j in float64 in LDS and round once.
+ *   Only the lower triangle of L is read.  The forward product's A has K = j0, a multiple of 64; the backward product has no
+ *   K-contiguous operand.  If *status != 0 on entry every triangular launch returns untouched and X keeps its bits.
+ *   work: 64 * ldx floats.  TNT_BADARG: L null / unaligned (1), ldl < n or not a multiple of 4 (2), n outside [1, 32768] (3),
+ *   X null / unaligned (4), ldx < G or not a multiple of 4 (5), G < 1 (6), work null / unaligned (7), status null (8).
+ *
+ * tnt_gram_center_f32: K <- H K H in place, H = I - 11^T / n, for a symmetric K [n][ldk] (both triangles held), so that the
+ *   n x N scans are never copied or centred themselves.  mean: n + 1 floats, kept for the caller (the centred cross-Gram of
+ *   new rows needs the training means): mean[i] = (sum_j K_ij) / n, mean[n] = (sum_i mean[i]) / n.  Two launches: one wave per
+ *   row for the means (lane l adds the float4 l, l + 64, ... in float64, then the butterfly); then 16 rows per workgroup,
+ *   every workgroup forming the grand mean itself from mean[0..n) in float64 in one fixed order (thread t adds t, t + 256, ...,
+ *   then a binary tree), and K_ij <- (float)((double)K_ij - mean[i] - mean[j] + grand).  tnt_colsum_f32 is not used for the
+ *   first half: it adds in float32 over row chunks through a work buffer, and the means here are taken in float64.
+ *   TNT_BADARG: K null / unaligned (1), ldk < n or not a multiple of 4 (2), n outside [1, 32768] (3), mean null (4). */
+int32_t tnt_cholesky_f32(const float* K, int32_t ldk, float* L, int32_t ldl, int32_t n, float shift, float* work,
+                         int32_t* status, void* stream);
+int32_t tnt_cholesky_solve_f32(const float* L, int32_t ldl, int32_t n, float* X, int32_t ldx, int32_t G, float* work,
+                               const int32_t* status, void* stream);
+int32_t tnt_gram_center_f32(float* K, int32_t ldk, int32_t n, float* mean, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

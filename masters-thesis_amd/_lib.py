@@ -18,7 +18,7 @@ P = C.c_void_p          # any device pointer
 I32, I64, U32, U64, F32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 # the tnt_version() this table was written against (csrc/rowops.hip); the two move together
-TNT_VERSION = 137
+TNT_VERSION = 138
 
 # name -> argtypes (restype is always int32); order mirrors include/tnt_hip.h
 SIGNATURES = {
@@ -201,6 +201,9 @@ SIGNATURES = {
     "tnt_row_inv_norm_f32": [P, I64, P, I64, I32, P],
     "tnt_cosine_topk_f32": [P, I64, P, P, P, P, I32, I32, I32, P],
     "tnt_contrastive_loss_f32": [P, I32, P, I32, P, P, P, P, P, I32, I32, F32, F32, I32, F32, P],
+    "tnt_cholesky_f32": [P, I32, P, I32, I32, F32, P, P, P],
+    "tnt_cholesky_solve_f32": [P, I32, I32, P, I32, I32, P, P, P],
+    "tnt_gram_center_f32": [P, I32, I32, P, P],
 }
 
 _lib = None

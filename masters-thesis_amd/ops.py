@@ -1079,6 +1079,33 @@ class HipBackend:
                    _p(work), _p(loss_row), _p(hit_row), _p(out), int(B), int(G), float(inv_temperature),
                    float(soft_inv_temperature), int(bool(symmetric)), float(weight), self._s())
 
+    def cholesky(self, K, ldk, L, ldl, n, shift, work, status):
+        """the lower factor of K + shift I into L (tnt_cholesky_f32; definition in include/tnt_hip.h): only K's lower triangle
+        is read, only L's is written; work cholesky_work_floats(n) floats; status one int32 word, zeroed by the call, 1 + the
+        row of the first bad pivot afterwards"""
+        self._call(self.lib.tnt_cholesky_f32, "tnt_cholesky_f32", _p(K), int(ldk), _p(L), int(ldl), int(n), float(shift),
+                   _p(work), _p(status), self._s())
+
+    def cholesky_solve(self, L, ldl, n, X, ldx, G, work, status):
+        """X <- (L L^T)^-1 X in place (tnt_cholesky_solve_f32); work cholesky_solve_work_floats(ldx) floats; a nonzero status
+        word leaves X untouched"""
+        self._call(self.lib.tnt_cholesky_solve_f32, "tnt_cholesky_solve_f32", _p(L), int(ldl), int(n), _p(X), int(ldx), int(G),
+                   _p(work), _p(status), self._s())
+
+    def gram_center(self, K, ldk, n, mean):
+        """K <- H K H in place, H = I - 11^T / n (tnt_gram_center_f32); mean: n + 1 floats, the row means and the grand mean"""
+        self._call(self.lib.tnt_gram_center_f32, "tnt_gram_center_f32", _p(K), int(ldk), int(n), _p(mean), self._s())
+
+
+def cholesky_work_floats(n):
+    """floats of ``work`` of tnt_cholesky_f32 (the formula of include/tnt_hip.h): the 64 columns of one block step's product"""
+    return 64 * n
+
+
+def cholesky_solve_work_floats(ldx):
+    """floats of ``work`` of tnt_cholesky_solve_f32: the 64 rows of one block step's product"""
+    return 64 * ldx
+
 
 def contrastive_work_floats(B, soft):
     """floats of ``work`` of tnt_contrastive_loss_f32 (TNT_CONTRASTIVE_WORK_FLOATS of include/tnt_hip.h): the squared norms and
