@@ -1904,6 +1904,53 @@ int32_t tnt_cholesky_solve_f32(const float* L, int32_t ldl, int32_t n, float* X,
                                const int32_t* status, void* stream);
 int32_t tnt_gram_center_f32(float* K, int32_t ldk, int32_t n, float* mean, void* stream);
 
+/* ---- symmetric eigensolver of order <= 128 for PCA of the scans (csrc/eigen.hip; masters_thesis_amd/pca.py).  Block subspace
+ * iteration on the n x n Gram matrix of the scans needs two small dense decompositions per iteration: the eigenvectors of the
+ * m x m Ritz matrix and the matrix that orthonormalises a block of m columns from their Gram matrix.  Both are ONE launch of ONE
+ * workgroup (16 waves) of the same kernel, with the matrix and the eigenvectors held in LDS in float32 (two 128 x 129 float
+ * arrays, 132 KB of the CU's 160 KB, as dynamic LDS).  No atomics, every sum and every rotation in a fixed order: the same
+ * input gives the same bits.
+ *
+ * tnt_syev_jacobi_f32: all eigenvalues and eigenvectors of the symmetric float32 matrix A [m][lda], 1 <= m <= 128.
+ *   Only A's lower triangle (diagonal included) is read; it is mirrored on load; A is never written.
+ *   Cyclic Jacobi in the round-robin ordering of the circle method over n2 = m rounded up to even, n1 = n2 - 1: round r
+ *   (0 <= r < n1) holds the pairs {r, n1} (slot 0) and {(r + k) mod n1, (r - k) mod n1} for slots k = 1 .. n2 / 2 - 1, each
+ *   ordered p < q.  For odd m index n1 = m is the bye and slot 0 is left out: a round has floor(m / 2) disjoint pairs for
+ *   every m, and a sweep has m - 1 rounds for even m and m rounds for odd m (m (m - 1) / 2 pairs either way).
+ *   Pair (p, q) of a round is rotated iff  |a_qp| > 2^-24 sqrt(|a_pp a_qq|)  and  |a_qp| > 2^-24 ||A||_F / sqrt(m),  both
+ *   evaluated in float64 on the float32 entries the round starts with; ||A||_F is taken once at load in float64 (each row
+ *   left to right, then the rows top to bottom).  For a rotated pair, in float64:  th = (a_qq - a_pp) / (2 a_qp),
+ *   t = sign(th) / (|th| + sqrt(1 + th^2)) (sign(0) = +1), c = 1 / sqrt(1 + t^2), s = t c, rounded once to float32, and the
+ *   new diagonal pair a_pp - t a_qp, a_qq + t a_qp, rounded once.  Then A <- J^T A J and V <- V J, J = [c s; -s c] on (p, q), in
+ *   float32:  x' = fma(c, x, -(s y)),  y' = fma(s, x, c y);  the 2 x 2 block itself is set to the new diagonal pair and two
+ *   exact zeros.  Both triangles of A are kept; decisions read the lower one.
+ *   The kernel stops after the first sweep in which no pair rotated (info[0] = 0) or after max_sweeps sweeps (info[0] = 1; w
+ *   and V are written and are what the last sweep left).
+ *   w [m]: the diagonal in descending order, ties in ascending order of the column they came from.  V [m][ldv]: column i is
+ *   the eigenvector of w[i] as the float32 rotations left it (unit to rounding), negated where needed so that its entry of
+ *   largest magnitude -- the first one on ties -- is positive.  Columns [m, ldv) of V are not written.
+ *   info: three int32 words in device memory.  info[0]: 0 converged; 1 not converged within max_sweeps; 2 a non-finite entry in
+ *   the lower triangle, w and V untouched.  info[1]: sweeps run (the last, rotation-free one included).  info[2]: m.
+ *   TNT_BADARG, nothing launched: A null or not 16-byte aligned (1), lda < m or not a multiple of 4 (2), m outside [1, 128] (3),
+ *   w null or not 4-byte aligned (4), V null or not 16-byte aligned (5), ldv < m or not a multiple of 4 (6), max_sweeps outside
+ *   [1, 64] (7), info null or not 4-byte aligned (8), V == A (9); the dynamic LDS refused by the device (90).
+ *
+ * tnt_gram_whiten_f32: M [m][ldm] with (Z M)^T (Z M) = I from the Gram matrix S = Z^T Z [m][lds] of a block of m columns
+ *   (lower triangle read).  d_j = S_jj; r_j = 1 / sqrt(d_j) in float64 where d_j is finite and > 0, else 0 (a zero column is
+ *   dropped); C = diag(r) S diag(r) formed in float64 and rounded once; (w, W) = the eigen-decomposition of C exactly as above
+ *   (max_sweeps 64, the sort and the sign rule included);  M = diag(r) W diag(1 / sqrt(max(w_i, tau w_0))), a column whose
+ *   max(w_i, tau w_0) is not > 0 set to zero, formed in float64 and rounded once.  w [m]: the eigenvalues of C.  info[0] and
+ *   info[1] as above; info[2]: the number of w_i > tau w_0, the numerical rank (0 with info[0] = 2).  Where the rank is full Z M
+ *   has orthonormal columns; where it is not, its columns have norm <= 1 and span the same space, and nothing is NaN.  The
+ *   scaling to unit diagonal makes C well conditioned for nearly orthogonal columns however they are graded.
+ *   TNT_BADARG: S null / unaligned (1), lds < m or not a multiple of 4 (2), m outside [1, 128] (3), M null / unaligned (4),
+ *   ldm < m or not a multiple of 4 (5), tau not in (0, 1) (6), w null / not 4-byte aligned (7), info likewise (8), M == S (9);
+ *   (90) as above. */
+int32_t tnt_syev_jacobi_f32(const float* A, int32_t lda, int32_t m, float* w, float* V, int32_t ldv, int32_t max_sweeps,
+                            int32_t* info, void* stream);
+int32_t tnt_gram_whiten_f32(const float* S, int32_t lds, int32_t m, float* M, int32_t ldm, float tau, float* w, int32_t* info,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,8 @@ SIGNATURES = {
     "tnt_cholesky_f32": [P, I32, P, I32, I32, F32, P, P, P],
     "tnt_cholesky_solve_f32": [P, I32, I32, P, I32, I32, P, P, P],
     "tnt_gram_center_f32": [P, I32, I32, P, P],
+    "tnt_syev_jacobi_f32": [P, I32, I32, P, P, I32, I32, P, P],
+    "tnt_gram_whiten_f32": [P, I32, I32, P, I32, F32, P, P, P],
 }
 
 _lib = None

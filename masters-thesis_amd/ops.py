@@ -1096,6 +1096,19 @@ class HipBackend:
         """K <- H K H in place, H = I - 11^T / n (tnt_gram_center_f32); mean: n + 1 floats, the row means and the grand mean"""
         self._call(self.lib.tnt_gram_center_f32, "tnt_gram_center_f32", _p(K), int(ldk), int(n), _p(mean), self._s())
 
+    def syev_jacobi(self, A, lda, m, w, V, ldv, info, max_sweeps=64):
+        """all eigenvalues (w, descending) and eigenvectors (the columns of V) of the symmetric matrix whose lower triangle A
+        holds, m <= 128, by one workgroup's cyclic Jacobi (tnt_syev_jacobi_f32; definition in include/tnt_hip.h); info: three
+        int32 words -- 0 / 1 (not converged) / 2 (non-finite input, w and V untouched), sweeps run, m"""
+        self._call(self.lib.tnt_syev_jacobi_f32, "tnt_syev_jacobi_f32", _p(A), int(lda), int(m), _p(w), _p(V), int(ldv),
+                   int(max_sweeps), _p(info), self._s())
+
+    def gram_whiten(self, S, lds, m, M, ldm, tau, w, info):
+        """M with (Z M)^T (Z M) = I from the lower triangle of S = Z^T Z (tnt_gram_whiten_f32); w: the eigenvalues of S scaled
+        to unit diagonal; info as syev_jacobi, info[2] the number of w_i > tau w_0"""
+        self._call(self.lib.tnt_gram_whiten_f32, "tnt_gram_whiten_f32", _p(S), int(lds), int(m), _p(M), int(ldm), float(tau),
+                   _p(w), _p(info), self._s())
+
 
 def cholesky_work_floats(n):
     """floats of ``work`` of tnt_cholesky_f32 (the formula of include/tnt_hip.h): the 64 columns of one block step's product"""
